@@ -71,7 +71,7 @@ def committed_traffic(root=ROOT, res=512, dtype="fp16"):
     return round(rec["traffic_bytes_per_launch"]), name, "offline PMC (separate FETCH_SIZE / WRITE_SIZE passes) on these sources"
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -93,7 +93,28 @@ def parse():
                     help="--gpus N launcher: seconds after which still-running ranks are killed and the job returns 124 (0 = no limit)")
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="print the per-rank environment / command the N-rank launcher would start (one JSON line) and exit")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32 (inputs are seeded, so two builds compare output for output);
+    returns {name: shape}.  The arrays here are the latents of one step: far below the 64 MB bound."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
+        assert a.nbytes <= 64 << 20, f"{name}: {a.nbytes} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def rank_environments(n, port, base=None):
@@ -412,6 +433,11 @@ def main():
     elapsed_by_rank = per_rank(elapsed)
     elapsed = max_over_ranks(elapsed)
     assert torch.isfinite(state["x"]).all(), "latents diverged"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # guided_step's return value of the last timed step: the latents [1, H/8, W/8, 4], f32 channels-last (copied now, before
+        # the profiled steps below advance the state)
+        dumped = dump_outputs(args.dump_outputs, {"latents": state["x"]})
 
     # ---- roofline of the dominant kernel (k_gemm_dma: MFMA implicit GEMM), HIP events on its stream ------------------------
     import ctypes
@@ -682,6 +708,8 @@ def main():
             "roofline": roof, "hbm_kernels": hbm, "cpu_baseline": cpu, "phases": phases, "batched_edits": batch_info,
             "edits": edits_info, "res768_bf16": res768,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "shapes": dumped}
         sys.stdout.flush()
         rc = sections.finish(out, json_fd)
     else:

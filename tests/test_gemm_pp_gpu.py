@@ -6,7 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_unet_kernels_gpu import DT, L, P, close, dev, run_gemm
+from test_unet_kernels_gpu import DT, L, P, close, dev, poisoned, run_gemm
 
 pytestmark = pytest.mark.gpu
 
@@ -133,7 +133,7 @@ def test_pp_geglu_epilogues(family, dtype, M, Fd, K):
         ys = {}
         for fam in (0, 1):
             family(fam)
-            y = torch.empty(M, Fd, dtype=dtype, device=dev())
+            y = poisoned((M, Fd), dtype)
             L().check(L().lib().dh_dbg_gemm_glu(DT[dtype], 0, P(A), K, P(W), M, 2 * Fd, K, P(None), P(None), P(y), P(None), P(None),
                                                 L().stream_ptr()), "dh_dbg_gemm_glu")
             ys[fam] = y
@@ -182,8 +182,8 @@ def test_pp_persistent_workgroups_walk_several_tiles(family, dtype):
         res = []
         for persist in (0, 1):
             lib.dh_dbg_gemm_pp_persist(persist)
-            pre = torch.empty(M, 2 * Fd, dtype=dtype, device=dev())
-            y = torch.empty(M, Fd, dtype=dtype, device=dev())
+            pre = poisoned((M, 2 * Fd), dtype)
+            y = poisoned((M, Fd), dtype)
             L().check(lib.dh_dbg_gemm_glu(DT[dtype], 0, P(A), K, P(W), M, 2 * Fd, K, P(None), P(pre), P(y), P(None), P(None), L().stream_ptr()),
                       "dh_dbg_gemm_glu")
             res.append((pre, y))

@@ -2,6 +2,8 @@
 fp32 references of the same op.  Tolerances are fp16/bf16-storage tolerances: the kernels
 read 16-bit inputs, accumulate in f32 and round the output once."""
 import ctypes
+import os
+import sys
 
 import pytest
 import torch
@@ -26,22 +28,61 @@ def P(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+# Hard ceiling on any single element, in units of its tolerance atol + rtol |ref|.  The 1e-4 fraction of elements allowed
+# over tolerance is there for 16-bit rounding of near-ties and of the odd large product; none of that puts an element several
+# tolerances off, while a wrong tail row or a stray column does.  Measured on the MI355X (DH_CLOSE_RATIOS=<file> logs the worst
+# ratio of every call): 2.05 at most, the attention dq of test_attention_forward_backward at fp16, B = 2, H = 5, Nq = 1024,
+# Nk = 77; every other site of this file, tests/test_gemm_pp_gpu.py and tests/test_kernel_strides_gpu.py stays at 1.3 or
+# below, the GEMM / conv / norm sites below 0.3.  8 is about four times the worst measured ratio.
+CLOSE_CEILING = 8.0
+
+
 def close(got, ref, rtol, atol, what=""):
-    err = (got.float() - ref.float()).abs()
-    tol = atol + rtol * ref.float().abs()
-    bad = (err > tol).float().mean().item()
-    assert bad < 1e-4, f"{what}: max err {err.max().item():.4g}, frac bad {bad:.3g}, ref max {ref.abs().max().item():.3g}"
+    """got ~ ref: same shape; finite wherever ref is; at most 1e-4 of the elements over atol + rtol |ref|, none over
+    CLOSE_CEILING times that.  The message names the worst element (flat index and coordinates)."""
+    assert tuple(got.shape) == tuple(ref.shape), f"{what}: shape {tuple(got.shape)} != reference {tuple(ref.shape)}"
+    g, r = got.float(), ref.float()
+    rfin = torch.isfinite(r)
+    nonfin = (~torch.isfinite(g) & rfin) | (~rfin & ~((g == r) | (torch.isnan(g) & torch.isnan(r))))
+    tol = atol + rtol * r.abs()
+    ratio = torch.where(nonfin, torch.full_like(r, float("inf")), ((g - r).abs() / tol).nan_to_num(0.0))
+    worst = int(ratio.argmax())
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), ratio.shape)) if ratio.dim() else ()
+    wr = ratio.reshape(-1)[worst].item()
+    log = os.environ.get("DH_CLOSE_RATIOS")
+    if log:
+        caller = sys._getframe(1)
+        with open(log, "a") as f:
+            f.write(f"{os.path.basename(caller.f_code.co_filename)}:{caller.f_lineno}\t{what}\t{wr:.4g}\n")
+    n_nonfin = int(nonfin.sum())
+    bad = (ratio > 1.0).float().mean().item()
+    msg = (f"{what}: worst element {idx} got {g.reshape(-1)[worst].item():.6g} ref {r.reshape(-1)[worst].item():.6g} "
+           f"({wr:.3g} x tolerance), non-finite {n_nonfin}, frac bad {bad:.3g}, ref max {r.abs().max().item():.3g}")
+    assert n_nonfin == 0, msg
+    assert wr <= CLOSE_CEILING, msg
+    assert bad < 1e-4, msg
+
+
+def poisoned(shape, dtype):
+    """An output buffer for a kernel under test, filled with NaN (integers: -1) so that an element the kernel never writes
+    fails close() instead of passing on whatever the allocator left there."""
+    if dtype.is_floating_point:
+        return torch.full(shape, float("nan"), dtype=dtype, device=dev())
+    return torch.full(shape, -1, dtype=dtype, device=dev())
 
 
 def run_gemm(dtype, A, lda, W, M, N, K, mode=0, geo=(0, 0, 0, 0, 0, 1, 0), bias=None, rowvec=None, rpb=1, R=None, silu=0,
-             split=True):
+             split=True, C=None, ldc=None, ldr=None):
+    """dh_dbg_gemm.  C = None: a fresh NaN-filled [M][N] output; else C is written in place with row pitch ldc (R may alias it).
+    The split-K slab is NaN-filled too: every slab element the reduce reads must have been written by the K loop first."""
     lib = L().lib()
-    C = torch.empty((M, N), dtype=dtype, device=dev())
-    part = torch.empty(16 << 20, dtype=torch.float32, device=dev()) if split else None
+    if C is None:
+        C, ldc = poisoned((M, N), dtype), N
+    part = poisoned((16 << 20,), torch.float32) if split else None
     Hin, Win, Cin, Hout, Wout, stride, up = geo
     rc = lib.dh_dbg_gemm(DT[dtype], P(A), lda, P(W), M, N, K, mode, Hin, Win, Cin, Hout, Wout, stride, up, P(bias),
-                         P(rowvec), rowvec.shape[1] if rowvec is not None else 0, rpb, P(R), N, P(C), N, silu, P(part),
-                         part.numel() if part is not None else 0, L().stream_ptr())
+                         P(rowvec), rowvec.shape[1] if rowvec is not None else 0, rpb, P(R), N if ldr is None else ldr, P(C), ldc,
+                         silu, P(part), part.numel() if part is not None else 0, L().stream_ptr())
     L().check(rc, "dh_dbg_gemm")
     return C
 
@@ -89,8 +130,8 @@ def test_gemm_layernorm_fold(dtype, M, N, K, mean_over_std):
     s = Wf.float().sum(dim=1).contiguous()
     t = (W0.float() @ beta + bias).contiguous()
     ref = F.layer_norm(x.float(), (K,), gamma, beta, 1e-5) @ W0.float().t() + bias
-    C = torch.empty(M, N, dtype=dtype, device=dev())
-    stats = torch.empty(M, 2, dtype=torch.float32, device=dev())
+    C = poisoned((M, N), dtype)
+    stats = poisoned((M, 2), torch.float32)
     lib = L().lib()
     L().check(lib.dh_dbg_gemm_lnfold(DT[dtype], P(x), K, P(Wf.contiguous()), M, N, K, P(s), P(t), P(stats), 1e-5, P(C), N,
                                      L().stream_ptr()), "dh_dbg_gemm_lnfold")
@@ -135,7 +176,7 @@ def test_conv3_forward_and_input_gradient(dtype, B, Cin, Cout, H, stride, up):
     wb = w.flip(2, 3).permute(1, 2, 3, 0).reshape(Cin, 9 * Cout).contiguous()           # [Cin][tap'][Cout]
     if up:
         hi = run_gemm(dtype, nhwc(dy), Cout, wb, B * Ho * Ho, Cin, 9 * Cout, mode=1, geo=(Ho, Ho, Cout, Ho, Ho, 1, 0))
-        dx = torch.empty((B, H, H, Cin), dtype=dtype, device=dev())
+        dx = poisoned((B, H, H, Cin), dtype)
         L().check(L().lib().dh_dbg_pool2x2(DT[dtype], P(hi), P(dx), B, H, H, Cin, 0, L().stream_ptr()))
     elif stride == 2:
         dx = run_gemm(dtype, nhwc(dy), Cout, wb, B * H * H, Cin, 9 * Cout, mode=2, geo=(Ho, Ho, Cout, H, H, 1, 0)).view(B, H, H, Cin)
@@ -159,8 +200,8 @@ def test_groupnorm(dtype, B, HW, C, silu):
     if silu:
         ref = F.silu(ref)
     gref, = torch.autograd.grad(ref, xr, dy.float())
-    y = torch.empty_like(x); dx = acc0.clone()
-    stats = torch.empty(B * 32 * 2, dtype=torch.float32, device=dev()); scr = torch.empty(B * 32 * 32 * 3 + 64, dtype=torch.float32, device=dev())
+    y = poisoned(x.shape, dtype); dx = acc0.clone()          # dx accumulates onto acc0 by design
+    stats = poisoned((B * 32 * 2,), torch.float32); scr = torch.empty(B * 32 * 32 * 3 + 64, dtype=torch.float32, device=dev())
     L().check(L().lib().dh_dbg_groupnorm(DT[dtype], P(x), P(gamma), P(beta), P(y), P(stats), P(dy), P(dx), P(scr), B, HW, C, 32,
                                          1e-5, silu, 1, L().stream_ptr()))
     tol = 4e-3 if dtype == torch.float16 else 2.5e-2
@@ -178,7 +219,7 @@ def test_layernorm(dtype, rows, C):
     xr = x.float().requires_grad_(True)
     ref = F.layer_norm(xr, (C,), gamma, beta, 1e-5)
     gref, = torch.autograd.grad(ref, xr, dy.float())
-    y = torch.empty_like(x); dx = torch.empty_like(x); stats = torch.empty(rows * 2, dtype=torch.float32, device=dev())
+    y = poisoned(x.shape, dtype); dx = poisoned(x.shape, dtype); stats = poisoned((rows * 2,), torch.float32)
     L().check(L().lib().dh_dbg_layernorm(DT[dtype], P(x), P(gamma), P(beta), P(y), P(stats), P(dy), P(add), P(dx), rows, C, 1e-5, L().stream_ptr()))
     tol = 4e-3 if dtype == torch.float16 else 2.5e-2
     close(y, ref, tol, tol, "ln fwd")
@@ -203,7 +244,7 @@ def test_geglu(dtype):
     gref, = torch.autograd.grad(ref, xr, dy.float())
     idx = glu_paired_index(Fd).to(dev())
     xp = x[:, idx].contiguous()                      # the engine keeps this tensor in the paired column order
-    y = torch.empty(rows, Fd, dtype=dtype, device=dev()); dxp = torch.empty_like(xp)
+    y = poisoned((rows, Fd), dtype); dxp = poisoned(xp.shape, dtype)
     L().check(L().lib().dh_dbg_geglu(DT[dtype], P(xp), P(y), P(dy), P(dxp), rows, Fd, L().stream_ptr()))
     dx = torch.empty_like(dxp); dx[:, idx] = dxp
     tol = 4e-3 if dtype == torch.float16 else 2.5e-2
@@ -230,8 +271,8 @@ def test_gemm_geglu_epilogues(dtype, M, Fd, K):
     y_ref = pre16[:, :Fd] * F.gelu(pre16[:, Fd:])
     tol = 4e-3 if dtype == torch.float16 else 2.5e-2
     for save in (True, False):
-        pre = torch.zeros(M, 2 * Fd, dtype=dtype, device=dev()) if save else None
-        y = torch.empty(M, Fd, dtype=dtype, device=dev())
+        pre = poisoned((M, 2 * Fd), dtype) if save else None
+        y = poisoned((M, Fd), dtype)
         L().check(lib.dh_dbg_gemm_glu(DT[dtype], 0, P(A), K, P(Wp), M, 2 * Fd, K, P(bp), P(pre), P(y), P(None), P(None),
                                       L().stream_ptr()), "dh_dbg_gemm_glu fwd")
         # (the activation is computed from the ROUNDED pre-activations: a pre-activation one 16-bit ulp off moves y by ~|h| ulp)
@@ -249,7 +290,7 @@ def test_gemm_geglu_epilogues(dtype, M, Fd, K):
     dy = A2.float() @ Wb.float().t()
     gref, = torch.autograd.grad(out, xr, dy)
     xp = x[:, idx].contiguous()
-    dxp = torch.zeros_like(xp)
+    dxp = poisoned(xp.shape, dtype)
     L().check(lib.dh_dbg_gemm_glu(DT[dtype], 1, P(A2), K2, P(Wb), M, Fd, K2, P(None), P(None), P(None), P(xp), P(dxp),
                                   L().stream_ptr()), "dh_dbg_gemm_glu bwd")
     dx = torch.empty_like(dxp); dx[:, idx] = dxp
@@ -273,15 +314,16 @@ def test_attention_forward_backward(dtype, B, H, Nq, Nk):
     ref = (torch.softmax(s, dim=-1) @ sp(vr, Nk)).transpose(1, 2).reshape(B, Nq, C)
     lse_ref = torch.logsumexp(s, dim=-1)
     gq, gk, gv = torch.autograd.grad(ref, (qr, kr, vr), do.float())
-    o = torch.empty_like(q); lse = torch.empty(B, H, Nq, dtype=torch.float32, device=dev()); delta = torch.empty_like(lse)
-    dq = torch.empty_like(q); dk = torch.empty_like(k); dv = torch.empty_like(v)
+    o = poisoned(q.shape, dtype); lse = poisoned((B, H, Nq), torch.float32); delta = poisoned((B, H, Nq), torch.float32)
+    dq = poisoned(q.shape, dtype); dk = poisoned(k.shape, dtype); dv = poisoned(v.shape, dtype)
     L().check(L().lib().dh_dbg_attention(DT[dtype], P(q), C, P(k), P(v), C, P(o), C, P(lse), P(do), P(delta), P(dq), P(dk), P(dv),
                                          B, H, Nq, Nk, L().stream_ptr()))
     tol = 5e-3 if dtype == torch.float16 else 3e-2
-    close(o, ref, tol, tol, "attn fwd")
-    close(lse, lse_ref, 1e-3, 2e-3, "attn lse")
+    what = f"attn {dtype} B={B} H={H} Nq={Nq} Nk={Nk}"
+    close(o, ref, tol, tol, what + " fwd")
+    close(lse, lse_ref, 1e-3, 2e-3, what + " lse")
     for got, r, nm in ((dq, gq, "dq"), (dk, gk, "dk"), (dv, gv, "dv")):
-        close(got, r, 2 * tol, 2 * tol * max(1.0, r.abs().max().item()) * 0.2, "attn " + nm)
+        close(got, r, 2 * tol, 2 * tol * max(1.0, r.abs().max().item()) * 0.2, what + " " + nm)
 
 
 def test_cross_lane_helpers():
@@ -290,8 +332,8 @@ def test_cross_lane_helpers():
     torch.manual_seed(5)
     for trial in range(4):
         x = torch.randn(64, device=dev()) * (10.0 ** trial)
-        out = torch.zeros(320, device=dev())
-        ex = torch.zeros(256, dtype=torch.int32, device=dev())
+        out = poisoned((320,), torch.float32)
+        ex = poisoned((256,), torch.int32)
         L().check(L().lib().dh_dbg_lane_ops(P(x), P(out), P(ex), L().stream_ptr()), "lane ops")
         torch.cuda.synchronize()
         xs = x.double().cpu()
@@ -340,9 +382,9 @@ def test_gemm_groupnorm_statistics_by_producer(dtype, B, HW, N, K, conv, expect)
     W = (torch.randn(N, K, generator=g, device=dev()) / K ** 0.5).to(dtype)
     bias = torch.randn(N, generator=g, device=dev()) * 3.0             # a DC offset per channel: the unshifted sums must survive it
     gamma = torch.randn(N, generator=g, device=dev()); beta = torch.randn(N, generator=g, device=dev())
-    C = torch.empty(M, N, dtype=dtype, device=dev()); Y = torch.empty_like(C)
-    stats = torch.zeros(B * G, 2, device=dev()); scratch = torch.zeros(1 << 20, device=dev())
-    part = torch.empty(16 << 20, dtype=torch.float32, device=dev())
+    C = poisoned((M, N), dtype); Y = poisoned((M, N), dtype)
+    stats = poisoned((B * G, 2), torch.float32); scratch = torch.zeros(1 << 20, device=dev())
+    part = poisoned((16 << 20,), torch.float32)
     have = ctypes.c_int(-1)
     L().check(lib.dh_dbg_gemm_groupnorm(DT[dtype], P(A), lda, P(W), M, N, K, mode, H, H, Cin, P(bias), P(C), P(part), part.numel(), HW, G,
                                         P(gamma), P(beta), 1e-5, 1, P(Y), P(stats), P(scratch), ctypes.byref(have), L().stream_ptr()),
@@ -392,10 +434,10 @@ def test_gemm_groupnorm_backward_statistics_by_producer(dtype, B, HW, N, K, conv
     xd = x.double().view(B, HW, G, N // G)
     mean = xd.mean(dim=(1, 3)); rstd = (xd.var(dim=(1, 3), unbiased=False) + 1e-5).rsqrt()
     stats = torch.stack([mean, rstd], dim=-1).float().contiguous()
-    part = torch.empty(16 << 20, dtype=torch.float32, device=dev())
+    part = poisoned((16 << 20,), torch.float32)
 
     def run(stage):
-        C = torch.empty(M, N, dtype=dtype, device=dev()); dx = torch.empty_like(C)
+        C = poisoned((M, N), dtype); dx = poisoned((M, N), dtype)
         scratch = torch.full((1 << 20,), float("nan"), device=dev())
         have = ctypes.c_int(-1)
         L().check(lib.dh_dbg_gemm_stage(stage), "stage")

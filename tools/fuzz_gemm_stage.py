@@ -24,6 +24,8 @@ part = torch.empty(48 << 20, dtype=torch.float32, device=dev)
 
 def gemm(dtype, A, lda, W, M, N, K, mode, geo, bias, rowvec, rpb, R, split):
     C = torch.full((M, N), float("nan"), dtype=dtype, device=dev)
+    if split:
+        part.fill_(float("nan"))                 # every slab element the reduce reads is written by the K loop first
     _lib.check(L.dh_dbg_gemm(DT[dtype], P(A), lda, P(W), M, N, K, mode, *geo, P(bias), P(rowvec), rowvec.shape[1] if rowvec is not None else 0, rpb,
                              P(R), N, P(C), N, 0, P(part) if split else P(None), part.numel() if split else 0, _lib.stream_ptr()), "dh_dbg_gemm")
     return C
@@ -77,13 +79,13 @@ try:
                 L.dh_dbg_gemm_stage(stage)
                 if kind == "glu_fwd":
                     W = (torch.randn(2 * Fd, K, generator=torch.Generator(device=dev).manual_seed(ci), device=dev) / K ** 0.5).to(dtype)
-                    pre = torch.empty(M, 2 * Fd, dtype=dtype, device=dev); y = torch.empty(M, Fd, dtype=dtype, device=dev)
+                    pre = torch.full((M, 2 * Fd), float("nan"), dtype=dtype, device=dev); y = torch.full((M, Fd), float("nan"), dtype=dtype, device=dev)
                     _lib.check(L.dh_dbg_gemm_glu(DT[dtype], 0, P(A), K, P(W), M, 2 * Fd, K, P(None), P(pre), P(y), P(None), P(None), _lib.stream_ptr()), "glu fwd")
                     outs.append(torch.cat([pre, y], dim=1))
                 else:
                     Wb = (torch.randn(Fd, K, generator=torch.Generator(device=dev).manual_seed(ci), device=dev) / K ** 0.5).to(dtype)
                     pre = torch.randn(M, 2 * Fd, generator=torch.Generator(device=dev).manual_seed(ci + 1), device=dev).to(dtype)
-                    dx = torch.empty(M, 2 * Fd, dtype=dtype, device=dev)
+                    dx = torch.full((M, 2 * Fd), float("nan"), dtype=dtype, device=dev)
                     _lib.check(L.dh_dbg_gemm_glu(DT[dtype], 1, P(A), K, P(Wb), M, Fd, K, P(None), P(None), P(None), P(pre), P(dx), _lib.stream_ptr()), "glu bwd")
                     outs.append(dx)
             same = torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))

@@ -106,6 +106,8 @@ SIGNATURES = {
     "dh_unet_io_ptr": (c_i, [c_p, c_i, c_i, ctypes.POINTER(c_p), ctypes.POINTER(c_sz)]),
     "dh_mse_cotangent": (c_i, [c_p, c_p, c_i, c_f, c_f, c_p, c_p, c_p, c_p]),
     "dh_adam_step_scaled": (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_p]),
+    "dh_mse_cotangent_batch": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_d, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "dh_adam_step_scaled_batch": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p]),
 }
 
 # test hooks (csrc/debug_api.cpp): single-kernel entry points used only by tests/

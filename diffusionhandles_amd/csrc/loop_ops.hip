@@ -115,6 +115,76 @@ __global__ void k_adam_scaled(float* p, const float* g, float* m, float* v, floa
   p[i] = p[i] - (lr / bc1) * (mi / denom);
 }
 
+// k_mse_cotangent for `batch` images of n elements each, one workgroup per image (blockIdx.x = image), with the early stop of
+// the null-text inner loop: an image inactive on entry gets d_eps = 0 and S = 1 (its loss is still written); updated[b] =
+// active[b] on entry, active[b] &= !((double)loss < threshold).  Workgroup b alone reads and writes active[b] / updated[b].
+__global__ void __launch_bounds__(1024) k_mse_cotangent_batch(const float* a_all, const float* b_all, int n, float k, float amp,
+                                                              double threshold, int* active, int* updated, float* loss_out,
+                                                              float* d_eps_all, float* scale_out) {
+  __shared__ double sm[16];
+  __shared__ float smax[16];
+  const int img = blockIdx.x;
+  const size_t off = (size_t)img * n;
+  const float* a = a_all + off;
+  const float* b = b_all + off;
+  float* d_eps = d_eps_all + off;
+  const int on = active[img];           // read by every thread before the barriers below; written once after them
+  double l = 0.0;
+  float mx = 0.f;
+  const float k2 = 2.f / (float)n;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const float d = a[i] - b[i];
+    l += (double)d * (double)d;
+    mx = fmaxf(mx, fabsf(k2 * d));
+  }
+  l = block_sum(l, sm);
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  mx = 0.f;
+  for (int w = 0; w < (int)((blockDim.x + 63) >> 6); ++w) mx = fmaxf(mx, smax[w]);
+  mx *= fabsf(k);
+  float S = 1.f;
+  if (on && amp > 0.f && mx > 0.f && mx < INFINITY) {
+    int e = 0;
+    (void)frexpf(amp / mx, &e);
+    e = e - 1;
+    e = e > 100 ? 100 : (e < -100 ? -100 : e);
+    S = ldexpf(1.f, e);
+  }
+  const float kS = k * S;
+  if (on) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) d_eps[i] = (k2 * (a[i] - b[i])) * kS;
+  } else {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) d_eps[i] = 0.f;
+  }
+  if (threadIdx.x == 0) {
+    const float loss = (float)(l / (double)n);
+    loss_out[img] = loss;
+    scale_out[img] = S;
+    updated[img] = on;
+    active[img] = (on && !((double)loss < threshold)) ? 1 : 0;
+  }
+}
+
+// k_adam_scaled on image blockIdx.y of `batch` (n elements each), skipped as a whole where updated[image] == 0
+__global__ void k_adam_scaled_batch(float* p, const float* g, float* m, float* v, float lr, float b1, float b2, float eps,
+                                    float bc1, float bc2_sqrt, const float* g_scale, const int* updated, int n) {
+  const int img = blockIdx.y;
+  if (!updated[img]) return;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t j = (size_t)img * n + i;
+  float gi = g[j] / g_scale[img];
+  if (!isfinite(gi)) return;
+  float mi = m[j] + (1.f - b1) * (gi - m[j]);
+  float vi = b2 * v[j] + (1.f - b2) * gi * gi;
+  m[j] = mi;
+  v[j] = vi;
+  float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p[j] = p[j] - (lr / bc1) * (mi / denom);
+}
+
 }  // namespace dh
 using namespace dh;
 
@@ -173,6 +243,28 @@ extern "C" int dh_adam_step_scaled(float* p, const float* g, const float* g_scal
   float bc2 = sqrtf(1.f - powf(beta2, (float)step));
   hipLaunchKernelGGL(k_adam_scaled, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, lr, beta1, beta2,
                      eps, bc1, bc2, g_scale, n);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_mse_cotangent_batch(const float* rec, const float* target, int batch, int n, float k, float amp,
+                                      double threshold, int* active, int* updated, float* loss_out, float* d_eps,
+                                      float* scale_out, void* stream) {
+  DH_REQUIRE(rec && target && active && updated && loss_out && d_eps && scale_out && batch >= 1 && n > 0, "bad arguments");
+  hipLaunchKernelGGL(k_mse_cotangent_batch, dim3(batch), dim3(1024), 0, (hipStream_t)stream, rec, target, n, k, amp,
+                     threshold, active, updated, loss_out, d_eps, scale_out);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_adam_step_scaled_batch(float* p, const float* g, const float* g_scale, const int* updated, float* m, float* v,
+                                         float lr, float beta1, float beta2, float eps, int step, int batch, int n,
+                                         void* stream) {
+  DH_REQUIRE(p && g && g_scale && updated && m && v && batch >= 1 && batch <= 65535 && n > 0 && step >= 1, "bad arguments");
+  float bc1 = 1.f - powf(beta1, (float)step);
+  float bc2 = sqrtf(1.f - powf(beta2, (float)step));
+  hipLaunchKernelGGL(k_adam_scaled_batch, dim3(cdiv(n, 256), batch), dim3(256), 0, (hipStream_t)stream, p, g, m, v, lr, beta1,
+                     beta2, eps, bc1, bc2, g_scale, updated, n);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

@@ -37,6 +37,31 @@ class DiffusionHandles:
                 init_latents=init_noise, depth=disparity, uncond_embeddings=null_text_emb, prompt=prompt)
         return null_text_emb, init_noise, activations, latent_image
 
+    def _require_identity_batch(self, K):
+        unet = self.diffuser.unet
+        if unet is not None and (unet.max_batch < 2 * K or unet.max_diff_batch < K):
+            raise RuntimeError(f"engine max_batch {unet.max_batch} / max_diff_batch {unet.max_diff_batch} too small for {K} "
+                               f"images: build the diffuser with max_batch >= {2 * K}")
+
+    def invert_input_images(self, imgs, depths, prompts):
+        """invert_input_image for K images of the same resolution in B = K passes (not in the reference).
+        -> [(null_text_emb [T,1,77,D], init_noise [1,4,h,w])] per image.  Needs max_batch >= 2K."""
+        self._require_identity_batch(len(imgs))
+        disparities = [normalize_depth(1.0 / depth) for depth in depths]
+        res = self.inverter.invert_batch(target_imgs=imgs, depths=disparities, prompts=prompts, num_inner_steps=5)
+        return [(null_text_emb, init_noise) for _, init_noise, null_text_emb in res]
+
+    def generate_input_images(self, depths, prompts, null_text_embs=None, init_noises=None):
+        """generate_input_image for K images in B = 2K CFG passes (not in the reference).
+        -> [(null_text_emb, init_noise, activations [3], latent_image)] per image.  Needs max_batch >= 2K."""
+        self._require_identity_batch(len(depths))
+        disparities = [normalize_depth(1.0 / depth) for depth in depths]
+        with torch.no_grad():
+            res = self.diffuser.initial_inference_batch(init_latents=init_noises, depths=disparities,
+                                                        uncond_embeddings=null_text_embs, prompts=prompts)
+        return [(null_text_emb, init_noise, activations, latent_image)
+                for activations, latent_image, null_text_emb, init_noise in res]
+
     def set_foreground(self, depth, fg_mask, bg_depth):
         """Background depth = input depth with the hole of the (15x cross-dilated) foreground mask in-filled
         from the background depth's Laplacian (reference diffusion_handles.py:90-111)."""

@@ -323,6 +323,66 @@ class GuidedStableDiffuser(GuidedDiffuser):
         activations = [a.permute(0, 3, 1, 2) for a in store]      # [T,C,h,w] views of channels-last storage
         return activations, x.permute(0, 3, 1, 2), uncond_embeddings, init_latents
 
+    @torch.no_grad()
+    def initial_inference_batch(self, init_latents, depths, uncond_embeddings, prompts):
+        """initial_inference for K images of the engine's resolution in B = 2K CFG passes (not in the reference).  Lists of K
+        in (init_latents / uncond_embeddings entries may be None, or the lists themselves None), one (activations, latents,
+        uncond_embeddings, init_latents) per image out.  Needs max_batch >= 2K.  Every image is seeded as its own
+        initial_inference call would be (torch.manual_seed(conf.seed) per image, so images without init_latents share the
+        noise), and its activations come from its conditional half, the capture rule of initial_inference; at K = 1 the
+        result is bit-identical to initial_inference."""
+        K = len(prompts)
+        init_latents = [None] * K if init_latents is None else list(init_latents)
+        uncond_embeddings = [None] * K if uncond_embeddings is None else list(uncond_embeddings)
+        if K < 1 or not (len(depths) == len(init_latents) == len(uncond_embeddings) == K):
+            raise ValueError("initial_inference_batch: init_latents, depths, uncond_embeddings and prompts must be non-empty "
+                             "and of the same length")
+        if self.unet.max_batch < 2 * K:
+            raise RuntimeError(f"engine max_batch {self.unet.max_batch} < 2*K = {2 * K}: build the diffuser with "
+                               f"max_batch >= {2 * K}")
+        s = self.unet.sample_size
+        for b, lat in enumerate(init_latents):
+            if lat is not None and tuple(lat.shape[-2:]) != (s, s):
+                raise ValueError(f"initial_inference_batch: init_latents {b} is {tuple(lat.shape[-2:])}, the engine runs "
+                                 f"{(s, s)} latents")
+        with self.on_stream():
+            return self._initial_inference_batch(init_latents, depths, uncond_embeddings, prompts)
+
+    def _initial_inference_batch(self, init_latents, depths, uncond_embeddings, prompts):
+        K = len(prompts)
+        self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
+        timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
+        T = len(timesteps)
+        s = self.unet.sample_size
+        inits, uncs = [], []
+        for lat, unc in zip(init_latents, uncond_embeddings):
+            torch.manual_seed(self.conf.seed)              # as K initial_inference calls, one after the other
+            if lat is None:
+                nlat = self.unet.config.in_channels - 1 if self.conf.use_depth else self.unet.config.in_channels
+                noise = torch.randn([1, nlat, s, s], dtype=torch.float32).to(self.device)
+                lat = self.scheduler.add_noise(torch.zeros_like(noise), noise, timesteps[0])
+            inits.append(lat)
+            uncs.append(self._encode([""])[None].expand(T, -1, -1, -1) if unc is None else unc)
+        depth_nhwc = None
+        if self.conf.use_depth:
+            depth_nhwc = torch.cat([_nhwc(self.init_depth(d.to(self.device, torch.float32))) for d in depths])
+        cond = torch.cat([self._encode([p]) for p in prompts]).contiguous()
+        x = torch.cat([_nhwc(lat.to(self.device, torch.float32)) for lat in inits])
+        store = [[torch.empty((T,) + shp, dtype=self.dtype, device=self.device) for shp in self.unet.act_shapes]
+                 for _ in range(K)]
+        for t_idx, t in enumerate(timesteps):
+            # [uncond_1 .. uncond_K | cond_1 .. cond_K]: image b's conditional half is batch item K + b
+            unc = torch.cat([u[t_idx].reshape(1, *cond.shape[1:]).to(self.device, torch.float32) for u in uncs])
+            text = torch.cat([unc, cond]).contiguous()
+            sample = self._unet_input(x, depth_nhwc).repeat(2, 1, 1, 1)
+            eps, acts = self.unet.forward(sample, float(t), text, save_for_backward=False, want_acts=True)
+            for b in range(K):
+                for k in range(3):
+                    store[b][k][t_idx].copy_(acts[k][K + b])
+            x = self.ddim_step(x, eps[:K], eps[K:], t)
+        return [([a.permute(0, 3, 1, 2) for a in store[b]], x[b:b + 1].permute(0, 3, 1, 2), uncs[b], inits[b])
+                for b in range(K)]
+
     def prepare_guidance(self, depth, prompt, activations_orig, correspondences, fg_weight=None, bg_weight=None, orig=None,
                          cond=None):
         """Everything of guided_inference that is constant over the denoising loop.  `orig`: the channels-last copies of

@@ -187,3 +187,102 @@ class StableNullInverter(NullInverter):
                                         max_timesteps)
         self.last_ddim_latents = ddim_latents
         return (target_img, recon_img), ddim_latents[-1].permute(0, 3, 1, 2), uncond
+
+    # ---- K images of the same resolution inverted together (not in the reference: a batch-1 script) ---------------------
+    @torch.no_grad()
+    def null_step_batch(self, cur, uncond, cond, depth, i, target, num_inner_steps, epsilon, record=None):
+        """null_step for K images at once: cur / target [K,H,W,4], uncond / cond [K,77,D] (uncond updated in place), depth
+        [K,H,W,1] or None.  Every image keeps its own Adam state, cotangent scale and early stop (dh_mse_cotangent_batch /
+        dh_adam_step_scaled_batch): an image that stopped rides along in the B = K passes with its embedding frozen.  One
+        host read of the K active flags per inner step; the loop ends when no image is active.  Returns the inner steps
+        taken per image."""
+        L = _lib.lib()
+        K = cur.shape[0]
+        n = cur[0].numel()
+        loss_dev = torch.zeros(K, dtype=torch.float32, device=cur.device)
+        scale_dev = torch.ones(K, dtype=torch.float32, device=cur.device)
+        active = torch.ones(K, dtype=torch.int32, device=cur.device)
+        updated = torch.zeros(K, dtype=torch.int32, device=cur.device)
+        d_eps = torch.empty_like(cur)
+        m = torch.zeros_like(uncond)
+        v = torch.zeros_like(uncond)
+        lr = 1e-2 * (1.0 - i / 100.0)
+        t = self.scheduler.timesteps[i]
+        a_t, a_p = self.scheduler.step_alphas(t)
+        k = (1.0 - self.guidance_scale) * ((1 - a_p) ** 0.5 - (a_p ** 0.5) * ((1 - a_t) ** 0.5) / (a_t ** 0.5))
+        threshold = epsilon + i * 2e-5
+        eps_c = self.get_noise_pred_single(cur, t, cond, depth)
+        self._eps_c = eps_c
+        taken = [0] * K
+        on = [1] * K
+        for j in range(num_inner_steps):
+            eps_u = self.get_noise_pred_single(cur, t, uncond, depth, save=True)
+            rec = self._step(cur, eps_u, eps_c, self.guidance_scale, a_t, a_p)
+            _lib.check(L.dh_mse_cotangent_batch(_lib.ptr(rec), _lib.ptr(target), K, n, k, self.cotangent_amp, threshold,
+                                                _lib.ptr(active), _lib.ptr(updated), _lib.ptr(loss_dev), _lib.ptr(d_eps),
+                                                _lib.ptr(scale_dev), _lib.stream_ptr()), "dh_mse_cotangent_batch")
+            _, d_text = self.model.unet.backward(None, d_eps, want_sample_grad=False, want_text_grad=True)
+            _lib.check(L.dh_adam_step_scaled_batch(_lib.ptr(uncond), _lib.ptr(d_text), _lib.ptr(scale_dev), _lib.ptr(updated),
+                                                   _lib.ptr(m), _lib.ptr(v), lr, 0.9, 0.999, 1e-8, j + 1, K, uncond[0].numel(),
+                                                   _lib.stream_ptr()), "dh_adam_step_scaled_batch")
+            taken = [n_ + o for n_, o in zip(taken, on)]
+            if record is not None:
+                record.setdefault("loss", []).append(loss_dev.tolist())
+                record.setdefault("updated", []).append(list(on))
+            on = active.tolist()                 # the one host read of the inner step (null_step reads the loss instead)
+            if not any(on):
+                break
+        return taken
+
+    def invert_batch(self, target_imgs, depths, prompts, num_inner_steps=10, early_stop_epsilon=1e-5, max_timesteps=None):
+        """K images of the engine's resolution, each with its own depth and prompt, inverted in B = K engine passes: the DDIM
+        inversion, then per timestep one B = K conditional forward, up to num_inner_steps x (saved B = K forward, backward to
+        the K text embeddings, per-image Adam step and early stop) and the B = K unconditional forward of the CFG step.
+        Returns one ((img, recon), init_noise [1,4,h,w], uncond [T,1,77,D]) per image, in input order; at K = 1 bit-identical
+        to invert().  Needs an engine whose saved forwards may be K wide (max_diff_batch >= K)."""
+        K = len(target_imgs)
+        if K < 1 or not (len(depths) == len(prompts) == K):
+            raise ValueError("invert_batch: target_imgs, depths and prompts must be non-empty and of the same length")
+        unet = self.model.unet
+        if unet.max_diff_batch < K:
+            raise RuntimeError(f"engine max_diff_batch {unet.max_diff_batch} < K = {K}: inverting {K} images together needs "
+                               f"max_diff_batch >= {K} (a diffuser built with max_batch >= {2 * K})")
+        hw = tuple(self.model.get_image_shape()[:2])
+        for b, img in enumerate(target_imgs):
+            if tuple(img.shape[-2:]) != hw:
+                raise ValueError(f"invert_batch: image {b} is {tuple(img.shape[-2:])}, the engine runs {hw} images")
+        with self.model.on_stream():
+            return self._invert_batch(target_imgs, depths, prompts, num_inner_steps, early_stop_epsilon, max_timesteps)
+
+    @torch.no_grad()
+    def _invert_batch(self, target_imgs, depths, prompts, num_inner_steps, epsilon, max_timesteps):
+        dev = self.model.device
+        K = len(target_imgs)
+        depth_nhwc = None
+        if self.model.conf.use_depth:
+            depth_nhwc = torch.cat([self.model.init_depth(d.to(dev, torch.float32)).permute(0, 2, 3, 1) for d in depths])
+            depth_nhwc = depth_nhwc.contiguous()
+        contexts = [self.model.init_prompt(p) for p in prompts]
+        uncond = torch.cat([c[0:1] for c in contexts]).contiguous()
+        cond = torch.cat([c[1:2] for c in contexts]).contiguous()
+        latent = self.image2latent(torch.cat([img.to(dev, torch.float32) for img in target_imgs]))
+        recon = self.latent2image(latent)
+        ddim_latents = self.ddim_loop(latent.permute(0, 2, 3, 1).contiguous(), torch.cat([uncond, cond]), depth_nhwc)
+        out = []
+        cur = ddim_latents[-1]
+        steps = self.num_ddim_steps if max_timesteps is None else max_timesteps
+        taken = []
+        for i in range(steps):
+            target = ddim_latents[len(ddim_latents) - i - 2]
+            t = self.scheduler.timesteps[i]
+            a_t, a_p = self.scheduler.step_alphas(t)
+            taken.append(self.null_step_batch(cur, uncond, cond, depth_nhwc, i, target, num_inner_steps, epsilon))
+            out.append(uncond.clone())
+            # the CFG step with the optimised embeddings: the conditional half is this timestep's eps_c (null_optimization)
+            eu = self.get_noise_pred_single(cur, t, uncond, depth_nhwc)
+            cur = self._step(cur, eu, self._eps_c, self.guidance_scale, a_t, a_p)
+        unconds = torch.stack(out, dim=0)                       # [T,K,77,D]
+        self.inner_steps_taken = [[s[b] for s in taken] for b in range(K)]
+        self.last_ddim_latents = ddim_latents
+        init_noise = ddim_latents[-1].permute(0, 3, 1, 2)
+        return [((target_imgs[b], recon[b:b + 1]), init_noise[b:b + 1], unconds[:, b:b + 1].contiguous()) for b in range(K)]

@@ -292,6 +292,18 @@ int dh_mse_cotangent(const float* rec, const float* target, int n, float k, floa
 /* dh_adam_step on g / g_scale[0] (g_scale: device scalar, the S of dh_mse_cotangent) */
 int dh_adam_step_scaled(float* p, const float* g, const float* g_scale, float* m, float* v, float lr, float beta1,
                         float beta2, float eps, int step, int n, void* stream);
+/* dh_mse_cotangent for `batch` images of n elements each (rec / target / d_eps [batch][n]; loss_out / scale_out [batch]),
+ * with the per-image early stop of the null-text inner loop (stable_null_inverter.py:141-158; checked after the step's Adam
+ * update): an image with active[b] == 0 on entry gets d_eps = 0 and S = 1; every image gets loss_out[b];
+ * updated[b] = active[b] on entry, then active[b] = active[b] && !((double)loss_out[b] < threshold).  The threshold is a double
+ * compared against the f32 loss widened to double, like the host's `loss.item() < epsilon + 2e-5 i`.  batch = 1 is bit-identical
+ * to dh_mse_cotangent. */
+int dh_mse_cotangent_batch(const float* rec, const float* target, int batch, int n, float k, float amp, double threshold,
+                           int* active, int* updated, float* loss_out, float* d_eps, float* scale_out, void* stream);
+/* dh_adam_step_scaled on image b of `batch` (p / g / m / v [batch][n]) with g_scale[b], only where updated[b] != 0 (the others
+ * keep parameters and moments); batch = 1 is bit-identical to dh_adam_step_scaled */
+int dh_adam_step_scaled_batch(float* p, const float* g, const float* g_scale, const int* updated, float* m, float* v, float lr,
+                              float beta1, float beta2, float eps, int step, int batch, int n, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * SD AutoencoderKL decoder on the engine's kernels: the decode that ends every edit

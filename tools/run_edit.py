@@ -71,7 +71,14 @@ def parse():
     ap.add_argument("--input-dir", default=None, help="directory of the scene directories of --test-set (default: the JSON's directory)")
     ap.add_argument("--config", default=None, help="configuration YAML (the reference's --config_path, test/config/*.yaml)")
     ap.add_argument("--max-scenes", type=int, default=0, help="--test-set: only the first N scenes")
-    return ap.parse_args()
+    ap.add_argument("--identity-batch", type=int, default=1,
+                    help="--test-set: the scenes that need an identity (not skipped, no cache file) are inverted and initially "
+                         "inferred K at a time (DiffusionHandles.invert_input_images / generate_input_images; the engine is "
+                         "built with max_batch >= 2K); 1 = one scene at a time")
+    args = ap.parse_args()
+    if args.identity_batch < 1 or (args.identity_batch > 1 and args.test_set is None):
+        ap.error("--identity-batch K needs K >= 1, and K > 1 needs --test-set")
+    return args
 
 
 def main():
@@ -89,8 +96,9 @@ def main():
             ucfg = dict(SD2_DEPTH, sample_size=res // 8)
             if not conf.guided_diffuser.use_depth:
                 ucfg["in_channels"] = 4          # use_depth: false (test/config/no_depth.yaml): no depth channel beside the latent
+            extra = {} if args.identity_batch == 1 else {"max_batch": 2 * args.identity_batch}
             state["dh"] = DiffusionHandles(conf, dtype=torch.float16 if args.dtype == "fp16" else torch.bfloat16,
-                                           unet_config=ucfg).to(torch.device("cuda:0"))
+                                           unet_config=ucfg, **extra).to(torch.device("cuda:0"))
         return state["dh"]
 
     if args.test_set is None:
@@ -109,12 +117,25 @@ def main():
     if args.max_scenes > 0:
         names = names[:args.max_scenes]
     reports = []
+    sub = argparse.Namespace(**vars(args))
+    # the identity cache of a scene lives in its own output directory unless the caller disabled it
+    sub.identity_cache = None
+    identities = {}                 # --identity-batch > 1: the identities of the current chunk, by scene
     for idx, (scene, transform_names) in enumerate(names):
         sys.stderr.write(f"[{idx + 1}/{len(names)}] {scene}: {len(transform_names)} transforms\n")
-        sub = argparse.Namespace(**vars(args))
-        # the identity cache of a scene lives in its own output directory unless the caller disabled it
-        sub.identity_cache = None
-        rep = run_scene(sub, conf, handles, os.path.join(input_dir, scene), os.path.join(args.out, scene), list(transform_names))
+        if args.identity_batch > 1 and scene not in identities:
+            need = lambda i: needs_identity(sub, os.path.join(input_dir, names[i][0]), os.path.join(args.out, names[i][0]),
+                                            list(names[i][1]))
+            if need(idx):
+                chunk = [idx]
+                j = idx + 1
+                while len(chunk) < args.identity_batch and j < len(names):
+                    if need(j):
+                        chunk.append(j)
+                    j += 1
+                identities = identity_chunk(sub, handles, [(os.path.join(input_dir, names[i][0]), names[i][0]) for i in chunk])
+        rep = run_scene(sub, conf, handles, os.path.join(input_dir, scene), os.path.join(args.out, scene), list(transform_names),
+                        identity=identities.pop(scene, None))
         rep["scene"] = scene
         reports.append(rep)
     set_name = os.path.splitext(os.path.basename(args.test_set))[0]
@@ -131,14 +152,39 @@ def main():
     print(json.dumps(total))
 
 
-def run_scene(args, conf, handles, scene, out, transform_names):
-    """One scene (the body of the reference's loop, test_diffusion_handles.py:66-175): identity (inversion + initial inference,
-    or the cache), set_foreground, one transform_foreground per transform.  transform_names: the subset / order the test set
-    lists for this scene (names the scene's transforms.json does not have are skipped with a warning, :126-128)."""
-    from diffusionhandles_amd.scene_io import load_scene, transform_args, write_png
-    from diffusionhandles_amd.synthetic import TRANSFORMS, make_image, make_scene
-    os.makedirs(out, exist_ok=True)
+def needs_identity(args, scene, out, transform_names):
+    """--identity-batch: whether run_scene would compute this scene's identity (not skipped, no cache file to load)."""
+    p = prepare_scene(args, scene, out, transform_names, warn=False)
+    if args.skip_existing and p["transforms"] and all(p["exists"].values()):
+        return False
+    return args.no_identity_cache or not os.path.exists(os.path.join(out, "identity.npz"))
+
+
+def identity_chunk(args, handles, scenes):
+    """The identities of K scenes of one resolution in batched passes: DiffusionHandles.invert_input_images (B = K) and
+    generate_input_images (B = 2 K).  scenes: [(scene directory, name)].  Returns {name: (null_text, noise, acts, latent,
+    seconds)}, seconds = the chunk's time divided by its number of scenes."""
+    from diffusionhandles_amd.scene_io import load_scene
     dev = torch.device("cuda:0")
+    scs = [load_scene(d, args.res) for d, _ in scenes]
+    dh = handles(args.res)
+    imgs = [sc["img"].to(dev) for sc in scs]
+    depths = [sc["depth"].to(dev) for sc in scs]
+    prompts = [sc["prompt"] for sc in scs]
+    t0 = time.time()
+    null_texts, noises = [None] * len(scs), [None] * len(scs)
+    if not args.skip_inversion:
+        null_texts, noises = map(list, zip(*dh.invert_input_images(imgs, depths, prompts)))
+    res = dh.generate_input_images(depths, prompts, null_texts, noises)
+    torch.cuda.synchronize()
+    share = (time.time() - t0) / len(scs)
+    return {name: r + (share,) for (_, name), r in zip(scenes, res)}
+
+
+def prepare_scene(args, scene, out, transform_names, warn=True):
+    """The inputs and the transform list of one scene, and which of its edits exist already."""
+    from diffusionhandles_amd.scene_io import load_scene, transform_args
+    from diffusionhandles_amd.synthetic import TRANSFORMS, make_image, make_scene
     if scene:
         sc = load_scene(scene, args.res)
         img, depth, bg_depth, mask, prompt, res = sc["img"], sc["depth"], sc["bg_depth"], sc["fg_mask"], sc["prompt"], args.res
@@ -153,7 +199,7 @@ def run_scene(args, conf, handles, scene, out, transform_names):
     if transform_names is not None:
         have = {tf["name"]: tf for tf in transforms}
         for n in transform_names:
-            if n not in have:
+            if warn and n not in have:
                 sys.stderr.write(f"WARNING: transform {n} not found for scene {scene}; skipping\n")
         transforms = [have[n] for n in transform_names if n in have]
     if args.max_edits > 0:
@@ -161,13 +207,30 @@ def run_scene(args, conf, handles, scene, out, transform_names):
     for i, tf in enumerate(transforms):
         tf.setdefault("name", f"edit{i}")
     exists = {tf["name"]: os.path.exists(os.path.join(out, tf["name"] + ".png")) for tf in transforms}
+    return dict(img=img, depth=depth, bg_depth=bg_depth, mask=mask, prompt=prompt, res=res, transforms=transforms, exists=exists)
+
+
+def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
+    """One scene (the body of the reference's loop, test_diffusion_handles.py:66-175): identity (inversion + initial inference,
+    or the cache), set_foreground, one transform_foreground per transform.  transform_names: the subset / order the test set
+    lists for this scene (names the scene's transforms.json does not have are skipped with a warning, :126-128).
+    identity: (null_text, noise, acts, latent, seconds) computed by identity_chunk (--identity-batch), written to the cache."""
+    from diffusionhandles_amd.scene_io import write_png
+    os.makedirs(out, exist_ok=True)
+    dev = torch.device("cuda:0")
+    p = prepare_scene(args, scene, out, transform_names)
+    img, depth, bg_depth, mask, prompt, res = p["img"], p["depth"], p["bg_depth"], p["mask"], p["prompt"], p["res"]
+    transforms, exists = p["transforms"], p["exists"]
     if args.skip_existing and transforms and all(exists.values()):
         return dict(resolution=res, mode=args.mode, skipped_scene=True, edits=[dict(name=n, skipped=True) for n in exists])
     dh = handles(res)
     depth, bg_depth, mask, img = depth.to(dev), bg_depth.to(dev), mask.to(dev), img.to(dev)
     t0 = time.time()
     cache = None if args.no_identity_cache else (args.identity_cache or os.path.join(out, "identity.npz"))
-    identity_from_cache = cache is not None and os.path.exists(cache)
+    identity_from_cache = identity is None and cache is not None and os.path.exists(cache)
+    chunk_s = 0.0
+    if identity is not None:
+        null_text, noise, acts, latent, chunk_s = identity
     if identity_from_cache:
         # the input-image identity as the reference caches it (and as its web services pass it around,
         # webapp/webapps/diffhandles_webapp.py:82-94): float32 arrays under the reference's keys
@@ -177,10 +240,11 @@ def run_scene(args, conf, handles, scene, out, transform_names):
             acts = [torch.from_numpy(z[f"activations{i + 1}"]).to(dev) for i in range(3)]
             latent = torch.from_numpy(z["latent_image"]).to(dev)
     else:
-        null_text, noise = (None, None)
-        if not args.skip_inversion:
-            null_text, noise = dh.invert_input_image(img, depth, prompt)
-        null_text, noise, acts, latent = dh.generate_input_image(depth, prompt, null_text, noise)
+        if identity is None:
+            null_text, noise = (None, None)
+            if not args.skip_inversion:
+                null_text, noise = dh.invert_input_image(img, depth, prompt)
+            null_text, noise, acts, latent = dh.generate_input_image(depth, prompt, null_text, noise)
         if cache is not None:
             os.makedirs(os.path.dirname(os.path.abspath(cache)), exist_ok=True)
             np.savez(cache, null_text_emb=null_text.float().cpu().numpy(),
@@ -189,11 +253,13 @@ def run_scene(args, conf, handles, scene, out, transform_names):
                      latent_image=latent.float().cpu().numpy())
     bg_depth = dh.set_foreground(depth, mask, bg_depth)
     torch.cuda.synchronize()
-    t_identity = time.time() - t0
+    t_identity = time.time() - t0 + chunk_s
     recon = dh.diffuser.decode_latent_image(latent)
     write_png(os.path.join(out, "recon.png"), recon[0].permute(1, 2, 0).float().cpu().numpy())
     report = dict(resolution=res, mode=args.mode, identity_s=round(t_identity, 2), identity_from_cache=bool(identity_from_cache),
                   edits=[])
+    if args.identity_batch > 1:
+        report["identity_batch"] = args.identity_batch
     for tf in transforms:
         if args.skip_existing and exists[tf["name"]]:
             report["edits"].append(dict(name=tf["name"], skipped=True))

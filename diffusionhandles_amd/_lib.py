@@ -120,6 +120,19 @@ DEBUG_SIGNATURES = {
     # (dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, C, partial, partial_elems, HW, G, x, gamma, beta, stats, silu, dx, scratch, have_out, stream)
     "dh_dbg_gemm_groupnorm_bwd": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_sz, c_i, c_i, c_p, c_p, c_p, c_p, c_i,
                                         c_p, c_p, ctypes.POINTER(c_i), c_p]),
+    # the same two with a residual R (row pitch ldr; NULL, or C itself)
+    # (dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, bias, R, ldr, C, partial, partial_elems, HW, G, gamma, beta, eps, silu, Y, stats,
+    #  scratch, have_out, stream)
+    "dh_dbg_gemm_groupnorm_res": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_sz, c_i, c_i, c_p, c_p,
+                                    c_f, c_i, c_p, c_p, c_p, ctypes.POINTER(c_i), c_p]),
+    # (dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, R, ldr, C, partial, partial_elems, HW, G, x, gamma, beta, stats, silu, dx, scratch,
+    #  have_out, stream)
+    "dh_dbg_gemm_groupnorm_bwd_res": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_sz, c_i, c_i, c_p, c_p, c_p,
+                                        c_p, c_i, c_p, c_p, ctypes.POINTER(c_i), c_p]),
+    # (dtype, a, Ca, b, Cb, out, B, HW, G, gamma, beta, eps, silu, Y, stats, scratch, stream)
+    "dh_dbg_concat_groupnorm": (c_i, [c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p]),
+    "dh_dbg_gemm_last_tile": (c_i, [ctypes.POINTER(c_i)]),
+    "dh_dbg_unet_concat_ops": (c_i, [ctypes.POINTER(UNetConfig), ctypes.POINTER(c_i), c_i, ctypes.POINTER(c_i)]),
     "dh_dbg_gemm_lnfold": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_l, c_p]),
     "dh_dbg_gemm_glu": (c_i, [c_i, c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "dh_dbg_gemm_family": (c_i, [c_i]),

@@ -52,9 +52,10 @@ extern "C" int dh_dbg_gemm(int dtype, const void* A, long lda, const void* W, in
 // GEMM (dense or 3x3 convolution) followed by the GroupNorm(+SiLU) of its output, the way the engine's forward runs the pair: the
 // GroupNorm's slice statistics come from the GEMM launch when it can leave them (split-K reduce, or -- round 6 -- the epilogue of an
 // unsplit k_gemm_dma launch: gemm.hip gn_epi) and from the statistics kernel otherwise.  *have_out = what the GEMM reported
-// (0 = statistics kernel, 1 = reduce, > 1 = slices left by the epilogue); stats [B * G][2] = (mean, rstd).
-extern "C" int dh_dbg_gemm_groupnorm(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin, int Win,
-                                     int Cin, const float* bias, void* C, float* partial, size_t partial_elems, int HW, int G,
+// (0 = statistics kernel, 1 = reduce, > 1 = slices left by the epilogue); stats [B * G][2] = (mean, rstd).  R (row pitch ldr) is
+// the residual added before rounding, or NULL; it may be C itself (in place, as the engine's resnet shortcut adds run).
+extern "C" int dh_dbg_gemm_groupnorm_res(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin, int Win,
+                                     int Cin, const float* bias, const void* R, long ldr, void* C, float* partial, size_t partial_elems, int HW, int G,
                                      const float* gamma, const float* beta, float eps, int silu, void* Y, float* stats, float* scratch,
                                      int* have_out, void* stream) {
   DH_REQUIRE(A && W && C && Y && stats && scratch && gamma && beta && K % 64 == 0 && N % 64 == 0 && HW > 0 && M % HW == 0, "bad arguments");
@@ -69,7 +70,7 @@ extern "C" int dh_dbg_gemm_groupnorm(int dtype, const void* A, long lda, const v
   launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream, mode != 0 ? Cin : 0);
   GemmArgs g;
   g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = mode; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
-  g.Hout = Hin; g.Wout = Win; g.stride = 1; g.up = 0; g.bias = bias; g.C = C; g.ldc = N;
+  g.Hout = Hin; g.Wout = Win; g.stride = 1; g.up = 0; g.bias = bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = N;
   g.partial = partial; g.partial_elems = partial_elems;
   int have = 0;
   g.gn_part = scratch; g.gn_HW = HW; g.gn_G = G; g.gn_done = &have;
@@ -79,11 +80,20 @@ extern "C" int dh_dbg_gemm_groupnorm(int dtype, const void* A, long lda, const v
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
+// ... without a residual (the hook's original signature, kept for its existing callers)
+extern "C" int dh_dbg_gemm_groupnorm(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin, int Win,
+                                     int Cin, const float* bias, void* C, float* partial, size_t partial_elems, int HW, int G,
+                                     const float* gamma, const float* beta, float eps, int silu, void* Y, float* stats, float* scratch,
+                                     int* have_out, void* stream) {
+  return dh_dbg_gemm_groupnorm_res(dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, bias, nullptr, N, C, partial, partial_elems, HW, G,
+                                   gamma, beta, eps, silu, Y, stats, scratch, have_out, stream);
+}
 // ... and the backward twin: C = A W^T is dy of GroupNorm(x) (+ SiLU) with saved (mean, rstd) in `stats`; the GEMM (its split-K
 // reduce, or its own epilogue: *have_out > 1 = that many slices per group) leaves the backward slice statistics in `scratch` and
-// the GroupNorm backward writes dx.  (engine: every input-gradient GEMM in front of a GroupNorm backward)
-extern "C" int dh_dbg_gemm_groupnorm_bwd(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
-                                         int Win, int Cin, void* C, float* partial, size_t partial_elems, int HW, int G, const void* x,
+// the GroupNorm backward writes dx.  (engine: every input-gradient GEMM in front of a GroupNorm backward; R = C, pitch ldr, when the
+// gradient already holds a contribution it accumulates onto -- NULL otherwise)
+extern "C" int dh_dbg_gemm_groupnorm_bwd_res(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
+                                         int Win, int Cin, const void* R, long ldr, void* C, float* partial, size_t partial_elems, int HW, int G, const void* x,
                                          const float* gamma, const float* beta, const float* stats, int silu, void* dx,
                                          float* scratch, int* have_out, void* stream) {
   DH_REQUIRE(A && W && C && x && dx && stats && scratch && gamma && beta && K % 64 == 0 && N % 64 == 0 && HW > 0 && M % HW == 0, "bad arguments");
@@ -98,7 +108,7 @@ extern "C" int dh_dbg_gemm_groupnorm_bwd(int dtype, const void* A, long lda, con
   launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream, mode != 0 ? Cin : 0);
   GemmArgs g;
   g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = mode; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
-  g.Hout = Hin; g.Wout = Win; g.stride = 1; g.up = 0; g.C = C; g.ldc = N;
+  g.Hout = Hin; g.Wout = Win; g.stride = 1; g.up = 0; g.R = R; g.ldr = ldr; g.C = C; g.ldc = N;
   g.partial = partial; g.partial_elems = partial_elems;
   int have = 0;
   g.gnb_x = x; g.gnb_ldx = N; g.gnb_gamma = gamma; g.gnb_beta = beta; g.gnb_stats = stats; g.gnb_silu = silu;
@@ -106,6 +116,28 @@ extern "C" int dh_dbg_gemm_groupnorm_bwd(int dtype, const void* A, long lda, con
   launch_gemm(dtype, g, (hipStream_t)stream);
   launch_groupnorm_bwd(dtype, x, C, gamma, beta, stats, dx, scratch, M / HW, HW, N, G, silu, 0, (hipStream_t)stream, have, GnBwdSplit());
   if (have_out) *have_out = have;
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// ... without a residual (the hook's original signature, kept for its existing callers)
+extern "C" int dh_dbg_gemm_groupnorm_bwd(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
+                                         int Win, int Cin, void* C, float* partial, size_t partial_elems, int HW, int G, const void* x,
+                                         const float* gamma, const float* beta, const float* stats, int silu, void* dx,
+                                         float* scratch, int* have_out, void* stream) {
+  return dh_dbg_gemm_groupnorm_bwd_res(dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, nullptr, N, C, partial, partial_elems, HW, G, x,
+                                       gamma, beta, stats, silu, dx, scratch, have_out, stream);
+}
+// channel concatenation a | b followed by the GroupNorm(+SiLU) of the result, the way the engine's forward runs OP_CONCAT in front
+// of a GroupNorm: k_concat_gn writes out [B * HW][Ca + Cb] and the slice statistics, the apply kernel merges them.
+// stats [B * G][2] = (mean, rstd); scratch holds the slices.
+extern "C" int dh_dbg_concat_groupnorm(int dtype, const void* a, int Ca, const void* b, int Cb, void* out, int B, int HW, int G,
+                                       const float* gamma, const float* beta, float eps, int silu, void* Y, float* stats,
+                                       float* scratch, void* stream) {
+  DH_REQUIRE(a && b && out && Y && stats && scratch && gamma && beta && B > 0 && HW > 0 && G > 0, "bad arguments");
+  DH_REQUIRE(Ca % 8 == 0 && Cb % 8 == 0 && (Ca + Cb) % G == 0 && (GN_GB * ((Ca + Cb) / G)) % 8 == 0 && GN_GB * ((Ca + Cb) / G) <= 2048,
+             "shape the fused concatenation does not take");
+  launch_concat_gn(dtype, a, Ca, b, Cb, out, scratch, B, HW, G, (hipStream_t)stream);
+  launch_groupnorm_fwd(dtype, out, gamma, beta, Y, stats, scratch, B, HW, Ca + Cb, G, eps, silu, (hipStream_t)stream, 1);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

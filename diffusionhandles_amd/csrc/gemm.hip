@@ -41,6 +41,11 @@ struct GemmProf {
 static GemmProf g_prof;
 static int g_buf_stage = 1;     // test hook (dh_dbg_gemm_stage): 0 = the address form of rounds 1-5 everywhere
 static int g_pp_force = 0;      // test hook (dh_dbg_gemm_family): 0 = policy, 1 = never k_gemm_pp, 2 = k_gemm_pp whenever it can carry the launch
+// what the last gemm_dispatch launched (test hook dh_dbg_gemm_last_tile): written after each decision, never read by the dispatch
+struct GemmTileReport {
+  int bm, bn, kg, stages, mw, splits, pp, gn_epi, reduce_gn;
+};
+static thread_local GemmTileReport g_last_tile;
 #ifdef DH_TUNING
 static unsigned long long* g_gemm_ts = nullptr;      // device buffer of 8 stamps (dh_dbg_gemm_timeline)
 #endif
@@ -220,6 +225,14 @@ template <> __device__ __forceinline__ void frag_sums<bf16>(const uint4& f_in, f
 // offset, rows past M and taps outside the image = an out-of-range offset that the hardware turns into zeros (no zero page, no
 // 64-bit address arithmetic, no select pair, no M0 save / restore per piece).  Dense and stride-1 3x3 operands; the generic
 // gather (stride 2, up-sampled source, transposed stride 2) keeps the address form.
+// Which k_gemm_dma tiles leave GroupNorm slice statistics in their epilogue: the forward form (gn_epi 1: two wave columns, at most
+// 128 columns, the plain epilogue) and the backward form (gn_epi 2: 64-column tiles of at most 128 rows, one wave group).  The
+// dispatch asks for a form only where these hold, and the kernel compiles the form only where they hold: one predicate for both.
+constexpr bool gn_epi_fwd_tile(int BN, int GLU, bool LNF) { return GLU == 0 && !LNF && BN % 64 == 0 && BN <= 128; }
+constexpr bool gn_epi_bwd_tile(int BM, int BN, int WG, int GLU, bool LNF) {
+  return gn_epi_fwd_tile(BN, GLU, LNF) && BN == 64 && BM <= 128 && WG == 1;
+}
+
 template <class T, int BM, int BN, int ST, int MODE, int ABL = 0, int WG = 1, int KG = 1, int MW = 1, bool LNF = false, int GLU = 0, bool BUF = false>   // ABL: diagnostics (1 = no LDS reads/MFMA, 2 = no DMA in the loop)
 __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) {
   static_assert(!BUF || MODE != GM_GENERIC, "the generic gather stages through addresses");
@@ -480,7 +493,8 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
   // input tile x rides under the K loop in the residual's prefetch registers (the dispatch takes the form only when there is no
   // residual), and thread n of the first wave fetches (gamma, beta, mean, rstd) of tile column n for the table the epilogue
   // builds in LDS -- four registers across the loop instead of 64
-  constexpr bool GNB = WNS == 2 && GLU == 0 && BN == 64 && WG == 1 && PRE && !LNF;
+  constexpr bool GNB = gn_epi_bwd_tile(BM, BN, WG, GLU, LNF);
+  static_assert(!GNB || (PRE && WNS == 2), "the backward form carries the GroupNorm input tile in the residual's prefetch registers");
   const bool gnb = GNB && p.gn_epi == 2 && p.splits == 1;
   const bool pre_x = gnb && (KG == 1 || kg == 0);
   float4 gnb_col = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -782,8 +796,16 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
   // order, and the tile leaves (n, mean, M2) of every group fragment it covers as "slice" 2 * row_tile + part of the
   // [b][g][3][S] layout k_gn_apply merges (part 1 = the tail of a group whose first channel lies in the previous column tile;
   // a group wholly inside the tile writes an empty part 1).
-  constexpr bool GNE = WNS == 2 && GLU == 0 && BN <= 128 && BN % 64 == 0;
+  // The forward sums are pivot-shifted: every column of a wave is summed relative to its value in the wave's first row (lane 0 /
+  // lane 32 of row block 0: broadcast by readlane for that row block, kept for the others in a per-wave table at the start of the
+  // idle rings -- 32 more registers per lane would spill the 256x128 tile), so a group mean of many standard deviations, carried
+  // by the bias or by the inputs alike, does not cancel digits in sum(x^2) - sum(x)^2 / n; the (wave, column) pieces are merged
+  // as (mean, M2) pairs (Chan) in gn_finish.
+  constexpr bool GNE = gn_epi_fwd_tile(BN, GLU, LNF);
   const bool gn_epi = GNE && p.splits == 1 && (p.gn_epi == 1 || (GNB && p.gn_epi == 2));     // (the dispatch asks for form 2 only on GNB tiles)
+  static_assert(!GNE || NWV * CPW * 4 <= KG * ST * STAGE - 4096, "the pivot table lies below the column-sum scratch");
+  float* gpt = reinterpret_cast<float*>(smem_all) + wave * CPW;      // this wave's column pivots
+  if (GNE && gn_epi && !(GNB && gnb)) __syncthreads();             // every wave is done with the rings / the merge buffers
   float gsa[GNE ? TN : 1][16], gsq[GNE ? TN : 1][16];
   if (GNE) {
 #pragma unroll
@@ -791,12 +813,27 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
 #pragma unroll
       for (int r = 0; r < 16; ++r) { gsa[j][r] = 0.f; gsq[j][r] = 0.f; }
   }
-  auto gn_acc = [&](int j, int g, uint2 packed) {
+  auto gn_acc = [&](int i, int j, int g, uint2 packed) {
     if constexpr (GNE) {
       typedef T T4g __attribute__((ext_vector_type(4)));
       const T4g ov = __builtin_bit_cast(T4g, packed);
+      float v[4], pv[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) { const float v = to_f32<T>(ov[c]); gsa[j][4 * g + c] += v; gsq[j][4 * g + c] += v * v; }
+      for (int c = 0; c < 4; ++c) v[c] = to_f32<T>(ov[c]);
+      float4* pt = reinterpret_cast<float4*>(gpt + j * 32 + 8 * g + 4 * hi);
+      if (i == 0) {        // (every row of the tile is valid when the dispatch asks for the statistics: the wave is whole here)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int p0 = __builtin_amdgcn_readlane(__float_as_int(v[c]), 0), p1 = __builtin_amdgcn_readlane(__float_as_int(v[c]), 32);
+          pv[c] = __int_as_float(hi ? p1 : p0);
+        }
+        if (ln == 0) *pt = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+        const float4 t = *pt;
+        pv[0] = t.x; pv[1] = t.y; pv[2] = t.z; pv[3] = t.w;
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) { const float d = v[c] - pv[c]; gsa[j][4 * g + c] += d; gsq[j][4 * g + c] += d * d; }
     }
   };
   // BACKWARD flavour (gnb): the tile is dy of the GroupNorm (+ SiLU) whose input tile sits in rpre; the per-element terms are
@@ -845,7 +882,10 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
           { const LanePair pq = row_pair(q); q = pq.a + pq.b; }
           if (ln == 0) {
             const int col = wn * CPW + j * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
-            *reinterpret_cast<float2*>(cs + (wm * BN + col) * 2) = make_float2(a, q);
+            // forward: (mean, M2) of the column's RPW rows in this wave; backward: the plain sums
+            const float2 v2 = (GNB && gnb) ? make_float2(a, q) : make_float2(gpt[j * 32 + 8 * (r >> 2) + 4 * hi + (r & 3)] + a * (1.f / RPW),
+                                                                             q - a * a * (1.f / RPW));
+            *reinterpret_cast<float2*>(cs + (wm * BN + col) * 2) = v2;
           }
         }
       __syncthreads();
@@ -855,23 +895,45 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
       if (tid < (BN / 8) * 8 && g < G && g * cpg < n0 + BN) {
         const int lo = g * cpg, hi_c = lo + cpg;
         const int c_lo = (lo > n0 ? lo : n0) - n0, c_hi = (hi_c < n0 + BN ? hi_c : n0 + BN) - n0;
-        float a = 0.f, q = 0.f;
-        for (int c = c_lo + sub; c < c_hi; c += 8) {
+        const int b = m0 / p.gn_HW, rt = (m0 - b * p.gn_HW) / BM;
+        const int part = lo < n0 ? 1 : 0;
+        if (GNB && gnb) {
+          float a = 0.f, q = 0.f;
+          for (int c = c_lo + sub; c < c_hi; c += 8) {
 #pragma unroll
-          for (int w2 = 0; w2 < WMS; ++w2) { const float2 v = *reinterpret_cast<const float2*>(cs + (w2 * BN + c) * 2); a += v.x; q += v.y; }
-        }
-        a = oct_sum(a); q = oct_sum(q);
-        if (sub == 0) {
-          const int b = m0 / p.gn_HW, rt = (m0 - b * p.gn_HW) / BM;
-          const int part = lo < n0 ? 1 : 0;
-          if (GNB && gnb) {
+            for (int w2 = 0; w2 < WMS; ++w2) { const float2 v = *reinterpret_cast<const float2*>(cs + (w2 * BN + c) * 2); a += v.x; q += v.y; }
+          }
+          a = oct_sum(a); q = oct_sum(q);
+          if (sub == 0) {
             float2* o = reinterpret_cast<float2*>(p.gn_part) + (size_t)(b * G + g) * Sx + 2 * rt + part;
             o[0] = make_float2(a, q);
             if (part == 0 && hi_c <= n0 + BN) o[1] = make_float2(0.f, 0.f);
-          } else {
-            const float n = (float)BM * (float)(c_hi - c_lo);
+          }
+        } else {
+          // Chan over the WMS x (c_hi - c_lo) column pieces of RPW rows each: the mean relative to the first piece, then
+          // M2 = sum M2_c + RPW sum (mean_c - mean)^2
+          const float ref = cs[c_lo * 2];
+          float dm = 0.f;
+          for (int c = c_lo + sub; c < c_hi; c += 8) {
+#pragma unroll
+            for (int w2 = 0; w2 < WMS; ++w2) dm += cs[(w2 * BN + c) * 2] - ref;
+          }
+          dm = oct_sum(dm);
+          const float pieces = (float)WMS * (float)(c_hi - c_lo);
+          const float mean = ref + dm / pieces;
+          float m2 = 0.f;
+          for (int c = c_lo + sub; c < c_hi; c += 8) {
+#pragma unroll
+            for (int w2 = 0; w2 < WMS; ++w2) {
+              const float2 v = *reinterpret_cast<const float2*>(cs + (w2 * BN + c) * 2);
+              const float d = v.x - mean;
+              m2 += v.y + (float)RPW * d * d;
+            }
+          }
+          m2 = oct_sum(m2);
+          if (sub == 0) {
             float* o = p.gn_part + ((size_t)(b * G + g) * 3) * Sx + 2 * rt + part;
-            o[0] = n; o[Sx] = a / n; o[2 * Sx] = q - a * a / n;
+            o[0] = (float)RPW * pieces; o[Sx] = mean; o[2 * Sx] = m2;
             if (part == 0 && hi_c <= n0 + BN) { o[1] = 0.f; o[Sx + 1] = 0.f; o[2 * Sx + 1] = 0.f; }      // the whole group lies in this tile
           }
         }
@@ -909,7 +971,7 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
           T4 o;
           o[0] = from_f32<T>(v0); o[1] = from_f32<T>(v1); o[2] = from_f32<T>(v2); o[3] = from_f32<T>(v3);
           w[g] = __builtin_bit_cast(uint2, o);
-          if (gn_epi) { if (GNB && gnb) gnb_acc(g, w[g], rpre[i][j][g]); else gn_acc(j, g, w[g]); }
+          if (gn_epi) { if (GNB && gnb) gnb_acc(g, w[g], rpre[i][j][g]); else gn_acc(i, j, g, w[g]); }
         }
         const uint4 ca = half_exchange(w[0], w[1]), cb = half_exchange(w[2], w[3]);
         *reinterpret_cast<uint4*>(orow + j * 32) = ca;
@@ -941,7 +1003,7 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
         for (int g = 0; g < 4; ++g) {
           w[g] = epilogue_pack<T>(p, m, nb + 8 * g + 4 * hi, acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2],
                                   acc[i][j][4 * g + 3], pre_r, rpre[i][j][g], pre_b, bpre[PRE_B ? j : 0][g]);
-          if (gn_epi) gn_acc(j, g, w[g]);
+          if (gn_epi) gn_acc(i, j, g, w[g]);
         }
         const uint4 ca = half_exchange(w[0], w[1]), cb = half_exchange(w[2], w[3]);
         T* out = reinterpret_cast<T*>(p.C) + (size_t)m * p.ldc + nb + 8 * hi;
@@ -1027,6 +1089,7 @@ __global__ void k_splitk_reduce(const GemmK p) {
 template <class T, bool BWD>
 __global__ void __launch_bounds__(256) k_splitk_reduce_gn(const GemmK p) {
   __shared__ float sm_red[4][2 * GN_GB];
+  __shared__ float sm_piv[GN_GB];
   const int HW = p.gn_HW, G = p.gn_G, S = p.gn_S;
   const int s = blockIdx.x, g0 = blockIdx.y * GN_GB, b = blockIdx.z, cpg = div_small(p.N, rcp_fast(G));
   const int W = GN_GB * cpg, nch = W >> 3;
@@ -1034,28 +1097,29 @@ __global__ void __launch_bounds__(256) k_splitk_reduce_gn(const GemmK p) {
   const int RP = div_small((int)blockDim.x, inv_nch);
   const int r0 = div_small(HW * s, inv_S), r1 = div_small(HW * (s + 1), inv_S);
   const size_t slab = (size_t)p.M * p.N;
-  // sums are NOT pivot-shifted here (a pivot would cost a dependent pass over the slabs before the main one): conv /
-  // linear outputs are zero-centred to within a few standard deviations, where E[x^2] - E[x]^2 over the <= 10^4
-  // elements of a slice is accurate to ~1e-6 relative in f32; slices are merged with Chan's formula in the apply kernel
+  // forward sums are pivot-shifted like k_gn_partial's, by the group's first element of the slice (row r0): the threads of
+  // row r0 publish it through LDS after their first row, so a group mean of many standard deviations (from the bias or from
+  // the inputs) does not cancel digits in sum(x^2) - sum(x)^2 / n; slices are merged with Chan's formula in the apply kernel
   const int rr = div_small((int)threadIdx.x, inv_nch), ch = threadIdx.x - rr * nch;
   float ga[GN_GB], gq[GN_GB];
 #pragma unroll
   for (int gl = 0; gl < GN_GB; ++gl) { ga[gl] = 0.f; gq[gl] = 0.f; }
   const int n = g0 * cpg + ch * 8;
-  if (rr < RP && n < p.N) {
-    int gi[8];
-    float av[8], qv[8], pv[8];
+  const bool live = rr < RP && n < p.N;
+  int gi[8];
+  float av[8], qv[8], pv[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      gi[i] = div_small(ch * 8 + i, inv_cpg);
-      av[i] = 0.f; qv[i] = 0.f; pv[i] = 0.f;
-    }
-    float bias8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < 8; ++i) {
+    gi[i] = div_small(ch * 8 + i, inv_cpg);
+    av[i] = 0.f; qv[i] = 0.f; pv[i] = 0.f;
+  }
+  float bias8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float gm[8], bt[8], mu[8], rs[8];
+  if (live) {
     if (p.bias) {
       *reinterpret_cast<float4*>(bias8) = *reinterpret_cast<const float4*>(p.bias + n);
       *reinterpret_cast<float4*>(bias8 + 4) = *reinterpret_cast<const float4*>(p.bias + n + 4);
     }
-    float gm[8], bt[8], mu[8], rs[8];
     if (BWD) {           // output = dy of a GroupNorm: accumulate sum d and sum d * xhat (d = dy * gamma * act')
       *reinterpret_cast<float4*>(gm) = *reinterpret_cast<const float4*>(p.gnb_gamma + n);
       *reinterpret_cast<float4*>(gm + 4) = *reinterpret_cast<const float4*>(p.gnb_gamma + n + 4);
@@ -1067,72 +1131,97 @@ __global__ void __launch_bounds__(256) k_splitk_reduce_gn(const GemmK p) {
         mu[i] = p.gnb_stats[2 * sg]; rs[i] = p.gnb_stats[2 * sg + 1];
       }
     }
-    for (int r = r0 + rr; r < r1; r += RP) {
-      const int m = b * HW + r;
-      float v[8];
+  }
+  // one row of the thread's 8 channels: reduce the slabs, apply the epilogue, store the 16-bit result; the forward returns the
+  // rounded values in f, the backward accumulates its sums
+  auto row = [&](int r, float* f) {
+    const int m = b * HW + r;
+    float v[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = 0.f;
-      const float* pp = p.partial + (size_t)m * p.N + n;
-      int z = 0;
-      for (; z + 4 <= p.splits; z += 4) {             // four slabs in flight; added in slab order
-        float4 x0[4], x1[4];
+    for (int i = 0; i < 8; ++i) v[i] = 0.f;
+    const float* pp = p.partial + (size_t)m * p.N + n;
+    int z = 0;
+    for (; z + 4 <= p.splits; z += 4) {             // four slabs in flight; added in slab order
+      float4 x0[4], x1[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          x0[j] = *reinterpret_cast<const float4*>(pp + (size_t)(z + j) * slab);
-          x1[j] = *reinterpret_cast<const float4*>(pp + (size_t)(z + j) * slab + 4);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[0] += x0[j].x; v[1] += x0[j].y; v[2] += x0[j].z; v[3] += x0[j].w;
-          v[4] += x1[j].x; v[5] += x1[j].y; v[6] += x1[j].z; v[7] += x1[j].w;
-        }
-      }
-      for (; z < p.splits; ++z) {
-        const float4 x0 = *reinterpret_cast<const float4*>(pp + (size_t)z * slab);
-        const float4 x1 = *reinterpret_cast<const float4*>(pp + (size_t)z * slab + 4);
-        v[0] += x0.x; v[1] += x0.y; v[2] += x0.z; v[3] += x0.w;
-        v[4] += x1.x; v[5] += x1.y; v[6] += x1.z; v[7] += x1.w;
+      for (int j = 0; j < 4; ++j) {
+        x0[j] = *reinterpret_cast<const float4*>(pp + (size_t)(z + j) * slab);
+        x1[j] = *reinterpret_cast<const float4*>(pp + (size_t)(z + j) * slab + 4);
       }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] += bias8[i];
-      if (p.rowvec) {
-        const float* rv = p.rowvec + (size_t)div_small(m, p.inv_rows_per_batch) * p.rowvec_ld + n;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] += rv[i];
+      for (int j = 0; j < 4; ++j) {
+        v[0] += x0[j].x; v[1] += x0[j].y; v[2] += x0[j].z; v[3] += x0[j].w;
+        v[4] += x1[j].x; v[5] += x1[j].y; v[6] += x1[j].z; v[7] += x1[j].w;
       }
-      if (p.act_silu) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = v[i] / (1.f + __expf(-v[i]));
-      }
-      if (p.R) {
-        const uint4 raw = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.R) + (size_t)m * p.ldr + n);
-        const T* rv = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] += to_f32<T>(rv[i]);
-      }
-      T o[8];
-      if (!BWD) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          o[i] = from_f32<T>(v[i]);
-          const float d = to_f32<T>(o[i]) - pv[i];
-          av[i] += d; qv[i] += d * d;
-        }
-      } else {
-        const uint4 rawx = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.gnb_x) + (size_t)m * p.gnb_ldx + n);
-        const T* xv = reinterpret_cast<const T*>(&rawx);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          o[i] = from_f32<T>(v[i]);
-          const float xh = (to_f32<T>(xv[i]) - mu[i]) * rs[i];
-          float d = to_f32<T>(o[i]);
-          if (p.gnb_silu) d *= silu_grad(xh * gm[i] + bt[i]);
-          d *= gm[i];
-          av[i] += d; qv[i] += d * xh;
-        }
-      }
-      *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.C) + (size_t)m * p.ldc + n) = *reinterpret_cast<uint4*>(o);
     }
+    for (; z < p.splits; ++z) {
+      const float4 x0 = *reinterpret_cast<const float4*>(pp + (size_t)z * slab);
+      const float4 x1 = *reinterpret_cast<const float4*>(pp + (size_t)z * slab + 4);
+      v[0] += x0.x; v[1] += x0.y; v[2] += x0.z; v[3] += x0.w;
+      v[4] += x1.x; v[5] += x1.y; v[6] += x1.z; v[7] += x1.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] += bias8[i];
+    if (p.rowvec) {
+      const float* rv = p.rowvec + (size_t)div_small(m, p.inv_rows_per_batch) * p.rowvec_ld + n;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] += rv[i];
+    }
+    if (p.act_silu) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = v[i] / (1.f + __expf(-v[i]));
+    }
+    if (p.R) {
+      const uint4 raw = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.R) + (size_t)m * p.ldr + n);
+      const T* rv = reinterpret_cast<const T*>(&raw);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] += to_f32<T>(rv[i]);
+    }
+    T o[8];
+    if (!BWD) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { o[i] = from_f32<T>(v[i]); f[i] = to_f32<T>(o[i]); }
+    } else {
+      const uint4 rawx = *reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(p.gnb_x) + (size_t)m * p.gnb_ldx + n);
+      const T* xv = reinterpret_cast<const T*>(&rawx);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        o[i] = from_f32<T>(v[i]);
+        const float xh = (to_f32<T>(xv[i]) - mu[i]) * rs[i];
+        float d = to_f32<T>(o[i]);
+        if (p.gnb_silu) d *= silu_grad(xh * gm[i] + bt[i]);
+        d *= gm[i];
+        av[i] += d; qv[i] += d * xh;
+      }
+    }
+    *reinterpret_cast<uint4*>(reinterpret_cast<T*>(p.C) + (size_t)m * p.ldc + n) = *reinterpret_cast<uint4*>(o);
+  };
+  auto acc = [&](const float* f) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const float d = f[i] - pv[i]; av[i] += d; qv[i] += d * d; }
+  };
+  float f[8];
+  if (BWD) {
+    if (live)
+      for (int r = r0 + rr; r < r1; r += RP) row(r, f);
+  } else {
+    // the first row of every thread, then the pivots: row r0 of each group's first channel (a slice has >= 4 rows)
+    const bool first = live && r0 + rr < r1;
+    if (first) row(r0 + rr, f);
+    if (first && rr == 0) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (ch * 8 + i == gi[i] * cpg) sm_piv[gi[i]] = f[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pv[i] = g0 + gi[i] < G ? sm_piv[gi[i]] : 0.f;
+    if (first) {
+      acc(f);
+      for (int r = r0 + rr + RP; r < r1; r += RP) { row(r, f); acc(f); }
+    }
+  }
+  if (live) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1158,7 +1247,7 @@ __global__ void __launch_bounds__(256) k_splitk_reduce_gn(const GemmK p) {
     } else {
       const float cnt = (float)(r1 - r0) * (float)cpg;
       float* o = p.gn_part + ((size_t)(b * G + g) * 3) * S + s;
-      o[0] = cnt; o[S] = sa / cnt; o[2 * S] = sq - sa * sa / cnt;
+      o[0] = cnt; o[S] = sm_piv[gl] + sa / cnt; o[2 * S] = sq - sa * sa / cnt;
     }
   }
 }
@@ -1195,6 +1284,7 @@ static void launch_tile_b(int gm, bool lnf, dim3 grid, hipStream_t st, const Gem
 // k.pp_a_bytes != 0: the operands fit buffer descriptors (gemm_dispatch) -- dense and stride-1 3x3 launches stage through them
 template <class T, int BM, int BN, int ST, int WG, int KG, int MW>
 static void launch_tile(int gm, bool lnf, dim3 grid, hipStream_t st, const GemmK& k, int glu = 0) {
+  g_last_tile.bm = BM; g_last_tile.bn = BN; g_last_tile.kg = KG; g_last_tile.stages = ST; g_last_tile.mw = MW;
   if (k.pp_a_bytes != 0 && gm != GM_GENERIC) launch_tile_b<T, BM, BN, ST, WG, KG, MW, true>(gm, lnf, grid, st, k, glu);
   else launch_tile_b<T, BM, BN, ST, WG, KG, MW, false>(gm, lnf, grid, st, k, glu);
 }
@@ -1225,6 +1315,7 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
   DH_KNOB(kWnt, "DH_W_NT", 0);                      // non-temporal weight DMA for GEMMs of at most this many row tiles (0 = never)
 #endif
   const bool lnf = k.ln_s != nullptr;
+  g_last_tile = GemmTileReport{};
   int BM = 128, BN = (k.N % 128 == 0) ? 128 : 64;
   const int ktiles = k.K / BK;
   // grids that fill the chip with 256- / 128-row tiles and carry the plain epilogue: the eight-wave ping-pong kernel (gemm_pp.hip)
@@ -1305,17 +1396,17 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
   // only; tiles of whole images' rows, groups no wider than a column tile, at most 64 "slices" = 2 per row tile for the merge
   // in k_gn_apply).  *gn_done then carries the slice count (> 1) instead of 1.
   k.gn_epi = 0; k.gn_cpg = 0;
-  if ((g_buf_stage & 4) == 0 && splits == 1 && !use_pp && !t160 && !n320 && !glu && k.gn_part && !k.gnb_x && gn_done && k.gn_G > 0 && k.gn_HW > 0 && k.C &&
-      k.wide_store && k.M % k.gn_HW == 0 && k.gn_HW % BM == 0 && k.N % k.gn_G == 0 && k.N % BN == 0 && BN % 64 == 0 && BN <= 128) {
+  if ((g_buf_stage & 4) == 0 && splits == 1 && !use_pp && gn_epi_fwd_tile(BN, glu, lnf) && k.gn_part && !k.gnb_x && gn_done && k.gn_G > 0 &&
+      k.gn_HW > 0 && k.C && k.wide_store && k.M % k.gn_HW == 0 && k.gn_HW % BM == 0 && k.N % k.gn_G == 0 && k.N % BN == 0) {
     const int cpg = k.N / k.gn_G, sx = 2 * (k.gn_HW / BM);
     if (cpg >= 8 && cpg <= BN && sx <= 64) { k.gn_epi = 1; k.gn_cpg = cpg; k.gn_S = sx; }
   }
   // ... and the BACKWARD slice statistics (sum d, sum d * xhat) when the output is dy of a GroupNorm: 64-column tiles of up to 128
   // rows, no bias / residual / per-image vector (an input-gradient GEMM has none; the residual's prefetch registers carry the
   // GroupNorm's input tile).  *gn_done = the slice count, as above.
-  if ((g_buf_stage & 8) == 0 && splits == 1 && !use_pp && !glu && !lnf && k.gn_part && k.gnb_x && gn_done && k.gn_G > 0 && k.gn_HW > 0 && k.C &&
-      k.wide_store && k.pre_r && !k.R && !k.bias && !k.rowvec && !k.act_silu && k.M % k.gn_HW == 0 && k.gn_HW % BM == 0 && k.N % k.gn_G == 0 &&
-      k.N % BN == 0 && BN == 64 && BM <= 128 && (((size_t)k.gnb_x | (size_t)(k.gnb_ldx * 2)) & 7) == 0) {
+  if ((g_buf_stage & 8) == 0 && splits == 1 && !use_pp && gn_epi_bwd_tile(BM, BN, 1, glu, lnf) && k.gn_part && k.gnb_x && gn_done && k.gn_G > 0 &&
+      k.gn_HW > 0 && k.C && k.wide_store && k.pre_r && !k.R && !k.bias && !k.rowvec && !k.act_silu && k.M % k.gn_HW == 0 && k.gn_HW % BM == 0 &&
+      k.N % k.gn_G == 0 && k.N % BN == 0 && (((size_t)k.gnb_x | (size_t)(k.gnb_ldx * 2)) & 7) == 0) {
     const int cpg = k.N / k.gn_G, sx = 2 * (k.gn_HW / BM);
     if (cpg >= 8 && cpg <= BN && sx <= 64) { k.gn_epi = 2; k.gn_cpg = cpg; k.gn_S = sx; }
   }
@@ -1389,7 +1480,7 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
   else if (force_tile == 7) launch_tile<T, 128, 160, 4, 1, 1, 1>(gm, false, grid, st, k);
   else
 #endif
-  if (use_pp) { pp.splits = splits; launch_gemm_pp(dtype, k, pp, st, g_prof.e0, g_prof.e1); }
+  if (use_pp) { pp.splits = splits; g_last_tile.bm = pp.bm; g_last_tile.bn = pp.bn; launch_gemm_pp(dtype, k, pp, st, g_prof.e0, g_prof.e1); }
   else if (t160) launch_tile<T, 128, 160, 4, 1, 1, 1>(gm, false, grid, st, k);
   else if (mw2) launch_tile<T, 256, 128, 3, 1, 1, 2>(gm, lnf, grid, st, k, glu);
   else if (BM == 128 && BN == 128 && (glu || (kMw128 && tiles_per_split >= kMw128))) launch_tile<T, 128, 128, 4, 1, 1, 2>(gm, lnf, grid, st, k, glu);
@@ -1413,6 +1504,7 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
   else if (BN == 128) launch_tile<T, 128, 128, 4, 1, 1, 1>(gm, lnf, grid, st, k);
   else launch_tile<T, 128, 64, 5, 1, 1, 1>(gm, lnf, grid, st, k);
   g_prof.e0 = g_prof.e1 = nullptr;
+  g_last_tile.splits = splits; g_last_tile.pp = use_pp ? 1 : 0; g_last_tile.gn_epi = k.gn_epi;
   if (k.gn_epi) *gn_done = k.gn_S;
   if (splits > 1) {
     if (k.gn_part && k.gn_G > 0 && k.gn_HW > 0 && k.N % k.gn_G == 0 && (GN_GB * (k.N / k.gn_G)) % 8 == 0 &&
@@ -1420,6 +1512,7 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
       k.gn_S = gn_slices(k.gn_HW, k.M / k.gn_HW);
       if (k.gnb_x) hipLaunchKernelGGL((k_splitk_reduce_gn<T, true>), dim3(k.gn_S, cdiv(k.gn_G, GN_GB), k.M / k.gn_HW), dim3(256), 0, st, k);
       else hipLaunchKernelGGL((k_splitk_reduce_gn<T, false>), dim3(k.gn_S, cdiv(k.gn_G, GN_GB), k.M / k.gn_HW), dim3(256), 0, st, k);
+      g_last_tile.reduce_gn = 1;
       if (gn_done) *gn_done = 1;
     } else if (k.lnb_x && lnb_done && !k.bias && !k.rowvec && !k.R && !k.act_silu && k.N % 8 == 0 && k.ldc == k.N) {
       // the rows are the dy of a LayerNorm: reduce + LayerNorm backward in one launch (dy itself is not written)
@@ -1476,6 +1569,16 @@ extern "C" int dh_dbg_gemm_family(int force) {
 // test hook: 1 = dense / stride-1 3x3 operands of k_gemm_dma stage through buffer descriptors (shipped), 0 = through addresses
 extern "C" int dh_dbg_gemm_stage(int buf) {
   dh::g_buf_stage = buf;          // bit 0: buffer staging; bit 2 (value 4): NO GroupNorm forward statistics in the GEMM epilogue; bit 3 (8): NO backward ones
+  return DH_OK;
+}
+
+// test hook: the tile the last GEMM launch ran -- out[9] = BM, BN, K groups, stages, wave multiplier, splits, k_gemm_pp (0 / 1),
+// gn_epi (0 none, 1 forward, 2 backward GroupNorm statistics in the epilogue), the split-K reduce left GroupNorm statistics (0 / 1)
+extern "C" int dh_dbg_gemm_last_tile(int* out) {
+  DH_REQUIRE(out != nullptr, "null pointer");
+  const dh::GemmTileReport& r = dh::g_last_tile;
+  const int v[9] = {r.bm, r.bn, r.kg, r.stages, r.mw, r.splits, r.pp, r.gn_epi, r.reduce_gn};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
   return DH_OK;
 }
 

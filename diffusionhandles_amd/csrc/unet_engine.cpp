@@ -1380,3 +1380,30 @@ extern "C" int dh_unet_stats(const dh_unet* u, double* flops_fwd, double* flops_
   if (launches) *launches = (int64_t)u->ops.size();
   return DH_OK;
 }
+
+// test hook: the channel concatenations of the op list a configuration builds (host only, nothing is allocated on the device).
+// Per OP_CONCAT, in tape order, out[5 i ..] = (Ca, Cb, rows per image, groups of the GroupNorm that follows, 1 if the forward
+// fuses the GroupNorm statistics into the concatenation -- k_concat_gn -- else 0); *n_out = the number of concatenations.
+extern "C" int dh_dbg_unet_concat_ops(const dh_unet_config* cfg, int* out, int cap, int* n_out) {
+  DH_REQUIRE(cfg && n_out && (out || cap == 0), "null pointer");
+  dh_unet u;
+  u.cfg = *cfg;
+  const int rc = build(u);
+  if (rc != DH_OK) return rc;
+  int n = 0;
+  for (size_t i = 0; i < u.ops.size(); ++i) {
+    const Op& o = u.ops[i];
+    if (o.type != OP_CONCAT) continue;
+    const Ten &a = u.tens[o.in0], &b = u.tens[o.in1], &t = u.tens[o.out];
+    const int G = o.gn_next >= 0 ? u.ops[o.gn_next].groups : 0;
+    const bool fused = o.gn_next >= 0 && i + 1 < u.ops.size() && a.C % 8 == 0 && b.C % 8 == 0 && t.C % G == 0 &&
+                       (GN_GB * (t.C / G)) % 8 == 0 && GN_GB * (t.C / G) <= 2048;
+    if (n < cap) {
+      int* e = out + 5 * n;
+      e[0] = a.C; e[1] = b.C; e[2] = t.rows; e[3] = G; e[4] = fused ? 1 : 0;
+    }
+    ++n;
+  }
+  *n_out = n;
+  return DH_OK;
+}

@@ -300,15 +300,18 @@ __device__ __forceinline__ void gn_combine(const float* part, int b, int G, int 
     cm[k] = on ? p[S + s] : 0.f;
     cq[k] = on ? p[2 * S + s] : 0.f;
   }
+  // the mean relative to slice 0's (never empty): a group mean of many standard deviations keeps its digits in the weighted sum
+  const float ref = act ? p[S] : 0.f;
   float n = 0.f, sm = 0.f;
 #pragma unroll
-  for (int k = 0; k < GN_COMBINE_K; ++k) { n += cn[k]; sm += cn[k] * cm[k]; }
+  for (int k = 0; k < GN_COMBINE_K; ++k) { n += cn[k]; sm += cn[k] * (cm[k] - ref); }
   n = oct_sum(n); sm = oct_sum(sm);
-  const float mean = sm / n;
+  const float mean = ref + sm / n;
   float m2 = 0.f;
 #pragma unroll
   for (int k = 0; k < GN_COMBINE_K; ++k) { const float d = cm[k] - mean; m2 += cq[k] + cn[k] * d * d; }
   m2 = oct_sum(m2);
+  m2 = m2 > 0.f ? m2 : 0.f;          // a slice M2 that rounded below zero must not turn rstd into NaN
   if (act && sub == 0) {
     const float rstd = rsqrtf(m2 / n + eps);
     sm_stats[g] = make_float2(mean, rstd);

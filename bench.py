@@ -14,7 +14,9 @@ the GPU; --launch-timeout bounds the job); under `python -m torch.distributed.ru
 given.  Profiling: put a profiler in front of a `--gpus 1` run (or of one rank) only -- `rocprofv3 ... -- python3 bench.py --gpus N`
 would make the profiler-initialised parent spawn the ranks.
 
-Next to the headline the same run reports (rank 0 unless stated; none of it inside the timed region):
+A plain run does only what the headline needs: it builds the engine and the per-image identity (initial inference), warms
+up, times --steps steps, writes --dump-outputs if asked and prints the line.  With --full the same run then reports, next to
+the headline (rank 0 unless stated; none of it inside the timed region; the --no-* switches skip single records):
   roofline        dominant kernel (k_gemm_dma) by HIP events on its stream, + committed PMC traffic
   hbm_kernels     guidance energy and batched re-projection, achieved GB/s
   phases          BASELINE config 2 "with and without the per-image phase": null-text inversion (50 timesteps x <= 5
@@ -25,7 +27,7 @@ Next to the headline the same run reports (rank 0 unless stated; none of it insi
   res768_bf16     BASELINE config 5: 768x768, bf16 U-Net, f32 guidance energy / cotangent / latent update
   cpu_baseline    the oracle on the host cores: U-Net step, and per piece z-buffer / cells / energy
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0; the records a plain run does not measure are null in it.
 """
 import argparse
 import json
@@ -78,8 +80,14 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--res", type=int, default=512, help="image resolution of the headline (512 = BASELINE config 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure every secondary record (roofline, HBM kernels, per-image phases, "
+                         "batched edits, 768x768 bf16, CPU baseline); --profile-steps, --streams and the --no-* switches "
+                         "shape those records")
     ap.add_argument("--profile-steps", type=int, default=3, help="extra steps run with the HIP-event GEMM bracket")
-    ap.add_argument("--batch-edits", type=int, default=8, help="K edits of one image per U-Net batch (config 3 / 4); 0 = skip")
+    ap.add_argument("--batch-edits", type=int, default=8,
+                    help="K edits of one image per U-Net batch (config 3 / 4); 0 = skip.  Also sizes the engine (max_batch 2K) of "
+                         "every run, plain or --full")
     ap.add_argument("--streams", type=int, default=2,
                     help="concurrent edit lanes per GPU for the edits.concurrent record (engine arenas + streams on one copy of "
                          "the weights; never the single-edit headline); <= 1 = skip.  Two since round 5: a third lane's stream can "
@@ -362,9 +370,10 @@ def main():
     conf = C.load_default()
     lat = args.res // 8
     # the SD AutoencoderKL and the SD-2 CLIP text tower with random weights, both on the engine's kernels ("sd-native" /
-    # "sd2-native"): the decode on an edit's critical path, the encode and the prompt embedding of the per-image phase are real ones
+    # "sd2-native"): the decode on an edit's critical path, the encode and the prompt embedding of the per-image phase are real ones.
+    # The timed steps decode nothing, so a plain run builds no VAE; the engine is sized alike in both runs (the same arena layout)
     dh = DiffusionHandles(conf, dtype=dtype, unet_config=dict(SD2_DEPTH, sample_size=lat), max_batch=max(2, 2 * K),
-                          vae="sd-native", text_encoder="sd2-native").to(dev)
+                          vae="sd-native" if args.full else None, text_encoder="sd2-native").to(dev)
     gd = dh.diffuser
     depth, bg_depth, mask = (t.to(dev) for t in make_scene(args.res))
     prompt = "a sphere on a plane"
@@ -380,11 +389,12 @@ def main():
     noise = torch.randn(1, 4, lat, lat).to(dev)
     # untimed warm-up of the decoder and of the engine's graphs (the PyTorch-ROCm encoder's first call lets MIOpen pick /
     # compile its convolution kernels: seconds that belong to no phase; it runs inside the inversion warm-up below)
-    with torch.no_grad():
-        gd.decode_latent_image(torch.zeros(1, 4, lat, lat, device=dev))
-        if K > 1:
-            gd.decode_latent_image(torch.zeros(K, 4, lat, lat, device=dev))
-    if rank == 0 and args.phases:
+    if args.full:
+        with torch.no_grad():
+            gd.decode_latent_image(torch.zeros(1, 4, lat, lat, device=dev))
+            if K > 1:
+                gd.decode_latent_image(torch.zeros(K, 4, lat, lat, device=dev))
+    if rank == 0 and args.full and args.phases:
         img = make_image(args.res).to(dev)
         dh.inverter.invert(img, disparity, prompt, num_inner_steps=5, max_timesteps=1)
         torch.cuda.synchronize()
@@ -443,7 +453,7 @@ def main():
     import ctypes
     L = _lib.lib()
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.no_grad(), gd.on_stream():
             _lib.check(L.dh_gemm_profile_begin())
             for _ in range(max(1, args.profile_steps)):
@@ -579,7 +589,7 @@ def main():
                 del imgs2
 
     sections = Sections()
-    if K > 1:
+    if args.full and K > 1:
         if world > 1:
             batched_section()          # every rank meets the same barriers: an exception must end the job, not leave ranks waiting
         else:
@@ -646,7 +656,7 @@ def main():
         return out
 
     hbm = None
-    if rank == 0:
+    if rank == 0 and args.full:
         hbm = sections.run("hbm_records", lambda: hbm_records(gd, st, depth, bg_depth, mask, args.res))
 
     # one whole edit: transform_foreground = re-projection + 38 guided + 12 unguided steps + AutoencoderKL decode
@@ -680,13 +690,13 @@ def main():
 
     # ---- BASELINE config 5: 768x768, bf16 U-Net + f32 guidance (energy, cotangent seed, latent gradient and update in f32) ----
     res768 = None
-    if rank == 0 and args.res768 and args.res == 512:
+    if rank == 0 and args.full and args.res768 and args.res == 512:
         del dh, gd, st, acts
         torch.cuda.empty_cache()
         res768 = sections.run("res768_bf16", lambda: bench_768(conf, dev, prompt, TRANSFORMS, Y, max(5, args.steps // 2)))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.res == 512:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and args.res == 512:
         cpu = sections.run("cpu_baseline", cpu_baseline)
         if cpu is not None and "error" in cpu.get("pieces", {}):
             sections.errors.append({"section": "cpu_baseline.pieces", "error": cpu["pieces"]["error"]})
@@ -696,7 +706,7 @@ def main():
         out = {
             "metric": f"guided-denoise steps/sec at {args.res}x{args.res} (SD2-depth)",
             "value": round(value, 3), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "full": args.full,
             "per_rank": {"ms_per_step": [round(v / args.steps * 1e3, 3) for v in elapsed_by_rank],
                          "steps_per_s": [round(args.steps / v, 3) for v in elapsed_by_rank], "backend": backend if world > 1 else None,
                          "what": "each rank's own timed region (rank order); value = world x steps / MAX over ranks"},

@@ -27,6 +27,13 @@ def test_parse_dump_outputs_and_steps():
             bench.parse(bad)
 
 
+def test_parse_full_is_off_by_default():
+    bench = _bench()
+    assert bench.parse([]).full is False
+    a = bench.parse(["--full", "--no-phases"])
+    assert a.full is True and a.phases is False
+
+
 def test_dump_outputs_writes_float32_npy(tmp_path):
     bench = _bench()
     x = torch.randn(1, 8, 8, 4, generator=torch.Generator().manual_seed(0)).half()

@@ -23,7 +23,7 @@ def _env(**extra):
 
 
 def test_bench_two_ranks_on_one_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full",
                         "--batch-edits", "0", "--streams", "1", "--no-phases", "--no-res768", "--no-cpu-baseline"],
                        env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -40,6 +40,22 @@ def test_bench_two_ranks_on_one_gpu():
     print("two ranks on one GPU over gloo:", out["value"], "steps/s in total; per rank", pr["steps_per_s"])
 
 
+def test_bench_plain_run_measures_the_headline_only():
+    """A run without --full: the headline and its per-rank figures, every secondary record null, no errors, exit 0."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                       env=_env(), capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["errors"] == [] and out["n_gpus"] == 2 and out["value"] > 0
+    assert out["unit"] == "steps/s" and out["higher_is_better"] is True and out["dtype"] == "f16"
+    assert abs(out["value"] - 2 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-2 * out["value"]
+    assert len(out["per_rank"]["ms_per_step"]) == 2
+    for name in ("roofline", "hbm_kernels", "cpu_baseline", "phases", "batched_edits", "edits", "res768_bf16"):
+        assert out[name] is None, name
+
+
 def _n_gpus():
     import torch
     return torch.cuda.device_count()      # (counting devices does not initialise the GPU in this process)
@@ -50,7 +66,7 @@ def test_bench_two_ranks_over_rccl_one_rank_per_gpu():
     """The branch an 8-GPU node runs (round 6): backend "nccl" (= RCCL), one rank per device, init_process_group(device_id),
     device-side barrier / MAX / all_gather of the timings, the batched section on every rank.  Skipped on a 1-GPU box -- there
     the same control flow runs over gloo (tests above) and this branch stays unmeasured."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full",
                         "--batch-edits", "2", "--streams", "1", "--no-phases", "--no-res768", "--no-cpu-baseline"],
                        env=dict(_env(), DH_BENCH_BACKEND="nccl"), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -73,7 +89,7 @@ def test_sharded_driver_two_ranks_over_rccl(tmp_path):
 def test_bench_reports_a_failed_secondary_section_and_exits_non_zero():
     """A broken secondary record must not pass the driver unnoticed: the line is printed WITH the failure under "errors" and
     the return code is 3 (here the failure is injected into the batched section; the headline is still measured)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch-edits", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--batch-edits", "2",
                         "--streams", "1", "--no-phases", "--no-res768", "--no-cpu-baseline"],
                        env=dict(_env(), DH_BENCH_INJECT_FAIL="batched_section"), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])

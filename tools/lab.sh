@@ -290,7 +290,7 @@ grep "^rep" gpurun_out/invert/log.txt
 # scan-small-grids: every launch shape of the guided steps with its workgroup count (finds launches that leave the chip idle)
 recipe_scan_small_grids() { (
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
-rm -rf /tmp/scan; rocprofv3 --kernel-trace --output-format csv -d /tmp/scan -- python3 bench.py --no-phases --no-res768 --no-cpu-baseline --batch-edits 0 > /dev/null 2>&1
+rm -rf /tmp/scan; rocprofv3 --kernel-trace --output-format csv -d /tmp/scan -- python3 bench.py --full --no-phases --no-res768 --no-cpu-baseline --batch-edits 0 > /dev/null 2>&1
 f=$(ls /tmp/scan/*/*kernel_trace.csv | head -1)
 python3 - $f <<'PY' > gpurun_out/scan_small_grids.txt
 import csv, sys, re, collections
@@ -375,9 +375,9 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/final
 mkdir -p $O
 cd $R
-timeout 900 python bench.py 2>/dev/null | tail -1 > $O/bench_n1.json
+timeout 900 python bench.py --full 2>/dev/null | tail -1 > $O/bench_n1.json
 cd /tmp; export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 $R/bench.py --no-phases --no-res768 --no-cpu-baseline --batch-edits 0 2>/dev/null | tail -1 > $O/bench_under_rocprof.json
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 $R/bench.py --full --no-phases --no-res768 --no-cpu-baseline --batch-edits 0 2>/dev/null | tail -1 > $O/bench_under_rocprof.json
 cd $R
 T=$(ls /tmp/prof_bench/*/*kernel_trace.csv | head -1)
 S=$(ls /tmp/prof_bench/*/*kernel_stats.csv | head -1)
@@ -417,7 +417,7 @@ recipe_ab_stage() {
   echo "# bench.py: steps/s, GEMM avg launch us (HIP events), GEMM launches per step, batched edit-steps/s, 768^2 bf16 steps/s" >> "$out"
   for rep in 1 2; do for st in "$@"; do
     echo "== stage $st" >> "$out"
-    DH_GEMM_STAGE=$st timeout 300 python bench.py --steps 20 --warmup 5 2>/dev/null | python -c "
+    DH_GEMM_STAGE=$st timeout 300 python bench.py --full --steps 20 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d['value'], d['roofline']['avg_launch_us'], d['roofline']['launches_per_step'], d['batched_edits']['edit_steps_per_s'], d['res768_bf16']['value'])" >> "$out"

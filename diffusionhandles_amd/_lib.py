@@ -108,6 +108,8 @@ SIGNATURES = {
     "dh_adam_step_scaled": (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_p]),
     "dh_mse_cotangent_batch": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_d, c_p, c_p, c_p, c_p, c_p, c_p]),
     "dh_adam_step_scaled_batch": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p]),
+    "dh_latent_update_guarded": (c_i, [c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p]),
+    "dh_ddim_cfg_step_flagged": (c_i, [c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_i, c_i, c_p, c_i, c_i, c_p]),
 }
 
 # test hooks (csrc/debug_api.cpp): single-kernel entry points used only by tests/

@@ -3,6 +3,10 @@ import os
 
 import yaml
 
+# guided_diffuser keys that config/default.yaml (and the reference's configuration files) do not carry, with the meaning of
+# their absence: grad_scale 'static' = the fixed 16-bit backward scale, 'auto' = per-edit scale + overflow guard
+OPTIONAL_GUIDED_KEYS = {"grad_scale": "static"}
+
 
 class Conf(dict):
     """dict with attribute access, nested."""

@@ -185,6 +185,109 @@ __global__ void k_adam_scaled_batch(float* p, const float* g, float* m, float* v
   p[j] = p[j] - (lr / bc1) * (mi / denom);
 }
 
+
+// ---- guarded forms of the guided loop's update and DDIM step ('auto' guidance scale) -------------------------------
+// Status of an edit: int[4] = {kinds seen (bit 0: backward overflow, update held; bit 1: non-finite latent after the DDIM
+// step), number of held updates, code of the first failure ((t_idx + 1) << 16 | (iteration & 0xff) << 8 | kind; 0 = none),
+// 0}.  Written with ordinary global stores / atomics, only on failure.
+constexpr int GU_THREADS = 1024, GU_PER = 48;      // one workgroup holds an edit of up to 48 K elements in registers (96^2 x 4 = 36 K)
+__device__ __forceinline__ bool nonfinite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ int status_code(int t_idx, int iteration, int kind) {
+  return ((t_idx + 1) << 16) | ((iteration & 0xff) << 8) | kind;
+}
+
+// one workgroup per edit (blockIdx.x): out = x - (lr / S_e) * g if the edit's gradient slice is finite, else out = x and the
+// edit's status records the held update.  g: [pixels][gc] per edit, the first c channels of every pixel; S_e =
+// scale[e * tab_stride + tab_index] (a power of two).  Every element of g is read once, into registers.
+__global__ void __launch_bounds__(GU_THREADS) k_latent_update_guarded(float* out, const float* x, const float* g, int gc, int c,
+                                                                      int n, float lr, const float* scale, int tab_stride,
+                                                                      int tab_index, int* status, float* gmax, int t_idx,
+                                                                      int iteration) {
+  __shared__ int sbad[GU_THREADS / 64];
+  __shared__ float smax[GU_THREADS / 64];
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const float* ge = g + (size_t)e * (n / c) * gc;
+  const float* xe = x + (size_t)e * n;
+  float* oe = out + (size_t)e * n;
+  float v[GU_PER];
+  int bad = 0;
+  float mx = 0.f;
+#pragma unroll
+  for (int j = 0; j < GU_PER; ++j) {
+    const int i = tid + j * GU_THREADS;
+    v[j] = 0.f;
+    if (i < n) {
+      const int p = i / c, ch = i - p * c;
+      v[j] = ge[(size_t)p * gc + ch];
+      bad |= nonfinite_bits(v[j]) ? 1 : 0;
+      mx = fmaxf(mx, fabsf(v[j]));
+    }
+  }
+  bad = wave_max(bad);
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) { sbad[tid >> 6] = bad; smax[tid >> 6] = mx; }
+  __syncthreads();
+  bad = 0;
+  mx = 0.f;
+  for (int w = 0; w < GU_THREADS / 64; ++w) { bad |= sbad[w]; mx = fmaxf(mx, smax[w]); }
+  const float S = scale[(size_t)e * tab_stride + tab_index];
+  if (!bad) {
+    int ex = 0;
+    (void)frexpf(S, &ex);
+    const float k = ldexpf(lr, 1 - ex);          // lr / S, exact for a power of two S
+#pragma unroll
+    for (int j = 0; j < GU_PER; ++j) {
+      const int i = tid + j * GU_THREADS;
+      if (i < n) oe[i] = xe[i] - k * v[j];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < GU_PER; ++j) {
+      const int i = tid + j * GU_THREADS;
+      if (i < n) oe[i] = xe[i];
+    }
+  }
+  if (tid == 0) {
+    if (gmax) gmax[e] = bad ? NAN : mx / S;
+    if (bad) {
+      int* st = status + 4 * e;
+      st[0] |= 1;
+      st[1] += 1;
+      if (st[2] == 0) st[2] = status_code(t_idx, iteration, 1);
+    }
+  }
+}
+
+// k_ddim_cfg, and bit 1 of the status of edit i / n_edit where an output element is not finite: a wave ballot, then one lane
+// per (wave, failing edit) does the global atomics -- nothing is written while the outputs are finite
+__global__ void k_ddim_cfg_flagged(float* out, const float* x, const float* eu, const float* ec, float scale, float sa_t,
+                                   float s1a_t, float sa_p, float s1a_p, int n, int n_edit, int* status, int t_idx,
+                                   int iteration) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < n;
+  bool bad = false;
+  if (valid) {
+    float e = ec[i];
+    if (eu) { float u = eu[i]; e = u + scale * (e - u); }
+    float x0 = (x[i] - s1a_t * e) / sa_t;
+    const float o = sa_p * x0 + s1a_p * e;
+    out[i] = o;
+    bad = nonfinite_bits(o);
+  }
+  const int edit = valid ? i / n_edit : 0;
+  const int lane = threadIdx.x & 63;
+  unsigned long long m = __ballot(bad);
+  while (m) {
+    const int l = __ffsll((long long)m) - 1;
+    const int el = __shfl(edit, l, 64);
+    if (lane == l) {
+      atomicOr(&status[4 * el], 2);
+      atomicCAS(&status[4 * el + 2], 0, status_code(t_idx, iteration, 2));
+    }
+    m &= ~__ballot(bad && edit == el);
+  }
+}
+
 }  // namespace dh
 using namespace dh;
 
@@ -289,6 +392,31 @@ extern "C" int dh_pack_sample(float* dst, const float* latent, int latent_batch,
   const int n = batch * pixels * (latent_channels + cd);
   hipLaunchKernelGGL(k_pack_sample, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, dst, latent, latent_batch,
                      latent_channels, depth, depth_batch, cd, pixels, n);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_latent_update_guarded(float* x_out, const float* x, const float* g, int g_channels, int channels, float lr,
+                                        int pixels, int edits, const float* scale_table, int table_stride, int table_index,
+                                        int* status, float* gmax, int t_idx, int iteration, void* stream) {
+  DH_REQUIRE(x_out && x && g && scale_table && status && pixels > 0 && channels > 0 && g_channels >= channels && edits >= 1 &&
+             table_stride >= 1 && table_index >= 0 && table_index < table_stride && t_idx >= 0 && t_idx < 32767 && iteration >= 0,
+             "bad arguments");
+  DH_REQUIRE((long long)pixels * channels <= (long long)GU_THREADS * GU_PER, "latent too large for one workgroup per edit");
+  hipLaunchKernelGGL(k_latent_update_guarded, dim3(edits), dim3(GU_THREADS), 0, (hipStream_t)stream, x_out, x, g, g_channels,
+                     channels, pixels * channels, lr, scale_table, table_stride, table_index, status, gmax, t_idx, iteration);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_ddim_cfg_step_flagged(float* x_out, const float* x, const float* eps_u, const float* eps_c, float scale,
+                                        float alpha_t, float alpha_prev, int n, int n_edit, int* status, int t_idx, int iteration,
+                                        void* stream) {
+  DH_REQUIRE(x_out && x && eps_c && status && n > 0 && n_edit > 0 && n % n_edit == 0 && t_idx >= 0 && t_idx < 32767 &&
+             iteration >= 0, "bad arguments");
+  float sa_t = sqrtf(alpha_t), s1a_t = sqrtf(1.f - alpha_t), sa_p = sqrtf(alpha_prev), s1a_p = sqrtf(1.f - alpha_prev);
+  hipLaunchKernelGGL(k_ddim_cfg_flagged, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x_out, x, eps_u, eps_c, scale,
+                     sa_t, s1a_t, sa_p, s1a_p, n, n_edit, status, t_idx, iteration);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

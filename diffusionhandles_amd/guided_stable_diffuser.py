@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import guidance_scale as _gs
 from .guided_diffuser import GuidedDiffuser
 from .losses import (EnergyPlan, energy_and_grad, energy_and_grad_planned,
                      process_correspondences as _process_correspondences)
@@ -114,6 +115,10 @@ class GuidedStableDiffuser(GuidedDiffuser):
         self.device = torch.device("cpu")
         # fp16 needs the guidance gradient scaled through the backward pass
         self.grad_scale = 256.0 if dtype == torch.float16 else 1.0
+        # conf.grad_scale 'auto' (absent = 'static'): a power-of-two scale per edit and (timestep, iteration) from a host bound
+        # of the cotangent (guidance_scale.py), the guarded latent update and the flagged DDIM step, FloatingPointError at the
+        # end of a call when an edit met a non-finite value
+        self.grad_scale_mode = _gs.resolve_mode(conf)
         # guided_step drives the engine through its own I/O buffers (no device copies / torch.cat around the passes); False
         # routes the same kernels through caller-owned tensors (bit-identical; kept for tools/ab_inplace.py)
         self._inplace_io = True
@@ -272,6 +277,43 @@ class GuidedStableDiffuser(GuidedDiffuser):
                                       a_p, x.numel(), _lib.stream_ptr()), "dh_ddim_cfg_step")
         return out
 
+    def _ddim_step_flagged(self, x, eps_u, eps_c, t, status, t_idx, iteration, scale=CFG_SCALE):
+        """ddim_step, plus the status bit of every edit (batch item) whose output has a non-finite element."""
+        a_t, a_p = self.scheduler.step_alphas(t)
+        out = torch.empty_like(x)
+        _lib.check(_lib.lib().dh_ddim_cfg_step_flagged(_lib.ptr(out), _lib.ptr(x), _lib.ptr(eps_u), _lib.ptr(eps_c), float(scale),
+                                                       a_t, a_p, x.numel(), x[0].numel(), _lib.ptr(status), int(t_idx),
+                                                       int(iteration), _lib.stream_ptr()), "dh_ddim_cfg_step_flagged")
+        return out
+
+    def _latent_update_guarded(self, x_new, x, d_sample, table, status, t_idx, iteration):
+        """x_new = x - 0.1 d_sample / S per edit (batch item), held where the edit's d_sample has a non-finite element.
+        table: [edits, T, I] device scales."""
+        E, T, I = table.shape
+        _lib.check(_lib.lib().dh_latent_update_guarded(_lib.ptr(x_new), _lib.ptr(x), _lib.ptr(d_sample), d_sample.shape[-1],
+                                                       x.shape[-1], 0.1, x[0].numel() // x.shape[-1], E, _lib.ptr(table),
+                                                       T * I, t_idx * I + iteration, _lib.ptr(status), None, int(t_idx),
+                                                       int(iteration), _lib.stream_ptr()), "dh_latent_update_guarded")
+
+    @staticmethod
+    def raise_on_status(statuses):
+        """statuses: list of (edit index, host int[4] status of dh_latent_update_guarded / dh_ddim_cfg_step_flagged).  Raises
+        FloatingPointError naming every failing edit with its first (t_idx, iteration) and what failed; .edits = their indices."""
+        bad = []
+        for e, s in statuses:
+            s = [int(v) for v in s]
+            if s[0] == 0:
+                continue
+            code = s[2]
+            t_idx, it, kind = (code >> 16) - 1, (code >> 8) & 0xff, code & 0xff
+            what = "backward overflow, update held" if kind == 1 else "non-finite latent after the DDIM step"
+            extra = f" ({s[1]} updates held)" if s[1] else ""
+            bad.append((e, f"edit {e}: {what} at (t_idx={t_idx}, iteration={it}){extra}"))
+        if bad:
+            err = FloatingPointError("guided edit hit a non-finite value: " + "; ".join(m for _, m in bad))
+            err.edits = [e for e, _ in bad]
+            raise err
+
     def _unet_input(self, x, depth_nhwc, reps=1):
         """x [1,H,W,4], depth [1,H,W,1] -> [reps,H,W,5]"""
         s = torch.cat([x, depth_nhwc], dim=-1) if self.conf.use_depth else x
@@ -409,14 +451,24 @@ class GuidedStableDiffuser(GuidedDiffuser):
         if (self.conf.fg_patch_size == 1 and self.conf.bg_loss_type == "global_avg"
                 and all(o.shape[1] == st.size[0] and o.shape[2] == st.size[1] for o in st.orig[1:])):
             st.plan = EnergyPlan(st.pc, st.size[0], self.device)
+        st.auto = self.grad_scale_mode == "auto"
+        if st.auto:
+            # S per (timestep, iteration): host copy for the energy calls, device copy for the guarded update
+            st.scale_host, st.bounds = _gs.scale_table(
+                st.pc, st.size[0], [tuple(o.shape[1:]) for o in st.orig], st.schedule, int(self.conf.num_timesteps),
+                int(self.conf.num_optsteps), int(self.conf.guidance_max_step), self.conf.fg_patch_size,
+                self.conf.bg_patch_size, self.conf.bg_loss_type)
+            st.scale_dev = torch.tensor(st.scale_host, dtype=torch.float32).to(self.device)[None].contiguous()
+            st.status = torch.zeros((1, 4), dtype=torch.int32, device=self.device)
         return st
 
-    def _energy_grad(self, st, k, act, t_idx, fgw, bgw, out=None):
-        """d(energy of layer k)/d(act) * grad_scale, act [h,w,C] channels-last; `out`: where to write it."""
+    def _energy_grad(self, st, k, act, t_idx, fgw, bgw, out=None, scale=None):
+        """d(energy of layer k)/d(act) * scale (default grad_scale), act [h,w,C] channels-last; `out`: where to write it."""
+        scale = self.grad_scale if scale is None else scale
         if st.plan is not None and act.shape[0] == st.plan.grid and act.shape[1] == st.plan.grid:
-            return energy_and_grad_planned(act, st.orig[k][t_idx], st.plan, fgw, bgw, grad_scale=self.grad_scale, out=out)[1]
+            return energy_and_grad_planned(act, st.orig[k][t_idx], st.plan, fgw, bgw, grad_scale=scale, out=out)[1]
         return energy_and_grad(act, st.orig[k][t_idx], st.pc, fgw, bgw, self.conf.fg_patch_size, self.conf.bg_patch_size,
-                               st.size, self.conf.bg_loss_type, grad_scale=self.grad_scale, out=out)[1]
+                               st.size, self.conf.bg_loss_type, grad_scale=scale, out=out)[1]
 
     @staticmethod
     def _latent_buffer(st, x, iteration):
@@ -450,14 +502,21 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 _, acts = self.unet.forward(sample, float(t), st.cond, save_for_backward=True, want_acts=active, want_eps=False,
                                             text_key=st.cond_key, inplace=ip)
                 d_acts = [None, None, None]
+                S = float(st.scale_host[t_idx, iteration]) if st.auto else self.grad_scale
                 for k in active:
                     d_acts[k] = self.unet.io_view("act_grad", k)[:1] if ip else torch.empty_like(acts[k])
-                    self._energy_grad(st, k, acts[k][0], t_idx, fgw[k], bgw[k], out=d_acts[k][0])
+                    self._energy_grad(st, k, acts[k][0], t_idx, fgw[k], bgw[k], out=d_acts[k][0], scale=S)
                 d_sample, _ = self.unet.backward(d_acts, None, want_sample_grad=True, want_text_grad=False, inplace=ip)
                 x_new = self._latent_buffer(st, x, iteration)
-                _lib.check(L.dh_latent_update_strided(_lib.ptr(x_new), _lib.ptr(x), _lib.ptr(d_sample), d_sample.shape[-1],
-                                                      x.shape[-1], 0.1, self.grad_scale, x.numel() // x.shape[-1],
-                                                      _lib.stream_ptr()), "dh_latent_update_strided")
+                if st.auto:
+                    self._latent_update_guarded(x_new, x, d_sample, st.scale_dev, st.status, t_idx, iteration)
+                else:
+                    _lib.check(L.dh_latent_update_strided(_lib.ptr(x_new), _lib.ptr(x), _lib.ptr(d_sample), d_sample.shape[-1],
+                                                          x.shape[-1], 0.1, self.grad_scale, x.numel() // x.shape[-1],
+                                                          _lib.stream_ptr()), "dh_latent_update_strided")
+                if record is not None:
+                    record.setdefault("scale", []).append(S)
+                    record.setdefault("grad", []).append((d_sample[..., :x.shape[-1]].float() / S).permute(0, 3, 1, 2).clone())
                 x = x_new
             if record is not None:
                 record.setdefault("opt", []).append(x.permute(0, 3, 1, 2).clone())
@@ -465,7 +524,10 @@ class GuidedStableDiffuser(GuidedDiffuser):
         if images is not None:
             images.append(self.decode_latent_image(x.permute(0, 3, 1, 2)).cpu())
         eu, ec = self._cfg_eps(x, st.depth_nhwc, t, uncond, st.cond, inplace=self._inplace_io)      # (views: consumed by the step right here)
-        x = self.ddim_step(x, eu, ec, t)
+        if st.auto:
+            x = self._ddim_step_flagged(x, eu, ec, t, st.status, t_idx, iteration)
+        else:
+            x = self.ddim_step(x, eu, ec, t)
         if images is not None:
             images.append(self.decode_latent_image(x.permute(0, 3, 1, 2)).cpu())
         return x
@@ -477,10 +539,13 @@ class GuidedStableDiffuser(GuidedDiffuser):
         K = x.shape[0]
         depth = torch.cat([st.depth_nhwc for st in sts], dim=0) if self.conf.use_depth else None
         cond = sts[0].cond.expand(K, -1, -1).contiguous()
+        auto = sts[0].auto
+        if auto:
+            table, status = self._batch_guard(sts)
         iteration = 0
         while iteration < self.conf.num_optsteps and t_idx < self.conf.guidance_max_step:
-            fgw, bgw = sts[0].schedule(t_idx, iteration)
-            active = [k for k in range(3) if fgw[k] != 0.0 or bgw[k] != 0.0]
+            ws = [st.schedule(t_idx, iteration) for st in sts]          # (edits may carry their own weights)
+            active = [k for k in range(3) if any(fgw[k] != 0.0 or bgw[k] != 0.0 for fgw, bgw in ws)]
             if active:
                 # the same in-place engine I/O as guided_step: one pack launch for the K inputs, every edit's energy gradient
                 # written straight into its slice of the engine's cotangent buffer, d(sample) read in place
@@ -491,56 +556,93 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 for k in active:
                     d_acts[k] = self.unet.io_view("act_grad", k)[:K]
                     for e, st in enumerate(sts):
+                        fgw, bgw = ws[e]
                         fw = fgw[k] if st.n_pairs > 0 else 0.0
-                        self._energy_grad(st, k, acts[k][e], t_idx, fw, bgw[k], out=d_acts[k][e])
+                        S = float(st.scale_host[t_idx, iteration]) if auto else self.grad_scale
+                        self._energy_grad(st, k, acts[k][e], t_idx, fw, bgw[k], out=d_acts[k][e], scale=S)
                 d_sample, _ = self.unet.backward(d_acts, None, want_sample_grad=True, want_text_grad=False, inplace=True)
                 x_new = self._latent_buffer(sts[0], x, iteration)
-                _lib.check(L.dh_latent_update_strided(_lib.ptr(x_new), _lib.ptr(x), _lib.ptr(d_sample), d_sample.shape[-1],
-                                                      x.shape[-1], 0.1, self.grad_scale, x.numel() // x.shape[-1],
-                                                      _lib.stream_ptr()), "dh_latent_update_strided")
+                if auto:
+                    self._latent_update_guarded(x_new, x, d_sample, table, status, t_idx, iteration)
+                else:
+                    _lib.check(L.dh_latent_update_strided(_lib.ptr(x_new), _lib.ptr(x), _lib.ptr(d_sample), d_sample.shape[-1],
+                                                          x.shape[-1], 0.1, self.grad_scale, x.numel() // x.shape[-1],
+                                                          _lib.stream_ptr()), "dh_latent_update_strided")
                 x = x_new
             iteration += 1
         sample2 = self.unet.stage_sample(x, depth, 2 * K)          # the K edits twice: unconditional and conditional halves
         unc = uncond.reshape(1, *cond.shape[1:]).to(self.device, torch.float32).expand(K, -1, -1)
         text2 = torch.cat([unc, cond], dim=0).contiguous()
         eps, _ = self.unet.forward(sample2, float(t), text2, save_for_backward=False, want_acts=False, inplace=True)
+        if auto:
+            return self._ddim_step_flagged(x, eps[:K], eps[K:], t, status, t_idx, iteration)
         return self.ddim_step(x, eps[:K], eps[K:], t)
 
+    @staticmethod
+    def _batch_guard(sts):
+        """('auto') the [K, T, I] device scale table of a batch of guidance states and its [K, 4] status words, made at the
+        batch's first step and kept on the first state."""
+        key = tuple(id(st) for st in sts)
+        g = sts[0].__dict__.get("_batch_guard")
+        if g is None or g[0] != key:
+            table = torch.cat([st.scale_dev for st in sts]).contiguous()
+            status = torch.zeros((len(sts), 4), dtype=torch.int32, device=table.device)
+            g = sts[0]._batch_guard = (key, table, status)
+        return g[1], g[2]
+
+    @staticmethod
+    def _status_of(sts):
+        """device [K, 4] status of a guidance state (list of one) or batch, None in 'static' mode"""
+        if not sts[0].auto:
+            return None
+        if len(sts) == 1 and "_batch_guard" not in sts[0].__dict__:
+            return sts[0].status
+        return sts[0]._batch_guard[2]
+
     def _batch_edit_steps(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
-                          fg_weight=None, bg_weight=None, cond=None, orig=None):
+                          fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None):
         """The batched edit as a generator: yields after the preparation and after every denoising step (everything is only
         ENQUEUED on the current stream by then), returns the final latents [K,4,H,W] through StopIteration.  One body for the
-        one-stream call below and for the lanes of guided_inference_batch_lanes."""
+        one-stream call below and for the lanes of guided_inference_batch_lanes.  fg_weight / bg_weight: one value, or one per
+        edit.  status_out: a list that receives the device [K, 4] status ('auto') at the end."""
         K = len(depths)
+        per = lambda w, i: w[i] if isinstance(w, (list, tuple)) else w
         if self.unet.max_batch < 2 * K:
             raise RuntimeError(f"engine max_batch {self.unet.max_batch} < 2*K = {2 * K}")
         torch.manual_seed(self.conf.seed)
         self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
         timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
         sts = []
-        for d, c in zip(depths, correspondences_list):
-            sts.append(self.prepare_guidance(d, prompt, activations_orig, c, fg_weight, bg_weight,
+        for i, (d, c) in enumerate(zip(depths, correspondences_list)):
+            sts.append(self.prepare_guidance(d, prompt, activations_orig, c, per(fg_weight, i), per(bg_weight, i),
                                              orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond))
         x = _nhwc(latents.to(self.device, torch.float32)).expand(K, -1, -1, -1).contiguous()
         yield None
         for t_idx, t in enumerate(timesteps):
             x = self.guided_step_batch(sts, x, t_idx, t, uncond_embeddings[t_idx])
             yield None
+        if status_out is not None and sts[0].auto:
+            status_out.append(self._status_of(sts))
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_batch(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                fg_weight=None, bg_weight=None):
         """K edits of one image at once.  depths: list of K edited disparities [1,1,H,W]; correspondences_list:
-        K [N_k,4] tensors.  Needs an engine built with max_batch >= 2K.  Returns images [K,3,H,W]."""
+        K [N_k,4] tensors; fg_weight / bg_weight: one value or K.  Needs an engine built with max_batch >= 2K.  Returns images
+        [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value."""
+        status = []
         with torch.no_grad(), self.on_stream():
             gen = self._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
-                                         fg_weight, bg_weight)
+                                         fg_weight, bg_weight, status_out=status)
             try:
                 while True:
                     next(gen)
             except StopIteration as done:
                 self.last_latents = done.value
-            return self.decode_latent_image(self.last_latents)
+            image = self.decode_latent_image(self.last_latents)
+        if status:
+            self.raise_on_status(list(enumerate(status[0].cpu().tolist())))
+        return image
 
     # ---- lanes: concurrent edit streams on ONE copy of the weights --------------------------------------------------------
     def fork(self, max_batch=None):
@@ -642,22 +744,29 @@ class GuidedStableDiffuser(GuidedDiffuser):
             # lane 0 is THIS diffuser: it could not run its chunk, and forks sized 2 * kmax would be made for nothing
             raise RuntimeError(f"engine max_batch {self.unet.max_batch} < 2*K = {2 * kmax}: build the diffuser with max_batch >= {2 * kmax}")
         lanes = self.lanes(min(int(streams), len(chunks)))
+        statuses = [[] for _ in chunks]
         with torch.no_grad(), self.on_stream():
             cond = self._encode([prompt]).contiguous()
             orig = [a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in activations_orig]
 
-            def make(depths, corrs):
+            def make(depths, corrs, status):
                 def job(lane):
                     def body():
                         lat = yield from lane._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig,
-                                                                corrs, fg_weight, bg_weight, cond=cond, orig=orig)
+                                                                corrs, fg_weight, bg_weight, cond=cond, orig=orig,
+                                                                status_out=status)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
-            return GuidedStableDiffuser.run_lanes(lanes, [make(d, c) for d, c in chunks])
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s) for (d, c), s in zip(chunks, statuses)])
+            if any(statuses):      # edits numbered over the chunks in order; read after every lane has finished
+                offs = np.cumsum([0] + [len(d) for d, _ in chunks])
+                self.raise_on_status([(int(offs[i]) + b, row) for i, s in enumerate(statuses)
+                                      for b, row in enumerate(s[0].cpu().tolist())])
+        return images
 
     def _edit_steps(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences, fg_weight=None,
-                    bg_weight=None, cond=None, orig=None):
+                    bg_weight=None, cond=None, orig=None, status_out=None):
         """One edit as a generator (see _batch_edit_steps): yields after the preparation and after every denoising step,
         returns the final latents [1,4,H,W]."""
         torch.manual_seed(self.conf.seed)
@@ -669,6 +778,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         for t_idx, t in enumerate(timesteps):
             x = self.guided_step(st, x, t_idx, t, uncond_embeddings[t_idx])
             yield None
+        if status_out is not None and st.auto:
+            status_out.append(st.status)
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_lanes(self, latents, edits, uncond_embeddings, prompt, activations_orig, streams=2, fg_weight=None,
@@ -677,19 +788,23 @@ class GuidedStableDiffuser(GuidedDiffuser):
         argument pair of guided_inference; edit i runs on lane i % streams with exactly the passes guided_inference runs, so
         the images are bit-identical to the one-stream calls.  Returns a list of images [1,3,H,W]."""
         lanes = self.lanes(min(int(streams), len(edits)))
+        statuses = [[] for _ in edits]
         with torch.no_grad(), self.on_stream():
             cond = self._encode([prompt]).contiguous()
             orig = [a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in activations_orig]
 
-            def make(depth, corr):
+            def make(depth, corr, status):
                 def job(lane):
                     def body():
                         lat = yield from lane._edit_steps(latents, depth, uncond_embeddings, prompt, activations_orig, corr,
-                                                          fg_weight, bg_weight, cond=cond, orig=orig)
+                                                          fg_weight, bg_weight, cond=cond, orig=orig, status_out=status)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
-            return GuidedStableDiffuser.run_lanes(lanes, [make(d, c) for d, c in edits])
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s) for (d, c), s in zip(edits, statuses)])
+            if any(statuses):      # read after every lane has finished
+                self.raise_on_status([(i, s[0][0].cpu().tolist()) for i, s in enumerate(statuses)])
+        return images
 
     def guided_inference(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences,
                          fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None):
@@ -709,4 +824,6 @@ class GuidedStableDiffuser(GuidedDiffuser):
                     record.setdefault("step", []).append(x.permute(0, 3, 1, 2).clone())
             self.last_latents = x.permute(0, 3, 1, 2)
             image = self.decode_latent_image(self.last_latents)
+        if st.auto:      # the one read of the status, after the whole edit
+            self.raise_on_status([(0, st.status[0].cpu().tolist())])
         return (image, denoising_steps) if save_denoising_steps else image

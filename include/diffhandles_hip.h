@@ -269,6 +269,20 @@ int dh_latent_update(float* x_out, const float* x, const float* g, float lr, flo
  * channels of d(sample) = d(cat[latents, depth])) */
 int dh_latent_update_strided(float* x_out, const float* x, const float* g, int g_channels, int channels, float lr,
                              float grad_scale, int pixels, void* stream);
+/* Guarded forms for the 'auto' guidance scale (conf.guided_diffuser.grad_scale; the latent update of
+ * guided_stable_diffuser.py:434 and the DDIM step of :468-474).  status: int[edits][4] per edit = {kinds seen (bit 0: the
+ * backward overflowed and the update was held, bit 1: a latent element is not finite after the DDIM step), number of held
+ * updates, code of the first failure ((t_idx + 1) << 16 | (iteration & 0xff) << 8 | kind, 0 = none), 0}; the caller zeroes it.
+ * dh_latent_update_guarded: one workgroup per edit, edits of `pixels` x `channels` (at most 48 K elements) read out of g
+ * [edits][pixels][g_channels]; per edit, x_out = x - (lr / S_e) g if every element of its slice is finite, else x_out = x
+ * and the status records the held update.  S_e = scale_table[e * table_stride + table_index], a power of two; with S_e =
+ * grad_scale the result is bit-identical to dh_latent_update_strided.  gmax (may be NULL): [edits] max |g| / S_e (NaN when held). */
+int dh_latent_update_guarded(float* x_out, const float* x, const float* g, int g_channels, int channels, float lr, int pixels,
+                             int edits, const float* scale_table, int table_stride, int table_index, int* status, float* gmax,
+                             int t_idx, int iteration, void* stream);
+/* dh_ddim_cfg_step, plus bit 1 of status[i / n_edit] where output element i is not finite (n_edit: elements per edit) */
+int dh_ddim_cfg_step_flagged(float* x_out, const float* x, const float* eps_u, const float* eps_c, float scale, float alpha_t,
+                             float alpha_prev, int n, int n_edit, int* status, int t_idx, int iteration, void* stream);
 /* dst[b][p][:] = concat(latent[b or 0][p][0:latent_channels], depth[b or 0][p][0:depth_channels]) for b < batch: the U-Net
  * input `torch.cat([latents (x batch), depth (x batch)], dim=1)` (guided_stable_diffuser.py:400-401, 451-455) in one launch.
  * latent_batch / depth_batch divide batch: item b reads latent[b mod latent_batch] (1 = broadcast, batch = one each, K of 2K =

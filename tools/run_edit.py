@@ -38,7 +38,7 @@ def load_config(path):
     for k, v in over.items():
         if k == "guided_diffuser":
             for kk, vv in (v or {}).items():
-                if kk not in conf.guided_diffuser:
+                if kk not in conf.guided_diffuser and kk not in C.OPTIONAL_GUIDED_KEYS:
                     raise ValueError(f"{path}: unknown key guided_diffuser.{kk}")
                 conf.guided_diffuser[kk] = vv
         elif k in conf:

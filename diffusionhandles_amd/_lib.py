@@ -137,6 +137,8 @@ DEBUG_SIGNATURES = {
     "dh_dbg_unet_concat_ops": (c_i, [ctypes.POINTER(UNetConfig), ctypes.POINTER(c_i), c_i, ctypes.POINTER(c_i)]),
     "dh_dbg_gemm_lnfold": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_l, c_p]),
     "dh_dbg_gemm_glu": (c_i, [c_i, c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "dh_dbg_gemm_glub_split": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_p, c_l, c_i, c_p, c_p, ctypes.POINTER(c_i), c_p]),
+    "dh_dbg_unet_ff_fold": (c_i, [c_p, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_p, c_p, c_p]),
     "dh_dbg_gemm_family": (c_i, [c_i]),
     "dh_dbg_gemm_stage": (c_i, [c_i]),
     "dh_dbg_gemm_pp_variant": (c_i, [c_i, c_p]),

@@ -188,6 +188,35 @@ extern "C" int dh_dbg_gemm_glu(int dtype, int bwd, const void* A, long lda, cons
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
+extern "C" int dh_dbg_gemm_last_tile(int* out);
+// the column-split GEGLU backward (engine: the input-gradient GEMM of a transformer's proj_out folded into ff.net.2).  W [N][K]
+// plain; the tile A W^T [M][N] holds dy of a GEGLU in columns [0, F) (saved pre-activations x [M][2F], paired; dx [M][2F]
+// receives d_value | d_gate) and a plain output in columns [F, N), which goes to C [M][N - F] (row stride ldc; accumulate = 1 adds
+// it to what C holds).  tile (if set) receives dh_dbg_gemm_last_tile's nine values of the launch.
+extern "C" int dh_dbg_gemm_glub_split(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int F, void* C,
+                                      long ldc, int accumulate, const void* x, void* dx, int* tile, void* stream) {
+  DH_REQUIRE(A && W && C && x && dx && K % 64 == 0 && N % 64 == 0 && F % 64 == 0 && F > 0 && F < N, "bad arguments (K, N, F % 64; 0 < F < N)");
+  static void* tiled = nullptr;
+  static size_t tiled_cap = 0;
+  const int Np = (int)align_up((size_t)N, 128);     // whole 128-row tiles, zero past N (what the engine's folded weight holds)
+  const size_t need = (size_t)Np * K * 2;
+  if (need > tiled_cap) {
+    if (tiled) (void)hipFree(tiled);
+    DH_CHECK_HIP(hipMalloc(&tiled, need));
+    tiled_cap = need;
+  }
+  DH_CHECK_HIP(hipMemsetAsync(tiled, 0, need, (hipStream_t)stream));
+  launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream);
+  GemmArgs g;
+  g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = A_DENSE;
+  g.glub_x = x; g.glub_dx = dx; g.glub_f = F;
+  g.C = C; g.ldc = ldc;
+  if (accumulate) { g.R = C; g.ldr = ldc; }
+  launch_gemm(dtype, g, (hipStream_t)stream);
+  if (tile) dh_dbg_gemm_last_tile(tile);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
 extern "C" int dh_dbg_groupnorm(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats,
                                 const void* dy, void* dx, float* scratch, int B, int HW, int C, int G, float eps,
                                 int silu, int accumulate, void* stream) {

@@ -461,7 +461,9 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
   // sitting at the tail of the kernel (these loads are younger than the prologue DMAs and older than every later one,
   // so the counted vmcnt waits below can only become stricter)
   constexpr bool PRE = TM * TN <= 8;               // the prefetched tiles cost 8 registers per 32x32 output tile
-  const bool pre_r = PRE && p.R != nullptr && p.pre_r && p.splits == 1 && (WG == 1 || grp == 0) && (KG == 1 || kg == 0);
+  // (a GEGLU-backward tile of the column-split form writes no C: nothing to add there)
+  const bool pre_r = PRE && p.R != nullptr && p.pre_r && p.splits == 1 && (WG == 1 || grp == 0) && (KG == 1 || kg == 0) &&
+                     (GLU != 2 || !glub_tile_is_glu(n0, p.glub_f));
   // (the eight-wave 128x320 tile holds five column blocks per wave: 80 registers of prefetched bias would push it over the
   //  256-register budget of two waves per SIMD; its bias is read in the epilogue, a warm 1.3 KB vector)
   constexpr bool PRE_B = PRE && !(MW == 2 && BN == 320) && WNS == 2;
@@ -724,15 +726,17 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
     }
     return;
   }
-  if constexpr (GLU == 2) {
-    // GEGLU backward.  The tile holds dy (natural output columns o); the saved pre-activations of output columns
-    // [o0, o0 + 32) are the two paired 32-column blocks at 2 o0 + 32 q.  Per block the lane pair loads the value / gate chunks
-    // (16 bytes each), un-exchanges them to the (g, hi) ownership of the accumulators, and stores d_value / d_gate as
-    // 16-byte chunks after the inverse exchange.  Every load is issued before the first use.
+  // GEGLU backward.  The tile holds dy (natural output columns o); the saved pre-activations of output columns
+  // [o0, o0 + 32) are the two paired 32-column blocks at 2 o0 + 32 q.  Per block the lane pair loads the value / gate chunks
+  // (16 bytes each), un-exchanges them to the (g, hi) ownership of the accumulators, and stores d_value / d_gate as
+  // 16-byte chunks after the inverse exchange.  Every load is issued before the first use.
+  // Column-split form (p.glub_f < N: a transformer's proj_out folded into ff.net.2): only the tiles left of the seam hold dy of
+  // the GEGLU; the others fall through to the plain epilogue below (their C / R are passed shifted by glub_f columns).
+  if (GLU == 2 && glub_tile_is_glu(n0, p.glub_f)) {
     typedef T T4 __attribute__((ext_vector_type(4)));
     const T* X = reinterpret_cast<const T*>(p.glub_x);
     T* DX = reinterpret_cast<T*>(p.glub_dx);
-    const size_t ldx = 2 * (size_t)p.N;
+    const size_t ldx = 2 * (size_t)p.glub_f;
     uint4 Hc[TM][TN][2], Gc[TM][TN][2];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -741,7 +745,7 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         int nb = n0 + wn * CPW + j * 32;
-        if (nb >= p.N) nb = 0;
+        if (nb >= p.glub_f) nb = 0;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const T* src = X + (size_t)mc * ldx + 2 * nb + 32 * q + 8 * hi;
@@ -757,7 +761,7 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int nb = n0 + wn * CPW + j * 32;
-        if (nb >= p.N) continue;
+        if (nb >= p.glub_f) continue;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const uint4 hc = Hc[i][j][q], gc = Gc[i][j][q];
@@ -1345,9 +1349,12 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
   //  as many 128x128 two-stage tiles, two per CU: conv K = 5760 91.6 -> 95.9 us, batch-8 forward 12.74 -> 13.05 ms; the smaller tile
   //  stages a third more bytes per flop and that outweighs the 96 CUs it wakes up)
   if (mw2) { BM = 256; BN = 128; }
-  // GEGLU epilogues (dense, N a multiple of 128, never split): 64x64, 128x128 or 256x128 tiles only
+  // GEGLU epilogues (dense, N a multiple of 128 -- of 64 for the column-split backward -- never split): 64x64, 128x128 or 256x128
+  // tiles only
   const int glu = k.glu_y ? 1 : (k.glub_x ? 2 : 0);
   if (glu && !(BM == 64 && BN == 64)) { BM = mw2 ? 256 : 128; BN = 128; }
+  // the column-split GEGLU backward: no tile straddles the seam (the last column tile may run past N: W is readable there)
+  if (glu == 2 && !glub_split_ok(BN, k.glub_f)) { BM = 64; BN = 64; }
   // 128x160 tiles (four wave rows of 32 x 160) where exactly they fill the chip in ONE round and nothing needs K split: the
   // batched 32x32-latent level (M = 8192, N = 640: 64 x 4 = 256 workgroups instead of 160 256x128 ones) and its kin
   DH_KNOB(kT160, "DH_GEMM_T160", 224);              // fewest 128x160 tiles for that (0 = never)
@@ -1438,7 +1445,8 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
     if (k.mode != A_DENSE && k.Hout > 0 && k.Wout > 0) a_elems = (double)k.M / ((double)k.Hout * k.Wout) * k.Hin * k.Win * k.Cin;
     double c_elems = (double)k.M * k.N * (k.C ? 1.0 : 0.0) + (k.R ? (double)k.M * k.N : 0.0);
     if (k.glu_y) c_elems += 0.5 * (double)k.M * k.N;
-    if (k.glub_x) c_elems += 4.0 * (double)k.M * k.N;      // saved pre-activations read [M][2N], their gradient written [M][2N]
+    // saved pre-activations read [M][2F], their gradient written [M][2F] (C holds only the columns past F)
+    if (k.glub_x) c_elems += 4.0 * (double)k.M * k.glub_f - (k.C ? (double)k.M * k.glub_f : 0.0);
     if (k.gn_epi == 2) c_elems += (double)k.M * k.N;       // the GroupNorm input tile the backward statistics read
     g_prof.bytes += esz * (a_elems + (double)k.N * k.K + c_elems);
     g_prof.e0 = e0; g_prof.e1 = e1;
@@ -1516,7 +1524,7 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
       if (gn_done) *gn_done = 1;
     } else if (k.lnb_x && lnb_done && !k.bias && !k.rowvec && !k.R && !k.act_silu && k.N % 8 == 0 && k.ldc == k.N) {
       // the rows are the dy of a LayerNorm: reduce + LayerNorm backward in one launch (dy itself is not written)
-      launch_splitk_reduce_ln_bwd(dtype, k.partial, splits, k.lnb_x, k.lnb_gamma, k.lnb_stats, k.lnb_add, k.lnb_dx, k.M, k.N, st);
+      launch_splitk_reduce_ln_bwd(dtype, k.partial, splits, k.lnb_x, k.lnb_gamma, k.lnb_stats, k.lnb_add, k.lnb_dx, k.M, k.N, st, k.lnb_ldx);
       *lnb_done = 1;
     } else {
       const size_t groups = (size_t)k.M * k.N / 4;
@@ -1542,8 +1550,17 @@ double launch_gemm(int dtype, const GemmArgs& a, hipStream_t st) {
   k.gn_part = a.gn_part; k.gn_HW = a.gn_HW; k.gn_G = a.gn_G; k.gn_S = 0;
   k.gnb_x = a.gnb_x; k.gnb_ldx = a.gnb_ldx; k.gnb_gamma = a.gnb_gamma; k.gnb_beta = a.gnb_beta; k.gnb_stats = a.gnb_stats;
   k.gnb_silu = a.gnb_silu;
-  k.lnb_x = a.lnb_x; k.lnb_gamma = a.lnb_gamma; k.lnb_stats = a.lnb_stats; k.lnb_add = a.lnb_add; k.lnb_dx = a.lnb_dx;
+  k.lnb_x = a.lnb_x; k.lnb_ldx = a.lnb_ldx > 0 ? a.lnb_ldx : a.N;
+  k.lnb_gamma = a.lnb_gamma; k.lnb_stats = a.lnb_stats; k.lnb_add = a.lnb_add; k.lnb_dx = a.lnb_dx;
   k.glu_y = a.glu_y; k.glu_ldy = a.glu_ldy; k.glub_x = a.glub_x; k.glub_dx = a.glub_dx;
+  k.glub_f = a.glub_x && a.glub_f > 0 && a.glub_f < a.N ? a.glub_f : a.N;
+  if (k.glub_f < a.N) {
+    // the plain column block [glub_f, N) lands at column n - glub_f of C (and of R): the kernel indexes them by n
+    if (k.C) k.C = reinterpret_cast<unsigned short*>(k.C) - k.glub_f;
+    if (k.R) k.R = reinterpret_cast<const unsigned short*>(k.R) - k.glub_f;
+  } else if (a.glub_x) {
+    k.C = nullptr;        // (the whole tile is dy of the GEGLU: C is not written)
+  }
   if (a.gn_done) *a.gn_done = 0;
   if (a.lnb_done) *a.lnb_done = 0;
   if (dtype == DH_DTYPE_F16) gemm_dispatch<f16>(k, a.partial_elems, st, a.gn_done, a.lnb_done, dtype);

@@ -47,8 +47,9 @@ struct GemmK {   // kernel-side copy of GemmArgs (plain data)
   float* gn_part; int gn_HW, gn_G, gn_S;      // GroupNorm slice statistics of the output (split-K reduce, or the GEMM's own epilogue: gn_epi)
   int gn_epi, gn_cpg;                         // statistics in this launch's epilogue (unsplit k_gemm_dma; 1 = forward, 2 = backward with gnb_*): gn_S = 2 per row tile of an image, gn_cpg = channels per group
   const void* gnb_x; long gnb_ldx; const float *gnb_gamma, *gnb_beta, *gnb_stats; int gnb_silu;   // backward statistics
-  const void* lnb_x; const float *lnb_gamma, *lnb_stats; const void* lnb_add; void* lnb_dx;        // LayerNorm backward on the reduce (host side only)
+  const void* lnb_x; long lnb_ldx; const float *lnb_gamma, *lnb_stats; const void* lnb_add; void* lnb_dx;   // LayerNorm backward on the reduce (host side only)
   void* glu_y; long glu_ldy; const void* glub_x; void* glub_dx;                                    // GEGLU epilogues (GLU instantiations)
+  int glub_f;       // GLU = 2: output columns [0, glub_f) are the GEGLU's dy, [glub_f, N) take the plain epilogue (glub_tile_is_glu)
   // k_gemm_pp only (launch_gemm_pp fills them): row / column tile counts, work-item order (0 = column tile fastest, 1 = row
   // tile fastest), bytes the A / W buffer descriptors cover
   int pp_tm, pp_tn, pp_order, pp_nwork; unsigned pp_a_bytes, pp_w_bytes;
@@ -59,6 +60,11 @@ struct GemmK {   // kernel-side copy of GemmArgs (plain data)
 // gemm_pp.hip: the eight-wave ping-pong kernel.  gemm_pp_eligible: whether the shape / epilogue can run on it and the policy
 // wants it (`force`: test hook -- 0 policy, 1 never, 2 whenever the kernel can carry the launch); launch_gemm_pp launches it
 // (the caller has filled k.splits / k.k_per_split for the tile it reports through bm / bn).
+// The column-split GEGLU backward (GemmArgs::glub_f): which epilogue a column tile takes, and which tile widths can carry the
+// split -- one predicate for the dispatch (host) and the kernel (device).  A tile lies wholly on one side of the seam.
+__host__ __device__ constexpr bool glub_tile_is_glu(int n0, int glub_f) { return n0 < glub_f; }
+__host__ __device__ constexpr bool glub_split_ok(int BN, int glub_f) { return BN > 0 && glub_f % BN == 0; }
+
 struct PpPlan { int bm = 0, bn = 0, splits = 1; };
 bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan);
 void launch_gemm_pp(int dtype, const GemmK& k, const PpPlan& plan, hipStream_t st, hipEvent_t e0, hipEvent_t e1);

@@ -724,6 +724,7 @@ bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan)
   // g_pp_glu: -1 = this policy, 0 = never, 1 = always.
   const bool glu_here = force == 2 || g_pp_glu > 0 || (g_pp_glu < 0 && ((glu == 1 && k.M >= 2048) || k.M >= 32768));
   if (glu && !glu_here) return false;
+  if (glu == 2 && k.glub_f > 0 && k.glub_f < k.N) return false;      // the column-split form (a folded proj_out) is k_gemm_dma's
   if (glu && (k.mode != A_DENSE || k.N % 128 || k.rowvec || k.R || (glu == 1 && (k.glu_ldy % 8 || ((size_t)k.glu_y & 15))) ||
               (glu == 2 && (((size_t)k.glub_x & 15) || ((size_t)k.glub_dx & 15))))) return false;
   if (k.rowvec && (k.rowvec_ld % 4 || ((size_t)k.rowvec & 15))) return false;

@@ -32,13 +32,15 @@ struct Ten {
   size_t off = 0, goff = 0;   // element offsets into the activation / gradient arenas
   size_t off_fo = 0;          // ... into the activation arena during a forward nobody differentiates (liveness plan, plan_forward_only)
   int rows = 0, C = 0;        // rows per batch item
+  int ld = 0;                 // row pitch of the activation (= C, or the width of the tensor this one is a column window of)
+  int view = -1, col = 0;     // >= 0: the activation is columns [col, col + C) of tensor `view` (the gradient keeps a dense slot)
   bool req_grad = true;
   bool persistent = false;    // same slot in both layouts, max_batch items: read across passes (text K|V cache) or by the caller (captured activations)
 };
 
 struct Wt {
   size_t fwd_off = 0, bwd_off = 0;   // element offsets (16-bit arena, or f32 arena when f32)
-  int N = 0, K = 0, taps = 1;
+  int N = 0, K = 0, taps = 1;        // (pad_bwd: the input-gradient copy has align_up(K, 128) rows, zero past K)
   bool has_bwd = true, f32 = false;
   int glu_F = 0;                     // > 0: the rows are the [2F] value | gate rows of a GEGLU projection, stored in the paired order (glu_col)
 };
@@ -77,9 +79,20 @@ struct Op {
   int ln_fold = -1, folded = 0;
   long ln_s_off = -1, ln_t_off = -1;
   // GEGLU fused into the GEMMs around it: on the ff.net.0.proj GEMM, glu_op = index of the OP_GEGLU op that consumes its output
-  // (the epilogue writes that op's output as well); on the ff.net.2 GEMM, glub_op = the OP_GEGLU op that produced its input (its
-  // input-gradient GEMM writes the gradient of the pre-activations directly)
+  // (the epilogue writes that op's output as well); on the folded ff.net.2 + proj_out GEMM, glub_op = the OP_GEGLU op that
+  // produced its input (its input-gradient GEMM writes the gradient of the pre-activations directly) and in1 = the feed-forward
+  // input t2, the other column window of its A operand (FfFold)
   int glu_op = -1, glub_op = -1;
+};
+
+// A transformer's proj_out folded into its ff.net.2 (the feed-forward output t3 = ff.net.2(g) + t2 has no other reader, and
+// both maps are linear):  out = proj_out(t3) + x = [g | t2] . [W_po W_ffo | W_po]^T + (W_po b_ffo + b_po) + x,
+// one GEMM with K = 5C over the tensor [rows][5C] whose column windows are g (GEGLU output, [0, 4C)) and t2 ([4C, 5C)).
+// The unfolded parameters keep their own storage (what dh_unet_load_param fills); fold_ff rebuilds the folded weight
+// (forward [C][5C] and input-gradient [5C][C] copies) and bias from them whenever a parameter changes.
+struct FfFold {
+  int wt_po = -1, wt_ffo = -1, wt = -1;       // proj_out [C][C] (forward copy only), ff.net.2 [C][4C], the folded weight
+  long b_po = -1, b_ffo = -1, bias = -1;      // f32 arena: proj_out / ff.net.2 biases, the folded bias
 };
 
 }  // namespace dh
@@ -93,6 +106,7 @@ struct dh_unet {
   std::vector<Wt> wts;
   std::vector<ParamInfo> params;
   std::vector<Op> ops;
+  std::vector<FfFold> ffolds;
   std::map<std::string, int> pindex;
   // arena sizes (elements)
   size_t w16_elems = 0, pf_elems = 0, act_elems = 0, grad_elems = 0, f32_elems = 0;
@@ -157,9 +171,14 @@ struct Builder {
   // (offsets are assigned when the tape is complete: layout_tensors)
   int tensor(int rows, int C, bool req_grad = true) {
     Ten t;
-    t.rows = rows; t.C = C; t.req_grad = req_grad;
+    t.rows = rows; t.C = C; t.ld = C; t.req_grad = req_grad;
     u.tens.push_back(t);
     return (int)u.tens.size() - 1;
+  }
+  // tensor t's activation becomes columns [col, col + C) of tensor `root` (same rows)
+  void set_view(int t, int root, int col) {
+    Ten& tt = u.tens[t];
+    tt.view = root; tt.col = col; tt.ld = u.tens[root].C;
   }
   size_t f32_slot(size_t n) { size_t o = u.f32_elems; u.f32_elems += align_up(n, 64); return o; }
 
@@ -179,12 +198,12 @@ struct Builder {
     u.pindex[name] = (int)u.params.size();
     u.params.push_back(p);
   }
-  int weight(int N, int K, int taps = 1, bool has_bwd = true, bool f32 = false) {
+  int weight(int N, int K, int taps = 1, bool has_bwd = true, bool f32 = false, bool pad_bwd = false) {
     Wt w;
     w.N = N; w.K = K; w.taps = taps; w.has_bwd = has_bwd; w.f32 = f32;
     size_t& arena = f32 ? u.pf_elems : u.w16_elems;
     w.fwd_off = arena; arena += align_up((size_t)N * K, 128);
-    if (has_bwd) { w.bwd_off = arena; arena += align_up((size_t)N * K, 128); }
+    if (has_bwd) { w.bwd_off = arena; arena += align_up((size_t)N * (pad_bwd ? align_up((size_t)K, 128) : (size_t)K), 128); }
     u.wts.push_back(w);
     return (int)u.wts.size() - 1;
   }
@@ -330,7 +349,11 @@ struct Builder {
     c.out = tensor(N, C);
     c.lse_off = f32_slot((size_t)maxB * heads * N);
     u.ops.push_back(c);
+    // the feed-forward input t2 and the GEGLU output g are column windows of one tensor [rows][5C] (g | t2): the A operand of
+    // the folded ff.net.2 + proj_out GEMM (FfFold)
+    const int tg = tensor(N, 5 * C, false);
     int t2 = linear(c.out, b + ".attn2.to_out.0", C, true, t1);
+    set_view(t2, tg, 4 * C);
     // feed forward (GEGLU)
     int n3 = ln(t2, b + ".norm3");
     int gg = linear(n3, b + ".ff.net.0.proj", 8 * C, true, -1);
@@ -343,11 +366,24 @@ struct Builder {
     u.params[u.pindex[b + ".ff.net.0.proj.bias"]].glu_F = 4 * C;
     Op g;
     g.type = OP_GEGLU; g.in0 = gg; g.out = tensor(N, 4 * C);
+    set_view(g.out, tg, 0);
     u.ops.push_back(g);
     u.ops[ff1].glu_op = (int)u.ops.size() - 1;
-    int t3 = linear(g.out, b + ".ff.net.2", C, true, t2);
+    // ff.net.2 and proj_out: parameter storage for the fold only (no op reads them)
+    FfFold f;
+    f.wt_ffo = weight(C, 4 * C);                  // (its input-gradient copy [4C][C] is the B operand of the fold's product)
+    bind_mat(b + ".ff.net.2.weight", f.wt_ffo, C, 0, 4 * C, 1);
+    f.b_ffo = param_f32(b + ".ff.net.2.bias", C);
+    f.wt_po = weight(C, C, 1, false);
+    bind_mat(pre + ".proj_out.weight", f.wt_po, C, 0, C, 1);
+    f.b_po = param_f32(pre + ".proj_out.bias", C);
+    f.wt = weight(C, 5 * C, 1, true, false, true);   // (input-gradient copy padded to whole 128-row tiles: the backward's last column tile)
+    f.bias = (long)u.pf_elems; u.pf_elems += align_up((size_t)C, 64);
+    u.ffolds.push_back(f);
+    const int out = linear_w(tg, f.wt, f.bias, x);
     u.ops.back().glub_op = u.ops[ff1].glu_op;
-    return linear(t3, pre + ".proj_out", C, true, x);
+    u.ops.back().in1 = t2;
+    return out;
   }
 };
 
@@ -368,6 +404,7 @@ void count_fused(const dh_unet_config& c, int& temb_total, int& kv_total) {
 }
 
 static void layout_tensors(dh_unet& u);
+static size_t ff_fold_scratch(int C);
 
 int build(dh_unet& u) {
   const dh_unet_config& c = u.cfg;
@@ -483,6 +520,7 @@ int build(dh_unet& u) {
   size_t biggest = 0;
   for (const Ten& t : u.tens) biggest = std::max(biggest, (size_t)t.rows * t.C * c.max_diff_batch);
   u.scratch_elems = biggest * 4 + 1024;
+  for (const FfFold& f : u.ffolds) u.scratch_elems = std::max(u.scratch_elems, ff_fold_scratch(u.wts[f.wt_po].N));
   u.partial_elems = std::max<size_t>((size_t)48 << 20, biggest * 2);
   u.small_elems = (size_t)c.max_batch * 64 * 4096 + (size_t)c.max_batch * c.norm_groups * 4 + 4096;
   return DH_OK;
@@ -498,6 +536,8 @@ int build(dh_unet& u) {
 //     in tape order.  The batched CFG pass (B = 2 K) runs in a few hundred MB this way instead of needing every slot doubled.
 //   persistent tensors (text, text K|V: cached across passes; the three captured activations: read by the caller after the pass)
 //     keep ONE slot of max_batch items in both layouts and are never shared.
+//   column windows (Ten::view) live inside the tensor they are a window of: reading or writing one is a use of that tensor; their
+//     gradients have dense slots of their own.
 static void layout_tensors(dh_unet& u) {
   const size_t maxB = (size_t)u.cfg.max_batch, maxBd = (size_t)u.cfg.max_diff_batch;
   const int nt = (int)u.tens.size(), nops = (int)u.ops.size();
@@ -505,9 +545,10 @@ static void layout_tensors(dh_unet& u) {
   u.tens[u.t_kv].persistent = true;
   for (int i = 0; i < 3; ++i)
     if (u.act_ids[i] >= 0) u.tens[u.act_ids[i]].persistent = true;
+  auto root = [&](int t) { return t >= 0 && u.tens[t].view >= 0 ? u.tens[t].view : t; };
   std::vector<int> first(nt, nops), last(nt, -1);
-  auto rd = [&](int t, int oi) { if (t >= 0) { last[t] = std::max(last[t], oi); first[t] = std::min(first[t], oi); } };
-  auto wr = [&](int t, int oi) { if (t >= 0) { first[t] = std::min(first[t], oi); last[t] = std::max(last[t], oi); } };
+  auto rd = [&](int t, int oi) { t = root(t); if (t >= 0) { last[t] = std::max(last[t], oi); first[t] = std::min(first[t], oi); } };
+  auto wr = [&](int t, int oi) { t = root(t); if (t >= 0) { first[t] = std::min(first[t], oi); last[t] = std::max(last[t], oi); } };
   for (int oi = 0; oi < nops; ++oi) {
     const Op& o = u.ops[oi];
     rd(o.in0, oi); rd(o.in1, oi); rd(o.res, oi); wr(o.out, oi);
@@ -516,14 +557,18 @@ static void layout_tensors(dh_unet& u) {
   }
   // a tensor nothing in the tape writes (an input) or that the caller reads afterwards stays for the whole pass
   std::vector<char> written(nt, 0);
-  for (const Op& o : u.ops) { if (o.out >= 0) written[o.out] = 1; if (o.glu_op >= 0) written[u.ops[o.glu_op].out] = 1; }
+  for (const Op& o : u.ops) { if (o.out >= 0) written[root(o.out)] = 1; if (o.glu_op >= 0) written[root(u.ops[o.glu_op].out)] = 1; }
   for (int t = 0; t < nt; ++t)
-    if (!written[t] || t == u.t_final) { first[t] = 0; last[t] = nops; u.tens[t].persistent = u.tens[t].persistent || !written[t]; }
+    if (u.tens[t].view < 0 && (!written[t] || t == u.t_final)) {
+      first[t] = 0; last[t] = nops; u.tens[t].persistent = u.tens[t].persistent || !written[t];
+    }
   // saved layout + persistent slots
   u.act_elems = 0; u.grad_elems = 0;
   for (Ten& t : u.tens) {
-    t.off = u.act_elems;
-    u.act_elems += align_up((size_t)t.rows * t.C * (t.persistent ? maxB : maxBd), 128);
+    if (t.view < 0) {
+      t.off = u.act_elems;
+      u.act_elems += align_up((size_t)t.rows * t.C * (t.persistent ? maxB : maxBd), 128);
+    }
     if (t.req_grad) { t.goff = u.grad_elems; u.grad_elems += align_up((size_t)t.rows * t.C * maxBd, 128); }
   }
   // forward-only layout: first fit among the tensors alive at the definition point
@@ -538,6 +583,7 @@ static void layout_tensors(dh_unet& u) {
   for (const Live& l : live) fo_end = std::max(fo_end, l.end);
   for (int t : order) {
     Ten& tt = u.tens[t];
+    if (tt.view >= 0) continue;                                      // (placed with the tensor it is a window of, below)
     if (tt.persistent) { tt.off_fo = tt.off; continue; }
     if (last[t] < 0) { tt.off_fo = 0; continue; }                    // never touched by the tape
     const size_t size = align_up((size_t)tt.rows * tt.C * maxB, 128);
@@ -556,6 +602,11 @@ static void layout_tensors(dh_unet& u) {
   }
   u.fo_elems = fo_end;
   u.act_elems = std::max(u.act_elems, fo_end);
+  for (Ten& t : u.tens)
+    if (t.view >= 0) {
+      const Ten& r = u.tens[t.view];
+      t.off = r.off + t.col; t.off_fo = r.off_fo + t.col; t.persistent = r.persistent;
+    }
 }
 
 // torch layout [N][C][taps] f32 -> forward matrix rows [row_off, row_off+N) x K = taps*C (k = tap*C + c; tiled 3x3:
@@ -650,6 +701,66 @@ static bool use_ln_fold(const dh_unet* u, int B) {
   return (long)B * u->cfg.sample_size * u->cfg.sample_size <= lim;
 }
 
+// ---- proj_out folded into ff.net.2 (FfFold) --------------------------------------------------------------------------
+// tiled [N][K] -> plain row-major [N][K]
+template <class D>
+__global__ void k_untile(const D* src, int N, int K, D* dst) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)N * K) return;
+  const int n = (int)(idx / K), k = (int)(idx - (size_t)n * K);
+  dst[idx] = src[wt_index(n, k, K)];
+}
+// folded weight [C][5C] = [P | W_po] (P = W_po W_ffo, plain [C][4C]; W_po plain [C][C]) into the forward copy (tiled, K = 5C)
+// and the input-gradient copy (tiled [5C][C]; its padding rows stay zero)
+template <class D>
+__global__ void k_pack_ff_fold(const D* prod, const D* po, int C, D* fwd, D* bwd) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = 5 * C;
+  if (idx >= (size_t)C * K) return;
+  const int n = (int)(idx / K), k = (int)(idx - (size_t)n * K);
+  const D v = k < 4 * C ? prod[(size_t)n * 4 * C + k] : po[(size_t)n * C + k - 4 * C];
+  fwd[wt_index(n, k, K)] = v;
+  bwd[wt_index(k, n, C)] = v;
+}
+// folded bias b[n] = sum_j W_po[n][j] b_ffo[j] + b_po[n] (the stored 16-bit W_po, f32 accumulate); one workgroup per n
+template <class D>
+__global__ void __launch_bounds__(256) k_fold_ff_bias(const D* po, int C, const float* b_ffo, const float* b_po, float* out) {
+  __shared__ float sm[8];
+  const int n = blockIdx.x;
+  float s = 0.f;
+  for (int j = threadIdx.x; j < C; j += blockDim.x) s += to_f32<D>(po[(size_t)n * C + j]) * b_ffo[j];
+  s = block_sum(s, sm);
+  if (threadIdx.x == 0) out[n] = s + b_po[n];
+}
+
+// scratch elements the fold needs: W_po and the product, plain
+static size_t ff_fold_scratch(int C) { return align_up((size_t)C * C, 128) + (size_t)4 * C * C; }
+
+template <class D>
+static void fold_ff_t(dh_unet* u, hipStream_t st) {
+  for (const FfFold& f : u->ffolds) {
+    const Wt& po = u->wts[f.wt_po];
+    const Wt& ffo = u->wts[f.wt_ffo];
+    const Wt& wf = u->wts[f.wt];
+    const int C = po.N;
+    D* po_plain = (D*)u->scratch;
+    D* prod = po_plain + align_up((size_t)C * C, 128);
+    hipLaunchKernelGGL((k_untile<D>), dim3(cdiv(C * C, 256)), dim3(256), 0, st, (const D*)(u->w16 + po.fwd_off), C, C, po_plain);
+    // P = W_po W_ffo on the engine's own GEMM: A = W_po rows, B operand = the input-gradient copy of ff.net.2 ([4C][C] = W_ffo^T,
+    // tiled); f32 accumulate, rounded once to the storage type
+    GemmArgs g;
+    g.A = po_plain; g.lda = C;
+    g.W = u->w16 + ffo.bwd_off;
+    g.mode = A_DENSE; g.M = C; g.N = 4 * C; g.K = C;
+    g.C = prod; g.ldc = 4 * C;
+    launch_gemm(u->dtype, g, st);
+    hipLaunchKernelGGL((k_pack_ff_fold<D>), dim3(cdiv(5 * C * C, 256)), dim3(256), 0, st, (const D*)prod, (const D*)po_plain, C,
+                       (D*)(u->w16 + wf.fwd_off), (D*)(u->w16 + wf.bwd_off));
+    hipLaunchKernelGGL((k_fold_ff_bias<D>), dim3(C), dim3(256), 0, st, (const D*)po_plain, C, u->pf + f.b_ffo, u->pf + f.b_po,
+                       u->pf + f.bias);
+  }
+}
+
 static void fold_layernorms(dh_unet* u, hipStream_t st) {
   { int cmax = 0;
     for (const Op& o : u->ops) if (o.type == OP_LN) cmax = std::max(cmax, u->tens[o.in0].C);
@@ -669,6 +780,8 @@ static void fold_layernorms(dh_unet* u, hipStream_t st) {
       hipLaunchKernelGGL((k_fold_ln<bf16>), dim3(w.N), dim3(256), 0, st, (const bf16*)(u->w16 + w.bwd_off), w.N, u->pf + l.gamma_off,
                          u->pf + l.beta_off, bias, (bf16*)(u->w16 + w.fwd_off), w.K, u->pf + g.ln_s_off, u->pf + g.ln_t_off);
   }
+  if (u->dtype == DH_DTYPE_F16) fold_ff_t<f16>(u, st);
+  else fold_ff_t<bf16>(u, st);
   u->fold_dirty = false;
 }
 
@@ -843,21 +956,21 @@ static void fill_gemm(dh_unet* u, const Op& o, int B, GemmArgs& g) {
   const Wt& w = u->wts[o.wt];
   const Ten& ti = u->tens[o.in0];
   const Ten& to = u->tens[o.out];
-  g.A = u->aptr(o.in0) + o.in_col; g.lda = ti.C;
+  g.A = u->aptr(o.in0) + o.in_col; g.lda = ti.ld;
   g.W = u->w16 + w.fwd_off;
   g.M = B * to.rows; g.N = w.N; g.K = w.K;
   g.mode = o.mode; g.Hin = o.Hin; g.Win = o.Win; g.Cin = o.Cin; g.Hout = o.Hout; g.Wout = o.Wout;
   g.stride = o.stride; g.up = o.up;
   g.bias = o.bias_off >= 0 ? u->pf + o.bias_off : nullptr;
   if (o.rowvec_off >= 0) { g.rowvec = u->f32a + o.rowvec_off; g.rowvec_ld = o.rowvec_ld; g.rows_per_batch = to.rows; }
-  if (o.res >= 0) { g.R = u->aptr(o.res); g.ldr = u->tens[o.res].C; }
-  g.C = u->aptr(o.out); g.ldc = to.C;
+  if (o.res >= 0) { g.R = u->aptr(o.res); g.ldr = u->tens[o.res].ld; }
+  g.C = u->aptr(o.out); g.ldc = to.ld;
   g.act_silu = o.act_silu;
   g.partial = u->partial; g.partial_elems = u->partial_elems;
   if (o.ln_fold >= 0) {
     const Op& l = u->ops[o.ln_fold];
     if (use_ln_fold(u, B)) {     // A = the LayerNorm's INPUT; the normalisation happens in the epilogue (bias is inside ln_t)
-      g.A = u->aptr(l.in0); g.lda = u->tens[l.in0].C;
+      g.A = u->aptr(l.in0); g.lda = u->tens[l.in0].ld;
       g.bias = nullptr;
       g.ln_s = u->pf + o.ln_s_off; g.ln_t = u->pf + o.ln_t_off; g.ln_stats = u->f32a + l.stats_off; g.ln_eps = l.eps;
     } else {
@@ -907,7 +1020,7 @@ static void forward_ops(dh_unet* u, int B, int n_ops, int first_op, bool kv_hit,
         if (o.glu_op >= 0 && o.glu_op < n_ops) {
           // the GEGLU that follows runs in this GEMM's epilogue; the pre-activations go to memory only for a backward pass
           const Op& ge = u->ops[o.glu_op];
-          g.glu_y = u->aptr(ge.out); g.glu_ldy = u->tens[ge.out].C;
+          g.glu_y = u->aptr(ge.out); g.glu_ldy = u->tens[ge.out].ld;
           if (!save) g.C = nullptr;
         }
         u->flops_fwd += launch_gemm(dt, g, st);
@@ -927,7 +1040,7 @@ static void forward_ops(dh_unet* u, int B, int n_ops, int first_op, bool kv_hit,
         // (a folded LayerNorm on the large-batch path normalises without the affine part: it sits in the GEMM's weights)
         launch_layernorm_fwd(dt, u->aptr(o.in0), u->pf + (o.folded ? u->ones_off : o.gamma_off),
                              u->pf + (o.folded ? u->zeros_off : o.beta_off), u->aptr(o.out),
-                             u->f32a + o.stats_off, B * t.rows, t.C, o.eps, st);
+                             u->f32a + o.stats_off, B * t.rows, t.C, o.eps, st, t.ld);
         break;
       }
       case OP_ATTN: {
@@ -1124,6 +1237,25 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
           else u->galias[o.res] = o.out;      // first contribution: share dOut (nobody reads it after this op)
           u->gready[o.res] = 1;
         }
+        if (o.glub_op >= 0 && o.in1 >= 0) {
+          // the folded ff.net.2 + proj_out (FfFold): dOut [W_po W_ffo | W_po] = [d g | d t2] in one launch.  The column tiles of
+          // d g run the GEGLU backward in their epilogue (d g never goes to memory: the gradient of the pre-activations does),
+          // those of d t2 store it into t2's gradient -- the residual path it fed through ff.net.2 before the fold
+          const Op& ge = u->ops[o.glub_op];
+          const int t2 = o.in1;
+          GemmArgs g;
+          g.A = u->gptr(o.out); g.lda = to.C;
+          g.W = u->w16 + w.bwd_off;
+          g.mode = A_DENSE; g.M = B * to.rows; g.N = w.K; g.K = w.N;
+          g.partial = u->partial; g.partial_elems = u->partial_elems;
+          g.glub_x = u->aptr(ge.in0); g.glub_dx = u->gptr(ge.in0); g.glub_f = u->tens[ge.out].C;
+          g.C = u->gptr(t2); g.ldc = u->tens[t2].C;
+          if (u->gready[t2]) { g.R = g.C; g.ldr = g.ldc; }
+          u->flops_bwd += launch_gemm(dt, g, st);
+          u->gready[ge.in0] = 1; u->gready[ge.out] = 1; u->gready[t2] = 1;
+          glub_done = o.glub_op;
+          break;
+        }
         if (!ti.req_grad || !w.has_bwd) break;
         if (o.in0 == u->t_text && !bw.need_text) break;
         GemmArgs g;
@@ -1141,7 +1273,7 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
             // the gradient being written is dy of the LayerNorm that is processed next and this GEMM is its only consumer:
             // a split-K reduce applies that LayerNorm's backward to the summed rows directly
             const Op& ln = u->ops[oi - 1];
-            g.lnb_x = u->aptr(ln.in0); g.lnb_gamma = u->pf + ln.gamma_off; g.lnb_stats = u->f32a + ln.stats_off;
+            g.lnb_x = u->aptr(ln.in0); g.lnb_ldx = u->tens[ln.in0].ld; g.lnb_gamma = u->pf + ln.gamma_off; g.lnb_stats = u->f32a + ln.stats_off;
             g.lnb_add = u->gready[ln.in0] ? u->gptr(ln.in0) : nullptr; g.lnb_dx = u->gptr(ln.in0);
             g.lnb_done = &lnb_have;
             lnb_for = oi - 1;
@@ -1152,20 +1284,12 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
             // GEMM's own epilogue leaves that GroupNorm's backward slice statistics, as for the convolutions below
             const Op& gn = u->ops[oi - 1];
             const Ten& tx = u->tens[gn.in0];
-            g.gnb_x = u->aptr(gn.in0); g.gnb_ldx = tx.C;
+            g.gnb_x = u->aptr(gn.in0); g.gnb_ldx = tx.ld;
             g.gnb_gamma = u->pf + gn.gamma_off; g.gnb_beta = u->pf + gn.beta_off; g.gnb_stats = u->f32a + gn.stats_off;
             g.gnb_silu = gn.silu;
             g.gn_part = u->small; g.gn_HW = tx.rows; g.gn_G = gn.groups; g.gn_done = &gnb_have;
             gnb_have = 0;
             gnb_for = oi - 1;
-          }
-          if (o.glub_op >= 0 && o.glub_op == oi - 1 && !u->gready[o.in0] && o.in_col == 0 && w.K == ti.C) {
-            // the gradient being written is dy of the GEGLU processed next and this GEMM is its only consumer: the epilogue
-            // applies the GEGLU backward to its tile and writes the gradient of the pre-activations (dy never goes to memory)
-            const Op& ge = u->ops[o.glub_op];
-            g.glub_x = u->aptr(ge.in0); g.glub_dx = u->gptr(ge.in0); g.C = nullptr;
-            u->gready[ge.in0] = 1;
-            glub_done = o.glub_op;
           }
           u->flops_bwd += launch_gemm(dt, g, st);
           u->gready[o.in0] = 1;
@@ -1200,7 +1324,7 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
             // epilogue) also leaves that GroupNorm's backward slice statistics
             const Op& gn = u->ops[gi];
             const Ten& tx = u->tens[gn.in0];
-            g.gnb_x = u->aptr(gn.in0); g.gnb_ldx = tx.C;
+            g.gnb_x = u->aptr(gn.in0); g.gnb_ldx = tx.ld;
             g.gnb_gamma = u->pf + gn.gamma_off; g.gnb_beta = u->pf + gn.beta_off; g.gnb_stats = u->f32a + gn.stats_off;
             g.gnb_silu = gn.silu;
             g.gn_part = u->small; g.gn_HW = tx.rows; g.gn_G = gn.groups; g.gn_done = &gnb_have;
@@ -1244,7 +1368,7 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
         }
         const Ten& t = u->tens[o.in0];
         launch_layernorm_bwd(dt, u->aptr(o.in0), u->gptr(o.out), u->pf + o.gamma_off, u->f32a + o.stats_off,
-                             u->gready[o.in0] ? u->gptr(o.in0) : nullptr, u->gptr(o.in0), B * t.rows, t.C, st);
+                             u->gready[o.in0] ? u->gptr(o.in0) : nullptr, u->gptr(o.in0), B * t.rows, t.C, st, t.ld);
         u->gready[o.in0] = 1;
         break;
       }
@@ -1405,5 +1529,26 @@ extern "C" int dh_dbg_unet_concat_ops(const dh_unet_config* cfg, int* out, int c
     ++n;
   }
   *n_out = n;
+  return DH_OK;
+}
+
+// test hook: fold i of the transformers' proj_out into ff.net.2 (FfFold, in tape order).  *n_folds = their number; *C = the
+// channel count of fold i (when 0 <= i < n); w (if set) receives its forward weight [C][5C] row-major in the storage type
+// ([W_po W_ffo | W_po]), bias (if set) its f32 bias [C].  The fold is brought up to date on `stream` first.
+extern "C" int dh_dbg_unet_ff_fold(dh_unet* u, int i, int* n_folds, int* C, void* w, float* bias, void* stream) {
+  DH_REQUIRE(u && n_folds && C, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  *n_folds = (int)u->ffolds.size();
+  *C = 0;
+  if (i < 0 || i >= (int)u->ffolds.size()) return DH_OK;
+  if (u->fold_dirty) fold_layernorms(u, st);
+  const FfFold& f = u->ffolds[i];
+  const Wt& wf = u->wts[f.wt];
+  *C = wf.N;
+  if (w)
+    hipLaunchKernelGGL((k_untile<unsigned short>), dim3(cdiv(wf.N * wf.K, 256)), dim3(256), 0, st,
+                       (const unsigned short*)(u->w16 + wf.fwd_off), wf.N, wf.K, (unsigned short*)w);
+  if (bias) DH_CHECK_HIP(hipMemcpyAsync(bias, u->pf + f.bias, (size_t)wf.N * 4, hipMemcpyDeviceToDevice, st));
+  DH_LAUNCH_CHECK();
   return DH_OK;
 }

@@ -65,20 +65,24 @@ struct GemmArgs {
   // lnb_x != NULL: the output (dense, full rows of width N, nothing accumulated into it) is the gradient dy of a LayerNorm
   // whose INPUT is lnb_x.  When the launch goes through the split-K reduce, that kernel applies the LayerNorm backward to
   // the summed rows and writes lnb_dx (+ lnb_add) instead of C; *lnb_done is set to 1 and the caller skips the LayerNorm op.
-  const void* lnb_x = nullptr; const float *lnb_gamma = nullptr, *lnb_stats = nullptr; const void* lnb_add = nullptr;
-  void* lnb_dx = nullptr; int* lnb_done = nullptr;
+  const void* lnb_x = nullptr; long lnb_ldx = 0; const float *lnb_gamma = nullptr, *lnb_stats = nullptr; const void* lnb_add = nullptr;
+  void* lnb_dx = nullptr; int* lnb_done = nullptr;      // (lnb_ldx: row stride of lnb_x, 0 = N)
   // GEGLU in the epilogue (dense, no split-K; N = 2F in the paired column layout, see glu_col):
   //   glu_y != NULL (forward, the ff.net.0.proj GEMM): y[m][o] = h * gelu(gate) of the ROUNDED pre-activations goes to glu_y
   //   ([M][F], row stride glu_ldy); C may be NULL then (pre-activations not saved: no backward follows);
   //   glub_x != NULL (the input-gradient GEMM of ff.net.2, N = F): the tile is dy of the GEGLU whose saved pre-activations are
   //   glub_x [M][2F]; d_value = dy gelu(gate), d_gate = dy h gelu'(gate) go to glub_dx [M][2F] (paired layout), C is not written
+  //   glub_f > 0 (column-split form, N > glub_f): only output columns [0, glub_f) are dy of that GEGLU (F = glub_f, glub_x /
+  //   glub_dx [M][2F]); columns [glub_f, N) take the plain epilogue into C at column n - glub_f (row stride ldc; C points at
+  //   that column block, R likewise).  W must be readable up to row align_up(N, 128) (zero rows past N).
   void* glu_y = nullptr; long glu_ldy = 0;
-  const void* glub_x = nullptr; void* glub_dx = nullptr;
+  const void* glub_x = nullptr; void* glub_dx = nullptr; int glub_f = 0;
 };
 // split-K reduce + LayerNorm backward in one pass over the slabs (f32 [splits][rows][C]); dy is rounded to the storage type
 // before it is used, exactly as the reduce + k_ln_bwd pair does
+// (ldx: row stride of x, 0 = C; dy / add / dx are dense)
 void launch_splitk_reduce_ln_bwd(int dtype, const float* partial, int splits, const void* x, const float* gamma,
-                                 const float* stats, const void* add, void* dx, int rows, int C, hipStream_t st);
+                                 const float* stats, const void* add, void* dx, int rows, int C, hipStream_t st, long ldx = 0);
 // D[m][n] = sum_k A(m,k) W[n][k] (+bias, +rowvec, silu, +R); returns algorithmic flops
 double launch_gemm(int dtype, const GemmArgs& a, hipStream_t st);
 bool gemm_profiling_on();   // HIP-event bracket active (bench roofline pass): graphs are bypassed
@@ -129,11 +133,12 @@ void launch_groupnorm_bwd(int dtype, const void* x, const void* dy, const float*
 // y = gelu(x) (erf form), n elements (the text tower's MLP)
 void launch_gelu(int dtype, const void* x, void* y, size_t n, hipStream_t st);
 // LayerNorm over C per row; stats [rows][2]
+// (ldx: row stride of x, 0 = C; the other operands are dense)
 void launch_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats,
-                          int rows, int C, float eps, hipStream_t st);
+                          int rows, int C, float eps, hipStream_t st, long ldx = 0);
 // dx = ln_bwd(dy) (+ add)   (add may alias nothing; dx written)
 void launch_layernorm_bwd(int dtype, const void* x, const void* dy, const float* gamma, const float* stats,
-                          const void* add, void* dx, int rows, int C, hipStream_t st);
+                          const void* add, void* dx, int rows, int C, hipStream_t st, long ldx = 0);
 // GEGLU: y[m][j] = h * gelu(g), h = x[m][glu_col(j, 0)], g = x[m][glu_col(j, 1)] (paired column layout)
 void launch_geglu_fwd(int dtype, const void* x, void* y, int rows, int F, hipStream_t st);
 void launch_geglu_bwd(int dtype, const void* x, const void* dy, void* dx, int rows, int F, hipStream_t st);

@@ -611,7 +611,7 @@ constexpr int LN_MAXCH = 8;
 
 template <class T, int NCH>      // NCH: 8-element chunks per lane (C <= 512 * NCH)
 __global__ void __launch_bounds__(256, NCH <= 3 ? 4 : 1) k_ln_fwd(const T* x, const float* gamma, const float* beta, T* y, float* stats, int rows, int C,
-                         float eps) {
+                         float eps, long ldx) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -622,7 +622,7 @@ __global__ void __launch_bounds__(256, NCH <= 3 ? 4 : 1) k_ln_fwd(const T* x, co
   for (int k = 0; k < NCH; ++k) {
     const int ch = lane + 64 * k;
     if (ch < nch) {
-      raw[k] = *reinterpret_cast<const uint4*>(x + (size_t)row * C + ch * 8);
+      raw[k] = *reinterpret_cast<const uint4*>(x + (size_t)row * ldx + ch * 8);
       const T* v = reinterpret_cast<const T*>(&raw[k]);
 #pragma unroll
       for (int i = 0; i < 8; ++i) s += to_f32<T>(v[i]);
@@ -662,18 +662,18 @@ __global__ void __launch_bounds__(256, NCH <= 3 ? 4 : 1) k_ln_fwd(const T* x, co
 // operand of the row live needed 272 registers: one wave per SIMD, 0.9 TB/s on the batched passes).
 template <class T, int NCH>      // NCH: 8-element chunks per lane (C <= 512 * NCH)
 __global__ void __launch_bounds__(256, NCH == 1 ? 8 : (NCH <= 3 ? 4 : 1)) k_ln_bwd(const T* x, const T* dy, const float* gamma, const float* stats,
-                                                                  const T* add, T* dx, int rows, int C) {
+                                                                  const T* add, T* dx, int rows, int C, long ldx) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int nch = C / 8;
-  const size_t base = (size_t)row * C;
+  const size_t base = (size_t)row * C, xbase = (size_t)row * ldx;
   uint4 rx[NCH], rd[NCH];
 #pragma unroll
   for (int k = 0; k < NCH; ++k) {
     const int ch = lane + 64 * k;
     if (ch < nch) {
-      rx[k] = *reinterpret_cast<const uint4*>(x + base + ch * 8);
+      rx[k] = *reinterpret_cast<const uint4*>(x + xbase + ch * 8);
       rd[k] = *reinterpret_cast<const uint4*>(dy + base + ch * 8);
     }
   }
@@ -730,7 +730,7 @@ __global__ void __launch_bounds__(256, NCH == 1 ? 8 : (NCH <= 3 ? 4 : 1)) k_ln_b
 // rounded to the storage type first, so the result equals the two-kernel path bit for bit.
 template <class T, int NCH>
 __global__ void __launch_bounds__(256, NCH == 1 ? 4 : (NCH <= 3 ? 2 : 1)) k_splitk_reduce_ln_bwd(const float* part, int splits, const T* x, const float* gamma,
-                                                                       const float* stats, const T* add, T* dx, int rows, int C) {
+                                                                       const float* stats, const T* add, T* dx, int rows, int C, long ldx) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -741,7 +741,7 @@ __global__ void __launch_bounds__(256, NCH == 1 ? 4 : (NCH <= 3 ? 2 : 1)) k_spli
 #pragma unroll
   for (int k = 0; k < NCH; ++k) {
     const int ch = lane + 64 * k;
-    if (ch < nch) rx[k] = *reinterpret_cast<const uint4*>(x + base + ch * 8);
+    if (ch < nch) rx[k] = *reinterpret_cast<const uint4*>(x + (size_t)row * ldx + ch * 8);
 #pragma unroll
     for (int i = 0; i < 8; ++i) d[k][i] = 0.f;
   }
@@ -831,10 +831,11 @@ __global__ void __launch_bounds__(256, NCH == 1 ? 4 : (NCH <= 3 ? 2 : 1)) k_spli
   }
 }
 void launch_splitk_reduce_ln_bwd(int dtype, const float* partial, int splits, const void* x, const float* gamma,
-                                 const float* stats, const void* add, void* dx, int rows, int C, hipStream_t st) {
+                                 const float* stats, const void* add, void* dx, int rows, int C, hipStream_t st, long ldx) {
+  if (ldx <= 0) ldx = C;
   // one row per wave; few rows (the 16x16 / 8x8 levels): one-wave blocks so that every row gets its own CU
   const int wpb = rows <= 1024 ? 1 : 4;      // (backward pass -0.4 %)
-#define DH_RLN(TT, N) hipLaunchKernelGGL((k_splitk_reduce_ln_bwd<TT, N>), dim3(cdiv(rows, wpb)), dim3(64 * wpb), 0, st, partial, splits, (const TT*)x, gamma, stats, (const TT*)add, (TT*)dx, rows, C)
+#define DH_RLN(TT, N) hipLaunchKernelGGL((k_splitk_reduce_ln_bwd<TT, N>), dim3(cdiv(rows, wpb)), dim3(64 * wpb), 0, st, partial, splits, (const TT*)x, gamma, stats, (const TT*)add, (TT*)dx, rows, C, ldx)
   const int n = C <= 512 ? 1 : (C <= 1024 ? 2 : (C <= 1536 ? 3 : LN_MAXCH));
   if (dtype == DH_DTYPE_F16) {
     if (n == 1) DH_RLN(f16, 1); else if (n == 2) DH_RLN(f16, 2); else if (n == 3) DH_RLN(f16, 3); else DH_RLN(f16, LN_MAXCH);
@@ -845,9 +846,10 @@ void launch_splitk_reduce_ln_bwd(int dtype, const float* partial, int splits, co
 }
 
 void launch_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats,
-                          int rows, int C, float eps, hipStream_t st) {
+                          int rows, int C, float eps, hipStream_t st, long ldx) {
   DH_ABLATE(1);
-#define DH_LN_FWD(TT, N) hipLaunchKernelGGL((k_ln_fwd<TT, N>), dim3(cdiv(rows, 4)), dim3(256), 0, st, (const TT*)x, gamma, beta, (TT*)y, stats, rows, C, eps)
+  if (ldx <= 0) ldx = C;
+#define DH_LN_FWD(TT, N) hipLaunchKernelGGL((k_ln_fwd<TT, N>), dim3(cdiv(rows, 4)), dim3(256), 0, st, (const TT*)x, gamma, beta, (TT*)y, stats, rows, C, eps, ldx)
   const int n = C <= 512 ? 1 : (C <= 1024 ? 2 : (C <= 1536 ? 3 : LN_MAXCH));
   if (dtype == DH_DTYPE_F16) {
     if (n == 1) DH_LN_FWD(f16, 1); else if (n == 2) DH_LN_FWD(f16, 2); else if (n == 3) DH_LN_FWD(f16, 3); else DH_LN_FWD(f16, LN_MAXCH);
@@ -857,10 +859,11 @@ void launch_layernorm_fwd(int dtype, const void* x, const float* gamma, const fl
 #undef DH_LN_FWD
 }
 void launch_layernorm_bwd(int dtype, const void* x, const void* dy, const float* gamma, const float* stats,
-                          const void* add, void* dx, int rows, int C, hipStream_t st) {
+                          const void* add, void* dx, int rows, int C, hipStream_t st, long ldx) {
   DH_ABLATE(1);
+  if (ldx <= 0) ldx = C;
   const int wpb = rows <= 1024 ? 1 : 4;      // (backward pass -0.4 %)
-#define DH_LN_BWD(TT, N) hipLaunchKernelGGL((k_ln_bwd<TT, N>), dim3(cdiv(rows, wpb)), dim3(64 * wpb), 0, st, (const TT*)x, (const TT*)dy, gamma, stats, (const TT*)add, (TT*)dx, rows, C)
+#define DH_LN_BWD(TT, N) hipLaunchKernelGGL((k_ln_bwd<TT, N>), dim3(cdiv(rows, wpb)), dim3(64 * wpb), 0, st, (const TT*)x, (const TT*)dy, gamma, stats, (const TT*)add, (TT*)dx, rows, C, ldx)
   const int n = C <= 512 ? 1 : (C <= 1024 ? 2 : (C <= 1536 ? 3 : LN_MAXCH));
   if (dtype == DH_DTYPE_F16) {
     if (n == 1) DH_LN_BWD(f16, 1); else if (n == 2) DH_LN_BWD(f16, 2); else if (n == 3) DH_LN_BWD(f16, 3); else DH_LN_BWD(f16, LN_MAXCH);

@@ -37,6 +37,13 @@ class TextConfig(ctypes.Structure):
                 ("max_batch", c_i), ("eps", c_f), ("dtype", c_i)]
 
 
+class EnergyItem(ctypes.Structure):
+    """dh_energy_item: one item of dh_energy_fwd_bwd_planned_batch"""
+    _fields_ = [("cur", c_p), ("orig", c_p), ("plan", c_p), ("plan_bytes", c_sz), ("bg_orig", c_p), ("bg_trans", c_p),
+                ("loss_out", c_p), ("grad", c_p), ("n_pairs", c_i), ("n_bg_orig", c_i), ("n_bg_trans", c_i),
+                ("fg_w", c_f), ("bg_w", c_f), ("grad_scale", c_f)]
+
+
 # name -> (restype, argtypes); mirrors include/diffhandles_hip.h one to one
 SIGNATURES = {
     "dh_last_error": (ctypes.c_char_p, []),
@@ -63,6 +70,8 @@ SIGNATURES = {
     "dh_energy_planned_workspace_bytes": (c_i, [c_i, c_i, ctypes.POINTER(c_sz)]),
     "dh_energy_fwd_bwd_planned": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_i, c_p, c_i, c_p, c_i, c_f, c_f, c_f,
                                         c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "dh_energy_planned_batch_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
+    "dh_energy_fwd_bwd_planned_batch": (c_i, [ctypes.POINTER(EnergyItem), c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "dh_unet_create": (c_i, [ctypes.POINTER(UNetConfig), ctypes.POINTER(c_p)]),
     "dh_unet_create_shared": (c_i, [c_p, c_i, c_p, ctypes.POINTER(c_p)]),
     "dh_unet_destroy": (None, [c_p]),

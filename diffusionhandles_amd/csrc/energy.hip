@@ -389,65 +389,11 @@ constexpr int CQ_SL = COLSUM_S / 4;          // slices per quarter
 template <class T>
 __global__ void __launch_bounds__(8 * CQ_SL) k_colsum_q(const T* X1, const int* list1, int n1, const T* X2, const int* list2, int n2,
                                                        int C, float* partq) {
-  __shared__ float sp[CQ_SL][8][8];
-  const int z = blockIdx.z, q = blockIdx.y, sloc = threadIdx.x >> 3, cl = threadIdx.x & 7;
-  const int ch = blockIdx.x * 8 + cl;                       // 8-channel chunk
+  const int z = blockIdx.z;
   const T* X = z ? X2 : X1;
   const int* list = z ? list2 : list1;
   const int n = z ? n2 : n1;
-  const int sl = q * CQ_SL + sloc;
-  const int per = (n + COLSUM_S - 1) / COLSUM_S, b = sl * per, e = b + per < n ? b + per : n;
-  float acc[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-  if (ch * 8 < C) {
-    int k = b;
-    for (; k + 16 <= e; k += 16) {          // 16 gathers in flight; the adds keep the list order
-      int id[16];
-      uint4 raw[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) id[j] = list[k + j];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) raw[j] = *reinterpret_cast<const uint4*>(X + (size_t)id[j] * C + ch * 8);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const T* v = reinterpret_cast<const T*>(&raw[j]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] += to_f32<T>(v[i]);
-      }
-    }
-    if (k + 8 <= e) {
-      int id[8];
-      uint4 raw[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) id[j] = list[k + j];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) raw[j] = *reinterpret_cast<const uint4*>(X + (size_t)id[j] * C + ch * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const T* v = reinterpret_cast<const T*>(&raw[j]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] += to_f32<T>(v[i]);
-      }
-      k += 8;
-    }
-    for (; k < e; ++k) {
-      const uint4 raw = *reinterpret_cast<const uint4*>(X + (size_t)list[k] * C + ch * 8);
-      const T* v = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] += to_f32<T>(v[i]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) sp[sloc][cl][i] = acc[i];
-  __syncthreads();
-  if (threadIdx.x < 64) {                   // (chunk, channel): the quarter's slices in slice order
-    const int c2 = threadIdx.x >> 3, i = threadIdx.x & 7;
-    float a = 0.f;
-    for (int s = 0; s < CQ_SL; ++s) a += sp[s][c2][i];
-    const int c = (blockIdx.x * 8 + c2) * 8 + i;
-    if (c < C) partq[((size_t)z * 4 + q) * C + c] = a;
-  }
+#include "colsum_q_body.inc"
 }
 
 // thread = (target cell, 8-channel chunk); block = 256 / (C/8) cells
@@ -456,93 +402,73 @@ __global__ void __launch_bounds__(256) k_energy_grad(const T* orig, const T* cur
                                                      const int* src, const int* mult, const uint8_t* bgflag, const float* partq, int n1, int n2,
                                                      int C, int G2, float coef_fg,
                                                      float coef_bg, int use_bg, float scale, TG* grad, double* loss_part, double* bg_loss) {
+#include "energy_grad_body.inc"
+}
+
+// ---- K items in one launch pair (dh_energy_fwd_bwd_planned_batch) ---------------------------------------------------------
+// Everything an item's kernels need, carved and derived on the host; the table travels BY VALUE in the kernel arguments
+// (16 x 160 B: no device allocation, no copy, no synchronisation on the step path) and a workgroup reads its item's row
+// through scalar loads (the item index is a block index).  The bodies are the single kernels' own text.
+constexpr int ENERGY_MAX_ITEMS = 16;
+struct EnergyItem {
+  const void *orig, *cur;
+  const int *off, *ucnt, *src, *mult;
+  const uint8_t* bgflag;
+  const int *list1, *list2;
+  float* partq;
+  void* grad;
+  double *loss_part, *bg_loss;
+  float* loss_out;
+  int n1, n2, use_bg, n_fg_part;
+  float coef_fg, coef_bg, scale, fg_norm, bg_norm, fg_w, bg_w;
+};
+struct EnergyBatch {
+  EnergyItem it[ENERGY_MAX_ITEMS];
+};
+
+// grid (C / 64, 4 quarters, 2 K): list z & 1 of item z / 2; an item without a background term has no work here
+template <class T>
+__global__ void __launch_bounds__(8 * CQ_SL) k_colsum_q_batch(const EnergyBatch tab, int C) {
+  const EnergyItem& it = tab.it[blockIdx.z >> 1];
+  if (!it.use_bg) return;
+  const int z = blockIdx.z & 1;
+  const T* X = (const T*)(z ? it.cur : it.orig);
+  const int* list = z ? it.list2 : it.list1;
+  const int n = z ? it.n2 : it.n1;
+  float* partq = it.partq;
+#include "colsum_q_body.inc"
+}
+
+// grid (blocks of cells, K): item blockIdx.y, the cells of blockIdx.x
+template <class T, class TG>
+__global__ void __launch_bounds__(256) k_energy_grad_batch(const EnergyBatch tab, int C, int G2) {
+  const EnergyItem& it = tab.it[blockIdx.y];
+  const T *orig = (const T*)it.orig, *cur = (const T*)it.cur;
+  const int *off = it.off, *ucnt = it.ucnt, *src = it.src, *mult = it.mult;
+  const uint8_t* bgflag = it.bgflag;
+  const float* partq = it.partq;
+  const int n1 = it.n1, n2 = it.n2, use_bg = it.use_bg;
+  const float coef_fg = it.coef_fg, coef_bg = it.coef_bg, scale = it.scale;
+  TG* grad = (TG*)it.grad;
+  double *loss_part = it.loss_part, *bg_loss = it.bg_loss;
+#include "energy_grad_body.inc"
+}
+
+// one workgroup per item that asked for its loss values: k_final_loss's sums
+__global__ void k_final_loss_batch(const EnergyBatch tab) {
   __shared__ double sm[4];
-  const int nch = C / 8, cpb = (int)blockDim.x / nch;
-  const int lc = threadIdx.x / nch, ch = threadIdx.x - lc * nch;
-  const int cell = blockIdx.x * cpb + lc;
-  double la = 0.0, lb = 0.0;
-  // prologue: sign of the difference of the two background means of this thread's 8 channels from the quarter sums of k_colsum_q
-  // (a 2 x 4 x C f32 table, L2-resident; every lane of a chunk reads the same 16 sectors) -- the arithmetic of k_global_diff
-  float sgn[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) sgn[i] = 0.f;
-  if (use_bg && lc < cpb) {
-    float qa[4][8], qb[4][8];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      *reinterpret_cast<float4*>(&qa[q][0]) = *reinterpret_cast<const float4*>(partq + (size_t)q * C + ch * 8);
-      *reinterpret_cast<float4*>(&qa[q][4]) = *reinterpret_cast<const float4*>(partq + (size_t)q * C + ch * 8 + 4);
-      *reinterpret_cast<float4*>(&qb[q][0]) = *reinterpret_cast<const float4*>(partq + (size_t)(4 + q) * C + ch * 8);
-      *reinterpret_cast<float4*>(&qb[q][4]) = *reinterpret_cast<const float4*>(partq + (size_t)(4 + q) * C + ch * 8 + 4);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const float a = ((qa[0][i] + qa[1][i]) + qa[2][i]) + qa[3][i];
-      const float b = ((qb[0][i] + qb[1][i]) + qb[2][i]) + qb[3][i];
-      const float d = a / (float)n1 - b / (float)n2;
-      sgn[i] = (float)((d > 0.f) - (d < 0.f));
-      if (blockIdx.x == 0 && lc == 0) lb += (double)fabsf(d);          // the loss of the term: once, by the first cell's lanes of block 0
-    }
-  }
-  if (lc < cpb && cell < G2) {
-    const uint4 ra = *reinterpret_cast<const uint4*>(cur + (size_t)cell * C + ch * 8);
-    const T* av = reinterpret_cast<const T*>(&ra);
-    float a[8];
-    int sg[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { a[i] = to_f32<T>(av[i]); sg[i] = 0; }
-    const int b = off[cell], e = b + ucnt[cell];
-    int k = b;
-    for (; k + 8 <= e; k += 8) {        // 8 distinct source rows in flight
-      int id[8], mu[8];
-      uint4 ro[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { id[j] = src[k + j]; mu[j] = mult[k + j]; }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ro[j] = *reinterpret_cast<const uint4*>(orig + (size_t)id[j] * C + ch * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const T* ov = reinterpret_cast<const T*>(&ro[j]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float d = to_f32<T>(ov[i]) - a[i];
-          la += (double)mu[j] * (double)fabsf(d);
-          sg[i] += mu[j] * ((d > 0.f) - (d < 0.f));
-        }
-      }
-    }
-    for (; k < e; ++k) {
-      const uint4 ro = *reinterpret_cast<const uint4*>(orig + (size_t)src[k] * C + ch * 8);
-      const int mu = mult[k];
-      const T* ov = reinterpret_cast<const T*>(&ro);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d = to_f32<T>(ov[i]) - a[i];
-        la += (double)mu * (double)fabsf(d);
-        sg[i] += mu * ((d > 0.f) - (d < 0.f));
-      }
-    }
-    const bool bg = use_bg && bgflag[cell];
-    TG o[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float g = 0.f;
-      if (b < e) g += -coef_fg * (float)sg[i];
-      if (bg) g += -coef_bg * sgn[i];
-      o[i] = from_f32<TG>(g * scale);
-    }
-    if (sizeof(TG) == 2) {
-      *reinterpret_cast<uint4*>(grad + (size_t)cell * C + ch * 8) = *reinterpret_cast<uint4*>(o);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) grad[(size_t)cell * C + ch * 8 + i] = o[i];
-    }
-  }
-  la = block_sum(la, sm);
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = la;
-  if (blockIdx.x == 0 && use_bg) {
-    lb = block_sum(lb, sm);
-    if (threadIdx.x == 0) bg_loss[0] = lb;
+  const EnergyItem& it = tab.it[blockIdx.x];
+  if (!it.loss_out) return;
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < it.n_fg_part; i += blockDim.x) a += it.loss_part[i];
+  for (int i = threadIdx.x; i < it.use_bg; i += blockDim.x) b += it.bg_loss[i];
+  a = block_sum(a, sm);
+  b = block_sum(b, sm);
+  if (threadIdx.x == 0) {
+    float fg = (float)(a * (double)it.fg_norm), bg = (float)(b * (double)it.bg_norm);
+    it.loss_out[0] = it.fg_w * fg + it.bg_w * bg;
+    it.loss_out[1] = fg;
+    it.loss_out[2] = bg;
   }
 }
 
@@ -722,6 +648,81 @@ extern "C" int dh_energy_fwd_bwd_planned(const void* cur, const void* orig, int 
   if (loss_out)
     hipLaunchKernelGGL(k_final_loss, dim3(1), dim3(256), 0, st, w.fg_part, n_pairs > 0 ? nblocks : 0, fg_norm, w.bg_part,
                        use_bg ? 1 : 0, bg_norm, fg_w, bg_w, loss_out);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_energy_planned_batch_workspace_bytes(int C, int grid, int n_items, size_t* bytes) {
+  DH_REQUIRE(C >= 1 && grid >= 1 && bytes, "bad arguments");
+  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items");
+  Arena a(nullptr, (size_t)-1);
+  PlannedWs w;
+  for (int e = 0; e < n_items; ++e) carve_planned(a, C, grid, w);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_energy_fwd_bwd_planned_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
+                                               int grad_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(items && workspace, "null pointer");
+  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items (larger batches are not split)");
+  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
+  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
+  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1, "bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  const int G2 = grid * grid;
+  const int cpb = 256 / (C / 8);
+  const int nblocks = cdiv(G2, cpb);
+  Arena aw(workspace, workspace_bytes);
+  EnergyBatch tab;
+  bool any_bg = false, any_loss = false;
+  for (int e = 0; e < n_items; ++e) {
+    const dh_energy_item& in = items[e];
+    EnergyItem& it = tab.it[e];
+    DH_REQUIRE(in.cur && in.orig && in.grad && in.plan, "null pointer in an item");
+    DH_REQUIRE(in.n_pairs >= 0, "bad sizes");
+    Arena ap(const_cast<void*>(in.plan), in.plan_bytes);
+    EnergyPlan p;
+    DH_REQUIRE(carve_plan(ap, grid, in.n_pairs, p), "plan buffer too small");
+    PlannedWs w;
+    DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
+    it.orig = in.orig; it.cur = in.cur;
+    it.off = p.off; it.ucnt = p.cnt; it.src = p.src; it.mult = p.mult; it.bgflag = p.bgflag;
+    it.list1 = in.bg_orig; it.list2 = in.bg_trans;
+    it.partq = w.partq; it.grad = in.grad; it.loss_part = w.fg_part; it.bg_loss = w.bg_part; it.loss_out = in.loss_out;
+    it.n1 = in.n_bg_orig; it.n2 = in.n_bg_trans;
+    it.fg_norm = in.n_pairs > 0 ? 1.f / ((float)C * (float)in.n_pairs) : 0.f;
+    it.bg_norm = 0.f; it.coef_bg = 0.f; it.use_bg = 0;
+    if (in.n_bg_orig > 0 && in.n_bg_trans > 0) {
+      DH_REQUIRE(in.bg_orig && in.bg_trans, "null bg list");
+      it.bg_norm = 1.f / (float)C;
+      it.coef_bg = in.bg_w * it.bg_norm / (float)in.n_bg_trans;
+      it.use_bg = 1;
+      any_bg = true;
+    }
+    it.coef_fg = in.fg_w * it.fg_norm;
+    it.scale = in.grad_scale;
+    it.n_fg_part = in.n_pairs > 0 ? nblocks : 0;
+    it.fg_w = in.fg_w; it.bg_w = in.bg_w;
+    any_loss = any_loss || in.loss_out != nullptr;
+  }
+  for (int e = n_items; e < ENERGY_MAX_ITEMS; ++e) tab.it[e] = tab.it[0];      // (never indexed: defined kernel arguments)
+  if (any_bg) {
+    if (dtype == DH_DTYPE_F16)
+      hipLaunchKernelGGL((k_colsum_q_batch<f16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
+    else
+      hipLaunchKernelGGL((k_colsum_q_batch<bf16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
+  }
+#define DH_EGB(T_)                                                                                                             \
+  do {                                                                                                                         \
+    if (grad_dtype == DH_DTYPE_F16) hipLaunchKernelGGL((k_energy_grad_batch<T_, f16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, C, G2);        \
+    else if (grad_dtype == DH_DTYPE_BF16) hipLaunchKernelGGL((k_energy_grad_batch<T_, bf16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, C, G2); \
+    else hipLaunchKernelGGL((k_energy_grad_batch<T_, float>), dim3(nblocks, n_items), dim3(256), 0, st, tab, C, G2);           \
+  } while (0)
+  if (dtype == DH_DTYPE_F16) DH_EGB(f16);
+  else DH_EGB(bf16);
+#undef DH_EGB
+  if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

@@ -94,6 +94,52 @@ class DiffusionHandles:
                                                                             bg_weight))
         return imgs, [d for d, _ in edits]
 
+    EDIT_FIELDS = ("depth", "prompt", "fg_mask", "bg_depth", "null_text_emb", "init_noise", "activations")
+
+    def transform_foregrounds(self, edits, use_input_depth_normalization=False):
+        """K edits of DIFFERENT images in batched passes (not in the reference).  edits: K dicts with the arguments of
+        transform_foreground (EDIT_FIELDS, rot_angle / rot_axis / translation, optional fg_weight / bg_weight).  Edits that name
+        the same image (the same depth, mask, background-depth and activation tensors) are re-projected together, once per
+        image; then one GuidedStableDiffuser.guided_inference_items.  Returns (images [K,3,H,W], [K disparities]) in input
+        order.  'pc' re-projection only; one resolution; needs an engine with max_batch >= 2K."""
+        from .depth_transform import reproject_edits
+        if self.conf.depth_transform_mode != "pc":
+            raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
+                                      "batched re-projection (only 'pc')")
+        K = len(edits)
+        if K < 1 or any(set(self.EDIT_FIELDS) - set(e) for e in edits):
+            raise ValueError(f"transform_foregrounds: needs at least one edit, each with {self.EDIT_FIELDS}")
+        for i, e in enumerate(edits):
+            if tuple(e["depth"].shape[-2:]) != tuple(edits[0]["depth"].shape[-2:]):
+                raise ValueError(f"transform_foregrounds: edit {i} has another resolution than edit 0 "
+                                 f"({tuple(e['depth'].shape[-2:])} / {tuple(edits[0]['depth'].shape[-2:])})")
+        unet = self.diffuser.unet
+        if unet is not None and (unet.max_batch < 2 * K or unet.max_diff_batch < K):
+            raise RuntimeError(f"engine max_batch {unet.max_batch} / max_diff_batch {unet.max_diff_batch} too small for {K} edits: "
+                               f"build the diffuser with max_batch >= {2 * K}")
+        Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
+        dflt = lambda v, d: d if v is None else v
+        groups = {}                  # image -> indices of its edits, in input order
+        for i, e in enumerate(edits):
+            key = (id(e["depth"]), id(e["fg_mask"]), id(e["bg_depth"])) + tuple(id(a) for a in e["activations"])
+            groups.setdefault(key, []).append(i)
+        reproj = [None] * K
+        with torch.no_grad():
+            for idx in groups.values():
+                e0 = edits[idx[0]]
+                tfs = [(dflt(edits[i].get("rot_angle"), 0.0), dflt(edits[i].get("rot_axis"), Y),
+                        dflt(edits[i].get("translation"), torch.zeros(3))) for i in idx]
+                res = reproject_edits(e0["depth"], e0["bg_depth"], e0["fg_mask"],
+                                      self.diffuser.get_depth_intrinsics(device=e0["depth"].device), tfs,
+                                      use_input_depth_normalization, device_correspondences=True)
+                for i, r in zip(idx, res):
+                    reproj[i] = r
+            items = [dict(latents=e["init_noise"], depth=d, uncond_embeddings=e["null_text_emb"], prompt=e["prompt"],
+                          activations_orig=e["activations"], correspondences=c) for e, (d, c) in zip(edits, reproj)]
+            imgs = self.diffuser.guided_inference_items(items, [e.get("fg_weight") for e in edits],
+                                                        [e.get("bg_weight") for e in edits])
+        return imgs, [d for d, _ in reproj]
+
     def transform_foreground(self, depth, prompt, fg_mask, bg_depth, null_text_emb, init_noise, activations,
                              rot_angle=None, rot_axis=None, translation=None, fg_weight=None, bg_weight=None,
                              use_input_depth_normalization=False):

@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from . import guidance_scale as _gs
 from .guided_diffuser import GuidedDiffuser
-from .losses import (EnergyPlan, energy_and_grad, energy_and_grad_planned,
+from .losses import (MAX_BATCH_ITEMS, EnergyPlan, energy_and_grad, energy_and_grad_planned, energy_and_grad_planned_batch,
                      process_correspondences as _process_correspondences)
 from .scheduler import DDIMScheduler
 from .unet import HipUNet, SD2_DEPTH
@@ -122,6 +122,9 @@ class GuidedStableDiffuser(GuidedDiffuser):
         # guided_step drives the engine through its own I/O buffers (no device copies / torch.cat around the passes); False
         # routes the same kernels through caller-owned tensors (bit-identical; kept for tools/ab_inplace.py)
         self._inplace_io = True
+        # the batched loops evaluate the planned energy of their K items in one launch pair (dh_energy_fwd_bwd_planned_batch);
+        # False: one call per item (bit-identical; kept for tools/bench_edit_batch.py)
+        self._batch_energy = True
 
     # ---- plumbing -----------------------------------------------------------------------
     def to(self, device=None):
@@ -535,10 +538,50 @@ class GuidedStableDiffuser(GuidedDiffuser):
     # ---- batched edits: K transforms of ONE image identity in one U-Net batch (BASELINE config 3) ------
     def guided_step_batch(self, sts, x, t_idx, t, uncond):
         """x: [K,H,W,4]; sts: K guidance states (same prompt / original activations, different edits)."""
+        K = x.shape[0]
+        cond = sts[0].cond.expand(K, -1, -1).contiguous()
+        unc = uncond.reshape(1, *cond.shape[1:]).to(self.device, torch.float32).expand(K, -1, -1)
+        return self._guided_step_rows(sts, x, t_idx, t, cond, sts[0].cond_key, unc)
+
+    # ---- batched edits of DIFFERENT images: every item has its own prompt, depth, original activations and unconditional row ----
+    def guided_step_items(self, sts, x, t_idx, t, unconds):
+        """One guided-denoise step of K unrelated items in one U-Net batch.  x: [K,H,W,4]; sts: K guidance states
+        (prepare_guidance), each with its own cond, depth, orig, plan, schedule and guard table; unconds: [K,77,D], this
+        timestep's unconditional embedding of every item.  The passes of guided_step_batch: optimisation at B = K, CFG at
+        B = 2K over [K unconds | K conds]."""
+        K = x.shape[0]
+        key = tuple(id(st) for st in sts)
+        c = sts[0].__dict__.get("_items_cond")
+        if c is None or c[0] != key:
+            GuidedStableDiffuser._text_keys += 1          # the stacked prompts are a text of their own for the K|V cache
+            c = sts[0]._items_cond = (key, torch.cat([st.cond for st in sts]).contiguous(), GuidedStableDiffuser._text_keys)
+        unc = unconds.reshape(K, *c[1].shape[1:]).to(self.device, torch.float32)
+        return self._guided_step_rows(sts, x, t_idx, t, c[1], c[2], unc)
+
+    def _energy_grads(self, sts, k, acts_k, t_idx, iteration, ws, out):
+        """Layer k's energy gradient of every item: acts_k / out [K,h,w,C].  Items whose plan is on this layer's grid go through
+        the batched planned entry together, the others (resized layers, non-default configurations) one by one."""
+        auto = sts[0].auto
+        fw = [ws[e][0][k] if st.n_pairs > 0 else 0.0 for e, st in enumerate(sts)]
+        bw = [ws[e][1][k] for e in range(len(sts))]
+        S = [float(st.scale_host[t_idx, iteration]) if auto else self.grad_scale for st in sts]
+        g = acts_k.shape[1]
+        planned = [e for e, st in enumerate(sts) if st.plan is not None and g == st.plan.grid and acts_k.shape[2] == g]
+        if not (self._batch_energy and 2 <= len(planned) <= MAX_BATCH_ITEMS):
+            planned = []
+        if planned:
+            energy_and_grad_planned_batch([acts_k[e] for e in planned], [sts[e].orig[k][t_idx] for e in planned],
+                                          [sts[e].plan for e in planned], [fw[e] for e in planned], [bw[e] for e in planned],
+                                          [S[e] for e in planned], outs=[out[e] for e in planned])
+        for e, st in enumerate(sts):
+            if e not in planned:
+                self._energy_grad(st, k, acts_k[e], t_idx, fw[e], bw[e], out=out[e], scale=S[e])
+
+    def _guided_step_rows(self, sts, x, t_idx, t, cond, cond_key, unc):
+        """The batched step on K text rows: cond / unc [K,77,D] (one image: K copies of one row)."""
         L = _lib.lib()
         K = x.shape[0]
         depth = torch.cat([st.depth_nhwc for st in sts], dim=0) if self.conf.use_depth else None
-        cond = sts[0].cond.expand(K, -1, -1).contiguous()
         auto = sts[0].auto
         if auto:
             table, status = self._batch_guard(sts)
@@ -551,15 +594,11 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 # written straight into its slice of the engine's cotangent buffer, d(sample) read in place
                 sample = self.unet.stage_sample(x, depth, K)
                 _, acts = self.unet.forward(sample, float(t), cond, save_for_backward=True, want_acts=active, want_eps=False,
-                                            text_key=sts[0].cond_key, inplace=True)
+                                            text_key=cond_key, inplace=True)
                 d_acts = [None, None, None]
                 for k in active:
                     d_acts[k] = self.unet.io_view("act_grad", k)[:K]
-                    for e, st in enumerate(sts):
-                        fgw, bgw = ws[e]
-                        fw = fgw[k] if st.n_pairs > 0 else 0.0
-                        S = float(st.scale_host[t_idx, iteration]) if auto else self.grad_scale
-                        self._energy_grad(st, k, acts[k][e], t_idx, fw, bgw[k], out=d_acts[k][e], scale=S)
+                    self._energy_grads(sts, k, acts[k], t_idx, iteration, ws, d_acts[k])
                 d_sample, _ = self.unet.backward(d_acts, None, want_sample_grad=True, want_text_grad=False, inplace=True)
                 x_new = self._latent_buffer(sts[0], x, iteration)
                 if auto:
@@ -571,7 +610,6 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 x = x_new
             iteration += 1
         sample2 = self.unet.stage_sample(x, depth, 2 * K)          # the K edits twice: unconditional and conditional halves
-        unc = uncond.reshape(1, *cond.shape[1:]).to(self.device, torch.float32).expand(K, -1, -1)
         text2 = torch.cat([unc, cond], dim=0).contiguous()
         eps, _ = self.unet.forward(sample2, float(t), text2, save_for_backward=False, want_acts=False, inplace=True)
         if auto:
@@ -642,6 +680,54 @@ class GuidedStableDiffuser(GuidedDiffuser):
             image = self.decode_latent_image(self.last_latents)
         if status:
             self.raise_on_status(list(enumerate(status[0].cpu().tolist())))
+        return image
+
+    ITEM_FIELDS = ("latents", "depth", "uncond_embeddings", "prompt", "activations_orig", "correspondences")
+
+    def guided_inference_items(self, items, fg_weight=None, bg_weight=None):
+        """K edits of DIFFERENT images at once.  items: K records (dicts with the keys ITEM_FIELDS, or tuples in that order), the
+        arguments of guided_inference per item; fg_weight / bg_weight: one value or K.  Items with the same activations_orig
+        tensors share one channels-last copy of them, items with the same prompt one encoding.  One resolution (the
+        engine's); needs max_batch >= 2K and max_diff_batch >= K, raises otherwise (never splits).  Returns images [K,3,H,W]
+        in item order and sets last_latents; 'auto' grad_scale: FloatingPointError naming the items that met a non-finite
+        value."""
+        items = [it if isinstance(it, dict) else dict(zip(self.ITEM_FIELDS, it)) for it in items]
+        K = len(items)
+        if K < 1 or any(set(self.ITEM_FIELDS) - set(it) for it in items):
+            raise ValueError(f"guided_inference_items: needs at least one item, each with {self.ITEM_FIELDS}")
+        if self.unet.max_batch < 2 * K or self.unet.max_diff_batch < K:
+            raise RuntimeError(f"engine max_batch {self.unet.max_batch} / max_diff_batch {self.unet.max_diff_batch} too small for "
+                               f"{K} items: build the diffuser with max_batch >= {2 * K}")
+        s = self.unet.sample_size
+        for i, it in enumerate(items):
+            if tuple(it["latents"].shape[-2:]) != (s, s):
+                raise ValueError(f"guided_inference_items: latents of item {i} are {tuple(it['latents'].shape[-2:])}, the engine "
+                                 f"runs {(s, s)} latents")
+            if tuple(it["depth"].shape[-2:]) != tuple(items[0]["depth"].shape[-2:]):
+                raise ValueError(f"guided_inference_items: item {i} has another resolution than item 0 "
+                                 f"({tuple(it['depth'].shape[-2:])} / {tuple(items[0]['depth'].shape[-2:])})")
+        per = lambda w, i: w[i] if isinstance(w, (list, tuple)) else w
+        with torch.no_grad(), self.on_stream():
+            torch.manual_seed(self.conf.seed)
+            self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
+            timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
+            sts, origs, conds = [], {}, {}
+            for i, it in enumerate(items):
+                okey = tuple(id(a) for a in it["activations_orig"])
+                st = self.prepare_guidance(it["depth"], it["prompt"], it["activations_orig"], it["correspondences"],
+                                           per(fg_weight, i), per(bg_weight, i), orig=origs.get(okey), cond=conds.get(it["prompt"]))
+                origs[okey], conds[it["prompt"]] = st.orig, st.cond
+                sts.append(st)
+            x = torch.cat([_nhwc(it["latents"].to(self.device, torch.float32)) for it in items]).contiguous()
+            D = sts[0].cond.shape[1:]
+            uncs = torch.stack([it["uncond_embeddings"].to(self.device, torch.float32).reshape(len(timesteps), *D)
+                                for it in items], dim=1).contiguous()          # [T, K, 77, D]
+            for t_idx, t in enumerate(timesteps):
+                x = self.guided_step_items(sts, x, t_idx, t, uncs[t_idx])
+            self.last_latents = x.permute(0, 3, 1, 2)
+            image = self.decode_latent_image(self.last_latents)
+        if sts[0].auto:
+            self.raise_on_status(list(enumerate(self._status_of(sts).cpu().tolist())))
         return image
 
     # ---- lanes: concurrent edit streams on ONE copy of the weights --------------------------------------------------------

@@ -8,6 +8,7 @@ layout, `channels_last=True`); the return value of the loss functions is a scala
 d(loss)/d(activations) from one call, with no autograd graph.
 """
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -121,6 +122,67 @@ def energy_and_grad_planned(act, act_orig, plan, fg_weight, bg_weight, grad_scal
         float(fg_weight), float(bg_weight), float(grad_scale), _lib.ptr(loss), _lib.ptr(grad),
         _lib.DTYPE_CODE[a.dtype], _lib.ptr(ws), wsb, _lib.stream_ptr()), "dh_energy_fwd_bwd_planned")
     return loss, grad
+
+
+MAX_BATCH_ITEMS = 16      # ENERGY_MAX_ITEMS of csrc/energy.hip: the item table travels in the kernel arguments
+
+
+def _batch_state(plans, C):
+    """The item table of a batch of plans with its constant fields filled in, and the batch's workspace; kept on the first
+    plan (a batch's plans live as long as its guidance states; lanes own their plans, so nothing is shared across streams)."""
+    key = (C,) + tuple(id(p) for p in plans)
+    cache = plans[0].__dict__.setdefault("_batch", {})
+    hit = cache.get(key)
+    if hit is None or any(r() is not p for r, p in zip(hit[3], plans)):      # (an id may be reused after a plan has died)
+        cache.clear()
+        K = len(plans)
+        nb = ctypes.c_size_t()
+        _lib.check(_lib.lib().dh_energy_planned_batch_workspace_bytes(C, plans[0].grid, K, ctypes.byref(nb)),
+                   "dh_energy_planned_batch_workspace_bytes")
+        items = (_lib.EnergyItem * K)()
+        for it, p in zip(items, plans):
+            it.plan, it.plan_bytes, it.n_pairs = p.buf.data_ptr(), p.nbytes, p.n_pairs
+            it.bg_orig, it.n_bg_orig = p.dl["bg_orig"].data_ptr(), p.dl["bg_orig"].numel()
+            it.bg_trans, it.n_bg_trans = p.dl["bg_trans"].data_ptr(), p.dl["bg_trans"].numel()
+        cache[key] = (items, torch.empty(nb.value, dtype=torch.uint8, device=plans[0].buf.device), nb.value, [weakref.ref(p) for p in plans])
+    return cache[key][:3]
+
+
+def energy_and_grad_planned_batch(acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss=False, outs=None,
+                                  grad_dtype=None):
+    """energy_and_grad_planned for K <= 16 items in one launch pair (dh_energy_fwd_bwd_planned_batch): item e is (acts[e],
+    acts_orig[e], plans[e], fg_weights[e], bg_weights[e], grad_scales[e]); the items share the map shape and dtype and
+    nothing else (edits of one image or of different images).  Returns (loss [K,3] or None, [K gradients]); outs: where the
+    gradients are written.  Bit-identical per item to the single call.  More than 16 items raise (never split)."""
+    K = len(acts)
+    if K < 1 or not (len(acts_orig) == len(plans) == len(fg_weights) == len(bg_weights) == len(grad_scales) == K):
+        raise ValueError("planned energy batch: the per-item lists must be non-empty and of one length")
+    if K > MAX_BATCH_ITEMS:
+        raise ValueError(f"planned energy batch: {K} items, at most {MAX_BATCH_ITEMS} go into one call")
+    _lib.require_gpu(acts[0])
+    h, w, C = acts[0].shape
+    dt, grid = acts[0].dtype, plans[0].grid
+    gdt = dt if grad_dtype is None else grad_dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        raise ValueError("planned energy: maps must be 16-bit [grid, grid, C] of one dtype")
+    if outs is None:
+        outs = [torch.empty((h, w, C), dtype=gdt, device=acts[0].device) for _ in range(K)]
+    for a, o, p, g in zip(acts, acts_orig, plans, outs):
+        if (tuple(a.shape) != (grid, grid, C) or p.grid != grid or a.dtype != dt or o.dtype != dt or tuple(o.shape) != tuple(a.shape)
+                or not a.is_contiguous() or not o.is_contiguous()):
+            raise ValueError("planned energy batch: maps must be contiguous 16-bit [grid, grid, C] of one dtype and shape")
+        if tuple(g.shape) != (h, w, C) or g.dtype != gdt or not g.is_contiguous():
+            raise ValueError("planned energy batch: `outs` must be contiguous tensors like the activations")
+    loss = torch.zeros((K, 3), dtype=torch.float32, device=acts[0].device) if want_loss else None
+    items, ws, wsb = _batch_state(plans, C)
+    for e, it in enumerate(items):
+        it.cur, it.orig, it.grad = acts[e].data_ptr(), acts_orig[e].data_ptr(), outs[e].data_ptr()
+        it.loss_out = loss[e].data_ptr() if want_loss else None
+        it.fg_w, it.bg_w, it.grad_scale = float(fg_weights[e]), float(bg_weights[e]), float(grad_scales[e])
+    _lib.check(_lib.lib().dh_energy_fwd_bwd_planned_batch(items, K, _lib.DTYPE_CODE[dt], C, grid, _lib.DTYPE_CODE[gdt],
+                                                          _lib.ptr(ws), wsb, _lib.stream_ptr()),
+               "dh_energy_fwd_bwd_planned_batch")
+    return loss, outs
 
 
 def energy_and_grad(act, act_orig, processed_correspondences, fg_weight, bg_weight, fg_patch_size=1,

@@ -164,6 +164,29 @@ int dh_energy_fwd_bwd_planned(const void* cur, const void* orig, int dtype, int 
                               float fg_w, float bg_w, float grad_scale, float* loss_out, void* grad,
                               int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The planned evaluation for K <= 16 items (edits of one image or of different images) in ONE launch pair: one
+ * background column-sum launch (grid z = 2 K) and one gradient launch (grid y = item), plus one loss launch only when an
+ * item has a loss_out.  Nothing is shared between items: every field is what dh_energy_fwd_bwd_planned takes for that
+ * item (cur / orig / grad are unrelated pointers; n_pairs = 0, empty background lists, zero weights allowed); dtype, C,
+ * grid and grad_dtype are common.  The item table reaches the kernels by value in their arguments: no device allocation,
+ * copy or synchronisation.  Per element the arithmetic and its order are those of the single call: the gradient and the
+ * loss values of item e are bit-identical to dh_energy_fwd_bwd_planned's.  K > 16 is an error (never split). */
+typedef struct dh_energy_item {
+  const void* cur;
+  const void* orig;
+  const void* plan;
+  size_t plan_bytes;
+  const int32_t* bg_orig;
+  const int32_t* bg_trans;
+  float* loss_out;            /* NULL: no loss values for this item */
+  void* grad;
+  int n_pairs, n_bg_orig, n_bg_trans;
+  float fg_w, bg_w, grad_scale;
+} dh_energy_item;
+int dh_energy_planned_batch_workspace_bytes(int C, int grid, int n_items, size_t* bytes);
+int dh_energy_fwd_bwd_planned_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
+                                    int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------
  * SD-2-depth U-Net engine (model/unet_2d_condition.py:809-1198 and the block files it
  * calls): forward with the three decoder activation captures, and the backward pass to the

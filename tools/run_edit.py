@@ -75,7 +75,15 @@ def parse():
                     help="--test-set: the scenes that need an identity (not skipped, no cache file) are inverted and initially "
                          "inferred K at a time (DiffusionHandles.invert_input_images / generate_input_images; the engine is "
                          "built with max_batch >= 2K); 1 = one scene at a time")
+    ap.add_argument("--edit-batch", type=int, default=1,
+                    help="--test-set: the edits of ALL scenes are packed K at a time (parallel.pack_edit_batches) and every batch "
+                         "runs as one DiffusionHandles.transform_foregrounds (the engine is built with max_batch >= 2K; 'pc' mode); "
+                         "1 = one transform_foreground per edit")
+    ap.add_argument("--edit-batch-images", type=int, default=0,
+                    help="--edit-batch: at most N scenes in one batch (each keeps 0.53 GB of activations resident at 512x512); 0 = no bound")
     args = ap.parse_args()
+    if args.edit_batch < 1 or (args.edit_batch > 1 and args.test_set is None):
+        ap.error("--edit-batch K needs K >= 1, and K > 1 needs --test-set")
     if args.identity_batch < 1 or (args.identity_batch > 1 and args.test_set is None):
         ap.error("--identity-batch K needs K >= 1, and K > 1 needs --test-set")
     return args
@@ -96,7 +104,8 @@ def main():
             ucfg = dict(SD2_DEPTH, sample_size=res // 8)
             if not conf.guided_diffuser.use_depth:
                 ucfg["in_channels"] = 4          # use_depth: false (test/config/no_depth.yaml): no depth channel beside the latent
-            extra = {} if args.identity_batch == 1 else {"max_batch": 2 * args.identity_batch}
+            kmax = max(args.identity_batch, args.edit_batch)
+            extra = {} if kmax == 1 else {"max_batch": 2 * kmax}
             state["dh"] = DiffusionHandles(conf, dtype=torch.float16 if args.dtype == "fp16" else torch.bfloat16,
                                            unet_config=ucfg, **extra).to(torch.device("cuda:0"))
         return state["dh"]
@@ -121,6 +130,10 @@ def main():
     # the identity cache of a scene lives in its own output directory unless the caller disabled it
     sub.identity_cache = None
     identities = {}                 # --identity-batch > 1: the identities of the current chunk, by scene
+    batch_seconds = None
+    if args.edit_batch > 1:
+        reports, batch_seconds = run_test_set_batched(sub, conf, handles, names, input_dir)
+        names = []
     for idx, (scene, transform_names) in enumerate(names):
         sys.stderr.write(f"[{idx + 1}/{len(names)}] {scene}: {len(transform_names)} transforms\n")
         if args.identity_batch > 1 and scene not in identities:
@@ -148,6 +161,8 @@ def main():
     total = dict(test_set=set_name, scenes=reports, config=args.config, depth_transform_mode=conf.depth_transform_mode,
                  edits_run=sum(1 for r in reports for e in r["edits"] if not e.get("skipped")),
                  edits_skipped=sum(1 for r in reports for e in r["edits"] if e.get("skipped")))
+    if batch_seconds is not None:
+        total.update(edit_batch=args.edit_batch, batch_seconds=batch_seconds)
     json.dump(total, open(os.path.join(args.out, "report.json"), "w"), indent=1)
     print(json.dumps(total))
 
@@ -210,20 +225,12 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
     return dict(img=img, depth=depth, bg_depth=bg_depth, mask=mask, prompt=prompt, res=res, transforms=transforms, exists=exists)
 
 
-def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
-    """One scene (the body of the reference's loop, test_diffusion_handles.py:66-175): identity (inversion + initial inference,
-    or the cache), set_foreground, one transform_foreground per transform.  transform_names: the subset / order the test set
-    lists for this scene (names the scene's transforms.json does not have are skipped with a warning, :126-128).
-    identity: (null_text, noise, acts, latent, seconds) computed by identity_chunk (--identity-batch), written to the cache."""
+def scene_identity(args, dh, p, out, identity=None):
+    """The identity part of one scene: inversion + initial inference, the cache file, or `identity` from identity_chunk; then
+    set_foreground and recon.png.  Returns the scene's device tensors and the head of its report."""
     from diffusionhandles_amd.scene_io import write_png
-    os.makedirs(out, exist_ok=True)
     dev = torch.device("cuda:0")
-    p = prepare_scene(args, scene, out, transform_names)
     img, depth, bg_depth, mask, prompt, res = p["img"], p["depth"], p["bg_depth"], p["mask"], p["prompt"], p["res"]
-    transforms, exists = p["transforms"], p["exists"]
-    if args.skip_existing and transforms and all(exists.values()):
-        return dict(resolution=res, mode=args.mode, skipped_scene=True, edits=[dict(name=n, skipped=True) for n in exists])
-    dh = handles(res)
     depth, bg_depth, mask, img = depth.to(dev), bg_depth.to(dev), mask.to(dev), img.to(dev)
     t0 = time.time()
     cache = None if args.no_identity_cache else (args.identity_cache or os.path.join(out, "identity.npz"))
@@ -260,20 +267,12 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
                   edits=[])
     if args.identity_batch > 1:
         report["identity_batch"] = args.identity_batch
-    for tf in transforms:
-        if args.skip_existing and exists[tf["name"]]:
-            report["edits"].append(dict(name=tf["name"], skipped=True))
-            continue
-        t0 = time.time()
-        res_ = dh.transform_foreground(depth, prompt, mask, bg_depth, null_text, noise, acts, rot_angle=tf["rot_angle"],
-                                      rot_axis=tf["rot_axis"], translation=tf["translation"])
-        torch.cuda.synchronize()
-        dt = time.time() - t0
-        edited, disparity = res_[0], res_[1]
-        name = tf["name"]
-        write_png(os.path.join(out, f"{name}.png"), edited[0].permute(1, 2, 0).float().cpu().numpy())
-        write_png(os.path.join(out, f"{name}_disparity.png"), (disparity[0, 0] / disparity.max()).float().cpu().numpy())
-        report["edits"].append(dict(name=name, seconds=round(dt, 3)))
+    return depth, bg_depth, mask, img, null_text, noise, acts, report
+
+
+def write_scene_pages(args, out, img, mask, depth, bg_depth, prompt, res, report):
+    """report.json, the input images and the results page of one scene."""
+    from diffusionhandles_amd.scene_io import write_png
     json.dump(report, open(os.path.join(out, "report.json"), "w"), indent=1)
     # the results page of the reference's harness (test/generate_results_webpage.py: one row per edit with input, mask,
     # depth, background depth, reconstruction, edit, edited disparity), written without a template engine
@@ -293,6 +292,107 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
     with open(os.path.join(out, "summary.html"), "w") as f:
         f.write(f"<!doctype html><html><head><meta charset='utf-8'><title>{prompt}</title></head><body><h3>{prompt} "
                 f"({res}x{res}, {args.mode})</h3><table border='1' cellspacing='0' cellpadding='4'><tr>{head}</tr>{''.join(rows)}</table></body></html>")
+
+
+def run_test_set_batched(args, conf, handles, names, input_dir):
+    """--edit-batch K: the edits of every scene that are still to do (--skip-existing), packed K at a time over the scenes in
+    test-set order; a batch's scenes keep their identities resident while it runs, a finished scene's identity is dropped.
+    Writes the files run_scene writes.  Returns (scene reports, seconds per batch)."""
+    from diffusionhandles_amd.parallel import pack_edit_batches
+    from diffusionhandles_amd.scene_io import write_png
+    if conf.depth_transform_mode != "pc":
+        raise NotImplementedError("--edit-batch needs depth_transform_mode 'pc' (there is no batched mesh re-projection)")
+    prep, reports, todo = {}, {}, []
+    for scene, transform_names in names:
+        out = os.path.join(args.out, scene)
+        os.makedirs(out, exist_ok=True)
+        p = prep[scene] = prepare_scene(args, os.path.join(input_dir, scene), out, list(transform_names))
+        if args.skip_existing and p["transforms"] and all(p["exists"].values()):
+            reports[scene] = dict(resolution=p["res"], mode=args.mode, skipped_scene=True, scene=scene,
+                                  edits=[dict(name=n, skipped=True) for n in p["exists"]])
+            continue
+        todo.append((scene, [tf["name"] for tf in p["transforms"] if not (args.skip_existing and p["exists"][tf["name"]])]))
+    batches = pack_edit_batches(todo, args.edit_batch, args.edit_batch_images or None)
+    resident, seconds = {}, []
+    for bi, batch in enumerate(batches):
+        scenes = list(dict.fromkeys(s for s, _ in batch))
+        sys.stderr.write(f"[batch {bi + 1}/{len(batches)}] {len(batch)} edits of {', '.join(scenes)}\n")
+        for s in [s for s in resident if s not in scenes]:          # (a scene's edits are contiguous: it is finished)
+            del resident[s]
+        need = [s for s in scenes if s not in resident]
+        ident = {}
+        if args.identity_batch > 1:          # the batch's scenes without a cache file, --identity-batch at a time
+            fresh = [s for s in need if needs_identity(args, os.path.join(input_dir, s), os.path.join(args.out, s),
+                                                       [tf["name"] for tf in prep[s]["transforms"]])]
+            for i in range(0, len(fresh), args.identity_batch):
+                ident.update(identity_chunk(args, handles, [(os.path.join(input_dir, s), s)
+                                                            for s in fresh[i:i + args.identity_batch]]))
+        for s in need:
+            p = prep[s]
+            d, bg, m, img, null_text, noise, acts, rep = scene_identity(args, handles(p["res"]), p, os.path.join(args.out, s),
+                                                                        ident.pop(s, None))
+            resident[s] = dict(depth=d, bg_depth=bg, fg_mask=m, img=img, null_text_emb=null_text, init_noise=noise,
+                               activations=acts, prompt=p["prompt"])
+            rep.update(scene=s, edit_batch=args.edit_batch,
+                       edits=[dict(name=n, skipped=True) for n, ex in p["exists"].items() if args.skip_existing and ex])
+            reports[s] = rep
+        edits = []
+        for s, name in batch:
+            tf = next(t for t in prep[s]["transforms"] if t["name"] == name)
+            r = resident[s]
+            edits.append(dict(depth=r["depth"], prompt=r["prompt"], fg_mask=r["fg_mask"], bg_depth=r["bg_depth"],
+                              null_text_emb=r["null_text_emb"], init_noise=r["init_noise"], activations=r["activations"],
+                              rot_angle=tf["rot_angle"], rot_axis=tf["rot_axis"], translation=tf["translation"]))
+        t0 = time.time()
+        images, disparities = handles(prep[scenes[0]]["res"]).transform_foregrounds(edits)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        seconds.append(round(dt, 3))
+        for (s, name), image, disparity in zip(batch, images, disparities):
+            out = os.path.join(args.out, s)
+            write_png(os.path.join(out, f"{name}.png"), image.permute(1, 2, 0).float().cpu().numpy())
+            write_png(os.path.join(out, f"{name}_disparity.png"), (disparity[0, 0] / disparity.max()).float().cpu().numpy())
+            reports[s]["edits"].append(dict(name=name, seconds=round(dt / len(batch), 3), batch=bi))
+        for s in scenes:             # a scene whose last edit ran in this batch is complete: its pages
+            if not any(s == s2 for later in batches[bi + 1:] for s2, _ in later):
+                r, p = resident[s], prep[s]
+                order = {tf["name"]: i for i, tf in enumerate(p["transforms"])}
+                reports[s]["edits"].sort(key=lambda e: order[e["name"]])
+                write_scene_pages(args, os.path.join(args.out, s), r["img"], r["fg_mask"], r["depth"], r["bg_depth"], p["prompt"],
+                                  p["res"], reports[s])
+    return [reports[s] for s, _ in names if s in reports], seconds
+
+
+def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
+    """One scene (the body of the reference's loop, test_diffusion_handles.py:66-175): identity (inversion + initial inference,
+    or the cache), set_foreground, one transform_foreground per transform.  transform_names: the subset / order the test set
+    lists for this scene (names the scene's transforms.json does not have are skipped with a warning, :126-128).
+    identity: (null_text, noise, acts, latent, seconds) computed by identity_chunk (--identity-batch), written to the cache."""
+    from diffusionhandles_amd.scene_io import write_png
+    os.makedirs(out, exist_ok=True)
+    dev = torch.device("cuda:0")
+    p = prepare_scene(args, scene, out, transform_names)
+    img, depth, bg_depth, mask, prompt, res = p["img"], p["depth"], p["bg_depth"], p["mask"], p["prompt"], p["res"]
+    transforms, exists = p["transforms"], p["exists"]
+    if args.skip_existing and transforms and all(exists.values()):
+        return dict(resolution=res, mode=args.mode, skipped_scene=True, edits=[dict(name=n, skipped=True) for n in exists])
+    dh = handles(res)
+    depth, bg_depth, mask, img, null_text, noise, acts, report = scene_identity(args, dh, p, out, identity)
+    for tf in transforms:
+        if args.skip_existing and exists[tf["name"]]:
+            report["edits"].append(dict(name=tf["name"], skipped=True))
+            continue
+        t0 = time.time()
+        res_ = dh.transform_foreground(depth, prompt, mask, bg_depth, null_text, noise, acts, rot_angle=tf["rot_angle"],
+                                      rot_axis=tf["rot_axis"], translation=tf["translation"])
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        edited, disparity = res_[0], res_[1]
+        name = tf["name"]
+        write_png(os.path.join(out, f"{name}.png"), edited[0].permute(1, 2, 0).float().cpu().numpy())
+        write_png(os.path.join(out, f"{name}_disparity.png"), (disparity[0, 0] / disparity.max()).float().cpu().numpy())
+        report["edits"].append(dict(name=name, seconds=round(dt, 3)))
+    write_scene_pages(args, out, img, mask, depth, bg_depth, prompt, res, report)
     return report
 
 

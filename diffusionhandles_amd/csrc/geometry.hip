@@ -39,11 +39,28 @@ __global__ void k_unproject(const float* depth, int res, const float* gx, const 
 // row order, then / float32(N).  The additions are inherently serial (bit-exact order); the unprojection is
 // not: the whole workgroup stages the next 1024 points into LDS while lanes 0..2 (one coordinate each)
 // fold the previous 1024 in order.
+//
+// Several rigid bodies (dh_reproject_object_edits): object m owns fg_pix[start[m] .. start[m + 1]); the table travels BY VALUE
+// in the kernel arguments (the idiom of energy.hip's item table).  Workgroup m folds its own slice, so the M serial chains run
+// side by side; entries past the last object hold the total, so no slice index can leave the list.
+constexpr int MAX_OBJECTS = 8;
+struct ObjTable {
+  int start[MAX_OBJECTS + 1];
+};
+static ObjTable obj_table(int n_objects, const int* obj_start, int n_fg) {
+  ObjTable t;
+  for (int m = 0; m <= MAX_OBJECTS; ++m) t.start[m] = m < n_objects ? obj_start[m] : n_fg;
+  return t;
+}
+
 constexpr int CEN_CHUNK = 1024;
-__global__ void __launch_bounds__(CEN_CHUNK) k_centroid(const float* depth, const int* fg_pix, int n, int res, const float* gx,
-                                                         const float* gy, float ifx, float ify, float* cen) {
+__global__ void __launch_bounds__(CEN_CHUNK) k_centroid(const float* depth, const int* fg_pix, const ObjTable tab, int res,
+                                                         const float* gx, const float* gy, float ifx, float ify, float* cen) {
   __shared__ float sv[2][3][CEN_CHUNK];
   const int t = threadIdx.x;
+  const int n = tab.start[blockIdx.x + 1] - tab.start[blockIdx.x];
+  fg_pix += tab.start[blockIdx.x];
+  cen += 4 * blockIdx.x;
   float acc = 0.f;
   const int nchunks = (n + CEN_CHUNK - 1) / CEN_CHUNK;
   for (int c = 0; c <= nchunks; ++c) {
@@ -104,11 +121,12 @@ struct Xf {
   double ax, ay, az, c, s, tx, ty, tz;
 };
 
-// one thread per (edit, point): points [0,R2) are background pixels, [R2,R2+n_fg) foreground.
+// one thread per (edit, point): points [0,R2) are background pixels, [R2,R2+n_fg) foreground, object after object.
+// xf: n_obj rows per edit (edit-major), cen: 4 floats per object.
 __global__ void k_points(const float* depth, const float* bg_depth, const int* fg_pix, int n_fg, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
-                         const Xf* xf, const float* cen, unsigned long long* zbuf, int* pix_out,
-                         unsigned long long* key_out) {
+                         const Xf* xf, const float* cen, const ObjTable tab, int n_obj, unsigned long long* zbuf,
+                         int* pix_out, unsigned long long* key_out) {
   const int R2 = res * res, P = R2 + n_fg;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
@@ -121,8 +139,12 @@ __global__ void k_points(const float* depth, const float* bg_depth, const int* f
   } else {
     float x, y, z;
     unproject_px(depth, fg_pix[i - R2], res, gx, gy, ifx, ify, x, y, z);
-    const Xf t = xf[e];
-    const float c0 = cen[0], c1 = cen[1], c2 = cen[2];
+    // the object of this point: a compare chain against the table's scalars (unused entries hold n_fg: never passed)
+    int m = 0;
+#pragma unroll
+    for (int k = 1; k < MAX_OBJECTS; ++k) m += (i - R2 >= tab.start[k]) ? 1 : 0;
+    const Xf t = xf[e * n_obj + m];
+    const float c0 = cen[4 * m], c1 = cen[4 * m + 1], c2 = cen[4 * m + 2];
     const float q0 = x - c0, q1 = y - c1, q2 = z - c2;
     const float a0 = (float)t.ax, a1 = (float)t.ay, a2 = (float)t.az;
     const float cr0 = a1 * q2 - a2 * q1;
@@ -801,10 +823,10 @@ struct ReprojectWs {
   CgSync* cgsync;
 };
 
-static bool carve(Arena& a, int res, int n_fg, int K, ReprojectWs& w) {
+static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w) {
   const size_t R2 = (size_t)res * res, P = R2 + n_fg;
-  w.xf = a.take<Xf>(K);
-  w.cen = a.take<float>(4);
+  w.xf = a.take<Xf>((size_t)K * M);
+  w.cen = a.take<float>(4 * M);
   w.zbuf = a.take<unsigned long long>(K * R2);
   w.owner = a.take<int>(K * R2);
   w.pix = a.take<int>(K * P);
@@ -831,13 +853,17 @@ static bool carve(Arena& a, int res, int n_fg, int K, ReprojectWs& w) {
 
 using namespace dh;
 
-extern "C" int dh_reproject_workspace_bytes(int res, int n_fg, int n_edits, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && n_fg >= 0 && n_edits >= 1 && bytes, "bad arguments");
+extern "C" int dh_reproject_objects_workspace_bytes(int res, int n_fg, int n_edits, int n_objects, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && n_fg >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
   Arena a(nullptr, (size_t)-1);
   ReprojectWs w;
-  carve(a, res, n_fg, n_edits, w);
+  carve(a, res, n_fg, n_edits, n_objects, w);
   *bytes = a.off + 256;
   return DH_OK;
+}
+
+extern "C" int dh_reproject_workspace_bytes(int res, int n_fg, int n_edits, size_t* bytes) {
+  return dh_reproject_objects_workspace_bytes(res, n_fg, n_edits, 1, bytes);
 }
 
 extern "C" int dh_fg_pixel_list(const uint8_t* fg_mask, int res, int32_t* fg_pix, int32_t* n_fg_dev, void* workspace,
@@ -862,26 +888,34 @@ extern "C" int dh_unproject(const float* depth, int res, const float* grid_x, co
 extern "C" int dh_masked_centroid(const float* depth, const int32_t* fg_pix, int n_fg, int res, const float* grid_x,
                                   const float* grid_y, float inv_fx, float inv_fy, float* centroid, void* stream) {
   DH_REQUIRE(depth && fg_pix && centroid && n_fg > 0, "bad arguments");
-  hipLaunchKernelGGL(k_centroid, dim3(1), dim3(CEN_CHUNK), 0, (hipStream_t)stream, depth, fg_pix, n_fg, res, grid_x, grid_y,
-                     inv_fx, inv_fy, centroid);
+  const int one[2] = {0, n_fg};
+  hipLaunchKernelGGL(k_centroid, dim3(1), dim3(CEN_CHUNK), 0, (hipStream_t)stream, depth, fg_pix, obj_table(1, one, n_fg), res,
+                     grid_x, grid_y, inv_fx, inv_fy, centroid);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
 
-extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg, int res,
-                                  const float* grid_x, const float* grid_y, float inv_fx, float inv_fy, double fx,
-                                  double fy, int n_edits, const double* xforms_host, const float* bounds, float* zmap,
-                                  uint8_t* raw_mask, uint8_t* clean_mask, float* disparity, uint8_t* vis,
-                                  int32_t* target_xy, int64_t* corr, int32_t* counts, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-  DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host, "null input");
+// n_objects rigid bodies per edit: object m owns fg_pix[obj_start[m] .. obj_start[m + 1]) and row e * n_objects + m of xforms_host.
+// Only k_centroid and k_points know about objects; from the z-buffer on the point list is one list.
+extern "C" int dh_reproject_object_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                         int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                         const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                         const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                         uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                         int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
+  DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
+  DH_REQUIRE(obj_start[0] == 0 && obj_start[n_objects] == n_fg, "obj_start must run from 0 to n_fg");
+  for (int m = 0; m < n_objects; ++m) DH_REQUIRE(obj_start[m] < obj_start[m + 1], "obj_start must increase (no empty object)");
   hipStream_t st = (hipStream_t)stream;
-  const int K = n_edits, R2 = res * res, P = R2 + n_fg;
+  const int K = n_edits, M = n_objects, R2 = res * res, P = R2 + n_fg;
+  const ObjTable tab = obj_table(M, obj_start, n_fg);
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
-  DH_REQUIRE(carve(a, res, n_fg, K, w), "workspace too small");
+  DH_REQUIRE(carve(a, res, n_fg, K, M, w), "workspace too small");
 
   int2 hc[MAX_OFFS], ho[MAX_OFFS];
   const int kc = res / 50, ko = res / 250;
@@ -890,7 +924,7 @@ extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, con
   const int no = ellipse_offsets(ko < 1 ? 1 : ko, ho);
   DH_CHECK_HIP(hipMemcpyAsync(w.offs_close, hc, nc * sizeof(int2), hipMemcpyHostToDevice, st));
   DH_CHECK_HIP(hipMemcpyAsync(w.offs_open, ho, no * sizeof(int2), hipMemcpyHostToDevice, st));
-  DH_CHECK_HIP(hipMemcpyAsync(w.xf, xforms_host, K * sizeof(Xf), hipMemcpyHostToDevice, st));
+  DH_CHECK_HIP(hipMemcpyAsync(w.xf, xforms_host, (size_t)K * M * sizeof(Xf), hipMemcpyHostToDevice, st));
   DH_CHECK_HIP(hipMemsetAsync(w.zbuf, 0xff, (size_t)K * R2 * sizeof(unsigned long long), st));
   DH_CHECK_HIP(hipMemsetAsync(w.owner, 0x7f, (size_t)K * R2 * sizeof(int), st));
   DH_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)K * 4 * sizeof(int), st));
@@ -898,10 +932,10 @@ extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, con
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0, (size_t)2 * K * sizeof(unsigned int), st));
   for (int e = 0; e < K; ++e) DH_CHECK_HIP(hipMemsetAsync(w.minmax + 2 * e, 0xff, sizeof(unsigned int), st));
 
-  hipLaunchKernelGGL(k_centroid, dim3(1), dim3(CEN_CHUNK), 0, st, depth, fg_pix, n_fg, res, grid_x, grid_y, inv_fx, inv_fy,
+  hipLaunchKernelGGL(k_centroid, dim3(M), dim3(CEN_CHUNK), 0, st, depth, fg_pix, tab, res, grid_x, grid_y, inv_fx, inv_fy,
                      w.cen);
   hipLaunchKernelGGL(k_points, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_fg, res, grid_x,
-                     grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, w.zbuf, w.pix, w.key);
+                     grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, tab, M, w.zbuf, w.pix, w.key);
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), K), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, raw_mask,
                      disparity, w.minmax);
@@ -950,6 +984,18 @@ extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, con
                      reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg, int res,
+                                  const float* grid_x, const float* grid_y, float inv_fx, float inv_fy, double fx,
+                                  double fy, int n_edits, const double* xforms_host, const float* bounds, float* zmap,
+                                  uint8_t* raw_mask, uint8_t* clean_mask, float* disparity, uint8_t* vis,
+                                  int32_t* target_xy, int64_t* corr, int32_t* counts, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  const int32_t one[2] = {0, n_fg};
+  return dh_reproject_object_edits(depth, bg_depth, fg_pix, n_fg, 1, one, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, n_edits,
+                                   xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
+                                   workspace, workspace_bytes, stream);
 }
 
 extern "C" int dh_laplacian_blend_workspace_bytes(int res, size_t* bytes) {

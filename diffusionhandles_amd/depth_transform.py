@@ -90,6 +90,9 @@ def _xform_rows(transforms):
     return rows
 
 
+MAX_OBJECTS = 8              # csrc/geometry.hip: the object table travels in the kernel arguments
+
+
 def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_depth_normalization=False,
                     return_debug=False, device_correspondences=False):
     """K edits of one image.  transforms: list of (rot_angle_deg, rot_axis[3], translation[3]).
@@ -99,25 +102,70 @@ def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_
     over as a CPU tensor (depth_transform.py:339-343) and so does `transform_depth`; device_correspondences=True leaves
     them where the kernels wrote them, for callers that feed them straight back to the device (the batched edit path:
     `process_correspondences` accepts either) -- K device-to-host copies and K uploads less per call.
+
+    The one-object call of `reproject_object_edits`.
     """
-    if fg_mask.shape[-2] != fg_mask.shape[-1]:
-        raise RuntimeError(f"Expected fg_mask to be square, got shape {fg_mask.shape[-2]} x {fg_mask.shape[-1]}.")
+    return reproject_object_edits(depth, bg_depth, [fg_mask], intrinsics, [[tf] for tf in transforms],
+                                  use_input_depth_normalization, return_debug, device_correspondences)
+
+
+def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_input_depth_normalization=False,
+                           return_debug=False, device_correspondences=False):
+    """K edits of one image with M rigid bodies each (not in the reference).  fg_masks: M pairwise disjoint [1,1,H,W] masks
+    (1 <= M <= 8); bg_depth: the depth with ALL objects removed; edits: K lists of M (rot_angle_deg, rot_axis[3],
+    translation[3]), one per mask.
+
+    Object m turns about the centroid of its own masked points, then moves.  The point list is the background pixels, then
+    the points of object 0 in row-major order, then object 1, ...: one z-buffer over all of it, so the objects occlude the
+    background and each other, and equal depths go to the earlier object.  Mask clean-up, correspondence filter, in-fill
+    and normalisation see the union.  Empty masks are dropped (with their transforms); all empty = the empty-mask result of
+    `reproject_edits`.  ValueError for overlapping masks, M > 8, or an edit that does not have M transforms.
+
+    Returns what `reproject_edits` returns: the correspondences [N,4] int64 (ox, oy, tx, ty) in point-list order (object
+    order, row-major within an object).  The debug dict also has obj_start, the M' + 1 offsets of the kept objects'
+    slices in fg_pix / vis / target_xy.
+    """
+    fg_masks = list(fg_masks)
+    M = len(fg_masks)
+    if not 1 <= M <= MAX_OBJECTS:
+        raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got {M}")
+    edits = [list(tfs) for tfs in edits]
+    for e, tfs in enumerate(edits):
+        if len(tfs) != M:
+            raise ValueError(f"Edit {e} has {len(tfs)} transforms for {M} foreground masks")
+    for fg_mask in fg_masks:
+        if fg_mask.shape[-2] != fg_mask.shape[-1]:
+            raise RuntimeError(f"Expected fg_mask to be square, got shape {fg_mask.shape[-2]} x {fg_mask.shape[-1]}.")
+        if fg_mask.shape[-1] != fg_masks[0].shape[-1]:
+            raise ValueError("Expected all foreground masks to have one size")
     if depth.dim() != 4 or depth.shape[0] != 1:
         raise ValueError("Only batch size 1 is supported")
-    res = fg_mask.shape[-1]
+    res = fg_masks[0].shape[-1]
+    # the M pixel counts and the overlap flag: ONE device-to-host copy (none for host masks), before any launch of the library
+    flat = [(fg_mask.detach() != 0).reshape(-1) for fg_mask in fg_masks]
+    masks_u8 = (flat[0][None] if M == 1 else torch.stack(flat)).to(torch.uint8)
+    stats = masks_u8.sum(dim=1)
+    if M > 1:
+        stats = torch.cat([stats, (masks_u8.sum(dim=0) > 1).any()[None].to(stats.dtype)])
+    stats = stats.tolist()
+    if M > 1 and stats[M]:
+        raise ValueError("The foreground masks overlap")
+    kept = [m for m in range(M) if stats[m] > 0]
+    obj_start = np.zeros(len(kept) + 1, dtype=np.int32)
+    obj_start[1:] = np.cumsum([stats[m] for m in kept])
+    n_fg = int(obj_start[-1])
     out_dev = depth.device
     dev = _compute_device(depth)
     L = _lib.lib()
     st = _lib.stream_ptr()
     d = depth.detach().to(dev, torch.float32).contiguous()
     bg = bg_depth.detach().to(dev, torch.float32).contiguous()
-    mask_u8 = (fg_mask.detach().to(dev) != 0).to(torch.uint8).contiguous().view(-1)
-    K = len(transforms)
+    masks_u8 = masks_u8.to(dev).contiguous()
+    K = len(edits)
     bounds = None
     if use_input_depth_normalization:
         disp_in = 1.0 / d
         bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
-    n_fg = int(mask_u8.sum().item())
     if n_fg == 0:
         # empty foreground: the input disparity and no correspondences (depth_transform.py:203-216)
         lo_hi = None if bounds is None else (bounds[0], bounds[1])
@@ -131,13 +179,16 @@ def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_
     kcpu = intrinsics.detach().to("cpu", torch.float32)
     fx, fy = float(kcpu[0, 0]), float(kcpu[1, 1])
     R2 = res * res
+    Mk = len(kept)
     fg_pix = torch.empty(R2, dtype=torch.int32, device=dev)
-    n_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_dev = torch.zeros(Mk, dtype=torch.int32, device=dev)
     ws_small = torch.empty(4096, dtype=torch.uint8, device=dev)
-    _lib.check(L.dh_fg_pixel_list(_lib.ptr(mask_u8), res, _lib.ptr(fg_pix), _lib.ptr(n_dev), _lib.ptr(ws_small),
-                                  ws_small.numel(), st), "dh_fg_pixel_list")
+    for j, m in enumerate(kept):              # disjoint masks: the slices fill fg_pix[0 .. n_fg), n_fg <= R2
+        _lib.check(L.dh_fg_pixel_list(_lib.ptr(masks_u8[m]), res, _lib.ptr(fg_pix[int(obj_start[j]):]), _lib.ptr(n_dev[j:]),
+                                      _lib.ptr(ws_small), ws_small.numel(), st), "dh_fg_pixel_list")
     nbytes = ctypes.c_size_t()
-    _lib.check(L.dh_reproject_workspace_bytes(res, n_fg, K, ctypes.byref(nbytes)), "dh_reproject_workspace_bytes")
+    _lib.check(L.dh_reproject_objects_workspace_bytes(res, n_fg, K, Mk, ctypes.byref(nbytes)),
+               "dh_reproject_objects_workspace_bytes")
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     zmap = torch.empty((K, res, res), dtype=torch.float32, device=dev)
     raw = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
@@ -147,12 +198,13 @@ def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_
     txy = torch.empty((K, n_fg, 2), dtype=torch.int32, device=dev)
     corr = torch.empty((K, n_fg, 4), dtype=torch.int64, device=dev)
     counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
-    rows = np.ascontiguousarray(_xform_rows(transforms))
-    _lib.check(L.dh_reproject_edits(
-        _lib.ptr(d), _lib.ptr(bg), _lib.ptr(fg_pix), n_fg, res, _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, K,
+    rows = np.ascontiguousarray(_xform_rows([tfs[m] for tfs in edits for m in kept]))      # edit-major, K x Mk rows
+    _lib.check(L.dh_reproject_object_edits(
+        _lib.ptr(d), _lib.ptr(bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
+        _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, K,
         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bounds),
         _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
-        _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st), "dh_reproject_edits")
+        _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st), "dh_reproject_object_edits")
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
     out = []
@@ -161,7 +213,7 @@ def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_
         out.append((disp[e][None, None].to(out_dev), corr[e, :n] if device_correspondences else corr[e, :n].cpu()))
     if return_debug:
         dbg = dict(zmap=zmap, raw_mask=raw, clean_mask=clean, vis=vis, target_xy=txy, counts=counts_h,
-                   fg_pix=fg_pix[:n_fg], corr_dev=corr)
+                   fg_pix=fg_pix[:n_fg], corr_dev=corr, obj_start=obj_start)
         return out, dbg
     return out
 

@@ -64,7 +64,13 @@ class DiffusionHandles:
 
     def set_foreground(self, depth, fg_mask, bg_depth):
         """Background depth = input depth with the hole of the (15x cross-dilated) foreground mask in-filled
-        from the background depth's Laplacian (reference diffusion_handles.py:90-111)."""
+        from the background depth's Laplacian (reference diffusion_handles.py:90-111).  fg_mask may be a list of masks
+        (several objects, transform_foreground_objects): the blend runs over their union."""
+        if isinstance(fg_mask, (list, tuple)):
+            union = fg_mask[0] != 0
+            for m in fg_mask[1:]:
+                union = union | (m != 0)
+            fg_mask = union.to(fg_mask[0].dtype)
         return laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15)
 
     def transform_foreground_batch(self, depth, prompt, fg_mask, bg_depth, null_text_emb, init_noise, activations,
@@ -93,6 +99,49 @@ class DiffusionHandles:
                                                                             activations, max(1, int(streams)), fg_weight,
                                                                             bg_weight))
         return imgs, [d for d, _ in edits]
+
+    def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences):
+        from .depth_transform import reproject_object_edits
+        if self.conf.depth_transform_mode != "pc":
+            raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no multi-object "
+                                      "re-projection (only 'pc')")
+        Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
+        dflt = lambda v, d: d if v is None else v
+        edits = [[(dflt(a, 0.0), dflt(ax, Y), dflt(tr, torch.zeros(3))) for a, ax, tr in tfs] for tfs in edits]
+        return reproject_object_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
+                                      use_input_depth_normalization, device_correspondences=device_correspondences)
+
+    def transform_foreground_objects(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
+                                     transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False):
+        """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
+        bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
+        rot_axis[3], translation[3]), one per mask.  Each object turns about its own centroid; they occlude the background
+        and each other (depth_transform.reproject_object_edits).  The guidance sees the union of the correspondences: its
+        foreground term is the mean over all pairs, so the objects weigh by covered area (no per-object weights).
+        Returns what transform_foreground returns.  'pc' re-projection only."""
+        with torch.no_grad():
+            (edited_disparity, correspondences), = self._reproject_objects(
+                "transform_foreground_objects", depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False)
+            results = self.diffuser.guided_inference(
+                latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
+                activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
+                bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps)
+        if self.conf.guided_diffuser.save_denoising_steps:
+            edited_img, denoising_steps = results
+            return edited_img, edited_disparity, denoising_steps
+        return results, edited_disparity
+
+    def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
+                                           edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False):
+        """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
+        edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]).  Returns (images [K,3,H,W], [K disparities]) as
+        transform_foreground_batch does on one stream."""
+        with torch.no_grad():
+            res = self._reproject_objects("transform_foreground_objects_batch", depth, bg_depth, fg_masks, edits,
+                                          use_input_depth_normalization, True)
+            imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
+                                                        [c for _, c in res], fg_weight, bg_weight)
+        return imgs, [d for d, _ in res]
 
     EDIT_FIELDS = ("depth", "prompt", "fg_mask", "bg_depth", "null_text_emb", "init_noise", "activations")
 

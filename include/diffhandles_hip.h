@@ -73,6 +73,23 @@ int dh_reproject_edits(const float* depth, const float* bg_depth, const int32_t*
                        float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
                        uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* Several rigid bodies per edit (not in the reference): dh_reproject_edits with n_objects (1..8) foreground objects.
+ *   fg_pix      the objects' pixel lists, concatenated: object m owns fg_pix[obj_start[m] .. obj_start[m+1]), row-major
+ *               within the object (dh_fg_pixel_list per mask, written into consecutive slices); the masks are disjoint
+ *   obj_start   HOST, n_objects + 1 ints: 0 = obj_start[0] < obj_start[1] < ... < obj_start[n_objects] = n_fg
+ *   xforms_host n_edits x n_objects rows of 8 doubles, edit-major: row e * n_objects + m moves object m in edit e,
+ *               about the centroid of ITS OWN points (sequential float32 mean over its slice)
+ * The point list is background, object 0, object 1, ...; ONE z-buffer over it (winner = min (z, point index)), so objects
+ * occlude the background and each other and equal depths go to the earlier object.  vis / target_xy / corr are indexed
+ * and ordered by position in fg_pix; everything else as dh_reproject_edits, which is the n_objects = 1 call of this one. */
+int dh_reproject_objects_workspace_bytes(int res, int n_fg, int n_edits, int n_objects, size_t* bytes);
+int dh_reproject_object_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                              int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                              const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                              int n_edits, const double* xforms_host, const float* bounds,
+                              float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                              uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);

@@ -1,26 +1,49 @@
 #!/usr/bin/env python3
-"""Batched K=8 reprojection of the bench scene (run under rocprofv3 --stats for per-kernel times)."""
+"""Batched K=8 reprojection of the bench scene (run under rocprofv3 --stats for per-kernel times).
+DH_OBJECTS=M (default 1): M = 1 is reproject_edits on the one-sphere scene; M = 2 is reproject_object_edits on the two-sphere
+scene of tests/multi_object_ref.py (both objects move in every edit; edit 0 is the one where object 0 hides object 1).
+DH_CALLS=n timed calls (default 5); the line reports their mean, median and minimum."""
 import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import torch
-from diffusionhandles_amd.depth_transform import reproject_edits
 from diffusionhandles_amd.guided_stable_diffuser import GuidedStableDiffuser
 from diffusionhandles_amd.synthetic import TRANSFORMS, make_scene
 dev = torch.device("cuda:0")
 res = int(os.environ.get("DH_RES", "512"))
-depth, bg_depth, mask = (t.to(dev) for t in make_scene(res))
+M = int(os.environ.get("DH_OBJECTS", "1"))
+n = int(os.environ.get("DH_CALLS", "5"))
 K = 8
-tfs = [(TRANSFORMS[i % 8][0], torch.tensor([0.0, 1.0, 0.0]), torch.tensor(TRANSFORMS[i % 8][1])) for i in range(K)]
+Y = torch.tensor([0.0, 1.0, 0.0])
+tfs = [(TRANSFORMS[i % 8][0], Y, torch.tensor(TRANSFORMS[i % 8][1])) for i in range(K)]
 intr = GuidedStableDiffuser.get_depth_intrinsics(dev)
+if M == 1:
+    from diffusionhandles_amd.depth_transform import reproject_edits
+    depth, bg_depth, mask = (t.to(dev) for t in make_scene(res))
+    call = lambda **kw: reproject_edits(depth, bg_depth, mask, intr, tfs, **kw)
+elif M == 2:
+    from diffusionhandles_amd.depth_transform import reproject_object_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    depth, bg_depth, masks = R.two_spheres(res)
+    depth, bg_depth, masks = depth.to(dev), bg_depth.to(dev), [m.to(dev) for m in masks]
+    as_t = lambda tf: (tf[0], torch.tensor(tf[1]), torch.tensor(tf[2]))
+    edits = [[as_t(tf) for tf in R.OCCLUDING]] + [[tfs[i], tfs[(i + 3) % 8]] for i in range(1, K)]
+    call = lambda **kw: reproject_object_edits(depth, bg_depth, masks, intr, edits, **kw)
+else:
+    sys.exit("DH_OBJECTS: 1 or 2")
 for _ in range(2):
-    reproject_edits(depth, bg_depth, mask, intr, tfs)
+    call()
 torch.cuda.synchronize()
-t0 = time.time()
-n = 5
+times = []
 for _ in range(n):
-    out = reproject_edits(depth, bg_depth, mask, intr, tfs)
-torch.cuda.synchronize()
-out, dbg = reproject_edits(depth, bg_depth, mask, intr, tfs, return_debug=True)
+    t0 = time.perf_counter()
+    out = call()
+    torch.cuda.synchronize()
+    times.append((time.perf_counter() - t0) * 1e3)
+out, dbg = call(return_debug=True)
 cn = dbg["counts"]
-print(f"K={K} res={res}: {(time.time()-t0)/n*1e3:.2f} ms per call; correspondences {[int(c.shape[0]) for _, c in out]}; "
+times.sort()
+print(f"K={K} M={M} res={res}: {sum(times)/n:.2f} ms per call (median {times[n // 2]:.2f}, min {times[0]:.2f}, {n} calls); "
+      f"foreground points {int(dbg['fg_pix'].numel())}; correspondences {[int(c.shape[0]) for _, c in out]}; "
       f"in-fill pixels {[int(v) for v in cn[:, 2]]}; CG iterations {[int(v) for v in cn[:, 3]]}")

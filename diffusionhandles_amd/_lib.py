@@ -75,6 +75,13 @@ SIGNATURES = {
                                         c_p, c_p, c_i, c_p, c_sz, c_p]),
     "dh_energy_planned_batch_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
     "dh_energy_fwd_bwd_planned_batch": (c_i, [ctypes.POINTER(EnergyItem), c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "dh_energy_plan_objects_bytes": (c_i, [c_i, c_i, ctypes.POINTER(c_sz)]),
+    "dh_energy_plan_build_objects": (c_i, [c_p, c_p, c_i, c_p, c_i, c_i, c_i, ctypes.POINTER(c_f), ctypes.POINTER(ctypes.c_int32),
+                                           c_p, c_sz, c_p]),
+    "dh_energy_fwd_bwd_planned_objects": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_i, c_p, c_i, c_p, c_i, c_f, c_f, c_f,
+                                                c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "dh_energy_planned_objects_batch_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
+    "dh_energy_fwd_bwd_planned_objects_batch": (c_i, [ctypes.POINTER(EnergyItem), c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "dh_unet_create": (c_i, [ctypes.POINTER(UNetConfig), ctypes.POINTER(c_p)]),
     "dh_unet_create_shared": (c_i, [c_p, c_i, c_p, ctypes.POINTER(c_p)]),
     "dh_unet_destroy": (None, [c_p]),

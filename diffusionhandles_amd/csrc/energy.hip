@@ -12,6 +12,8 @@
 // accumulated in float64 (segment order is the only order dependence).
 #include "common.h"
 
+#include <cmath>
+
 namespace dh {
 
 // ---- map load / store (with optional bilinear resize, align_corners = False) ----------
@@ -472,6 +474,113 @@ __global__ void k_final_loss_batch(const EnergyBatch tab) {
   }
 }
 
+// ---- a weight per object (dh_energy_plan_build_objects, dh_energy_fwd_bwd_planned_objects[_batch]) --------------------------
+// The foreground term becomes sum_m omega_m * mean_c mean_{n in object m} |.|, omega_m = w_m / sum of the weights of the objects
+// that have pairs.  The gradient of a target cell then mixes pairs of different objects with different coefficients, so the CSR
+// segment of a cell lists distinct (object, source cell) entries in ascending (object, cell) order, with one byte per entry for
+// the object.  The plan buffer is carve_plan's, then the raw fill and the object block (layout: energy_grad_obj_body.inc).
+constexpr int ENERGY_MAX_OBJECTS = 8;
+constexpr int OBJ_HEADER = 128;              // omega[8] f32, N[8] i32, omega / N [8] f64
+struct EnergyPlanObj {
+  EnergyPlan base;
+  int* raw;                                  // the fill before the dedupe: object << 24 | source cell, in the CSR's segments
+  uint8_t* objp;                             // header, then the object of every entry of base.src / base.mult
+};
+static bool carve_plan_obj(Arena& a, int grid, int n_pairs, EnergyPlanObj& p) {
+  carve_plan(a, grid, n_pairs, p.base);
+  p.raw = a.take<int>(n_pairs > 0 ? n_pairs : 1);
+  p.objp = a.take<uint8_t>((size_t)OBJ_HEADER + (n_pairs > 0 ? n_pairs : 1));
+  return a.ok();
+}
+struct ObjHeader {
+  float omega[ENERGY_MAX_OBJECTS];
+  int n[ENERGY_MAX_OBJECTS];
+  double lossw[ENERGY_MAX_OBJECTS];
+};
+__global__ void k_store_obj_header(const ObjHeader h, uint8_t* objp) {
+  const int i = threadIdx.x;
+  if (i >= ENERGY_MAX_OBJECTS) return;
+  reinterpret_cast<float*>(objp)[i] = h.omega[i];
+  reinterpret_cast<int*>(objp + 32)[i] = h.n[i];
+  reinterpret_cast<double*>(objp + 64)[i] = h.lossw[i];
+}
+
+__global__ void k_fill_obj(const int* pairs, const uint8_t* pair_obj, int n, int* cursor, int* raw) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int o = pairs[2 * (size_t)i], t = pairs[2 * (size_t)i + 1];
+  raw[atomicAdd(&cursor[t], 1)] = (int)((unsigned)o | ((unsigned)pair_obj[i] << 24));
+}
+
+// k_dedupe_sources per object: M passes over the segment with the one LDS histogram (a G2 x M histogram would not fit); pass m
+// appends the distinct source cells of object m in ascending order behind those of the objects before it.  The distinct entries
+// of a segment are never more than its raw entries, so every write stays inside the segment.
+__global__ void __launch_bounds__(256) k_dedupe_sources_obj(const int* off, const int* raw, int* src, int* mult, uint8_t* obj,
+                                                            int* ucnt, int G2, int M) {
+  extern __shared__ int hist[];          // [G2] counts, then [256] scan scratch
+  int* scan = hist + G2;
+  const int t = blockIdx.x, b = off[t], e = off[t + 1];
+  if (b == e) { if (threadIdx.x == 0) ucnt[t] = 0; return; }
+  const int per = (G2 + blockDim.x - 1) / blockDim.x, c0 = threadIdx.x * per, c1 = min(c0 + per, G2);
+  int base = b;
+  for (int m = 0; m < M; ++m) {
+    for (int c = threadIdx.x; c < G2; c += blockDim.x) hist[c] = 0;
+    __syncthreads();
+    for (int k = b + threadIdx.x; k < e; k += blockDim.x) {
+      const unsigned key = (unsigned)raw[k];
+      const int c = (int)(key & 0xffffffu);
+      if ((int)(key >> 24) == m && c < G2) atomicAdd(&hist[c], 1);
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int c = c0; c < c1; ++c) mine += hist[c] != 0;
+    scan[threadIdx.x] = mine;
+    __syncthreads();
+    for (int o = 1; o < (int)blockDim.x; o <<= 1) {
+      const int v = (int)threadIdx.x >= o ? scan[threadIdx.x - o] : 0;
+      __syncthreads();
+      scan[threadIdx.x] += v;
+      __syncthreads();
+    }
+    int pos = base + scan[threadIdx.x] - mine;
+    for (int c = c0; c < c1; ++c)
+      if (hist[c]) { src[pos] = c; mult[pos] = hist[c]; obj[pos] = (uint8_t)m; ++pos; }
+    base += scan[blockDim.x - 1];
+    __syncthreads();                     // hist and scan are reused by the next pass
+  }
+  if (threadIdx.x == 0) ucnt[t] = base - b;
+}
+
+// k_energy_grad with a weight per object: thread = (target cell, 8-channel chunk); block = 256 / (C/8) cells
+template <class T, class TG>
+__global__ void __launch_bounds__(256) k_energy_grad_obj(const T* orig, const T* cur, const int* off, const int* ucnt,
+                                                         const int* src, const int* mult, const uint8_t* objp, const uint8_t* bgflag,
+                                                         const float* partq, int n1, int n2, int C, int G2, float fg_w,
+                                                         float coef_bg, int use_bg, float scale, TG* grad, double* loss_part,
+                                                         double* bg_loss) {
+#include "energy_grad_obj_body.inc"
+}
+
+// K items: the item table of the unweighted batch (k_colsum_q_batch and k_final_loss_batch run on it as they are; coef_fg holds
+// the plain fg_w) and, next to it, one pointer per item to the object block of its plan -- both by value
+struct EnergyObjPtrs {
+  const uint8_t* p[ENERGY_MAX_ITEMS];
+};
+template <class T, class TG>
+__global__ void __launch_bounds__(256) k_energy_grad_obj_batch(const EnergyBatch tab, const EnergyObjPtrs ot, int C, int G2) {
+  const EnergyItem& it = tab.it[blockIdx.y];
+  const T *orig = (const T*)it.orig, *cur = (const T*)it.cur;
+  const int *off = it.off, *ucnt = it.ucnt, *src = it.src, *mult = it.mult;
+  const uint8_t* objp = ot.p[blockIdx.y];
+  const uint8_t* bgflag = it.bgflag;
+  const float* partq = it.partq;
+  const int n1 = it.n1, n2 = it.n2, use_bg = it.use_bg;
+  const float fg_w = it.coef_fg, coef_bg = it.coef_bg, scale = it.scale;
+  TG* grad = (TG*)it.grad;
+  double *loss_part = it.loss_part, *bg_loss = it.bg_loss;
+#include "energy_grad_obj_body.inc"
+}
+
 }  // namespace dh
 
 using namespace dh;
@@ -722,6 +831,198 @@ extern "C" int dh_energy_fwd_bwd_planned_batch(const dh_energy_item* items, int 
   if (dtype == DH_DTYPE_F16) DH_EGB(f16);
   else DH_EGB(bf16);
 #undef DH_EGB
+  if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+// ---- a weight per object --------------------------------------------------------------------------------------------------
+extern "C" int dh_energy_plan_objects_bytes(int grid, int n_pairs, size_t* bytes) {
+  DH_REQUIRE(grid >= 1 && n_pairs >= 0 && bytes, "bad arguments");
+  Arena a(nullptr, (size_t)-1);
+  EnergyPlanObj p;
+  carve_plan_obj(a, grid, n_pairs, p);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_energy_plan_build_objects(const int32_t* pairs, const uint8_t* pair_obj, int n_pairs, const int32_t* bg_trans,
+                                            int n_bg_trans, int grid, int n_objects, const float* weights, const int32_t* counts,
+                                            void* plan, size_t plan_bytes, void* stream) {
+  DH_REQUIRE(plan && grid >= 1 && n_pairs >= 0 && n_bg_trans >= 0, "bad arguments");
+  DH_REQUIRE((size_t)(grid * grid + 256) * sizeof(int) <= 64 * 1024, "grid too large for the dedupe histogram");
+  DH_REQUIRE((n_pairs == 0 || (pairs && pair_obj)) && (n_bg_trans == 0 || bg_trans), "null list");
+  DH_REQUIRE(n_objects >= 1 && n_objects <= ENERGY_MAX_OBJECTS, "1..8 objects");
+  DH_REQUIRE(weights && counts, "null weights or counts");
+  double sum = 0.0;
+  long long total = 0;
+  for (int m = 0; m < n_objects; ++m) {
+    DH_REQUIRE(std::isfinite(weights[m]) && weights[m] >= 0.f, "an object weight is negative or not finite");
+    DH_REQUIRE(counts[m] >= 0, "negative object count");
+    total += counts[m];
+    if (counts[m] > 0) sum += (double)weights[m];
+  }
+  DH_REQUIRE(total == (long long)n_pairs, "the object counts do not add up to n_pairs");
+  DH_REQUIRE(n_pairs == 0 || sum > 0.0, "no positive weight among the objects that have pairs");
+  ObjHeader h;
+  for (int m = 0; m < ENERGY_MAX_OBJECTS; ++m) {
+    const bool live = m < n_objects && counts[m] > 0;
+    const double om = live ? (double)weights[m] / sum : 0.0;
+    h.omega[m] = (float)om;
+    h.n[m] = live ? counts[m] : 0;
+    h.lossw[m] = live ? om / (double)counts[m] : 0.0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int G2 = grid * grid;
+  Arena a(plan, plan_bytes);
+  EnergyPlanObj po;
+  DH_REQUIRE(carve_plan_obj(a, grid, n_pairs, po), "plan buffer too small");
+  const EnergyPlan& p = po.base;
+  DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
+  DH_CHECK_HIP(hipMemsetAsync(p.bgflag, 0, G2, st));
+  hipLaunchKernelGGL(k_store_obj_header, dim3(1), dim3(64), 0, st, h, po.objp);
+  if (n_pairs > 0) hipLaunchKernelGGL(k_hist, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, p.cnt, p.w1, p.w2);
+  hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, st, p.cnt, G2, p.off, p.cursor);
+  if (n_pairs > 0) {
+    hipLaunchKernelGGL(k_fill_obj, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, pair_obj, n_pairs, p.cursor, po.raw);
+    hipLaunchKernelGGL(k_dedupe_sources_obj, dim3(G2), dim3(256), (size_t)(G2 + 256) * sizeof(int), st, p.off, po.raw, p.src, p.mult,
+                       po.objp + OBJ_HEADER, p.cnt, G2, n_objects);
+  } else {
+    DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
+  }
+  if (n_bg_trans > 0) hipLaunchKernelGGL(k_flag_cells, dim3(cdiv(n_bg_trans, 256)), dim3(256), 0, st, bg_trans, n_bg_trans, p.bgflag);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+template <class T, class TG>
+static void launch_energy_grad_obj(const void* orig, const void* cur, const EnergyPlanObj& po, const PlannedWs& w, int C, int G2,
+                                   float fg_w, float coef_bg, int use_bg, float scale, void* grad, int nblocks, hipStream_t st,
+                                   int n1, int n2) {
+  const EnergyPlan& p = po.base;
+  hipLaunchKernelGGL((k_energy_grad_obj<T, TG>), dim3(nblocks), dim3(256), 0, st, (const T*)orig, (const T*)cur, p.off, p.cnt,
+                     p.src, p.mult, po.objp, p.bgflag, w.partq, n1, n2, C, G2, fg_w, coef_bg, use_bg, scale, (TG*)grad, w.fg_part,
+                     w.bg_part);
+}
+
+extern "C" int dh_energy_fwd_bwd_planned_objects(const void* cur, const void* orig, int dtype, int C, int grid, const void* plan,
+                                                 size_t plan_bytes, int n_pairs, const int32_t* bg_orig, int n_bg_orig,
+                                                 const int32_t* bg_trans, int n_bg_trans, float fg_w, float bg_w,
+                                                 float grad_scale, float* loss_out, void* grad, int grad_dtype, void* workspace,
+                                                 size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(cur && orig && grad && plan && workspace, "null pointer");
+  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
+  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
+  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1 && n_pairs >= 0, "bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  const int G2 = grid * grid;
+  Arena ap(const_cast<void*>(plan), plan_bytes);
+  EnergyPlanObj po;
+  DH_REQUIRE(carve_plan_obj(ap, grid, n_pairs, po), "plan buffer too small");
+  Arena aw(workspace, workspace_bytes);
+  PlannedWs w;
+  DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
+
+  const float fg_norm = n_pairs > 0 ? 1.f / (float)C : 0.f;      // the loss partials carry omega_m / N_m
+  float bg_norm = 0.f, coef_bg = 0.f;
+  int use_bg = 0;
+  if (n_bg_orig > 0 && n_bg_trans > 0) {
+    DH_REQUIRE(bg_orig && bg_trans, "null bg list");
+    if (dtype == DH_DTYPE_F16)
+      hipLaunchKernelGGL((k_colsum_q<f16>), dim3(cdiv(C, 64), 4, 2), dim3(8 * CQ_SL), 0, st, (const f16*)orig, bg_orig, n_bg_orig,
+                         (const f16*)cur, bg_trans, n_bg_trans, C, w.partq);
+    else
+      hipLaunchKernelGGL((k_colsum_q<bf16>), dim3(cdiv(C, 64), 4, 2), dim3(8 * CQ_SL), 0, st, (const bf16*)orig, bg_orig, n_bg_orig,
+                         (const bf16*)cur, bg_trans, n_bg_trans, C, w.partq);
+    bg_norm = 1.f / (float)C;
+    coef_bg = bg_w * bg_norm / (float)n_bg_trans;
+    use_bg = 1;
+  }
+  const int cpb = 256 / (C / 8);
+  const int nblocks = cdiv(G2, cpb);
+#define DH_EGO(T_)                                                                                                         \
+  do {                                                                                                                     \
+    if (grad_dtype == DH_DTYPE_F16) launch_energy_grad_obj<T_, f16>(orig, cur, po, w, C, G2, fg_w, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans);        \
+    else if (grad_dtype == DH_DTYPE_BF16) launch_energy_grad_obj<T_, bf16>(orig, cur, po, w, C, G2, fg_w, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans); \
+    else launch_energy_grad_obj<T_, float>(orig, cur, po, w, C, G2, fg_w, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans);    \
+  } while (0)
+  if (dtype == DH_DTYPE_F16) DH_EGO(f16);
+  else DH_EGO(bf16);
+#undef DH_EGO
+  if (loss_out)
+    hipLaunchKernelGGL(k_final_loss, dim3(1), dim3(256), 0, st, w.fg_part, n_pairs > 0 ? nblocks : 0, fg_norm, w.bg_part,
+                       use_bg ? 1 : 0, bg_norm, fg_w, bg_w, loss_out);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_energy_planned_objects_batch_workspace_bytes(int C, int grid, int n_items, size_t* bytes) {
+  return dh_energy_planned_batch_workspace_bytes(C, grid, n_items, bytes);
+}
+
+extern "C" int dh_energy_fwd_bwd_planned_objects_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
+                                                       int grad_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(items && workspace, "null pointer");
+  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items (larger batches are not split)");
+  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
+  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
+  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1, "bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  const int G2 = grid * grid;
+  const int cpb = 256 / (C / 8);
+  const int nblocks = cdiv(G2, cpb);
+  Arena aw(workspace, workspace_bytes);
+  EnergyBatch tab;
+  EnergyObjPtrs ot;
+  bool any_bg = false, any_loss = false;
+  for (int e = 0; e < n_items; ++e) {
+    const dh_energy_item& in = items[e];
+    EnergyItem& it = tab.it[e];
+    DH_REQUIRE(in.cur && in.orig && in.grad && in.plan, "null pointer in an item");
+    DH_REQUIRE(in.n_pairs >= 0, "bad sizes");
+    Arena ap(const_cast<void*>(in.plan), in.plan_bytes);
+    EnergyPlanObj po;
+    DH_REQUIRE(carve_plan_obj(ap, grid, in.n_pairs, po), "plan buffer too small");
+    const EnergyPlan& p = po.base;
+    PlannedWs w;
+    DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
+    ot.p[e] = po.objp;
+    it.orig = in.orig; it.cur = in.cur;
+    it.off = p.off; it.ucnt = p.cnt; it.src = p.src; it.mult = p.mult; it.bgflag = p.bgflag;
+    it.list1 = in.bg_orig; it.list2 = in.bg_trans;
+    it.partq = w.partq; it.grad = in.grad; it.loss_part = w.fg_part; it.bg_loss = w.bg_part; it.loss_out = in.loss_out;
+    it.n1 = in.n_bg_orig; it.n2 = in.n_bg_trans;
+    it.fg_norm = in.n_pairs > 0 ? 1.f / (float)C : 0.f;
+    it.bg_norm = 0.f; it.coef_bg = 0.f; it.use_bg = 0;
+    if (in.n_bg_orig > 0 && in.n_bg_trans > 0) {
+      DH_REQUIRE(in.bg_orig && in.bg_trans, "null bg list");
+      it.bg_norm = 1.f / (float)C;
+      it.coef_bg = in.bg_w * it.bg_norm / (float)in.n_bg_trans;
+      it.use_bg = 1;
+      any_bg = true;
+    }
+    it.coef_fg = in.fg_w;                // the weighted kernel forms fg_w * omega_m / (C N_m) itself
+    it.scale = in.grad_scale;
+    it.n_fg_part = in.n_pairs > 0 ? nblocks : 0;
+    it.fg_w = in.fg_w; it.bg_w = in.bg_w;
+    any_loss = any_loss || in.loss_out != nullptr;
+  }
+  for (int e = n_items; e < ENERGY_MAX_ITEMS; ++e) { tab.it[e] = tab.it[0]; ot.p[e] = ot.p[0]; }      // (never indexed)
+  if (any_bg) {
+    if (dtype == DH_DTYPE_F16)
+      hipLaunchKernelGGL((k_colsum_q_batch<f16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
+    else
+      hipLaunchKernelGGL((k_colsum_q_batch<bf16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
+  }
+#define DH_EGOB(T_)                                                                                                            \
+  do {                                                                                                                         \
+    if (grad_dtype == DH_DTYPE_F16) hipLaunchKernelGGL((k_energy_grad_obj_batch<T_, f16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2);        \
+    else if (grad_dtype == DH_DTYPE_BF16) hipLaunchKernelGGL((k_energy_grad_obj_batch<T_, bf16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2); \
+    else hipLaunchKernelGGL((k_energy_grad_obj_batch<T_, float>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2);   \
+  } while (0)
+  if (dtype == DH_DTYPE_F16) DH_EGOB(f16);
+  else DH_EGOB(bf16);
+#undef DH_EGOB
   if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
   DH_LAUNCH_CHECK();
   return DH_OK;

@@ -111,36 +111,55 @@ class DiffusionHandles:
         return reproject_object_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
                                       use_input_depth_normalization, device_correspondences=device_correspondences)
 
+    @staticmethod
+    def _object_labels(fg_masks, object_weights):
+        """Host checks of object_weights against the M masks (ValueError, before any launch) and the label image the
+        guidance needs; (None, None) for None: the unweighted path."""
+        if object_weights is None:
+            return None, None
+        from .losses import check_object_weights, object_label_image
+        weights = check_object_weights(object_weights, len(fg_masks))
+        return object_label_image(fg_masks), weights
+
     def transform_foreground_objects(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
-                                     transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False):
+                                     transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
+                                     object_weights=None):
         """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
         rot_axis[3], translation[3]), one per mask.  Each object turns about its own centroid; they occlude the background
         and each other (depth_transform.reproject_object_edits).  The guidance sees the union of the correspondences: its
-        foreground term is the mean over all pairs, so the objects weigh by covered area (no per-object weights).
-        Returns what transform_foreground returns.  'pc' re-projection only."""
+        foreground term is the mean over all pairs, so the objects weigh by covered area -- unless object_weights says
+        otherwise: "equal" holds every object equally, a sequence of M floats (finite, >= 0, not all zero) sets each weight;
+        objects without a visible correspondence drop out and the rest are renormalised (DESIGN.md "A weight per object";
+        default configuration only).  Returns what transform_foreground returns.  'pc' re-projection only."""
+        labels, object_weights = self._object_labels(fg_masks, object_weights)
         with torch.no_grad():
             (edited_disparity, correspondences), = self._reproject_objects(
                 "transform_foreground_objects", depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False)
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
-                bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps)
+                bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps,
+                object_labels=labels, object_weights=object_weights)
         if self.conf.guided_diffuser.save_denoising_steps:
             edited_img, denoising_steps = results
             return edited_img, edited_disparity, denoising_steps
         return results, edited_disparity
 
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
-                                           edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False):
+                                           edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
+                                           object_weights=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
         edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]).  Returns (images [K,3,H,W], [K disparities]) as
-        transform_foreground_batch does on one stream."""
+        transform_foreground_batch does on one stream.  object_weights: as in transform_foreground_objects, one list for all
+        K edits."""
+        labels, object_weights = self._object_labels(fg_masks, object_weights)
         with torch.no_grad():
             res = self._reproject_objects("transform_foreground_objects_batch", depth, bg_depth, fg_masks, edits,
                                           use_input_depth_normalization, True)
             imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
-                                                        [c for _, c in res], fg_weight, bg_weight)
+                                                        [c for _, c in res], fg_weight, bg_weight, object_labels=labels,
+                                                        object_weights=object_weights)
         return imgs, [d for d, _ in res]
 
     EDIT_FIELDS = ("depth", "prompt", "fg_mask", "bg_depth", "null_text_emb", "init_noise", "activations")

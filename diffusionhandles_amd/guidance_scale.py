@@ -2,7 +2,7 @@
 
 The guidance energy is L1 (csrc/energy.hip), so the cotangent it writes for a layer is, per activation element,
   -coef_fg * (signed multiplicity sum of the pairs that target the cell) - coef_bg * sign        (patch size 1)
-with coef_fg = fg_w / (C n_pairs), coef_bg = bg_w / (C n_bg_trans) ('global_avg') or bg_w / (C n_bg_both) ('local_avg').
+with coef_fg = fg_w / (C n_pairs) (fg_w omega_m / (C N_m) for a pair of object m under object weights), coef_bg = bg_w / (C n_bg_trans) ('global_avg') or bg_w / (C n_bg_both) ('local_avg').
 Its largest magnitude is bounded by the weights and the correspondence structure alone: the multiplicity of each target
 cell, spread through the masked box filter of a patch size > 1 (k_spread: sum over the window of count / window-weight),
 and, for a map smaller than the cell grid, through the adjoint of the bilinear resize (k_store_grad).  No activation value
@@ -93,15 +93,32 @@ def _to_input(grid_map, h, w):
     return _bilinear_matrix(h, G).T @ grid_map @ _bilinear_matrix(w, G)
 
 
-def layer_unit_bounds(pc, grid, h, w, C, fg_patch=1, bg_patch=1, bg_loss_type="global_avg"):
+def layer_unit_bounds(pc, grid, h, w, C, fg_patch=1, bg_patch=1, bg_loss_type="global_avg", objects=None, omega=None):
     """(U_fg, U_bg): maps [h, w] with |cotangent| <= fg_w U_fg + bg_w U_bg (before the grad scale) for one layer whose
-    activation is h x w x C, under the correspondences pc (the dict of process_correspondences)."""
+    activation is h x w x C, under the correspondences pc (the dict of process_correspondences).
+    objects / omega (a weight per object, losses.object_omegas): the 0-based object of every pair and omega_m; the coefficient
+    of a pair of object m is omega_m / (C N_m), so the foreground map is sum_m (omega_m / N_m) cnt_m / C with cnt_m the
+    per-cell target counts of object m.  Patch size 1 only (the weighted energy has no pooled form)."""
     G = int(grid)
     tgt = np.asarray(pc["transformed_y"], dtype=np.int64) * G + np.asarray(pc["transformed_x"], dtype=np.int64)
     n_pairs = tgt.size
     zero = np.zeros((G, G))
     fg = zero
-    if n_pairs > 0:
+    if objects is not None:
+        if fg_patch != 1:
+            raise NotImplementedError("object weights: fg_patch_size must be 1")
+        objects = np.asarray(objects, dtype=np.int64)
+        omega = np.asarray(omega, dtype=np.float64)
+        if objects.size != n_pairs:
+            raise ValueError(f"{objects.size} objects for {n_pairs} pairs")
+        acc = np.zeros(G * G, dtype=np.float64)
+        for m in range(len(omega)):                      # ascending objects: the kernel's order
+            sel = objects == m
+            n_m = int(sel.sum())
+            if n_m > 0:
+                acc += (omega[m] / n_m) * np.bincount(tgt[sel], minlength=G * G)
+        fg = acc.reshape(G, G) / C
+    elif n_pairs > 0:
         cnt = np.bincount(tgt, minlength=G * G).reshape(G, G)
         fg = _pair_map(cnt, fg_patch) / (C * n_pairs)
     bg = zero
@@ -123,11 +140,11 @@ def layer_unit_bounds(pc, grid, h, w, C, fg_patch=1, bg_patch=1, bg_loss_type="g
 
 
 def scale_table(pc, grid, shapes, schedule, n_steps, n_iters, max_step, fg_patch=1, bg_patch=1, bg_loss_type="global_avg",
-                target=TARGET_AMPLITUDE):
+                target=TARGET_AMPLITUDE, objects=None, omega=None):
     """[n_steps, n_iters] float64 table of S (powers of two) for one edit, and the [n_steps, n_iters, 3] bounds B_k behind it.
     shapes: (h, w, C) of the three guided activations; schedule(t_idx, iteration) -> (fg 3-list, bg 3-list).  Entries of
-    steps past max_step (no guidance) are 1."""
-    units = [layer_unit_bounds(pc, grid, h, w, C, fg_patch, bg_patch, bg_loss_type) for h, w, C in shapes]
+    steps past max_step (no guidance) are 1.  objects / omega: a weight per object (layer_unit_bounds)."""
+    units = [layer_unit_bounds(pc, grid, h, w, C, fg_patch, bg_patch, bg_loss_type, objects, omega) for h, w, C in shapes]
     peaks = [(U_fg.ravel(), U_bg.ravel()) for U_fg, U_bg in units]      # fixed maps: only the two weights change per entry
     n_pairs = len(pc["transformed_x"])
     S = np.ones((n_steps, n_iters), dtype=np.float64)

@@ -22,8 +22,8 @@ import torch
 from . import _lib
 from . import guidance_scale as _gs
 from .guided_diffuser import GuidedDiffuser
-from .losses import (MAX_BATCH_ITEMS, EnergyPlan, energy_and_grad, energy_and_grad_planned, energy_and_grad_planned_batch,
-                     process_correspondences as _process_correspondences)
+from .losses import (MAX_BATCH_ITEMS, EnergyPlan, check_object_weights as _check_object_weights, energy_and_grad,
+                     energy_and_grad_planned, energy_and_grad_planned_batch, process_correspondences as _process_correspondences)
 from .scheduler import DDIMScheduler
 from .unet import HipUNet, SD2_DEPTH
 
@@ -428,16 +428,43 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return [([a.permute(0, 3, 1, 2) for a in store[b]], x[b:b + 1].permute(0, 3, 1, 2), uncs[b], inits[b])
                 for b in range(K)]
 
+    def _check_object_weights(self, object_labels, object_weights, activations_orig):
+        """Host checks of prepare_guidance's object weights, before any device work: labels present, default configuration."""
+        if object_labels is None:
+            raise ValueError("object_weights need object_labels (the label image of the object masks)")
+        if self.conf.fg_patch_size != 1:
+            raise NotImplementedError(f"object_weights with fg_patch_size = {self.conf.fg_patch_size} (only 1: the weighted "
+                                      "energy has no pooled form)")
+        if self.conf.bg_loss_type != "global_avg":
+            raise NotImplementedError(f"object_weights with bg_loss_type = {self.conf.bg_loss_type!r} (only 'global_avg')")
+        size = tuple(activations_orig[2].shape[-2:])
+        for k in (1, 2):                     # the layers build_weight_schedule guides
+            if tuple(activations_orig[k].shape[-2:]) != size:
+                raise NotImplementedError(f"object_weights with guided layer {k} off the cell grid "
+                                          f"({tuple(activations_orig[k].shape[-2:])} / {size})")
+        # (the number of objects is the label image's: the facade checks the length against its masks)
+        n = len(object_weights) if hasattr(object_weights, "__len__") and not isinstance(object_weights, str) else 0
+        _check_object_weights(object_weights, n)
+
     def prepare_guidance(self, depth, prompt, activations_orig, correspondences, fg_weight=None, bg_weight=None, orig=None,
-                         cond=None):
+                         cond=None, object_labels=None, object_weights=None):
         """Everything of guided_inference that is constant over the denoising loop.  `orig`: the channels-last copies of
         the original activations of another guidance state of the SAME image (K edits of one image share them); `cond`: the
-        prompt embedding when the caller already has it (lanes: the text tower is not run concurrently with itself)."""
+        prompt embedding when the caller already has it (lanes: the text tower is not run concurrently with itself).
+        object_labels / object_weights (multi-object edits): the label image of the object masks (losses.object_label_image)
+        and "equal" or one weight per object -- the foreground term then weighs the objects by omega_m instead of by their
+        pair counts (DESIGN.md "A weight per object").  None: the area weighting, on the unchanged path."""
         from types import SimpleNamespace
+        if object_weights is not None:
+            self._check_object_weights(object_labels, object_weights, activations_orig)
         fg_weight = self.conf.fg_weight if fg_weight is None else fg_weight
         bg_weight = self.conf.bg_weight if bg_weight is None else bg_weight
         st = SimpleNamespace()
-        st.pc = self.process_correspondences(correspondences, img_res=depth.shape[-1], bg_erosion=self.conf.bg_erosion)
+        if object_weights is None:
+            st.pc = self.process_correspondences(correspondences, img_res=depth.shape[-1], bg_erosion=self.conf.bg_erosion)
+        else:
+            st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
+                                             device=self.device, object_labels=object_labels)
         st.depth_nhwc = _nhwc(self.init_depth(depth.to(self.device, torch.float32))) if self.conf.use_depth else None
         st.cond = self._encode([prompt]).contiguous() if cond is None else cond
         GuidedStableDiffuser._text_keys += 1
@@ -453,14 +480,18 @@ class GuidedStableDiffuser(GuidedDiffuser):
         st.plan = None
         if (self.conf.fg_patch_size == 1 and self.conf.bg_loss_type == "global_avg"
                 and all(o.shape[1] == st.size[0] and o.shape[2] == st.size[1] for o in st.orig[1:])):
-            st.plan = EnergyPlan(st.pc, st.size[0], self.device)
+            st.plan = EnergyPlan(st.pc, st.size[0], self.device, object_weights=object_weights)
+        elif object_weights is not None:
+            raise NotImplementedError("object_weights need the planned energy (default configuration, layers on the cell grid)")
+        weighted = st.plan is not None and st.plan.weighted
         st.auto = self.grad_scale_mode == "auto"
         if st.auto:
             # S per (timestep, iteration): host copy for the energy calls, device copy for the guarded update
             st.scale_host, st.bounds = _gs.scale_table(
                 st.pc, st.size[0], [tuple(o.shape[1:]) for o in st.orig], st.schedule, int(self.conf.num_timesteps),
                 int(self.conf.num_optsteps), int(self.conf.guidance_max_step), self.conf.fg_patch_size,
-                self.conf.bg_patch_size, self.conf.bg_loss_type)
+                self.conf.bg_patch_size, self.conf.bg_loss_type, objects=st.pc["object"] if weighted else None,
+                omega=st.plan.omega if weighted else None)
             st.scale_dev = torch.tensor(st.scale_host, dtype=torch.float32).to(self.device)[None].contiguous()
             st.status = torch.zeros((1, 4), dtype=torch.int32, device=self.device)
         return st
@@ -567,6 +598,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         S = [float(st.scale_host[t_idx, iteration]) if auto else self.grad_scale for st in sts]
         g = acts_k.shape[1]
         planned = [e for e, st in enumerate(sts) if st.plan is not None and g == st.plan.grid and acts_k.shape[2] == g]
+        if len({sts[e].plan.weighted for e in planned}) > 1:
+            planned = []          # weighted and unweighted plans do not share a launch: such a batch goes item by item
         if not (self._batch_energy and 2 <= len(planned) <= MAX_BATCH_ITEMS):
             planned = []
         if planned:
@@ -638,11 +671,13 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return sts[0]._batch_guard[2]
 
     def _batch_edit_steps(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
-                          fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None):
+                          fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None,
+                          object_weights=None):
         """The batched edit as a generator: yields after the preparation and after every denoising step (everything is only
         ENQUEUED on the current stream by then), returns the final latents [K,4,H,W] through StopIteration.  One body for the
         one-stream call below and for the lanes of guided_inference_batch_lanes.  fg_weight / bg_weight: one value, or one per
-        edit.  status_out: a list that receives the device [K, 4] status ('auto') at the end."""
+        edit.  status_out: a list that receives the device [K, 4] status ('auto') at the end.  object_labels / object_weights: one
+        label image and one weight list for all K edits (prepare_guidance)."""
         K = len(depths)
         per = lambda w, i: w[i] if isinstance(w, (list, tuple)) else w
         if self.unet.max_batch < 2 * K:
@@ -653,7 +688,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         sts = []
         for i, (d, c) in enumerate(zip(depths, correspondences_list)):
             sts.append(self.prepare_guidance(d, prompt, activations_orig, c, per(fg_weight, i), per(bg_weight, i),
-                                             orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond))
+                                             orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond,
+                                             object_labels=object_labels, object_weights=object_weights))
         x = _nhwc(latents.to(self.device, torch.float32)).expand(K, -1, -1, -1).contiguous()
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -664,14 +700,16 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_batch(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
-                               fg_weight=None, bg_weight=None):
+                               fg_weight=None, bg_weight=None, object_labels=None, object_weights=None):
         """K edits of one image at once.  depths: list of K edited disparities [1,1,H,W]; correspondences_list:
         K [N_k,4] tensors; fg_weight / bg_weight: one value or K.  Needs an engine built with max_batch >= 2K.  Returns images
-        [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value."""
+        [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value.  object_labels / object_weights: one
+        label image and one weight list for all K edits (prepare_guidance)."""
         status = []
         with torch.no_grad(), self.on_stream():
             gen = self._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
-                                         fg_weight, bg_weight, status_out=status)
+                                         fg_weight, bg_weight, status_out=status, object_labels=object_labels,
+                                         object_weights=object_weights)
             try:
                 while True:
                     next(gen)
@@ -893,12 +931,15 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return images
 
     def guided_inference(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences,
-                         fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None):
+                         fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None, object_labels=None,
+                         object_weights=None):
+        """object_labels / object_weights: a weight per object for the foreground term (prepare_guidance)."""
         with torch.no_grad(), self.on_stream():
             torch.manual_seed(self.conf.seed)
             self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
             timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
-            st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight)
+            st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight,
+                                       object_labels=object_labels, object_weights=object_weights)
             denoising_steps = {"opt": [], "post-opt": []} if save_denoising_steps else None
             x = _nhwc(latents.to(self.device, torch.float32))
             for t_idx, t in enumerate(timesteps):

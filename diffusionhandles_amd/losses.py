@@ -23,8 +23,64 @@ class ProcessedCorrespondences(dict):
     device_lists = None
 
 
-def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None):
-    """[N,4] int64 (ox,oy,tx,ty) -> dict with original_x/y, transformed_x/y, background_x/y[_orig|_trans]."""
+MAX_OBJECTS = 8           # ENERGY_MAX_OBJECTS of csrc/energy.hip
+
+
+def object_label_image(fg_masks):
+    """[H, W] uint8 label image of M pairwise disjoint masks: 0 outside all of them, m + 1 inside mask m."""
+    if len(fg_masks) < 1 or len(fg_masks) > MAX_OBJECTS:
+        raise ValueError(f"object labels: {len(fg_masks)} masks, 1 to {MAX_OBJECTS} are supported")
+    m0 = torch.as_tensor(fg_masks[0])
+    H, W = m0.shape[-2:]
+    label = torch.zeros((H, W), dtype=torch.uint8, device=m0.device)
+    for m, mask in enumerate(fg_masks):
+        inside = torch.as_tensor(mask).reshape(H, W) != 0
+        if bool((label[inside] != 0).any()):
+            raise ValueError(f"object labels: mask {m} overlaps an earlier mask")
+        label[inside] = m + 1
+    return label
+
+
+def check_object_weights(object_weights, n_objects):
+    """None | "equal" | a sequence of n_objects finite weights >= 0, not all zero -> None | list of floats (host checks only)."""
+    if object_weights is None:
+        return None
+    if isinstance(object_weights, str):
+        if object_weights != "equal":
+            raise ValueError(f"object_weights must be None, 'equal' or a sequence of floats, got {object_weights!r}")
+        return [1.0] * int(n_objects)
+    try:
+        w = [float(v) for v in object_weights]
+    except TypeError:
+        raise ValueError(f"object_weights must be None, 'equal' or a sequence of floats, got {object_weights!r}") from None
+    if len(w) != int(n_objects):
+        raise ValueError(f"object_weights has {len(w)} entries for {n_objects} objects")
+    if any(not np.isfinite(v) or v < 0.0 for v in w):
+        raise ValueError(f"object_weights must be finite and >= 0, got {w}")
+    if not any(v > 0.0 for v in w):
+        raise ValueError("object_weights are all zero")
+    return w
+
+
+def object_omegas(objects, weights):
+    """(N_m, omega_m) float64 of per-pair objects (0-based ints) and weights w_m: omega_m = w_m / sum of w_j over the objects
+    that have pairs, 0 for an object without pairs.  ValueError when no object that has pairs has a positive weight."""
+    w = np.asarray(weights, dtype=np.float64)
+    counts = np.bincount(np.asarray(objects, dtype=np.int64), minlength=len(w))
+    if len(counts) > len(w):
+        raise ValueError(f"a pair belongs to object {len(counts) - 1}, there are {len(w)} weights")
+    live = counts > 0
+    total = float(w[live].sum())
+    if live.any() and not total > 0.0:
+        raise ValueError("object_weights: no positive weight among the objects that have correspondences")
+    omega = np.where(live, w / total, 0.0) if live.any() else np.zeros_like(w)
+    return counts, omega
+
+
+def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, object_labels=None):
+    """[N,4] int64 (ox,oy,tx,ty) -> dict with original_x/y, transformed_x/y, background_x/y[_orig|_trans].
+    object_labels ([H, W] uint8, object_label_image): adds "object", the 0-based object of every kept pair (int64, host), and
+    `pair_obj` (uint8, device) to device_lists."""
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     L = _lib.lib()
@@ -56,6 +112,18 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
     })
     out.device_lists = dict(pairs=pairs, bg_both=lists[0], bg_orig=lists[1], bg_trans=lists[2],
                             bg_masks=bg_masks.view(3, grid, grid), grid=grid)
+    if object_labels is not None:
+        lab = torch.as_tensor(object_labels).to(dev)
+        ok = (corr[:, 2] >= 0) & (corr[:, 2] < img_res) & (corr[:, 3] >= 0) & (corr[:, 3] < img_res)      # k_valid's test
+        kept = corr[ok]
+        obj = lab[kept[:, 1], kept[:, 0]].to(torch.int64) - 1
+        oh = obj.cpu().numpy()
+        if oh.shape[0] != ph.shape[0]:
+            raise RuntimeError("object labels: the kept correspondences do not match the cell pairs")
+        if oh.size and oh.min() < 0:
+            raise ValueError("object labels: a correspondence starts outside every object mask")
+        out["object"] = oh
+        out.device_lists["pair_obj"] = obj.to(torch.uint8).contiguous()
     return out
 
 
@@ -66,9 +134,12 @@ def _device_lists(pc, dev, grid):
     g = grid
     mk = lambda y, x: torch.as_tensor(np.asarray(pc[y]) * g + np.asarray(pc[x]), dtype=torch.int32, device=dev)
     pairs = torch.stack([mk("original_y", "original_x"), mk("transformed_y", "transformed_x")], dim=-1).contiguous()
-    return dict(pairs=pairs, bg_both=mk("background_y", "background_x"),
-                bg_orig=mk("background_y_orig", "background_x_orig"),
-                bg_trans=mk("background_y_trans", "background_x_trans"), grid=g)
+    dl = dict(pairs=pairs, bg_both=mk("background_y", "background_x"),
+              bg_orig=mk("background_y_orig", "background_x_orig"),
+              bg_trans=mk("background_y_trans", "background_x_trans"), grid=g)
+    if "object" in pc:
+        dl["pair_obj"] = torch.as_tensor(np.asarray(pc["object"]), dtype=torch.uint8, device=dev)
+    return dl
 
 
 _WS = {}
@@ -76,13 +147,31 @@ _WS = {}
 
 class EnergyPlan:
     """Per-edit constants of the guidance energy on one cell grid: device index lists, the
-    target-cell -> source-cells CSR and the transformed-background flags (dh_energy_plan_build)."""
+    target-cell -> source-cells CSR and the transformed-background flags (dh_energy_plan_build).
+    object_weights ("equal" or one weight per object; the correspondences must carry "object", process_correspondences with
+    object_labels): the weighted plan of dh_energy_plan_build_objects -- `weighted` is then True, `omega` / `counts` hold
+    omega_m and N_m, and the planned calls route to the _objects entries.  None, or a single object: the plan above."""
 
-    def __init__(self, processed_correspondences, grid, device):
+    weighted = False
+
+    def __init__(self, processed_correspondences, grid, device, object_weights=None):
         L = _lib.lib()
         self.grid = int(grid)
         self.dl = _device_lists(processed_correspondences, device, self.grid)
         self.n_pairs = int(self.dl["pairs"].shape[0])
+        self._ws = {}
+        if object_weights is not None:
+            if "object" not in processed_correspondences:
+                raise ValueError("EnergyPlan: object_weights need correspondences processed with object_labels")
+            objects = np.asarray(processed_correspondences["object"], dtype=np.int64)
+            M = (int(objects.max()) + 1 if objects.size else 1) if isinstance(object_weights, str) else len(object_weights)
+            w = check_object_weights(object_weights, M)
+            if not 1 <= M <= MAX_OBJECTS:
+                raise ValueError(f"EnergyPlan: {M} objects, 1 to {MAX_OBJECTS} are supported")
+            counts, omega = object_omegas(objects, w)
+            if M > 1:
+                self._build_weighted(L, w, counts, omega, device)
+                return
         nb = ctypes.c_size_t()
         _lib.check(L.dh_energy_plan_bytes(self.grid, self.n_pairs, ctypes.byref(nb)), "dh_energy_plan_bytes")
         self.nbytes = nb.value
@@ -90,7 +179,20 @@ class EnergyPlan:
         _lib.check(L.dh_energy_plan_build(_lib.ptr(self.dl["pairs"]), self.n_pairs, _lib.ptr(self.dl["bg_trans"]),
                                           self.dl["bg_trans"].numel(), self.grid, _lib.ptr(self.buf), self.nbytes,
                                           _lib.stream_ptr()), "dh_energy_plan_build")
-        self._ws = {}
+
+    def _build_weighted(self, L, w, counts, omega, device):
+        M = len(w)
+        if self.dl.get("pair_obj") is None or self.dl["pair_obj"].numel() != self.n_pairs:
+            raise ValueError("EnergyPlan: the device lists carry no object per pair")
+        self.weighted, self.counts, self.omega = True, counts, omega
+        nb = ctypes.c_size_t()
+        _lib.check(L.dh_energy_plan_objects_bytes(self.grid, self.n_pairs, ctypes.byref(nb)), "dh_energy_plan_objects_bytes")
+        self.nbytes = nb.value
+        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        _lib.check(L.dh_energy_plan_build_objects(
+            _lib.ptr(self.dl["pairs"]), _lib.ptr(self.dl["pair_obj"]), self.n_pairs, _lib.ptr(self.dl["bg_trans"]),
+            self.dl["bg_trans"].numel(), self.grid, M, (ctypes.c_float * M)(*w), (ctypes.c_int32 * M)(*[int(c) for c in counts]),
+            _lib.ptr(self.buf), self.nbytes, _lib.stream_ptr()), "dh_energy_plan_build_objects")
 
     def workspace(self, C):
         if C not in self._ws:
@@ -100,27 +202,33 @@ class EnergyPlan:
         return self._ws[C]
 
 
-def energy_and_grad_planned(act, act_orig, plan, fg_weight, bg_weight, grad_scale=1.0, want_loss=False, out=None):
+def energy_and_grad_planned(act, act_orig, plan, fg_weight, bg_weight, grad_scale=1.0, want_loss=False, out=None,
+                            grad_dtype=None):
     """Default-configuration evaluation through a prebuilt EnergyPlan: act / act_orig [grid,grid,C] channels-last,
     16-bit, contiguous.  Returns (loss[3] or None, grad like act); `out`: where the gradient is written (e.g. the engine's
-    own cotangent buffer of that activation)."""
+    own cotangent buffer of that activation); grad_dtype: the gradient's dtype (default: the activation's).  A weighted plan
+    (EnergyPlan with object_weights) goes through dh_energy_fwd_bwd_planned_objects."""
     _lib.require_gpu(act)
     h, w, C = act.shape
     if h != plan.grid or w != plan.grid or act.dtype not in (torch.float16, torch.bfloat16) or act_orig.dtype != act.dtype:
         raise ValueError("planned energy: maps must be 16-bit [grid, grid, C] of one dtype")
     a = act.detach().contiguous()
     o = act_orig.detach().contiguous()
-    if out is not None and (out.shape != a.shape or out.dtype != a.dtype or not out.is_contiguous()):
+    gdt = a.dtype if grad_dtype is None else grad_dtype
+    if out is not None and (out.shape != a.shape or out.dtype != gdt or not out.is_contiguous()):
         raise ValueError("planned energy: `out` must be a contiguous tensor like the activation")
-    grad = torch.empty_like(a) if out is None else out
+    grad = torch.empty(a.shape, dtype=gdt, device=a.device) if out is None else out
     loss = torch.zeros(3, dtype=torch.float32, device=a.device) if want_loss else None
     ws, wsb = plan.workspace(C)
     dl = plan.dl
-    _lib.check(_lib.lib().dh_energy_fwd_bwd_planned(
+    L = _lib.lib()
+    entry = L.dh_energy_fwd_bwd_planned_objects if plan.weighted else L.dh_energy_fwd_bwd_planned
+    _lib.check(entry(
         _lib.ptr(a), _lib.ptr(o), _lib.DTYPE_CODE[a.dtype], C, plan.grid, _lib.ptr(plan.buf), plan.nbytes, plan.n_pairs,
         _lib.ptr(dl["bg_orig"]), dl["bg_orig"].numel(), _lib.ptr(dl["bg_trans"]), dl["bg_trans"].numel(),
         float(fg_weight), float(bg_weight), float(grad_scale), _lib.ptr(loss), _lib.ptr(grad),
-        _lib.DTYPE_CODE[a.dtype], _lib.ptr(ws), wsb, _lib.stream_ptr()), "dh_energy_fwd_bwd_planned")
+        _lib.DTYPE_CODE[grad.dtype], _lib.ptr(ws), wsb, _lib.stream_ptr()),
+        "dh_energy_fwd_bwd_planned_objects" if plan.weighted else "dh_energy_fwd_bwd_planned")
     return loss, grad
 
 
@@ -153,7 +261,8 @@ def energy_and_grad_planned_batch(acts, acts_orig, plans, fg_weights, bg_weights
     """energy_and_grad_planned for K <= 16 items in one launch pair (dh_energy_fwd_bwd_planned_batch): item e is (acts[e],
     acts_orig[e], plans[e], fg_weights[e], bg_weights[e], grad_scales[e]); the items share the map shape and dtype and
     nothing else (edits of one image or of different images).  Returns (loss [K,3] or None, [K gradients]); outs: where the
-    gradients are written.  Bit-identical per item to the single call.  More than 16 items raise (never split)."""
+    gradients are written.  Bit-identical per item to the single call.  More than 16 items raise (never split).  The plans are
+    all weighted (EnergyPlan with object_weights: dh_energy_fwd_bwd_planned_objects_batch) or all unweighted."""
     K = len(acts)
     if K < 1 or not (len(acts_orig) == len(plans) == len(fg_weights) == len(bg_weights) == len(grad_scales) == K):
         raise ValueError("planned energy batch: the per-item lists must be non-empty and of one length")
@@ -173,15 +282,19 @@ def energy_and_grad_planned_batch(acts, acts_orig, plans, fg_weights, bg_weights
             raise ValueError("planned energy batch: maps must be contiguous 16-bit [grid, grid, C] of one dtype and shape")
         if tuple(g.shape) != (h, w, C) or g.dtype != gdt or not g.is_contiguous():
             raise ValueError("planned energy batch: `outs` must be contiguous tensors like the activations")
+    weighted = plans[0].weighted
+    if any(p.weighted != weighted for p in plans):
+        raise ValueError("planned energy batch: weighted and unweighted plans do not go into one call")
     loss = torch.zeros((K, 3), dtype=torch.float32, device=acts[0].device) if want_loss else None
     items, ws, wsb = _batch_state(plans, C)
     for e, it in enumerate(items):
         it.cur, it.orig, it.grad = acts[e].data_ptr(), acts_orig[e].data_ptr(), outs[e].data_ptr()
         it.loss_out = loss[e].data_ptr() if want_loss else None
         it.fg_w, it.bg_w, it.grad_scale = float(fg_weights[e]), float(bg_weights[e]), float(grad_scales[e])
-    _lib.check(_lib.lib().dh_energy_fwd_bwd_planned_batch(items, K, _lib.DTYPE_CODE[dt], C, grid, _lib.DTYPE_CODE[gdt],
-                                                          _lib.ptr(ws), wsb, _lib.stream_ptr()),
-               "dh_energy_fwd_bwd_planned_batch")
+    L = _lib.lib()
+    entry = L.dh_energy_fwd_bwd_planned_objects_batch if weighted else L.dh_energy_fwd_bwd_planned_batch
+    _lib.check(entry(items, K, _lib.DTYPE_CODE[dt], C, grid, _lib.DTYPE_CODE[gdt], _lib.ptr(ws), wsb, _lib.stream_ptr()),
+               "dh_energy_fwd_bwd_planned_objects_batch" if weighted else "dh_energy_fwd_bwd_planned_batch")
     return loss, outs
 
 

@@ -204,6 +204,31 @@ int dh_energy_planned_batch_workspace_bytes(int C, int grid, int n_items, size_t
 int dh_energy_fwd_bwd_planned_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
                                     int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A weight per object for the foreground term of multi-object edits (extends dh_energy_plan_build /
+ * dh_energy_fwd_bwd_planned / dh_energy_fwd_bwd_planned_batch; same configuration, dtypes and workspaces).  With N_m pairs
+ * of object m and weights w_m >= 0, omega_m = w_m / (sum of w_j over the objects with N_j > 0) and
+ *     fg_term = sum_m omega_m * mean_c mean_{n in object m} | A_orig[c, o_n] - A_cur[c, t_n] |
+ * so the coefficient of a pair of object m is fg_w * omega_m / (C N_m) instead of fg_w / (C N).  The background term and the
+ * background lists are unchanged (the union's).  pair_obj: the 0-based object of every pair (device, one byte each);
+ * weights / counts: n_objects host values, counts[m] = N_m (they must add up to n_pairs).  Errors, before any launch:
+ * n_objects outside 1..8, a negative or non-finite weight, no positive weight among the objects that have pairs
+ * (n_pairs = 0 is allowed: no foreground term).  A plan built here is only valid for the two _objects evaluations below
+ * (it needs dh_energy_plan_objects_bytes); they take what their unweighted forms take, workspaces included
+ * (dh_energy_planned_workspace_bytes for the single call).  One launch pair, one writer per gradient element, a fixed
+ * summation order (objects ascending): bit-reproducible, and the batch is bit-identical per item to the single call. */
+int dh_energy_plan_objects_bytes(int grid, int n_pairs, size_t* bytes);
+int dh_energy_plan_build_objects(const int32_t* pairs, const uint8_t* pair_obj, int n_pairs, const int32_t* bg_trans,
+                                 int n_bg_trans, int grid, int n_objects, const float* weights, const int32_t* counts,
+                                 void* plan, size_t plan_bytes, void* stream);
+int dh_energy_fwd_bwd_planned_objects(const void* cur, const void* orig, int dtype, int C, int grid,
+                                      const void* plan, size_t plan_bytes, int n_pairs,
+                                      const int32_t* bg_orig, int n_bg_orig, const int32_t* bg_trans, int n_bg_trans,
+                                      float fg_w, float bg_w, float grad_scale, float* loss_out, void* grad,
+                                      int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
+int dh_energy_planned_objects_batch_workspace_bytes(int C, int grid, int n_items, size_t* bytes);
+int dh_energy_fwd_bwd_planned_objects_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
+                                            int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------
  * SD-2-depth U-Net engine (model/unet_2d_condition.py:809-1198 and the block files it
  * calls): forward with the three decoder activation captures, and the backward pass to the

@@ -2,11 +2,17 @@
 """Planned guidance-energy evaluation on the bench scene's real correspondences (run under rocprofv3 --kernel-trace).
 
 Prints one JSON line with what each kernel of an evaluation touches (bytes), so that tools/hbm_report.py can turn the
-kernel trace into achieved GB/s per kernel:  DH_RES=512|768, C = 320 and 640 (act2 and act1 of the SD-2-depth U-Net)."""
+kernel trace into achieved GB/s per kernel:  DH_RES=512|768, C = 320 and 640 (act2 and act1 of the SD-2-depth U-Net).
+
+DH_OBJECT_WEIGHTS=equal: instead, the weighted evaluation (a weight per object, dh_energy_fwd_bwd_planned_objects) next to the
+unweighted one on the same correspondences -- the OCCLUDING edit of the two-sphere scene of tests/multi_object_ref.py, C = 640 and
+1280 -- timed with device events over DH_CALLS evaluations (default 200), alternating the two in blocks; one JSON line, also
+written to profiles/object_weights/bench_energy_res<res>.json (DH_OUT: another directory)."""
 import json
 import os
 import sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import torch
 from diffusionhandles_amd import losses as LS
 from diffusionhandles_amd.depth_transform import transform_depth
@@ -15,6 +21,65 @@ from diffusionhandles_amd.synthetic import TRANSFORMS, make_scene
 dev = torch.device("cuda:0")
 res = int(os.environ.get("DH_RES", "512"))
 grid = res // 8
+
+
+def object_weights_bench(ow):
+    from diffusionhandles_amd.depth_transform import reproject_object_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    depth, bg_depth, masks = R.two_spheres(res)
+    depth, bg_depth, masks = depth.to(dev), bg_depth.to(dev), [m.to(dev) for m in masks]
+    tfs = [(tf[0], torch.tensor(tf[1]), torch.tensor(tf[2])) for tf in R.OCCLUDING]
+    (_, corr), = reproject_object_edits(depth, bg_depth, masks, GuidedStableDiffuser.get_depth_intrinsics(dev), [tfs])
+    pc = LS.process_correspondences(corr, res, 0, grid=grid, device=dev, object_labels=LS.object_label_image(masks))
+    plain, weighted = LS.EnergyPlan(pc, grid, dev), LS.EnergyPlan(pc, grid, dev, object_weights=ow)
+    assert weighted.weighted and not plain.weighted
+    G2 = grid * grid
+    tgt = torch.as_tensor(pc["transformed_y"]) * grid + torch.as_tensor(pc["transformed_x"])
+    src = torch.as_tensor(pc["original_y"]) * grid + torch.as_tensor(pc["original_x"])
+    obj = torch.as_tensor(pc["object"])
+    per_obj = [sorted(set(tgt[obj == m].tolist())) for m in range(len(weighted.counts))]
+    shared = set(per_obj[0]).intersection(*per_obj[1:])
+    info = dict(res=res, grid=grid, object_weights=ow, correspondences=int(corr.shape[0]), pairs_per_object=[int(c) for c in weighted.counts],
+                omega=[float(o) for o in weighted.omega], target_cells_per_object=[len(c) for c in per_obj], target_cells_shared=len(shared),
+                entries_unweighted=int(torch.unique(torch.stack([src, tgt], 1), dim=0).shape[0]),
+                entries_weighted=int(torch.unique(torch.stack([obj, src, tgt], 1), dim=0).shape[0]), layers=[])
+    n = int(os.environ.get("DH_CALLS", "200"))
+    gen = torch.Generator().manual_seed(1)
+    for C in (640, 1280):
+        cur = torch.randn(grid, grid, C, generator=gen).half().to(dev)
+        org = torch.randn(grid, grid, C, generator=gen).half().to(dev)
+        out = torch.empty_like(cur)
+        run = lambda p: LS.energy_and_grad_planned(cur, org, p, 3.0, 2.0, grad_scale=256.0, out=out)
+        for p in (plain, weighted):
+            for _ in range(20):
+                run(p)
+        torch.cuda.synchronize()
+        best = {"unweighted": [], "weighted": []}
+        for _ in range(5):                                   # alternating blocks of n calls
+            for name, p in (("unweighted", plain), ("weighted", weighted)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    run(p)
+                e1.record()
+                torch.cuda.synchronize()
+                best[name].append(e0.elapsed_time(e1) * 1e3 / n)
+        med = {k: sorted(v)[len(v) // 2] for k, v in best.items()}
+        info["layers"].append(dict(C=C, us_per_evaluation_median=med, us_per_evaluation_blocks=best,
+                                   weighted_over_unweighted=med["weighted"] / med["unweighted"]))
+    line = json.dumps(info)
+    out_dir = os.environ.get("DH_OUT") or os.path.join(ROOT, "profiles", "object_weights")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, f"bench_energy_res{res}.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if os.environ.get("DH_OBJECT_WEIGHTS"):
+    v = os.environ["DH_OBJECT_WEIGHTS"]
+    object_weights_bench(v if v == "equal" else [float(x) for x in v.split(",")])
+    sys.exit(0)
 depth, bg, mask = (t.to(dev) for t in make_scene(res))
 ang, tr = TRANSFORMS[2]
 _, corr = transform_depth(depth, bg, mask, GuidedStableDiffuser.get_depth_intrinsics(), rot_angle=ang,

@@ -82,6 +82,8 @@ SIGNATURES = {
                                                 c_p, c_p, c_i, c_p, c_sz, c_p]),
     "dh_energy_planned_objects_batch_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
     "dh_energy_fwd_bwd_planned_objects_batch": (c_i, [ctypes.POINTER(EnergyItem), c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "dh_energy_fwd_bwd_planned_mixed_batch": (c_i, [ctypes.POINTER(EnergyItem), ctypes.POINTER(ctypes.c_uint8), c_i, c_i, c_i, c_i, c_i,
+                                              c_p, c_sz, c_p]),
     "dh_unet_create": (c_i, [ctypes.POINTER(UNetConfig), ctypes.POINTER(c_p)]),
     "dh_unet_create_shared": (c_i, [c_p, c_i, c_p, ctypes.POINTER(c_p)]),
     "dh_unet_destroy": (None, [c_p]),

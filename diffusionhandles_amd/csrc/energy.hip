@@ -581,6 +581,31 @@ __global__ void __launch_bounds__(256) k_energy_grad_obj_batch(const EnergyBatch
 #include "energy_grad_obj_body.inc"
 }
 
+// K items, some weighted and some not, in one launch (dh_energy_fwd_bwd_planned_mixed_batch): ot.p[item] is the object block of
+// a weighted item's plan and null for an unweighted one, whose row carries coef_fg = fg_w / (C N) as in k_energy_grad_batch.  The
+// branch depends on blockIdx.y alone, so a workgroup is wholly in one arm and the barriers of block_sum are reached by all of
+// its threads; each arm is the text of its own kernel, in a scope of its own.
+template <class T, class TG>
+__global__ void __launch_bounds__(256) k_energy_grad_mixed_batch(const EnergyBatch tab, const EnergyObjPtrs ot, int C, int G2) {
+  const EnergyItem& it = tab.it[blockIdx.y];
+  const T *orig = (const T*)it.orig, *cur = (const T*)it.cur;
+  const int *off = it.off, *ucnt = it.ucnt, *src = it.src, *mult = it.mult;
+  const uint8_t* objp = ot.p[blockIdx.y];
+  const uint8_t* bgflag = it.bgflag;
+  const float* partq = it.partq;
+  const int n1 = it.n1, n2 = it.n2, use_bg = it.use_bg;
+  const float coef_bg = it.coef_bg, scale = it.scale;
+  TG* grad = (TG*)it.grad;
+  double *loss_part = it.loss_part, *bg_loss = it.bg_loss;
+  if (objp) {
+    const float fg_w = it.coef_fg;
+#include "energy_grad_obj_body.inc"
+  } else {
+    const float coef_fg = it.coef_fg;
+#include "energy_grad_body.inc"
+  }
+}
+
 }  // namespace dh
 
 using namespace dh;
@@ -1023,6 +1048,83 @@ extern "C" int dh_energy_fwd_bwd_planned_objects_batch(const dh_energy_item* ite
   if (dtype == DH_DTYPE_F16) DH_EGOB(f16);
   else DH_EGOB(bf16);
 #undef DH_EGOB
+  if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+// ---- weighted and unweighted items in one launch pair ------------------------------------------------------------------------
+extern "C" int dh_energy_fwd_bwd_planned_mixed_batch(const dh_energy_item* items, const uint8_t* weighted, int n_items, int dtype,
+                                                     int C, int grid, int grad_dtype, void* workspace, size_t workspace_bytes,
+                                                     void* stream) {
+  DH_REQUIRE(items && weighted && workspace, "null pointer");
+  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items (larger batches are not split)");
+  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
+  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
+  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1, "bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  const int G2 = grid * grid;
+  const int cpb = 256 / (C / 8);
+  const int nblocks = cdiv(G2, cpb);
+  Arena aw(workspace, workspace_bytes);
+  EnergyBatch tab;
+  EnergyObjPtrs ot;
+  bool any_bg = false, any_loss = false;
+  for (int e = 0; e < n_items; ++e) {
+    const dh_energy_item& in = items[e];
+    EnergyItem& it = tab.it[e];
+    DH_REQUIRE(in.cur && in.orig && in.grad && in.plan, "null pointer in an item");
+    DH_REQUIRE(in.n_pairs >= 0, "bad sizes");
+    Arena ap(const_cast<void*>(in.plan), in.plan_bytes);
+    EnergyPlanObj po;
+    if (weighted[e]) {
+      DH_REQUIRE(carve_plan_obj(ap, grid, in.n_pairs, po), "plan buffer too small for a weighted plan");
+      ot.p[e] = po.objp;
+    } else {
+      DH_REQUIRE(carve_plan(ap, grid, in.n_pairs, po.base), "plan buffer too small");
+      ot.p[e] = nullptr;
+    }
+    const EnergyPlan& p = po.base;
+    PlannedWs w;
+    DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
+    it.orig = in.orig; it.cur = in.cur;
+    it.off = p.off; it.ucnt = p.cnt; it.src = p.src; it.mult = p.mult; it.bgflag = p.bgflag;
+    it.list1 = in.bg_orig; it.list2 = in.bg_trans;
+    it.partq = w.partq; it.grad = in.grad; it.loss_part = w.fg_part; it.bg_loss = w.bg_part; it.loss_out = in.loss_out;
+    it.n1 = in.n_bg_orig; it.n2 = in.n_bg_trans;
+    // an item's row is the row of its own batched entry: the weighted kernel body forms fg_w * omega_m / (C N_m) itself
+    if (weighted[e]) it.fg_norm = in.n_pairs > 0 ? 1.f / (float)C : 0.f;
+    else it.fg_norm = in.n_pairs > 0 ? 1.f / ((float)C * (float)in.n_pairs) : 0.f;
+    it.bg_norm = 0.f; it.coef_bg = 0.f; it.use_bg = 0;
+    if (in.n_bg_orig > 0 && in.n_bg_trans > 0) {
+      DH_REQUIRE(in.bg_orig && in.bg_trans, "null bg list");
+      it.bg_norm = 1.f / (float)C;
+      it.coef_bg = in.bg_w * it.bg_norm / (float)in.n_bg_trans;
+      it.use_bg = 1;
+      any_bg = true;
+    }
+    it.coef_fg = weighted[e] ? in.fg_w : in.fg_w * it.fg_norm;
+    it.scale = in.grad_scale;
+    it.n_fg_part = in.n_pairs > 0 ? nblocks : 0;
+    it.fg_w = in.fg_w; it.bg_w = in.bg_w;
+    any_loss = any_loss || in.loss_out != nullptr;
+  }
+  for (int e = n_items; e < ENERGY_MAX_ITEMS; ++e) { tab.it[e] = tab.it[0]; ot.p[e] = ot.p[0]; }      // (never indexed)
+  if (any_bg) {
+    if (dtype == DH_DTYPE_F16)
+      hipLaunchKernelGGL((k_colsum_q_batch<f16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
+    else
+      hipLaunchKernelGGL((k_colsum_q_batch<bf16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
+  }
+#define DH_EGMB(T_)                                                                                                            \
+  do {                                                                                                                         \
+    if (grad_dtype == DH_DTYPE_F16) hipLaunchKernelGGL((k_energy_grad_mixed_batch<T_, f16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2);        \
+    else if (grad_dtype == DH_DTYPE_BF16) hipLaunchKernelGGL((k_energy_grad_mixed_batch<T_, bf16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2); \
+    else hipLaunchKernelGGL((k_energy_grad_mixed_batch<T_, float>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2); \
+  } while (0)
+  if (dtype == DH_DTYPE_F16) DH_EGMB(f16);
+  else DH_EGMB(bf16);
+#undef DH_EGMB
   if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
   DH_LAUNCH_CHECK();
   return DH_OK;

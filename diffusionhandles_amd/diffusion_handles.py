@@ -148,35 +148,77 @@ class DiffusionHandles:
 
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                           object_weights=None):
+                                           object_weights=None, streams=1, batch=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
         edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]).  Returns (images [K,3,H,W], [K disparities]) as
-        transform_foreground_batch does on one stream.  object_weights: as in transform_foreground_objects, one list for all
-        K edits."""
+        transform_foreground_batch does.  object_weights: as in transform_foreground_objects, one list for all K edits.
+        streams / batch: transform_foreground_batch's -- chunks of `batch` edits (default ceil(K / streams)) on `streams`
+        lanes, batch = 1 runs single edits on the lanes; images are bit-identical to the one-stream result at the same batch."""
         labels, object_weights = self._object_labels(fg_masks, object_weights)
+        K = len(edits)
         with torch.no_grad():
             res = self._reproject_objects("transform_foreground_objects_batch", depth, bg_depth, fg_masks, edits,
                                           use_input_depth_normalization, True)
-            imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
-                                                        [c for _, c in res], fg_weight, bg_weight, object_labels=labels,
-                                                        object_weights=object_weights)
+            per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
+            obj = dict(object_labels=labels, object_weights=object_weights)
+            if streams <= 1 and per >= K:
+                imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
+                                                            [c for _, c in res], fg_weight, bg_weight, **obj)
+            elif per <= 1:
+                imgs = torch.cat(self.diffuser.guided_inference_lanes(init_noise, res, null_text_emb, prompt, activations,
+                                                                      max(1, int(streams)), fg_weight, bg_weight, **obj))
+            else:
+                chunks = [([d for d, _ in res[i:i + per]], [c for _, c in res[i:i + per]]) for i in range(0, K, per)]
+                imgs = torch.cat(self.diffuser.guided_inference_batch_lanes(init_noise, chunks, null_text_emb, prompt,
+                                                                            activations, max(1, int(streams)), fg_weight,
+                                                                            bg_weight, **obj))
         return imgs, [d for d, _ in res]
 
     EDIT_FIELDS = ("depth", "prompt", "fg_mask", "bg_depth", "null_text_emb", "init_noise", "activations")
 
     def transform_foregrounds(self, edits, use_input_depth_normalization=False):
         """K edits of DIFFERENT images in batched passes (not in the reference).  edits: K dicts with the arguments of
-        transform_foreground (EDIT_FIELDS, rot_angle / rot_axis / translation, optional fg_weight / bg_weight).  Edits that name
-        the same image (the same depth, mask, background-depth and activation tensors) are re-projected together, once per
-        image; then one GuidedStableDiffuser.guided_inference_items.  Returns (images [K,3,H,W], [K disparities]) in input
-        order.  'pc' re-projection only; one resolution; needs an engine with max_batch >= 2K."""
+        transform_foreground (EDIT_FIELDS, rot_angle / rot_axis / translation, optional fg_weight / bg_weight) -- or, for an
+        edit that moves several objects (transform_foreground_objects), `fg_masks` (M masks) in place of fg_mask, `transforms`
+        (M triples (rot_angle, rot_axis, translation), None members defaulted) in place of rot_angle / rot_axis / translation,
+        and optionally `object_weights`.  An edit with both forms or with neither, or with a `transforms` list that is not M
+        long, raises ValueError naming the edit, before any device work.  Edits that name the same image (the same depth, mask,
+        background-depth and activation tensors) are re-projected together, once per image (multi-object edits: one label
+        image per image); then one GuidedStableDiffuser.guided_inference_items for single- and multi-object edits alike.
+        Returns (images [K,3,H,W], [K disparities]) in input order.  'pc' re-projection only; one resolution; needs an engine
+        with max_batch >= 2K."""
         from .depth_transform import reproject_edits
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
                                       "batched re-projection (only 'pc')")
         K = len(edits)
-        if K < 1 or any(set(self.EDIT_FIELDS) - set(e) for e in edits):
+        common = tuple(f for f in self.EDIT_FIELDS if f != "fg_mask")
+        if K < 1 or any(set(common) - set(e) for e in edits):
             raise ValueError(f"transform_foregrounds: needs at least one edit, each with {self.EDIT_FIELDS}")
+        single_keys = ("fg_mask", "rot_angle", "rot_axis", "translation")
+        multi_keys = ("fg_masks", "transforms", "object_weights")
+        weights = [None] * K
+        for i, e in enumerate(edits):
+            single = any(e.get(k) is not None for k in single_keys)
+            multi = any(e.get(k) is not None for k in multi_keys)
+            if single and multi:
+                raise ValueError(f"transform_foregrounds: edit {i} mixes the one-object form {single_keys} with the multi-object "
+                                 f"form {multi_keys}")
+            if e.get("fg_mask") is None and e.get("fg_masks") is None:
+                raise ValueError(f"transform_foregrounds: edit {i} has neither fg_mask nor fg_masks")
+            if multi:
+                masks, tfs = e.get("fg_masks"), e.get("transforms")
+                if not isinstance(masks, (list, tuple)) or len(masks) < 1:
+                    raise ValueError(f"transform_foregrounds: edit {i}: fg_masks must be a non-empty list of masks")
+                if tfs is None or len(tfs) != len(masks):
+                    raise ValueError(f"transform_foregrounds: edit {i} has {0 if tfs is None else len(tfs)} transforms for "
+                                     f"{len(masks)} masks")
+                if e.get("object_weights") is not None:
+                    from .losses import check_object_weights
+                    try:
+                        weights[i] = check_object_weights(e["object_weights"], len(masks))
+                    except ValueError as err:
+                        raise ValueError(f"transform_foregrounds: edit {i}: {err}") from None
         for i, e in enumerate(edits):
             if tuple(e["depth"].shape[-2:]) != tuple(edits[0]["depth"].shape[-2:]):
                 raise ValueError(f"transform_foregrounds: edit {i} has another resolution than edit 0 "
@@ -187,23 +229,34 @@ class DiffusionHandles:
                                f"build the diffuser with max_batch >= {2 * K}")
         Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
         dflt = lambda v, d: d if v is None else v
-        groups = {}                  # image -> indices of its edits, in input order
+        groups = {}                  # image (and its mask tensors) -> indices of its edits, in input order
         for i, e in enumerate(edits):
-            key = (id(e["depth"]), id(e["fg_mask"]), id(e["bg_depth"])) + tuple(id(a) for a in e["activations"])
+            masks = tuple(id(m) for m in e["fg_masks"]) if e.get("fg_masks") is not None else (id(e["fg_mask"]),)
+            key = (id(e["depth"]), e.get("fg_masks") is not None) + masks + (id(e["bg_depth"]),) + tuple(id(a) for a in e["activations"])
             groups.setdefault(key, []).append(i)
-        reproj = [None] * K
+        reproj, labels = [None] * K, [None] * K
         with torch.no_grad():
             for idx in groups.values():
                 e0 = edits[idx[0]]
-                tfs = [(dflt(edits[i].get("rot_angle"), 0.0), dflt(edits[i].get("rot_axis"), Y),
-                        dflt(edits[i].get("translation"), torch.zeros(3))) for i in idx]
-                res = reproject_edits(e0["depth"], e0["bg_depth"], e0["fg_mask"],
-                                      self.diffuser.get_depth_intrinsics(device=e0["depth"].device), tfs,
-                                      use_input_depth_normalization, device_correspondences=True)
+                if e0.get("fg_masks") is not None:
+                    res = self._reproject_objects("transform_foregrounds", e0["depth"], e0["bg_depth"], list(e0["fg_masks"]),
+                                                  [list(edits[i]["transforms"]) for i in idx], use_input_depth_normalization, True)
+                    if any(weights[i] is not None for i in idx):
+                        from .losses import object_label_image
+                        label = object_label_image(list(e0["fg_masks"]))          # once per group
+                        for i in idx:
+                            labels[i] = label if weights[i] is not None else None
+                else:
+                    tfs = [(dflt(edits[i].get("rot_angle"), 0.0), dflt(edits[i].get("rot_axis"), Y),
+                            dflt(edits[i].get("translation"), torch.zeros(3))) for i in idx]
+                    res = reproject_edits(e0["depth"], e0["bg_depth"], e0["fg_mask"],
+                                          self.diffuser.get_depth_intrinsics(device=e0["depth"].device), tfs,
+                                          use_input_depth_normalization, device_correspondences=True)
                 for i, r in zip(idx, res):
                     reproj[i] = r
             items = [dict(latents=e["init_noise"], depth=d, uncond_embeddings=e["null_text_emb"], prompt=e["prompt"],
-                          activations_orig=e["activations"], correspondences=c) for e, (d, c) in zip(edits, reproj)]
+                          activations_orig=e["activations"], correspondences=c, object_labels=labels[i], object_weights=weights[i])
+                     for i, (e, (d, c)) in enumerate(zip(edits, reproj))]
             imgs = self.diffuser.guided_inference_items(items, [e.get("fg_weight") for e in edits],
                                                         [e.get("bg_weight") for e in edits])
         return imgs, [d for d, _ in reproj]

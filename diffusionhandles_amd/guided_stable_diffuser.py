@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from . import guidance_scale as _gs
+from . import losses as _losses
 from .guided_diffuser import GuidedDiffuser
 from .losses import (MAX_BATCH_ITEMS, EnergyPlan, check_object_weights as _check_object_weights, energy_and_grad,
                      energy_and_grad_planned, energy_and_grad_planned_batch, process_correspondences as _process_correspondences)
@@ -598,14 +599,15 @@ class GuidedStableDiffuser(GuidedDiffuser):
         S = [float(st.scale_host[t_idx, iteration]) if auto else self.grad_scale for st in sts]
         g = acts_k.shape[1]
         planned = [e for e, st in enumerate(sts) if st.plan is not None and g == st.plan.grid and acts_k.shape[2] == g]
-        if len({sts[e].plan.weighted for e in planned}) > 1:
-            planned = []          # weighted and unweighted plans do not share a launch: such a batch goes item by item
         if not (self._batch_energy and 2 <= len(planned) <= MAX_BATCH_ITEMS):
             planned = []
         if planned:
-            energy_and_grad_planned_batch([acts_k[e] for e in planned], [sts[e].orig[k][t_idx] for e in planned],
-                                          [sts[e].plan for e in planned], [fw[e] for e in planned], [bw[e] for e in planned],
-                                          [S[e] for e in planned], outs=[out[e] for e in planned])
+            # weighted and unweighted plans together: the mixed entry, still one launch pair; a set of one kind keeps its entry
+            mixed = len({sts[e].plan.weighted for e in planned}) > 1
+            entry = _losses.energy_and_grad_planned_mixed if mixed else energy_and_grad_planned_batch
+            entry([acts_k[e] for e in planned], [sts[e].orig[k][t_idx] for e in planned],
+                  [sts[e].plan for e in planned], [fw[e] for e in planned], [bw[e] for e in planned],
+                  [S[e] for e in planned], outs=[out[e] for e in planned])
         for e, st in enumerate(sts):
             if e not in planned:
                 self._energy_grad(st, k, acts_k[e], t_idx, fw[e], bw[e], out=out[e], scale=S[e])
@@ -724,7 +726,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference_items(self, items, fg_weight=None, bg_weight=None):
         """K edits of DIFFERENT images at once.  items: K records (dicts with the keys ITEM_FIELDS, or tuples in that order), the
-        arguments of guided_inference per item; fg_weight / bg_weight: one value or K.  Items with the same activations_orig
+        arguments of guided_inference per item, plus optional object_labels / object_weights (prepare_guidance: a multi-object
+        edit with a weight per object); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
         tensors share one channels-last copy of them, items with the same prompt one encoding.  One resolution (the
         engine's); needs max_batch >= 2K and max_diff_batch >= K, raises otherwise (never splits).  Returns images [K,3,H,W]
         in item order and sets last_latents; 'auto' grad_scale: FloatingPointError naming the items that met a non-finite
@@ -753,7 +756,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
             for i, it in enumerate(items):
                 okey = tuple(id(a) for a in it["activations_orig"])
                 st = self.prepare_guidance(it["depth"], it["prompt"], it["activations_orig"], it["correspondences"],
-                                           per(fg_weight, i), per(bg_weight, i), orig=origs.get(okey), cond=conds.get(it["prompt"]))
+                                           per(fg_weight, i), per(bg_weight, i), orig=origs.get(okey), cond=conds.get(it["prompt"]),
+                                           object_labels=it.get("object_labels"), object_weights=it.get("object_weights"))
                 origs[okey], conds[it["prompt"]] = st.orig, st.cond
                 sts.append(st)
             x = torch.cat([_nhwc(it["latents"].to(self.device, torch.float32)) for it in items]).contiguous()
@@ -858,11 +862,12 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return results
 
     def guided_inference_batch_lanes(self, latents, chunks, uncond_embeddings, prompt, activations_orig, streams=2,
-                                     fg_weight=None, bg_weight=None):
+                                     fg_weight=None, bg_weight=None, object_labels=None, object_weights=None):
         """Batched edits of one image on `streams` concurrent lanes.  chunks: list of (depths, correspondences_list), each the
         argument pair of one guided_inference_batch call; chunk i runs on lane i % streams.  Every lane executes exactly the
         passes the one-stream call executes for its chunk (same batch, same kernels, private arenas), so the images are
-        bit-identical to guided_inference_batch chunk by chunk.  Returns one image tensor [K_i,3,H,W] per chunk."""
+        bit-identical to guided_inference_batch chunk by chunk.  Returns one image tensor [K_i,3,H,W] per chunk.
+        object_labels / object_weights: one label image and one weight list for every edit (prepare_guidance)."""
         kmax = max(len(d) for d, _ in chunks)
         if self.unet.max_batch < 2 * kmax:
             # lane 0 is THIS diffuser: it could not run its chunk, and forks sized 2 * kmax would be made for nothing
@@ -878,7 +883,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
                     def body():
                         lat = yield from lane._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig,
                                                                 corrs, fg_weight, bg_weight, cond=cond, orig=orig,
-                                                                status_out=status)
+                                                                status_out=status, object_labels=object_labels,
+                                                                object_weights=object_weights)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
@@ -890,13 +896,14 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return images
 
     def _edit_steps(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences, fg_weight=None,
-                    bg_weight=None, cond=None, orig=None, status_out=None):
+                    bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None, object_weights=None):
         """One edit as a generator (see _batch_edit_steps): yields after the preparation and after every denoising step,
         returns the final latents [1,4,H,W]."""
         torch.manual_seed(self.conf.seed)
         self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
         timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
-        st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight, orig=orig, cond=cond)
+        st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight, orig=orig, cond=cond,
+                                   object_labels=object_labels, object_weights=object_weights)
         x = _nhwc(latents.to(self.device, torch.float32))
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -907,10 +914,11 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_lanes(self, latents, edits, uncond_embeddings, prompt, activations_orig, streams=2, fg_weight=None,
-                               bg_weight=None):
+                               bg_weight=None, object_labels=None, object_weights=None):
         """Single (B = 1) edits of one image on `streams` concurrent lanes.  edits: list of (depth, correspondences), the
         argument pair of guided_inference; edit i runs on lane i % streams with exactly the passes guided_inference runs, so
-        the images are bit-identical to the one-stream calls.  Returns a list of images [1,3,H,W]."""
+        the images are bit-identical to the one-stream calls.  Returns a list of images [1,3,H,W].  object_labels /
+        object_weights: one label image and one weight list for every edit (prepare_guidance)."""
         lanes = self.lanes(min(int(streams), len(edits)))
         statuses = [[] for _ in edits]
         with torch.no_grad(), self.on_stream():
@@ -921,7 +929,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 def job(lane):
                     def body():
                         lat = yield from lane._edit_steps(latents, depth, uncond_embeddings, prompt, activations_orig, corr,
-                                                          fg_weight, bg_weight, cond=cond, orig=orig, status_out=status)
+                                                          fg_weight, bg_weight, cond=cond, orig=orig, status_out=status,
+                                                          object_labels=object_labels, object_weights=object_weights)
                         return lane._decode_serialized(lat)
                     return body()
                 return job

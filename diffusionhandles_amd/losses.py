@@ -256,13 +256,9 @@ def _batch_state(plans, C):
     return cache[key][:3]
 
 
-def energy_and_grad_planned_batch(acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss=False, outs=None,
-                                  grad_dtype=None):
-    """energy_and_grad_planned for K <= 16 items in one launch pair (dh_energy_fwd_bwd_planned_batch): item e is (acts[e],
-    acts_orig[e], plans[e], fg_weights[e], bg_weights[e], grad_scales[e]); the items share the map shape and dtype and
-    nothing else (edits of one image or of different images).  Returns (loss [K,3] or None, [K gradients]); outs: where the
-    gradients are written.  Bit-identical per item to the single call.  More than 16 items raise (never split).  The plans are
-    all weighted (EnergyPlan with object_weights: dh_energy_fwd_bwd_planned_objects_batch) or all unweighted."""
+def _planned_batch_call(entry_name, flags, acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss, outs, grad_dtype):
+    """The argument checks and the item table of the batched planned entries, then the call: `entry_name` with the per-item
+    flags of the mixed entry (flags = True) or without them."""
     K = len(acts)
     if K < 1 or not (len(acts_orig) == len(plans) == len(fg_weights) == len(bg_weights) == len(grad_scales) == K):
         raise ValueError("planned energy batch: the per-item lists must be non-empty and of one length")
@@ -282,20 +278,41 @@ def energy_and_grad_planned_batch(acts, acts_orig, plans, fg_weights, bg_weights
             raise ValueError("planned energy batch: maps must be contiguous 16-bit [grid, grid, C] of one dtype and shape")
         if tuple(g.shape) != (h, w, C) or g.dtype != gdt or not g.is_contiguous():
             raise ValueError("planned energy batch: `outs` must be contiguous tensors like the activations")
-    weighted = plans[0].weighted
-    if any(p.weighted != weighted for p in plans):
-        raise ValueError("planned energy batch: weighted and unweighted plans do not go into one call")
     loss = torch.zeros((K, 3), dtype=torch.float32, device=acts[0].device) if want_loss else None
     items, ws, wsb = _batch_state(plans, C)
     for e, it in enumerate(items):
         it.cur, it.orig, it.grad = acts[e].data_ptr(), acts_orig[e].data_ptr(), outs[e].data_ptr()
         it.loss_out = loss[e].data_ptr() if want_loss else None
         it.fg_w, it.bg_w, it.grad_scale = float(fg_weights[e]), float(bg_weights[e]), float(grad_scales[e])
-    L = _lib.lib()
-    entry = L.dh_energy_fwd_bwd_planned_objects_batch if weighted else L.dh_energy_fwd_bwd_planned_batch
-    _lib.check(entry(items, K, _lib.DTYPE_CODE[dt], C, grid, _lib.DTYPE_CODE[gdt], _lib.ptr(ws), wsb, _lib.stream_ptr()),
-               "dh_energy_fwd_bwd_planned_objects_batch" if weighted else "dh_energy_fwd_bwd_planned_batch")
+    # the flags are host bytes: the entry reads them while it fills the kernels' by-value tables, no kernel does
+    head = (items, (ctypes.c_uint8 * K)(*[1 if p.weighted else 0 for p in plans])) if flags else (items,)
+    _lib.check(getattr(_lib.lib(), entry_name)(*head, K, _lib.DTYPE_CODE[dt], C, grid, _lib.DTYPE_CODE[gdt], _lib.ptr(ws), wsb,
+                                               _lib.stream_ptr()), entry_name)
     return loss, outs
+
+
+def energy_and_grad_planned_batch(acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss=False, outs=None,
+                                  grad_dtype=None):
+    """energy_and_grad_planned for K <= 16 items in one launch pair (dh_energy_fwd_bwd_planned_batch): item e is (acts[e],
+    acts_orig[e], plans[e], fg_weights[e], bg_weights[e], grad_scales[e]); the items share the map shape and dtype and
+    nothing else (edits of one image or of different images).  Returns (loss [K,3] or None, [K gradients]); outs: where the
+    gradients are written.  Bit-identical per item to the single call.  More than 16 items raise (never split).  The plans are
+    all weighted (EnergyPlan with object_weights: dh_energy_fwd_bwd_planned_objects_batch) or all unweighted; a mix goes to
+    energy_and_grad_planned_mixed."""
+    if any(p.weighted != plans[0].weighted for p in plans):
+        raise ValueError("planned energy batch: weighted and unweighted plans do not go into one call")
+    entry = "dh_energy_fwd_bwd_planned_objects_batch" if plans and plans[0].weighted else "dh_energy_fwd_bwd_planned_batch"
+    return _planned_batch_call(entry, False, acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss, outs, grad_dtype)
+
+
+def energy_and_grad_planned_mixed(acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss=False, outs=None,
+                                  grad_dtype=None):
+    """energy_and_grad_planned_batch for ANY mix of weighted and unweighted plans in one launch pair
+    (dh_energy_fwd_bwd_planned_mixed_batch); same arguments and return value.  Item e is bit-identical to
+    energy_and_grad_planned on it alone, whichever kind its plan is; all-weighted and all-unweighted batches are accepted too
+    (and equal energy_and_grad_planned_batch)."""
+    return _planned_batch_call("dh_energy_fwd_bwd_planned_mixed_batch", True, acts, acts_orig, plans, fg_weights, bg_weights,
+                               grad_scales, want_loss, outs, grad_dtype)
 
 
 def energy_and_grad(act, act_orig, processed_correspondences, fg_weight, bg_weight, fg_patch_size=1,

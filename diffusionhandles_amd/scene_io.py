@@ -432,18 +432,61 @@ def load_image(path):
     return torch.from_numpy(a.astype(np.float32) / scale).permute(2, 0, 1).contiguous()
 
 
+MAX_SCENE_OBJECTS = 8          # losses.MAX_OBJECTS
+
+
+def _check_object_entries(scene_dir, transforms, n_masks):
+    """transforms.json against the scene's masks: a multi-mask scene (n_masks >= 1 mask_m.png files) wants {"objects": [n_masks
+    entries]} everywhere, a single-mask scene (n_masks = 0) no "objects" at all.  ValueError naming the scene and the entry."""
+    for name, t in transforms.items():
+        has = isinstance(t, dict) and "objects" in t
+        if n_masks == 0:
+            if has:
+                raise ValueError(f"{scene_dir}: transform {name!r} has \"objects\" but the scene has one mask (mask.png, no mask_0.png)")
+            continue
+        if not has:
+            raise ValueError(f"{scene_dir}: transform {name!r} has no \"objects\" list but the scene has {n_masks} object masks "
+                             "(mask_0.png ...)")
+        if not isinstance(t["objects"], (list, tuple)) or len(t["objects"]) != n_masks:
+            n = len(t["objects"]) if isinstance(t["objects"], (list, tuple)) else "no"
+            raise ValueError(f"{scene_dir}: transform {name!r} lists {n} objects, the scene has {n_masks} object masks")
+
+
 def load_scene_geometry(scene_dir, img_res=512):
     """The geometric inputs of a scene only -- what `transform_depth` needs (test/test_diffusion_handles.py:213-215, 247-261):
     dict(transforms, fg_mask [1,1,R,R] in {0,1}, depth [1,1,R,R], bg_depth [1,1,R,R]).  Needs transforms.json, mask.png,
-    depth.exr / .npy, bg_depth.exr / .npy; no image, no prompt."""
+    depth.exr / .npy, bg_depth.exr / .npy; no image, no prompt.
+    A scene with a mask_0.png is a multi-object scene (not in the reference): its masks are mask_0.png .. mask_{M-1}.png
+    (consecutive, 1 <= M <= 8, each read like mask.png; a mask.png beside them is not read), bg_depth is the depth with all of
+    them removed, and every transforms.json entry is {"objects": [M ordinary entries], "object_weights": "equal" | [M floats]
+    (optional)} (object_transform_args).  The dict then also has fg_masks, the list of the M masks, and fg_mask is their union."""
     import torch
     j = os.path.join
     with open(j(scene_dir, "transforms.json")) as f:
         transforms = json.load(f, object_pairs_hook=OrderedDict)
-    mask = load_image(j(scene_dir, "mask.png"))[None]
-    if mask.shape[1] > 1:
-        mask = mask.mean(dim=1, keepdim=True)
-    mask = (crop_and_resize(mask, img_res) > 0.5).to(torch.float32)
+
+    def mask_of(name):
+        mask = load_image(j(scene_dir, name))[None]
+        if mask.shape[1] > 1:
+            mask = mask.mean(dim=1, keepdim=True)
+        return (crop_and_resize(mask, img_res) > 0.5).to(torch.float32)
+
+    masks = None
+    if os.path.exists(j(scene_dir, "mask_0.png")):
+        M = 1
+        while os.path.exists(j(scene_dir, f"mask_{M}.png")):
+            M += 1
+        if M > MAX_SCENE_OBJECTS:
+            raise ValueError(f"{scene_dir}: {M} object masks, at most {MAX_SCENE_OBJECTS} are supported")
+        _check_object_entries(scene_dir, transforms, M)
+        masks = [mask_of(f"mask_{m}.png") for m in range(M)]
+        union = masks[0] != 0
+        for m in masks[1:]:
+            union = union | (m != 0)
+        mask = union.to(torch.float32)
+    else:
+        _check_object_entries(scene_dir, transforms, 0)
+        mask = mask_of("mask.png")
 
     def depth_of(stem):
         if os.path.exists(j(scene_dir, stem + ".exr")):
@@ -454,12 +497,16 @@ def load_scene_geometry(scene_dir, img_res=512):
             raise FileNotFoundError(j(scene_dir, stem + ".exr"))
         return crop_and_resize(torch.from_numpy(np.ascontiguousarray(d))[None, None], img_res).to(torch.float32)
 
-    return dict(transforms=transforms, fg_mask=mask, depth=depth_of("depth"), bg_depth=depth_of("bg_depth"))
+    geo = dict(transforms=transforms, fg_mask=mask, depth=depth_of("depth"), bg_depth=depth_of("bg_depth"))
+    if masks is not None:
+        geo["fg_masks"] = masks
+    return geo
 
 
 def load_scene(scene_dir, img_res=512):
     """`load_diffhandles_inputs` (test/test_diffusion_handles.py:208-263) -> dict(transforms, prompt, img [1,3,R,R],
-    fg_mask [1,1,R,R] in {0,1}, depth [1,1,R,R], bg_depth [1,1,R,R])."""
+    fg_mask [1,1,R,R] in {0,1}, depth [1,1,R,R], bg_depth [1,1,R,R]); a multi-object scene also has fg_masks
+    (load_scene_geometry)."""
     j = os.path.join
     with open(j(scene_dir, "prompt.txt")) as f:
         lines = [ln for ln in f.read().splitlines() if len(ln) > 0]
@@ -468,8 +515,11 @@ def load_scene(scene_dir, img_res=512):
     img = load_image(j(scene_dir, "input.png"))[None]
     img = crop_and_resize(img[:, :3], img_res)
     geo = load_scene_geometry(scene_dir, img_res)
-    return dict(transforms=geo["transforms"], prompt=lines[0], img=img, fg_mask=geo["fg_mask"], depth=geo["depth"],
-                bg_depth=geo["bg_depth"])
+    sc = dict(transforms=geo["transforms"], prompt=lines[0], img=img, fg_mask=geo["fg_mask"], depth=geo["depth"],
+              bg_depth=geo["bg_depth"])
+    if "fg_masks" in geo:          # a multi-object scene (load_scene_geometry)
+        sc["fg_masks"] = geo["fg_masks"]
+    return sc
 
 
 def transform_args(t):
@@ -478,3 +528,19 @@ def transform_args(t):
     return dict(rot_angle=float(t.get("rotation_angle", 0.0)),
                 rot_axis=torch.tensor(t.get("rotation_axis", [0.0, 1.0, 0.0]), dtype=torch.float32),
                 translation=torch.tensor(t.get("translation", [0.0, 0.0, 0.0]), dtype=torch.float32))
+
+
+def object_transform_args(entry):
+    """One transforms.json entry of a multi-object scene, {"objects": [t_0 .. t_{M-1}], "object_weights": "equal" | [w ..]} ->
+    the `transforms` / `object_weights` keyword arguments of `transform_foreground_objects`: M (rot_angle, rot_axis,
+    translation) triples in mask order (`{}` leaves an object in place) and None, "equal" or a list of floats."""
+    if not isinstance(entry, dict) or "objects" not in entry:
+        raise ValueError("object_transform_args: the entry has no \"objects\" list")
+    triples = []
+    for t in entry["objects"]:
+        a = transform_args(t)
+        triples.append((a["rot_angle"], a["rot_axis"], a["translation"]))
+    w = entry.get("object_weights")
+    if w is not None and not isinstance(w, str):
+        w = [float(v) for v in w]
+    return dict(transforms=triples, object_weights=w)

@@ -229,6 +229,18 @@ int dh_energy_planned_objects_batch_workspace_bytes(int C, int grid, int n_items
 int dh_energy_fwd_bwd_planned_objects_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
                                             int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* K <= 16 items of which some carry a weighted plan (dh_energy_plan_build_objects) and some a plain one
+ * (dh_energy_plan_build), in ONE launch pair: the column-sum and loss launches of dh_energy_fwd_bwd_planned_batch and one
+ * gradient launch whose workgroups take the weighted or the unweighted arithmetic by their item.  weighted: n_items host
+ * bytes, non-zero where item e's plan buffer is a weighted plan; read on the host only (the kernels receive one object-block
+ * pointer per item by value, null for an unweighted item): no device allocation, copy or synchronisation.  The workspace is
+ * dh_energy_planned_batch_workspace_bytes'.  Item e's gradient and loss values are bit-identical to
+ * dh_energy_fwd_bwd_planned_objects' (weighted) or dh_energy_fwd_bwd_planned's (unweighted) on the same inputs; any mix is
+ * allowed, all of one kind included.  Errors, before any launch: K outside 1..16 (never split), a plan buffer smaller than
+ * its kind needs (so a weighted flag on a plain plan's buffer is refused). */
+int dh_energy_fwd_bwd_planned_mixed_batch(const dh_energy_item* items, const uint8_t* weighted, int n_items, int dtype, int C,
+                                          int grid, int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------
  * SD-2-depth U-Net engine (model/unet_2d_condition.py:809-1198 and the block files it
  * calls): forward with the three decoder activation captures, and the backward pass to the

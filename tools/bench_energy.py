@@ -7,7 +7,13 @@ kernel trace into achieved GB/s per kernel:  DH_RES=512|768, C = 320 and 640 (ac
 DH_OBJECT_WEIGHTS=equal: instead, the weighted evaluation (a weight per object, dh_energy_fwd_bwd_planned_objects) next to the
 unweighted one on the same correspondences -- the OCCLUDING edit of the two-sphere scene of tests/multi_object_ref.py, C = 640 and
 1280 -- timed with device events over DH_CALLS evaluations (default 200), alternating the two in blocks; one JSON line, also
-written to profiles/object_weights/bench_energy_res<res>.json (DH_OUT: another directory)."""
+written to profiles/object_weights/bench_energy_res<res>.json (DH_OUT: another directory).
+
+DH_MIXED=1: instead, a batch of K = 8 items of which 4 carry a weighted plan and 4 a plain one (the OCCLUDING edit and a second
+edit of the two-sphere scene, interleaved), C = 320, 640 and 1280, three ways: the one launch pair of
+dh_energy_fwd_bwd_planned_mixed_batch, the item-by-item route (8 single calls) and the all-unweighted batch of 8
+(dh_energy_fwd_bwd_planned_batch) -- same timing scheme; one JSON line, also written to
+profiles/mixed_objects/bench_energy_res<res>.json (DH_OUT: another directory)."""
 import json
 import os
 import sys
@@ -76,6 +82,70 @@ def object_weights_bench(ow):
     print(line)
 
 
+def mixed_bench():
+    from diffusionhandles_amd.depth_transform import reproject_object_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    K = 8
+    depth, bg_depth, masks = R.two_spheres(res)
+    depth, bg_depth, masks = depth.to(dev), bg_depth.to(dev), [m.to(dev) for m in masks]
+    apart = [(10.0, R.Y, (-0.1, 0.0, 0.0)), (-30.0, R.Y, (0.15, 0.0, 0.0))]
+    edits = [[(tf[0], torch.tensor(tf[1]), torch.tensor(tf[2])) for tf in e] for e in (R.OCCLUDING, apart)]
+    rp = reproject_object_edits(depth, bg_depth, masks, GuidedStableDiffuser.get_depth_intrinsics(dev), edits)
+    labels = LS.object_label_image(masks)
+    pcs = [LS.process_correspondences(corr, res, 0, grid=grid, device=dev, object_labels=labels) for _, corr in rp]
+    # item e: edit e % 2 (per pair of items), weighted where e is even -- weighted and unweighted interleaved
+    mixed = [LS.EnergyPlan(pcs[(e // 2) % 2], grid, dev, object_weights="equal" if e % 2 == 0 else None) for e in range(K)]
+    plain = [LS.EnergyPlan(pcs[(e // 2) % 2], grid, dev) for e in range(K)]
+    assert [p.weighted for p in mixed] == [e % 2 == 0 for e in range(K)] and not any(p.weighted for p in plain)
+    info = dict(res=res, grid=grid, items=K, weighted_items=4, pairs_per_item=[p.n_pairs for p in mixed], layers=[])
+    n = int(os.environ.get("DH_CALLS", "200"))
+    gen = torch.Generator().manual_seed(1)
+    fw, bw, sc = [3.0] * K, [2.0] * K, [256.0] * K
+    for C in (320, 640, 1280):
+        cur = list(torch.randn(K, grid, grid, C, generator=gen).half().to(dev))
+        org = list(torch.randn(K, grid, grid, C, generator=gen).half().to(dev))
+        outs = list(torch.empty(K, grid, grid, C, dtype=torch.float16, device=dev))
+
+        def one_launch():
+            LS.energy_and_grad_planned_mixed(cur, org, mixed, fw, bw, sc, outs=outs)
+
+        def item_by_item():
+            for e in range(K):
+                LS.energy_and_grad_planned(cur[e], org[e], mixed[e], fw[e], bw[e], grad_scale=sc[e], out=outs[e])
+
+        def unweighted_batch():
+            LS.energy_and_grad_planned_batch(cur, org, plain, fw, bw, sc, outs=outs)
+        ways = (("mixed_one_launch", one_launch), ("mixed_item_by_item", item_by_item), ("unweighted_batch", unweighted_batch))
+        for _, run in ways:
+            for _ in range(20):
+                run()
+        torch.cuda.synchronize()
+        best = {name: [] for name, _ in ways}
+        for _ in range(5):                                   # alternating blocks of n calls
+            for name, run in ways:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
+                best[name].append(e0.elapsed_time(e1) * 1e3 / n)
+        med = {k: sorted(v)[len(v) // 2] for k, v in best.items()}
+        info["layers"].append(dict(C=C, us_per_batch_median=med, us_per_batch_blocks=best,
+                                   item_by_item_over_one_launch=med["mixed_item_by_item"] / med["mixed_one_launch"],
+                                   one_launch_over_unweighted_batch=med["mixed_one_launch"] / med["unweighted_batch"]))
+    line = json.dumps(info)
+    out_dir = os.environ.get("DH_OUT") or os.path.join(ROOT, "profiles", "mixed_objects")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, f"bench_energy_res{res}.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if os.environ.get("DH_MIXED"):
+    mixed_bench()
+    sys.exit(0)
 if os.environ.get("DH_OBJECT_WEIGHTS"):
     v = os.environ["DH_OBJECT_WEIGHTS"]
     object_weights_bench(v if v == "equal" else [float(x) for x in v.split(",")])

@@ -9,6 +9,9 @@ scene directory, writing PNGs and the .npz identity cache with the reference's k
                                                                  #   input.png, mask.png, depth.exr, bg_depth.exr (or .npy),
                                                                  #   prompt.txt, transforms.json {name: {translation,
                                                                  #   rotation_axis, rotation_angle}}
+                                                                 # several objects: mask_0.png .. mask_{M-1}.png and entries
+                                                                 #   {name: {"objects": [M such entries], "object_weights":
+                                                                 #   "equal" | [M floats]}} (scene_io.load_scene_geometry; pc mode)
   python tools/run_edit.py --scene tests/golden/scene_banana_fruits --out /tmp/edit   # a scene of the reference's test data
 PNG / OpenEXR are read by diffusionhandles_amd.scene_io (no imaging library offline).
 Real weights: DIFFHANDLES_UNET_SAFETENSORS / DIFFHANDLES_VAE_SAFETENSORS / DIFFHANDLES_TEXT_ENCODER_DIR /
@@ -198,12 +201,20 @@ def identity_chunk(args, handles, scenes):
 
 def prepare_scene(args, scene, out, transform_names, warn=True):
     """The inputs and the transform list of one scene, and which of its edits exist already."""
-    from diffusionhandles_amd.scene_io import load_scene, transform_args
+    from diffusionhandles_amd.scene_io import load_scene, object_transform_args, transform_args
     from diffusionhandles_amd.synthetic import TRANSFORMS, make_image, make_scene
+    masks = None                    # a multi-object scene (mask_0.png ...): the list of its masks; `mask` is then their union
     if scene:
         sc = load_scene(scene, args.res)
         img, depth, bg_depth, mask, prompt, res = sc["img"], sc["depth"], sc["bg_depth"], sc["fg_mask"], sc["prompt"], args.res
-        transforms = [dict(name=n, **transform_args(t)) for n, t in sc["transforms"].items()]
+        masks = sc.get("fg_masks")
+        if masks is not None and args.mode != "pc":
+            raise NotImplementedError(f"{scene}: a multi-object scene ({len(masks)} masks) needs --mode pc; depth_transform_mode "
+                                      f"{args.mode!r} has no multi-object re-projection")
+        if masks is not None:       # entries {"objects": [...], "object_weights": ...}: transforms / object_weights per edit
+            transforms = [dict(name=n, **object_transform_args(t)) for n, t in sc["transforms"].items()]
+        else:
+            transforms = [dict(name=n, **transform_args(t)) for n, t in sc["transforms"].items()]
     else:
         res = args.res
         depth, bg_depth, mask = make_scene(res)
@@ -222,7 +233,8 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
     for i, tf in enumerate(transforms):
         tf.setdefault("name", f"edit{i}")
     exists = {tf["name"]: os.path.exists(os.path.join(out, tf["name"] + ".png")) for tf in transforms}
-    return dict(img=img, depth=depth, bg_depth=bg_depth, mask=mask, prompt=prompt, res=res, transforms=transforms, exists=exists)
+    return dict(img=img, depth=depth, bg_depth=bg_depth, mask=mask, masks=masks, prompt=prompt, res=res, transforms=transforms,
+                exists=exists)
 
 
 def scene_identity(args, dh, p, out, identity=None):
@@ -258,7 +270,11 @@ def scene_identity(args, dh, p, out, identity=None):
                      init_noise=noise.float().cpu().numpy(), activations1=acts[0].float().cpu().numpy(),
                      activations2=acts[1].float().cpu().numpy(), activations3=acts[2].float().cpu().numpy(),
                      latent_image=latent.float().cpu().numpy())
-    bg_depth = dh.set_foreground(depth, mask, bg_depth)
+    if p.get("masks") is not None:          # several objects: the blend runs over the union of the list
+        p["masks_dev"] = [m.to(dev) for m in p["masks"]]
+        bg_depth = dh.set_foreground(depth, p["masks_dev"], bg_depth)
+    else:
+        bg_depth = dh.set_foreground(depth, mask, bg_depth)
     torch.cuda.synchronize()
     t_identity = time.time() - t0 + chunk_s
     recon = dh.diffuser.decode_latent_image(latent)
@@ -331,8 +347,8 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
             p = prep[s]
             d, bg, m, img, null_text, noise, acts, rep = scene_identity(args, handles(p["res"]), p, os.path.join(args.out, s),
                                                                         ident.pop(s, None))
-            resident[s] = dict(depth=d, bg_depth=bg, fg_mask=m, img=img, null_text_emb=null_text, init_noise=noise,
-                               activations=acts, prompt=p["prompt"])
+            resident[s] = dict(depth=d, bg_depth=bg, fg_mask=m, fg_masks=p.get("masks_dev"), img=img, null_text_emb=null_text,
+                               init_noise=noise, activations=acts, prompt=p["prompt"])
             rep.update(scene=s, edit_batch=args.edit_batch,
                        edits=[dict(name=n, skipped=True) for n, ex in p["exists"].items() if args.skip_existing and ex])
             reports[s] = rep
@@ -340,9 +356,13 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
         for s, name in batch:
             tf = next(t for t in prep[s]["transforms"] if t["name"] == name)
             r = resident[s]
-            edits.append(dict(depth=r["depth"], prompt=r["prompt"], fg_mask=r["fg_mask"], bg_depth=r["bg_depth"],
-                              null_text_emb=r["null_text_emb"], init_noise=r["init_noise"], activations=r["activations"],
-                              rot_angle=tf["rot_angle"], rot_axis=tf["rot_axis"], translation=tf["translation"]))
+            common = dict(depth=r["depth"], prompt=r["prompt"], bg_depth=r["bg_depth"], null_text_emb=r["null_text_emb"],
+                          init_noise=r["init_noise"], activations=r["activations"])
+            if r["fg_masks"] is not None:
+                edits.append(dict(common, fg_masks=r["fg_masks"], transforms=tf["transforms"], object_weights=tf["object_weights"]))
+            else:
+                edits.append(dict(common, fg_mask=r["fg_mask"], rot_angle=tf["rot_angle"], rot_axis=tf["rot_axis"],
+                                  translation=tf["translation"]))
         t0 = time.time()
         images, disparities = handles(prep[scenes[0]]["res"]).transform_foregrounds(edits)
         torch.cuda.synchronize()
@@ -365,7 +385,8 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
 
 def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
     """One scene (the body of the reference's loop, test_diffusion_handles.py:66-175): identity (inversion + initial inference,
-    or the cache), set_foreground, one transform_foreground per transform.  transform_names: the subset / order the test set
+    or the cache), set_foreground, one transform_foreground per transform (a multi-object scene, mask_0.png ...:
+    set_foreground on the list of masks and one transform_foreground_objects per entry).  transform_names: the subset / order the test set
     lists for this scene (names the scene's transforms.json does not have are skipped with a warning, :126-128).
     identity: (null_text, noise, acts, latent, seconds) computed by identity_chunk (--identity-batch), written to the cache."""
     from diffusionhandles_amd.scene_io import write_png
@@ -383,8 +404,12 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
             report["edits"].append(dict(name=tf["name"], skipped=True))
             continue
         t0 = time.time()
-        res_ = dh.transform_foreground(depth, prompt, mask, bg_depth, null_text, noise, acts, rot_angle=tf["rot_angle"],
-                                      rot_axis=tf["rot_axis"], translation=tf["translation"])
+        if p.get("masks_dev") is not None:
+            res_ = dh.transform_foreground_objects(depth, prompt, p["masks_dev"], bg_depth, null_text, noise, acts,
+                                                   transforms=tf["transforms"], object_weights=tf["object_weights"])
+        else:
+            res_ = dh.transform_foreground(depth, prompt, mask, bg_depth, null_text, noise, acts, rot_angle=tf["rot_angle"],
+                                          rot_axis=tf["rot_axis"], translation=tf["translation"])
         torch.cuda.synchronize()
         dt = time.time() - t0
         edited, disparity = res_[0], res_[1]

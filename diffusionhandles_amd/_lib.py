@@ -162,6 +162,10 @@ DEBUG_SIGNATURES = {
     "dh_dbg_unet_ff_fold": (c_i, [c_p, c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_p, c_p, c_p]),
     "dh_dbg_gemm_family": (c_i, [c_i]),
     "dh_dbg_gemm_stage": (c_i, [c_i]),
+    "dh_dbg_gemm_xattn": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_i, c_i,
+                                ctypes.POINTER(c_i), c_p]),
+    "dh_dbg_gemm_xattn_dq": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(c_i), c_p]),
+    "dh_dbg_gemm_xattn_carried": (c_i, [ctypes.POINTER(c_i), ctypes.POINTER(ctypes.c_longlong)]),
     "dh_dbg_gemm_pp_variant": (c_i, [c_i, c_p]),
     "dh_dbg_gemm_pp_ablate": (c_i, [c_i]),
     "dh_dbg_gemm_pp_persist": (c_i, [c_i]),

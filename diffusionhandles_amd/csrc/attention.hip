@@ -14,42 +14,10 @@
 // 16-byte store and every tile exists once.
 // The backward kernels use the same two product shapes (one with the roles of keys and
 // queries exchanged).  dQ and dK/dV are separate kernels (no atomics, deterministic).
-#include "unet_kernels.h"
+#include "attn_tile.h"
 
 namespace dh {
 
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef __bf16 v8b __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-
-template <class T> struct Mma;
-template <> struct Mma<f16> {
-  static __device__ __forceinline__ v16f run(uint4 a, uint4 b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mma<bf16> {
-  static __device__ __forceinline__ v16f run(uint4 a, uint4 b, v16f c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8b, a), __builtin_bit_cast(v8b, b), c, 0, 0, 0);
-  }
-};
-
-constexpr int HD = 64;        // head dim
-constexpr int TLD = 72;       // LDS row stride in halves (144 B: conflict-free b128 and tr_b16 reads)
-constexpr int TILE = 64 * TLD;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
-constexpr float SCALE = 0.125f;               // 1/sqrt(64)
-constexpr float CEXP = SCALE * LOG2E;         // scores are exponentiated as exp2(s * CEXP - m * CEXP)
-
-__device__ __forceinline__ v16f zero16() {
-  v16f z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 #ifndef DH_ATTN_ABL
 #define DH_ATTN_ABL 0      // timing-only ablations of the forward loop (tools/lab.sh ablate-attn): never set in the product build
 #endif
@@ -109,30 +77,6 @@ __device__ __forceinline__ void commit_tile(const TileRegs<GT>& t, unsigned shor
     const int idx = tid + j * GT;
     if (512 % GT == 0 || idx < 512) *reinterpret_cast<u4v*>(&rm[(idx >> 3) * TLD + (idx & 7) * 8]) = t.v[j];
   }
-}
-
-// acc = sum_kk mfma(A = rows (rowbase + lane&31) of an LDS row-major tile, B = register fragments)
-template <class T>
-__device__ __forceinline__ v16f tile_times_frags(const unsigned short* tile, int rowbase, int ln, int hi, const uint4 (&f)[4]) {
-  v16f acc = zero16();
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const uint4 a = *reinterpret_cast<const uint4*>(&tile[(rowbase + ln) * TLD + 16 * kk + 8 * hi]);
-    acc = Mma<T>::run(a, f[kk], acc);
-  }
-  return acc;
-}
-
-// A operand = TRANSPOSE of a row-major tile: fragment row = tile column (cbase + lane&31), reduction slots =
-// tile rows r0.., in the accumulator order (rows r0 + 4 hi + 0..3 and r0 + 8 + 4 hi + 0..3).
-// `tptr` = &tile[(4 hi + (t >> 2)) * TLD + 16 * ((lane >> 4) & 1) + 4 * (t & 3)], t = lane & 15 (per lane, hoisted)
-__device__ __forceinline__ uint4 tr_frag(const unsigned short* tptr, int cbase, int r0) {
-  typedef __attribute__((address_space(3))) v4s* lp;
-  const unsigned short* a = tptr + r0 * TLD + cbase;
-  const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(a));
-  const v4s up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(a + 8 * TLD));
-  const uint2 l2 = __builtin_bit_cast(uint2, lo), u2 = __builtin_bit_cast(uint2, up);
-  return make_uint4(l2.x, l2.y, u2.x, u2.y);
 }
 
 // ---- dense tiles filled by LDS-DMA (k_attn_fwd, DB = true) --------------------------------------------------------
@@ -230,26 +174,6 @@ __device__ __forceinline__ uint4 dtr_frag(const unsigned short* trow, int lo_c, 
   return make_uint4(l2.x, l2.y, u2.x, u2.y);
 }
 
-// registers 8s..8s+7 of an accumulator -> B operand (16-bit)
-template <class T>
-__device__ __forceinline__ uint4 pack8(const v16f& p, int s);
-template <>
-__device__ __forceinline__ uint4 pack8<f16>(const v16f& p, int s) {
-  uint4 o;
-  o.x = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 0], p[8 * s + 1]));
-  o.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 2], p[8 * s + 3]));
-  o.z = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 4], p[8 * s + 5]));
-  o.w = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 6], p[8 * s + 7]));
-  return o;
-}
-template <>
-__device__ __forceinline__ uint4 pack8<bf16>(const v16f& p, int s) {
-  bf16 o[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (bf16)p[8 * s + j];
-  return *reinterpret_cast<uint4*>(o);
-}
-
 // store a transposed accumulator pair (rows = d, col = lane's row) as row `row` of a [rows][ld] matrix.  The two lanes
 // of a row (lane, lane ^ 32) own alternating 4-column groups: they swap two groups and write 16-byte chunks.
 // Must be called by both lanes of a pair (the guard `row valid` is the same for both).
@@ -271,8 +195,6 @@ __device__ __forceinline__ void store_rows_t(T* base, long ld, long row, int col
     *reinterpret_cast<uint4*>(out + 16) = cb;
   }
 }
-
-__device__ __forceinline__ int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 // Workgroup barrier of the register-staged tile loops that orders LDS traffic ONLY.  __syncthreads() is a fence + s_barrier, and
 // the fence is `s_waitcnt vmcnt(0) lgkmcnt(0)`: it drains the global loads of the NEXT tile that were issued a moment earlier

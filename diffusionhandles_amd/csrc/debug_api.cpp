@@ -163,6 +163,64 @@ extern "C" int dh_dbg_gemm_lnfold(int dtype, const void* A, long lda, const void
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
+// q projection + cross-attention the way the engine's forward runs attn2 (head dim 64, H = N / 64 heads, B images of M / B queries):
+// q = A W^T (+ bias), or the LayerNorm-folded form when ln_s is given (see dh_dbg_gemm_lnfold); o [M][N] = softmax(q K^T / 8) V per
+// head over the Nk keys of the row's image (k / v: [B * Nk][ldk], head h at column 64 h), lse [B][H][M / B].  The GEMM's dispatch
+// decides whether its epilogue carries the attention (*carried = 1: one launch, and q is written only when save != 0) or the
+// attention kernel runs behind it (*carried = 0).
+extern "C" int dh_dbg_gemm_xattn(int dtype, const void* A, long lda, const void* W, int M, int N, int K, const float* bias,
+                                 const float* ln_s, const float* ln_t, float* ln_stats, float ln_eps, void* q, const void* k,
+                                 const void* v, long ldk, void* o, float* lse, int B, int Nk, int save, int* carried, void* stream) {
+  DH_REQUIRE(A && W && q && k && v && o && lse && K % 64 == 0 && N % 64 == 0 && B > 0 && M % B == 0 && Nk > 0, "bad arguments");
+  DH_REQUIRE(!ln_s || (ln_t && ln_stats), "the folded LayerNorm needs ln_s, ln_t and ln_stats");
+  static void* tiled = nullptr;
+  static size_t tiled_cap = 0;
+  const size_t need = (size_t)N * K * 2;
+  if (need > tiled_cap) {
+    if (tiled) (void)hipFree(tiled);
+    DH_CHECK_HIP(hipMalloc(&tiled, need));
+    tiled_cap = need;
+  }
+  launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream);
+  GemmArgs g;
+  g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = A_DENSE; g.bias = bias; g.C = q; g.ldc = N;
+  if (ln_s) { g.ln_s = ln_s; g.ln_t = ln_t; g.ln_stats = ln_stats; g.ln_eps = ln_eps; }
+  int have = 0;
+  g.xa_k = k; g.xa_v = v; g.xa_ldk = ldk; g.xa_o = o; g.xa_ldo = N; g.xa_lse = lse; g.xa_H = N / 64; g.xa_Nq = M / B; g.xa_Nk = Nk;
+  g.xa_save = save; g.xa_done = &have;
+  launch_gemm(dtype, g, (hipStream_t)stream);
+  if (!have) launch_attention_fwd(dtype, q, N, k, v, ldk, o, N, lse, B, N / 64, M / B, Nk, (hipStream_t)stream);
+  if (carried) *carried = have;
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// ... and the backward to q the way the engine runs it when no text gradient is wanted: dO = A W^T [M][N] (the input-gradient GEMM
+// of attn2.to_out.0) and dq of the cross-attention with saved q, o [M][N], lse and k / v as above.  *carried = 1: the GEMM's
+// epilogue wrote dq and d_o is untouched; *carried = 0: d_o holds dO and the dQ kernel ran behind the GEMM.
+extern "C" int dh_dbg_gemm_xattn_dq(int dtype, const void* A, long lda, const void* W, int M, int N, int K, void* d_o, const void* q,
+                                    const void* k, const void* v, long ldk, const void* o, const float* lse, void* dq, int B, int Nk,
+                                    int* carried, void* stream) {
+  DH_REQUIRE(A && W && d_o && q && k && v && o && lse && dq && K % 64 == 0 && N % 64 == 0 && B > 0 && M % B == 0 && Nk > 0, "bad arguments");
+  static void* tiled = nullptr;
+  static size_t tiled_cap = 0;
+  const size_t need = (size_t)N * K * 2;
+  if (need > tiled_cap) {
+    if (tiled) (void)hipFree(tiled);
+    DH_CHECK_HIP(hipMalloc(&tiled, need));
+    tiled_cap = need;
+  }
+  launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream);
+  GemmArgs g;
+  g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = A_DENSE; g.C = d_o; g.ldc = N;
+  int have = 0;
+  g.xa_k = k; g.xa_v = v; g.xa_ldk = ldk; g.xa_o = const_cast<void*>(o); g.xa_ldo = N; g.xa_lse = const_cast<float*>(lse);
+  g.xa_H = N / 64; g.xa_Nq = M / B; g.xa_Nk = Nk; g.xa_q = q; g.xa_ldq = N; g.xa_dq = dq; g.xa_lddq = N; g.xa_done = &have;
+  launch_gemm(dtype, g, (hipStream_t)stream);
+  if (!have) launch_attention_bwd_dq(dtype, q, N, k, v, ldk, o, N, d_o, N, lse, nullptr, dq, N, B, N / 64, M / B, Nk, (hipStream_t)stream);
+  if (carried) *carried = have;
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
 // the GEGLU epilogues of the dense GEMM (engine: ff.net.0.proj forward, ff.net.2 input-gradient).  bwd = 0: W [N = 2F][K] and bias
 // in the PAIRED row order (unet_kernels.h glu_col), C (may be NULL) receives the pre-activations [M][2F] (paired), y [M][F] =
 // value * gelu(gate).  bwd = 1: the GEMM's tile A W^T [M][N = F] is dy of a GEGLU with saved pre-activations x [M][2F] (paired);

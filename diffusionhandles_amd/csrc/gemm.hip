@@ -25,6 +25,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "attn_tile.h"
 #include "gemm_k.h"
 
 namespace dh {
@@ -46,6 +47,8 @@ struct GemmTileReport {
   int bm, bn, kg, stages, mw, splits, pp, gn_epi, reduce_gn;
 };
 static thread_local GemmTileReport g_last_tile;
+static thread_local int g_last_xattn = 0;           // the last launch carried a cross-attention in its epilogue (dh_dbg_gemm_xattn_carried)
+static thread_local long long g_xattn_total = 0;    // ... and how many launches of this thread have
 #ifdef DH_TUNING
 static unsigned long long* g_gemm_ts = nullptr;      // device buffer of 8 stamps (dh_dbg_gemm_timeline)
 #endif
@@ -220,6 +223,11 @@ template <> __device__ __forceinline__ void frag_sums<bf16>(const uint4& f_in, f
 // pre-activations only when p.C is set); GLU = 2: the tile is dy of a GEGLU: the epilogue reads the saved pre-activations of its
 // rows and writes d_value / d_gate instead of dy.  Both keep the activation where the data already sits in registers
 // (reference model/attention.py:345-400; diffusers GEGLU [ext]).
+// GLU = EPI_XATTN (3): the tile is q of one cross-attention head (64 columns) for BM queries of one image: the epilogue runs that
+// head's attention over its (at most XA_KEYS) text keys and writes o and lse; q goes to memory only for a backward pass.  The
+// 16-bit q tile crosses the two wave columns through the idle rings, K and V ride under the K loop in registers like the residual.
+// GLU = EPI_XATTN_DQ (4): the tile is dO of one cross-attention head (the input-gradient GEMM of attn2.to_out.0): the epilogue forms
+// dq of its queries from the saved q, o, lse and the head's K / V (k_attn_bwd_dq's products) and writes dq; dO is not written.
 // BUF (round 6): the staging of k_gemm_pp under this kernel's loop -- the LDS-DMA goes through a buffer descriptor
 // (`buffer_load_dwordx4 ... lds`): one 32-bit lane offset per piece computed once, the K cursor / the 3x3 tap in the scalar
 // offset, rows past M and taps outside the image = an out-of-range offset that the hardware turns into zeros (no zero page, no
@@ -522,6 +530,52 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
     }
   }
 
+  // cross-attention epilogue (p.xa): the head's K and V rows do not depend on this launch -- their 2 x XA_KEYS x 8 sixteen-byte
+  // chunks are fetched now by the 256 threads of the first wave group and fly under the K loop (rows past Nk read the last key
+  // again: finite values behind masked scores, as in attention.hip)
+  constexpr bool XA = GLU == EPI_XATTN || GLU == EPI_XATTN_DQ, XB = GLU == EPI_XATTN_DQ;
+  static_assert(!XB || !LNF, "the input-gradient GEMM carries no LayerNorm");
+  static_assert(!XA || xattn_epi_tile(BM, BN, WG, MW, BUF), "the cross-attention epilogue lives on the buffer-staged 64x64 / 128x64 tiles");
+  constexpr int XA_CH = XA_KEYS * 8 / 256;         // chunks per thread and matrix
+  u4v xa_kr[XA ? XA_CH : 1], xa_vr[XA ? XA_CH : 1];      // (vector types: a struct copy from memory is a memcpy the private array does not survive as registers)
+  if constexpr (XA) {
+    if (KG == 1 || kg == 0) {
+      const int b = div_small(m0, __builtin_amdgcn_rcpf((float)p.xa_Nq));
+      const size_t head = (size_t)b * p.xa_Nk * p.xa_ldk + n0;
+      const T* kp = reinterpret_cast<const T*>(p.xa_k) + head;
+      const T* vp = reinterpret_cast<const T*>(p.xa_v) + head;
+#pragma unroll
+      for (int j = 0; j < XA_CH; ++j) {
+        const int idx = tid + j * 256;
+        int r = idx >> 3;
+        r = r < p.xa_Nk ? r : p.xa_Nk - 1;
+        const size_t off = (size_t)r * p.xa_ldk + (idx & 7) * 8;
+        xa_kr[j] = *reinterpret_cast<const u4v*>(kp + off);
+        xa_vr[j] = *reinterpret_cast<const u4v*>(vp + off);
+      }
+    }
+  }
+  // ... and the backward form's saved q / o rows and lse of the 32 queries this wave will own in the epilogue (B-operand fragments
+  // straight from memory, as k_attn_bwd_dq loads them; rows past M read row M - 1 again and are never stored)
+  constexpr int XA_WPR = XA ? 4 / (BM / 32) : 1;      // waves per 32-query block of the tile
+  u4v xb_qf[XB ? 4 : 1], xb_of[XB ? 4 : 1];
+  float xb_lse = 0.f;
+  if constexpr (XB) {
+    if (KG == 1 || kg == 0) {
+      int m = m0 + (wave_s / XA_WPR) * 32 + ln;
+      m = m < p.M ? m : p.M - 1;
+      const T* qp = reinterpret_cast<const T*>(p.xa_q) + (size_t)m * p.xa_ldq + n0 + 8 * hi;
+      const T* op = reinterpret_cast<const T*>(p.xa_o) + (size_t)m * p.xa_ldo + n0 + 8 * hi;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        xb_qf[kk] = *reinterpret_cast<const u4v*>(qp + 16 * kk);
+        xb_of[kk] = *reinterpret_cast<const u4v*>(op + 16 * kk);
+      }
+      const int b = div_small(m0, __builtin_amdgcn_rcpf((float)p.xa_Nq));
+      xb_lse = p.xa_lse[((size_t)b * p.xa_H + blockIdx.y) * p.xa_Nq + (m - b * p.xa_Nq)] * LOG2E;
+    }
+  }
+
   constexpr int KK = BK / 16 / WG;                // k-steps of a tile multiplied by this wave group
   const int kk0 = grp * KK;
   // The K loop carries as little VALU work as it can: a wave's own vector instructions (and those of the wave it shares a
@@ -676,6 +730,169 @@ __global__ void __launch_bounds__(256 * WG * KG * MW) k_gemm_dma(const GemmK p) 
     }
   }
 
+  if constexpr (XA) {
+    // Cross-attention of this head.  The rounded q tile (what the unfused kernel would read back) goes to LDS at the padded row
+    // stride of attention.hip, K and V behind it; then every 32-row block of the tile is one wave's queries (64-row tiles: two
+    // waves per block, one half of the head dimension of O each) and the products are k_attn_fwd's -- S^T = K Q^T with the keys
+    // past Nk masked, ONE exact softmax over all keys (no running maximum: they all sit in registers), O^T = V^T P^T with P
+    // rounded to 16 bits -- fully unrolled over the three 32-key blocks.  The backward form (XB) stages its dO tile the same way and
+    // runs k_attn_bwd_dq's products: P = exp2(S c - lse), dP^T = V dO^T, dS = P (dP - delta), dQ^T = K^T dS^T, scaled once at the end.
+    typedef T T4 __attribute__((ext_vector_type(4)));
+    static_assert((BM + 2 * XA_KEYS) * TLD * 2 <= KG * ST * STAGE, "q, K and V tiles fit the idle rings");
+    unsigned short* sq = reinterpret_cast<unsigned short*>(smem_all);
+    unsigned short* sk = sq + BM * TLD;
+    unsigned short* sv = sk + XA_KEYS * TLD;
+    const bool hb = p.bias != nullptr;
+    __syncthreads();                                 // every wave is done with the rings / the merge buffers
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int row = wm * RPW + i * 32 + ln, m = m0 + row;
+      uint2 w[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        float v0 = acc[i][0][4 * g], v1 = acc[i][0][4 * g + 1], v2 = acc[i][0][4 * g + 2], v3 = acc[i][0][4 * g + 3];
+        if (hb) { const float4 b = bpre[0][g]; v0 += b.x; v1 += b.y; v2 += b.z; v3 += b.w; }
+        T4 o;
+        o[0] = from_f32<T>(v0); o[1] = from_f32<T>(v1); o[2] = from_f32<T>(v2); o[3] = from_f32<T>(v3);
+        w[g] = __builtin_bit_cast(uint2, o);
+      }
+      const uint4 ca = half_exchange(w[0], w[1]), cb = half_exchange(w[2], w[3]);
+      if (!XB && p.xa_save && m < p.M) {
+        T* orow = reinterpret_cast<T*>(p.C) + (size_t)m * p.ldc + n0 + wn * CPW + 8 * hi;
+        *reinterpret_cast<uint4*>(orow) = ca;
+        *reinterpret_cast<uint4*>(orow + 16) = cb;
+      }
+      *reinterpret_cast<uint4*>(&sq[row * TLD + wn * CPW + 8 * hi]) = ca;
+      *reinterpret_cast<uint4*>(&sq[row * TLD + wn * CPW + 8 * hi + 16]) = cb;
+    }
+#pragma unroll
+    for (int j = 0; j < XA_CH; ++j) {
+      const int idx = tid + j * 256;
+      *reinterpret_cast<u4v*>(&sk[(idx >> 3) * TLD + (idx & 7) * 8]) = xa_kr[j];
+      *reinterpret_cast<u4v*>(&sv[(idx >> 3) * TLD + (idx & 7) * 8]) = xa_vr[j];
+    }
+    __syncthreads();
+    constexpr int WPR = XA_WPR, NDT = 2 / WPR;      // waves per 32-query block, 32-wide halves of the head dimension per wave
+    const int rb = wave_s / WPR, dt0 = (wave_s % WPR) * NDT;
+    uint4 qf[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) qf[kk] = *reinterpret_cast<const uint4*>(&sq[(rb * 32 + ln) * TLD + 16 * kk + 8 * hi]);
+    const int t16 = lane & 15;
+    const int tr_off = (4 * hi + (t16 >> 2)) * TLD + 16 * ((lane >> 4) & 1) + 4 * (t16 & 3);      // (tr_frag's per-lane tile offset)
+    if constexpr (XB) {
+      // qf holds the dO fragments of the wave's rows; delta = rowsum(dO o O) from the fragments, as the unfused kernel sums it
+      typedef T T8 __attribute__((ext_vector_type(8)));
+      uint4 sqf[4];
+      float del = 0.f;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const T8 ov = __builtin_bit_cast(T8, xb_of[kk]), dv = __builtin_bit_cast(T8, qf[kk]);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) del += to_f32<T>(ov[c]) * to_f32<T>(dv[c]);
+        sqf[kk] = __builtin_bit_cast(uint4, xb_qf[kk]);
+      }
+      del = xor32_sum(del);
+      const unsigned short* kt = sk + tr_off;
+      v16f dqa[NDT];
+#pragma unroll
+      for (int d = 0; d < NDT; ++d) dqa[d] = zero16();
+#pragma unroll
+      for (int kb = 0; kb < XA_KEYS / 32; ++kb) {
+        v16f sc = tile_times_frags<T>(sk, kb * 32, ln, hi, sqf);
+        const v16f dp = tile_times_frags<T>(sv, kb * 32, ln, hi, qf);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float pr = kb * 32 + acc_row(r, hi) < p.xa_Nk ? fast_exp2(__builtin_fmaf(sc[r], CEXP, -xb_lse)) : 0.f;
+          sc[r] = pr * (dp[r] - del);
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const uint4 dsf = pack8<T>(sc, s2);
+#pragma unroll
+          for (int d = 0; d < NDT; ++d) dqa[d] = Mfma<T>::run(tr_frag(kt, (dt0 + d) * 32, kb * 32 + 16 * s2), dsf, dqa[d]);
+        }
+      }
+      const int m = m0 + rb * 32 + ln;
+      if (m < p.M) {
+        T* orow = reinterpret_cast<T*>(p.xa_dq) + (size_t)m * p.xa_lddq + n0 + 8 * hi;
+#pragma unroll
+        for (int d = 0; d < NDT; ++d) {
+          uint2 w[4];
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            T4 o;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[c] = from_f32<T>(dqa[d][4 * g + c] * SCALE);
+            w[g] = __builtin_bit_cast(uint2, o);
+          }
+          const uint4 ca = half_exchange(w[0], w[1]), cb = half_exchange(w[2], w[3]);
+          *reinterpret_cast<uint4*>(orow + (dt0 + d) * 32) = ca;
+          *reinterpret_cast<uint4*>(orow + (dt0 + d) * 32 + 16) = cb;
+        }
+      }
+      return;
+    }
+    v16f sc[XA_KEYS / 32];
+#pragma unroll
+    for (int kb = 0; kb < XA_KEYS / 32; ++kb) {
+      sc[kb] = tile_times_frags<T>(sk, kb * 32, ln, hi, qf);
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (kb * 32 + acc_row(r, hi) >= p.xa_Nk) sc[kb][r] = -INFINITY;
+    }
+    float mx = sc[0][0];
+#pragma unroll
+    for (int kb = 0; kb < XA_KEYS / 32; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[kb][r]);
+    mx = xor32_max(mx);
+    const float mc = mx * CEXP;
+    float l = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < XA_KEYS / 32; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        sc[kb][r] = fast_exp2(__builtin_fmaf(sc[kb][r], CEXP, -mc));
+        l += sc[kb][r];
+      }
+    l = xor32_sum(l);
+    const unsigned short* vt = sv + tr_off;
+    v16f oa[NDT];
+#pragma unroll
+    for (int d = 0; d < NDT; ++d) oa[d] = zero16();
+#pragma unroll
+    for (int kb = 0; kb < XA_KEYS / 32; ++kb)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const uint4 pf = pack8<T>(sc[kb], s2);
+#pragma unroll
+        for (int d = 0; d < NDT; ++d) oa[d] = Mfma<T>::run(tr_frag(vt, (dt0 + d) * 32, kb * 32 + 16 * s2), pf, oa[d]);
+      }
+    const int m = m0 + rb * 32 + ln;
+    if (m < p.M) {
+      const float inv_l = 1.f / l;
+      T* orow = reinterpret_cast<T*>(p.xa_o) + (size_t)m * p.xa_ldo + n0 + 8 * hi;
+#pragma unroll
+      for (int d = 0; d < NDT; ++d) {
+        uint2 w[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          T4 o;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) o[c] = from_f32<T>(oa[d][4 * g + c] * inv_l);
+          w[g] = __builtin_bit_cast(uint2, o);
+        }
+        const uint4 ca = half_exchange(w[0], w[1]), cb = half_exchange(w[2], w[3]);
+        *reinterpret_cast<uint4*>(orow + (dt0 + d) * 32) = ca;
+        *reinterpret_cast<uint4*>(orow + (dt0 + d) * 32 + 16) = cb;
+      }
+      if (hi == 0 && dt0 == 0) {
+        const int b = div_small(m0, __builtin_amdgcn_rcpf((float)p.xa_Nq));
+        p.xa_lse[((size_t)b * p.xa_H + blockIdx.y) * p.xa_Nq + (m - b * p.xa_Nq)] = (mc + log2f(l)) * LN2;
+      }
+    }
+    return;
+  }
 
   if constexpr (GLU == 1) {
     // GEGLU forward.  Lane (ln, hi) owns value columns {8 g + 4 hi ..+3} (g = 0, 1) of every 32-column block and their gates
@@ -1274,6 +1491,11 @@ static void launch_tile_b(int gm, bool lnf, dim3 grid, hipStream_t st, const Gem
     if (glu == 1) { DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_DENSE, 0, WG, KG, MW, false, 1, BUF>)); return; }
     if (glu == 2) { DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_DENSE, 0, WG, KG, MW, false, 2, BUF>)); return; }
   }
+  if constexpr (xattn_epi_tile(BM, BN, WG, MW, BUF)) {
+    if (glu == EPI_XATTN && lnf) { DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_DENSE, 0, WG, KG, MW, true, EPI_XATTN, BUF>)); return; }
+    if (glu == EPI_XATTN) { DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_DENSE, 0, WG, KG, MW, false, EPI_XATTN, BUF>)); return; }
+    if (glu == EPI_XATTN_DQ) { DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_DENSE, 0, WG, KG, MW, false, EPI_XATTN_DQ, BUF>)); return; }
+  }
   if (gm == GM_DENSE) {
     if constexpr (WG == 1 && BN != 320 && BN != 160) {      // (the 128x320 / 128x160 tiles are never asked for the folded LayerNorm)
       if (lnf) { DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_DENSE, 0, WG, KG, MW, true, 0, BUF>)); return; }
@@ -1303,7 +1525,7 @@ static void launch_tile(int gm, bool lnf, dim3 grid, hipStream_t st, const GemmK
 #endif
 
 template <class T>
-static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn_done, int* lnb_done, int dtype) {
+static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn_done, int* lnb_done, int* xa_done, int dtype) {
   DH_KNOB(kSplitTiles, "DH_SPLITK_TILES", 200);     // split K only under this many output tiles ...
   DH_KNOB(kSplitMinK, "DH_SPLITK_MINKT", 32);       // ... and from this many K tiles (24 -> 32: +1 % on the guided step)
   DH_KNOB(kSplitTarget, "DH_SPLITK_TARGET", 256);   // workgroups aimed at
@@ -1428,6 +1650,40 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
 #else
   dim3 grid(tm, tn, splits);
 #endif
+  int gm = GM_GENERIC;
+  if (k.mode == A_DENSE) gm = GM_DENSE;
+  else if (k.mode == A_CONV3 && k.stride == 1 && k.up == 0 && k.pad == 1) gm = GM_CONV_S1;
+  // buffer-descriptor staging (BUF instantiations) whenever both operands lie below 2 GiB and the rows are 16-byte aligned
+  // (every launch of the U-Net / VAE / text engines; anything else keeps the address form)
+  if (!use_pp) {
+    k.pp_a_bytes = 0; k.pp_w_bytes = 0;
+    size_t ab = 0;
+    if (k.mode == A_DENSE) ab = ((size_t)(k.M - 1) * k.lda + k.K) * 2;
+    else if (k.Hout > 0 && k.Wout > 0 && k.M % (k.Hout * k.Wout) == 0)
+      ab = (size_t)(k.M / (k.Hout * k.Wout)) * k.Hin * k.Win * (size_t)k.lda * 2;
+    const size_t wb = (size_t)align_up((size_t)k.N, 64) * k.K * 2;
+    const bool conv_ok = k.mode == A_DENSE || (k.Cin % 64 == 0 && k.K == 9 * k.Cin);
+    if ((g_buf_stage & 1) && ab > 0 && conv_ok && ab + (size_t)(k.Win + 1) * k.lda * 2 < 0x7ff00000ull && wb < 0x7ff00000ull && k.lda % 8 == 0 &&
+        ((size_t)k.A & 15) == 0 && ((size_t)k.W & 15) == 0) {
+      k.pp_a_bytes = (unsigned)ab; k.pp_w_bytes = (unsigned)wb;
+    }
+  }
+  // Cross-attention in the epilogue (EPI_XATTN): the q projection of a cross-attention whose 64-column tiles are whole heads and
+  // whose row tiles lie inside one image (a tile never mixes two images' K / V), unsplit, with the plain bias-only epilogue, at
+  // most XA_KEYS keys, every operand 16-byte aligned.  *xa_done tells the caller that the attention has been launched with it.
+  k.xa = 0;
+  const bool xa_bwd = k.xa_dq != nullptr;
+  if (k.xa_o && xa_done && (g_buf_stage & (xa_bwd ? 32 : 16)) == 0 && splits == 1 && !use_pp && !glu && !t160 && !n320 && !mw2 &&
+      xattn_epi_tile(BM, BN, 1, 1, k.pp_a_bytes != 0) && gm == GM_DENSE && k.xa_Nk >= 1 && k.xa_Nk <= XA_KEYS && k.xa_Nq > 0 &&
+      k.N == 64 * k.xa_H && k.M % k.xa_Nq == 0 && k.M < (1 << 22) && (k.M == k.xa_Nq || k.xa_Nq % BM == 0) && k.C && k.wide_store && k.pre_r &&
+      !k.R && !k.rowvec && !k.act_silu && !k.gn_epi && k.xa_lse && k.xa_ldk % 8 == 0 && k.xa_ldo % 8 == 0 &&
+      (((size_t)k.xa_k | (size_t)k.xa_v | (size_t)k.xa_o) & 15) == 0 &&
+      (!xa_bwd || (!lnf && !k.bias && k.xa_q && k.xa_ldq % 8 == 0 && k.xa_lddq % 8 == 0 && (((size_t)k.xa_q | (size_t)k.xa_dq) & 15) == 0)))
+    k.xa = xa_bwd ? 2 : 1;
+#ifdef DH_TUNING
+  if (force_tile) k.xa = 0;
+#endif
+  const int epi = k.xa == 2 ? EPI_XATTN_DQ : (k.xa ? EPI_XATTN : glu);
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (g_prof.on) {
     if (g_prof.used + 2 > g_prof.ev.size()) {
@@ -1448,26 +1704,10 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
     // saved pre-activations read [M][2F], their gradient written [M][2F] (C holds only the columns past F)
     if (k.glub_x) c_elems += 4.0 * (double)k.M * k.glub_f - (k.C ? (double)k.M * k.glub_f : 0.0);
     if (k.gn_epi == 2) c_elems += (double)k.M * k.N;       // the GroupNorm input tile the backward statistics read
+    if (k.xa == 1) c_elems += (k.xa_save ? 1.0 : 0.0) * (double)k.M * k.N + 2.0 * (k.M / k.xa_Nq) * (double)k.xa_Nk * k.N;   // o for q (q too when saved), the heads' K and V
+    if (k.xa == 2) c_elems += 2.0 * (double)k.M * k.N + 2.0 * (k.M / k.xa_Nq) * (double)k.xa_Nk * k.N;     // dq for dO; q, o, K and V read
     g_prof.bytes += esz * (a_elems + (double)k.N * k.K + c_elems);
     g_prof.e0 = e0; g_prof.e1 = e1;
-  }
-  int gm = GM_GENERIC;
-  if (k.mode == A_DENSE) gm = GM_DENSE;
-  else if (k.mode == A_CONV3 && k.stride == 1 && k.up == 0 && k.pad == 1) gm = GM_CONV_S1;
-  // buffer-descriptor staging (BUF instantiations) whenever both operands lie below 2 GiB and the rows are 16-byte aligned
-  // (every launch of the U-Net / VAE / text engines; anything else keeps the address form)
-  if (!use_pp) {
-    k.pp_a_bytes = 0; k.pp_w_bytes = 0;
-    size_t ab = 0;
-    if (k.mode == A_DENSE) ab = ((size_t)(k.M - 1) * k.lda + k.K) * 2;
-    else if (k.Hout > 0 && k.Wout > 0 && k.M % (k.Hout * k.Wout) == 0)
-      ab = (size_t)(k.M / (k.Hout * k.Wout)) * k.Hin * k.Win * (size_t)k.lda * 2;
-    const size_t wb = (size_t)align_up((size_t)k.N, 64) * k.K * 2;
-    const bool conv_ok = k.mode == A_DENSE || (k.Cin % 64 == 0 && k.K == 9 * k.Cin);
-    if ((g_buf_stage & 1) && ab > 0 && conv_ok && ab + (size_t)(k.Win + 1) * k.lda * 2 < 0x7ff00000ull && wb < 0x7ff00000ull && k.lda % 8 == 0 &&
-        ((size_t)k.A & 15) == 0 && ((size_t)k.W & 15) == 0) {
-      k.pp_a_bytes = (unsigned)ab; k.pp_w_bytes = (unsigned)wb;
-    }
   }
 #ifdef DH_TUNING
   // ablations of the K loop (timing only): 1 = no LDS reads / MFMA, 2 = no DMA in the loop, 3 = 1 on the dense kernel
@@ -1500,18 +1740,20 @@ static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn
   // (same-box A/B, profiles/r04_ab_two_per_cu.txt: B = 2 forward 5.46 -> 5.30 ms, backward 6.82 -> 6.67 ms; 96x96 latents bf16 B = 1
   // forward 6.49 -> 6.32 ms, backward 9.55 -> 9.40 ms; guided step 34.97 -> 35.30 steps/s)
   else if (kTwoPerCu && BM == 128 && BN == 64 && tiles * splits > 256 && tiles * splits <= 512)
-    launch_tile<T, 128, 64, 3, 1, 1, 1>(gm, lnf, grid, st, k);
-  else if (BM == 128 && BN == 64 && tiles_per_split >= kKg2MinKt) launch_tile<T, 128, 64, 3, 1, 2, 1>(gm, lnf, grid, st, k);
+    launch_tile<T, 128, 64, 3, 1, 1, 1>(gm, lnf, grid, st, k, epi);
+  else if (BM == 128 && BN == 64 && tiles_per_split >= kKg2MinKt) launch_tile<T, 128, 64, 3, 1, 2, 1>(gm, lnf, grid, st, k, epi);
   // eight waves (4 x 2, 32 x 160 outputs each): the two-stage ring has one 57-KB tile in flight and its 56 one-KiB DMA pieces were
   // issued by four waves, 14 each at 60 - 185 cycles apiece -- the issue, not the latency, bounded the tile; with seven pieces per
   // wave: M = 32768, N = 320 dense K = 320 20.6 -> 14.9 us, K = 1280 40.1 -> 34.6 us, conv K = 2880 76.8 -> 67.3 us, batch-8
   // forward 13.55 -> 13.15 ms (profiles/r04_ab_n320_eight_waves.txt)
   else if (BN == 320) launch_tile<T, 128, 320, 2, 1, 1, 2>(gm, false, grid, st, k);
-  else if (BM == 64) launch_tile<T, 64, 64, 4, 1, 1, 1>(gm, lnf, grid, st, k, glu);      // (rings of 6 / 8 stages: pass 2 % SLOWER; round 3, eight stages only on the <= 256-workgroup long-K launches: guided step -1.1 %)
+  else if (BM == 64) launch_tile<T, 64, 64, 4, 1, 1, 1>(gm, lnf, grid, st, k, epi);      // (rings of 6 / 8 stages: pass 2 % SLOWER; round 3, eight stages only on the <= 256-workgroup long-K launches: guided step -1.1 %)
   else if (BN == 128 && kManyBlocks > 0 && tiles * splits >= kManyBlocks) launch_tile<T, 128, 128, 2, 1, 1, 1>(gm, lnf, grid, st, k);   // 64 KiB: two workgroups per CU
   else if (BN == 128) launch_tile<T, 128, 128, 4, 1, 1, 1>(gm, lnf, grid, st, k);
-  else launch_tile<T, 128, 64, 5, 1, 1, 1>(gm, lnf, grid, st, k);
+  else launch_tile<T, 128, 64, 5, 1, 1, 1>(gm, lnf, grid, st, k, epi);
   g_prof.e0 = g_prof.e1 = nullptr;
+  g_last_xattn = k.xa;                             // (1 forward, 2 backward)
+  if (k.xa) { ++g_xattn_total; *xa_done = 1; }
   g_last_tile.splits = splits; g_last_tile.pp = use_pp ? 1 : 0; g_last_tile.gn_epi = k.gn_epi;
   if (k.gn_epi) *gn_done = k.gn_S;
   if (splits > 1) {
@@ -1561,10 +1803,14 @@ double launch_gemm(int dtype, const GemmArgs& a, hipStream_t st) {
   } else if (a.glub_x) {
     k.C = nullptr;        // (the whole tile is dy of the GEGLU: C is not written)
   }
+  k.xa = 0; k.xa_k = a.xa_k; k.xa_v = a.xa_v; k.xa_ldk = a.xa_ldk; k.xa_o = a.xa_o; k.xa_ldo = a.xa_ldo; k.xa_lse = a.xa_lse;
+  k.xa_H = a.xa_H; k.xa_Nq = a.xa_Nq; k.xa_Nk = a.xa_Nk; k.xa_save = a.xa_save;
+  k.xa_q = a.xa_q; k.xa_ldq = a.xa_ldq; k.xa_dq = a.xa_dq; k.xa_lddq = a.xa_lddq;
   if (a.gn_done) *a.gn_done = 0;
   if (a.lnb_done) *a.lnb_done = 0;
-  if (dtype == DH_DTYPE_F16) gemm_dispatch<f16>(k, a.partial_elems, st, a.gn_done, a.lnb_done, dtype);
-  else gemm_dispatch<bf16>(k, a.partial_elems, st, a.gn_done, a.lnb_done, dtype);
+  if (a.xa_done) *a.xa_done = 0;
+  if (dtype == DH_DTYPE_F16) gemm_dispatch<f16>(k, a.partial_elems, st, a.gn_done, a.lnb_done, a.xa_done, dtype);
+  else gemm_dispatch<bf16>(k, a.partial_elems, st, a.gn_done, a.lnb_done, a.xa_done, dtype);
   return 2.0 * (double)a.M * (double)a.N * (double)a.K;
 }
 
@@ -1585,7 +1831,7 @@ extern "C" int dh_dbg_gemm_family(int force) {
 
 // test hook: 1 = dense / stride-1 3x3 operands of k_gemm_dma stage through buffer descriptors (shipped), 0 = through addresses
 extern "C" int dh_dbg_gemm_stage(int buf) {
-  dh::g_buf_stage = buf;          // bit 0: buffer staging; bit 2 (value 4): NO GroupNorm forward statistics in the GEMM epilogue; bit 3 (8): NO backward ones
+  dh::g_buf_stage = buf;          // bit 0: buffer staging; bit 2 (value 4): NO GroupNorm forward statistics in the GEMM epilogue; bit 3 (8): NO backward ones; bit 4 (16): NO cross-attention in the q projection's epilogue; bit 5 (32): NO cross-attention dQ in the to_out input-gradient's epilogue
   return DH_OK;
 }
 
@@ -1596,6 +1842,14 @@ extern "C" int dh_dbg_gemm_last_tile(int* out) {
   const dh::GemmTileReport& r = dh::g_last_tile;
   const int v[9] = {r.bm, r.bn, r.kg, r.stages, r.mw, r.splits, r.pp, r.gn_epi, r.reduce_gn};
   for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return DH_OK;
+}
+
+// test hook: *last = the last GEMM launch of this thread carried a cross-attention in its epilogue (0 no, 1 forward, 2 dQ), *total = how many
+// launches of this thread have since the library was loaded (either pointer may be NULL)
+extern "C" int dh_dbg_gemm_xattn_carried(int* last, long long* total) {
+  if (last) *last = dh::g_last_xattn;
+  if (total) *total = dh::g_xattn_total;
   return DH_OK;
 }
 

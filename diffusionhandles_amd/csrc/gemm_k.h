@@ -54,6 +54,14 @@ struct GemmK {   // kernel-side copy of GemmArgs (plain data)
   // tile fastest), bytes the A / W buffer descriptors cover
   int pp_tm, pp_tn, pp_order, pp_nwork; unsigned pp_a_bytes, pp_w_bytes;
   unsigned long long* pp_ts;        // timeline stamps (measurement variants only)
+  // cross-attention in the epilogue (EPI_XATTN instantiations of k_gemm_dma; xa = 1 when the dispatch took the form): the tile is q
+  // of head n0 / 64 for BM queries of ONE image; xa_k / xa_v = the K / V rows of image 0 at head column 0 ([B * xa_Nk][xa_ldk]),
+  // xa_o [M][xa_ldo], xa_lse [B][H][xa_Nq] in k_attn_fwd's convention; q itself goes to C only when xa_save is set
+  int xa, xa_Nq, xa_Nk, xa_H, xa_save;
+  const void *xa_k, *xa_v; long xa_ldk; void* xa_o; long xa_ldo; float* xa_lse;
+  // ... and its backward to q (EPI_XATTN_DQ, xa = 2): the tile is dO; xa_q / xa_o / xa_lse are the saved forward tensors (read),
+  // xa_dq [M][xa_lddq] receives dq; C is not written
+  const void* xa_q; long xa_ldq; void* xa_dq; long xa_lddq;
 };
 
 
@@ -64,6 +72,16 @@ struct GemmK {   // kernel-side copy of GemmArgs (plain data)
 // split -- one predicate for the dispatch (host) and the kernel (device).  A tile lies wholly on one side of the seam.
 __host__ __device__ constexpr bool glub_tile_is_glu(int n0, int glub_f) { return n0 < glub_f; }
 __host__ __device__ constexpr bool glub_split_ok(int BN, int glub_f) { return BN > 0 && glub_f % BN == 0; }
+
+// Cross-attention in the epilogue of the q projection (GemmArgs::xa_o), and its dQ in the epilogue of the to_out input-gradient GEMM
+// (GemmArgs::xa_dq): the epilogue form numbers (the GLU template argument of
+// k_gemm_dma carries it), the key rows the form stages (three 32-key blocks: the 77 text tokens), and which tiles compile / may be
+// asked for it -- a 64-column tile is one head, each of its 32-row blocks one wave's queries.  One predicate for dispatch and kernel.
+constexpr int EPI_XATTN = 3, EPI_XATTN_DQ = 4;
+constexpr int XA_KEYS = 96;
+__host__ __device__ constexpr bool xattn_epi_tile(int BM, int BN, int WG, int MW, bool BUF) {
+  return BN == 64 && (BM == 64 || BM == 128) && WG == 1 && MW == 1 && BUF;
+}
 
 struct PpPlan { int bm = 0, bn = 0, splits = 1; };
 bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan);

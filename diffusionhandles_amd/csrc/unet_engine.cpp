@@ -83,6 +83,12 @@ struct Op {
   // produced its input (its input-gradient GEMM writes the gradient of the pre-activations directly) and in1 = the feed-forward
   // input t2, the other column window of its A operand (FfFold)
   int glu_op = -1, glub_op = -1;
+  // cross-attention run by the GEMM in front of it: on the attn2.to_q GEMM, xattn_op = index of the cross OP_ATTN that consumes its
+  // output (the GEMM's epilogue runs it where the dispatch can carry it, launch_gemm's xa_done; the OP_ATTN launches nothing then)
+  int xattn_op = -1;
+  // ... and on the attn2.to_out.0 GEMM, xattn_bwd_op = index of that OP_ATTN: when no text gradient is wanted, the epilogue of the
+  // GEMM's input-gradient launch turns its dO tile into dq (the attention's backward launches nothing then)
+  int xattn_bwd_op = -1;
 };
 
 // A transformer's proj_out folded into its ff.net.2 (the feed-forward output t3 = ff.net.2(g) + t2 has no other reader, and
@@ -349,10 +355,13 @@ struct Builder {
     c.out = tensor(N, C);
     c.lse_off = f32_slot((size_t)maxB * heads * N);
     u.ops.push_back(c);
+    u.ops[u.ops.size() - 2].xattn_op = (int)u.ops.size() - 1;      // (the q GEMM right in front of it)
     // the feed-forward input t2 and the GEGLU output g are column windows of one tensor [rows][5C] (g | t2): the A operand of
     // the folded ff.net.2 + proj_out GEMM (FfFold)
     const int tg = tensor(N, 5 * C, false);
+    const int xop = (int)u.ops.size() - 1;
     int t2 = linear(c.out, b + ".attn2.to_out.0", C, true, t1);
+    u.ops.back().xattn_bwd_op = xop;
     set_view(t2, tg, 4 * C);
     // feed forward (GEGLU)
     int n3 = ln(t2, b + ".norm3");
@@ -554,6 +563,7 @@ static void layout_tensors(dh_unet& u) {
     rd(o.in0, oi); rd(o.in1, oi); rd(o.res, oi); wr(o.out, oi);
     if (o.ln_fold >= 0) rd(u.ops[o.ln_fold].in0, oi);
     if (o.glu_op >= 0) wr(u.ops[o.glu_op].out, oi);
+    if (o.xattn_op >= 0) wr(u.ops[o.xattn_op].out, oi);
   }
   // a tensor nothing in the tape writes (an input) or that the caller reads afterwards stays for the whole pass
   std::vector<char> written(nt, 0);
@@ -984,6 +994,7 @@ static void forward_ops(dh_unet* u, int B, int n_ops, int first_op, bool kv_hit,
   const dh_unet_config& c = u->cfg;
   u->flops_fwd = 0;
   int gn_have = 0;       // the op just executed left the GroupNorm slice statistics of its output in u->small
+  int xa_have = 0;       // the q GEMM just executed ran the cross-attention behind it in its epilogue
   if (!kv_hit) launch_f32_to_t(dt, u->in_text, u->aptr(u->t_text), (size_t)B * c.text_len * c.cross_attention_dim, st);
   for (int oi = first_op; oi < n_ops; ++oi) {
     const Op& o = u->ops[oi];
@@ -1023,6 +1034,17 @@ static void forward_ops(dh_unet* u, int B, int n_ops, int first_op, bool kv_hit,
           g.glu_y = u->aptr(ge.out); g.glu_ldy = u->tens[ge.out].ld;
           if (!save) g.C = nullptr;
         }
+        xa_have = 0;
+        if (o.xattn_op >= 0 && o.xattn_op < n_ops) {
+          // the cross-attention that follows runs in this GEMM's epilogue where the dispatch can carry it; q goes to memory only
+          // for a backward pass
+          const Op& at = u->ops[o.xattn_op];
+          const unsigned short* kv = u->aptr(at.in1) + at.kv_col;
+          const int C = u->tens[at.out].C;
+          g.xa_k = kv; g.xa_v = kv + C; g.xa_ldk = u->tens[at.in1].C; g.xa_o = u->aptr(at.out); g.xa_ldo = C;
+          g.xa_lse = u->f32a + at.lse_off; g.xa_H = at.heads; g.xa_Nq = at.Nq; g.xa_Nk = at.Nk; g.xa_save = save ? 1 : 0;
+          g.xa_done = &xa_have;
+        }
         u->flops_fwd += launch_gemm(dt, g, st);
         break;
       }
@@ -1050,7 +1072,7 @@ static void forward_ops(dh_unet* u, int B, int n_ops, int first_op, bool kv_hit,
           const unsigned short* qkv = u->aptr(o.in0);
           launch_attention_fwd(dt, qkv, tq.C, qkv + C, qkv + 2 * C, tq.C, u->aptr(o.out), C, u->f32a + o.lse_off, B,
                                o.heads, o.Nq, o.Nk, st);
-        } else {
+        } else if (!(oi > 0 && u->ops[oi - 1].xattn_op == oi && xa_have)) {      // (else: done in the epilogue of the GEMM in front of it)
           const Ten& tkv = u->tens[o.in1];
           const unsigned short* kv = u->aptr(o.in1) + o.kv_col;
           launch_attention_fwd(dt, u->aptr(o.in0), tq.C, kv, kv + C, tkv.C, u->aptr(o.out), C, u->f32a + o.lse_off, B,
@@ -1205,6 +1227,7 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
   int lnb_have = 0, lnb_for = -1;       // the split-K reduce just run applied the backward of LayerNorm op lnb_for
   int cat_done = -1;                    // the GroupNorm backward just run wrote the gradient of concatenation op cat_done to its sources
   int glub_done = -1;                   // the input-gradient GEMM just run wrote the pre-activation gradient of GEGLU op glub_done
+  int xb_have = 0, xb_for = -1;         // the input-gradient GEMM just run wrote dq of cross-attention op xb_for from its epilogue
   for (int oi = (int)u->ops.size() - 1; oi >= 0; --oi) {
     const Op& o = u->ops[oi];
     // only the text gradient is wanted (null-text optimisation): nothing below the first cross-attention contributes to it
@@ -1290,6 +1313,19 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
             g.gn_part = u->small; g.gn_HW = tx.rows; g.gn_G = gn.groups; g.gn_done = &gnb_have;
             gnb_have = 0;
             gnb_for = oi - 1;
+          }
+          xb_have = 0;
+          if (o.xattn_bwd_op >= 0 && !bw.need_text && !u->gready[o.in0] && o.in0 == u->ops[o.xattn_bwd_op].out) {
+            // dO of a cross-attention whose K / V gradient nobody wants: dq comes out of this launch's epilogue where the dispatch
+            // can carry it (dO has no other reader and is not written then)
+            const Op& at = u->ops[o.xattn_bwd_op];
+            const unsigned short* kv = u->aptr(at.in1) + at.kv_col;
+            const int C = u->tens[at.out].C, ldq = u->tens[at.in0].C;
+            g.xa_k = kv; g.xa_v = kv + C; g.xa_ldk = u->tens[at.in1].C; g.xa_o = u->aptr(at.out); g.xa_ldo = C;
+            g.xa_lse = u->f32a + at.lse_off; g.xa_H = at.heads; g.xa_Nq = at.Nq; g.xa_Nk = at.Nk;
+            g.xa_q = u->aptr(at.in0); g.xa_ldq = ldq; g.xa_dq = u->gptr(at.in0); g.xa_lddq = ldq;
+            g.xa_done = &xb_have;
+            xb_for = o.xattn_bwd_op;
           }
           u->flops_bwd += launch_gemm(dt, g, st);
           u->gready[o.in0] = 1;
@@ -1393,6 +1429,9 @@ static void backward_ops(dh_unet* u, int B, unsigned act_mask, bool has_eps, boo
           launch_attention_bwd_dkv(dt, qkv, tq.C, qkv + C, qkv + 2 * C, tq.C, u->gptr(o.out), C, u->f32a + o.lse_off,
                                    delta, dqkv + C, dqkv + 2 * C, tq.C, B, o.heads, o.Nq, o.Nk, st);
           u->flops_bwd += 14.0 * B * o.heads * (double)o.Nq * o.Nk * 64;
+        } else if (xb_have && xb_for == oi) {       // dq written by the epilogue of the input-gradient GEMM behind it
+          xb_have = 0;
+          u->flops_bwd += 6.0 * B * o.heads * (double)o.Nq * o.Nk * 64;
         } else {
           const Ten& tkv = u->tens[o.in1];
           const unsigned short* kv = u->aptr(o.in1) + o.kv_col;

@@ -77,6 +77,17 @@ struct GemmArgs {
   //   that column block, R likewise).  W must be readable up to row align_up(N, 128) (zero rows past N).
   void* glu_y = nullptr; long glu_ldy = 0;
   const void* glub_x = nullptr; void* glub_dx = nullptr; int glub_f = 0;
+  // Cross-attention in the epilogue (xa_o != NULL: the GEMM is the q projection of a cross-attention with head dim 64, N = 64 H,
+  // M = B * xa_Nq): where the dispatch can carry it (dense, unsplit, 64-column k_gemm_dma tiles that lie inside one image, at most
+  // XA_KEYS keys) the launch also writes o = softmax(q K^T / 8) V and lse as launch_attention_fwd would from the stored q, and
+  // *xa_done is set to 1; otherwise the launch is the plain GEMM and the caller launches the attention.  xa_k / xa_v: image 0,
+  // head 0 of [B * xa_Nk][xa_ldk]; xa_save = 0: q is not written when the form is taken (no backward reads it).
+  const void *xa_k = nullptr, *xa_v = nullptr; long xa_ldk = 0; void* xa_o = nullptr; long xa_ldo = 0; float* xa_lse = nullptr;
+  int xa_H = 0, xa_Nq = 0, xa_Nk = 0, xa_save = 1; int* xa_done = nullptr;
+  // xa_dq != NULL: the backward twin -- the GEMM is the input-gradient of that attention's output projection (its tile is dO of one
+  // head); where the dispatch can carry it the launch writes dq [M][xa_lddq] as launch_attention_bwd_dq would from the stored dO, C
+  // (dO) is NOT written and *xa_done is set to 1.  xa_q / xa_o / xa_lse are the saved q, o and lse of the forward (read only).
+  const void* xa_q = nullptr; long xa_ldq = 0; void* xa_dq = nullptr; long xa_lddq = 0;
 };
 // split-K reduce + LayerNorm backward in one pass over the slabs (f32 [splits][rows][C]); dy is rounded to the storage type
 // before it is used, exactly as the reduce + k_ln_bwd pair does

@@ -180,6 +180,8 @@ DEBUG_SIGNATURES = {
     "dh_dbg_pool2x2": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "dh_dbg_ellipse_offsets": (c_i, [c_i, ctypes.POINTER(ctypes.c_int32), c_i, ctypes.POINTER(c_i)]),
     "dh_dbg_lane_ops": (c_i, [c_p, c_p, c_p, c_p]),
+    "dh_dbg_cg_limits": (c_i, [ctypes.POINTER(c_i)]),
+    "dh_dbg_cg_max_iter": (c_i, [c_i]),
 }
 
 

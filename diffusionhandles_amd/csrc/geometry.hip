@@ -374,6 +374,14 @@ __global__ void k_normalize(int R2, float* disp, const unsigned int* minmax, con
   inpaint[o] = (clean[o] != 0) != (raw[o] != 0) ? 1 : 0;
 }
 
+// What the in-fill solvers publish in the iteration slot instead of a count when the field is not valid (the host raises):
+// -1 = the bounded grid barrier of k_cg_fill_multi ran out; -2 = the iteration cap was reached with the residual still above the
+// tolerance (any solver); -3 = the pipelined recurrence broke down (a step length that is not positive and finite).
+constexpr int CG_BARRIER_TIMEOUT = -1, CG_NOT_CONVERGED = -2, CG_BREAKDOWN = -3;
+// test hook (dh_dbg_cg_max_iter): > 0 = the iteration cap of the in-fill calls that follow, 0 = each call's own
+static int g_cg_max_iter = 0;
+static inline int cg_cap(int own) { return g_cg_max_iter > 0 ? g_cg_max_iter : own; }
+
 // Harmonic in-fill: A x = b with A = 4 I - adjacency(masked), solved by CG in float64 by ONE
 // workgroup per edit (deterministic fixed-tree reductions).  The vectors are indexed by UNKNOWN (compact, coalesced);
 // the four neighbour unknowns of every unknown are resolved once through a pixel -> unknown map, so an iteration is
@@ -457,7 +465,7 @@ __global__ void __launch_bounds__(1024) k_cg_fill(int res, float* disp, const ui
   }
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += blockDim.x) d[U[i]] = (float)x[i];
-  if (threadIdx.x == 0) counts_out[e * count_stride + slot_it] = it;
+  if (threadIdx.x == 0) counts_out[e * count_stride + slot_it] = it == max_iter && rs > tol2 * bnorm ? CG_NOT_CONVERGED : it;
 }
 
 
@@ -554,7 +562,7 @@ __device__ __forceinline__ void cg_fill_lds(int e, int res, float* disp, const u
     const int i = threadIdx.x + sl * 1024;
     if (i < n) d[U[i]] = (float)x[sl];
   }
-  if (threadIdx.x == 0) counts_out[e * count_stride + slot_it] = it;
+  if (threadIdx.x == 0) counts_out[e * count_stride + slot_it] = it == max_iter && rs > tol2 * bnorm ? CG_NOT_CONVERGED : it;
 }
 
 // Holes too large for one CU's LDS: CGM_WGS workgroups per system.  One workgroup is bound by its CU's memory pipe (15 eight-byte
@@ -565,6 +573,7 @@ __device__ __forceinline__ void cg_fill_lds(int e, int res, float* disp, const u
 // agent-scope acquire, __syncthreads (cdna_hip_programming.md Guideline 16); the dot products are per-workgroup partials written
 // before the seam and added by everyone in workgroup order afterwards: identical in every workgroup (the convergence test must
 // agree: it decides whether the next seam is entered) and deterministic.
+constexpr int CG_REPLACE = 50;                 // k_cg_fill_multi: iterations between two residual replacements
 constexpr int CGM_WGS = 16, CGM_EPT = 4;       // unknowns per thread <= 4: n <= 16 * 4 * 1024 (r, w, z, s of an unknown: 8 registers; 8 unknowns spilled)
 struct CgSync { unsigned arrive; unsigned fail; unsigned pad[30]; double red[2][CGM_WGS]; double red2[2][CGM_WGS]; };
 // Forward progress of the seams needs the CGM_WGS workgroups of a system co-resident.  In-order dispatch gives that on an
@@ -652,14 +661,15 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
   // r, w, z, s of a thread's unknowns live in registers; x and p are private global arrays (p takes over the array the
   // right-hand side was exchanged through); only w is shared, double-buffered (neighbours read the old one while the new one is
   // written).  Same fixed point as cg_fill_lds / k_cg_fill (the iterates differ in rounding: f64, relative residual 1e-12).
+  // The recurrences alone drift apart on the larger holes; every CG_REPLACE-th iteration ties them back to x and p (in the loop).
   double* pv = r;                                // b is exchanged through this array during the set-up; afterwards it holds p
   double rl[CGM_EPT], wl[CGM_EPT], zl[CGM_EPT], sl[CGM_EPT];
   double part = 0.0;
 #pragma unroll
   for (int k = 0; k < CGM_EPT; ++k) {
-    const int i = i0 + (int)threadIdx.x + k * 1024;
+    const unsigned i = (unsigned)i0 + threadIdx.x + k * 1024u;
     rl[k] = 0.0; wl[k] = 0.0; zl[k] = 0.0; sl[k] = 0.0;
-    if (i < i1) {
+    if (i < (unsigned)i1) {
       const int pix = U[i], y = pix / res, xx = pix - y * res;
       double b = 0.0;
       int2 ud = make_int2(-1, -1), lr = make_int2(-1, -1);
@@ -689,8 +699,8 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
   if (!alive) { if (threadIdx.x == 0) atomicMin(&counts_out[e * count_stride + slot_it], -1); return; }
 #pragma unroll
   for (int k = 0; k < CGM_EPT; ++k) {           // w = A r (r = b: x starts at zero)
-    const int i = i0 + (int)threadIdx.x + k * 1024;
-    if (i < i1) {
+    const unsigned i = (unsigned)i0 + threadIdx.x + k * 1024u;
+    if (i < (unsigned)i1) {
       const int2 ud = nud[i], lr = nlr[i];
       double a = 4.0 * rl[k];
       if (ud.x >= 0) a -= cg_get(r + ud.x);
@@ -701,9 +711,33 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
       cg_put(P[0] + i, a);
     }
   }
+  // the right-hand side of unknown i again (the set-up's sum, in its order), for the residual replacement
+  auto rhs_of = [&](unsigned i) {
+    const int pix = U[i], y = pix / res, xx = pix - y * res;
+    double b = 0.0;
+    if (y > 0 && !mk[pix - res]) b += (double)d[pix - res];
+    if (y < res - 1 && !mk[pix + res]) b += (double)d[pix + res];
+    if (xx > 0 && !mk[pix - 1]) b += (double)d[pix - 1];
+    if (xx < res - 1 && !mk[pix + 1]) b += (double)d[pix + 1];
+    if (rhs_extra) b -= (double)rhs_extra[(size_t)e * R2 + pix];
+    return b;
+  };
+  // A v at unknown i: the own value from a register, the neighbours' read past the caches from the array v was published in
+  auto lap_at = [&](const double* v, double own, int2 ud, int2 lr) {
+    double a = 4.0 * own;
+    if (ud.x >= 0) a -= cg_get(v + ud.x);
+    if (ud.y >= 0) a -= cg_get(v + ud.y);
+    if (lr.x >= 0) a -= cg_get(v + lr.x);
+    if (lr.y >= 0) a -= cg_get(v + lr.y);
+    return a;
+  };
+  // an index the compiler cannot see through: the addresses of the loop's accesses are formed where they are used (a shift and an
+  // add per access, beside loads that go past the caches) instead of being hoisted out of the loop, where four unknowns x seven
+  // arrays of 64-bit addresses, kept alive across the replacement, spilled to scratch (116 .. 148 bytes per lane; now none)
+  auto cold_index = [](unsigned i) { asm volatile("" : "+v"(i)); return i; };
   double gamma_old = 1.0, alpha_old = 1.0;
-  int cur = 0, it = 0;
-  for (; it < max_iter; ++it) {
+  int cur = 0, it = 0, code = 0;
+  for (;; ++it) {
     double pg = 0.0, pd = 0.0;
 #pragma unroll
     for (int k = 0; k < CGM_EPT; ++k) { pg += rl[k] * rl[k]; pd += wl[k] * rl[k]; }
@@ -711,36 +745,86 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
     all_sum2(pg, pd, (it + 1) & 1, gamma, delta);     // (slots alternate: a workgroup still adding one cannot be overtaken by the next write to it)
     if (!alive) break;
     if (!(gamma > tol2 * bnorm)) break;
+    if (it >= max_iter) { code = CG_NOT_CONVERGED; break; }      // (gamma is the residual of iterate max_iter itself: one seam more than the cap)
     const double beta = it ? gamma / gamma_old : 0.0;
     const double alpha = it ? gamma / (delta - beta * gamma / alpha_old) : gamma / delta;
+    // BREAKDOWN GUARD.  A is positive definite, so in exact arithmetic the denominator is (p, A p) > 0; a step that is not
+    // positive and finite means the recurred delta has drifted off it (or carries a NaN).  Nothing of it reaches x: the system
+    // leaves with CG_BREAKDOWN and no disparity written (gamma, delta are identical in every workgroup: they all leave here).
+    if (!(alpha > 0.0 && alpha <= 1.7976931348623157e308)) { code = CG_BREAKDOWN; break; }
+    // RESIDUAL REPLACEMENT (Cools, Yetkin, Agullo, Giraud & Vanroose 2018, without their automatic criterion: a fixed period).
+    // r, w, s, z are carried by recurrence, each with its own rounding error, and nothing ties them back to x and p; from
+    // ~40 000 unknowns on (some 700 iterations of the classic recurrence) the drift of w - A r and s - A p makes the recurred
+    // delta useless: denominators turn negative and the solve takes 1.5 .. 20 x the classic iteration count or runs into the
+    // cap, at the same final accuracy.  So every CG_REPLACE-th iteration ends with   r = b - A x,  s = A p,  then  w = A r,
+    // z = A s   from the true x and p.  x and p are private otherwise; on these iterations they are also published.
+    const bool replace = (it + 1) % CG_REPLACE == 0;
     const double* wo = P[cur];
     double* wn = P[cur ^ 1];
 #pragma unroll
     for (int k = 0; k < CGM_EPT; ++k) {
-      const int i = i0 + (int)threadIdx.x + k * 1024;
-      if (i < i1) {
+      const unsigned i = cold_index((unsigned)i0 + threadIdx.x + k * 1024u);
+      if (i < (unsigned)i1) {
         const int2 ud = nud[i], lr = nlr[i];
-        double q = 4.0 * wl[k];
-        if (ud.x >= 0) q -= cg_get(wo + ud.x);
-        if (ud.y >= 0) q -= cg_get(wo + ud.y);
-        if (lr.x >= 0) q -= cg_get(wo + lr.x);
-        if (lr.y >= 0) q -= cg_get(wo + lr.y);
+        const double q = lap_at(wo, wl[k], ud, lr);
         zl[k] = q + beta * zl[k];
         sl[k] = wl[k] + beta * sl[k];
         const double pk = it ? rl[k] + beta * pv[i] : rl[k];
-        pv[i] = pk;
-        x[i] += alpha * pk;
+        const double xk = x[i] + alpha * pk;
         rl[k] -= alpha * sl[k];
         wl[k] -= alpha * zl[k];
-        cg_put(wn + i, wl[k]);
+        pv[i] = pk;
+        x[i] = xk;
+        if (replace) {                           // (after the plain stores: this thread's own plain loads keep seeing what they always saw)
+          cg_put(pv + i, pk);
+          cg_put(x + i, xk);
+          sl[k] = pk; zl[k] = xk;                // (p and x of this unknown, carried to the products below)
+        } else {
+          cg_put(wn + i, wl[k]);
+        }
+      }
+    }
+    if (replace) {
+      // three seams more than a plain iteration: (1) x and p of every workgroup visible, and nobody still reads wo;
+      // r = b - A x goes through wo, s = A p through wn; (2) both visible: w = A r, z = A s; (3) nobody still reads wn,
+      // which then takes the new w as on every other iteration.
+      if (!cg_seam<false>(sy, ++epoch)) { alive = false; break; }
+#pragma unroll
+      for (int k = 0; k < CGM_EPT; ++k) {
+        const unsigned i = cold_index((unsigned)i0 + threadIdx.x + k * 1024u);
+        if (i < (unsigned)i1) {
+          const int2 ud = nud[i], lr = nlr[i];
+          rl[k] = rhs_of(i) - lap_at(x, zl[k], ud, lr);
+          sl[k] = lap_at(pv, sl[k], ud, lr);
+          cg_put(P[cur] + i, rl[k]);
+          cg_put(wn + i, sl[k]);
+        }
+      }
+      if (!cg_seam<false>(sy, ++epoch)) { alive = false; break; }
+#pragma unroll
+      for (int k = 0; k < CGM_EPT; ++k) {
+        const unsigned i = cold_index((unsigned)i0 + threadIdx.x + k * 1024u);
+        if (i < (unsigned)i1) {
+          const int2 ud = nud[i], lr = nlr[i];
+          wl[k] = lap_at(wo, rl[k], ud, lr);
+          zl[k] = lap_at(wn, sl[k], ud, lr);
+        }
+      }
+      if (!cg_seam<false>(sy, ++epoch)) { alive = false; break; }
+#pragma unroll
+      for (int k = 0; k < CGM_EPT; ++k) {
+        const unsigned i = cold_index((unsigned)i0 + threadIdx.x + k * 1024u);
+        if (i < (unsigned)i1) cg_put(wn + i, wl[k]);
       }
     }
     gamma_old = gamma; alpha_old = alpha;
     cur ^= 1;
   }
-  if (!alive) { if (threadIdx.x == 0) atomicMin(&counts_out[e * count_stride + slot_it], -1); return; }
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += 1024) d[U[i]] = (float)x[i];
-  if (threadIdx.x == 0 && wg == 0) atomicMin(&counts_out[e * count_stride + slot_it], it);      // (a -1 of another workgroup stays)
+  if (!alive) { if (threadIdx.x == 0) atomicMin(&counts_out[e * count_stride + slot_it], CG_BARRIER_TIMEOUT); return; }
+  // not converged / broken down: the code instead of a count, and the disparity stays unwritten (all workgroups agree on it)
+  if (code == 0)
+    for (int i = i0 + (int)threadIdx.x; i < i1; i += 1024) d[U[i]] = (float)x[i];
+  if (threadIdx.x == 0 && wg == 0) atomicMin(&counts_out[e * count_stride + slot_it], code ? code : it);      // (a -1 of another workgroup stays, unless this is a code below it)
 }
 
 // cross-element binary dilation (scipy.ndimage.binary_dilation default structure, border 0)
@@ -798,6 +882,18 @@ extern "C" int dh_dbg_ellipse_offsets(int k, int32_t* xy, int cap, int* n_out) {
   const int n = dh::ellipse_offsets(k, tmp);
   for (int i = 0; i < n; ++i) { xy[2 * i] = tmp[i].x; xy[2 * i + 1] = tmp[i].y; }
   *n_out = n;
+  return DH_OK;
+}
+// test hooks (host only): the dispatch limits of the in-fill solvers {largest n solved on chip, largest n of the multi-workgroup
+// kernel, its workgroups per system}, and an iteration cap for the in-fill calls that follow (0 restores each call's own)
+extern "C" int dh_dbg_cg_limits(int* out3) {
+  DH_REQUIRE(out3, "bad arguments");
+  out3[0] = dh::CG_SLOTS * 1024; out3[1] = dh::CGM_WGS * dh::CGM_EPT * 1024; out3[2] = dh::CGM_WGS;
+  return DH_OK;
+}
+extern "C" int dh_dbg_cg_max_iter(int cap) {
+  DH_REQUIRE(cap >= 0, "bad arguments");
+  dh::g_cg_max_iter = cap;
   return DH_OK;
 }
 namespace dh {
@@ -977,10 +1073,10 @@ extern "C" int dh_reproject_object_edits(const float* depth, const float* bg_dep
   // register budget (65 536 unknowns) the single-workgroup kernel
   DH_CHECK_HIP(hipMemsetAsync(w.cgsync, 0, (size_t)K * sizeof(CgSync), st));
   hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, K), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
-                     w.vr, w.vp, w.vq, 20000, 1e-24, counts, (const float*)nullptr, cg_lds ? CG_SLOTS * 1024 : 0, w.owner,
+                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, cg_lds ? CG_SLOTS * 1024 : 0, w.owner,
                      reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P, w.cgsync);
   hipLaunchKernelGGL(k_cg_fill, dim3(K), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
-                     w.vr, w.vp, w.vq, 20000, 1e-24, counts, (const float*)nullptr, CGM_WGS * CGM_EPT * 1024, w.owner,
+                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CGM_WGS * CGM_EPT * 1024, w.owner,
                      reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P);
   DH_LAUNCH_CHECK();
   return DH_OK;
@@ -1040,8 +1136,8 @@ extern "C" int dh_laplacian_blend(const float* depth, const float* bg_depth, con
   compact(src, R2, 1, 0, unk, 0, counts + 2, 1, bc, st);
   DH_CHECK_HIP(hipMemsetAsync(cgs, 0, sizeof(CgSync), st));
   hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, 1), dim3(1024), 0, st, res, out, src, unk, counts, 4, 2, 3, vx, vr, vp, vq,
-                     50000, 1e-24, counts, (const float*)lap, CG_SLOTS * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2, cgs);
-  hipLaunchKernelGGL(k_cg_fill, dim3(1), dim3(1024), 0, st, res, out, src, unk, counts, 4, 2, 3, vx, vr, vp, vq, 50000,
+                     cg_cap(50000), 1e-24, counts, (const float*)lap, CG_SLOTS * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2, cgs);
+  hipLaunchKernelGGL(k_cg_fill, dim3(1), dim3(1024), 0, st, res, out, src, unk, counts, 4, 2, 3, vx, vr, vp, vq, cg_cap(50000),
                      1e-24, counts, (const float*)lap, CGM_WGS * CGM_EPT * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2);
   DH_LAUNCH_CHECK();
   return DH_OK;

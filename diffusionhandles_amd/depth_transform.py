@@ -218,12 +218,30 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
     return out
 
 
+INFILL_BARRIER_TIMEOUT, INFILL_NOT_CONVERGED, INFILL_BREAKDOWN = -1, -2, -3      # counts[..., 3] < 0 (geometry.hip)
+
+
+class InfillNotConverged(RuntimeError):
+    """The harmonic in-fill's CG left without reaching its tolerance: at the iteration cap, or on a breakdown."""
+
+
 def _check_infill(iterations):
-    """counts[..., 3] = CG iterations of the harmonic in-fill; -1 = the multi-workgroup solver's bounded grid barrier ran out
-    (its workgroups were not co-resident: CU masks, another process holding the chip) -- an error, never a hang."""
-    if bool((iterations < 0).any()):
+    """counts[..., 3] = CG iterations of the harmonic in-fill.  Negative = the result is not valid, an error and never a hang
+    or a silently unconverged field: -1 = the multi-workgroup solver's bounded grid barrier ran out (its workgroups were not
+    co-resident: CU masks, another process holding the chip); -2 = a solver reached its iteration cap with the residual still
+    above the tolerance; -3 = the pipelined recurrence broke down (a step length that is not positive and finite)."""
+    if not bool((iterations < 0).any()):
+        return
+    if bool((iterations == INFILL_BARRIER_TIMEOUT).any()):
         raise RuntimeError("harmonic in-fill: the multi-workgroup CG's grid barrier timed out (workgroups not co-resident); "
                            "the result is not valid")
+    if bool((iterations == INFILL_NOT_CONVERGED).any()):
+        raise InfillNotConverged("harmonic in-fill: CG reached its iteration cap before the residual met the tolerance; "
+                                 "the result is not valid")
+    if bool((iterations == INFILL_BREAKDOWN).any()):
+        raise InfillNotConverged("harmonic in-fill: the pipelined CG broke down (step length not positive and finite); "
+                                 "the result is not valid")
+    raise RuntimeError(f"harmonic in-fill: unknown failure code {int(iterations.min())}; the result is not valid")
 
 
 def transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
@@ -331,10 +349,11 @@ def transform_depth(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_ax
     raise ValueError(f"Unknown depth transform mode '{depth_transform_mode}'.")
 
 
-def laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15):
+def laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15, return_iterations=False):
     """set_foreground's background-depth update (diffusion_handles.py:90-111): `depth` everywhere except
     inside the dilated foreground mask, where the background depth's Laplacian is integrated from the
-    surrounding depth values.  [1,1,H,W] tensors in, [1,1,H,W] float32 out (on depth.device)."""
+    surrounding depth values.  [1,1,H,W] tensors in, [1,1,H,W] float32 out (on depth.device); with return_iterations also
+    the CG iteration count of the solve."""
     res = depth.shape[-1]
     if depth.shape[-2] != res:
         raise RuntimeError("square depth maps only")
@@ -351,5 +370,8 @@ def laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15):
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     _lib.check(L.dh_laplacian_blend(_lib.ptr(d), _lib.ptr(bg), _lib.ptr(m), res, int(dilate_iterations), _lib.ptr(out),
                                     _lib.ptr(counts), _lib.ptr(ws), nbytes.value, _lib.stream_ptr()), "dh_laplacian_blend")
-    _check_infill(counts[3:4].cpu())
+    its = counts[3:4].cpu()
+    _check_infill(its)
+    if return_iterations:
+        return out[None, None].to(out_dev), int(its[0])
     return out[None, None].to(out_dev)

@@ -348,17 +348,9 @@ static bool carve_planned(Arena& a, int C, int grid, PlannedWs& w) {
   return a.ok();
 }
 
-// one workgroup per target cell: its source list (one entry per pixel pair: ~8x8 pixels share a cell pair) becomes
-// (distinct source cell, multiplicity) in ascending cell order, through an LDS histogram over the grid's cells
-__global__ void __launch_bounds__(256) k_dedupe_sources(const int* off, int* src, int* mult, int* ucnt, int G2) {
-  extern __shared__ int hist[];          // [G2] counts, then [256] scan scratch
-  int* scan = hist + G2;
-  const int t = blockIdx.x, b = off[t], e = off[t + 1];
-  if (b == e) { if (threadIdx.x == 0) ucnt[t] = 0; return; }
-  for (int c = threadIdx.x; c < G2; c += blockDim.x) hist[c] = 0;
-  __syncthreads();
-  for (int k = b + threadIdx.x; k < e; k += blockDim.x) atomicAdd(&hist[src[k]], 1);
-  __syncthreads();
+// The distinct cells of the workgroup's LDS histogram, in ascending order, with their counts -> src / mult [pos0 ..), and m -> obj
+// there when the plan keeps an object per entry.  Returns how many, in every thread, behind a barrier: hist and scan are free.
+__device__ __forceinline__ int emit_distinct(const int* hist, int* scan, int G2, int pos0, int* src, int* mult, uint8_t* obj, int m) {
   const int per = (G2 + blockDim.x - 1) / blockDim.x, c0 = threadIdx.x * per, c1 = min(c0 + per, G2);
   int mine = 0;
   for (int c = c0; c < c1; ++c) mine += hist[c] != 0;
@@ -370,10 +362,30 @@ __global__ void __launch_bounds__(256) k_dedupe_sources(const int* off, int* src
     scan[threadIdx.x] += v;
     __syncthreads();
   }
-  int pos = b + scan[threadIdx.x] - mine;
+  int pos = pos0 + scan[threadIdx.x] - mine;
   for (int c = c0; c < c1; ++c)
-    if (hist[c]) { src[pos] = c; mult[pos] = hist[c]; ++pos; }
-  if (threadIdx.x == blockDim.x - 1) ucnt[t] = scan[threadIdx.x];
+    if (hist[c]) {
+      src[pos] = c; mult[pos] = hist[c];
+      if (obj) obj[pos] = (uint8_t)m;
+      ++pos;
+    }
+  const int n = scan[blockDim.x - 1];
+  __syncthreads();
+  return n;
+}
+
+// one workgroup per target cell: its source list (one entry per pixel pair: ~8x8 pixels share a cell pair) becomes
+// (distinct source cell, multiplicity) in ascending cell order, through an LDS histogram over the grid's cells
+__global__ void __launch_bounds__(256) k_dedupe_sources(const int* off, int* src, int* mult, int* ucnt, int G2) {
+  extern __shared__ int hist[];          // [G2] counts, then [256] scan scratch
+  const int t = blockIdx.x, b = off[t], e = off[t + 1];
+  if (b == e) { if (threadIdx.x == 0) ucnt[t] = 0; return; }
+  for (int c = threadIdx.x; c < G2; c += blockDim.x) hist[c] = 0;
+  __syncthreads();
+  for (int k = b + threadIdx.x; k < e; k += blockDim.x) atomicAdd(&hist[src[k]], 1);
+  __syncthreads();
+  const int n = emit_distinct(hist, hist + G2, G2, b, src, mult, nullptr, 0);
+  if (threadIdx.x == 0) ucnt[t] = n;
 }
 
 __global__ void k_flag_cells(const int* list, int n, uint8_t* flag) {
@@ -518,10 +530,8 @@ __global__ void k_fill_obj(const int* pairs, const uint8_t* pair_obj, int n, int
 __global__ void __launch_bounds__(256) k_dedupe_sources_obj(const int* off, const int* raw, int* src, int* mult, uint8_t* obj,
                                                             int* ucnt, int G2, int M) {
   extern __shared__ int hist[];          // [G2] counts, then [256] scan scratch
-  int* scan = hist + G2;
   const int t = blockIdx.x, b = off[t], e = off[t + 1];
   if (b == e) { if (threadIdx.x == 0) ucnt[t] = 0; return; }
-  const int per = (G2 + blockDim.x - 1) / blockDim.x, c0 = threadIdx.x * per, c1 = min(c0 + per, G2);
   int base = b;
   for (int m = 0; m < M; ++m) {
     for (int c = threadIdx.x; c < G2; c += blockDim.x) hist[c] = 0;
@@ -532,21 +542,7 @@ __global__ void __launch_bounds__(256) k_dedupe_sources_obj(const int* off, cons
       if ((int)(key >> 24) == m && c < G2) atomicAdd(&hist[c], 1);
     }
     __syncthreads();
-    int mine = 0;
-    for (int c = c0; c < c1; ++c) mine += hist[c] != 0;
-    scan[threadIdx.x] = mine;
-    __syncthreads();
-    for (int o = 1; o < (int)blockDim.x; o <<= 1) {
-      const int v = (int)threadIdx.x >= o ? scan[threadIdx.x - o] : 0;
-      __syncthreads();
-      scan[threadIdx.x] += v;
-      __syncthreads();
-    }
-    int pos = base + scan[threadIdx.x] - mine;
-    for (int c = c0; c < c1; ++c)
-      if (hist[c]) { src[pos] = c; mult[pos] = hist[c]; obj[pos] = (uint8_t)m; ++pos; }
-    base += scan[blockDim.x - 1];
-    __syncthreads();                     // hist and scan are reused by the next pass
+    base += emit_distinct(hist, hist + G2, G2, base, src, mult, obj, m);
   }
   if (threadIdx.x == 0) ucnt[t] = base - b;
 }
@@ -685,6 +681,38 @@ extern "C" int dh_energy_fwd_bwd(const void* cur, const void* orig, int dtype, i
   return DH_OK;
 }
 
+// ---- planned path, host side ------------------------------------------------------------------------------------------------
+// One routine per job, whatever the entry: build_plan (both plan builds), fill_item (every derived constant of an item, for
+// single and batched calls alike -- item e of a batch is bit-identical to its single call because both rows come from here),
+// run_planned_single and run_planned_batch (the launches).  `who` is the entry's name: error texts name the entry, not a helper.
+static int refuse(const char* who, const char* msg) {
+  set_error(std::string(who) + ": " + msg);
+  return DH_ERR_ARG;
+}
+static int launch_status(const char* who) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return DH_OK;
+  set_error(std::string(who) + " launch: " + hipGetErrorString(e));
+  return DH_ERR_HIP;
+}
+
+// f(Tag<T>) / f(Tag<T>, Tag<TG>) with the storage types of the activations (16-bit) and of the gradient
+template <class T>
+struct Tag { using type = T; };
+template <class F>
+static void with_dtype(int dtype, F&& f) {
+  if (dtype == DH_DTYPE_F16) f(Tag<f16>{});
+  else f(Tag<bf16>{});
+}
+template <class F>
+static void with_dtypes(int dtype, int grad_dtype, F&& f) {
+  with_dtype(dtype, [&](auto t) {
+    if (grad_dtype == DH_DTYPE_F16) f(t, Tag<f16>{});
+    else if (grad_dtype == DH_DTYPE_BF16) f(t, Tag<bf16>{});
+    else f(t, Tag<float>{});
+  });
+}
+
 extern "C" int dh_energy_plan_bytes(int grid, int n_pairs, size_t* bytes) {
   DH_REQUIRE(grid >= 1 && n_pairs >= 0 && bytes, "bad arguments");
   Arena a(nullptr, (size_t)-1);
@@ -694,174 +722,6 @@ extern "C" int dh_energy_plan_bytes(int grid, int n_pairs, size_t* bytes) {
   return DH_OK;
 }
 
-extern "C" int dh_energy_plan_build(const int32_t* pairs, int n_pairs, const int32_t* bg_trans, int n_bg_trans, int grid,
-                                    void* plan, size_t plan_bytes, void* stream) {
-  DH_REQUIRE(plan && grid >= 1 && n_pairs >= 0 && n_bg_trans >= 0, "bad arguments");
-  DH_REQUIRE((n_pairs == 0 || pairs) && (n_bg_trans == 0 || bg_trans), "null list");
-  hipStream_t st = (hipStream_t)stream;
-  const int G2 = grid * grid;
-  Arena a(plan, plan_bytes);
-  EnergyPlan p;
-  DH_REQUIRE(carve_plan(a, grid, n_pairs, p), "plan buffer too small");
-  DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
-  DH_CHECK_HIP(hipMemsetAsync(p.bgflag, 0, G2, st));
-  if (n_pairs > 0) hipLaunchKernelGGL(k_hist, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, p.cnt, p.w1, p.w2);
-  hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, st, p.cnt, G2, p.off, p.cursor);
-  if (n_pairs > 0) hipLaunchKernelGGL(k_fill, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, p.cursor, p.src);
-  if (n_pairs > 0)
-    hipLaunchKernelGGL(k_dedupe_sources, dim3(G2), dim3(256), (size_t)(G2 + 256) * sizeof(int), st, p.off, p.src, p.mult, p.cnt, G2);
-  else
-    DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
-  if (n_bg_trans > 0) hipLaunchKernelGGL(k_flag_cells, dim3(cdiv(n_bg_trans, 256)), dim3(256), 0, st, bg_trans, n_bg_trans, p.bgflag);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-extern "C" int dh_energy_planned_workspace_bytes(int C, int grid, size_t* bytes) {
-  DH_REQUIRE(C >= 1 && grid >= 1 && bytes, "bad arguments");
-  Arena a(nullptr, (size_t)-1);
-  PlannedWs w;
-  carve_planned(a, C, grid, w);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-template <class T, class TG>
-static void launch_energy_grad(const void* orig, const void* cur, const EnergyPlan& p, const PlannedWs& w, int C, int G2,
-                               float coef_fg, float coef_bg, int use_bg, float scale, void* grad, int nblocks,
-                               hipStream_t st, int n1, int n2) {
-  hipLaunchKernelGGL((k_energy_grad<T, TG>), dim3(nblocks), dim3(256), 0, st, (const T*)orig, (const T*)cur, p.off, p.cnt,
-                     p.src, p.mult, p.bgflag, w.partq, n1, n2, C, G2, coef_fg, coef_bg, use_bg, scale, (TG*)grad, w.fg_part, w.bg_part);
-}
-
-extern "C" int dh_energy_fwd_bwd_planned(const void* cur, const void* orig, int dtype, int C, int grid, const void* plan,
-                                         size_t plan_bytes, int n_pairs, const int32_t* bg_orig, int n_bg_orig,
-                                         const int32_t* bg_trans, int n_bg_trans, float fg_w, float bg_w, float grad_scale,
-                                         float* loss_out, void* grad, int grad_dtype, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
-  DH_REQUIRE(cur && orig && grad && plan && workspace, "null pointer");
-  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
-  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
-  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1 && n_pairs >= 0, "bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  const int G2 = grid * grid;
-  Arena ap(const_cast<void*>(plan), plan_bytes);
-  EnergyPlan p;
-  DH_REQUIRE(carve_plan(ap, grid, n_pairs, p), "plan buffer too small");
-  Arena aw(workspace, workspace_bytes);
-  PlannedWs w;
-  DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
-
-  const float fg_norm = n_pairs > 0 ? 1.f / ((float)C * (float)n_pairs) : 0.f;
-  float bg_norm = 0.f, coef_bg = 0.f;
-  int use_bg = 0;
-  if (n_bg_orig > 0 && n_bg_trans > 0) {
-    DH_REQUIRE(bg_orig && bg_trans, "null bg list");
-    if (dtype == DH_DTYPE_F16)
-      hipLaunchKernelGGL((k_colsum_q<f16>), dim3(cdiv(C, 64), 4, 2), dim3(8 * CQ_SL), 0, st, (const f16*)orig, bg_orig, n_bg_orig,
-                         (const f16*)cur, bg_trans, n_bg_trans, C, w.partq);
-    else
-      hipLaunchKernelGGL((k_colsum_q<bf16>), dim3(cdiv(C, 64), 4, 2), dim3(8 * CQ_SL), 0, st, (const bf16*)orig, bg_orig, n_bg_orig,
-                         (const bf16*)cur, bg_trans, n_bg_trans, C, w.partq);
-    bg_norm = 1.f / (float)C;
-    coef_bg = bg_w * bg_norm / (float)n_bg_trans;
-    use_bg = 1;
-  }
-  const int cpb = 256 / (C / 8);
-  const int nblocks = cdiv(G2, cpb);
-  const float coef_fg = fg_w * fg_norm;
-#define DH_EG(T_)                                                                                                          \
-  do {                                                                                                                     \
-    if (grad_dtype == DH_DTYPE_F16) launch_energy_grad<T_, f16>(orig, cur, p, w, C, G2, coef_fg, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans);        \
-    else if (grad_dtype == DH_DTYPE_BF16) launch_energy_grad<T_, bf16>(orig, cur, p, w, C, G2, coef_fg, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans); \
-    else launch_energy_grad<T_, float>(orig, cur, p, w, C, G2, coef_fg, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans);    \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_EG(f16);
-  else DH_EG(bf16);
-#undef DH_EG
-  if (loss_out)
-    hipLaunchKernelGGL(k_final_loss, dim3(1), dim3(256), 0, st, w.fg_part, n_pairs > 0 ? nblocks : 0, fg_norm, w.bg_part,
-                       use_bg ? 1 : 0, bg_norm, fg_w, bg_w, loss_out);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-extern "C" int dh_energy_planned_batch_workspace_bytes(int C, int grid, int n_items, size_t* bytes) {
-  DH_REQUIRE(C >= 1 && grid >= 1 && bytes, "bad arguments");
-  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items");
-  Arena a(nullptr, (size_t)-1);
-  PlannedWs w;
-  for (int e = 0; e < n_items; ++e) carve_planned(a, C, grid, w);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-extern "C" int dh_energy_fwd_bwd_planned_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
-                                               int grad_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  DH_REQUIRE(items && workspace, "null pointer");
-  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items (larger batches are not split)");
-  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
-  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
-  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1, "bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  const int G2 = grid * grid;
-  const int cpb = 256 / (C / 8);
-  const int nblocks = cdiv(G2, cpb);
-  Arena aw(workspace, workspace_bytes);
-  EnergyBatch tab;
-  bool any_bg = false, any_loss = false;
-  for (int e = 0; e < n_items; ++e) {
-    const dh_energy_item& in = items[e];
-    EnergyItem& it = tab.it[e];
-    DH_REQUIRE(in.cur && in.orig && in.grad && in.plan, "null pointer in an item");
-    DH_REQUIRE(in.n_pairs >= 0, "bad sizes");
-    Arena ap(const_cast<void*>(in.plan), in.plan_bytes);
-    EnergyPlan p;
-    DH_REQUIRE(carve_plan(ap, grid, in.n_pairs, p), "plan buffer too small");
-    PlannedWs w;
-    DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
-    it.orig = in.orig; it.cur = in.cur;
-    it.off = p.off; it.ucnt = p.cnt; it.src = p.src; it.mult = p.mult; it.bgflag = p.bgflag;
-    it.list1 = in.bg_orig; it.list2 = in.bg_trans;
-    it.partq = w.partq; it.grad = in.grad; it.loss_part = w.fg_part; it.bg_loss = w.bg_part; it.loss_out = in.loss_out;
-    it.n1 = in.n_bg_orig; it.n2 = in.n_bg_trans;
-    it.fg_norm = in.n_pairs > 0 ? 1.f / ((float)C * (float)in.n_pairs) : 0.f;
-    it.bg_norm = 0.f; it.coef_bg = 0.f; it.use_bg = 0;
-    if (in.n_bg_orig > 0 && in.n_bg_trans > 0) {
-      DH_REQUIRE(in.bg_orig && in.bg_trans, "null bg list");
-      it.bg_norm = 1.f / (float)C;
-      it.coef_bg = in.bg_w * it.bg_norm / (float)in.n_bg_trans;
-      it.use_bg = 1;
-      any_bg = true;
-    }
-    it.coef_fg = in.fg_w * it.fg_norm;
-    it.scale = in.grad_scale;
-    it.n_fg_part = in.n_pairs > 0 ? nblocks : 0;
-    it.fg_w = in.fg_w; it.bg_w = in.bg_w;
-    any_loss = any_loss || in.loss_out != nullptr;
-  }
-  for (int e = n_items; e < ENERGY_MAX_ITEMS; ++e) tab.it[e] = tab.it[0];      // (never indexed: defined kernel arguments)
-  if (any_bg) {
-    if (dtype == DH_DTYPE_F16)
-      hipLaunchKernelGGL((k_colsum_q_batch<f16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
-    else
-      hipLaunchKernelGGL((k_colsum_q_batch<bf16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
-  }
-#define DH_EGB(T_)                                                                                                             \
-  do {                                                                                                                         \
-    if (grad_dtype == DH_DTYPE_F16) hipLaunchKernelGGL((k_energy_grad_batch<T_, f16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, C, G2);        \
-    else if (grad_dtype == DH_DTYPE_BF16) hipLaunchKernelGGL((k_energy_grad_batch<T_, bf16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, C, G2); \
-    else hipLaunchKernelGGL((k_energy_grad_batch<T_, float>), dim3(nblocks, n_items), dim3(256), 0, st, tab, C, G2);           \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_EGB(f16);
-  else DH_EGB(bf16);
-#undef DH_EGB
-  if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-// ---- a weight per object --------------------------------------------------------------------------------------------------
 extern "C" int dh_energy_plan_objects_bytes(int grid, int n_pairs, size_t* bytes) {
   DH_REQUIRE(grid >= 1 && n_pairs >= 0 && bytes, "bad arguments");
   Arena a(nullptr, (size_t)-1);
@@ -869,6 +729,41 @@ extern "C" int dh_energy_plan_objects_bytes(int grid, int n_pairs, size_t* bytes
   carve_plan_obj(a, grid, n_pairs, p);
   *bytes = a.off + 256;
   return DH_OK;
+}
+
+// h: the object header of a weighted plan (then pair_obj and n_objects are read), null for a plain one
+static int build_plan(const char* who, const int32_t* pairs, const uint8_t* pair_obj, int n_pairs, const int32_t* bg_trans,
+                      int n_bg_trans, int grid, const ObjHeader* h, int n_objects, void* plan, size_t plan_bytes, hipStream_t st) {
+  const int G2 = grid * grid;
+  const size_t dedupe_lds = (size_t)(G2 + 256) * sizeof(int);
+  Arena a(plan, plan_bytes);
+  EnergyPlanObj po;
+  if (!(h ? carve_plan_obj(a, grid, n_pairs, po) : carve_plan(a, grid, n_pairs, po.base))) return refuse(who, "plan buffer too small");
+  const EnergyPlan& p = po.base;
+  DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
+  DH_CHECK_HIP(hipMemsetAsync(p.bgflag, 0, G2, st));
+  if (h) hipLaunchKernelGGL(k_store_obj_header, dim3(1), dim3(64), 0, st, *h, po.objp);
+  if (n_pairs > 0) hipLaunchKernelGGL(k_hist, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, p.cnt, p.w1, p.w2);
+  hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, st, p.cnt, G2, p.off, p.cursor);
+  if (n_pairs <= 0) {
+    DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
+  } else if (h) {
+    hipLaunchKernelGGL(k_fill_obj, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, pair_obj, n_pairs, p.cursor, po.raw);
+    hipLaunchKernelGGL(k_dedupe_sources_obj, dim3(G2), dim3(256), dedupe_lds, st, p.off, po.raw, p.src, p.mult,
+                       po.objp + OBJ_HEADER, p.cnt, G2, n_objects);
+  } else {
+    hipLaunchKernelGGL(k_fill, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, p.cursor, p.src);
+    hipLaunchKernelGGL(k_dedupe_sources, dim3(G2), dim3(256), dedupe_lds, st, p.off, p.src, p.mult, p.cnt, G2);
+  }
+  if (n_bg_trans > 0) hipLaunchKernelGGL(k_flag_cells, dim3(cdiv(n_bg_trans, 256)), dim3(256), 0, st, bg_trans, n_bg_trans, p.bgflag);
+  return launch_status(who);
+}
+
+extern "C" int dh_energy_plan_build(const int32_t* pairs, int n_pairs, const int32_t* bg_trans, int n_bg_trans, int grid,
+                                    void* plan, size_t plan_bytes, void* stream) {
+  DH_REQUIRE(plan && grid >= 1 && n_pairs >= 0 && n_bg_trans >= 0, "bad arguments");
+  DH_REQUIRE((n_pairs == 0 || pairs) && (n_bg_trans == 0 || bg_trans), "null list");
+  return build_plan(__func__, pairs, nullptr, n_pairs, bg_trans, n_bg_trans, grid, nullptr, 0, plan, plan_bytes, (hipStream_t)stream);
 }
 
 extern "C" int dh_energy_plan_build_objects(const int32_t* pairs, const uint8_t* pair_obj, int n_pairs, const int32_t* bg_trans,
@@ -897,87 +792,25 @@ extern "C" int dh_energy_plan_build_objects(const int32_t* pairs, const uint8_t*
     h.n[m] = live ? counts[m] : 0;
     h.lossw[m] = live ? om / (double)counts[m] : 0.0;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const int G2 = grid * grid;
-  Arena a(plan, plan_bytes);
-  EnergyPlanObj po;
-  DH_REQUIRE(carve_plan_obj(a, grid, n_pairs, po), "plan buffer too small");
-  const EnergyPlan& p = po.base;
-  DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
-  DH_CHECK_HIP(hipMemsetAsync(p.bgflag, 0, G2, st));
-  hipLaunchKernelGGL(k_store_obj_header, dim3(1), dim3(64), 0, st, h, po.objp);
-  if (n_pairs > 0) hipLaunchKernelGGL(k_hist, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, p.cnt, p.w1, p.w2);
-  hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, st, p.cnt, G2, p.off, p.cursor);
-  if (n_pairs > 0) {
-    hipLaunchKernelGGL(k_fill_obj, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pairs, pair_obj, n_pairs, p.cursor, po.raw);
-    hipLaunchKernelGGL(k_dedupe_sources_obj, dim3(G2), dim3(256), (size_t)(G2 + 256) * sizeof(int), st, p.off, po.raw, p.src, p.mult,
-                       po.objp + OBJ_HEADER, p.cnt, G2, n_objects);
-  } else {
-    DH_CHECK_HIP(hipMemsetAsync(p.cnt, 0, (G2 + 1) * sizeof(int), st));
-  }
-  if (n_bg_trans > 0) hipLaunchKernelGGL(k_flag_cells, dim3(cdiv(n_bg_trans, 256)), dim3(256), 0, st, bg_trans, n_bg_trans, p.bgflag);
-  DH_LAUNCH_CHECK();
+  return build_plan(__func__, pairs, pair_obj, n_pairs, bg_trans, n_bg_trans, grid, &h, n_objects, plan, plan_bytes, (hipStream_t)stream);
+}
+
+extern "C" int dh_energy_planned_workspace_bytes(int C, int grid, size_t* bytes) {
+  DH_REQUIRE(C >= 1 && grid >= 1 && bytes, "bad arguments");
+  Arena a(nullptr, (size_t)-1);
+  PlannedWs w;
+  carve_planned(a, C, grid, w);
+  *bytes = a.off + 256;
   return DH_OK;
 }
 
-template <class T, class TG>
-static void launch_energy_grad_obj(const void* orig, const void* cur, const EnergyPlanObj& po, const PlannedWs& w, int C, int G2,
-                                   float fg_w, float coef_bg, int use_bg, float scale, void* grad, int nblocks, hipStream_t st,
-                                   int n1, int n2) {
-  const EnergyPlan& p = po.base;
-  hipLaunchKernelGGL((k_energy_grad_obj<T, TG>), dim3(nblocks), dim3(256), 0, st, (const T*)orig, (const T*)cur, p.off, p.cnt,
-                     p.src, p.mult, po.objp, p.bgflag, w.partq, n1, n2, C, G2, fg_w, coef_bg, use_bg, scale, (TG*)grad, w.fg_part,
-                     w.bg_part);
-}
-
-extern "C" int dh_energy_fwd_bwd_planned_objects(const void* cur, const void* orig, int dtype, int C, int grid, const void* plan,
-                                                 size_t plan_bytes, int n_pairs, const int32_t* bg_orig, int n_bg_orig,
-                                                 const int32_t* bg_trans, int n_bg_trans, float fg_w, float bg_w,
-                                                 float grad_scale, float* loss_out, void* grad, int grad_dtype, void* workspace,
-                                                 size_t workspace_bytes, void* stream) {
-  DH_REQUIRE(cur && orig && grad && plan && workspace, "null pointer");
-  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
-  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
-  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1 && n_pairs >= 0, "bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  const int G2 = grid * grid;
-  Arena ap(const_cast<void*>(plan), plan_bytes);
-  EnergyPlanObj po;
-  DH_REQUIRE(carve_plan_obj(ap, grid, n_pairs, po), "plan buffer too small");
-  Arena aw(workspace, workspace_bytes);
+extern "C" int dh_energy_planned_batch_workspace_bytes(int C, int grid, int n_items, size_t* bytes) {
+  DH_REQUIRE(C >= 1 && grid >= 1 && bytes, "bad arguments");
+  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items");
+  Arena a(nullptr, (size_t)-1);
   PlannedWs w;
-  DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
-
-  const float fg_norm = n_pairs > 0 ? 1.f / (float)C : 0.f;      // the loss partials carry omega_m / N_m
-  float bg_norm = 0.f, coef_bg = 0.f;
-  int use_bg = 0;
-  if (n_bg_orig > 0 && n_bg_trans > 0) {
-    DH_REQUIRE(bg_orig && bg_trans, "null bg list");
-    if (dtype == DH_DTYPE_F16)
-      hipLaunchKernelGGL((k_colsum_q<f16>), dim3(cdiv(C, 64), 4, 2), dim3(8 * CQ_SL), 0, st, (const f16*)orig, bg_orig, n_bg_orig,
-                         (const f16*)cur, bg_trans, n_bg_trans, C, w.partq);
-    else
-      hipLaunchKernelGGL((k_colsum_q<bf16>), dim3(cdiv(C, 64), 4, 2), dim3(8 * CQ_SL), 0, st, (const bf16*)orig, bg_orig, n_bg_orig,
-                         (const bf16*)cur, bg_trans, n_bg_trans, C, w.partq);
-    bg_norm = 1.f / (float)C;
-    coef_bg = bg_w * bg_norm / (float)n_bg_trans;
-    use_bg = 1;
-  }
-  const int cpb = 256 / (C / 8);
-  const int nblocks = cdiv(G2, cpb);
-#define DH_EGO(T_)                                                                                                         \
-  do {                                                                                                                     \
-    if (grad_dtype == DH_DTYPE_F16) launch_energy_grad_obj<T_, f16>(orig, cur, po, w, C, G2, fg_w, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans);        \
-    else if (grad_dtype == DH_DTYPE_BF16) launch_energy_grad_obj<T_, bf16>(orig, cur, po, w, C, G2, fg_w, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans); \
-    else launch_energy_grad_obj<T_, float>(orig, cur, po, w, C, G2, fg_w, coef_bg, use_bg, grad_scale, grad, nblocks, st, n_bg_orig, n_bg_trans);    \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_EGO(f16);
-  else DH_EGO(bf16);
-#undef DH_EGO
-  if (loss_out)
-    hipLaunchKernelGGL(k_final_loss, dim3(1), dim3(256), 0, st, w.fg_part, n_pairs > 0 ? nblocks : 0, fg_norm, w.bg_part,
-                       use_bg ? 1 : 0, bg_norm, fg_w, bg_w, loss_out);
-  DH_LAUNCH_CHECK();
+  for (int e = 0; e < n_items; ++e) carve_planned(a, C, grid, w);
+  *bytes = a.off + 256;
   return DH_OK;
 }
 
@@ -985,147 +818,159 @@ extern "C" int dh_energy_planned_objects_batch_workspace_bytes(int C, int grid, 
   return dh_energy_planned_batch_workspace_bytes(C, grid, n_items, bytes);
 }
 
-extern "C" int dh_energy_fwd_bwd_planned_objects_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
-                                                       int grad_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  DH_REQUIRE(items && workspace, "null pointer");
-  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items (larger batches are not split)");
-  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
-  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
-  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1, "bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  const int G2 = grid * grid;
-  const int cpb = 256 / (C / 8);
-  const int nblocks = cdiv(G2, cpb);
-  Arena aw(workspace, workspace_bytes);
-  EnergyBatch tab;
-  EnergyObjPtrs ot;
-  bool any_bg = false, any_loss = false;
-  for (int e = 0; e < n_items; ++e) {
-    const dh_energy_item& in = items[e];
-    EnergyItem& it = tab.it[e];
-    DH_REQUIRE(in.cur && in.orig && in.grad && in.plan, "null pointer in an item");
-    DH_REQUIRE(in.n_pairs >= 0, "bad sizes");
-    Arena ap(const_cast<void*>(in.plan), in.plan_bytes);
-    EnergyPlanObj po;
-    DH_REQUIRE(carve_plan_obj(ap, grid, in.n_pairs, po), "plan buffer too small");
-    const EnergyPlan& p = po.base;
-    PlannedWs w;
-    DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
-    ot.p[e] = po.objp;
-    it.orig = in.orig; it.cur = in.cur;
-    it.off = p.off; it.ucnt = p.cnt; it.src = p.src; it.mult = p.mult; it.bgflag = p.bgflag;
-    it.list1 = in.bg_orig; it.list2 = in.bg_trans;
-    it.partq = w.partq; it.grad = in.grad; it.loss_part = w.fg_part; it.bg_loss = w.bg_part; it.loss_out = in.loss_out;
-    it.n1 = in.n_bg_orig; it.n2 = in.n_bg_trans;
-    it.fg_norm = in.n_pairs > 0 ? 1.f / (float)C : 0.f;
-    it.bg_norm = 0.f; it.coef_bg = 0.f; it.use_bg = 0;
-    if (in.n_bg_orig > 0 && in.n_bg_trans > 0) {
-      DH_REQUIRE(in.bg_orig && in.bg_trans, "null bg list");
-      it.bg_norm = 1.f / (float)C;
-      it.coef_bg = in.bg_w * it.bg_norm / (float)in.n_bg_trans;
-      it.use_bg = 1;
-      any_bg = true;
-    }
-    it.coef_fg = in.fg_w;                // the weighted kernel forms fg_w * omega_m / (C N_m) itself
-    it.scale = in.grad_scale;
-    it.n_fg_part = in.n_pairs > 0 ? nblocks : 0;
-    it.fg_w = in.fg_w; it.bg_w = in.bg_w;
-    any_loss = any_loss || in.loss_out != nullptr;
-  }
-  for (int e = n_items; e < ENERGY_MAX_ITEMS; ++e) { tab.it[e] = tab.it[0]; ot.p[e] = ot.p[0]; }      // (never indexed)
-  if (any_bg) {
-    if (dtype == DH_DTYPE_F16)
-      hipLaunchKernelGGL((k_colsum_q_batch<f16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
-    else
-      hipLaunchKernelGGL((k_colsum_q_batch<bf16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
-  }
-#define DH_EGOB(T_)                                                                                                            \
-  do {                                                                                                                         \
-    if (grad_dtype == DH_DTYPE_F16) hipLaunchKernelGGL((k_energy_grad_obj_batch<T_, f16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2);        \
-    else if (grad_dtype == DH_DTYPE_BF16) hipLaunchKernelGGL((k_energy_grad_obj_batch<T_, bf16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2); \
-    else hipLaunchKernelGGL((k_energy_grad_obj_batch<T_, float>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2);   \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_EGOB(f16);
-  else DH_EGOB(bf16);
-#undef DH_EGOB
-  if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
-  DH_LAUNCH_CHECK();
+// workgroups of a gradient launch over one item: 256 / (C / 8) cells each
+static int grad_blocks(int C, int grid) { return cdiv(grid * grid, 256 / (C / 8)); }
+
+// Checks one item, carves its plan (by its kind; small_plan: the refusal of a buffer that is too small for that kind) and its
+// slice of the workspace, and fills its row and its object-block pointer (null: unweighted).  No launch happens here.
+static int fill_item(const char* who, const dh_energy_item& in, bool weighted, const char* small_plan, int C, int grid, int nblocks,
+                     Arena& aw, EnergyItem& it, const uint8_t*& objp) {
+  if (!(in.cur && in.orig && in.grad && in.plan)) return refuse(who, "null pointer in an item");
+  if (in.n_pairs < 0) return refuse(who, "bad sizes");
+  Arena ap(const_cast<void*>(in.plan), in.plan_bytes);
+  EnergyPlanObj po;
+  po.objp = nullptr;
+  if (!(weighted ? carve_plan_obj(ap, grid, in.n_pairs, po) : carve_plan(ap, grid, in.n_pairs, po.base))) return refuse(who, small_plan);
+  const EnergyPlan& p = po.base;
+  PlannedWs w;
+  if (!carve_planned(aw, C, grid, w)) return refuse(who, "workspace too small");
+  const bool bg = in.n_bg_orig > 0 && in.n_bg_trans > 0;
+  if (bg && !(in.bg_orig && in.bg_trans)) return refuse(who, "null bg list");
+  objp = po.objp;
+  it.orig = in.orig; it.cur = in.cur;
+  it.off = p.off; it.ucnt = p.cnt; it.src = p.src; it.mult = p.mult; it.bgflag = p.bgflag;
+  it.list1 = in.bg_orig; it.list2 = in.bg_trans;
+  it.partq = w.partq; it.grad = in.grad; it.loss_part = w.fg_part; it.bg_loss = w.bg_part; it.loss_out = in.loss_out;
+  it.n1 = in.n_bg_orig; it.n2 = in.n_bg_trans;
+  // weighted: the loss partials carry omega_m / N_m, and the kernel forms fg_w * omega_m / (C N_m) itself from the plain fg_w
+  if (weighted) it.fg_norm = in.n_pairs > 0 ? 1.f / (float)C : 0.f;
+  else it.fg_norm = in.n_pairs > 0 ? 1.f / ((float)C * (float)in.n_pairs) : 0.f;
+  it.coef_fg = weighted ? in.fg_w : in.fg_w * it.fg_norm;
+  it.bg_norm = bg ? 1.f / (float)C : 0.f;
+  it.coef_bg = bg ? in.bg_w * it.bg_norm / (float)in.n_bg_trans : 0.f;
+  it.use_bg = bg ? 1 : 0;
+  it.scale = in.grad_scale;
+  it.n_fg_part = in.n_pairs > 0 ? nblocks : 0;
+  it.fg_w = in.fg_w; it.bg_w = in.bg_w;
   return DH_OK;
 }
 
-// ---- weighted and unweighted items in one launch pair ------------------------------------------------------------------------
-extern "C" int dh_energy_fwd_bwd_planned_mixed_batch(const dh_energy_item* items, const uint8_t* weighted, int n_items, int dtype,
-                                                     int C, int grid, int grad_dtype, void* workspace, size_t workspace_bytes,
-                                                     void* stream) {
-  DH_REQUIRE(items && weighted && workspace, "null pointer");
-  DH_REQUIRE(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS, "the batched energy takes 1..16 items (larger batches are not split)");
-  DH_REQUIRE(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16, "the planned path takes 16-bit activations");
-  DH_REQUIRE(grad_dtype >= 0 && grad_dtype <= 2, "bad dtype");
-  DH_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1, "bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  const int G2 = grid * grid;
-  const int cpb = 256 / (C / 8);
-  const int nblocks = cdiv(G2, cpb);
+// ---- one evaluation: the single kernels, their scalar arguments read from the item's row ------------------------------------
+static int run_planned_single(const char* who, bool weighted, const dh_energy_item& in, int dtype, int C, int grid, int grad_dtype,
+                              void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (!(in.cur && in.orig && in.grad && in.plan && workspace)) return refuse(who, "null pointer");
+  if (!(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16)) return refuse(who, "the planned path takes 16-bit activations");
+  if (!(grad_dtype >= 0 && grad_dtype <= 2)) return refuse(who, "bad dtype");
+  if (!(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1 && in.n_pairs >= 0)) return refuse(who, "bad sizes");
+  const int G2 = grid * grid, nblocks = grad_blocks(C, grid);
+  Arena aw(workspace, workspace_bytes);
+  EnergyItem it;
+  const uint8_t* objp;
+  if (const int rc = fill_item(who, in, weighted, "plan buffer too small", C, grid, nblocks, aw, it, objp)) return rc;
+  if (it.use_bg)
+    with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((k_colsum_q<T>), dim3(cdiv(C, 64), 4, 2), dim3(8 * CQ_SL), 0, st, (const T*)it.orig, it.list1, it.n1,
+                         (const T*)it.cur, it.list2, it.n2, C, it.partq);
+    });
+  with_dtypes(dtype, grad_dtype, [&](auto t, auto tg) {
+    using T = typename decltype(t)::type;
+    using TG = typename decltype(tg)::type;
+    if (weighted)
+      hipLaunchKernelGGL((k_energy_grad_obj<T, TG>), dim3(nblocks), dim3(256), 0, st, (const T*)it.orig, (const T*)it.cur, it.off,
+                         it.ucnt, it.src, it.mult, objp, it.bgflag, it.partq, it.n1, it.n2, C, G2, it.coef_fg, it.coef_bg, it.use_bg,
+                         it.scale, (TG*)it.grad, it.loss_part, it.bg_loss);
+    else
+      hipLaunchKernelGGL((k_energy_grad<T, TG>), dim3(nblocks), dim3(256), 0, st, (const T*)it.orig, (const T*)it.cur, it.off,
+                         it.ucnt, it.src, it.mult, it.bgflag, it.partq, it.n1, it.n2, C, G2, it.coef_fg, it.coef_bg, it.use_bg,
+                         it.scale, (TG*)it.grad, it.loss_part, it.bg_loss);
+  });
+  if (it.loss_out)
+    hipLaunchKernelGGL(k_final_loss, dim3(1), dim3(256), 0, st, it.loss_part, it.n_fg_part, it.fg_norm, it.bg_loss, it.use_bg,
+                       it.bg_norm, it.fg_w, it.bg_w, it.loss_out);
+  return launch_status(who);
+}
+
+extern "C" int dh_energy_fwd_bwd_planned(const void* cur, const void* orig, int dtype, int C, int grid, const void* plan,
+                                         size_t plan_bytes, int n_pairs, const int32_t* bg_orig, int n_bg_orig,
+                                         const int32_t* bg_trans, int n_bg_trans, float fg_w, float bg_w, float grad_scale,
+                                         float* loss_out, void* grad, int grad_dtype, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  const dh_energy_item in = {cur, orig, plan, plan_bytes, bg_orig, bg_trans, loss_out, grad, n_pairs, n_bg_orig, n_bg_trans,
+                             fg_w, bg_w, grad_scale};      // (the field order of dh_energy_item)
+  return run_planned_single(__func__, false, in, dtype, C, grid, grad_dtype, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int dh_energy_fwd_bwd_planned_objects(const void* cur, const void* orig, int dtype, int C, int grid, const void* plan,
+                                                 size_t plan_bytes, int n_pairs, const int32_t* bg_orig, int n_bg_orig,
+                                                 const int32_t* bg_trans, int n_bg_trans, float fg_w, float bg_w,
+                                                 float grad_scale, float* loss_out, void* grad, int grad_dtype, void* workspace,
+                                                 size_t workspace_bytes, void* stream) {
+  const dh_energy_item in = {cur, orig, plan, plan_bytes, bg_orig, bg_trans, loss_out, grad, n_pairs, n_bg_orig, n_bg_trans,
+                             fg_w, bg_w, grad_scale};      // (the field order of dh_energy_item)
+  return run_planned_single(__func__, true, in, dtype, C, grid, grad_dtype, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ---- K items: one launch pair (plus the loss launch), whichever of the three gradient kernels the entry names ----------------
+enum class BatchKernel { PLAIN, OBJECTS, MIXED };      // k_energy_grad_batch, k_energy_grad_obj_batch, k_energy_grad_mixed_batch
+
+// weighted: one byte per item, non-zero where its plan buffer is a weighted plan (all 0 / all 1 for the two pure entries)
+static int run_planned_batch(const char* who, BatchKernel kernel, const dh_energy_item* items, const uint8_t* weighted, int n_items,
+                             int dtype, int C, int grid, int grad_dtype, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  if (!(items && weighted && workspace)) return refuse(who, "null pointer");
+  if (!(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS))
+    return refuse(who, "the batched energy takes 1..16 items (larger batches are not split)");
+  if (!(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16)) return refuse(who, "the planned path takes 16-bit activations");
+  if (!(grad_dtype >= 0 && grad_dtype <= 2)) return refuse(who, "bad dtype");
+  if (!(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1)) return refuse(who, "bad sizes");
+  const int G2 = grid * grid, nblocks = grad_blocks(C, grid);
   Arena aw(workspace, workspace_bytes);
   EnergyBatch tab;
   EnergyObjPtrs ot;
   bool any_bg = false, any_loss = false;
   for (int e = 0; e < n_items; ++e) {
-    const dh_energy_item& in = items[e];
-    EnergyItem& it = tab.it[e];
-    DH_REQUIRE(in.cur && in.orig && in.grad && in.plan, "null pointer in an item");
-    DH_REQUIRE(in.n_pairs >= 0, "bad sizes");
-    Arena ap(const_cast<void*>(in.plan), in.plan_bytes);
-    EnergyPlanObj po;
-    if (weighted[e]) {
-      DH_REQUIRE(carve_plan_obj(ap, grid, in.n_pairs, po), "plan buffer too small for a weighted plan");
-      ot.p[e] = po.objp;
-    } else {
-      DH_REQUIRE(carve_plan(ap, grid, in.n_pairs, po.base), "plan buffer too small");
-      ot.p[e] = nullptr;
-    }
-    const EnergyPlan& p = po.base;
-    PlannedWs w;
-    DH_REQUIRE(carve_planned(aw, C, grid, w), "workspace too small");
-    it.orig = in.orig; it.cur = in.cur;
-    it.off = p.off; it.ucnt = p.cnt; it.src = p.src; it.mult = p.mult; it.bgflag = p.bgflag;
-    it.list1 = in.bg_orig; it.list2 = in.bg_trans;
-    it.partq = w.partq; it.grad = in.grad; it.loss_part = w.fg_part; it.bg_loss = w.bg_part; it.loss_out = in.loss_out;
-    it.n1 = in.n_bg_orig; it.n2 = in.n_bg_trans;
-    // an item's row is the row of its own batched entry: the weighted kernel body forms fg_w * omega_m / (C N_m) itself
-    if (weighted[e]) it.fg_norm = in.n_pairs > 0 ? 1.f / (float)C : 0.f;
-    else it.fg_norm = in.n_pairs > 0 ? 1.f / ((float)C * (float)in.n_pairs) : 0.f;
-    it.bg_norm = 0.f; it.coef_bg = 0.f; it.use_bg = 0;
-    if (in.n_bg_orig > 0 && in.n_bg_trans > 0) {
-      DH_REQUIRE(in.bg_orig && in.bg_trans, "null bg list");
-      it.bg_norm = 1.f / (float)C;
-      it.coef_bg = in.bg_w * it.bg_norm / (float)in.n_bg_trans;
-      it.use_bg = 1;
-      any_bg = true;
-    }
-    it.coef_fg = weighted[e] ? in.fg_w : in.fg_w * it.fg_norm;
-    it.scale = in.grad_scale;
-    it.n_fg_part = in.n_pairs > 0 ? nblocks : 0;
-    it.fg_w = in.fg_w; it.bg_w = in.bg_w;
-    any_loss = any_loss || in.loss_out != nullptr;
+    // only the mixed entry says which kind of plan was too small
+    const char* small_plan = kernel == BatchKernel::MIXED && weighted[e] ? "plan buffer too small for a weighted plan" : "plan buffer too small";
+    if (const int rc = fill_item(who, items[e], weighted[e] != 0, small_plan, C, grid, nblocks, aw, tab.it[e], ot.p[e])) return rc;
+    any_bg = any_bg || tab.it[e].use_bg;
+    any_loss = any_loss || tab.it[e].loss_out != nullptr;
   }
-  for (int e = n_items; e < ENERGY_MAX_ITEMS; ++e) { tab.it[e] = tab.it[0]; ot.p[e] = ot.p[0]; }      // (never indexed)
-  if (any_bg) {
-    if (dtype == DH_DTYPE_F16)
-      hipLaunchKernelGGL((k_colsum_q_batch<f16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
-    else
-      hipLaunchKernelGGL((k_colsum_q_batch<bf16>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
-  }
-#define DH_EGMB(T_)                                                                                                            \
-  do {                                                                                                                         \
-    if (grad_dtype == DH_DTYPE_F16) hipLaunchKernelGGL((k_energy_grad_mixed_batch<T_, f16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2);        \
-    else if (grad_dtype == DH_DTYPE_BF16) hipLaunchKernelGGL((k_energy_grad_mixed_batch<T_, bf16>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2); \
-    else hipLaunchKernelGGL((k_energy_grad_mixed_batch<T_, float>), dim3(nblocks, n_items), dim3(256), 0, st, tab, ot, C, G2); \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_EGMB(f16);
-  else DH_EGMB(bf16);
-#undef DH_EGMB
+  for (int e = n_items; e < ENERGY_MAX_ITEMS; ++e) { tab.it[e] = tab.it[0]; ot.p[e] = ot.p[0]; }      // (never indexed: defined kernel arguments)
+  if (any_bg)
+    with_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((k_colsum_q_batch<T>), dim3(cdiv(C, 64), 4, 2 * n_items), dim3(8 * CQ_SL), 0, st, tab, C);
+    });
+  with_dtypes(dtype, grad_dtype, [&](auto t, auto tg) {
+    using T = typename decltype(t)::type;
+    using TG = typename decltype(tg)::type;
+    const dim3 blocks(nblocks, n_items);
+    if (kernel == BatchKernel::PLAIN) hipLaunchKernelGGL((k_energy_grad_batch<T, TG>), blocks, dim3(256), 0, st, tab, C, G2);
+    else if (kernel == BatchKernel::OBJECTS) hipLaunchKernelGGL((k_energy_grad_obj_batch<T, TG>), blocks, dim3(256), 0, st, tab, ot, C, G2);
+    else hipLaunchKernelGGL((k_energy_grad_mixed_batch<T, TG>), blocks, dim3(256), 0, st, tab, ot, C, G2);
+  });
   if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
+  return launch_status(who);
+}
+
+extern "C" int dh_energy_fwd_bwd_planned_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
+                                               int grad_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  static const uint8_t none[ENERGY_MAX_ITEMS] = {};
+  return run_planned_batch(__func__, BatchKernel::PLAIN, items, none, n_items, dtype, C, grid, grad_dtype, workspace, workspace_bytes,
+                           (hipStream_t)stream);
+}
+
+extern "C" int dh_energy_fwd_bwd_planned_objects_batch(const dh_energy_item* items, int n_items, int dtype, int C, int grid,
+                                                       int grad_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  static_assert(ENERGY_MAX_ITEMS == 16, "one flag per item");
+  static const uint8_t all[ENERGY_MAX_ITEMS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+  return run_planned_batch(__func__, BatchKernel::OBJECTS, items, all, n_items, dtype, C, grid, grad_dtype, workspace, workspace_bytes,
+                           (hipStream_t)stream);
+}
+
+extern "C" int dh_energy_fwd_bwd_planned_mixed_batch(const dh_energy_item* items, const uint8_t* weighted, int n_items, int dtype,
+                                                     int C, int grid, int grad_dtype, void* workspace, size_t workspace_bytes,
+                                                     void* stream) {
+  return run_planned_batch(__func__, BatchKernel::MIXED, items, weighted, n_items, dtype, C, grid, grad_dtype, workspace, workspace_bytes,
+                           (hipStream_t)stream);
 }

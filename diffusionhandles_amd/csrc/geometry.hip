@@ -10,6 +10,8 @@
 #include "common.h"
 #include "compact.h"
 
+#include <vector>
+
 namespace dh {
 
 // ---------------------------------------------------------------------- point geometry
@@ -117,12 +119,18 @@ __device__ __forceinline__ double unsort_f64(unsigned long long k) {
   return __longlong_as_double((long long)b);
 }
 
+// One transform row on the device = the row of dh_reproject_similarity_edits (DH_SIMILARITY_ROW doubles, diffhandles_hip.h):
+// the 8 doubles of dh_reproject_object_edits, then the scale per camera axis, the pivot and its flag (float32 values widened).
 struct Xf {
   double ax, ay, az, c, s, tx, ty, tz;
+  double sx, sy, sz, px, py, pz, has_pivot, reserved;
 };
+static_assert(sizeof(Xf) == DH_SIMILARITY_ROW * sizeof(double), "Xf is the similarity row");
 
 // one thread per (edit, point): points [0,R2) are background pixels, [R2,R2+n_fg) foreground, object after object.
-// xf: n_obj rows per edit (edit-major), cen: 4 floats per object.
+// xf: n_obj rows per edit (edit-major), cen: 4 floats per object.  The object turns about its row's pivot when the row has
+// one (edits of one call may pivot one object differently), else about its centroid; q is scaled per camera axis BEFORE
+// the rotation, one rounded f32 multiply per component (s = 1 leaves every bit of q as it was).
 __global__ void k_points(const float* depth, const float* bg_depth, const int* fg_pix, int n_fg, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
                          const Xf* xf, const float* cen, const ObjTable tab, int n_obj, unsigned long long* zbuf,
@@ -144,8 +152,11 @@ __global__ void k_points(const float* depth, const float* bg_depth, const int* f
 #pragma unroll
     for (int k = 1; k < MAX_OBJECTS; ++k) m += (i - R2 >= tab.start[k]) ? 1 : 0;
     const Xf t = xf[e * n_obj + m];
-    const float c0 = cen[4 * m], c1 = cen[4 * m + 1], c2 = cen[4 * m + 2];
-    const float q0 = x - c0, q1 = y - c1, q2 = z - c2;
+    // (the centroid is read whether or not the row has a pivot: three selects, no divergent branch around dependent loads)
+    const bool piv = t.has_pivot != 0.0;
+    const float g0 = cen[4 * m], g1 = cen[4 * m + 1], g2 = cen[4 * m + 2];
+    const float c0 = piv ? (float)t.px : g0, c1 = piv ? (float)t.py : g1, c2 = piv ? (float)t.pz : g2;
+    const float q0 = (x - c0) * (float)t.sx, q1 = (y - c1) * (float)t.sy, q2 = (z - c2) * (float)t.sz;
     const float a0 = (float)t.ax, a1 = (float)t.ay, a2 = (float)t.az;
     const float cr0 = a1 * q2 - a2 * q1;
     const float cr1 = a2 * q0 - a0 * q2;
@@ -991,21 +1002,33 @@ extern "C" int dh_masked_centroid(const float* depth, const int32_t* fg_pix, int
   return DH_OK;
 }
 
-// n_objects rigid bodies per edit: object m owns fg_pix[obj_start[m] .. obj_start[m + 1]) and row e * n_objects + m of xforms_host.
-// Only k_centroid and k_points know about objects; from the z-buffer on the point list is one list.
-extern "C" int dh_reproject_object_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                         int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                         const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                         const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                         uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                         int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                         void* stream) {
+// n_objects bodies per edit: object m owns fg_pix[obj_start[m] .. obj_start[m + 1]) and row e * n_objects + m of xforms_host
+// (DH_SIMILARITY_ROW doubles: rotation, translation, scale, pivot).  Only k_centroid and k_points know about objects; from the
+// z-buffer on the point list is one list.  The one code path of the re-projection: dh_reproject_object_edits and
+// dh_reproject_edits are its scale-1 / no-pivot calls.
+extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                             const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                             uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                             int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
   DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
   DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
   DH_REQUIRE(obj_start[0] == 0 && obj_start[n_objects] == n_fg, "obj_start must run from 0 to n_fg");
   for (int m = 0; m < n_objects; ++m) DH_REQUIRE(obj_start[m] < obj_start[m + 1], "obj_start must increase (no empty object)");
+  // every row before any launch: a scale that is not positive and finite would collapse or mirror the object or spread NaN over
+  // the z-buffer; a pivot is checked whether or not the row's flag selects it
+  for (size_t r = 0; r < (size_t)n_edits * n_objects; ++r) {
+    const double* row = xforms_host + r * DH_SIMILARITY_ROW;
+    for (int k = 8; k < 11; ++k)
+      DH_REQUIRE((float)row[k] > 0.0f && row[k] <= 3.4028234663852886e38, "transform row: the scale must be positive and finite");
+    for (int k = 11; k < 14; ++k)
+      DH_REQUIRE(row[k] >= -3.4028234663852886e38 && row[k] <= 3.4028234663852886e38, "transform row: the pivot must be finite");
+    DH_REQUIRE(row[14] == 0.0 || row[14] == 1.0, "transform row: the has-pivot flag must be 0 or 1");
+  }
   hipStream_t st = (hipStream_t)stream;
   const int K = n_edits, M = n_objects, R2 = res * res, P = R2 + n_fg;
   const ObjTable tab = obj_table(M, obj_start, n_fg);
@@ -1080,6 +1103,34 @@ extern "C" int dh_reproject_object_edits(const float* depth, const float* bg_dep
                      reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+// the rows of the rigid entries (8 doubles) widened to similarity rows: scale 1, no pivot.  The buffer outlives the call (the
+// copy to the device is asynchronous), one per calling thread.
+static const double* rigid_rows(const double* rows8, size_t n) {
+  thread_local std::vector<double> wide;
+  wide.assign(n * DH_SIMILARITY_ROW, 0.0);
+  for (size_t r = 0; r < n; ++r) {
+    double* w = wide.data() + r * DH_SIMILARITY_ROW;
+    for (int k = 0; k < 8; ++k) w[k] = rows8[r * 8 + k];
+    w[8] = w[9] = w[10] = 1.0;
+  }
+  return wide.data();
+}
+
+extern "C" int dh_reproject_object_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                         int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                         const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                         const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                         uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                         int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  DH_REQUIRE(xforms_host, "null input");
+  DH_REQUIRE(n_edits >= 1, "bad sizes");
+  DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
+  return dh_reproject_similarity_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx,
+                                       fy, n_edits, rigid_rows(xforms_host, (size_t)n_edits * n_objects), bounds, zmap, raw_mask,
+                                       clean_mask, disparity, vis, target_xy, corr, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg, int res,

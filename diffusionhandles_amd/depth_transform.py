@@ -76,9 +76,87 @@ def depth_to_world_coords(depth, intrinsics, extrinsics_R=None, extrinsics_t=Non
     return pts.to(depth.device)
 
 
-def _xform_rows(transforms):
-    """(angle_deg, axis, translation) -> 8 doubles per edit, with NumPy's own cos/sin."""
-    rows = np.zeros((len(transforms), 8), dtype=np.float64)
+def _f32_list(v):
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().reshape(-1).tolist()
+    elif isinstance(v, np.ndarray):
+        v = v.reshape(-1).tolist()
+    return [float(np.float32(x)) for x in v]
+
+
+def check_transform(tf, what="transform"):
+    """One object transform, (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3],
+    scale, pivot) -> the 5-tuple with scale as three float32 values and pivot as None or three float32 values.
+    scale: None (= 1), one positive number or three (sx, sy, sz) along the camera axes of `depth_to_world_coords`;
+    pivot: None (= the centroid of the object's masked points) or a point in the coordinates `depth_to_world_coords`
+    returns.  ValueError naming `what` for another tuple length, a scale that is not positive and finite as float32, a
+    pivot that is not three finite numbers.  Host only: no device work."""
+    try:
+        n = len(tf)
+    except TypeError:
+        n = -1
+    if n not in (3, 5):
+        raise ValueError(f"{what}: expected (rot_angle, rot_axis, translation) or (rot_angle, rot_axis, translation, scale, "
+                         f"pivot), got {n if n >= 0 else 'no'} members")
+    angle, axis, trans = tf[0], tf[1], tf[2]
+    scale, pivot = (tf[3], tf[4]) if n == 5 else (None, None)
+    if scale is None and pivot is None:          # the rigid transform: nothing to check
+        return angle, axis, trans, [1.0, 1.0, 1.0], None
+    if scale is None:
+        sc = [1.0, 1.0, 1.0]
+    else:
+        try:
+            with np.errstate(over="ignore"):
+                sc = _f32_list(scale) if isinstance(scale, (list, tuple, np.ndarray, torch.Tensor)) else [float(np.float32(scale))] * 3
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: scale must be one number or three, got {scale!r}") from None
+        if len(sc) == 1:
+            sc = sc * 3
+        if len(sc) != 3:
+            raise ValueError(f"{what}: scale must be one number or three, got {len(sc)}")
+        if not all(np.isfinite(v) and v > 0.0 for v in sc):
+            raise ValueError(f"{what}: scale must be positive and finite (as float32), got {sc}")
+    pv = None
+    if pivot is not None:
+        try:
+            with np.errstate(over="ignore"):
+                pv = _f32_list(pivot)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: pivot must be three numbers, got {pivot!r}") from None
+        if len(pv) != 3:
+            raise ValueError(f"{what}: pivot must be three numbers, got {len(pv)}")
+        if not all(np.isfinite(v) for v in pv):
+            raise ValueError(f"{what}: pivot must be finite (as float32), got {pv}")
+    return angle, axis, trans, sc, pv
+
+
+SIMILARITY_ROW = 16          # DH_SIMILARITY_ROW (include/diffhandles_hip.h)
+
+
+def _xform_rows(transforms, similarity=False):
+    """(angle_deg, axis, translation) -> 8 doubles per edit, with NumPy's own cos/sin: the rows of dh_reproject_edits /
+    dh_reproject_object_edits.  similarity=True: 3- or 5-tuples (check_transform) -> the 16 doubles of
+    dh_reproject_similarity_edits, the same 8 followed by scale[3], pivot[3], has-pivot flag, 0."""
+    if similarity:
+        return _similarity_rows([check_transform(tf) for tf in transforms])
+    return _rigid_rows(transforms, np.zeros((len(transforms), 8), dtype=np.float64))
+
+
+def _similarity_rows(checked):
+    """The rows of dh_reproject_similarity_edits from transforms that went through check_transform."""
+    rows = np.zeros((len(checked), SIMILARITY_ROW), dtype=np.float64)
+    _rigid_rows([tf[:3] for tf in checked], rows)
+    rows[:, 8:11] = 1.0
+    for i, (_, _, _, sc, pv) in enumerate(checked):
+        if sc != [1.0, 1.0, 1.0]:
+            rows[i, 8:11] = sc
+        if pv is not None:
+            rows[i, 11:14] = pv
+            rows[i, 14] = 1.0
+    return rows
+
+
+def _rigid_rows(transforms, rows):
     for i, (angle, axis, trans) in enumerate(transforms):
         ax = np.asarray(axis.detach().cpu().numpy() if isinstance(axis, torch.Tensor) else axis, dtype=np.float32)
         ax = ax / np.linalg.norm(ax)
@@ -95,7 +173,9 @@ MAX_OBJECTS = 8              # csrc/geometry.hip: the object table travels in th
 
 def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_depth_normalization=False,
                     return_debug=False, device_correspondences=False):
-    """K edits of one image.  transforms: list of (rot_angle_deg, rot_axis[3], translation[3]).
+    """K edits of one image.  transforms: list of (rot_angle_deg, rot_axis[3], translation[3]) or of
+    (rot_angle_deg, rot_axis[3], translation[3], scale, pivot) (check_transform; `reproject_object_edits` says what scale
+    and pivot do).
 
     Returns a list of (disparity [1,1,H,W] f32 on depth.device, correspondences [N,4] int64 CPU),
     plus a dict of the intermediate device tensors when return_debug is set.  The reference hands the correspondences
@@ -111,11 +191,18 @@ def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_
 
 def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_input_depth_normalization=False,
                            return_debug=False, device_correspondences=False):
-    """K edits of one image with M rigid bodies each (not in the reference).  fg_masks: M pairwise disjoint [1,1,H,W] masks
+    """K edits of one image with M bodies each (not in the reference).  fg_masks: M pairwise disjoint [1,1,H,W] masks
     (1 <= M <= 8); bg_depth: the depth with ALL objects removed; edits: K lists of M (rot_angle_deg, rot_axis[3],
-    translation[3]), one per mask.
+    translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.
 
-    Object m turns about the centroid of its own masked points, then moves.  The point list is the background pixels, then
+    Object m turns about the centroid of its own masked points, then moves.  With a 5-tuple it is first scaled -- scale:
+    None (= 1), one positive float or three (sx, sy, sz) along the camera axes of `depth_to_world_coords`, applied to the
+    offsets from the pivot BEFORE the rotation, so a non-uniform scale of a turned object stretches along the un-turned
+    camera axes -- and pivot (None = the centroid; else a point in the coordinates `depth_to_world_coords` returns, see
+    `pivot_at_pixel`) replaces the centroid for the scale and the turn.  Scale 1 with pivot None is the 3-tuple's result
+    bit for bit.  A magnified object leaves gaps between its points; the mask CLOSE bridges them only up to its element,
+    res // 50 (as when an object moves towards the camera).  ValueError naming the edit and the object for a malformed
+    transform (check_transform), before any device work.  The point list is the background pixels, then
     the points of object 0 in row-major order, then object 1, ...: one z-buffer over all of it, so the objects occlude the
     background and each other, and equal depths go to the earlier object.  Mask clean-up, correspondence filter, in-fill
     and normalisation see the union.  Empty masks are dropped (with their transforms); all empty = the empty-mask result of
@@ -133,6 +220,7 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
     for e, tfs in enumerate(edits):
         if len(tfs) != M:
             raise ValueError(f"Edit {e} has {len(tfs)} transforms for {M} foreground masks")
+    edits = [[check_transform(tf, f"edit {e}, object {m}") for m, tf in enumerate(tfs)] for e, tfs in enumerate(edits)]
     for fg_mask in fg_masks:
         if fg_mask.shape[-2] != fg_mask.shape[-1]:
             raise RuntimeError(f"Expected fg_mask to be square, got shape {fg_mask.shape[-2]} x {fg_mask.shape[-1]}.")
@@ -198,13 +286,13 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
     txy = torch.empty((K, n_fg, 2), dtype=torch.int32, device=dev)
     corr = torch.empty((K, n_fg, 4), dtype=torch.int64, device=dev)
     counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
-    rows = np.ascontiguousarray(_xform_rows([tfs[m] for tfs in edits for m in kept]))      # edit-major, K x Mk rows
-    _lib.check(L.dh_reproject_object_edits(
+    rows = _similarity_rows([tfs[m] for tfs in edits for m in kept])      # edit-major, K x Mk rows (C-contiguous)
+    _lib.check(L.dh_reproject_similarity_edits(
         _lib.ptr(d), _lib.ptr(bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
         _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, K,
         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bounds),
         _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
-        _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st), "dh_reproject_object_edits")
+        _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st), "dh_reproject_similarity_edits")
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
     out = []
@@ -244,15 +332,26 @@ def _check_infill(iterations):
     raise RuntimeError(f"harmonic in-fill: unknown failure code {int(iterations.min())}; the result is not valid")
 
 
+def pivot_at_pixel(depth, intrinsics, x, y):
+    """The point of pixel (x, y) = (column, row) of `depth` [1,1,H,W] in the coordinates `depth_to_world_coords` returns:
+    three float32 values (a CPU tensor), to hand to a transform as `pivot` -- "turn about this pixel"."""
+    h, w = depth.shape[-2:]
+    x, y = int(x), int(y)
+    if not (0 <= x < w and 0 <= y < h):
+        raise ValueError(f"pivot_at_pixel: pixel ({x}, {y}) is outside the {w} x {h} depth map")
+    return depth_to_world_coords(depth, intrinsics)[y, x].detach().to("cpu", torch.float32).clone()
+
+
 def transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
-                       use_input_depth_normalization=False):
+                       use_input_depth_normalization=False, scale=None, pivot=None):
+    """The reference's transform_depth_pc (its parameters are a prefix); scale / pivot: see `reproject_object_edits`."""
     if rot_angle is None:
         rot_angle = 0.0
     if rot_axis is None:
         rot_axis = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
     if translation is None:
         translation = torch.tensor([0.0, 0.0, 0.0], dtype=torch.float32)
-    (disp, corr), = reproject_edits(depth, bg_depth, fg_mask, intrinsics, [(rot_angle, rot_axis, translation)],
+    (disp, corr), = reproject_edits(depth, bg_depth, fg_mask, intrinsics, [(rot_angle, rot_axis, translation, scale, pivot)],
                                     use_input_depth_normalization)
     return disp, corr
 
@@ -260,10 +359,20 @@ def transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot
 MESH_BLUR_RADIUS = 1e-5      # depth_transform.py:152
 
 
-def mesh_xform(depth, fg_mask, intrinsics, rot_angle, rot_axis, translation):
+def _mesh_similarity(scale, pivot, what):
+    """scale / pivot of a mesh-mode call: checked as the point mode checks them (ValueError), then a scale other than 1 is
+    refused -- the mesh path has no scale.  Returns the pivot as None or three float32 values.  Host only."""
+    _, _, _, sc, pv = check_transform((0.0, None, None, scale, pivot), what)
+    if sc != [1.0, 1.0, 1.0]:
+        raise NotImplementedError(f"{what}: depth_transform_mode 'mesh' has no scale (got scale={scale!r}); use 'pc'")
+    return pv
+
+
+def mesh_xform(depth, fg_mask, intrinsics, rot_angle, rot_axis, translation, pivot=None):
     """The 11 float32 numbers dh_mesh_reproject takes: unit axis, cos, sin, translation, centroid of the masked
     points (transform_points, depth_transform.py:438-458; the centroid is the sequential float32 mean the point
-    path uses -- torch's own reduction order is not specified)."""
+    path uses -- torch's own reduction order is not specified).  pivot (three float32 values) takes the centroid's place."""
+    pivot = _mesh_similarity(None, pivot, "mesh_xform")
     dev = _compute_device(depth)
     res = depth.shape[-1]
     d = depth.detach().to(dev, torch.float32).contiguous()
@@ -278,14 +387,17 @@ def mesh_xform(depth, fg_mask, intrinsics, rot_angle, rot_axis, translation):
     ang = np.float32(rot_angle.item() if isinstance(rot_angle, torch.Tensor) else rot_angle)
     theta = np.float32(ang * np.float32(np.pi / 180.0))
     tr = translation.detach().cpu().numpy() if isinstance(translation, torch.Tensor) else np.asarray(translation)
-    c = cen.cpu().numpy()
+    c = cen.cpu().numpy() if pivot is None else np.asarray(pivot, dtype=np.float32)
     return np.array([ax[0], ax[1], ax[2], np.cos(theta), np.sin(theta), tr[0], tr[1], tr[2], c[0], c[1], c[2]],
                     dtype=np.float32)
 
 
 def transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
-                         use_input_depth_normalization=False, return_debug=False):
-    """depth_transform.py:91-195 with our own HIP triangle rasteriser in place of pytorch3d (parity unpinned)."""
+                         use_input_depth_normalization=False, return_debug=False, scale=None, pivot=None):
+    """depth_transform.py:91-195 with our own HIP triangle rasteriser in place of pytorch3d (parity unpinned).
+    pivot: None or three floats, the point the object turns about in place of its centroid; a scale other than 1 raises
+    NotImplementedError before any device work (the mesh path has no scale)."""
+    pivot = _mesh_similarity(scale, pivot, "transform_depth_mesh")
     if depth.dim() != 4 or depth.shape[0] != 1:
         raise ValueError("Only batch size 1 is supported")
     res = depth.shape[-1]
@@ -308,7 +420,7 @@ def transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, r
         rot_axis = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
     if translation is None:
         translation = torch.tensor([0.0, 0.0, 0.0], dtype=torch.float32)
-    xf = mesh_xform(depth, fg_mask, intrinsics, rot_angle, rot_axis, translation)
+    xf = mesh_xform(depth, fg_mask, intrinsics, rot_angle, rot_axis, translation, pivot)
     L = _lib.lib()
     bg = bg_depth.detach().to(dev, torch.float32).contiguous()
     m8 = mask.to(torch.uint8).contiguous()
@@ -338,14 +450,15 @@ def transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, r
 
 
 def transform_depth(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
-                    use_input_depth_normalization=False, depth_transform_mode="pc"):
-    """Same signature and return value as the reference's transform_depth (depth_transform.py:73-89)."""
+                    use_input_depth_normalization=False, depth_transform_mode="pc", scale=None, pivot=None):
+    """The reference's transform_depth (depth_transform.py:73-89): its signature is a prefix and its return value unchanged.
+    scale / pivot (not in the reference): see `reproject_object_edits`; mesh mode takes a pivot and refuses a scale."""
     if depth_transform_mode == "pc":
         return transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle, rot_axis, translation,
-                                  use_input_depth_normalization)
+                                  use_input_depth_normalization, scale, pivot)
     if depth_transform_mode == "mesh":
         return transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle, rot_axis, translation,
-                                    use_input_depth_normalization)
+                                    use_input_depth_normalization, scale=scale, pivot=pivot)
     raise ValueError(f"Unknown depth transform mode '{depth_transform_mode}'.")
 
 

@@ -77,7 +77,8 @@ class DiffusionHandles:
                                    transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
                                    streams=1, batch=None):
         """K edits of one image in batched passes (not in the reference; BASELINE config 3).
-        transforms: list of (rot_angle_deg, rot_axis[3], translation[3]).  Returns (images [K,3,H,W], [K disparities]).
+        transforms: list of (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
+        pivot) (transform_foreground says what scale and pivot do).  Returns (images [K,3,H,W], [K disparities]).
         streams > 1: the K edits are cut into chunks of `batch` (default ceil(K / streams)) and the chunks run on `streams`
         concurrent lanes that share the U-Net weights (GuidedStableDiffuser.fork); batch = 1 runs single (B = 1) edits on the
         lanes.  Images are bit-identical to the one-stream result at the same batch."""
@@ -107,7 +108,15 @@ class DiffusionHandles:
                                       "re-projection (only 'pc')")
         Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
         dflt = lambda v, d: d if v is None else v
-        edits = [[(dflt(a, 0.0), dflt(ax, Y), dflt(tr, torch.zeros(3))) for a, ax, tr in tfs] for tfs in edits]
+        if any(len(tfs) != len(fg_masks) for tfs in edits):          # (reproject_object_edits names the edit)
+            defaulted = edits
+        else:
+            from .depth_transform import check_transform
+            defaulted = []
+            for e, tfs in enumerate(edits):
+                full = [check_transform(tf, f"{what}: edit {e}, object {m}") for m, tf in enumerate(tfs)]
+                defaulted.append([(dflt(a, 0.0), dflt(ax, Y), dflt(tr, torch.zeros(3)), sc, pv) for a, ax, tr, sc, pv in full])
+        edits = defaulted
         return reproject_object_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
                                       use_input_depth_normalization, device_correspondences=device_correspondences)
 
@@ -126,7 +135,8 @@ class DiffusionHandles:
                                      object_weights=None):
         """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
-        rot_axis[3], translation[3]), one per mask.  Each object turns about its own centroid; they occlude the background
+        rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.  Each object
+        turns about its own centroid, or is scaled and turned about its pivot (transform_foreground); they occlude the background
         and each other (depth_transform.reproject_object_edits).  The guidance sees the union of the correspondences: its
         foreground term is the mean over all pairs, so the objects weigh by covered area -- unless object_weights says
         otherwise: "equal" holds every object equally, a sequence of M floats (finite, >= 0, not all zero) sets each weight;
@@ -150,7 +160,8 @@ class DiffusionHandles:
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
                                            object_weights=None, streams=1, batch=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
-        edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]).  Returns (images [K,3,H,W], [K disparities]) as
+        edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
+        pivot).  Returns (images [K,3,H,W], [K disparities]) as
         transform_foreground_batch does.  object_weights: as in transform_foreground_objects, one list for all K edits.
         streams / batch: transform_foreground_batch's -- chunks of `batch` edits (default ceil(K / streams)) on `streams`
         lanes, batch = 1 runs single edits on the lanes; images are bit-identical to the one-stream result at the same batch."""
@@ -178,16 +189,17 @@ class DiffusionHandles:
 
     def transform_foregrounds(self, edits, use_input_depth_normalization=False):
         """K edits of DIFFERENT images in batched passes (not in the reference).  edits: K dicts with the arguments of
-        transform_foreground (EDIT_FIELDS, rot_angle / rot_axis / translation, optional fg_weight / bg_weight) -- or, for an
-        edit that moves several objects (transform_foreground_objects), `fg_masks` (M masks) in place of fg_mask, `transforms`
-        (M triples (rot_angle, rot_axis, translation), None members defaulted) in place of rot_angle / rot_axis / translation,
-        and optionally `object_weights`.  An edit with both forms or with neither, or with a `transforms` list that is not M
-        long, raises ValueError naming the edit, before any device work.  Edits that name the same image (the same depth, mask,
+        transform_foreground (EDIT_FIELDS, rot_angle / rot_axis / translation / scale / pivot, optional fg_weight / bg_weight)
+        -- or, for an edit that moves several objects (transform_foreground_objects), `fg_masks` (M masks) in place of fg_mask,
+        `transforms` (M triples (rot_angle, rot_axis, translation) or 5-tuples (.., scale, pivot), None members defaulted) in
+        place of rot_angle / rot_axis / translation / scale / pivot, and optionally `object_weights`.  An edit with both forms
+        or with neither, with a `transforms` list that is not M long, or with a malformed transform (check_transform) raises
+        ValueError naming the edit, before any device work.  Edits that name the same image (the same depth, mask,
         background-depth and activation tensors) are re-projected together, once per image (multi-object edits: one label
         image per image); then one GuidedStableDiffuser.guided_inference_items for single- and multi-object edits alike.
         Returns (images [K,3,H,W], [K disparities]) in input order.  'pc' re-projection only; one resolution; needs an engine
         with max_batch >= 2K."""
-        from .depth_transform import reproject_edits
+        from .depth_transform import check_transform, reproject_edits
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
                                       "batched re-projection (only 'pc')")
@@ -195,7 +207,7 @@ class DiffusionHandles:
         common = tuple(f for f in self.EDIT_FIELDS if f != "fg_mask")
         if K < 1 or any(set(common) - set(e) for e in edits):
             raise ValueError(f"transform_foregrounds: needs at least one edit, each with {self.EDIT_FIELDS}")
-        single_keys = ("fg_mask", "rot_angle", "rot_axis", "translation")
+        single_keys = ("fg_mask", "rot_angle", "rot_axis", "translation", "scale", "pivot")
         multi_keys = ("fg_masks", "transforms", "object_weights")
         weights = [None] * K
         for i, e in enumerate(edits):
@@ -213,12 +225,16 @@ class DiffusionHandles:
                 if tfs is None or len(tfs) != len(masks):
                     raise ValueError(f"transform_foregrounds: edit {i} has {0 if tfs is None else len(tfs)} transforms for "
                                      f"{len(masks)} masks")
+                for m, tf in enumerate(tfs):
+                    check_transform(tf, f"transform_foregrounds: edit {i}, object {m}")
                 if e.get("object_weights") is not None:
                     from .losses import check_object_weights
                     try:
                         weights[i] = check_object_weights(e["object_weights"], len(masks))
                     except ValueError as err:
                         raise ValueError(f"transform_foregrounds: edit {i}: {err}") from None
+            else:
+                check_transform((0.0, None, None, e.get("scale"), e.get("pivot")), f"transform_foregrounds: edit {i}")
         for i, e in enumerate(edits):
             if tuple(e["depth"].shape[-2:]) != tuple(edits[0]["depth"].shape[-2:]):
                 raise ValueError(f"transform_foregrounds: edit {i} has another resolution than edit 0 "
@@ -248,7 +264,8 @@ class DiffusionHandles:
                             labels[i] = label if weights[i] is not None else None
                 else:
                     tfs = [(dflt(edits[i].get("rot_angle"), 0.0), dflt(edits[i].get("rot_axis"), Y),
-                            dflt(edits[i].get("translation"), torch.zeros(3))) for i in idx]
+                            dflt(edits[i].get("translation"), torch.zeros(3)), edits[i].get("scale"), edits[i].get("pivot"))
+                           for i in idx]
                     res = reproject_edits(e0["depth"], e0["bg_depth"], e0["fg_mask"],
                                           self.diffuser.get_depth_intrinsics(device=e0["depth"].device), tfs,
                                           use_input_depth_normalization, device_correspondences=True)
@@ -263,14 +280,21 @@ class DiffusionHandles:
 
     def transform_foreground(self, depth, prompt, fg_mask, bg_depth, null_text_emb, init_noise, activations,
                              rot_angle=None, rot_axis=None, translation=None, fg_weight=None, bg_weight=None,
-                             use_input_depth_normalization=False):
+                             use_input_depth_normalization=False, scale=None, pivot=None):
+        """The reference's transform_foreground (diffusion_handles.py:113-166), its parameters a prefix.  scale / pivot (not in the
+        reference) make the edit a similarity: scale -- None (= 1), one positive float or three (sx, sy, sz) along the camera
+        axes of depth_to_world_coords -- multiplies the offsets of the object's points from the pivot BEFORE the rotation (a
+        non-uniform scale of a turned object stretches along the un-turned camera axes); pivot -- None (= the centroid of the
+        masked points) or a point in those coordinates (depth_transform.pivot_at_pixel) -- is what the object is scaled and
+        turned about.  In 'pc' mode a magnified object leaves gaps between its points, bridged only up to the mask CLOSE's
+        element (res // 50); 'mesh' mode takes a pivot and refuses a scale (NotImplementedError)."""
         with torch.no_grad():
             edited_disparity, correspondences = transform_depth(
                 depth=depth, bg_depth=bg_depth, fg_mask=fg_mask,
                 intrinsics=self.diffuser.get_depth_intrinsics(device=depth.device),
                 rot_angle=rot_angle, rot_axis=rot_axis, translation=translation,
                 use_input_depth_normalization=use_input_depth_normalization,
-                depth_transform_mode=self.conf.depth_transform_mode)
+                depth_transform_mode=self.conf.depth_transform_mode, scale=scale, pivot=pivot)
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,

@@ -452,6 +452,42 @@ def _check_object_entries(scene_dir, transforms, n_masks):
             raise ValueError(f"{scene_dir}: transform {name!r} lists {n} objects, the scene has {n_masks} object masks")
 
 
+def _is_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _check_similarity_entry(where, t):
+    """The optional "scale" (a positive number or three) and "pivot" (three numbers) of one transforms.json entry; finite as
+    float32, which is what the re-projection takes them as.  ValueError naming `where`."""
+    if not isinstance(t, dict):
+        return
+    f32 = lambda v: float(np.float32(v))
+    with np.errstate(over="ignore"):
+        if "scale" in t:
+            sc = t["scale"]
+            vals = [sc] if _is_number(sc) else sc
+            if not isinstance(vals, (list, tuple)) or len(vals) not in ((1,) if _is_number(sc) else (3,)) or \
+                    not all(_is_number(v) for v in vals):
+                raise ValueError(f"{where}: \"scale\" must be a number or a list of 3 numbers, got {sc!r}")
+            if not all(np.isfinite(f32(v)) and f32(v) > 0.0 for v in vals):
+                raise ValueError(f"{where}: \"scale\" must be positive and finite, got {sc!r}")
+        if "pivot" in t:
+            pv = t["pivot"]
+            if not isinstance(pv, (list, tuple)) or len(pv) != 3 or not all(_is_number(v) for v in pv):
+                raise ValueError(f"{where}: \"pivot\" must be a list of 3 numbers, got {pv!r}")
+            if not all(np.isfinite(f32(v)) for v in pv):
+                raise ValueError(f"{where}: \"pivot\" must be finite, got {pv!r}")
+
+
+def _check_similarity_entries(scene_dir, transforms):
+    """Every entry of transforms.json, and every member of its "objects" list."""
+    for name, t in transforms.items():
+        _check_similarity_entry(f"{scene_dir}: transform {name!r}", t)
+        if isinstance(t, dict) and isinstance(t.get("objects"), (list, tuple)):
+            for m, o in enumerate(t["objects"]):
+                _check_similarity_entry(f"{scene_dir}: transform {name!r}, object {m}", o)
+
+
 def load_scene_geometry(scene_dir, img_res=512):
     """The geometric inputs of a scene only -- what `transform_depth` needs (test/test_diffusion_handles.py:213-215, 247-261):
     dict(transforms, fg_mask [1,1,R,R] in {0,1}, depth [1,1,R,R], bg_depth [1,1,R,R]).  Needs transforms.json, mask.png,
@@ -459,11 +495,15 @@ def load_scene_geometry(scene_dir, img_res=512):
     A scene with a mask_0.png is a multi-object scene (not in the reference): its masks are mask_0.png .. mask_{M-1}.png
     (consecutive, 1 <= M <= 8, each read like mask.png; a mask.png beside them is not read), bg_depth is the depth with all of
     them removed, and every transforms.json entry is {"objects": [M ordinary entries], "object_weights": "equal" | [M floats]
-    (optional)} (object_transform_args).  The dict then also has fg_masks, the list of the M masks, and fg_mask is their union."""
+    (optional)} (object_transform_args).  The dict then also has fg_masks, the list of the M masks, and fg_mask is their union.
+    An ordinary entry may also carry "scale" (a positive number, or 3 along the camera axes) and "pivot" (3 numbers, a point in
+    the coordinates of depth_to_world_coords) (not in the reference; transform_args); malformed values raise ValueError naming
+    the scene and the entry here, when the scene is loaded."""
     import torch
     j = os.path.join
     with open(j(scene_dir, "transforms.json")) as f:
         transforms = json.load(f, object_pairs_hook=OrderedDict)
+    _check_similarity_entries(scene_dir, transforms)
 
     def mask_of(name):
         mask = load_image(j(scene_dir, name))[None]
@@ -523,23 +563,32 @@ def load_scene(scene_dir, img_res=512):
 
 
 def transform_args(t):
-    """One transforms.json entry -> keyword arguments of `transform_foreground` (test_diffusion_handles.py:137-150)."""
+    """One transforms.json entry -> keyword arguments of `transform_foreground` (test_diffusion_handles.py:137-150).  `scale`
+    (a float or three) / `pivot` (three floats) only when the entry has "scale" / "pivot" (not in the reference)."""
     import torch
-    return dict(rot_angle=float(t.get("rotation_angle", 0.0)),
+    _check_similarity_entry("transform_args", t)
+    args = dict(rot_angle=float(t.get("rotation_angle", 0.0)),
                 rot_axis=torch.tensor(t.get("rotation_axis", [0.0, 1.0, 0.0]), dtype=torch.float32),
                 translation=torch.tensor(t.get("translation", [0.0, 0.0, 0.0]), dtype=torch.float32))
+    if "scale" in t:
+        args["scale"] = float(t["scale"]) if _is_number(t["scale"]) else tuple(float(v) for v in t["scale"])
+    if "pivot" in t:
+        args["pivot"] = tuple(float(v) for v in t["pivot"])
+    return args
 
 
 def object_transform_args(entry):
     """One transforms.json entry of a multi-object scene, {"objects": [t_0 .. t_{M-1}], "object_weights": "equal" | [w ..]} ->
     the `transforms` / `object_weights` keyword arguments of `transform_foreground_objects`: M (rot_angle, rot_axis,
-    translation) triples in mask order (`{}` leaves an object in place) and None, "equal" or a list of floats."""
+    translation) triples in mask order (`{}` leaves an object in place) and None, "equal" or a list of floats.  An object
+    whose entry has "scale" or "pivot" gives the 5-tuple (rot_angle, rot_axis, translation, scale, pivot) instead."""
     if not isinstance(entry, dict) or "objects" not in entry:
         raise ValueError("object_transform_args: the entry has no \"objects\" list")
     triples = []
     for t in entry["objects"]:
         a = transform_args(t)
-        triples.append((a["rot_angle"], a["rot_axis"], a["translation"]))
+        triple = (a["rot_angle"], a["rot_axis"], a["translation"])
+        triples.append(triple + (a.get("scale"), a.get("pivot")) if "scale" in a or "pivot" in a else triple)
     w = entry.get("object_weights")
     if w is not None and not isinstance(w, str):
         w = [float(v) for v in w]

@@ -90,6 +90,30 @@ int dh_reproject_object_edits(const float* depth, const float* bg_depth, const i
                               float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
                               uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
                               void* workspace, size_t workspace_bytes, void* stream);
+/* Similarity transforms per object (not in the reference): dh_reproject_object_edits with a scale per camera axis and an
+ * optional pivot.  Everything is as there except the transform row, which EXTENDS its 8 doubles to DH_SIMILARITY_ROW = 16:
+ *   [0..7]   ax, ay, az, cos, sin, tx, ty, tz     the row of dh_reproject_edits / dh_reproject_object_edits, unchanged
+ *   [8..10]  sx, sy, sz    scale along the camera axes of dh_unproject, float32 values widened; positive and finite
+ *   [11..13] px, py, pz    pivot, a point in the coordinates dh_unproject returns, float32 values widened; finite
+ *   [14]     has_pivot     1.0 = the object turns and scales about the pivot, 0.0 = about the centroid of its own points
+ *   [15]     reserved, 0
+ * With c = pivot or centroid (f32), P the unprojected point (f32), s the scale (f32):
+ *   q = fl32(P - c),  q' = fl32(q * s) per component,  then the rotation of dh_reproject_edits on q' (f32 cross and dot
+ *   products, the dot as (q'0 a0 + q'1 a1) + q'2 a2; f64 combination with cos / sin / 1 - cos),  (r + (double)c) + t.
+ * The scale acts BEFORE the rotation: a non-uniform scale of a turned object stretches along the un-turned camera axes.
+ * Scale 1 without a pivot is dh_reproject_object_edits in every output bit; a pivot equal to the centroid's own float32
+ * values likewise.  Rows of different edits may give one object different pivots.  A row with a scale that is not positive
+ * and finite, a pivot that is not finite, or a flag other than 0 / 1 is refused (DH_ERR_ARG) before any launch, the
+ * outputs untouched.  dh_reproject_edits and dh_reproject_object_edits are the scale-1 / no-pivot calls of this entry;
+ * the workspace is dh_reproject_objects_workspace_bytes' for all three. */
+#define DH_SIMILARITY_ROW 16
+int dh_reproject_similarity_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                  int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                  const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                                  int n_edits, const double* xforms_host, const float* bounds,
+                                  float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                                  uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);

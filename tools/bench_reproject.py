@@ -2,7 +2,8 @@
 """Batched K=8 reprojection of the bench scene (run under rocprofv3 --stats for per-kernel times).
 DH_OBJECTS=M (default 1): M = 1 is reproject_edits on the one-sphere scene; M = 2 is reproject_object_edits on the two-sphere
 scene of tests/multi_object_ref.py (both objects move in every edit; edit 0 is the one where object 0 hides object 1).
-DH_CALLS=n timed calls (default 5); the line reports their mean, median and minimum."""
+DH_CALLS=n timed calls (default 5); the line reports their mean, median and minimum.
+DH_SCALE=s (default unset): a second line times the same call with the uniform scale s on every object (5-tuples)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -32,18 +33,31 @@ elif M == 2:
     call = lambda **kw: reproject_object_edits(depth, bg_depth, masks, intr, edits, **kw)
 else:
     sys.exit("DH_OBJECTS: 1 or 2")
-for _ in range(2):
-    call()
-torch.cuda.synchronize()
-times = []
-for _ in range(n):
-    t0 = time.perf_counter()
-    out = call()
+scale = float(os.environ["DH_SCALE"]) if os.environ.get("DH_SCALE") else None
+
+
+def report(call, label):
+    for _ in range(2):
+        call()
     torch.cuda.synchronize()
-    times.append((time.perf_counter() - t0) * 1e3)
-out, dbg = call(return_debug=True)
-cn = dbg["counts"]
-times.sort()
-print(f"K={K} M={M} res={res}: {sum(times)/n:.2f} ms per call (median {times[n // 2]:.2f}, min {times[0]:.2f}, {n} calls); "
-      f"foreground points {int(dbg['fg_pix'].numel())}; correspondences {[int(c.shape[0]) for _, c in out]}; "
-      f"in-fill pixels {[int(v) for v in cn[:, 2]]}; CG iterations {[int(v) for v in cn[:, 3]]}")
+    times = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        out = call()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    out, dbg = call(return_debug=True)
+    cn = dbg["counts"]
+    times.sort()
+    print(f"K={K} M={M} res={res}{label}: {sum(times)/n:.2f} ms per call (median {times[n // 2]:.2f}, min {times[0]:.2f}, {n} calls); "
+          f"foreground points {int(dbg['fg_pix'].numel())}; correspondences {[int(c.shape[0]) for _, c in out]}; "
+          f"in-fill pixels {[int(v) for v in cn[:, 2]]}; CG iterations {[int(v) for v in cn[:, 3]]}")
+
+
+report(call, "")
+if scale is not None:
+    if M == 1:
+        tfs = [tf + (scale, None) for tf in tfs]
+    else:
+        edits = [[tf + (scale, None) for tf in e] for e in edits]
+    report(call, f" scale={scale:g}")

@@ -8,7 +8,9 @@ scene directory, writing PNGs and the .npz identity cache with the reference's k
   python tools/run_edit.py --scene DIR --out /tmp/edit           # DIR laid out like the reference's test/data/<set>/<scene>:
                                                                  #   input.png, mask.png, depth.exr, bg_depth.exr (or .npy),
                                                                  #   prompt.txt, transforms.json {name: {translation,
-                                                                 #   rotation_axis, rotation_angle}}
+                                                                 #   rotation_axis, rotation_angle}}; an entry may also have
+                                                                 #   "scale" (a number or 3) and "pivot" (3 numbers): pc mode
+                                                                 #   takes both, mesh mode a pivot only
                                                                  # several objects: mask_0.png .. mask_{M-1}.png and entries
                                                                  #   {name: {"objects": [M such entries], "object_weights":
                                                                  #   "equal" | [M floats]}} (scene_io.load_scene_geometry; pc mode)
@@ -232,6 +234,12 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
         transforms = transforms[:args.max_edits]
     for i, tf in enumerate(transforms):
         tf.setdefault("name", f"edit{i}")
+    if args.mode == "mesh":         # before the identity is computed: the mesh re-projection has no scale
+        from diffusionhandles_amd.depth_transform import check_transform
+        for tf in transforms:
+            if check_transform((0.0, None, None, tf.get("scale"), None), f"{scene}: transform {tf['name']!r}")[3] != [1.0] * 3:
+                raise NotImplementedError(f"{scene}: transform {tf['name']!r} has a scale ({tf['scale']!r}); --mode mesh has no "
+                                          "scale, use --mode pc")
     exists = {tf["name"]: os.path.exists(os.path.join(out, tf["name"] + ".png")) for tf in transforms}
     return dict(img=img, depth=depth, bg_depth=bg_depth, mask=mask, masks=masks, prompt=prompt, res=res, transforms=transforms,
                 exists=exists)
@@ -362,7 +370,7 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
                 edits.append(dict(common, fg_masks=r["fg_masks"], transforms=tf["transforms"], object_weights=tf["object_weights"]))
             else:
                 edits.append(dict(common, fg_mask=r["fg_mask"], rot_angle=tf["rot_angle"], rot_axis=tf["rot_axis"],
-                                  translation=tf["translation"]))
+                                  translation=tf["translation"], scale=tf.get("scale"), pivot=tf.get("pivot")))
         t0 = time.time()
         images, disparities = handles(prep[scenes[0]]["res"]).transform_foregrounds(edits)
         torch.cuda.synchronize()
@@ -409,7 +417,8 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
                                                    transforms=tf["transforms"], object_weights=tf["object_weights"])
         else:
             res_ = dh.transform_foreground(depth, prompt, mask, bg_depth, null_text, noise, acts, rot_angle=tf["rot_angle"],
-                                          rot_axis=tf["rot_axis"], translation=tf["translation"])
+                                          rot_axis=tf["rot_axis"], translation=tf["translation"], scale=tf.get("scale"),
+                                          pivot=tf.get("pivot"))
         torch.cuda.synchronize()
         dt = time.time() - t0
         edited, disparity = res_[0], res_[1]

@@ -59,6 +59,10 @@ SIGNATURES = {
     "dh_reproject_similarity_edits": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_p, c_p, c_f, c_f, c_d,
                                             c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
                                             c_p]),
+    "dh_reproject_footprints_workspace_bytes": (c_i, [c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
+    "dh_reproject_footprint_edits": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_p, c_p, c_f, c_f, c_d,
+                                           c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                           c_p, c_i, c_f, c_i]),
     "dh_unproject": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_p, c_p]),
     "dh_masked_centroid": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_p]),
     "dh_laplacian_blend_workspace_bytes": (c_i, [c_i, ctypes.POINTER(c_sz)]),
@@ -185,6 +189,7 @@ DEBUG_SIGNATURES = {
     "dh_dbg_lane_ops": (c_i, [c_p, c_p, c_p, c_p]),
     "dh_dbg_cg_limits": (c_i, [ctypes.POINTER(c_i)]),
     "dh_dbg_cg_max_iter": (c_i, [c_i]),
+    "dh_dbg_footprint_tier": (c_i, [c_i]),
 }
 
 

@@ -131,10 +131,13 @@ static_assert(sizeof(Xf) == DH_SIMILARITY_ROW * sizeof(double), "Xf is the simil
 // xf: n_obj rows per edit (edit-major), cen: 4 floats per object.  The object turns about its row's pivot when the row has
 // one (edits of one call may pivot one object differently), else about its centroid; q is scaled per camera axis BEFORE
 // the rotation, one rounded f32 multiply per component (s = 1 leaves every bit of q as it was).
+// FP (footprint splatting, further down): the foreground points also leave (u, v, Z) -- u, v before the clamp and the
+// rounding -- in uvz, 3 doubles per point and edit, for the triangles between them.  FP = false is the kernel as it was.
+template <bool FP>
 __global__ void k_points(const float* depth, const float* bg_depth, const int* fg_pix, int n_fg, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
                          const Xf* xf, const float* cen, const ObjTable tab, int n_obj, unsigned long long* zbuf,
-                         int* pix_out, unsigned long long* key_out) {
+                         int* pix_out, unsigned long long* key_out, double* uvz) {
   const int R2 = res * res, P = R2 + n_fg;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
@@ -175,6 +178,10 @@ __global__ void k_points(const float* depth, const float* bg_depth, const int* f
   double v = (fy * (-Y)) / Z;
   u = (u * 0.5 + 0.5) * m;
   v = (v * 0.5 + 0.5) * m;
+  if (FP && i >= R2) {
+    double* o = uvz + ((size_t)e * n_fg + (i - R2)) * 3;
+    o[0] = u; o[1] = v; o[2] = Z;
+  }
   u = fmin(fmax(u, 0.0), m);
   v = fmin(fmax(v, 0.0), m);
   const int ui = (int)rint(u), vi = (int)rint(v);
@@ -192,6 +199,168 @@ __global__ void k_resolve(int P, int R2, const unsigned long long* zbuf, const i
   if (i >= P) return;
   int pix = pix_arr[(size_t)e * P + i];
   if (key_arr[(size_t)e * P + i] == zbuf[(size_t)e * R2 + pix]) atomicMin(&owner[(size_t)e * R2 + pix], i);
+}
+
+// --------------------------------------------------------------------------- footprints
+// Footprint splatting ("Footprint splatting"): the triangles between neighbouring foreground points of ONE object
+// bid in the z-buffer of the points.  Every quad of source pixels (x, y) .. (x + 1, y + 1) has two triangles, in the vertex
+// order of the reference's depth_to_mesh: half 0 = (v10, v11, v01), half 1 = (v10, v01, v00) with v[row][col]; triangle id =
+// 2 * quad + half.  The vertices are the (u, v, Z) k_points<true> left: unclamped, unrounded.  All arithmetic is f64 in the
+// written order (this file is built without FMA contraction); fp_setup / fp_bid are the ONE statement of it, shared by the
+// thread tier, the wave tier and both z-buffer passes, so a bid recomputed in pass 2 has the bits it had in pass 1.
+struct FpTri {
+  double u0, v0, z0, u1, v1, z1, u2, v2, z2, area;
+  int c0, c1, r0, r1;      // candidate pixel centres, inclusive, inside the image
+};
+// (the fg_pix positions of the three vertices travel beside the struct as an int3 BY VALUE: as members, the bidder's
+// select-by-weight became an indexed load from a private copy of them -- 120 bytes of scratch per lane)
+
+// inverse of fg_pix: source pixel -> position in the point list (the map is -1 elsewhere: memset 0xff before)
+__global__ void k_fp_inverse(const int* fg_pix, int n_fg, int* inv) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n_fg) inv[fg_pix[j]] = j;
+}
+
+__device__ __forceinline__ int fp_object(int j, const ObjTable& tab) {
+  int m = 0;
+#pragma unroll
+  for (int k = 1; k < MAX_OBJECTS; ++k) m += (j >= tab.start[k]) ? 1 : 0;
+  return m;
+}
+
+// false = the triangle does not exist or is dropped (a vertex outside the masks or of another object, the depth-ratio guard,
+// Z <= 0, non-finite u / v, area <= 0, an empty candidate box)
+__device__ __forceinline__ bool fp_setup(int t, int e, int res, int n_fg, const int* inv, const ObjTable& tab, const double* uvz,
+                                         const float* depth, float max_ratio, FpTri& T, int3& J) {
+  const int q = t >> 1, h = t & 1, qy = q / (res - 1), qx = q - qy * (res - 1);
+  const int p00 = qy * res + qx, p01 = p00 + 1, p10 = p00 + res, p11 = p10 + 1;
+  const int s0 = p10, s1 = h ? p01 : p11, s2 = h ? p00 : p01;
+  const int j0 = inv[s0], j1 = inv[s1], j2 = inv[s2];
+  if ((j0 | j1 | j2) < 0) return false;
+  const int m0 = fp_object(j0, tab);
+  if (fp_object(j1, tab) != m0 || fp_object(j2, tab) != m0) return false;
+  if (max_ratio > 0.f) {          // on the SOURCE depths, f32: a quad across a depth step inside one mask makes no sheet
+    const float d0 = depth[s0], d1 = depth[s1], d2 = depth[s2];
+    const float zmin = fminf(fminf(d0, d1), d2), zmax = fmaxf(fmaxf(d0, d1), d2);
+    if (zmax > zmin * max_ratio) return false;
+  }
+  const double* a = uvz + ((size_t)e * n_fg + j0) * 3;
+  const double* b = uvz + ((size_t)e * n_fg + j1) * 3;
+  const double* c = uvz + ((size_t)e * n_fg + j2) * 3;
+  T.u0 = a[0]; T.v0 = a[1]; T.z0 = a[2];
+  T.u1 = b[0]; T.v1 = b[1]; T.z1 = b[2];
+  T.u2 = c[0]; T.v2 = c[1]; T.z2 = c[2];
+  if (!(T.z0 > 0.0 && T.z1 > 0.0 && T.z2 > 0.0)) return false;
+  const double big = 1.7976931348623157e308;
+  if (!(fabs(T.u0) <= big && fabs(T.v0) <= big && fabs(T.u1) <= big && fabs(T.v1) <= big && fabs(T.u2) <= big && fabs(T.v2) <= big))
+    return false;
+  T.area = (T.u0 - T.u1) * (T.v2 - T.v1) - (T.v0 - T.v1) * (T.u2 - T.u1);          // E(v0; v1, v2)
+  if (!(T.area > 0.0)) return false;
+  // the box is clipped in double: nothing outside the int range is ever converted
+  const double lim = (double)(res - 1);
+  const double cmin = fmax(ceil(fmin(fmin(T.u0, T.u1), T.u2)), 0.0), cmax = fmin(floor(fmax(fmax(T.u0, T.u1), T.u2)), lim);
+  const double rmin = fmax(ceil(fmin(fmin(T.v0, T.v1), T.v2)), 0.0), rmax = fmin(floor(fmax(fmax(T.v0, T.v1), T.v2)), lim);
+  if (!(cmin <= cmax && rmin <= rmax)) return false;
+  T.c0 = (int)cmin; T.c1 = (int)cmax; T.r0 = (int)rmin; T.r1 = (int)rmax;
+  J = make_int3(j0, j1, j2);
+  return true;
+}
+
+// the bid of triangle T at pixel centre (c, r), if it covers it (inclusive on every edge): pass 1 lowers the z key of the pixel,
+// pass 2 lowers the owner among the bids that carry the winning key.  Bidder = the vertex with the largest edge weight, ties
+// to the earlier vertex (NumPy's argmax).
+__device__ __forceinline__ void fp_bid(const FpTri& T, const int3 J, int c, int r, int pass, int res, int R2, unsigned long long* zbuf, int* owner) {
+  const double px = (double)c, py = (double)r;
+  const double w0 = (px - T.u1) * (T.v2 - T.v1) - (py - T.v1) * (T.u2 - T.u1);
+  const double w1 = (px - T.u2) * (T.v0 - T.v2) - (py - T.v2) * (T.u0 - T.u2);
+  const double w2 = (px - T.u0) * (T.v1 - T.v0) - (py - T.v0) * (T.u1 - T.u0);
+  if (!(w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0)) return;
+  const double b0 = w0 / T.area, b1 = w1 / T.area, b2 = w2 / T.area;
+  const double z = (b0 * T.z0 + b1 * T.z1) + b2 * T.z2;
+  const unsigned long long key = sortable_f64(z);
+  const int pix = r * res + c;
+  if (pass == 1) {
+    atomicMin(&zbuf[pix], key);
+  } else if (zbuf[pix] == key) {
+    int j = J.x;
+    double wm = w0;
+    if (w1 > wm) { j = J.y; wm = w1; }
+    if (w2 > wm) j = J.z;
+    atomicMin(&owner[pix], R2 + j);
+  }
+}
+
+// test hook (dh_dbg_footprint_tier): > 0 = the largest candidate box the thread tier walks itself, 0 = the default
+constexpr int FP_TIER_DEFAULT = 64;
+static int g_fp_tier = 0;
+static inline int fp_tier() { return g_fp_tier > 0 ? g_fp_tier : FP_TIER_DEFAULT; }
+
+// thread tier: one thread per (edit, triangle).  A box of more than `tier` candidates goes to the edit's list for the wave
+// tier (appended in pass 1; pass 2 replays the list); the result does not depend on `tier`: atomicMin commutes.
+__global__ void k_fp_tri(int pass, int res, int n_fg, const int* inv, const ObjTable tab, const double* uvz, const float* depth,
+                         float max_ratio, int tier, unsigned long long* zbuf, int* owner, int* big_list, int* big_count) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  const int nt = 2 * (res - 1) * (res - 1), R2 = res * res;
+  if (t >= nt) return;
+  FpTri T;
+  int3 J;
+  if (!fp_setup(t, e, res, n_fg, inv, tab, uvz, depth, max_ratio, T, J)) return;
+  const long long cand = (long long)(T.c1 - T.c0 + 1) * (T.r1 - T.r0 + 1);
+  if (cand > tier) {
+    if (pass == 1) big_list[(size_t)e * nt + atomicAdd(&big_count[e], 1)] = t;
+    return;
+  }
+  unsigned long long* zb = zbuf + (size_t)e * R2;
+  int* ow = owner + (size_t)e * R2;
+  for (int r = T.r0; r <= T.r1; ++r)
+    for (int c = T.c0; c <= T.c1; ++c) fp_bid(T, J, c, r, pass, res, R2, zb, ow);
+}
+
+// wave tier: one 64-lane wave per listed triangle, the lanes striding over its box
+constexpr int FP_WAVE_BLOCKS = 256;
+__global__ void __launch_bounds__(256) k_fp_wave(int pass, int res, int n_fg, const int* inv, const ObjTable tab, const double* uvz,
+                                                 const float* depth, float max_ratio, unsigned long long* zbuf, int* owner,
+                                                 const int* big_list, const int* big_count) {
+  const int e = blockIdx.y, lane = threadIdx.x & 63;
+  const int nt = 2 * (res - 1) * (res - 1), R2 = res * res;
+  const int n = big_count[e];
+  unsigned long long* zb = zbuf + (size_t)e * R2;
+  int* ow = owner + (size_t)e * R2;
+  for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < n; k += FP_WAVE_BLOCKS * 4) {
+    FpTri T;
+    int3 J;
+    if (!fp_setup(big_list[(size_t)e * nt + k], e, res, n_fg, inv, tab, uvz, depth, max_ratio, T, J)) continue;
+    const int W = T.c1 - T.c0 + 1, cand = W * (T.r1 - T.r0 + 1);          // (<= res * res: the box lies inside the image)
+    for (int i = lane; i < cand; i += 64) {
+      const int dr = i / W;
+      fp_bid(T, J, T.c0 + (i - dr * W), T.r0 + dr, pass, res, R2, zb, ow);
+    }
+  }
+}
+
+// with footprints a point is visible when it owns at least one pixel (vis zeroed before); keep = foreground-owned target
+// pixel inside the cleaned mask; the correspondences are one row per kept TARGET pixel, row-major
+__global__ void k_fp_vis(int R2, int n_fg, const int* owner, const uint8_t* raw_mask, uint8_t* vis, const uint8_t* clean,
+                         uint8_t* keep) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  if (p >= R2) return;
+  const size_t o = (size_t)e * R2 + p;
+  const bool fg = raw_mask[o] != 0;
+  if (vis && fg) vis[(size_t)e * n_fg + (owner[o] - R2)] = 1;
+  if (keep) keep[o] = (fg && clean[o]) ? 1 : 0;
+}
+
+__global__ void k_write_corr_target(int R2, int res, const int* fg_pix, const int* owner, const int* keep_idx, const int* counts,
+                                    int count_stride, size_t corr_stride, long long* corr) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  if (r >= counts[e * count_stride]) return;
+  const int t = keep_idx[(size_t)e * R2 + r];
+  const int p = fg_pix[owner[(size_t)e * R2 + t] - R2];
+  long long* c = corr + ((size_t)e * corr_stride + r) * 4;
+  c[0] = p % res;
+  c[1] = p / res;
+  c[2] = t % res;
+  c[3] = t / res;
 }
 
 __device__ __forceinline__ unsigned int sortable_f32(float x) {
@@ -341,13 +510,13 @@ __global__ void k_keep_flags(int n_fg, int R2, int P, const int* pix_arr, const 
 }
 
 __global__ void k_write_corr(int n_fg, int res, const int* fg_pix, const int* target_xy, const int* keep_idx,
-                             const int* counts, int count_stride, long long* corr) {
+                             const int* counts, int count_stride, size_t corr_stride, long long* corr) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
   if (r >= counts[e * count_stride]) return;
   int j = keep_idx[(size_t)e * n_fg + r];
   int p = fg_pix[j];
-  long long* c = corr + ((size_t)e * n_fg + r) * 4;
+  long long* c = corr + ((size_t)e * corr_stride + r) * 4;
   c[0] = p % res;
   c[1] = p / res;
   c[2] = target_xy[((size_t)e * n_fg + j) * 2 + 0];
@@ -907,6 +1076,13 @@ extern "C" int dh_dbg_cg_max_iter(int cap) {
   dh::g_cg_max_iter = cap;
   return DH_OK;
 }
+// test hook (host only): the largest candidate box of a footprint triangle that the thread tier draws itself in the calls that
+// follow (larger boxes go to the wave tier); 0 restores the default
+extern "C" int dh_dbg_footprint_tier(int tier) {
+  DH_REQUIRE(tier >= 0, "bad arguments");
+  dh::g_fp_tier = tier;
+  return DH_OK;
+}
 namespace dh {
 
 struct ReprojectWs {
@@ -928,9 +1104,14 @@ struct ReprojectWs {
   int2* offs_open;
   double *vx, *vr, *vp, *vq;
   CgSync* cgsync;
+  // footprints only (nothing is taken without them: the workspace of the other entries is what it was)
+  double* uvz;
+  int* inv;
+  int* big_list;
+  int* big_count;
 };
 
-static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w) {
+static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false) {
   const size_t R2 = (size_t)res * res, P = R2 + n_fg;
   w.xf = a.take<Xf>((size_t)K * M);
   w.cen = a.take<float>(4 * M);
@@ -953,6 +1134,13 @@ static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w) {
   w.vp = a.take<double>(K * R2);
   w.vq = a.take<double>(K * R2);
   w.cgsync = a.take<CgSync>(K);
+  w.uvz = nullptr; w.inv = nullptr; w.big_list = nullptr; w.big_count = nullptr;
+  if (footprints) {
+    w.uvz = a.take<double>((size_t)K * n_fg * 3);
+    w.inv = a.take<int>(R2);
+    w.big_list = a.take<int>((size_t)K * 2 * (res - 1) * (res - 1));
+    w.big_count = a.take<int>(K);
+  }
   return a.ok();
 }
 
@@ -965,6 +1153,16 @@ extern "C" int dh_reproject_objects_workspace_bytes(int res, int n_fg, int n_edi
   Arena a(nullptr, (size_t)-1);
   ReprojectWs w;
   carve(a, res, n_fg, n_edits, n_objects, w);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_reproject_footprints_workspace_bytes(int res, int n_fg, int n_edits, int n_objects, int footprints, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && n_fg >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
+  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
+  Arena a(nullptr, (size_t)-1);
+  ReprojectWs w;
+  carve(a, res, n_fg, n_edits, n_objects, w, footprints != 0);
   *bytes = a.off + 256;
   return DH_OK;
 }
@@ -1005,18 +1203,28 @@ extern "C" int dh_masked_centroid(const float* depth, const int32_t* fg_pix, int
 // n_objects bodies per edit: object m owns fg_pix[obj_start[m] .. obj_start[m + 1]) and row e * n_objects + m of xforms_host
 // (DH_SIMILARITY_ROW doubles: rotation, translation, scale, pivot).  Only k_centroid and k_points know about objects; from the
 // z-buffer on the point list is one list.  The one code path of the re-projection: dh_reproject_object_edits and
-// dh_reproject_edits are its scale-1 / no-pivot calls.
-extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+// dh_reproject_edits are its scale-1 / no-pivot calls, and all three are the footprints = 0 call of this entry.
+//
+// footprints = 1 (point mode's footprint splatting): the triangles between neighbouring points of one object bid in the same
+// z-buffer, in both passes; vis, the kept set and the correspondences are then taken per TARGET pixel (corr_capacity rows per
+// edit: res * res; without footprints n_fg).  max_ratio: 0 = none, else the depth-ratio guard of the triangles (finite, > 1).
+extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
                                              int n_objects, const int32_t* obj_start, int res, const float* grid_x,
                                              const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
                                              const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
                                              uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
                                              int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                             void* stream) {
+                                             void* stream, int footprints, float max_ratio, int corr_capacity) {
   DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
   DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
+  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
+  DH_REQUIRE(max_ratio == 0.f || (max_ratio > 1.f && max_ratio <= 3.4028234663852886e38f),
+             "footprint max_ratio must be 0 (none) or finite and > 1");
+  DH_REQUIRE(max_ratio == 0.f || footprints, "footprint max_ratio without footprints");
+  DH_REQUIRE((long long)corr_capacity >= (footprints ? (long long)res * res : (long long)n_fg),
+             "correspondence capacity too small (n_fg rows per edit without footprints, res * res with)");
   DH_REQUIRE(obj_start[0] == 0 && obj_start[n_objects] == n_fg, "obj_start must run from 0 to n_fg");
   for (int m = 0; m < n_objects; ++m) DH_REQUIRE(obj_start[m] < obj_start[m + 1], "obj_start must increase (no empty object)");
   // every row before any launch: a scale that is not positive and finite would collapse or mirror the object or spread NaN over
@@ -1034,7 +1242,8 @@ extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg
   const ObjTable tab = obj_table(M, obj_start, n_fg);
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
-  DH_REQUIRE(carve(a, res, n_fg, K, M, w), "workspace too small");
+  DH_REQUIRE(carve(a, res, n_fg, K, M, w, footprints != 0), "workspace too small");
+  const size_t corr_stride = (size_t)corr_capacity;
 
   int2 hc[MAX_OFFS], ho[MAX_OFFS];
   const int kc = res / 50, ko = res / 250;
@@ -1053,9 +1262,27 @@ extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg
 
   hipLaunchKernelGGL(k_centroid, dim3(M), dim3(CEN_CHUNK), 0, st, depth, fg_pix, tab, res, grid_x, grid_y, inv_fx, inv_fy,
                      w.cen);
-  hipLaunchKernelGGL(k_points, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_fg, res, grid_x,
-                     grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, tab, M, w.zbuf, w.pix, w.key);
+  // footprints: the triangle kernels run once per z-buffer pass, thread tier then wave tier (the list is built in pass 1)
+  const int n_tri = 2 * (res - 1) * (res - 1);
+  auto footprint_pass = [&](int pass) {
+    hipLaunchKernelGGL(k_fp_tri, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_fg, w.inv, tab, w.uvz, depth, max_ratio,
+                       fp_tier(), w.zbuf, w.owner, w.big_list, w.big_count);
+    hipLaunchKernelGGL(k_fp_wave, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_fg, w.inv, tab, w.uvz, depth, max_ratio,
+                       w.zbuf, w.owner, w.big_list, w.big_count);
+  };
+  if (footprints) {
+    DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
+    DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
+    hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
+    hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_fg, res, grid_x,
+                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, tab, M, w.zbuf, w.pix, w.key, w.uvz);
+    footprint_pass(1);
+  } else {
+    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_fg, res, grid_x,
+                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, tab, M, w.zbuf, w.pix, w.key, (double*)nullptr);
+  }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
+  if (footprints) footprint_pass(2);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), K), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, raw_mask,
                      disparity, w.minmax);
   hipLaunchKernelGGL(k_fg_vis, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, R2, P, res, w.pix, w.owner, vis,
@@ -1077,11 +1304,21 @@ extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg
     hipLaunchKernelGGL(k_morph, dim3(cdiv(R2, 256), K), dim3(256), 0, st, w.tmp_b, w.tmp_a, res, w.offs_open, no, 0);
     hipLaunchKernelGGL(k_morph, dim3(cdiv(R2, 256), K), dim3(256), 0, st, w.tmp_a, clean_mask, res, w.offs_open, no, 1);
   }
-  hipLaunchKernelGGL(k_keep_flags, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, R2, P, w.pix, vis, clean_mask,
-                     w.keep);
-  compact(w.keep, n_fg, K, n_fg, w.keep_idx, n_fg, counts + 0, 4, w.block_counts, st);
-  hipLaunchKernelGGL(k_write_corr, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, res, fg_pix, target_xy,
-                     w.keep_idx, counts, 4, (long long*)corr);
+  if (footprints) {
+    // per TARGET pixel: vis = the point owns a pixel, keep = foreground-owned and inside the cleaned mask.  The flags and the
+    // compacted list live in the in-fill's buffers (inpaint / unk: written again further down, after the rows are out)
+    DH_CHECK_HIP(hipMemsetAsync(vis, 0, (size_t)K * n_fg, st));
+    hipLaunchKernelGGL(k_fp_vis, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, n_fg, w.owner, raw_mask, vis, clean_mask, w.inpaint);
+    compact(w.inpaint, R2, K, R2, w.unk, R2, counts + 0, 4, w.block_counts, st);
+    hipLaunchKernelGGL(k_write_corr_target, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, res, fg_pix, w.owner, w.unk, counts, 4,
+                       corr_stride, (long long*)corr);
+  } else {
+    hipLaunchKernelGGL(k_keep_flags, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, R2, P, w.pix, vis, clean_mask,
+                       w.keep);
+    compact(w.keep, n_fg, K, n_fg, w.keep_idx, n_fg, counts + 0, 4, w.block_counts, st);
+    hipLaunchKernelGGL(k_write_corr, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, res, fg_pix, target_xy,
+                       w.keep_idx, counts, 4, corr_stride, (long long*)corr);
+  }
   hipLaunchKernelGGL(k_count_flags, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, vis, n_fg, counts, 4, 1);
   hipLaunchKernelGGL(k_normalize, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, disparity, w.minmax, bounds, raw_mask,
                      clean_mask, w.inpaint);
@@ -1103,6 +1340,18 @@ extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg
                      reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                             const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                             uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                             int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+  return dh_reproject_footprint_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx,
+                                      fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr,
+                                      counts, workspace, workspace_bytes, stream, 0, 0.f, n_fg);
 }
 
 // the rows of the rigid entries (8 doubles) widened to similarity rows: scale 1, no pivot.  The buffer outlives the call (the

@@ -171,8 +171,34 @@ def _rigid_rows(transforms, rows):
 MAX_OBJECTS = 8              # csrc/geometry.hip: the object table travels in the kernel arguments
 
 
+def check_footprints(footprints, footprint_max_ratio, what="footprints"):
+    """The footprint settings of a point-mode call -> (bool, None or the ratio as a float32 value).  ValueError for a ratio that
+    is not a finite float > 1 (as float32) and for a ratio without footprints.  Host only: no device work."""
+    footprints = bool(footprints)
+    if footprint_max_ratio is None:
+        return footprints, None
+    try:
+        with np.errstate(over="ignore"):
+            ratio = float(np.float32(footprint_max_ratio))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: footprint_max_ratio must be a number > 1 or None, got {footprint_max_ratio!r}") from None
+    if not (np.isfinite(ratio) and ratio > 1.0):
+        raise ValueError(f"{what}: footprint_max_ratio must be finite and > 1 (as float32), got {footprint_max_ratio!r}")
+    if not footprints:
+        raise ValueError(f"{what}: footprint_max_ratio={footprint_max_ratio!r} without footprints=True")
+    return footprints, ratio
+
+
+def mesh_has_no_footprints(footprints, footprint_max_ratio, what):
+    """Mesh mode draws triangles already: the footprint settings are checked as the point mode checks them, then
+    footprints=True is refused.  Host only."""
+    footprints, _ = check_footprints(footprints, footprint_max_ratio, what)
+    if footprints:
+        raise NotImplementedError(f"{what}: depth_transform_mode 'mesh' has no footprints (got footprints=True); use 'pc'")
+
+
 def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_depth_normalization=False,
-                    return_debug=False, device_correspondences=False):
+                    return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None):
     """K edits of one image.  transforms: list of (rot_angle_deg, rot_axis[3], translation[3]) or of
     (rot_angle_deg, rot_axis[3], translation[3], scale, pivot) (check_transform; `reproject_object_edits` says what scale
     and pivot do).
@@ -183,14 +209,15 @@ def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_
     them where the kernels wrote them, for callers that feed them straight back to the device (the batched edit path:
     `process_correspondences` accepts either) -- K device-to-host copies and K uploads less per call.
 
-    The one-object call of `reproject_object_edits`.
+    The one-object call of `reproject_object_edits` (footprints / footprint_max_ratio: see there).
     """
     return reproject_object_edits(depth, bg_depth, [fg_mask], intrinsics, [[tf] for tf in transforms],
-                                  use_input_depth_normalization, return_debug, device_correspondences)
+                                  use_input_depth_normalization, return_debug, device_correspondences, footprints,
+                                  footprint_max_ratio)
 
 
 def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_input_depth_normalization=False,
-                           return_debug=False, device_correspondences=False):
+                           return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None):
     """K edits of one image with M bodies each (not in the reference).  fg_masks: M pairwise disjoint [1,1,H,W] masks
     (1 <= M <= 8); bg_depth: the depth with ALL objects removed; edits: K lists of M (rot_angle_deg, rot_axis[3],
     translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.
@@ -211,7 +238,15 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
     Returns what `reproject_edits` returns: the correspondences [N,4] int64 (ox, oy, tx, ty) in point-list order (object
     order, row-major within an object).  The debug dict also has obj_start, the M' + 1 offsets of the kept objects'
     slices in fg_pix / vis / target_xy.
+
+    footprints=True (footprint splatting): the triangles between neighbouring points of ONE object bid in the
+    z-buffer too, so an enlarged or approaching object has no gaps between its points.  The correspondences are then one row
+    per foreground-owned target pixel inside the cleaned mask -- (ox, oy) of the owning point, (tx, ty) of the pixel -- in
+    ROW-MAJOR TARGET order, and there may be more of them than foreground points (at most H * W).  footprint_max_ratio: None
+    or a finite float > 1; a triangle whose source depths differ by more than this factor is left out (no sheets across a
+    depth step inside one mask).  ValueError for a bad ratio or a ratio without footprints, before any device work.
     """
+    footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
     fg_masks = list(fg_masks)
     M = len(fg_masks)
     if not 1 <= M <= MAX_OBJECTS:
@@ -275,8 +310,8 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
         _lib.check(L.dh_fg_pixel_list(_lib.ptr(masks_u8[m]), res, _lib.ptr(fg_pix[int(obj_start[j]):]), _lib.ptr(n_dev[j:]),
                                       _lib.ptr(ws_small), ws_small.numel(), st), "dh_fg_pixel_list")
     nbytes = ctypes.c_size_t()
-    _lib.check(L.dh_reproject_objects_workspace_bytes(res, n_fg, K, Mk, ctypes.byref(nbytes)),
-               "dh_reproject_objects_workspace_bytes")
+    _lib.check(L.dh_reproject_footprints_workspace_bytes(res, n_fg, K, Mk, int(footprints), ctypes.byref(nbytes)),
+               "dh_reproject_footprints_workspace_bytes")
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     zmap = torch.empty((K, res, res), dtype=torch.float32, device=dev)
     raw = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
@@ -284,15 +319,17 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
     disp = torch.empty((K, res, res), dtype=torch.float32, device=dev)
     vis = torch.empty((K, n_fg), dtype=torch.uint8, device=dev)
     txy = torch.empty((K, n_fg, 2), dtype=torch.int32, device=dev)
-    corr = torch.empty((K, n_fg, 4), dtype=torch.int64, device=dev)
+    cap = R2 if footprints else n_fg          # rows per edit: one per target pixel with footprints, one per point without
+    corr = torch.empty((K, cap, 4), dtype=torch.int64, device=dev)
     counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
     rows = _similarity_rows([tfs[m] for tfs in edits for m in kept])      # edit-major, K x Mk rows (C-contiguous)
-    _lib.check(L.dh_reproject_similarity_edits(
+    _lib.check(L.dh_reproject_footprint_edits(
         _lib.ptr(d), _lib.ptr(bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
         _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, K,
         rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bounds),
         _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
-        _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st), "dh_reproject_similarity_edits")
+        _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st, int(footprints), 0.0 if ratio is None else ratio, cap),
+        "dh_reproject_footprint_edits")
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
     out = []
@@ -342,9 +379,11 @@ def pivot_at_pixel(depth, intrinsics, x, y):
     return depth_to_world_coords(depth, intrinsics)[y, x].detach().to("cpu", torch.float32).clone()
 
 
-def transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
-                       use_input_depth_normalization=False, scale=None, pivot=None):
-    """The reference's transform_depth_pc (its parameters are a prefix); scale / pivot: see `reproject_object_edits`."""
+def transform_depth_footprints(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
+                               use_input_depth_normalization=False, scale=None, pivot=None, footprints=False,
+                               footprint_max_ratio=None):
+    """`transform_depth_pc` with the footprint settings of `reproject_object_edits` (point mode only).  `transform_depth` and
+    `transform_depth_pc` keep the parameter lists they have; `transform_depth_pc` is the footprints-off call of this one."""
     if rot_angle is None:
         rot_angle = 0.0
     if rot_axis is None:
@@ -352,8 +391,15 @@ def transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot
     if translation is None:
         translation = torch.tensor([0.0, 0.0, 0.0], dtype=torch.float32)
     (disp, corr), = reproject_edits(depth, bg_depth, fg_mask, intrinsics, [(rot_angle, rot_axis, translation, scale, pivot)],
-                                    use_input_depth_normalization)
+                                    use_input_depth_normalization, footprints=footprints, footprint_max_ratio=footprint_max_ratio)
     return disp, corr
+
+
+def transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
+                       use_input_depth_normalization=False, scale=None, pivot=None):
+    """The reference's transform_depth_pc (its parameters are a prefix); scale / pivot: see `reproject_object_edits`."""
+    return transform_depth_footprints(depth, bg_depth, fg_mask, intrinsics, rot_angle, rot_axis, translation,
+                                      use_input_depth_normalization, scale, pivot)
 
 
 MESH_BLUR_RADIUS = 1e-5      # depth_transform.py:152
@@ -393,10 +439,12 @@ def mesh_xform(depth, fg_mask, intrinsics, rot_angle, rot_axis, translation, piv
 
 
 def transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
-                         use_input_depth_normalization=False, return_debug=False, scale=None, pivot=None):
+                         use_input_depth_normalization=False, return_debug=False, scale=None, pivot=None, footprints=False,
+                         footprint_max_ratio=None):
     """depth_transform.py:91-195 with our own HIP triangle rasteriser in place of pytorch3d (parity unpinned).
     pivot: None or three floats, the point the object turns about in place of its centroid; a scale other than 1 raises
-    NotImplementedError before any device work (the mesh path has no scale)."""
+    NotImplementedError before any device work (the mesh path has no scale), and so does footprints=True (point mode only)."""
+    mesh_has_no_footprints(footprints, footprint_max_ratio, "transform_depth_mesh")
     pivot = _mesh_similarity(scale, pivot, "transform_depth_mesh")
     if depth.dim() != 4 or depth.shape[0] != 1:
         raise ValueError("Only batch size 1 is supported")
@@ -452,7 +500,8 @@ def transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, r
 def transform_depth(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
                     use_input_depth_normalization=False, depth_transform_mode="pc", scale=None, pivot=None):
     """The reference's transform_depth (depth_transform.py:73-89): its signature is a prefix and its return value unchanged.
-    scale / pivot (not in the reference): see `reproject_object_edits`; mesh mode takes a pivot and refuses a scale."""
+    scale / pivot (not in the reference): see `reproject_object_edits`; mesh mode takes a pivot and refuses a scale.
+    (Footprint splatting: `transform_depth_footprints`, point mode only.)"""
     if depth_transform_mode == "pc":
         return transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle, rot_axis, translation,
                                   use_input_depth_normalization, scale, pivot)

@@ -2,7 +2,7 @@
 import torch
 
 from . import conf as _conf
-from .depth_transform import laplacian_depth_blend, normalize_depth, transform_depth
+from .depth_transform import laplacian_depth_blend, normalize_depth, transform_depth, transform_depth_footprints
 from .guided_stable_diffuser import GuidedStableDiffuser
 from .stable_null_inverter import StableNullInverter
 
@@ -73,6 +73,20 @@ class DiffusionHandles:
             fg_mask = union.to(fg_mask[0].dtype)
         return laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15)
 
+    def _footprints(self, what):
+        """The optional top-level conf keys depth_transform_footprints (absent = false) and
+        depth_transform_footprint_max_ratio (absent = none) as the keywords of the depth_transform calls.  Checked on the host
+        (ValueError); a true depth_transform_footprints under a mode other than 'pc' raises NotImplementedError: the mesh mode
+        has no footprints.  No device work."""
+        from .depth_transform import check_footprints, mesh_has_no_footprints
+        conf = self.conf
+        get = conf.get if hasattr(conf, "get") else lambda k, d=None: getattr(conf, k, d)
+        fp, ratio = get("depth_transform_footprints", False), get("depth_transform_footprint_max_ratio", None)
+        if conf.depth_transform_mode != "pc":
+            mesh_has_no_footprints(fp, ratio, f"{what}: conf depth_transform_footprints")
+        fp, _ = check_footprints(fp, ratio, f"{what}: conf depth_transform_footprints")
+        return dict(footprints=fp, footprint_max_ratio=ratio)
+
     def transform_foreground_batch(self, depth, prompt, fg_mask, bg_depth, null_text_emb, init_noise, activations,
                                    transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
                                    streams=1, batch=None):
@@ -84,9 +98,10 @@ class DiffusionHandles:
         lanes.  Images are bit-identical to the one-stream result at the same batch."""
         from .depth_transform import reproject_edits
         K = len(transforms)
+        fp = self._footprints("transform_foreground_batch")
         with torch.no_grad():
             edits = reproject_edits(depth, bg_depth, fg_mask, self.diffuser.get_depth_intrinsics(device=depth.device),
-                                    transforms, use_input_depth_normalization, device_correspondences=True)
+                                    transforms, use_input_depth_normalization, device_correspondences=True, **fp)
             per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
             if streams <= 1 and per >= K:
                 imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in edits], null_text_emb, prompt,
@@ -103,6 +118,7 @@ class DiffusionHandles:
 
     def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences):
         from .depth_transform import reproject_object_edits
+        fp = self._footprints(what)
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no multi-object "
                                       "re-projection (only 'pc')")
@@ -118,7 +134,7 @@ class DiffusionHandles:
                 defaulted.append([(dflt(a, 0.0), dflt(ax, Y), dflt(tr, torch.zeros(3)), sc, pv) for a, ax, tr, sc, pv in full])
         edits = defaulted
         return reproject_object_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
-                                      use_input_depth_normalization, device_correspondences=device_correspondences)
+                                      use_input_depth_normalization, device_correspondences=device_correspondences, **fp)
 
     @staticmethod
     def _object_labels(fg_masks, object_weights):
@@ -200,6 +216,7 @@ class DiffusionHandles:
         Returns (images [K,3,H,W], [K disparities]) in input order.  'pc' re-projection only; one resolution; needs an engine
         with max_batch >= 2K."""
         from .depth_transform import check_transform, reproject_edits
+        fp = self._footprints("transform_foregrounds")
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
                                       "batched re-projection (only 'pc')")
@@ -268,7 +285,7 @@ class DiffusionHandles:
                            for i in idx]
                     res = reproject_edits(e0["depth"], e0["bg_depth"], e0["fg_mask"],
                                           self.diffuser.get_depth_intrinsics(device=e0["depth"].device), tfs,
-                                          use_input_depth_normalization, device_correspondences=True)
+                                          use_input_depth_normalization, device_correspondences=True, **fp)
                 for i, r in zip(idx, res):
                     reproj[i] = r
             items = [dict(latents=e["init_noise"], depth=d, uncond_embeddings=e["null_text_emb"], prompt=e["prompt"],
@@ -287,14 +304,19 @@ class DiffusionHandles:
         non-uniform scale of a turned object stretches along the un-turned camera axes); pivot -- None (= the centroid of the
         masked points) or a point in those coordinates (depth_transform.pivot_at_pixel) -- is what the object is scaled and
         turned about.  In 'pc' mode a magnified object leaves gaps between its points, bridged only up to the mask CLOSE's
-        element (res // 50); 'mesh' mode takes a pivot and refuses a scale (NotImplementedError)."""
+        element (res // 50) -- unless the conf has depth_transform_footprints: true (footprint splatting, point mode only;
+        depth_transform_footprint_max_ratio is its optional depth-ratio guard; depth_transform.reproject_object_edits);
+        'mesh' mode takes a pivot and refuses a scale and footprints (NotImplementedError)."""
+        fp = self._footprints("transform_foreground")
         with torch.no_grad():
-            edited_disparity, correspondences = transform_depth(
-                depth=depth, bg_depth=bg_depth, fg_mask=fg_mask,
-                intrinsics=self.diffuser.get_depth_intrinsics(device=depth.device),
-                rot_angle=rot_angle, rot_axis=rot_axis, translation=translation,
-                use_input_depth_normalization=use_input_depth_normalization,
-                depth_transform_mode=self.conf.depth_transform_mode, scale=scale, pivot=pivot)
+            geo = dict(depth=depth, bg_depth=bg_depth, fg_mask=fg_mask,
+                       intrinsics=self.diffuser.get_depth_intrinsics(device=depth.device),
+                       rot_angle=rot_angle, rot_axis=rot_axis, translation=translation,
+                       use_input_depth_normalization=use_input_depth_normalization, scale=scale, pivot=pivot)
+            if fp["footprints"]:          # ('pc' mode: _footprints refused the others; transform_depth keeps the reference's list)
+                edited_disparity, correspondences = transform_depth_footprints(**geo, **fp)
+            else:
+                edited_disparity, correspondences = transform_depth(**geo, depth_transform_mode=self.conf.depth_transform_mode)
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,

@@ -114,6 +114,27 @@ int dh_reproject_similarity_edits(const float* depth, const float* bg_depth, con
                                   float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
                                   uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
                                   void* workspace, size_t workspace_bytes, void* stream);
+/* Footprint splatting (not in the reference): dh_reproject_similarity_edits with, when footprints = 1, the triangles between
+ * neighbouring foreground points of ONE object bidding in the z-buffer of the points, so an enlarged or approaching object
+ * leaves no gaps between its points ("Footprint splatting", states the rules; all of it f64 in the written order).
+ *   footprints     0 = dh_reproject_similarity_edits in every output byte; 1 = on
+ *   max_ratio      0 = none; else finite and > 1: a triangle whose three SOURCE depths (f32) have zmax > fl32(zmin * max_ratio)
+ *                  is dropped (quads across a depth step inside one mask make no sheets).  Non-zero without footprints is refused.
+ *   corr_capacity  rows per edit of corr (its row stride): >= n_fg without footprints, >= res * res with; smaller is refused
+ * With footprints = 1: zmap, raw_mask, clean_mask, disparity and counts as before; vis[e][j] = point j owns at least one
+ * pixel; target_xy[e][j] stays the point's own rounded pixel; corr[e] has one row per foreground-owned target pixel inside the
+ * cleaned mask, (ox, oy) of the owning point and (tx, ty) of the pixel, in ROW-MAJOR TARGET order (there may be more rows than
+ * n_fg); counts[e][1] = number of visible points.  A refused argument is DH_ERR_ARG before any launch, the outputs untouched.
+ * The workspace is dh_reproject_footprints_workspace_bytes' (with footprints = 0: dh_reproject_objects_workspace_bytes'). */
+int dh_reproject_footprints_workspace_bytes(int res, int n_fg, int n_edits, int n_objects, int footprints, size_t* bytes);
+int dh_reproject_footprint_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                 int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                 const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                                 int n_edits, const double* xforms_host, const float* bounds,
+                                 float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                                 uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                                 void* workspace, size_t workspace_bytes, void* stream,
+                                 int footprints, float max_ratio, int corr_capacity);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);

@@ -3,7 +3,10 @@
 DH_OBJECTS=M (default 1): M = 1 is reproject_edits on the one-sphere scene; M = 2 is reproject_object_edits on the two-sphere
 scene of tests/multi_object_ref.py (both objects move in every edit; edit 0 is the one where object 0 hides object 1).
 DH_CALLS=n timed calls (default 5); the line reports their mean, median and minimum.
-DH_SCALE=s (default unset): a second line times the same call with the uniform scale s on every object (5-tuples)."""
+DH_SCALE=s (default unset): a second line times the same call with the uniform scale s on every object (5-tuples).
+DH_FOOTPRINTS=1 (default unset; combinable with DH_SCALE / DH_OBJECTS): every timed call is followed by the same call with
+footprint splatting on (profiles/footprints/).  DH_STEP=1: instead of the spheres, K copies of the step-scene edit of
+tests/footprints_ref.py with footprints on, once per tier threshold of DH_TIERS (comma-separated; 0 = the default)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -34,9 +37,18 @@ elif M == 2:
 else:
     sys.exit("DH_OBJECTS: 1 or 2")
 scale = float(os.environ["DH_SCALE"]) if os.environ.get("DH_SCALE") else None
+footprints = os.environ.get("DH_FOOTPRINTS", "0") not in ("", "0")
+CG_LDS, CG_MULTI = 8192, 65536          # dh_dbg_cg_limits: largest hole solved on chip / by the multi-workgroup CG
 
 
-def report(call, label):
+def solver(n):
+    return "-" if n == 0 else "lds" if n <= CG_LDS else "multi" if n <= CG_MULTI else "single"
+
+
+def report(call, label, **fp):
+    if fp:
+        label, inner = label + " footprints", call
+        call = lambda **kw: inner(**kw, **fp)
     for _ in range(2):
         call()
     torch.cuda.synchronize()
@@ -51,13 +63,35 @@ def report(call, label):
     times.sort()
     print(f"K={K} M={M} res={res}{label}: {sum(times)/n:.2f} ms per call (median {times[n // 2]:.2f}, min {times[0]:.2f}, {n} calls); "
           f"foreground points {int(dbg['fg_pix'].numel())}; correspondences {[int(c.shape[0]) for _, c in out]}; "
-          f"in-fill pixels {[int(v) for v in cn[:, 2]]}; CG iterations {[int(v) for v in cn[:, 3]]}")
+          f"in-fill pixels {[int(v) for v in cn[:, 2]]}; CG iterations {[int(v) for v in cn[:, 3]]}; "
+          f"solver {[solver(int(v)) for v in cn[:, 2]]}", flush=True)
 
 
+if os.environ.get("DH_STEP", "0") not in ("", "0"):
+    from diffusionhandles_amd import _lib
+    from diffusionhandles_amd.depth_transform import reproject_object_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import footprints_ref as F
+    depth, bg_depth, masks = F.step_scene(res)
+    depth, bg_depth, masks = depth.to(dev), bg_depth.to(dev), [m.to(dev) for m in masks]
+    edits = [[(tf[0], torch.tensor(tf[1]), torch.tensor(tf[2])) for tf in F.STEP_TURN]] * K
+    M = 1
+    call = lambda **kw: reproject_object_edits(depth, bg_depth, masks, intr, edits, **kw)
+    try:
+        for tier in [int(t) for t in os.environ.get("DH_TIERS", "0").split(",")]:
+            _lib.check(_lib.lib().dh_dbg_footprint_tier(tier), "dh_dbg_footprint_tier")
+            report(call, f" step scene, tier {tier if tier else 'default'}", footprints=True)
+    finally:
+        _lib.lib().dh_dbg_footprint_tier(0)
+    sys.exit(0)
 report(call, "")
+if footprints:
+    report(call, "", footprints=True)
 if scale is not None:
     if M == 1:
         tfs = [tf + (scale, None) for tf in tfs]
     else:
         edits = [[tf + (scale, None) for tf in e] for e in edits]
     report(call, f" scale={scale:g}")
+    if footprints:
+        report(call, f" scale={scale:g}", footprints=True)

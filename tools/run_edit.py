@@ -53,7 +53,25 @@ def load_config(path):
     return conf
 
 
-def parse():
+def apply_footprint_args(args, conf):
+    """--footprints / --footprint-max-ratio -> the optional conf keys depth_transform_footprints /
+    depth_transform_footprint_max_ratio (DiffusionHandles reads them for --scene, --test-set and --edit-batch alike), checked
+    as the library checks them (ValueError; NotImplementedError in mesh mode) before any engine is built.  Returns what the
+    report carries: {footprints, footprint_max_ratio}."""
+    from diffusionhandles_amd.depth_transform import check_footprints, mesh_has_no_footprints
+    if args.footprints:
+        conf["depth_transform_footprints"] = True
+    if args.footprint_max_ratio is not None:
+        conf["depth_transform_footprint_max_ratio"] = args.footprint_max_ratio
+    fp, ratio = conf.get("depth_transform_footprints", False), conf.get("depth_transform_footprint_max_ratio")
+    if conf.depth_transform_mode != "pc":
+        mesh_has_no_footprints(fp, ratio, "--footprints")
+    fp, ratio = check_footprints(fp, ratio, "--footprints")
+    args.footprint_report = dict(footprints=fp, footprint_max_ratio=ratio)
+    return args.footprint_report
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default=None)
     ap.add_argument("--out", default="edit_out")
@@ -86,7 +104,13 @@ def parse():
                          "1 = one transform_foreground per edit")
     ap.add_argument("--edit-batch-images", type=int, default=0,
                     help="--edit-batch: at most N scenes in one batch (each keeps 0.53 GB of activations resident at 512x512); 0 = no bound")
-    args = ap.parse_args()
+    ap.add_argument("--footprints", action="store_true",
+                    help="footprint splatting in 'pc' mode (conf key depth_transform_footprints): the triangles between "
+                         "neighbouring points of an object are drawn too, so an enlarged or approaching object has no gaps")
+    ap.add_argument("--footprint-max-ratio", type=float, default=None, metavar="R",
+                    help="with --footprints: leave out triangles whose source depths differ by more than the factor R > 1 "
+                         "(conf key depth_transform_footprint_max_ratio)")
+    args = ap.parse_args(argv)
     if args.edit_batch < 1 or (args.edit_batch > 1 and args.test_set is None):
         ap.error("--edit-batch K needs K >= 1, and K > 1 needs --test-set")
     if args.identity_batch < 1 or (args.identity_batch > 1 and args.test_set is None):
@@ -100,6 +124,7 @@ def main():
     if args.mode is not None:
         conf.depth_transform_mode = args.mode
     args.mode = conf.depth_transform_mode
+    apply_footprint_args(args, conf)
     state = {"dh": None}            # the engine is built on first use: a run that skips every scene never touches the GPU
 
     def handles(res):
@@ -164,6 +189,7 @@ def main():
                 f"{len(reports)} scenes</h3><table border='1' cellspacing='0' cellpadding='4'><tr><th>scene</th><th>edits</th>"
                 f"<th>identity s</th></tr>{rows}</table></body></html>")
     total = dict(test_set=set_name, scenes=reports, config=args.config, depth_transform_mode=conf.depth_transform_mode,
+                 **args.footprint_report,
                  edits_run=sum(1 for r in reports for e in r["edits"] if not e.get("skipped")),
                  edits_skipped=sum(1 for r in reports for e in r["edits"] if e.get("skipped")))
     if batch_seconds is not None:
@@ -288,7 +314,7 @@ def scene_identity(args, dh, p, out, identity=None):
     recon = dh.diffuser.decode_latent_image(latent)
     write_png(os.path.join(out, "recon.png"), recon[0].permute(1, 2, 0).float().cpu().numpy())
     report = dict(resolution=res, mode=args.mode, identity_s=round(t_identity, 2), identity_from_cache=bool(identity_from_cache),
-                  edits=[])
+                  edits=[], **getattr(args, "footprint_report", {}))
     if args.identity_batch > 1:
         report["identity_batch"] = args.identity_batch
     return depth, bg_depth, mask, img, null_text, noise, acts, report

@@ -44,9 +44,19 @@ class EnergyItem(ctypes.Structure):
                 ("fg_w", c_f), ("bg_w", c_f), ("grad_scale", c_f)]
 
 
+class GemmPlanQuery(ctypes.Structure):
+    """dh_gemm_plan_query: one GEMM launch described without pointers (dh_dbg_gemm_plan)"""
+    _fields_ = [("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("conv", ctypes.c_int32), ("hw", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("up", ctypes.c_int32), ("lda", ctypes.c_int64), ("ldc", ctypes.c_int64),
+                ("partial_elems", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("gn_HW", ctypes.c_int32), ("gn_G", ctypes.c_int32),
+                ("glub_f", ctypes.c_int32), ("xa_Nq", ctypes.c_int32), ("xa_Nk", ctypes.c_int32), ("xa_H", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/diffhandles_hip.h one to one
 SIGNATURES = {
     "dh_last_error": (ctypes.c_char_p, []),
+    # host-only query of the GEMM dispatch (declared in the header; tests/test_gemm_plan.py)
+    "dh_dbg_gemm_plan": (c_i, [ctypes.POINTER(GemmPlanQuery), ctypes.POINTER(ctypes.c_int32), c_i]),
     "dh_version": (c_i, []),
     "dh_device_count": (c_i, []),
     "dh_reproject_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),

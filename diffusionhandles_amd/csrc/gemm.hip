@@ -21,6 +21,9 @@
 // launch whose output is dy of a GroupNorm for that GroupNorm's BACKWARD statistics (gn_epi = 2; tools/fuzz_gn_epilogue.py).
 #include <stdlib.h>
 
+#include <string.h>
+
+#include <type_traits>
 #include <vector>
 
 #include <hip/hip_ext.h>
@@ -42,13 +45,14 @@ struct GemmProf {
 static GemmProf g_prof;
 static int g_buf_stage = 1;     // test hook (dh_dbg_gemm_stage): 0 = the address form of rounds 1-5 everywhere
 static int g_pp_force = 0;      // test hook (dh_dbg_gemm_family): 0 = policy, 1 = never k_gemm_pp, 2 = k_gemm_pp whenever it can carry the launch
-// what the last gemm_dispatch launched (test hook dh_dbg_gemm_last_tile): written after each decision, never read by the dispatch
-struct GemmTileReport {
-  int bm, bn, kg, stages, mw, splits, pp, gn_epi, reduce_gn;
-};
-static thread_local GemmTileReport g_last_tile;
-static thread_local int g_last_xattn = 0;           // the last launch carried a cross-attention in its epilogue (dh_dbg_gemm_xattn_carried)
-static thread_local long long g_xattn_total = 0;    // ... and how many launches of this thread have
+// the plan of this thread's last launch (test hooks dh_dbg_gemm_last_tile, dh_dbg_gemm_xattn_carried): written by launch_gemm after the
+// launch, never read by the planning
+static thread_local GemmPlan g_last_plan;
+// ... and the tile that launch really instantiated, written by launch_tile from its own template arguments (k_gemm_pp: bm, bn only):
+// dh_dbg_gemm_last_tile reports these, so a test that compares them with the plan sees a wrong arm of launch_planned's switch
+struct LaunchedTile { int bm, bn, kg, stages, mw; };
+static thread_local LaunchedTile g_launched_tile;
+static thread_local long long g_xattn_total = 0;    // how many launches of this thread have carried a cross-attention in their epilogue
 #ifdef DH_TUNING
 static unsigned long long* g_gemm_ts = nullptr;      // device buffer of 8 stamps (dh_dbg_gemm_timeline)
 #endif
@@ -1484,7 +1488,7 @@ __global__ void __launch_bounds__(256) k_splitk_reduce_gn(const GemmK p) {
 template <class T, int BM, int BN, int ST, int WG, int KG, int MW, bool BUF>
 static void launch_tile_b(int gm, bool lnf, dim3 grid, hipStream_t st, const GemmK& k, int glu) {
   constexpr int TH = 256 * WG * KG * MW;
-  // the tiles that carry the GEGLU epilogues (gemm_dispatch picks only these when glu != 0)
+  // the tiles that carry the GEGLU epilogues (pick_tile picks only these when glu != 0)
   constexpr bool GLUOK = WG == 1 && KG == 1 && ((BM == 256 && BN == 128 && MW == 2) || (BM == 128 && BN == 128 && MW == 2 && ST == 4) || (BM == 64 && BN == 64));
   if constexpr (GLUOK) {
     if (glu == 1 && lnf) { DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_DENSE, 0, WG, KG, MW, true, 1, BUF>)); return; }
@@ -1507,15 +1511,16 @@ static void launch_tile_b(int gm, bool lnf, dim3 grid, hipStream_t st, const Gem
     DH_GEMM_LAUNCH((k_gemm_dma<T, BM, BN, ST, GM_GENERIC, 0, WG, KG, MW>));
   }
 }
-// k.pp_a_bytes != 0: the operands fit buffer descriptors (gemm_dispatch) -- dense and stride-1 3x3 launches stage through them
+// k.pp_a_bytes != 0: the operands fit buffer descriptors (plan_extents) -- dense and stride-1 3x3 launches stage through them
 template <class T, int BM, int BN, int ST, int WG, int KG, int MW>
 static void launch_tile(int gm, bool lnf, dim3 grid, hipStream_t st, const GemmK& k, int glu = 0) {
-  g_last_tile.bm = BM; g_last_tile.bn = BN; g_last_tile.kg = KG; g_last_tile.stages = ST; g_last_tile.mw = MW;
+  g_launched_tile = LaunchedTile{BM, BN, KG, ST, MW};
   if (k.pp_a_bytes != 0 && gm != GM_GENERIC) launch_tile_b<T, BM, BN, ST, WG, KG, MW, true>(gm, lnf, grid, st, k, glu);
   else launch_tile_b<T, BM, BN, ST, WG, KG, MW, false>(gm, lnf, grid, st, k, glu);
 }
 #undef DH_GEMM_LAUNCH
 
+// ---- the plan: what one launch will be, decided on the host without touching the device (gemm_k.h: GemmPlan) --------------------------
 // Tile / split-K policy.  The constants are the round-1/2 bench.py A/B winners; a tuning build (-DDH_TUNING,
 // tools/lab.sh build-tuning) reads them from the environment instead, the product library carries no knobs.
 #ifdef DH_TUNING
@@ -1523,260 +1528,353 @@ static void launch_tile(int gm, bool lnf, dim3 grid, hipStream_t st, const GemmK
 #else
 #define DH_KNOB(name, env, dflt) constexpr int name = (dflt)
 #endif
+DH_KNOB(kSplitTiles, "DH_SPLITK_TILES", 200);     // split K only under this many output tiles ...
+DH_KNOB(kSplitMinK, "DH_SPLITK_MINKT", 32);       // ... and from this many K tiles (24 -> 32: +1 % on the guided step)
+DH_KNOB(kSplitTarget, "DH_SPLITK_TARGET", 256);   // workgroups aimed at
+DH_KNOB(kBigTiles, "DH_BIG_TILES", 128);          // fewer big tiles than this and a short K loop: 64x64 tiles (48 -> 128: +1 % step, +2 % at 768^2)
+DH_KNOB(kNarrowTiles, "DH_NARROW_TILES", 40);     // long-K GEMMs with at most this many 128x128 tiles use the 128x64 tile
+DH_KNOB(kN320, "DH_GEMM_N320", 224);              // row tiles from which N = 320 runs as one 128x320 tile (256 at batch 8: pass -4.5 %; 144 tiles lose 1 %)
+DH_KNOB(kMwBlocks, "DH_GEMM_MW", 64);             // 256x128 eight-wave tiles from this many of them
+DH_KNOB(kMwShortK, "DH_GEMM_MW_SHORTK", 128);     // ... from this many of them when the K loop is short (pick_tile)
+DH_KNOB(kT160, "DH_GEMM_T160", 224);              // fewest 128x160 tiles for that tile (0 = never)
+DH_KNOB(kKg2MinKt, "DH_KG2_MINKT", 4);            // K tiles per split from which the 128x64 tile splits K over two wave groups (16 -> 4: +1.4 % step)
+DH_KNOB(kManyBlocks, "DH_GEMM_MANY", 512);        // 128x128 grids from this size use two stages (two workgroups per CU)
+DH_KNOB(kMw128, "DH_GEMM_MW128", 1);              // min K tiles for eight waves on the 128x128 tile
+DH_KNOB(kTwoPerCu, "DH_GEMM_TWO_PER_CU", 1);      // 128x64 grids of 257..512 workgroups: the 74-KB three-stage tile, two workgroups per CU (pick_instance)
+#undef DH_KNOB
 
-template <class T>
-static void gemm_dispatch(GemmK k, size_t partial_elems, hipStream_t st, int* gn_done, int* lnb_done, int* xa_done, int dtype) {
-  DH_KNOB(kSplitTiles, "DH_SPLITK_TILES", 200);     // split K only under this many output tiles ...
-  DH_KNOB(kSplitMinK, "DH_SPLITK_MINKT", 32);       // ... and from this many K tiles (24 -> 32: +1 % on the guided step)
-  DH_KNOB(kSplitTarget, "DH_SPLITK_TARGET", 256);   // workgroups aimed at
-  DH_KNOB(kBigTiles, "DH_BIG_TILES", 128);          // fewer big tiles than this and a short K loop: 64x64 tiles (48 -> 128: +1 % step, +2 % at 768^2)
-  DH_KNOB(kNarrowTiles, "DH_NARROW_TILES", 40);     // long-K GEMMs with at most this many 128x128 tiles use the 128x64 tile
-  DH_KNOB(kN320, "DH_GEMM_N320", 224);              // row tiles from which N = 320 runs as one 128x320 tile (256 at batch 8: pass -4.5 %; 144 tiles lose 1 %)
-  DH_KNOB(kMwBlocks, "DH_GEMM_MW", 64);             // 256x128 eight-wave tiles from this many of them
-  DH_KNOB(kKg2MinKt, "DH_KG2_MINKT", 4);            // K tiles per split from which the 128x64 tile splits K over two wave groups (16 -> 4: +1.4 % step)
-  DH_KNOB(kManyBlocks, "DH_GEMM_MANY", 512);        // 128x128 grids from this size use two stages (two workgroups per CU)
-  DH_KNOB(kMw128, "DH_GEMM_MW128", 1);              // min K tiles for eight waves on the 128x128 tile
-  DH_KNOB(kTwoPerCu, "DH_GEMM_TWO_PER_CU", 1);      // 128x64 grids of 257..512 workgroups: the 74-KB three-stage tile, two workgroups per CU (see the dispatch below)
-#ifdef DH_TUNING
-  DH_KNOB(kWnt, "DH_W_NT", 0);                      // non-temporal weight DMA for GEMMs of at most this many row tiles (0 = never)
-#endif
-  const bool lnf = k.ln_s != nullptr;
-  g_last_tile = GemmTileReport{};
-  int BM = 128, BN = (k.N % 128 == 0) ? 128 : 64;
+static int glu_form(const GemmK& k) { return k.glu_y ? 1 : (k.glub_x ? 2 : 0); }
+static int gemm_mode(const GemmK& k) {
+  if (k.mode == A_DENSE) return GM_DENSE;
+  return (k.mode == A_CONV3 && k.stride == 1 && k.up == 0 && k.pad == 1) ? GM_CONV_S1 : GM_GENERIC;
+}
+
+// Step 1, the k_gemm_dma tile.  The three flags say which rule set it: later rules and the cross-attention form ask for them.
+struct TilePick { int bm, bn; bool n320, mw2, t160; };
+static TilePick pick_tile(const GemmK& k, int glu, bool lnf) {
+  TilePick t{128, (k.N % 128 == 0) ? 128 : 64, false, false, false};
   const int ktiles = k.K / BK;
-  // grids that fill the chip with 256- / 128-row tiles and carry the plain epilogue: the eight-wave ping-pong kernel (gemm_pp.hip)
-  PpPlan pp;
-  const bool use_pp = gemm_pp_plan(k, partial_elems, g_pp_force, &pp);
-  if (BN == 128 && ktiles >= 16 && cdiv(k.M, 128) * cdiv(k.N, 128) <= kNarrowTiles) BN = 64;
+  if (t.bn == 128 && ktiles >= 16 && cdiv(k.M, 128) * cdiv(k.N, 128) <= kNarrowTiles) t.bn = 64;
   // few output tiles and a K loop too short to be worth slabs + a reduce launch: 64x64 tiles
   // (M=256 N=1280 K=1280: 16.7 -> 8.8 us; M=1024 N=640 K=640: 12.1 -> 8.9 us)
-  if (k.M <= 64 || (cdiv(k.M, 128) * cdiv(k.N, BN) < kBigTiles && ktiles < kSplitMinK)) { BM = 64; BN = 64; }
+  if (k.M <= 64 || (cdiv(k.M, 128) * cdiv(k.N, t.bn) < kBigTiles && ktiles < kSplitMinK)) { t.bm = 64; t.bn = 64; }
   // N = 320 (the 64x64-latent convolutions and linears) with enough rows to fill the chip: one 128x320 tile per 128 rows,
   // so the A tile is staged once instead of five times (batched edits; a single image has only 32 such tiles)
   // (also N = 640 / 960 -- the fused q|k|v projection of the 64x64-latent level -- as two / three such column tiles: the A tile is
   //  staged three times instead of fifteen)
-  const bool n320 = kN320 > 0 && k.N % 320 == 0 && k.N <= 960 && !lnf && BM == 128 && BN == 64 && cdiv(k.M, 128) >= kN320;
-  if (n320) BN = 320;
+  t.n320 = kN320 > 0 && k.N % 320 == 0 && k.N <= 960 && !lnf && t.bm == 128 && t.bn == 64 && cdiv(k.M, 128) >= kN320;
+  if (t.n320) t.bn = 320;
   // grids that fill the machine: 256x128 tiles, eight waves (see MW)
   // (not when M <= 256 leaves a single row of 256-row tiles on fewer than half of the CUs: two rows of 128x128 eight-wave
   // tiles put twice the workgroups on the same K loop -- M = 256, N = 10240, K = 1280: 22.4 -> 15.5 us)
   // and in general not for short K loops on fewer than half of the CUs (per-shape sweep, tools/sweep_gemm_shapes.py:
   // M = 1024, N = 2560, K = 640: 16.6 -> 12.8 us; M = 512, N = 5120, K = 1280: 25.2 -> 20.2 us as 128x128 tiles); long K
   // loops keep the big tile, they split K over workgroups anyway
-  DH_KNOB(kMwShortK, "DH_GEMM_MW_SHORTK", 128);
   const long tiles256 = (long)cdiv(k.M, 256) * cdiv(k.N, 128);
-  const bool mw2 = kMwBlocks > 0 && k.N % 128 == 0 && tiles256 >= kMwBlocks &&
-                   !(k.M <= 256 && k.M > 128 && cdiv(k.N, 128) < 128) && (tiles256 >= kMwShortK || ktiles >= kSplitMinK);
+  t.mw2 = kMwBlocks > 0 && k.N % 128 == 0 && tiles256 >= kMwBlocks &&
+          !(k.M <= 256 && k.M > 128 && cdiv(k.N, 128) < 128) && (tiles256 >= kMwShortK || ktiles >= kSplitMinK);
   // (tried and dropped, profiles/r04_ab_two128.txt: a 256x128 grid of 129..255 workgroups -- M = 8192, N = 640 at batch 8: 160 -- as twice
   //  as many 128x128 two-stage tiles, two per CU: conv K = 5760 91.6 -> 95.9 us, batch-8 forward 12.74 -> 13.05 ms; the smaller tile
   //  stages a third more bytes per flop and that outweighs the 96 CUs it wakes up)
-  if (mw2) { BM = 256; BN = 128; }
+  if (t.mw2) { t.bm = 256; t.bn = 128; }
   // GEGLU epilogues (dense, N a multiple of 128 -- of 64 for the column-split backward -- never split): 64x64, 128x128 or 256x128
   // tiles only
-  const int glu = k.glu_y ? 1 : (k.glub_x ? 2 : 0);
-  if (glu && !(BM == 64 && BN == 64)) { BM = mw2 ? 256 : 128; BN = 128; }
+  if (glu && !(t.bm == 64 && t.bn == 64)) { t.bm = t.mw2 ? 256 : 128; t.bn = 128; }
   // the column-split GEGLU backward: no tile straddles the seam (the last column tile may run past N: W is readable there)
-  if (glu == 2 && !glub_split_ok(BN, k.glub_f)) { BM = 64; BN = 64; }
+  if (glu == 2 && !glub_split_ok(t.bn, k.glub_f)) { t.bm = 64; t.bn = 64; t.mw2 = false; }
   // 128x160 tiles (four wave rows of 32 x 160) where exactly they fill the chip in ONE round and nothing needs K split: the
   // batched 32x32-latent level (M = 8192, N = 640: 64 x 4 = 256 workgroups instead of 160 256x128 ones) and its kin
-  DH_KNOB(kT160, "DH_GEMM_T160", 224);              // fewest 128x160 tiles for that (0 = never)
   const long tiles160 = (long)cdiv(k.M, 128) * (k.N / 160);
-  const bool t160 = kT160 > 0 && k.N % 160 == 0 && !lnf && !glu && !n320 && BM != 64 && tiles160 >= kT160 && tiles160 <= 256;
-  if (t160) { BM = 128; BN = 160; }
-  if (use_pp) { BM = pp.bm; BN = pp.bn; }
-  const int tm = cdiv(k.M, BM), tn = cdiv(k.N, BN), tiles = tm * tn;
-  int splits = 1;
-  if (use_pp) splits = pp.splits;
-  else if (k.partial && !lnf && !glu && tiles < kSplitTiles && ktiles >= kSplitMinK) {
-    splits = kSplitTarget / tiles;
-    if (splits > ktiles / 4) splits = ktiles / 4;
-    if (splits > 32) splits = 32;
-    const size_t fit = partial_elems / ((size_t)k.M * k.N);
-    if ((size_t)splits > fit) splits = (int)fit;
-    if (splits < 1) splits = 1;
+  t.t160 = kT160 > 0 && k.N % 160 == 0 && !lnf && !glu && !t.n320 && t.bm != 64 && tiles160 >= kT160 && tiles160 <= 256;
+  if (t.t160) { t.bm = 128; t.bn = 160; }
+  return t;
+}
+
+// Step 2, the K split of a k_gemm_dma launch (k_gemm_pp brings its own: gemm_pp_plan)
+static int pick_splits(const GemmK& k, size_t partial_elems, int tiles, int glu, bool lnf) {
+  const int ktiles = k.K / BK;
+  if (!(k.partial && !lnf && !glu && tiles < kSplitTiles && ktiles >= kSplitMinK)) return 1;
+  return clamp_splits(kSplitTarget / tiles, ktiles / 4, 32, k, partial_elems);
+}
+
+// steps 1 and 2 together: the kernel family, its tile, the K split asked for (plan_finish cuts K evenly and may end with fewer)
+struct PlanDraft { bool pp; TilePick t; int splits; };
+static PlanDraft plan_draft(const GemmK& k, size_t partial_elems, const GemmHooks& h) {
+  const int glu = glu_form(k);
+  const bool lnf = k.ln_s != nullptr;
+  PlanDraft d;
+  // grids that fill the chip with 256- / 128-row tiles and carry the plain epilogue: the eight-wave ping-pong kernel (gemm_pp.hip)
+  PpPlan pp;
+  d.pp = gemm_pp_plan(k, partial_elems, h, &pp);
+  d.t = pick_tile(k, glu, lnf);
+  if (d.pp) { d.t.bm = pp.bm; d.t.bn = pp.bn; d.splits = pp.splits; }
+  else d.splits = pick_splits(k, partial_elems, cdiv(k.M, d.t.bm) * cdiv(k.N, d.t.bn), glu, lnf);
+  return d;
+}
+
+// Step 3, the descriptor extents: buffer-descriptor staging (BUF instantiations) whenever both operands lie below 2 GiB and the rows
+// are 16-byte aligned (every launch of the U-Net / VAE / text engines; anything else keeps the address form).  k_gemm_pp always
+// stages through descriptors (gemm_pp_plan has checked the same bounds).
+static void plan_extents(GemmPlan& p, const GemmK& k, const GemmHooks& h) {
+  const size_t ab = gemm_a_bytes(k);
+  if (p.pp) { p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)((size_t)k.N * k.K * 2); p.buf = 1; return; }
+  const size_t wb = (size_t)align_up((size_t)k.N, 64) * k.K * 2;
+  const bool conv_ok = k.mode == A_DENSE || (k.Cin % 64 == 0 && k.K == 9 * k.Cin);
+  if ((h.buf_stage & 1) && ab > 0 && conv_ok && ab + (size_t)(k.Win + 1) * k.lda * 2 < 0x7ff00000ull && wb < 0x7ff00000ull && k.lda % 8 == 0 &&
+      ((size_t)k.A & 15) == 0 && ((size_t)k.W & 15) == 0) {
+    p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
   }
-#ifdef DH_TUNING
-  // per-shape policy search (tools/sweep_gemm_shapes.py): DH_GEMM_LOG=1 prints every dispatch, DH_FORCE_TILE / DH_FORCE_SPLITS override
-  // the choice (1 = 64x64, 2 = 128x64 two K groups, 3 = 128x64, 4 = 128x128 eight waves, 5 = 128x128, 6 = 256x128 eight waves, 7 = 128x160)
-  static const int kLog = getenv("DH_GEMM_LOG") ? atoi(getenv("DH_GEMM_LOG")) : 0;
-  const int kForceTile = getenv("DH_FORCE_TILE") ? atoi(getenv("DH_FORCE_TILE")) : 0;          // (re-read per dispatch: one process sweeps)
-  const int kForceSplits = getenv("DH_FORCE_SPLITS") ? atoi(getenv("DH_FORCE_SPLITS")) : 0;
-  int force_tile = 0;
-  if (kForceTile && !use_pp && !(k.glu_y || k.glub_x)) {
-    const int fbm = kForceTile == 1 ? 64 : (kForceTile == 6 ? 256 : 128), fbn = kForceTile == 7 ? 160 : ((kForceTile <= 3) ? 64 : 128);
-    if ((k.N % fbn == 0 || fbn == 64) && !(fbn == 160 && lnf)) { BM = fbm; BN = fbn; force_tile = kForceTile; }
-  }
-  if (kForceSplits && !use_pp && k.partial && !lnf) {
-    splits = kForceSplits;
-    if (splits > ktiles / 2) splits = ktiles / 2 > 0 ? ktiles / 2 : 1;
-    const size_t fit = partial_elems / ((size_t)k.M * k.N);
-    if ((size_t)splits > fit) splits = (int)fit;
-    if (splits < 1) splits = 1;
-  }
-  if (kLog) fprintf(stderr, "GEMMLOG M=%d N=%d K=%d mode=%d lnf=%d gn=%d gnb=%d bias=%d R=%d rowvec=%d | pp=%d BM=%d BN=%d splits=%d\n", k.M, k.N, k.K,
-                    k.mode == A_DENSE ? 0 : (k.mode == A_CONV3 && k.stride == 1 && k.up == 0 ? 1 : 2), (int)lnf, k.gn_part != nullptr,
-                    k.gnb_x != nullptr, k.bias != nullptr, k.R != nullptr, k.rowvec != nullptr, (int)use_pp, BM, BN, splits);
-#endif
-  const int tiles_per_split = cdiv(ktiles, splits);
-  splits = cdiv(ktiles, tiles_per_split);
-  k.splits = splits;
-  k.k_per_split = tiles_per_split * BK;
-  // GroupNorm statistics in the epilogue: an unsplit k_gemm_dma launch whose output the next op normalises (forward statistics
-  // only; tiles of whole images' rows, groups no wider than a column tile, at most 64 "slices" = 2 per row tile for the merge
-  // in k_gn_apply).  *gn_done then carries the slice count (> 1) instead of 1.
-  k.gn_epi = 0; k.gn_cpg = 0;
-  if ((g_buf_stage & 4) == 0 && splits == 1 && !use_pp && gn_epi_fwd_tile(BN, glu, lnf) && k.gn_part && !k.gnb_x && gn_done && k.gn_G > 0 &&
-      k.gn_HW > 0 && k.C && k.wide_store && k.M % k.gn_HW == 0 && k.gn_HW % BM == 0 && k.N % k.gn_G == 0 && k.N % BN == 0) {
-    const int cpg = k.N / k.gn_G, sx = 2 * (k.gn_HW / BM);
-    if (cpg >= 8 && cpg <= BN && sx <= 64) { k.gn_epi = 1; k.gn_cpg = cpg; k.gn_S = sx; }
-  }
-  // ... and the BACKWARD slice statistics (sum d, sum d * xhat) when the output is dy of a GroupNorm: 64-column tiles of up to 128
-  // rows, no bias / residual / per-image vector (an input-gradient GEMM has none; the residual's prefetch registers carry the
-  // GroupNorm's input tile).  *gn_done = the slice count, as above.
-  if ((g_buf_stage & 8) == 0 && splits == 1 && !use_pp && gn_epi_bwd_tile(BM, BN, 1, glu, lnf) && k.gn_part && k.gnb_x && gn_done && k.gn_G > 0 &&
-      k.gn_HW > 0 && k.C && k.wide_store && k.pre_r && !k.R && !k.bias && !k.rowvec && !k.act_silu && k.M % k.gn_HW == 0 && k.gn_HW % BM == 0 &&
-      k.N % k.gn_G == 0 && k.N % BN == 0 && (((size_t)k.gnb_x | (size_t)(k.gnb_ldx * 2)) & 7) == 0) {
-    const int cpg = k.N / k.gn_G, sx = 2 * (k.gn_HW / BM);
-    if (cpg >= 8 && cpg <= BN && sx <= 64) { k.gn_epi = 2; k.gn_cpg = cpg; k.gn_S = sx; }
-  }
-#ifdef DH_TUNING
-  k.w_nt = kWnt > 0 && tm <= kWnt;
-  static const int kLnfAbl = getenv("DH_LNF_ABL") ? atoi(getenv("DH_LNF_ABL")) : 0;
-  k.lnf_abl = kLnfAbl;
-  k.ts = g_gemm_ts;
-#endif
-#ifdef DH_TUNING
-  dim3 grid(force_tile ? cdiv(k.M, BM) : tm, force_tile ? cdiv(k.N, BN) : tn, splits);
-#else
-  dim3 grid(tm, tn, splits);
-#endif
-  int gm = GM_GENERIC;
-  if (k.mode == A_DENSE) gm = GM_DENSE;
-  else if (k.mode == A_CONV3 && k.stride == 1 && k.up == 0 && k.pad == 1) gm = GM_CONV_S1;
-  // buffer-descriptor staging (BUF instantiations) whenever both operands lie below 2 GiB and the rows are 16-byte aligned
-  // (every launch of the U-Net / VAE / text engines; anything else keeps the address form)
-  if (!use_pp) {
-    k.pp_a_bytes = 0; k.pp_w_bytes = 0;
-    size_t ab = 0;
-    if (k.mode == A_DENSE) ab = ((size_t)(k.M - 1) * k.lda + k.K) * 2;
-    else if (k.Hout > 0 && k.Wout > 0 && k.M % (k.Hout * k.Wout) == 0)
-      ab = (size_t)(k.M / (k.Hout * k.Wout)) * k.Hin * k.Win * (size_t)k.lda * 2;
-    const size_t wb = (size_t)align_up((size_t)k.N, 64) * k.K * 2;
-    const bool conv_ok = k.mode == A_DENSE || (k.Cin % 64 == 0 && k.K == 9 * k.Cin);
-    if ((g_buf_stage & 1) && ab > 0 && conv_ok && ab + (size_t)(k.Win + 1) * k.lda * 2 < 0x7ff00000ull && wb < 0x7ff00000ull && k.lda % 8 == 0 &&
-        ((size_t)k.A & 15) == 0 && ((size_t)k.W & 15) == 0) {
-      k.pp_a_bytes = (unsigned)ab; k.pp_w_bytes = (unsigned)wb;
-    }
-  }
-  // Cross-attention in the epilogue (EPI_XATTN): the q projection of a cross-attention whose 64-column tiles are whole heads and
-  // whose row tiles lie inside one image (a tile never mixes two images' K / V), unsplit, with the plain bias-only epilogue, at
-  // most XA_KEYS keys, every operand 16-byte aligned.  *xa_done tells the caller that the attention has been launched with it.
-  k.xa = 0;
-  const bool xa_bwd = k.xa_dq != nullptr;
-  if (k.xa_o && xa_done && (g_buf_stage & (xa_bwd ? 32 : 16)) == 0 && splits == 1 && !use_pp && !glu && !t160 && !n320 && !mw2 &&
-      xattn_epi_tile(BM, BN, 1, 1, k.pp_a_bytes != 0) && gm == GM_DENSE && k.xa_Nk >= 1 && k.xa_Nk <= XA_KEYS && k.xa_Nq > 0 &&
-      k.N == 64 * k.xa_H && k.M % k.xa_Nq == 0 && k.M < (1 << 22) && (k.M == k.xa_Nq || k.xa_Nq % BM == 0) && k.C && k.wide_store && k.pre_r &&
-      !k.R && !k.rowvec && !k.act_silu && !k.gn_epi && k.xa_lse && k.xa_ldk % 8 == 0 && k.xa_ldo % 8 == 0 &&
-      (((size_t)k.xa_k | (size_t)k.xa_v | (size_t)k.xa_o) & 15) == 0 &&
-      (!xa_bwd || (!lnf && !k.bias && k.xa_q && k.xa_ldq % 8 == 0 && k.xa_lddq % 8 == 0 && (((size_t)k.xa_q | (size_t)k.xa_dq) & 15) == 0)))
-    k.xa = xa_bwd ? 2 : 1;
-#ifdef DH_TUNING
-  if (force_tile) k.xa = 0;
-#endif
-  const int epi = k.xa == 2 ? EPI_XATTN_DQ : (k.xa ? EPI_XATTN : glu);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_prof.on) {
-    if (g_prof.used + 2 > g_prof.ev.size()) {
-      const size_t old = g_prof.ev.size();
-      g_prof.ev.resize(old + 4096);
-      for (size_t i = old; i < g_prof.ev.size(); ++i) (void)hipEventCreate(&g_prof.ev[i]);
-    }
-    e0 = g_prof.ev[g_prof.used++];
-    e1 = g_prof.ev[g_prof.used++];
-    g_prof.flops += 2.0 * (double)k.M * (double)k.N * (double)k.K;
-    // every operand once, in its storage type: the A source (dense rows; for a convolution the source image, not its im2col
-    // view), the weights, the output (the GEGLU forms: what they read and write instead), the residual
-    const double esz = 2.0;
-    double a_elems = (double)k.M * k.K;
-    if (k.mode != A_DENSE && k.Hout > 0 && k.Wout > 0) a_elems = (double)k.M / ((double)k.Hout * k.Wout) * k.Hin * k.Win * k.Cin;
-    double c_elems = (double)k.M * k.N * (k.C ? 1.0 : 0.0) + (k.R ? (double)k.M * k.N : 0.0);
-    if (k.glu_y) c_elems += 0.5 * (double)k.M * k.N;
-    // saved pre-activations read [M][2F], their gradient written [M][2F] (C holds only the columns past F)
-    if (k.glub_x) c_elems += 4.0 * (double)k.M * k.glub_f - (k.C ? (double)k.M * k.glub_f : 0.0);
-    if (k.gn_epi == 2) c_elems += (double)k.M * k.N;       // the GroupNorm input tile the backward statistics read
-    if (k.xa == 1) c_elems += (k.xa_save ? 1.0 : 0.0) * (double)k.M * k.N + 2.0 * (k.M / k.xa_Nq) * (double)k.xa_Nk * k.N;   // o for q (q too when saved), the heads' K and V
-    if (k.xa == 2) c_elems += 2.0 * (double)k.M * k.N + 2.0 * (k.M / k.xa_Nq) * (double)k.xa_Nk * k.N;     // dq for dO; q, o, K and V read
-    g_prof.bytes += esz * (a_elems + (double)k.N * k.K + c_elems);
-    g_prof.e0 = e0; g_prof.e1 = e1;
-  }
-#ifdef DH_TUNING
-  // ablations of the K loop (timing only): 1 = no LDS reads / MFMA, 2 = no DMA in the loop, 3 = 1 on the dense kernel
-  static const int kAbl = getenv("DH_GEMM_ABLATE") ? atoi(getenv("DH_GEMM_ABLATE")) : 0;
-  if (kAbl == 1 && BM == 128 && BN == 128) { hipLaunchKernelGGL((k_gemm_dma<T, 128, 128, 4, GM_CONV_S1, 1>), grid, dim3(256), 0, st, k); }
-  else if (kAbl == 2 && BM == 128 && BN == 128) { hipLaunchKernelGGL((k_gemm_dma<T, 128, 128, 4, GM_CONV_S1, 2>), grid, dim3(256), 0, st, k); }
-  else if (kAbl == 3 && BM == 128 && BN == 128) { hipLaunchKernelGGL((k_gemm_dma<T, 128, 128, 4, GM_DENSE, 1>), grid, dim3(256), 0, st, k); }
-  else if (kAbl == 1 && mw2 && gm == GM_CONV_S1) { hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_CONV_S1, 1, 1, 1, 2>), grid, dim3(512), 0, st, k); }
-  else if (kAbl == 2 && mw2 && gm == GM_CONV_S1) { hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_CONV_S1, 2, 1, 1, 2>), grid, dim3(512), 0, st, k); }
-  else if (kAbl == 1 && mw2 && gm == GM_DENSE && !lnf) { hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_DENSE, 1, 1, 1, 2>), grid, dim3(512), 0, st, k); }
-  else if (kAbl == 2 && mw2 && gm == GM_DENSE && !lnf) { hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_DENSE, 2, 1, 1, 2>), grid, dim3(512), 0, st, k); }
-  else if (force_tile == 1) launch_tile<T, 64, 64, 4, 1, 1, 1>(gm, lnf, grid, st, k);
-  else if (force_tile == 2) launch_tile<T, 128, 64, 3, 1, 2, 1>(gm, lnf, grid, st, k);
-  else if (force_tile == 3) launch_tile<T, 128, 64, 5, 1, 1, 1>(gm, lnf, grid, st, k);
-  else if (force_tile == 4) launch_tile<T, 128, 128, 4, 1, 1, 2>(gm, lnf, grid, st, k);
-  else if (force_tile == 5) launch_tile<T, 128, 128, 4, 1, 1, 1>(gm, lnf, grid, st, k);
-  else if (force_tile == 6) launch_tile<T, 256, 128, 3, 1, 1, 2>(gm, lnf, grid, st, k);
-  else if (force_tile == 7) launch_tile<T, 128, 160, 4, 1, 1, 1>(gm, false, grid, st, k);
-  else
-#endif
-  if (use_pp) { pp.splits = splits; g_last_tile.bm = pp.bm; g_last_tile.bn = pp.bn; launch_gemm_pp(dtype, k, pp, st, g_prof.e0, g_prof.e1); }
-  else if (t160) launch_tile<T, 128, 160, 4, 1, 1, 1>(gm, false, grid, st, k);
-  else if (mw2) launch_tile<T, 256, 128, 3, 1, 1, 2>(gm, lnf, grid, st, k, glu);
-  else if (BM == 128 && BN == 128 && (glu || (kMw128 && tiles_per_split >= kMw128))) launch_tile<T, 128, 128, 4, 1, 1, 2>(gm, lnf, grid, st, k, glu);
-  // two wave groups on disjoint K ranges: measured ahead only on the 128x64 tile (conv 4096x320x2880: 28.5 -> 24.9 us,
-  // x5760: 50.8 -> 42.7 us; 128x128 tiles and short loops lose to the merge; 64x64 tiles: no K grouping wins in situ)
+  p.buf = p.a_bytes != 0 && p.gm != GM_GENERIC;
+}
+
+// Step 4, what rides along in the epilogue of an unsplit k_gemm_dma launch.  Each form is one predicate here, one GemmPlan field
+// and one arm of launch_tile_b.  (The GEGLU forms are not optional: glu_form() is part of the request and pick_tile gives them a
+// tile that carries them.)
+// GroupNorm statistics, either direction: tiles of whole images' rows, groups no wider than a column tile, at most 64 "slices" = 2 per
+// row tile for the merge in k_gn_apply.  *gn_done then carries the slice count (> 1) instead of 1.
+static bool gn_epi_shape_ok(const GemmK& k, const GemmPlan& p) {
+  if (!(p.splits == 1 && !p.pp && k.gn_part && k.gn_G > 0 && k.gn_HW > 0 && k.C && k.wide_store && k.M % k.gn_HW == 0 &&
+        k.gn_HW % p.bm == 0 && k.N % k.gn_G == 0 && k.N % p.bn == 0)) return false;
+  const int cpg = k.N / k.gn_G, sx = 2 * (k.gn_HW / p.bm);
+  return cpg >= 8 && cpg <= p.bn && sx <= 64;
+}
+// forward statistics: the next op normalises this launch's output
+static bool gn_epi_fwd_ok(const GemmK& k, const GemmPlan& p, const GemmHooks& h, int glu) {
+  return (h.buf_stage & 4) == 0 && gn_epi_fwd_tile(p.bn, glu, p.lnf) && !k.gnb_x && h.gn_done && gn_epi_shape_ok(k, p);
+}
+// ... and the BACKWARD slice statistics (sum d, sum d * xhat) when the output is dy of a GroupNorm: 64-column tiles of up to 128
+// rows, no bias / residual / per-image vector (an input-gradient GEMM has none; the residual's prefetch registers carry the
+// GroupNorm's input tile)
+static bool gn_epi_bwd_ok(const GemmK& k, const GemmPlan& p, const GemmHooks& h, int glu) {
+  return (h.buf_stage & 8) == 0 && gn_epi_bwd_tile(p.bm, p.bn, 1, glu, p.lnf) && k.gnb_x && h.gn_done && gn_epi_shape_ok(k, p) && k.pre_r &&
+         !k.R && !k.bias && !k.rowvec && !k.act_silu && (((size_t)k.gnb_x | (size_t)(k.gnb_ldx * 2)) & 7) == 0;
+}
+// Cross-attention (EPI_XATTN): the q projection of a cross-attention whose 64-column tiles are whole heads and whose row tiles lie
+// inside one image (a tile never mixes two images' K / V), unsplit, with the plain bias-only epilogue, at most XA_KEYS keys, every
+// operand 16-byte aligned; its dQ (EPI_XATTN_DQ) in the to_out input-gradient GEMM, with no bias and no folded LayerNorm.
+// *xa_done tells the caller that the attention has been launched with the GEMM.
+static bool xattn_epi_ok(const GemmK& k, const GemmPlan& p, const TilePick& t, const GemmHooks& h, int glu) {
+  const bool bwd = k.xa_dq != nullptr;
+  return k.xa_o && h.xa_done && (h.buf_stage & (bwd ? 32 : 16)) == 0 && p.splits == 1 && !p.pp && !glu && !t.t160 && !t.n320 && !t.mw2 &&
+         xattn_epi_tile(p.bm, p.bn, 1, 1, p.a_bytes != 0) && p.gm == GM_DENSE && k.xa_Nk >= 1 && k.xa_Nk <= XA_KEYS && k.xa_Nq > 0 &&
+         k.N == 64 * k.xa_H && k.M % k.xa_Nq == 0 && k.M < (1 << 22) && (k.M == k.xa_Nq || k.xa_Nq % p.bm == 0) && k.C && k.wide_store && k.pre_r &&
+         !k.R && !k.rowvec && !k.act_silu && !p.gn_epi && k.xa_lse && k.xa_ldk % 8 == 0 && k.xa_ldo % 8 == 0 &&
+         (((size_t)k.xa_k | (size_t)k.xa_v | (size_t)k.xa_o) & 15) == 0 &&
+         (!bwd || (!p.lnf && !k.bias && k.xa_q && k.xa_ldq % 8 == 0 && k.xa_lddq % 8 == 0 && (((size_t)k.xa_q | (size_t)k.xa_dq) & 15) == 0));
+}
+
+// Step 5, the instantiation of the tile: ring stages, K groups, wave multiplier (the arms of launch_planned's switch)
+static void pick_instance(GemmPlan& p, int glu, int tiles_per_split) {
+  const long wgs = (long)p.grid[0] * p.grid[1] * p.splits;
+  auto set = [&](int st, int kg, int mw) { p.stages = st; p.wg = 1; p.kg = kg; p.mw = mw; };
+  if (p.bn == 160) set(4, 1, 1);
+  else if (p.bm == 256) set(3, 1, 2);
+  else if (p.bm == 128 && p.bn == 128 && (glu || (kMw128 && tiles_per_split >= kMw128))) set(4, 1, 2);
   // between one and two workgroups per CU (the 96x96-latent level of a 768x768 image: 72 x 5 = 360 tiles; the B = 2 CFG pass at
   // 64x64 latents: 64 x 5 = 320): the 147-KB two-group tile fits one workgroup per CU, so such a grid runs as two rounds with the
   // second one mostly empty; a three-stage ring without the K groups is 74 KB, two workgroups share a CU and the grid is one round
   // (same-box A/B, profiles/r04_ab_two_per_cu.txt: B = 2 forward 5.46 -> 5.30 ms, backward 6.82 -> 6.67 ms; 96x96 latents bf16 B = 1
   // forward 6.49 -> 6.32 ms, backward 9.55 -> 9.40 ms; guided step 34.97 -> 35.30 steps/s)
-  else if (kTwoPerCu && BM == 128 && BN == 64 && tiles * splits > 256 && tiles * splits <= 512)
-    launch_tile<T, 128, 64, 3, 1, 1, 1>(gm, lnf, grid, st, k, epi);
-  else if (BM == 128 && BN == 64 && tiles_per_split >= kKg2MinKt) launch_tile<T, 128, 64, 3, 1, 2, 1>(gm, lnf, grid, st, k, epi);
+  else if (kTwoPerCu && p.bm == 128 && p.bn == 64 && wgs > 256 && wgs <= 512) set(3, 1, 1);
+  // two wave groups on disjoint K ranges: measured ahead only on the 128x64 tile (conv 4096x320x2880: 28.5 -> 24.9 us,
+  // x5760: 50.8 -> 42.7 us; 128x128 tiles and short loops lose to the merge; 64x64 tiles: no K grouping wins in situ)
+  else if (p.bm == 128 && p.bn == 64 && tiles_per_split >= kKg2MinKt) set(3, 2, 1);
   // eight waves (4 x 2, 32 x 160 outputs each): the two-stage ring has one 57-KB tile in flight and its 56 one-KiB DMA pieces were
   // issued by four waves, 14 each at 60 - 185 cycles apiece -- the issue, not the latency, bounded the tile; with seven pieces per
   // wave: M = 32768, N = 320 dense K = 320 20.6 -> 14.9 us, K = 1280 40.1 -> 34.6 us, conv K = 2880 76.8 -> 67.3 us, batch-8
   // forward 13.55 -> 13.15 ms (profiles/r04_ab_n320_eight_waves.txt)
-  else if (BN == 320) launch_tile<T, 128, 320, 2, 1, 1, 2>(gm, false, grid, st, k);
-  else if (BM == 64) launch_tile<T, 64, 64, 4, 1, 1, 1>(gm, lnf, grid, st, k, epi);      // (rings of 6 / 8 stages: pass 2 % SLOWER; round 3, eight stages only on the <= 256-workgroup long-K launches: guided step -1.1 %)
-  else if (BN == 128 && kManyBlocks > 0 && tiles * splits >= kManyBlocks) launch_tile<T, 128, 128, 2, 1, 1, 1>(gm, lnf, grid, st, k);   // 64 KiB: two workgroups per CU
-  else if (BN == 128) launch_tile<T, 128, 128, 4, 1, 1, 1>(gm, lnf, grid, st, k);
-  else launch_tile<T, 128, 64, 5, 1, 1, 1>(gm, lnf, grid, st, k, epi);
+  else if (p.bn == 320) set(2, 1, 2);
+  else if (p.bm == 64) set(4, 1, 1);      // (rings of 6 / 8 stages: pass 2 % SLOWER; round 3, eight stages only on the <= 256-workgroup long-K launches: guided step -1.1 %)
+  else if (p.bn == 128 && kManyBlocks > 0 && wgs >= kManyBlocks) set(2, 1, 1);   // 64 KiB: two workgroups per CU
+  else if (p.bn == 128) set(4, 1, 1);
+  else set(5, 1, 1);
+}
+
+// Step 6, the launch after a split GEMM: the plain reduce, or one that also leaves the GroupNorm slice statistics of the summed output
+// (forward, or backward when it is dy of a GroupNorm), or -- the rows are the dy of a LayerNorm -- reduce + LayerNorm backward in one
+// launch (dy itself is not written)
+static int pick_reduce(const GemmK& k, const GemmPlan& p, const GemmHooks& h) {
+  if (p.splits <= 1) return RED_NONE;
+  if (k.gn_part && k.gn_G > 0 && k.gn_HW > 0 && k.N % k.gn_G == 0 && (GN_GB * (k.N / k.gn_G)) % 8 == 0 &&
+      GN_GB * (k.N / k.gn_G) <= 2048 && k.M % k.gn_HW == 0) return k.gnb_x ? RED_GN_BWD : RED_GN_FWD;
+  if (k.lnb_x && h.lnb_done && !k.bias && !k.rowvec && !k.R && !k.act_silu && k.N % 8 == 0 && k.ldc == k.N) return RED_LN_BWD;
+  return RED_PLAIN;
+}
+
+// the cut (K tiles spread evenly over the splits) and steps 3 - 6
+static GemmPlan plan_finish(const PlanDraft& d, const GemmK& k, const GemmHooks& h) {
+  GemmPlan p{};
+  const int glu = glu_form(k), ktiles = k.K / BK;
+  p.pp = d.pp ? 1 : 0; p.bm = d.t.bm; p.bn = d.t.bn; p.lnf = k.ln_s != nullptr; p.gm = gemm_mode(k);
+  const int tiles_per_split = cdiv(ktiles, d.splits);
+  p.splits = cdiv(ktiles, tiles_per_split);
+  p.k_per_split = tiles_per_split * BK;
+  if (gn_epi_fwd_ok(k, p, h, glu)) p.gn_epi = 1;
+  if (gn_epi_bwd_ok(k, p, h, glu)) p.gn_epi = 2;
+  if (p.gn_epi) { p.gn_cpg = k.N / k.gn_G; p.gn_S = 2 * (k.gn_HW / p.bm); }
+  plan_extents(p, k, h);
+  if (xattn_epi_ok(k, p, d.t, h, glu)) p.xa = k.xa_dq ? 2 : 1;
+  p.epi = p.xa == 2 ? EPI_XATTN_DQ : (p.xa ? EPI_XATTN : glu);
+  if (p.pp) {
+    // persistent grid: one workgroup per CU (256: a multiple of 8, the XCD order of the work items holds in every round)
+    const unsigned nwork = (unsigned)(cdiv(k.M, p.bm) * (k.N / p.bn) * p.splits);
+    p.grid[0] = (h.pp_persist == 0 || nwork <= (unsigned)h.cus) ? nwork : (unsigned)h.cus; p.grid[1] = p.grid[2] = 1;
+  } else {
+    p.grid[0] = cdiv(k.M, p.bm); p.grid[1] = cdiv(k.N, p.bn); p.grid[2] = p.splits;
+    pick_instance(p, glu, tiles_per_split);
+  }
+  p.reduce = pick_reduce(k, p, h);
+  if (p.reduce == RED_GN_FWD || p.reduce == RED_GN_BWD) p.gn_S = gn_slices(k.gn_HW, k.M / k.gn_HW);
+  return p;
+}
+
+GemmPlan gemm_plan(const GemmK& k, size_t partial_elems, const GemmHooks& h) { return plan_finish(plan_draft(k, partial_elems, h), k, h); }
+
+// ---- the tuning build (tools/lab.sh build-tuning): everything it adds to the decision, applied to the finished plan --------------
+#ifdef DH_TUNING
+// per-shape policy search (tools/sweep_gemm_shapes.py): DH_GEMM_LOG=1 prints every dispatch, DH_FORCE_TILE / DH_FORCE_SPLITS override
+// the choice (1 = 64x64, 2 = 128x64 two K groups, 3 = 128x64, 4 = 128x128 eight waves, 5 = 128x128, 6 = 256x128 eight waves, 7 = 128x160);
+// a forced plan is the draft with the tile / split replaced, finished again, without the cross-attention form
+static void tune_plan(GemmPlan& p, GemmK& k, size_t partial_elems, const GemmHooks& h) {
+  static const int kLog = getenv("DH_GEMM_LOG") ? atoi(getenv("DH_GEMM_LOG")) : 0;
+  static const int kWnt = getenv("DH_W_NT") ? atoi(getenv("DH_W_NT")) : 0;                     // non-temporal weight DMA for GEMMs of at most this many row tiles (0 = never)
+  static const int kLnfAbl = getenv("DH_LNF_ABL") ? atoi(getenv("DH_LNF_ABL")) : 0;
+  const int kForceTile = getenv("DH_FORCE_TILE") ? atoi(getenv("DH_FORCE_TILE")) : 0;          // (re-read per dispatch: one process sweeps)
+  const int kForceSplits = getenv("DH_FORCE_SPLITS") ? atoi(getenv("DH_FORCE_SPLITS")) : 0;
+  const bool lnf = k.ln_s != nullptr;
+  PlanDraft d = plan_draft(k, partial_elems, h);
+  int force_tile = 0;
+  if (kForceTile && !d.pp && !glu_form(k)) {
+    const int fbm = kForceTile == 1 ? 64 : (kForceTile == 6 ? 256 : 128), fbn = kForceTile == 7 ? 160 : ((kForceTile <= 3) ? 64 : 128);
+    if ((k.N % fbn == 0 || fbn == 64) && !(fbn == 160 && lnf)) { d.t.bm = fbm; d.t.bn = fbn; force_tile = kForceTile; }
+  }
+  const bool force_splits = kForceSplits && !d.pp && k.partial && !lnf;
+  if (force_splits) d.splits = clamp_splits(kForceSplits, (k.K / BK) / 2, 1 << 30, k, partial_elems);
+  if (kLog) fprintf(stderr, "GEMMLOG M=%d N=%d K=%d mode=%d lnf=%d gn=%d gnb=%d bias=%d R=%d rowvec=%d | pp=%d BM=%d BN=%d splits=%d\n", k.M, k.N, k.K,
+                    k.mode == A_DENSE ? 0 : (k.mode == A_CONV3 && k.stride == 1 && k.up == 0 ? 1 : 2), (int)lnf, k.gn_part != nullptr,
+                    k.gnb_x != nullptr, k.bias != nullptr, k.R != nullptr, k.rowvec != nullptr, (int)d.pp, d.t.bm, d.t.bn, d.splits);
+  if (force_tile || force_splits) p = plan_finish(d, k, h);
+  if (force_tile) {
+    static const int inst[8][3] = {{0, 0, 0}, {4, 1, 1}, {3, 2, 1}, {5, 1, 1}, {4, 1, 2}, {4, 1, 1}, {3, 1, 2}, {4, 1, 1}};      // stages, K groups, wave multiplier
+    p.stages = inst[force_tile][0]; p.kg = inst[force_tile][1]; p.mw = inst[force_tile][2];
+    p.xa = 0; p.epi = 0;
+  }
+  // DH_GEMM_LOG=2: the whole request and plan of every launch -- the rows tests/test_gemm_plan.py pins (its query fields, then
+  // dh_dbg_gemm_plan's output order)
+  if (kLog > 1) {
+    const int conv = k.mode == A_DENSE ? 0 : (k.mode == A_CONV3 ? 1 : 2);
+    const unsigned flags = (k.bias ? 1u : 0u) | (k.R ? 2u : 0u) | (k.rowvec ? 4u : 0u) | (k.act_silu ? 8u : 0u) | (lnf ? 16u : 0u) |
+                           (k.gn_part ? 32u : 0u) | (k.gnb_x ? 64u : 0u) | (k.lnb_x ? 128u : 0u) | (k.glu_y ? 256u : 0u) | (k.glub_x ? 512u : 0u) |
+                           (k.xa_o && !k.xa_dq ? 1024u : 0u) | (k.xa_dq ? 2048u : 0u) | ((((size_t)k.A | (size_t)k.W | (size_t)k.C) & 15) == 0 ? 4096u : 0u);
+    int v[GEMM_PLAN_FIELDS];
+    memcpy(v, &p, sizeof(v));
+    fprintf(stderr, "GEMMPLAN q %d %d %d %d %d %d %d %ld %ld %zu %u %d %d %d %d %d %d |", k.M, k.N, k.K, conv, k.Hin, k.stride, k.up, k.lda, k.ldc,
+            partial_elems, flags, k.gn_HW, k.gn_G, k.glub_x ? k.glub_f : 0, k.xa_Nq, k.xa_Nk, k.xa_H);
+    for (int i = 0; i < GEMM_PLAN_FIELDS; ++i) fprintf(stderr, " %d", v[i]);
+    fprintf(stderr, "\n");
+  }
+  k.w_nt = kWnt > 0 && cdiv(k.M, p.bm) <= kWnt;
+  k.lnf_abl = kLnfAbl;
+  k.ts = g_gemm_ts;
+}
+#else
+static inline void tune_plan(GemmPlan&, GemmK&, size_t, const GemmHooks&) {}
+#endif
+
+// ---- accounting, launch, publish -------------------------------------------------------------------------------------------------------
+// profiled runs (dh_gemm_profile_begin): the event pair that brackets the launch, its flops and algorithmic bytes
+static void prof_account(const GemmK& k, const GemmPlan& p) {
+  if (!g_prof.on) return;
+  if (g_prof.used + 2 > g_prof.ev.size()) {
+    const size_t old = g_prof.ev.size();
+    g_prof.ev.resize(old + 4096);
+    for (size_t i = old; i < g_prof.ev.size(); ++i) (void)hipEventCreate(&g_prof.ev[i]);
+  }
+  g_prof.e0 = g_prof.ev[g_prof.used++];
+  g_prof.e1 = g_prof.ev[g_prof.used++];
+  g_prof.flops += 2.0 * (double)k.M * (double)k.N * (double)k.K;
+  // every operand once, in its storage type: the A source (dense rows; for a convolution the source image, not its im2col
+  // view), the weights, the output (the GEGLU forms: what they read and write instead), the residual
+  const double esz = 2.0;
+  double a_elems = (double)k.M * k.K;
+  if (k.mode != A_DENSE && k.Hout > 0 && k.Wout > 0) a_elems = (double)k.M / ((double)k.Hout * k.Wout) * k.Hin * k.Win * k.Cin;
+  double c_elems = (double)k.M * k.N * (k.C ? 1.0 : 0.0) + (k.R ? (double)k.M * k.N : 0.0);
+  if (k.glu_y) c_elems += 0.5 * (double)k.M * k.N;
+  // saved pre-activations read [M][2F], their gradient written [M][2F] (C holds only the columns past F)
+  if (k.glub_x) c_elems += 4.0 * (double)k.M * k.glub_f - (k.C ? (double)k.M * k.glub_f : 0.0);
+  if (p.gn_epi == 2) c_elems += (double)k.M * k.N;       // the GroupNorm input tile the backward statistics read
+  if (p.xa == 1) c_elems += (k.xa_save ? 1.0 : 0.0) * (double)k.M * k.N + 2.0 * (k.M / k.xa_Nq) * (double)k.xa_Nk * k.N;   // o for q (q too when saved), the heads' K and V
+  if (p.xa == 2) c_elems += 2.0 * (double)k.M * k.N + 2.0 * (k.M / k.xa_Nq) * (double)k.xa_Nk * k.N;     // dq for dO; q, o, K and V read
+  g_prof.bytes += esz * (a_elems + (double)k.N * k.K + c_elems);
+}
+
+constexpr unsigned tile_key(int bm, int bn, int st, int kg, int mw) { return (unsigned)(bm | bn << 10 | st << 20 | kg << 24 | mw << 26); }
+
+// the plan into the argument block, the kernel the plan names, the reduce it names
+template <class T>
+static void launch_planned(const GemmPlan& p, GemmK k, hipStream_t st) {
+  constexpr int dtype = std::is_same<T, f16>::value ? DH_DTYPE_F16 : DH_DTYPE_BF16;
+  k.splits = p.splits; k.k_per_split = p.k_per_split;
+  k.gn_epi = p.gn_epi; k.gn_cpg = p.gn_cpg; k.xa = p.xa;
+  if (p.gn_epi) k.gn_S = p.gn_S;
+  if (!p.pp) { k.pp_a_bytes = p.a_bytes; k.pp_w_bytes = p.w_bytes; }
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+  g_launched_tile = LaunchedTile{};
+  bool ablated = false;
+#ifdef DH_TUNING
+  // ablations of the K loop (timing only): 1 = no LDS reads / MFMA, 2 = no DMA in the loop, 3 = 1 on the dense kernel
+  static const int kAbl = getenv("DH_GEMM_ABLATE") ? atoi(getenv("DH_GEMM_ABLATE")) : 0;
+  const bool t128 = !p.pp && p.bm == 128 && p.bn == 128, t256 = !p.pp && p.bm == 256;
+  ablated = true;
+  if (kAbl == 1 && t128) hipLaunchKernelGGL((k_gemm_dma<T, 128, 128, 4, GM_CONV_S1, 1>), grid, dim3(256), 0, st, k);
+  else if (kAbl == 2 && t128) hipLaunchKernelGGL((k_gemm_dma<T, 128, 128, 4, GM_CONV_S1, 2>), grid, dim3(256), 0, st, k);
+  else if (kAbl == 3 && t128) hipLaunchKernelGGL((k_gemm_dma<T, 128, 128, 4, GM_DENSE, 1>), grid, dim3(256), 0, st, k);
+  else if (kAbl == 1 && t256 && p.gm == GM_CONV_S1) hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_CONV_S1, 1, 1, 1, 2>), grid, dim3(512), 0, st, k);
+  else if (kAbl == 2 && t256 && p.gm == GM_CONV_S1) hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_CONV_S1, 2, 1, 1, 2>), grid, dim3(512), 0, st, k);
+  else if (kAbl == 1 && t256 && p.gm == GM_DENSE && !p.lnf) hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_DENSE, 1, 1, 1, 2>), grid, dim3(512), 0, st, k);
+  else if (kAbl == 2 && t256 && p.gm == GM_DENSE && !p.lnf) hipLaunchKernelGGL((k_gemm_dma<T, 256, 128, 3, GM_DENSE, 2, 1, 1, 2>), grid, dim3(512), 0, st, k);
+  else ablated = false;
+#endif
+#define DH_TILE(BM, BN, ST, KG, MW) \
+  case tile_key(BM, BN, ST, KG, MW): launch_tile<T, BM, BN, ST, 1, KG, MW>(p.gm, p.lnf != 0, grid, st, k, p.epi); break
+  if (ablated) {        // (tuning build: a timing ablation stood in for the planned kernel)
+  } else if (p.pp) {
+    PpPlan pp;
+    pp.bm = p.bm; pp.bn = p.bn; pp.splits = p.splits; pp.grid = p.grid[0];
+    g_launched_tile.bm = pp.bm; g_launched_tile.bn = pp.bn;
+    launch_gemm_pp(dtype, k, pp, st, g_prof.e0, g_prof.e1);
+  } else switch (tile_key(p.bm, p.bn, p.stages, p.kg, p.mw)) {
+    DH_TILE(128, 160, 4, 1, 1);
+    DH_TILE(256, 128, 3, 1, 2);
+    DH_TILE(128, 128, 4, 1, 2);
+    DH_TILE(128, 64, 3, 1, 1);
+    DH_TILE(128, 64, 3, 2, 1);
+    DH_TILE(128, 320, 2, 1, 2);
+    DH_TILE(64, 64, 4, 1, 1);
+    DH_TILE(128, 128, 2, 1, 1);
+    DH_TILE(128, 128, 4, 1, 1);
+    DH_TILE(128, 64, 5, 1, 1);
+    default:               // pick_instance (or a forced tile) named a tile that is not instantiated: no kernel ran, the output is stale
+      fprintf(stderr, "launch_planned: no k_gemm_dma instantiation for tile %dx%d stages %d kg %d mw %d\n", p.bm, p.bn, p.stages, p.kg, p.mw);
+      abort();
+  }
+#undef DH_TILE
   g_prof.e0 = g_prof.e1 = nullptr;
-  g_last_xattn = k.xa;                             // (1 forward, 2 backward)
-  if (k.xa) { ++g_xattn_total; *xa_done = 1; }
-  g_last_tile.splits = splits; g_last_tile.pp = use_pp ? 1 : 0; g_last_tile.gn_epi = k.gn_epi;
-  if (k.gn_epi) *gn_done = k.gn_S;
-  if (splits > 1) {
-    if (k.gn_part && k.gn_G > 0 && k.gn_HW > 0 && k.N % k.gn_G == 0 && (GN_GB * (k.N / k.gn_G)) % 8 == 0 &&
-        GN_GB * (k.N / k.gn_G) <= 2048 && k.M % k.gn_HW == 0) {
-      k.gn_S = gn_slices(k.gn_HW, k.M / k.gn_HW);
-      if (k.gnb_x) hipLaunchKernelGGL((k_splitk_reduce_gn<T, true>), dim3(k.gn_S, cdiv(k.gn_G, GN_GB), k.M / k.gn_HW), dim3(256), 0, st, k);
-      else hipLaunchKernelGGL((k_splitk_reduce_gn<T, false>), dim3(k.gn_S, cdiv(k.gn_G, GN_GB), k.M / k.gn_HW), dim3(256), 0, st, k);
-      g_last_tile.reduce_gn = 1;
-      if (gn_done) *gn_done = 1;
-    } else if (k.lnb_x && lnb_done && !k.bias && !k.rowvec && !k.R && !k.act_silu && k.N % 8 == 0 && k.ldc == k.N) {
-      // the rows are the dy of a LayerNorm: reduce + LayerNorm backward in one launch (dy itself is not written)
-      launch_splitk_reduce_ln_bwd(dtype, k.partial, splits, k.lnb_x, k.lnb_gamma, k.lnb_stats, k.lnb_add, k.lnb_dx, k.M, k.N, st, k.lnb_ldx);
-      *lnb_done = 1;
-    } else {
-      const size_t groups = (size_t)k.M * k.N / 4;
-      hipLaunchKernelGGL((k_splitk_reduce<T>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, k);
-    }
+  if (p.reduce == RED_GN_FWD || p.reduce == RED_GN_BWD) {
+    k.gn_S = p.gn_S;
+    const dim3 rgrid(k.gn_S, cdiv(k.gn_G, GN_GB), k.M / k.gn_HW);
+    if (p.reduce == RED_GN_BWD) hipLaunchKernelGGL((k_splitk_reduce_gn<T, true>), rgrid, dim3(256), 0, st, k);
+    else hipLaunchKernelGGL((k_splitk_reduce_gn<T, false>), rgrid, dim3(256), 0, st, k);
+  } else if (p.reduce == RED_LN_BWD) {
+    launch_splitk_reduce_ln_bwd(dtype, k.partial, p.splits, k.lnb_x, k.lnb_gamma, k.lnb_stats, k.lnb_add, k.lnb_dx, k.M, k.N, st, k.lnb_ldx);
+  } else if (p.reduce == RED_PLAIN) {
+    const size_t groups = (size_t)k.M * k.N / 4;
+    hipLaunchKernelGGL((k_splitk_reduce<T>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, k);
   }
 }
-#undef DH_KNOB
 
-double launch_gemm(int dtype, const GemmArgs& a, hipStream_t st) {
+// GemmArgs -> the kernel-side argument block, every decision still open (splits = 1, no epilogue riders)
+static GemmK fill_gemm_k(const GemmArgs& a) {
   GemmK k;
   k.A = a.A; k.lda = a.lda; k.W = a.W; k.M = a.M; k.N = a.N; k.K = a.K;
   k.mode = a.mode; k.Hin = a.Hin; k.Win = a.Win; k.Cin = a.Cin; k.Hout = a.Hout; k.Wout = a.Wout;
@@ -1789,7 +1887,7 @@ double launch_gemm(int dtype, const GemmArgs& a, hipStream_t st) {
   k.pre_r = 1;
   k.wide_store = a.N % 32 == 0 && a.ldc % 8 == 0 && ((size_t)a.C & 15) == 0;
   k.ln_s = a.ln_s; k.ln_t = a.ln_t; k.ln_stats = a.ln_stats; k.ln_eps = a.ln_eps;
-  k.gn_part = a.gn_part; k.gn_HW = a.gn_HW; k.gn_G = a.gn_G; k.gn_S = 0;
+  k.gn_part = a.gn_part; k.gn_HW = a.gn_HW; k.gn_G = a.gn_G; k.gn_S = 0; k.gn_epi = 0; k.gn_cpg = 0;
   k.gnb_x = a.gnb_x; k.gnb_ldx = a.gnb_ldx; k.gnb_gamma = a.gnb_gamma; k.gnb_beta = a.gnb_beta; k.gnb_stats = a.gnb_stats;
   k.gnb_silu = a.gnb_silu;
   k.lnb_x = a.lnb_x; k.lnb_ldx = a.lnb_ldx > 0 ? a.lnb_ldx : a.N;
@@ -1806,11 +1904,35 @@ double launch_gemm(int dtype, const GemmArgs& a, hipStream_t st) {
   k.xa = 0; k.xa_k = a.xa_k; k.xa_v = a.xa_v; k.xa_ldk = a.xa_ldk; k.xa_o = a.xa_o; k.xa_ldo = a.xa_ldo; k.xa_lse = a.xa_lse;
   k.xa_H = a.xa_H; k.xa_Nq = a.xa_Nq; k.xa_Nk = a.xa_Nk; k.xa_save = a.xa_save;
   k.xa_q = a.xa_q; k.xa_ldq = a.xa_ldq; k.xa_dq = a.xa_dq; k.xa_lddq = a.xa_lddq;
-  if (a.gn_done) *a.gn_done = 0;
-  if (a.lnb_done) *a.lnb_done = 0;
-  if (a.xa_done) *a.xa_done = 0;
-  if (dtype == DH_DTYPE_F16) gemm_dispatch<f16>(k, a.partial_elems, st, a.gn_done, a.lnb_done, a.xa_done, dtype);
-  else gemm_dispatch<bf16>(k, a.partial_elems, st, a.gn_done, a.lnb_done, a.xa_done, dtype);
+  return k;
+}
+
+// the test hooks and the device, read once per launch
+static GemmHooks current_hooks() {
+  GemmHooks h;
+  gemm_pp_hooks(&h);
+  h.pp_force = g_pp_force; h.buf_stage = g_buf_stage;
+  return h;
+}
+
+// fill, plan, account, launch, publish
+double launch_gemm(int dtype, const GemmArgs& a, hipStream_t st) {
+  GemmK k = fill_gemm_k(a);
+  GemmHooks h = current_hooks();
+  h.gn_done = a.gn_done != nullptr; h.lnb_done = a.lnb_done != nullptr; h.xa_done = a.xa_done != nullptr;
+  GemmPlan p = gemm_plan(k, a.partial_elems, h);
+  tune_plan(p, k, a.partial_elems, h);
+  prof_account(k, p);
+  if (dtype == DH_DTYPE_F16) launch_planned<f16>(p, k, st);
+  else launch_planned<bf16>(p, k, st);
+  // what the launch carried, for the caller (the slice count of an epilogue's GroupNorm statistics, 1 for the reduce's) and for
+  // the test hooks (dh_dbg_gemm_last_tile, dh_dbg_gemm_xattn_carried)
+  g_last_plan = p;
+  const bool reduce_gn = p.reduce == RED_GN_FWD || p.reduce == RED_GN_BWD;
+  if (a.gn_done) *a.gn_done = p.gn_epi ? p.gn_S : (reduce_gn ? 1 : 0);
+  if (a.lnb_done) *a.lnb_done = p.reduce == RED_LN_BWD ? 1 : 0;
+  if (a.xa_done) *a.xa_done = p.xa ? 1 : 0;
+  if (p.xa) ++g_xattn_total;
   return 2.0 * (double)a.M * (double)a.N * (double)a.K;
 }
 
@@ -1839,16 +1961,64 @@ extern "C" int dh_dbg_gemm_stage(int buf) {
 // gn_epi (0 none, 1 forward, 2 backward GroupNorm statistics in the epilogue), the split-K reduce left GroupNorm statistics (0 / 1)
 extern "C" int dh_dbg_gemm_last_tile(int* out) {
   DH_REQUIRE(out != nullptr, "null pointer");
-  const dh::GemmTileReport& r = dh::g_last_tile;
-  const int v[9] = {r.bm, r.bn, r.kg, r.stages, r.mw, r.splits, r.pp, r.gn_epi, r.reduce_gn};
+  const dh::GemmPlan& p = dh::g_last_plan;
+  const dh::LaunchedTile& t = dh::g_launched_tile;
+  const int v[9] = {t.bm, t.bn, t.kg, t.stages, t.mw, p.splits, p.pp, p.gn_epi, p.reduce == dh::RED_GN_FWD || p.reduce == dh::RED_GN_BWD};
   for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return DH_OK;
+}
+
+// host-only query of the whole plan (no launch, no device needed): what launch_gemm would decide for the launch `q` describes, under
+// the hooks in force.  out[0..22] = the GemmPlan fields in their declared order (gemm_k.h): pp, bm, bn, stages, wg, kg, mw, gm, buf,
+// lnf, epi, splits, k_per_split, grid x / y / z, a_bytes, w_bytes, gn_epi, gn_cpg, gn_S, xa, reduce.  tests/test_gemm_plan.py pins
+// the table of the SD-2-depth passes on the CPU.
+extern "C" int dh_dbg_gemm_plan(const dh_gemm_plan_query* q, int32_t* out, int n_out) {
+  using namespace dh;
+  static_assert(sizeof(GemmPlan) == GEMM_PLAN_FIELDS * sizeof(int32_t), "GemmPlan is GEMM_PLAN_FIELDS 32-bit fields");
+  DH_REQUIRE(q && out && n_out >= GEMM_PLAN_FIELDS, "null pointer, or fewer than 23 output slots");
+  DH_REQUIRE(q->M > 0 && q->N > 0 && q->K >= 64 && q->conv >= 0 && q->conv <= 2 && (q->conv == 0 || (q->hw > 0 && (q->stride == 1 || q->stride == 2))),
+             "bad shape");
+  static __attribute__((aligned(16))) unsigned char dummy[32];
+  static int carried;
+  void* ptr = (q->flags & DH_GEMM_Q_ALIGNED) ? dummy : dummy + 2;
+  float* fptr = reinterpret_cast<float*>(dummy);
+  GemmArgs a;
+  a.A = ptr; a.W = ptr; a.C = ptr; a.M = q->M; a.N = q->N; a.K = q->K;
+  a.mode = q->conv == 0 ? A_DENSE : (q->conv == 1 ? A_CONV3 : A_CONVT2);
+  if (q->conv) {
+    a.Hin = a.Win = q->hw; a.Cin = q->K / 9; a.stride = q->stride; a.up = q->up;
+    a.Hout = a.Wout = q->conv == 2 ? 2 * q->hw : q->hw * (q->up ? 2 : 1) / q->stride;
+  }
+  a.lda = q->lda > 0 ? q->lda : (q->conv ? q->K / 9 : q->K);
+  a.ldc = q->ldc > 0 ? q->ldc : q->N;
+  a.partial = q->partial_elems ? fptr : nullptr; a.partial_elems = q->partial_elems;
+  if (q->flags & DH_GEMM_Q_BIAS) a.bias = fptr;
+  if (q->flags & DH_GEMM_Q_RESIDUAL) { a.R = ptr; a.ldr = q->N; }
+  if (q->flags & DH_GEMM_Q_ROWVEC) { a.rowvec = fptr; a.rowvec_ld = q->N; }
+  a.act_silu = (q->flags & DH_GEMM_Q_SILU) ? 1 : 0;
+  if (q->flags & DH_GEMM_Q_LNF) { a.ln_s = fptr; a.ln_t = fptr; a.ln_stats = fptr; }
+  if (q->flags & DH_GEMM_Q_GN_STATS) { a.gn_part = fptr; a.gn_HW = q->gn_HW; a.gn_G = q->gn_G; a.gn_done = &carried; }
+  if (q->flags & DH_GEMM_Q_GN_BWD) { a.gnb_x = ptr; a.gnb_ldx = q->N; }
+  if (q->flags & DH_GEMM_Q_LN_BWD) { a.lnb_x = ptr; a.lnb_done = &carried; }
+  if (q->flags & DH_GEMM_Q_GLU_FWD) { a.glu_y = ptr; a.glu_ldy = q->N / 2; }
+  if (q->flags & DH_GEMM_Q_GLU_BWD) { a.glub_x = ptr; a.glub_dx = ptr; a.glub_f = q->glub_f; }
+  if (q->flags & (DH_GEMM_Q_XATTN_FWD | DH_GEMM_Q_XATTN_DQ)) {
+    a.xa_k = ptr; a.xa_v = ptr; a.xa_o = ptr; a.xa_lse = fptr; a.xa_ldk = q->N; a.xa_ldo = q->N;
+    a.xa_Nq = q->xa_Nq; a.xa_Nk = q->xa_Nk; a.xa_H = q->xa_H; a.xa_done = &carried;
+  }
+  if (q->flags & DH_GEMM_Q_XATTN_DQ) { a.xa_q = ptr; a.xa_dq = ptr; a.xa_ldq = q->N; a.xa_lddq = q->N; }
+  const GemmK k = fill_gemm_k(a);
+  GemmHooks h = current_hooks();
+  h.gn_done = a.gn_done != nullptr; h.lnb_done = a.lnb_done != nullptr; h.xa_done = a.xa_done != nullptr;
+  const GemmPlan p = gemm_plan(k, a.partial_elems, h);
+  memcpy(out, &p, sizeof(p));
   return DH_OK;
 }
 
 // test hook: *last = the last GEMM launch of this thread carried a cross-attention in its epilogue (0 no, 1 forward, 2 dQ), *total = how many
 // launches of this thread have since the library was loaded (either pointer may be NULL)
 extern "C" int dh_dbg_gemm_xattn_carried(int* last, long long* total) {
-  if (last) *last = dh::g_last_xattn;
+  if (last) *last = dh::g_last_plan.xa;
   if (total) *total = dh::g_xattn_total;
   return DH_OK;
 }

@@ -65,9 +65,9 @@ struct GemmK {   // kernel-side copy of GemmArgs (plain data)
 };
 
 
-// gemm_pp.hip: the eight-wave ping-pong kernel.  gemm_pp_eligible: whether the shape / epilogue can run on it and the policy
-// wants it (`force`: test hook -- 0 policy, 1 never, 2 whenever the kernel can carry the launch); launch_gemm_pp launches it
-// (the caller has filled k.splits / k.k_per_split for the tile it reports through bm / bn).
+// gemm_pp.hip: the eight-wave ping-pong kernel.  gemm_pp_plan (below): whether the shape / epilogue can run on it and the policy
+// wants it (GemmHooks::pp_force: test hook -- 0 policy, 1 never, 2 whenever the kernel can carry the launch); launch_gemm_pp
+// launches it (the caller has filled k.splits / k.k_per_split for the tile it reports through bm / bn).
 // The column-split GEGLU backward (GemmArgs::glub_f): which epilogue a column tile takes, and which tile widths can carry the
 // split -- one predicate for the dispatch (host) and the kernel (device).  A tile lies wholly on one side of the seam.
 __host__ __device__ constexpr bool glub_tile_is_glu(int n0, int glub_f) { return n0 < glub_f; }
@@ -83,8 +83,52 @@ __host__ __device__ constexpr bool xattn_epi_tile(int BM, int BN, int WG, int MW
   return BN == 64 && (BM == 64 || BM == 128) && WG == 1 && MW == 1 && BUF;
 }
 
-struct PpPlan { int bm = 0, bn = 0, splits = 1; };
-bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan);
+// ---- the host-side plan of one launch (gemm.hip: gemm_plan decides, launch_planned launches; DESIGN.md, "GEMM plan") --------------
+// Everything the decision reads besides the launch itself: the test hooks, which carry-outs the caller can take, the CU count.
+struct GemmHooks {
+  int pp_force = 0;       // dh_dbg_gemm_family: 0 policy, 1 never k_gemm_pp, 2 k_gemm_pp whenever it can carry the launch
+  int pp_glu = -1;        // dh_dbg_gemm_pp_glu: the GEGLU epilogues on k_gemm_pp (-1 policy, 0 never, 1 always)
+  int pp_persist = 1;     // dh_dbg_gemm_pp_persist: 0 = one k_gemm_pp workgroup per work item
+  int buf_stage = 1;      // dh_dbg_gemm_stage (bit 0 buffer staging; bits 2-5 switch the epilogue forms OFF)
+  int cus = 256;          // compute units (pp_device_cus; 256 = the MI355X, and the value without a device)
+  bool gn_done = false, lnb_done = false, xa_done = false;      // the caller passed GemmArgs::gn_done / lnb_done / xa_done
+};
+void gemm_pp_hooks(GemmHooks* h);       // gemm_pp.hip: fills pp_glu, pp_persist and cus (the one place that asks the device)
+
+enum { RED_NONE = 0, RED_PLAIN = 1, RED_GN_FWD = 2, RED_GN_BWD = 3, RED_LN_BWD = 4 };      // the launch after a split-K GEMM
+constexpr int GEMM_PLAN_FIELDS = 23;    // dh_dbg_gemm_plan writes the fields below in this order, one int32 each
+struct GemmPlan {
+  // which kernel
+  int pp;                               // 1 = k_gemm_pp (tile bm x bn; stages .. mw are 0), 0 = k_gemm_dma
+  int bm, bn, stages, wg, kg, mw;       // the k_gemm_dma tile = the template arguments of launch_tile
+  int gm;                               // GM_DENSE / GM_CONV_S1 / GM_GENERIC
+  int buf, lnf, epi;                    // BUF form, folded LayerNorm, epilogue form (0, GLU 1 / 2, EPI_XATTN, EPI_XATTN_DQ)
+  // how it is cut
+  int splits, k_per_split; unsigned grid[3];
+  unsigned a_bytes, w_bytes;            // descriptor extents (0 = address form)
+  // what rides along
+  int gn_epi, gn_cpg, gn_S, xa;         // GroupNorm statistics (1 fwd / 2 bwd in the epilogue; gn_S: slices of the epilogue or the reduce), cross-attention (1 fwd / 2 dQ)
+  int reduce;                           // RED_*
+};
+GemmPlan gemm_plan(const GemmK& k, size_t partial_elems, const GemmHooks& h);
+
+// bytes the A buffer descriptor must cover (dense rows; a convolution: the whole source tensor); 0 = no whole images
+inline size_t gemm_a_bytes(const GemmK& k) {
+  if (k.mode == A_DENSE) return ((size_t)(k.M - 1) * k.lda + k.K) * 2;
+  if (k.Hout <= 0 || k.Wout <= 0 || k.M % (k.Hout * k.Wout) != 0) return 0;
+  return (size_t)(k.M / (k.Hout * k.Wout)) * k.Hin * k.Win * (size_t)k.lda * 2;
+}
+// a K split count: at most by_k (K tiles per split), at most `most`, no more f32 slabs than the workspace holds, at least 1
+inline int clamp_splits(int splits, int by_k, int most, const GemmK& k, size_t partial_elems) {
+  if (splits > by_k) splits = by_k;
+  if (splits > most) splits = most;
+  const size_t fit = partial_elems / ((size_t)k.M * k.N);
+  if ((size_t)splits > fit) splits = (int)fit;
+  return splits < 1 ? 1 : splits;
+}
+
+struct PpPlan { int bm = 0, bn = 0, splits = 1; unsigned grid = 0; };      // grid: workgroups (persistent: one per CU at most)
+bool gemm_pp_plan(const GemmK& k, size_t partial_elems, const GemmHooks& h, PpPlan* plan);
 void launch_gemm_pp(int dtype, const GemmK& k, const PpPlan& plan, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 
 }  // namespace dh

@@ -690,16 +690,9 @@ static int pp_mode(const GemmK& k) {
   return PP_GENERIC;
 }
 
-// bytes the A descriptor must cover
-static size_t pp_a_bytes(const GemmK& k) {
-  if (k.mode == A_DENSE) return ((size_t)(k.M - 1) * k.lda + k.K) * 2;
-  const size_t B = (size_t)k.M / ((size_t)k.Hout * k.Wout);
-  return B * k.Hin * k.Win * (size_t)k.lda * 2;
-}
-
 // Compute units of the current device (cached): the persistent grid has one workgroup per CU and the policy asks for 7/8 of a
 // round of tiles.  256 on an MI355X in SPX mode (what every measurement of this file was taken on) and the fallback without a device
-// (dh_dbg_gemm_pp_plan on the CPU); a partitioned (CPX) or smaller device gets its own count instead of a mistuned 256.
+// (the host-only plan queries on the CPU); a partitioned (CPX) or smaller device gets its own count instead of a mistuned 256.
 static int pp_device_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -711,7 +704,11 @@ static int pp_device_cus() {
 }
 
 static int g_pp_glu = -1;                           // dh_dbg_gemm_pp_glu: the GEGLU-epilogue launches (-1 policy, 0 never, 1 always)
-bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan) {
+static int g_pp_persist = 1;                        // dh_dbg_gemm_pp_persist: 0 = one workgroup per work item (the round-by-round form)
+void gemm_pp_hooks(GemmHooks* h) { h->pp_glu = g_pp_glu; h->pp_persist = g_pp_persist; h->cus = pp_device_cus(); }
+
+bool gemm_pp_plan(const GemmK& k, size_t partial_elems, const GemmHooks& h, PpPlan* plan) {
+  const int force = h.pp_force;
   if (force == 1) return false;
   // what the kernel carries: the plain epilogue (bias, per-image vector, residual), 16-byte aligned rows, descriptors below 2 GiB
   if (k.ln_s || k.act_silu) return false;
@@ -721,8 +718,8 @@ bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan)
   // changed that (profiles/r05_ab_pp_shortk.txt, M = 32768, F = 1280: forward 133 -> 124 us saving / 110 -> 97 not saving, backward
   // 121 -> 113; M = 8192, F = 2560: forward 93.5 -> 90.9 / 86.6 -> 82.3 but backward 68 -> 73; the other batch sizes in
   // profiles/r05_ab_pp_glu_by_batch.txt): forward from M = 2048 on, backward from M = 32768 on.
-  // g_pp_glu: -1 = this policy, 0 = never, 1 = always.
-  const bool glu_here = force == 2 || g_pp_glu > 0 || (g_pp_glu < 0 && ((glu == 1 && k.M >= 2048) || k.M >= 32768));
+  // h.pp_glu: -1 = this policy, 0 = never, 1 = always.
+  const bool glu_here = force == 2 || h.pp_glu > 0 || (h.pp_glu < 0 && ((glu == 1 && k.M >= 2048) || k.M >= 32768));
   if (glu && !glu_here) return false;
   if (glu == 2 && k.glub_f > 0 && k.glub_f < k.N) return false;      // the column-split form (a folded proj_out) is k_gemm_dma's
   if (glu && (k.mode != A_DENSE || k.N % 128 || k.rowvec || k.R || (glu == 1 && (k.glu_ldy % 8 || ((size_t)k.glu_y & 15))) ||
@@ -737,7 +734,7 @@ bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan)
   if ((k.C && (k.ldc % 8 || ((size_t)k.C & 15))) || k.lda % 8 || ((size_t)k.A & 15) || ((size_t)k.W & 15)) return false;
   if (k.R && (k.ldr % 8 || ((size_t)k.R & 15))) return false;
   if (k.mode != A_DENSE && (k.Hout <= 0 || k.Wout <= 0 || k.M % (k.Hout * k.Wout) || k.Cin % 64 || k.K != 9 * k.Cin)) return false;
-  const size_t ab = pp_a_bytes(k) + (size_t)(k.Win + 1) * k.lda * 2, wb = (size_t)k.N * k.K * 2;
+  const size_t ab = gemm_a_bytes(k) + (size_t)(k.Win + 1) * k.lda * 2, wb = (size_t)k.N * k.K * 2;
   if (ab >= 0x7ff00000ull || wb >= 0x7ff00000ull) return false;
   const int ktiles = k.K / 64;
   // tile: the 160-column tile where it divides N (N = 320, 640, 960, 1280 ...), else 128 columns (the GEGLU epilogues: 128, a
@@ -746,7 +743,7 @@ bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan)
   const int tn = k.N / bn;
   const long t256 = (long)cdiv(k.M, 256) * tn, t128 = (long)cdiv(k.M, 128) * tn;
   int bm = 0, splits = 1;
-  const int cus = pp_device_cus(), fill = cus - cus / 8;      // 256 / 224 on the MI355X
+  const int cus = h.cus, fill = cus - cus / 8;      // 256 / 224 on the MI355X
   if (t256 >= fill) bm = 256;                                // one round or more of 256-row tiles
   else if (t128 >= fill) bm = 128;                           // (M = 8192, N = 640 at batch 8: 64 x 4)
   else if (!glu && k.partial && ktiles >= 64 && t256 >= 64 && k.M >= 1024 && k.M <= 4096) {
@@ -755,11 +752,7 @@ bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan)
     // shapes of this kind stay on k_gemm_dma's tiles.  From 64 K tiles on: the B = 1 input gradients with K = 2880 (45 tiles, M = 4096,
     // N = 640 / 960) lose 7 - 18 % here, K = 5760 wins 3 - 4 % (profiles/r05_ab_pp_splitk_branch.txt)
     bm = 256;
-    splits = (int)(cus / t256);
-    if (splits > ktiles / 8) splits = ktiles / 8;
-    if (splits > 8) splits = 8;
-    const size_t fit = partial_elems / ((size_t)k.M * k.N);
-    if ((size_t)splits > fit) splits = (int)fit;
+    splits = clamp_splits((int)(cus / t256), ktiles / 8, 8, k, partial_elems);
     if (splits < 2) bm = 0;
   }
   if (force == 2 && bm == 0) { bm = k.M > 128 ? 256 : 128; splits = 1; }      // test hook: any shape the kernel can carry
@@ -773,7 +766,6 @@ bool gemm_pp_plan(const GemmK& k, size_t partial_elems, int force, PpPlan* plan)
 // wave and tile the last 1 / 3 go out between the MFMAs of the multiply segment, which balances the two segments of an interval
 // (-> 59.7 us; 128x160 conv K = 5760 76.2 -> 65.9 us)
 constexpr int PP_SHIP_256 = PPV_K64 | (1 << PPV_NDIM_SHIFT), PP_SHIP_128 = PPV_K64 | (3 << PPV_NDIM_SHIFT);
-static int g_pp_persist = 1;                        // dh_dbg_gemm_pp_persist: 0 = one workgroup per work item (the round-by-round form)
 static int g_pp_ablate = 0;                         // dh_dbg_gemm_pp_ablate (measurement build)
 static int g_pp_variant = -1;                       // measurement builds (-DDH_PP_VARIANTS): dh_dbg_gemm_pp_variant; -1 = shipped
 static unsigned long long* g_pp_ts = nullptr;
@@ -837,7 +829,7 @@ void launch_gemm_pp(int dtype, const GemmK& kin, const PpPlan& plan, hipStream_t
   k.k_per_split = tiles_per_split * 64;
   k.pp_tm = cdiv(k.M, plan.bm);
   k.pp_tn = k.N / plan.bn;
-  k.pp_a_bytes = (unsigned)pp_a_bytes(k);
+  k.pp_a_bytes = (unsigned)gemm_a_bytes(k);
   k.pp_w_bytes = (unsigned)((size_t)k.N * k.K * 2);
   k.pp_ts = g_pp_ts;
   // which operand panel consecutive work items (= one XCD's L2) share: the column tiles of a row tile share its A rows, the
@@ -848,10 +840,7 @@ void launch_gemm_pp(int dtype, const GemmK& kin, const PpPlan& plan, hipStream_t
   const double row_fastest = w_tot + (double)(k.pp_tn * k.splits < 8 ? k.pp_tn * k.splits : 8) * a_tot;
   k.pp_order = (row_fastest < col_fastest ? 1 : 0) | g_pp_ablate;
   k.pp_nwork = k.pp_tm * k.pp_tn * k.splits;
-  // persistent grid: one workgroup per CU (256: a multiple of 8, the XCD order of the work items holds in every round)
-  int slots = pp_device_cus();
-  if (g_pp_persist == 0 || k.pp_nwork <= slots) slots = k.pp_nwork;
-  dim3 grid((unsigned)slots);
+  dim3 grid(plan.grid);        // (gemm_plan: persistent, one workgroup per CU at most)
   const int mode = pp_mode(k);
   if (dtype == DH_DTYPE_F16) pp_launch<f16>(k, plan, mode, grid, st, e0, e1);
   else pp_launch<bf16>(k, plan, mode, grid, st, e0, e1);
@@ -875,7 +864,9 @@ extern "C" int dh_dbg_gemm_pp_plan(int M, int N, int K, int conv, int hw, int gl
   if (glu == 1) { k.glu_y = dummy; k.glu_ldy = N / 2; }
   if (glu == 2) { k.glub_x = dummy; k.glub_dx = dummy; k.C = nullptr; }
   dh::PpPlan plan;
-  const bool use = dh::gemm_pp_plan(k, partial_elems, 0, &plan);
+  dh::GemmHooks h;
+  dh::gemm_pp_hooks(&h);
+  const bool use = dh::gemm_pp_plan(k, partial_elems, h, &plan);
   *bm = use ? plan.bm : 0; *bn = use ? plan.bn : 0; *splits = use ? plan.splits : 0;
   return DH_OK;
 }

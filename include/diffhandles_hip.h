@@ -498,6 +498,38 @@ int dh_text_encoder_load_param(dh_text_encoder* e, int i, const float* src, void
 size_t dh_text_encoder_bytes(const dh_text_encoder* e);
 int dh_text_encoder_encode(dh_text_encoder* e, const float* embeds, int batch, int tokens, float* out, void* stream);
 
+/* --------------------------------------------------------------------------------------
+ * Host-only query of the GEMM dispatch (csrc/gemm.hip: gemm_plan): which kernel, tile, K split, epilogue riders and reduce a
+ * launch of this description gets.  No launch, no device needed; the description carries no pointers.  out receives 23 values:
+ * pp, bm, bn, stages, wg, kg, mw, gm (0 dense, 1 stride-1 3x3, 2 generic), buf, lnf, epi (0 plain, 1 / 2 GEGLU forward / backward,
+ * 3 / 4 cross-attention forward / dQ), splits, k_per_split, grid x, y, z, a_bytes, w_bytes, gn_epi (1 forward, 2 backward GroupNorm
+ * statistics in the epilogue), gn_cpg, gn_S, xa, reduce (0 none, 1 plain, 2 / 3 with GroupNorm forward / backward statistics,
+ * 4 with the LayerNorm backward).  tests/test_gemm_plan.py pins the table of the SD-2-depth passes.
+ * ------------------------------------------------------------------------------------ */
+#define DH_GEMM_Q_BIAS 0x1u
+#define DH_GEMM_Q_RESIDUAL 0x2u
+#define DH_GEMM_Q_ROWVEC 0x4u        /* per-image vector */
+#define DH_GEMM_Q_SILU 0x8u
+#define DH_GEMM_Q_LNF 0x10u          /* folded LayerNorm */
+#define DH_GEMM_Q_GN_STATS 0x20u     /* GroupNorm statistics of the output wanted (gn_HW, gn_G) */
+#define DH_GEMM_Q_GN_BWD 0x40u       /* ... the backward statistics: the output is dy of that GroupNorm */
+#define DH_GEMM_Q_LN_BWD 0x80u       /* LayerNorm backward on the split-K reduce */
+#define DH_GEMM_Q_GLU_FWD 0x100u
+#define DH_GEMM_Q_GLU_BWD 0x200u     /* glub_f: columns of the GEGLU's dy (N = all) */
+#define DH_GEMM_Q_XATTN_FWD 0x400u   /* cross-attention in the epilogue (xa_Nq, xa_Nk, xa_H) */
+#define DH_GEMM_Q_XATTN_DQ 0x800u    /* ... its dQ */
+#define DH_GEMM_Q_ALIGNED 0x1000u    /* every operand 16-byte aligned (and, by its shape, below 2 GiB) */
+typedef struct dh_gemm_plan_query {
+  int32_t M, N, K;
+  int32_t conv;              /* 0 dense, 1 = 3x3 convolution (K = 9 Cin), 2 = input gradient of a stride-2 3x3 convolution */
+  int32_t hw, stride, up;    /* conv: side of the square source image, stride 1 / 2, nearest-2x up-sampled source */
+  int64_t lda, ldc;          /* 0 = the defaults: K (dense) or Cin (conv); N */
+  uint64_t partial_elems;    /* f32 elements of split-K workspace */
+  uint32_t flags;            /* DH_GEMM_Q_* */
+  int32_t gn_HW, gn_G, glub_f, xa_Nq, xa_Nk, xa_H;
+} dh_gemm_plan_query;
+int dh_dbg_gemm_plan(const dh_gemm_plan_query* q, int32_t* out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

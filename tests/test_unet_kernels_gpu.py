@@ -111,6 +111,64 @@ def test_gemm_dense(dtype, M, N, K):
         close(C, F.silu(z), tol, tol, "gemm silu/rowvec")
 
 
+# case -> the arm of launch_planned's switch it reaches: (k_gemm_pp, BM, BN, stages, K groups, wave multiplier).  The first five are the
+# shapes the query was specified with; under the policy's short-K rule four of them run the 64x64 tile, so the smallest shapes that
+# reach the 128x128 tile, the unsplit 128x64 tile, a convolution off the 64x64 tile and k_gemm_pp follow (tests/test_gemm_plan.py has
+# the thresholds these sit on)
+PLAN_CASES = {
+    "64x64x64": (0, 64, 64, 4, 1, 1),
+    "256x128x2048 split": (0, 128, 64, 3, 2, 1),
+    "128x320x64": (0, 64, 64, 4, 1, 1),
+    "512x128x64 bias": (0, 64, 64, 4, 1, 1),
+    "conv 8x8 Cin 64": (0, 64, 64, 4, 1, 1),
+    "2048x1024x640": (0, 128, 128, 4, 1, 2),         # 16 x 8 = 128 big tiles: the 128x128 eight-wave tile
+    "1024x640x2048": (0, 128, 64, 3, 2, 1),          # 8 x 5 = 40 tiles of 128x128, 32 K tiles, no workspace: the unsplit 128x64 tile
+    "conv 16x16 Cin 256": (0, 128, 64, 3, 2, 1),     # 36 K tiles: a stride-1 3x3 convolution on the 128x64 tile
+    "14336x320x64": (1, 128, 160, 0, 0, 0),          # 112 x 2 = 224 tiles of 128x160: k_gemm_pp
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("case", list(PLAN_CASES))
+def test_gemm_plan_query_equals_launch(dtype, case):
+    """What the host-only query (dh_dbg_gemm_plan) says about a launch is what launch_gemm then does: dh_dbg_gemm_last_tile reports
+    the tile, K groups, stages and waves that launch_tile wrote from its own template arguments (so a wrong arm of launch_planned's
+    switch fails here) and the splits, family and GroupNorm riders of the plan the launch ran.  PLAN_CASES names the arm each small
+    shape reaches.  The outputs are checked against fp32 as everywhere in this file."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_gemm_plan import ALIGNED, BIAS, named, plan
+    g = torch.Generator(device=dev()).manual_seed(len(case))
+    bias, split, conv, hw = None, False, 0, 0
+    if case.startswith("conv"):
+        hw, Cin = int(case.split()[1].split("x")[0]), int(case.split()[-1])
+        M, N, K, conv = hw * hw, 64, 9 * Cin, 1
+        x = torch.randn(1, Cin, hw, hw, generator=g, device=dev()).to(dtype)
+        w = (torch.randn(N, Cin, 3, 3, generator=g, device=dev()) / K ** 0.5).to(dtype)
+        ref = nhwc(F.conv2d(x.float(), w.float(), None, padding=1)).reshape(M, N)
+        A, lda, W, mode, geo = nhwc(x), Cin, w.permute(0, 2, 3, 1).reshape(N, K).contiguous(), 1, (hw, hw, Cin, hw, hw, 1, 0)
+    else:
+        M, N, K = (int(v) for v in case.split()[0].split("x"))
+        split = "split" in case
+        A = torch.randn(M, K, generator=g, device=dev()).to(dtype)
+        W = (torch.randn(N, K, generator=g, device=dev()) / K ** 0.5).to(dtype)
+        ref = A.float() @ W.float().t()
+        lda, mode, geo = K, 0, (0, 0, 0, 0, 0, 1, 0)
+        if "bias" in case:
+            bias = torch.randn(N, generator=g, device=dev())
+            ref = ref + bias
+    C = run_gemm(dtype, A, lda, W, M, N, K, mode=mode, geo=geo, bias=bias, split=split)
+    rep = (ctypes.c_int * 9)()
+    L().check(L().lib().dh_dbg_gemm_last_tile(rep), "dh_dbg_gemm_last_tile")
+    p = named(plan(M, N, K, conv, hw, flags=ALIGNED | (BIAS if bias is not None else 0), part=(16 << 20) if split else 0))
+    print(f"{case} {dtype}: last tile {list(rep)}, plan {p}")
+    # (the first five values are what launch_tile wrote from its own template arguments, the rest the plan the launch was given)
+    assert list(rep) == [p["bm"], p["bn"], p["kg"], p["stages"], p["mw"], p["splits"], p["pp"], p["gn_epi"], int(p["reduce"] in (2, 3))]
+    assert (p["pp"], p["bm"], p["bn"], p["stages"], p["kg"], p["mw"]) == PLAN_CASES[case]
+    assert (p["splits"] > 1) == split and p["reduce"] == (1 if split else 0) and p["gm"] == conv
+    tol = 4e-3 if dtype == torch.float16 else 2.5e-2
+    close(C, ref, tol, tol, f"gemm {case}")
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("M,N,K", [(4096, 960, 320), (1024, 640, 640), (256, 2560, 1280)])
 @pytest.mark.parametrize("mean_over_std", [0.0, 3.0, 30.0])

@@ -169,6 +169,20 @@ DEBUG_SIGNATURES = {
     #  have_out, stream)
     "dh_dbg_gemm_groupnorm_bwd_res": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_sz, c_i, c_i, c_p, c_p, c_p,
                                         c_p, c_i, c_p, c_p, ctypes.POINTER(c_i), c_p]),
+    # ... and with the whole convolution geometry (and the forward's per-image vector)
+    # (dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, Hout, Wout, stride, up, bias, rowvec, rowvec_ld, rows_per_batch, R, ldr, C, partial,
+    #  partial_elems, HW, G, gamma, beta, eps, silu, Y, stats, scratch, have_out, stream)
+    "dh_dbg_gemm_groupnorm_geo": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_l,
+                                        c_p, c_p, c_sz, c_i, c_i, c_p, c_p, c_f, c_i, c_p, c_p, c_p, ctypes.POINTER(c_i), c_p]),
+    # (dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, Hout, Wout, stride, up, R, ldr, C, partial, partial_elems, HW, G, x, gamma, beta,
+    #  stats, silu, dx, scratch, have_out, stream)
+    "dh_dbg_gemm_groupnorm_bwd_geo": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_sz,
+                                            c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, ctypes.POINTER(c_i), c_p]),
+    # (dtype, A, lda, W, M, N, K, ln_s, ln_t, ln_stats, ln_eps, C, y, stream)
+    "dh_dbg_gemm_lnfold_glu": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p]),
+    # (dtype, A, lda, W, M, N, K, x, ldx, gamma, stats, add, dy, dx, partial, partial_elems, done_out, stream)
+    "dh_dbg_gemm_layernorm_bwd": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                        ctypes.POINTER(c_i), c_p]),
     # (dtype, a, Ca, b, Cb, out, B, HW, G, gamma, beta, eps, silu, Y, stats, scratch, stream)
     "dh_dbg_concat_groupnorm": (c_i, [c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p]),
     "dh_dbg_gemm_last_tile": (c_i, [ctypes.POINTER(c_i)]),

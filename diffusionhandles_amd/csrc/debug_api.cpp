@@ -54,10 +54,11 @@ extern "C" int dh_dbg_gemm(int dtype, const void* A, long lda, const void* W, in
 // unsplit k_gemm_dma launch: gemm.hip gn_epi) and from the statistics kernel otherwise.  *have_out = what the GEMM reported
 // (0 = statistics kernel, 1 = reduce, > 1 = slices left by the epilogue); stats [B * G][2] = (mean, rstd).  R (row pitch ldr) is
 // the residual added before rounding, or NULL; it may be C itself (in place, as the engine's resnet shortcut adds run).
-extern "C" int dh_dbg_gemm_groupnorm_res(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin, int Win,
-                                     int Cin, const float* bias, const void* R, long ldr, void* C, float* partial, size_t partial_elems, int HW, int G,
-                                     const float* gamma, const float* beta, float eps, int silu, void* Y, float* stats, float* scratch,
-                                     int* have_out, void* stream) {
+extern "C" int dh_dbg_gemm_groupnorm_geo(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin, int Win,
+                                         int Cin, int Hout, int Wout, int stride, int up, const float* bias, const float* rowvec, int rowvec_ld,
+                                         int rows_per_batch, const void* R, long ldr, void* C, float* partial, size_t partial_elems, int HW, int G,
+                                         const float* gamma, const float* beta, float eps, int silu, void* Y, float* stats, float* scratch,
+                                         int* have_out, void* stream) {
   DH_REQUIRE(A && W && C && Y && stats && scratch && gamma && beta && K % 64 == 0 && N % 64 == 0 && HW > 0 && M % HW == 0, "bad arguments");
   static void* tiled = nullptr;        // (this hook's own tiled copy: dh_dbg_gemm keeps the capacity of ITS buffer)
   static size_t cap = 0;
@@ -70,7 +71,8 @@ extern "C" int dh_dbg_gemm_groupnorm_res(int dtype, const void* A, long lda, con
   launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream, mode != 0 ? Cin : 0);
   GemmArgs g;
   g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = mode; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
-  g.Hout = Hin; g.Wout = Win; g.stride = 1; g.up = 0; g.bias = bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = N;
+  g.Hout = Hout; g.Wout = Wout; g.stride = stride; g.up = up; g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld;
+  g.rows_per_batch = rows_per_batch; g.R = R; g.ldr = ldr; g.C = C; g.ldc = N;
   g.partial = partial; g.partial_elems = partial_elems;
   int have = 0;
   g.gn_part = scratch; g.gn_HW = HW; g.gn_G = G; g.gn_done = &have;
@@ -79,6 +81,15 @@ extern "C" int dh_dbg_gemm_groupnorm_res(int dtype, const void* A, long lda, con
   if (have_out) *have_out = have;
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+// ... a stride-1 convolution without up-sampling or a dense GEMM, no per-image vector (the hook's signature before
+// dh_dbg_gemm_groupnorm_geo took the whole geometry, kept for its existing callers)
+extern "C" int dh_dbg_gemm_groupnorm_res(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin, int Win,
+                                     int Cin, const float* bias, const void* R, long ldr, void* C, float* partial, size_t partial_elems, int HW, int G,
+                                     const float* gamma, const float* beta, float eps, int silu, void* Y, float* stats, float* scratch,
+                                     int* have_out, void* stream) {
+  return dh_dbg_gemm_groupnorm_geo(dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, Hin, Win, 1, 0, bias, nullptr, 0, 1, R, ldr, C, partial,
+                                   partial_elems, HW, G, gamma, beta, eps, silu, Y, stats, scratch, have_out, stream);
 }
 // ... without a residual (the hook's original signature, kept for its existing callers)
 extern "C" int dh_dbg_gemm_groupnorm(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin, int Win,
@@ -92,10 +103,11 @@ extern "C" int dh_dbg_gemm_groupnorm(int dtype, const void* A, long lda, const v
 // reduce, or its own epilogue: *have_out > 1 = that many slices per group) leaves the backward slice statistics in `scratch` and
 // the GroupNorm backward writes dx.  (engine: every input-gradient GEMM in front of a GroupNorm backward; R = C, pitch ldr, when the
 // gradient already holds a contribution it accumulates onto -- NULL otherwise)
-extern "C" int dh_dbg_gemm_groupnorm_bwd_res(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
-                                         int Win, int Cin, const void* R, long ldr, void* C, float* partial, size_t partial_elems, int HW, int G, const void* x,
-                                         const float* gamma, const float* beta, const float* stats, int silu, void* dx,
-                                         float* scratch, int* have_out, void* stream) {
+extern "C" int dh_dbg_gemm_groupnorm_bwd_geo(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
+                                             int Win, int Cin, int Hout, int Wout, int stride, int up, const void* R, long ldr, void* C,
+                                             float* partial, size_t partial_elems, int HW, int G, const void* x, const float* gamma,
+                                             const float* beta, const float* stats, int silu, void* dx, float* scratch, int* have_out,
+                                             void* stream) {
   DH_REQUIRE(A && W && C && x && dx && stats && scratch && gamma && beta && K % 64 == 0 && N % 64 == 0 && HW > 0 && M % HW == 0, "bad arguments");
   static void* tiled = nullptr;
   static size_t cap = 0;
@@ -108,7 +120,7 @@ extern "C" int dh_dbg_gemm_groupnorm_bwd_res(int dtype, const void* A, long lda,
   launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream, mode != 0 ? Cin : 0);
   GemmArgs g;
   g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = mode; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
-  g.Hout = Hin; g.Wout = Win; g.stride = 1; g.up = 0; g.R = R; g.ldr = ldr; g.C = C; g.ldc = N;
+  g.Hout = Hout; g.Wout = Wout; g.stride = stride; g.up = up; g.R = R; g.ldr = ldr; g.C = C; g.ldc = N;
   g.partial = partial; g.partial_elems = partial_elems;
   int have = 0;
   g.gnb_x = x; g.gnb_ldx = N; g.gnb_gamma = gamma; g.gnb_beta = beta; g.gnb_stats = stats; g.gnb_silu = silu;
@@ -118,6 +130,15 @@ extern "C" int dh_dbg_gemm_groupnorm_bwd_res(int dtype, const void* A, long lda,
   if (have_out) *have_out = have;
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+// ... a stride-1 convolution without up-sampling or a dense GEMM (the hook's signature before dh_dbg_gemm_groupnorm_bwd_geo took the
+// whole geometry, kept for its existing callers)
+extern "C" int dh_dbg_gemm_groupnorm_bwd_res(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
+                                         int Win, int Cin, const void* R, long ldr, void* C, float* partial, size_t partial_elems, int HW, int G, const void* x,
+                                         const float* gamma, const float* beta, const float* stats, int silu, void* dx,
+                                         float* scratch, int* have_out, void* stream) {
+  return dh_dbg_gemm_groupnorm_bwd_geo(dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, Hin, Win, 1, 0, R, ldr, C, partial, partial_elems, HW, G, x,
+                                       gamma, beta, stats, silu, dx, scratch, have_out, stream);
 }
 // ... without a residual (the hook's original signature, kept for its existing callers)
 extern "C" int dh_dbg_gemm_groupnorm_bwd(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
@@ -243,6 +264,57 @@ extern "C" int dh_dbg_gemm_glu(int dtype, int bwd, const void* A, long lda, cons
   if (bwd) { g.glub_x = x; g.glub_dx = dx; }
   else { g.C = C; g.ldc = N; g.glu_y = y; g.glu_ldy = N / 2; }
   launch_gemm(dtype, g, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// the GEGLU forward epilogue on a LayerNorm-folded GEMM (engine: ff.net.0.proj at B <= 3): A is the LayerNorm input, W [N = 2F][K]
+// carries gamma, ln_s / ln_t as dh_dbg_gemm_lnfold takes them (the bias inside ln_t), all three in the PAIRED row order; C (may be
+// NULL) receives the pre-activations [M][2F] (paired), y [M][F] = value * gelu(gate), ln_stats [M][2] = (mean, rstd)
+extern "C" int dh_dbg_gemm_lnfold_glu(int dtype, const void* A, long lda, const void* W, int M, int N, int K, const float* ln_s,
+                                      const float* ln_t, float* ln_stats, float ln_eps, void* C, void* y, void* stream) {
+  DH_REQUIRE(A && W && y && ln_s && ln_t && ln_stats && K % 64 == 0 && N % 128 == 0, "bad arguments (K % 64, N % 128)");
+  static void* tiled = nullptr;
+  static size_t tiled_cap = 0;
+  const size_t need = (size_t)N * K * 2;
+  if (need > tiled_cap) {
+    if (tiled) (void)hipFree(tiled);
+    DH_CHECK_HIP(hipMalloc(&tiled, need));
+    tiled_cap = need;
+  }
+  launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream);
+  GemmArgs g;
+  g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = A_DENSE; g.C = C; g.ldc = N;
+  g.ln_s = ln_s; g.ln_t = ln_t; g.ln_stats = ln_stats; g.ln_eps = ln_eps;
+  g.glu_y = y; g.glu_ldy = N / 2;
+  launch_gemm(dtype, g, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// input-gradient GEMM -> LayerNorm backward the way the engine's backward pass runs the pair: dy = A W^T [M][N] is the gradient of
+// LayerNorm(x) (x: row pitch ldx, saved (mean, rstd) in stats [M][2]); dx [M][N] = the LayerNorm's input gradient (+ add when
+// given).  *done_out = 1: the split-K reduce of the GEMM applied the backward to the summed rows and dy is untouched; 0: dy
+// holds the GEMM's output and the LayerNorm backward ran behind it.
+extern "C" int dh_dbg_gemm_layernorm_bwd(int dtype, const void* A, long lda, const void* W, int M, int N, int K, const void* x, long ldx,
+                                         const float* gamma, const float* stats, const void* add, void* dy, void* dx, float* partial,
+                                         size_t partial_elems, int* done_out, void* stream) {
+  DH_REQUIRE(A && W && x && gamma && stats && dy && dx && K % 64 == 0 && N % 64 == 0 && ldx >= N, "bad arguments (N, K must be multiples of 64)");
+  static void* tiled = nullptr;
+  static size_t tiled_cap = 0;
+  const size_t need = (size_t)N * K * 2;
+  if (need > tiled_cap) {
+    if (tiled) (void)hipFree(tiled);
+    DH_CHECK_HIP(hipMalloc(&tiled, need));
+    tiled_cap = need;
+  }
+  launch_tile_weights(dtype, W, tiled, N, K, (hipStream_t)stream);
+  GemmArgs g;
+  g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = A_DENSE; g.C = dy; g.ldc = N;
+  g.partial = partial; g.partial_elems = partial_elems;
+  int done = 0;
+  g.lnb_x = x; g.lnb_ldx = ldx; g.lnb_gamma = gamma; g.lnb_stats = stats; g.lnb_add = add; g.lnb_dx = dx; g.lnb_done = &done;
+  launch_gemm(dtype, g, (hipStream_t)stream);
+  if (!done) launch_layernorm_bwd(dtype, x, dy, gamma, stats, add, dx, M, N, (hipStream_t)stream, ldx);
+  if (done_out) *done_out = done;
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

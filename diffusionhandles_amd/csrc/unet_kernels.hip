@@ -336,7 +336,7 @@ __global__ void __launch_bounds__(256) k_gn_apply(const T* x, const float* gamma
   bool live = idx < total;
   unsigned pix = live ? idx / cchunks : 0;
   size_t row = (size_t)b * HW + pix;
-  int c0 = (int)(idx - pix * cchunks) * 8;
+  int c0 = live ? (int)(idx - pix * cchunks) * 8 : 0;                  // (a thread past the end loads chunk 0 of its image, not bytes past x, gamma and beta)
   uint4 raw = *reinterpret_cast<const uint4*>(x + row * C + c0);      // in flight under the slice combine
   float gmv[8], btv[8];                                               // so are the affine parameters of the 8 channels
   *reinterpret_cast<float4*>(gmv) = *reinterpret_cast<const float4*>(gamma + c0);
@@ -424,7 +424,7 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(const T* x, const T* dy, c
   bool live = idx < total;
   unsigned pix = live ? idx / cchunks : 0;
   size_t row = (size_t)b * HW + pix;
-  int c0 = (int)(idx - pix * cchunks) * 8;
+  int c0 = live ? (int)(idx - pix * cchunks) * 8 : 0;                  // (a thread past the end loads chunk 0 of its image, not bytes past x, gamma and beta)
   uint4 rx = *reinterpret_cast<const uint4*>(x + row * C + c0);       // in flight under the slice combine
   uint4 rd = *reinterpret_cast<const uint4*>(dy + row * C + c0);
   uint4 ro = make_uint4(0, 0, 0, 0);
@@ -727,7 +727,8 @@ __global__ void __launch_bounds__(256, NCH == 1 ? 8 : (NCH <= 3 ? 4 : 1)) k_ln_b
 
 // The same backward with dy = the sum of `splits` f32 slabs [splits][rows][C] of a split-K input-gradient GEMM (no bias, no
 // residual): the reduce launch and the LayerNorm backward launch in one kernel, dy never goes to memory.  The sum is
-// rounded to the storage type first, so the result equals the two-kernel path bit for bit.
+// rounded to the storage type first and the backward below is k_ln_bwd's own arithmetic, so the result equals the two-kernel
+// path bit for bit.
 template <class T, int NCH>
 __global__ void __launch_bounds__(256, NCH == 1 ? 4 : (NCH <= 3 ? 2 : 1)) k_splitk_reduce_ln_bwd(const float* part, int splits, const T* x, const float* gamma,
                                                                        const float* stats, const T* add, T* dx, int rows, int C, long ldx) {
@@ -785,10 +786,19 @@ __global__ void __launch_bounds__(256, NCH == 1 ? 4 : (NCH <= 3 ? 2 : 1)) k_spli
       }
     }
   }
+  // the summed dy, rounded to the storage type and packed the way k_ln_bwd loads it.  From here on the arithmetic is k_ln_bwd's,
+  // expression for expression: the compiler may contract a * b + c into an fma wherever the source's expressions let it, so the
+  // two kernels round alike only while their expressions have the same shape.  (This kernel used to keep the product dy * gamma of
+  // the first pass in registers for the second; k_ln_bwd forms it again inside d - s1, where it can fuse.  About one element in
+  // 10^4 then came out one 16-bit ulp off the two-kernel path; tests/test_gemm_classes_gpu.py compares the two bit for bit.)
+  uint4 rd[NCH];
 #pragma unroll
-  for (int k = 0; k < NCH; ++k)
+  for (int k = 0; k < NCH; ++k) {
+    T o[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) d[k][i] = to_f32<T>(from_f32<T>(d[k][i]));
+    for (int i = 0; i < 8; ++i) o[i] = from_f32<T>(d[k][i]);
+    rd[k] = *reinterpret_cast<uint4*>(o);
+  }
   const float mean = stats[2 * (size_t)row], rstd = stats[2 * (size_t)row + 1];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -799,12 +809,13 @@ __global__ void __launch_bounds__(256, NCH == 1 ? 4 : (NCH <= 3 ? 2 : 1)) k_spli
       const float4 g1 = *reinterpret_cast<const float4*>(gamma + ch * 8 + 4);
       const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
       const T* xv = reinterpret_cast<const T*>(&rx[k]);
+      const T* dv = reinterpret_cast<const T*>(&rd[k]);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float xh = (to_f32<T>(xv[i]) - mean) * rstd;
-        d[k][i] *= g[i];
-        s1 += d[k][i];
-        s2 += d[k][i] * xh;
+        const float d = to_f32<T>(dv[i]) * g[i];
+        s1 += d;
+        s2 += d * xh;
       }
     }
   }
@@ -814,15 +825,20 @@ __global__ void __launch_bounds__(256, NCH == 1 ? 4 : (NCH <= 3 ? 2 : 1)) k_spli
   for (int k = 0; k < NCH; ++k) {
     const int ch = lane + 64 * k;
     if (ch < nch) {
+      const float4 g0 = *reinterpret_cast<const float4*>(gamma + ch * 8);
+      const float4 g1 = *reinterpret_cast<const float4*>(gamma + ch * 8 + 4);
+      const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
       uint4 ra = make_uint4(0, 0, 0, 0);
       if (add) ra = *reinterpret_cast<const uint4*>(add + base + ch * 8);
       const T* xv = reinterpret_cast<const T*>(&rx[k]);
+      const T* dv = reinterpret_cast<const T*>(&rd[k]);
       const T* av = reinterpret_cast<const T*>(&ra);
       T o[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float xh = (to_f32<T>(xv[i]) - mean) * rstd;
-        float r = rstd * (d[k][i] - s1 - xh * s2);
+        const float d = to_f32<T>(dv[i]) * g[i];
+        float r = rstd * (d - s1 - xh * s2);
         if (add) r += to_f32<T>(av[i]);
         o[i] = from_f32<T>(r);
       }

@@ -44,6 +44,11 @@ class EnergyItem(ctypes.Structure):
                 ("fg_w", c_f), ("bg_w", c_f), ("grad_scale", c_f)]
 
 
+class LockItem(ctypes.Structure):
+    """dh_lock_item: one edit of dh_ddim_cfg_step_locked"""
+    _fields_ = [("keep", c_p), ("ref", c_p)]
+
+
 class GemmPlanQuery(ctypes.Structure):
     """dh_gemm_plan_query: one GEMM launch described without pointers (dh_dbg_gemm_plan)"""
     _fields_ = [("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("conv", ctypes.c_int32), ("hw", ctypes.c_int32),
@@ -148,6 +153,9 @@ SIGNATURES = {
     "dh_adam_step_scaled_batch": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_p]),
     "dh_latent_update_guarded": (c_i, [c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p]),
     "dh_ddim_cfg_step_flagged": (c_i, [c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_i, c_i, c_p, c_i, c_i, c_p]),
+    "dh_ddim_cfg_step_locked": (c_i, [c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.POINTER(LockItem), c_i, c_p, c_i, c_i,
+                                      c_p]),
+    "dh_keep_map": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_sz, c_p]),
 }
 
 # test hooks (csrc/debug_api.cpp): single-kernel entry points used only by tests/

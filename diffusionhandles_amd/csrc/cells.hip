@@ -65,9 +65,71 @@ __global__ void k_three_masks(const uint8_t* two, uint8_t* three, int n) {
   three[2 * n + i] = t;
 }
 
+// ---- keep map of the background lock (dh_keep_map) ---------------------------------------------------------------------
+// region [s*s] u8, zeroed by the entry: 1 where a cell holds a non-zero pixel of the mask or of the release image (one
+// thread per pixel; racing byte stores all write 1) ...
+__global__ void k_keep_region_pixels(const uint8_t* mask, const uint8_t* release, int res, int s, uint8_t* region) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= res * res) return;
+  if ((mask && mask[i]) || (release && release[i])) {
+    const int cs = res / s, y = i / res, x = i - y * res;
+    region[(y / cs) * s + x / cs] = 1;
+  }
+}
+
+// ... or a correspondence's source pixel, or its target pixel when that lies in the image
+__global__ void k_keep_region_corr(const long long* corr, int n, int res, int s, uint8_t* region) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long long* c = corr + 4 * (size_t)i;
+  const int cs = res / s;
+  if (c[0] >= 0 && c[0] < res && c[1] >= 0 && c[1] < res) region[(int)(c[1] / cs) * s + (int)(c[0] / cs)] = 1;
+  if (c[2] >= 0 && c[2] < res && c[3] >= 0 && c[3] < res) region[(int)(c[3] / cs) * s + (int)(c[2] / cs)] = 1;
+}
+
+// one thread per cell: d = Chebyshev distance to the nearest region cell inside the window of dilate + feather + 1 cells,
+// clipped by the border; keep = 0 for d <= dilate, (d - dilate) / (feather + 1) up to the window's edge, 1 beyond it
+__global__ void k_keep_distance(const uint8_t* region, int s, int dilate, int feather, float* keep) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= s * s) return;
+  const int y = i / s, x = i - y * s;
+  const int R = dilate + feather + 1;
+  const int y0 = max(y - R, 0), y1 = min(y + R, s - 1), x0 = max(x - R, 0), x1 = min(x + R, s - 1);
+  int d = R + 1;
+  for (int yy = y0; yy <= y1; ++yy) {
+    const int dy = abs(yy - y);
+    if (dy >= d) continue;
+    const uint8_t* row = region + (size_t)yy * s;
+    for (int xx = x0; xx <= x1; ++xx)
+      if (row[xx]) d = min(d, max(dy, abs(xx - x)));
+  }
+  float k = 1.f;
+  if (d <= dilate) k = 0.f;
+  else if (d <= R) k = fminf(1.f, (float)(d - dilate) / (float)(feather + 1));
+  keep[i] = k;
+}
+
 }  // namespace dh
 
 using namespace dh;
+
+extern "C" int dh_keep_map(const int64_t* corr, int n, const uint8_t* mask, const uint8_t* release, int res, int s, int dilate,
+                           int feather, float* keep, void* workspace, size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(keep && workspace && n >= 0 && (n == 0 || corr), "bad arguments");
+  DH_REQUIRE(s >= 1 && s <= 4096 && res >= s && res <= 32768 && res % s == 0, "res must be a multiple of s");
+  DH_REQUIRE(dilate >= 0 && feather >= 0 && dilate + feather <= 31, "dilate, feather >= 0 and dilate + feather <= 31");
+  DH_REQUIRE(workspace_bytes >= (size_t)s * s, "workspace too small (s * s bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* region = (uint8_t*)workspace;
+  DH_CHECK_HIP(hipMemsetAsync(region, 0, (size_t)s * s, st));
+  if (mask || release)
+    hipLaunchKernelGGL(k_keep_region_pixels, dim3(cdiv(res * res, 256)), dim3(256), 0, st, mask, release, res, s, region);
+  if (n > 0)
+    hipLaunchKernelGGL(k_keep_region_corr, dim3(cdiv(n, 256)), dim3(256), 0, st, (const long long*)corr, n, res, s, region);
+  hipLaunchKernelGGL(k_keep_distance, dim3(cdiv(s * s, 256)), dim3(256), 0, st, region, s, dilate, feather, keep);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
 
 extern "C" int dh_cells_workspace_bytes(int n, int grid, size_t* bytes) {
   DH_REQUIRE(n >= 0 && grid >= 1 && bytes, "bad arguments");

@@ -288,8 +288,69 @@ __global__ void k_ddim_cfg_flagged(float* out, const float* x, const float* eu, 
   }
 }
 
+// ---- background lock: the DDIM step blended with the reconstruction outside the edit's region -----------------------
+// The item table travels by value in the kernel arguments (the idiom of energy.hip); the item is a block index, so its row
+// is read through scalar loads.
+constexpr int LOCK_MAX_ITEMS = 16;
+struct LockTable {
+  dh_lock_item it[LOCK_MAX_ITEMS];
+};
+
+// grid (blocks of an edit's elements, edits).  o = k_ddim_cfg's value; out = o where keep == 0 or the edit is not locked,
+// the reconstruction r where keep == 1, o + keep (r - o) in between.  status (may be NULL): bit 1 of the edit's word where
+// o -- the step BEFORE the blend -- is not finite, as k_ddim_cfg_flagged sets it.
+__global__ void k_ddim_cfg_locked(float* out, const float* x, const float* eu, const float* ec, float scale, float sa_t,
+                                  float s1a_t, float sa_p, float s1a_p, int n_edit, int channels, const LockTable tab,
+                                  int* status, int t_idx, int iteration) {
+  const int edit = blockIdx.y;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  const float* keep = tab.it[edit].keep;
+  const float* ref = tab.it[edit].ref;
+  bool bad = false;
+  if (j < n_edit) {
+    const size_t i = (size_t)edit * n_edit + j;
+    float e = ec[i];
+    if (eu) { float u = eu[i]; e = u + scale * (e - u); }
+    float x0 = (x[i] - s1a_t * e) / sa_t;
+    const float o = sa_p * x0 + s1a_p * e;
+    bad = nonfinite_bits(o);
+    float v = o;
+    if (keep) {
+      const float k = keep[j / channels];
+      if (k >= 1.f) v = ref[j];
+      else if (k > 0.f) v = o + k * (ref[j] - o);
+    }
+    out[i] = v;
+  }
+  if (status && __ballot(bad) && (threadIdx.x & 63) == 0) {
+    atomicOr(&status[4 * edit], 2);
+    atomicCAS(&status[4 * edit + 2], 0, status_code(t_idx, iteration, 2));
+  }
+}
+
 }  // namespace dh
 using namespace dh;
+
+extern "C" int dh_ddim_cfg_step_locked(float* x_out, const float* x, const float* eps_u, const float* eps_c, float scale,
+                                       float alpha_t, float alpha_prev, int n, int n_edit, int channels,
+                                       const dh_lock_item* items, int n_items, int* status, int t_idx, int iteration,
+                                       void* stream) {
+  DH_REQUIRE(x_out && x && eps_c && items && n > 0 && n_edit > 0 && n % n_edit == 0 && channels > 0 && n_edit % channels == 0 &&
+             t_idx >= 0 && t_idx < 32767 && iteration >= 0, "bad arguments");
+  DH_REQUIRE(n_items >= 1 && n_items <= LOCK_MAX_ITEMS, "1 to 16 items (one per edit; never split)");
+  DH_REQUIRE(n_items == n / n_edit, "one item per edit of the batch");
+  LockTable tab;
+  for (int e = 0; e < LOCK_MAX_ITEMS; ++e) tab.it[e] = dh_lock_item{nullptr, nullptr};
+  for (int e = 0; e < n_items; ++e) {
+    DH_REQUIRE(!items[e].keep || items[e].ref, "a locked item needs its reconstruction latent");
+    tab.it[e] = items[e];
+  }
+  float sa_t = sqrtf(alpha_t), s1a_t = sqrtf(1.f - alpha_t), sa_p = sqrtf(alpha_prev), s1a_p = sqrtf(1.f - alpha_prev);
+  hipLaunchKernelGGL(k_ddim_cfg_locked, dim3(cdiv(n_edit, 256), n_items), dim3(256), 0, (hipStream_t)stream, x_out, x, eps_u,
+                     eps_c, scale, sa_t, s1a_t, sa_p, s1a_p, n_edit, channels, tab, status, t_idx, iteration);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
 
 extern "C" int dh_ddim_cfg_step(float* x_out, const float* x, const float* eps_u, const float* eps_c, float scale,
                                 float alpha_t, float alpha_prev, int n, void* stream) {

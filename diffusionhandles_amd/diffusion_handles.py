@@ -87,33 +87,65 @@ class DiffusionHandles:
         fp, _ = check_footprints(fp, ratio, f"{what}: conf depth_transform_footprints")
         return dict(footprints=fp, footprint_max_ratio=ratio)
 
+    def _lock_setup(self, what, activations, depth, release_mask=None):
+        """The optional top-level conf keys background_lock (absent = false), background_lock_dilate and
+        background_lock_feather (cells, absent = 2 each) and what an edit call needs for its lock: None with the lock off (a
+        release_mask is then an error), else (dilate, feather, trajectory, release_mask [res,res] or None).  Host checks only
+        (ValueError naming `what`): malformed keys, a release mask that is no res x res image, activations without the
+        reconstruction trajectory -- never a silent unlocked edit."""
+        from . import background_lock as BL
+        reach = BL.lock_conf(self.conf, what)
+        if reach is None:
+            if release_mask is not None:
+                raise ValueError(f"{what}: release_mask needs conf background_lock: true")
+            return None
+        release = BL.check_release_mask(release_mask, depth.shape[-1], what)
+        return reach + (BL.require_trajectory(activations, what), release)
+
+    def _edit_lock(self, setup, fg_masks, correspondences, depth):
+        """(keep, trajectory) of one edit -- its keep map from its mask(s), correspondences and release mask -- or None."""
+        if setup is None:
+            return None
+        from . import background_lock as BL
+        dilate, feather, trajectory, release = setup
+        corr = torch.as_tensor(correspondences).to(self.device)
+        keep = BL.keep_map(corr, fg_masks, release, depth.shape[-1], self.diffuser.unet.sample_size, dilate, feather)
+        self.last_keep_maps.append(keep)
+        return keep, trajectory
+
+    last_keep_maps = ()          # the keep maps of the last edit call with the background lock on, in edit order
+
     def transform_foreground_batch(self, depth, prompt, fg_mask, bg_depth, null_text_emb, init_noise, activations,
                                    transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                   streams=1, batch=None):
+                                   streams=1, batch=None, release_mask=None):
         """K edits of one image in batched passes (not in the reference; BASELINE config 3).
         transforms: list of (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
         pivot) (transform_foreground says what scale and pivot do).  Returns (images [K,3,H,W], [K disparities]).
         streams > 1: the K edits are cut into chunks of `batch` (default ceil(K / streams)) and the chunks run on `streams`
         concurrent lanes that share the U-Net weights (GuidedStableDiffuser.fork); batch = 1 runs single (B = 1) edits on the
-        lanes.  Images are bit-identical to the one-stream result at the same batch."""
+        lanes.  Images are bit-identical to the one-stream result at the same batch.  release_mask (conf background_lock
+        only): extra area every edit's lock sets free (transform_foreground_objects)."""
         from .depth_transform import reproject_edits
         K = len(transforms)
         fp = self._footprints("transform_foreground_batch")
+        lk = self._lock_setup("transform_foreground_batch", activations, depth, release_mask)
         with torch.no_grad():
             edits = reproject_edits(depth, bg_depth, fg_mask, self.diffuser.get_depth_intrinsics(device=depth.device),
                                     transforms, use_input_depth_normalization, device_correspondences=True, **fp)
+            self.last_keep_maps = []
+            lock = {} if lk is None else dict(lock=[self._edit_lock(lk, fg_mask, c, depth) for _, c in edits])
             per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
             if streams <= 1 and per >= K:
                 imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in edits], null_text_emb, prompt,
-                                                            activations, [c for _, c in edits], fg_weight, bg_weight)
+                                                            activations, [c for _, c in edits], fg_weight, bg_weight, **lock)
             elif per <= 1:
                 imgs = torch.cat(self.diffuser.guided_inference_lanes(init_noise, edits, null_text_emb, prompt, activations,
-                                                                      max(1, int(streams)), fg_weight, bg_weight))
+                                                                      max(1, int(streams)), fg_weight, bg_weight, **lock))
             else:
                 chunks = [([d for d, _ in edits[i:i + per]], [c for _, c in edits[i:i + per]]) for i in range(0, K, per)]
                 imgs = torch.cat(self.diffuser.guided_inference_batch_lanes(init_noise, chunks, null_text_emb, prompt,
                                                                             activations, max(1, int(streams)), fg_weight,
-                                                                            bg_weight))
+                                                                            bg_weight, **lock))
         return imgs, [d for d, _ in edits]
 
     def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences):
@@ -148,7 +180,7 @@ class DiffusionHandles:
 
     def transform_foreground_objects(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                      transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                     object_weights=None):
+                                     object_weights=None, release_mask=None):
         """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
         rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.  Each object
@@ -157,16 +189,21 @@ class DiffusionHandles:
         foreground term is the mean over all pairs, so the objects weigh by covered area -- unless object_weights says
         otherwise: "equal" holds every object equally, a sequence of M floats (finite, >= 0, not all zero) sets each weight;
         objects without a visible correspondence drop out and the rest are renormalised (DESIGN.md "A weight per object";
-        default configuration only).  Returns what transform_foreground returns.  'pc' re-projection only."""
+        default configuration only).  Returns what transform_foreground returns.  'pc' re-projection only.  release_mask (conf
+        background_lock only): a res x res image, non-zero = extra area the lock sets free beside the masks and the
+        correspondences, such as the shadow an object leaves behind."""
         labels, object_weights = self._object_labels(fg_masks, object_weights)
+        lk = self._lock_setup("transform_foreground_objects", activations, depth, release_mask)
         with torch.no_grad():
             (edited_disparity, correspondences), = self._reproject_objects(
                 "transform_foreground_objects", depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False)
+            self.last_keep_maps = []
+            lock = {} if lk is None else dict(lock=self._edit_lock(lk, fg_masks, correspondences, depth))
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
                 bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps,
-                object_labels=labels, object_weights=object_weights)
+                object_labels=labels, object_weights=object_weights, **lock)
         if self.conf.guided_diffuser.save_denoising_steps:
             edited_img, denoising_steps = results
             return edited_img, edited_disparity, denoising_steps
@@ -174,20 +211,25 @@ class DiffusionHandles:
 
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                           object_weights=None, streams=1, batch=None):
+                                           object_weights=None, streams=1, batch=None, release_mask=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
         edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
         pivot).  Returns (images [K,3,H,W], [K disparities]) as
         transform_foreground_batch does.  object_weights: as in transform_foreground_objects, one list for all K edits.
         streams / batch: transform_foreground_batch's -- chunks of `batch` edits (default ceil(K / streams)) on `streams`
-        lanes, batch = 1 runs single edits on the lanes; images are bit-identical to the one-stream result at the same batch."""
+        lanes, batch = 1 runs single edits on the lanes; images are bit-identical to the one-stream result at the same batch.
+        release_mask: transform_foreground_objects', one for all K edits."""
         labels, object_weights = self._object_labels(fg_masks, object_weights)
+        lk = self._lock_setup("transform_foreground_objects_batch", activations, depth, release_mask)
         K = len(edits)
         with torch.no_grad():
             res = self._reproject_objects("transform_foreground_objects_batch", depth, bg_depth, fg_masks, edits,
                                           use_input_depth_normalization, True)
             per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
             obj = dict(object_labels=labels, object_weights=object_weights)
+            self.last_keep_maps = []
+            if lk is not None:
+                obj["lock"] = [self._edit_lock(lk, fg_masks, c, depth) for _, c in res]
             if streams <= 1 and per >= K:
                 imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
                                                             [c for _, c in res], fg_weight, bg_weight, **obj)
@@ -214,7 +256,8 @@ class DiffusionHandles:
         background-depth and activation tensors) are re-projected together, once per image (multi-object edits: one label
         image per image); then one GuidedStableDiffuser.guided_inference_items for single- and multi-object edits alike.
         Returns (images [K,3,H,W], [K disparities]) in input order.  'pc' re-projection only; one resolution; needs an engine
-        with max_batch >= 2K."""
+        with max_batch >= 2K.  With conf background_lock every edit is locked to its own image's reconstruction; an edit may
+        carry a `release_mask` (transform_foreground_objects)."""
         from .depth_transform import check_transform, reproject_edits
         fp = self._footprints("transform_foregrounds")
         if self.conf.depth_transform_mode != "pc":
@@ -252,6 +295,8 @@ class DiffusionHandles:
                         raise ValueError(f"transform_foregrounds: edit {i}: {err}") from None
             else:
                 check_transform((0.0, None, None, e.get("scale"), e.get("pivot")), f"transform_foregrounds: edit {i}")
+        lks = [self._lock_setup(f"transform_foregrounds: edit {i}", e["activations"], e["depth"], e.get("release_mask"))
+               for i, e in enumerate(edits)]
         for i, e in enumerate(edits):
             if tuple(e["depth"].shape[-2:]) != tuple(edits[0]["depth"].shape[-2:]):
                 raise ValueError(f"transform_foregrounds: edit {i} has another resolution than edit 0 "
@@ -288,8 +333,11 @@ class DiffusionHandles:
                                           use_input_depth_normalization, device_correspondences=True, **fp)
                 for i, r in zip(idx, res):
                     reproj[i] = r
+            self.last_keep_maps = []
             items = [dict(latents=e["init_noise"], depth=d, uncond_embeddings=e["null_text_emb"], prompt=e["prompt"],
-                          activations_orig=e["activations"], correspondences=c, object_labels=labels[i], object_weights=weights[i])
+                          activations_orig=e["activations"], correspondences=c, object_labels=labels[i], object_weights=weights[i],
+                          lock=self._edit_lock(lks[i], e["fg_masks"] if e.get("fg_masks") is not None else e["fg_mask"], c,
+                                               e["depth"]))
                      for i, (e, (d, c)) in enumerate(zip(edits, reproj))]
             imgs = self.diffuser.guided_inference_items(items, [e.get("fg_weight") for e in edits],
                                                         [e.get("bg_weight") for e in edits])
@@ -306,8 +354,10 @@ class DiffusionHandles:
         turned about.  In 'pc' mode a magnified object leaves gaps between its points, bridged only up to the mask CLOSE's
         element (res // 50) -- unless the conf has depth_transform_footprints: true (footprint splatting, point mode only;
         depth_transform_footprint_max_ratio is its optional depth-ratio guard; depth_transform.reproject_object_edits);
-        'mesh' mode takes a pivot and refuses a scale and footprints (NotImplementedError)."""
+        'mesh' mode takes a pivot and refuses a scale and footprints (NotImplementedError).  With conf background_lock: true
+        the edit's latents are held to the reconstruction outside its region (DESIGN.md "Background lock"; both modes)."""
         fp = self._footprints("transform_foreground")
+        lk = self._lock_setup("transform_foreground", activations, depth)
         with torch.no_grad():
             geo = dict(depth=depth, bg_depth=bg_depth, fg_mask=fg_mask,
                        intrinsics=self.diffuser.get_depth_intrinsics(device=depth.device),
@@ -317,10 +367,12 @@ class DiffusionHandles:
                 edited_disparity, correspondences = transform_depth_footprints(**geo, **fp)
             else:
                 edited_disparity, correspondences = transform_depth(**geo, depth_transform_mode=self.conf.depth_transform_mode)
+            self.last_keep_maps = []
+            lock = {} if lk is None else dict(lock=self._edit_lock(lk, fg_mask, correspondences, depth))
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
-                bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps)
+                bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps, **lock)
         if self.conf.guided_diffuser.save_denoising_steps:
             edited_img, denoising_steps = results
             return edited_img, edited_disparity, denoising_steps

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import background_lock as _bl
 from . import guidance_scale as _gs
 from . import losses as _losses
 from .guided_diffuser import GuidedDiffuser
@@ -272,10 +273,14 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return kw
 
     # ---- native loop pieces --------------------------------------------------------------
-    def ddim_step(self, x, eps_u, eps_c, t, scale=CFG_SCALE, eta=0.0, generator=None):
-        """x, eps: [B,H,W,4] f32 channels-last.  CFG combine + DDIM step in one kernel."""
+    def ddim_step(self, x, eps_u, eps_c, t, scale=CFG_SCALE, eta=0.0, generator=None, out=None):
+        """x, eps: [B,H,W,4] f32 channels-last.  CFG combine + DDIM step in one kernel.  out: where to write the result (a
+        contiguous f32 tensor of x's shape, not x itself); None: a new tensor."""
         a_t, a_p = self.scheduler.step_alphas(t)
-        out = torch.empty_like(x)
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+            raise ValueError("ddim_step: out must be a contiguous tensor of x's shape and dtype, and not x")
         L = _lib.lib()
         _lib.check(L.dh_ddim_cfg_step(_lib.ptr(out), _lib.ptr(x), _lib.ptr(eps_u), _lib.ptr(eps_c), float(scale), a_t,
                                       a_p, x.numel(), _lib.stream_ptr()), "dh_ddim_cfg_step")
@@ -288,6 +293,25 @@ class GuidedStableDiffuser(GuidedDiffuser):
         _lib.check(_lib.lib().dh_ddim_cfg_step_flagged(_lib.ptr(out), _lib.ptr(x), _lib.ptr(eps_u), _lib.ptr(eps_c), float(scale),
                                                        a_t, a_p, x.numel(), x[0].numel(), _lib.ptr(status), int(t_idx),
                                                        int(iteration), _lib.stream_ptr()), "dh_ddim_cfg_step_flagged")
+        return out
+
+    def _ddim_step_locked(self, sts, x, eps_u, eps_c, t, status, t_idx, iteration, scale=CFG_SCALE):
+        """The DDIM step of a batch in which some edit has a background lock (dh_ddim_cfg_step_locked, one launch in place
+        of the step's one launch): edit e's output is blended with sts[e].lock.ref[t_idx] by sts[e].lock.keep; states without
+        a lock get the plain step.  status: the [K, 4] status words ('auto'), or None ('static')."""
+        K = x.shape[0]
+        if K > _bl.MAX_ITEMS:
+            raise RuntimeError(f"background lock: {K} edits in one step, at most {_bl.MAX_ITEMS}")
+        a_t, a_p = self.scheduler.step_alphas(t)
+        out = torch.empty_like(x)
+        items = (_lib.LockItem * K)()
+        for e, st in enumerate(sts):
+            if st.lock is not None:
+                items[e].keep, items[e].ref = st.lock.keep.data_ptr(), st.lock.ref[t_idx].data_ptr()
+        _lib.check(_lib.lib().dh_ddim_cfg_step_locked(_lib.ptr(out), _lib.ptr(x), _lib.ptr(eps_u), _lib.ptr(eps_c), float(scale),
+                                                      a_t, a_p, x.numel(), x[0].numel(), x.shape[-1], items, K,
+                                                      _lib.ptr(status), int(t_idx), int(iteration), _lib.stream_ptr()),
+                   "dh_ddim_cfg_step_locked")
         return out
 
     def _latent_update_guarded(self, x_new, x, d_sample, table, status, t_idx, iteration):
@@ -337,7 +361,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
     # ---- reference API ----------------------------------------------------------------------
     @torch.no_grad()
     def initial_inference(self, init_latents, depth, uncond_embeddings, prompt):
-        """Returns (activations [3 x [T,C,h,w]], latents [1,4,H,W], uncond_embeddings, init_latents)."""
+        """Returns (activations [3 x [T,C,h,w]], latents [1,4,H,W], uncond_embeddings, init_latents).  activations is a list
+        subclass (background_lock.Activations) whose .trajectory [T,4,H,W] f32 holds the latent after every DDIM step."""
         with self.on_stream():
             return self._initial_inference(init_latents, depth, uncond_embeddings, prompt)
 
@@ -357,6 +382,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         x = _nhwc(init_latents.to(self.device, torch.float32))
         T = len(timesteps)
         store = [torch.empty((T,) + shp, dtype=self.dtype, device=self.device) for shp in self.unet.act_shapes]
+        # the reconstruction trajectory (background lock): every step writes its latent into its slice, no extra launch
+        traj = torch.empty((T,) + tuple(x.shape[1:]), dtype=torch.float32, device=self.device)
         for t_idx, t in enumerate(timesteps):
             # the reference runs a cond-only B=1 pass for the activations and then the B=2 CFG pass (guided_stable_diffuser.py
             # :222-257: three samples per step); the conditional half of the CFG pass has exactly the inputs of the B=1 pass, so
@@ -365,8 +392,9 @@ class GuidedStableDiffuser(GuidedDiffuser):
             eu, ec, acts = self._cfg_eps(x, depth_nhwc, t, uncond_embeddings[t_idx], cond, want_acts=True)
             for k in range(3):
                 store[k][t_idx].copy_(acts[k][1])
-            x = self.ddim_step(x, eu, ec, t)
-        activations = [a.permute(0, 3, 1, 2) for a in store]      # [T,C,h,w] views of channels-last storage
+            x = self.ddim_step(x, eu, ec, t, out=traj[t_idx:t_idx + 1])
+        # [T,C,h,w] views of channels-last storage
+        activations = _bl.Activations([a.permute(0, 3, 1, 2) for a in store], trajectory=traj.permute(0, 3, 1, 2))
         return activations, x.permute(0, 3, 1, 2), uncond_embeddings, init_latents
 
     @torch.no_grad()
@@ -416,6 +444,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
         x = torch.cat([_nhwc(lat.to(self.device, torch.float32)) for lat in inits])
         store = [[torch.empty((T,) + shp, dtype=self.dtype, device=self.device) for shp in self.unet.act_shapes]
                  for _ in range(K)]
+        traj = torch.empty((T,) + tuple(x.shape), dtype=torch.float32, device=self.device)      # [T,K,s,s,4]: initial_inference's, per image
         for t_idx, t in enumerate(timesteps):
             # [uncond_1 .. uncond_K | cond_1 .. cond_K]: image b's conditional half is batch item K + b
             unc = torch.cat([u[t_idx].reshape(1, *cond.shape[1:]).to(self.device, torch.float32) for u in uncs])
@@ -425,9 +454,9 @@ class GuidedStableDiffuser(GuidedDiffuser):
             for b in range(K):
                 for k in range(3):
                     store[b][k][t_idx].copy_(acts[k][K + b])
-            x = self.ddim_step(x, eps[:K], eps[K:], t)
-        return [([a.permute(0, 3, 1, 2) for a in store[b]], x[b:b + 1].permute(0, 3, 1, 2), uncs[b], inits[b])
-                for b in range(K)]
+            x = self.ddim_step(x, eps[:K], eps[K:], t, out=traj[t_idx])
+        return [(_bl.Activations([a.permute(0, 3, 1, 2) for a in store[b]], trajectory=traj[:, b].permute(0, 3, 1, 2)),
+                 x[b:b + 1].permute(0, 3, 1, 2), uncs[b], inits[b]) for b in range(K)]
 
     def _check_object_weights(self, object_labels, object_weights, activations_orig):
         """Host checks of prepare_guidance's object weights, before any device work: labels present, default configuration."""
@@ -448,8 +477,12 @@ class GuidedStableDiffuser(GuidedDiffuser):
         _check_object_weights(object_weights, n)
 
     def prepare_guidance(self, depth, prompt, activations_orig, correspondences, fg_weight=None, bg_weight=None, orig=None,
-                         cond=None, object_labels=None, object_weights=None):
-        """Everything of guided_inference that is constant over the denoising loop.  `orig`: the channels-last copies of
+                         cond=None, object_labels=None, object_weights=None, lock=None):
+        """Everything of guided_inference that is constant over the denoising loop.  `lock` (background lock): (keep [s,s],
+        trajectory [T,4,s,s]) -- the keep map of this edit (background_lock.keep_map) and the reconstruction trajectory of its
+        image (activations.trajectory) -- or a prepared background_lock.Lock (edits of one image share the channels-last copy
+        of the trajectory, as they share `orig`); after every DDIM step the edit's latents are then blended with the
+        reconstruction's (DESIGN.md "Background lock").  `orig`: the channels-last copies of
         the original activations of another guidance state of the SAME image (K edits of one image share them); `cond`: the
         prompt embedding when the caller already has it (lanes: the text tower is not run concurrently with itself).
         object_labels / object_weights (multi-object edits): the label image of the object masks (losses.object_label_image)
@@ -495,7 +528,12 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 omega=st.plan.omega if weighted else None)
             st.scale_dev = torch.tensor(st.scale_host, dtype=torch.float32).to(self.device)[None].contiguous()
             st.status = torch.zeros((1, 4), dtype=torch.int32, device=self.device)
+        st.lock = self._locks(lock, 1, "prepare_guidance")[0]
         return st
+
+    def _locks(self, lock, K, what):
+        """`lock` of a loop call as K prepared background_lock.Lock / None (edits of one image share the trajectory's copy)."""
+        return _bl.prepare_locks(lock, K, self.device, self.unet.sample_size, int(self.conf.num_timesteps), what)
 
     def _energy_grad(self, st, k, act, t_idx, fgw, bgw, out=None, scale=None):
         """d(energy of layer k)/d(act) * scale (default grad_scale), act [h,w,C] channels-last; `out`: where to write it."""
@@ -559,7 +597,9 @@ class GuidedStableDiffuser(GuidedDiffuser):
         if images is not None:
             images.append(self.decode_latent_image(x.permute(0, 3, 1, 2)).cpu())
         eu, ec = self._cfg_eps(x, st.depth_nhwc, t, uncond, st.cond, inplace=self._inplace_io)      # (views: consumed by the step right here)
-        if st.auto:
+        if st.lock is not None:
+            x = self._ddim_step_locked([st], x, eu, ec, t, st.status if st.auto else None, t_idx, iteration)
+        elif st.auto:
             x = self._ddim_step_flagged(x, eu, ec, t, st.status, t_idx, iteration)
         else:
             x = self.ddim_step(x, eu, ec, t)
@@ -647,6 +687,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         sample2 = self.unet.stage_sample(x, depth, 2 * K)          # the K edits twice: unconditional and conditional halves
         text2 = torch.cat([unc, cond], dim=0).contiguous()
         eps, _ = self.unet.forward(sample2, float(t), text2, save_for_backward=False, want_acts=False, inplace=True)
+        if any(st.lock is not None for st in sts):
+            return self._ddim_step_locked(sts, x, eps[:K], eps[K:], t, status if auto else None, t_idx, iteration)
         if auto:
             return self._ddim_step_flagged(x, eps[:K], eps[K:], t, status, t_idx, iteration)
         return self.ddim_step(x, eps[:K], eps[K:], t)
@@ -674,16 +716,18 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def _batch_edit_steps(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                           fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None,
-                          object_weights=None):
+                          object_weights=None, lock=None):
         """The batched edit as a generator: yields after the preparation and after every denoising step (everything is only
         ENQUEUED on the current stream by then), returns the final latents [K,4,H,W] through StopIteration.  One body for the
         one-stream call below and for the lanes of guided_inference_batch_lanes.  fg_weight / bg_weight: one value, or one per
         edit.  status_out: a list that receives the device [K, 4] status ('auto') at the end.  object_labels / object_weights: one
-        label image and one weight list for all K edits (prepare_guidance)."""
+        label image and one weight list for all K edits (prepare_guidance).  lock: one (keep, trajectory) for all K edits or a list
+        of K (prepare_guidance; None entries are unlocked edits)."""
         K = len(depths)
         per = lambda w, i: w[i] if isinstance(w, (list, tuple)) else w
         if self.unet.max_batch < 2 * K:
             raise RuntimeError(f"engine max_batch {self.unet.max_batch} < 2*K = {2 * K}")
+        locks = self._locks(lock, K, "guided_inference_batch")
         torch.manual_seed(self.conf.seed)
         self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
         timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
@@ -691,7 +735,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
         for i, (d, c) in enumerate(zip(depths, correspondences_list)):
             sts.append(self.prepare_guidance(d, prompt, activations_orig, c, per(fg_weight, i), per(bg_weight, i),
                                              orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond,
-                                             object_labels=object_labels, object_weights=object_weights))
+                                             object_labels=object_labels, object_weights=object_weights, lock=locks[i]))
         x = _nhwc(latents.to(self.device, torch.float32)).expand(K, -1, -1, -1).contiguous()
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -702,16 +746,17 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_batch(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
-                               fg_weight=None, bg_weight=None, object_labels=None, object_weights=None):
+                               fg_weight=None, bg_weight=None, object_labels=None, object_weights=None, lock=None):
         """K edits of one image at once.  depths: list of K edited disparities [1,1,H,W]; correspondences_list:
         K [N_k,4] tensors; fg_weight / bg_weight: one value or K.  Needs an engine built with max_batch >= 2K.  Returns images
         [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value.  object_labels / object_weights: one
-        label image and one weight list for all K edits (prepare_guidance)."""
+        label image and one weight list for all K edits (prepare_guidance).  lock: the background lock, one (keep, trajectory)
+        for all K edits or a list of K (prepare_guidance)."""
         status = []
         with torch.no_grad(), self.on_stream():
             gen = self._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                          fg_weight, bg_weight, status_out=status, object_labels=object_labels,
-                                         object_weights=object_weights)
+                                         object_weights=object_weights, lock=lock)
             try:
                 while True:
                     next(gen)
@@ -727,7 +772,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
     def guided_inference_items(self, items, fg_weight=None, bg_weight=None):
         """K edits of DIFFERENT images at once.  items: K records (dicts with the keys ITEM_FIELDS, or tuples in that order), the
         arguments of guided_inference per item, plus optional object_labels / object_weights (prepare_guidance: a multi-object
-        edit with a weight per object); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
+        edit with a weight per object) and an optional lock ((keep, trajectory), prepare_guidance: locked and unlocked items may
+        share a batch); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
         tensors share one channels-last copy of them, items with the same prompt one encoding.  One resolution (the
         engine's); needs max_batch >= 2K and max_diff_batch >= K, raises otherwise (never splits).  Returns images [K,3,H,W]
         in item order and sets last_latents; 'auto' grad_scale: FloatingPointError naming the items that met a non-finite
@@ -753,11 +799,13 @@ class GuidedStableDiffuser(GuidedDiffuser):
             self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
             timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
             sts, origs, conds = [], {}, {}
+            locks = self._locks([it.get("lock") for it in items], K, "guided_inference_items")
             for i, it in enumerate(items):
                 okey = tuple(id(a) for a in it["activations_orig"])
                 st = self.prepare_guidance(it["depth"], it["prompt"], it["activations_orig"], it["correspondences"],
                                            per(fg_weight, i), per(bg_weight, i), orig=origs.get(okey), cond=conds.get(it["prompt"]),
-                                           object_labels=it.get("object_labels"), object_weights=it.get("object_weights"))
+                                           object_labels=it.get("object_labels"), object_weights=it.get("object_weights"),
+                                           lock=locks[i])
                 origs[okey], conds[it["prompt"]] = st.orig, st.cond
                 sts.append(st)
             x = torch.cat([_nhwc(it["latents"].to(self.device, torch.float32)) for it in items]).contiguous()
@@ -862,12 +910,13 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return results
 
     def guided_inference_batch_lanes(self, latents, chunks, uncond_embeddings, prompt, activations_orig, streams=2,
-                                     fg_weight=None, bg_weight=None, object_labels=None, object_weights=None):
+                                     fg_weight=None, bg_weight=None, object_labels=None, object_weights=None, lock=None):
         """Batched edits of one image on `streams` concurrent lanes.  chunks: list of (depths, correspondences_list), each the
         argument pair of one guided_inference_batch call; chunk i runs on lane i % streams.  Every lane executes exactly the
         passes the one-stream call executes for its chunk (same batch, same kernels, private arenas), so the images are
         bit-identical to guided_inference_batch chunk by chunk.  Returns one image tensor [K_i,3,H,W] per chunk.
-        object_labels / object_weights: one label image and one weight list for every edit (prepare_guidance)."""
+        object_labels / object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one
+        (keep, trajectory) for every edit, or a list with one entry per edit over the chunks in order."""
         kmax = max(len(d) for d, _ in chunks)
         if self.unet.max_batch < 2 * kmax:
             # lane 0 is THIS diffuser: it could not run its chunk, and forks sized 2 * kmax would be made for nothing
@@ -877,33 +926,36 @@ class GuidedStableDiffuser(GuidedDiffuser):
         with torch.no_grad(), self.on_stream():
             cond = self._encode([prompt]).contiguous()
             orig = [a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in activations_orig]
+            # (prepared here, on this stream, which every lane waits for: the lanes share the copies)
+            offs = np.cumsum([0] + [len(d) for d, _ in chunks])
+            locks = self._locks(lock, int(offs[-1]), "guided_inference_batch_lanes")
 
-            def make(depths, corrs, status):
+            def make(depths, corrs, status, lk):
                 def job(lane):
                     def body():
                         lat = yield from lane._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig,
                                                                 corrs, fg_weight, bg_weight, cond=cond, orig=orig,
                                                                 status_out=status, object_labels=object_labels,
-                                                                object_weights=object_weights)
+                                                                object_weights=object_weights, lock=lk)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
-            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s) for (d, c), s in zip(chunks, statuses)])
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, locks[int(offs[i]):int(offs[i + 1])])
+                                                            for i, ((d, c), s) in enumerate(zip(chunks, statuses))])
             if any(statuses):      # edits numbered over the chunks in order; read after every lane has finished
-                offs = np.cumsum([0] + [len(d) for d, _ in chunks])
                 self.raise_on_status([(int(offs[i]) + b, row) for i, s in enumerate(statuses)
                                       for b, row in enumerate(s[0].cpu().tolist())])
         return images
 
     def _edit_steps(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences, fg_weight=None,
-                    bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None, object_weights=None):
+                    bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None, object_weights=None, lock=None):
         """One edit as a generator (see _batch_edit_steps): yields after the preparation and after every denoising step,
-        returns the final latents [1,4,H,W]."""
+        returns the final latents [1,4,H,W].  lock: the edit's background lock (prepare_guidance)."""
         torch.manual_seed(self.conf.seed)
         self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
         timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
         st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight, orig=orig, cond=cond,
-                                   object_labels=object_labels, object_weights=object_weights)
+                                   object_labels=object_labels, object_weights=object_weights, lock=lock)
         x = _nhwc(latents.to(self.device, torch.float32))
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -914,41 +966,45 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_lanes(self, latents, edits, uncond_embeddings, prompt, activations_orig, streams=2, fg_weight=None,
-                               bg_weight=None, object_labels=None, object_weights=None):
+                               bg_weight=None, object_labels=None, object_weights=None, lock=None):
         """Single (B = 1) edits of one image on `streams` concurrent lanes.  edits: list of (depth, correspondences), the
         argument pair of guided_inference; edit i runs on lane i % streams with exactly the passes guided_inference runs, so
         the images are bit-identical to the one-stream calls.  Returns a list of images [1,3,H,W].  object_labels /
-        object_weights: one label image and one weight list for every edit (prepare_guidance)."""
+        object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one (keep, trajectory)
+        for every edit, or a list with one entry per edit."""
         lanes = self.lanes(min(int(streams), len(edits)))
         statuses = [[] for _ in edits]
         with torch.no_grad(), self.on_stream():
             cond = self._encode([prompt]).contiguous()
             orig = [a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in activations_orig]
+            locks = self._locks(lock, len(edits), "guided_inference_lanes")      # (on this stream, which every lane waits for)
 
-            def make(depth, corr, status):
+            def make(depth, corr, status, lk):
                 def job(lane):
                     def body():
                         lat = yield from lane._edit_steps(latents, depth, uncond_embeddings, prompt, activations_orig, corr,
                                                           fg_weight, bg_weight, cond=cond, orig=orig, status_out=status,
-                                                          object_labels=object_labels, object_weights=object_weights)
+                                                          object_labels=object_labels, object_weights=object_weights, lock=lk)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
-            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s) for (d, c), s in zip(edits, statuses)])
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, lk) for (d, c), s, lk in zip(edits, statuses, locks)])
             if any(statuses):      # read after every lane has finished
                 self.raise_on_status([(i, s[0][0].cpu().tolist()) for i, s in enumerate(statuses)])
         return images
 
     def guided_inference(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences,
                          fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None, object_labels=None,
-                         object_weights=None):
-        """object_labels / object_weights: a weight per object for the foreground term (prepare_guidance)."""
+                         object_weights=None, lock=None):
+        """object_labels / object_weights: a weight per object for the foreground term (prepare_guidance).  lock: (keep,
+        trajectory), the background lock -- after every DDIM step the latents are blended with the reconstruction's outside
+        the edit's region (prepare_guidance; DESIGN.md "Background lock")."""
         with torch.no_grad(), self.on_stream():
             torch.manual_seed(self.conf.seed)
             self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
             timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
             st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight,
-                                       object_labels=object_labels, object_weights=object_weights)
+                                       object_labels=object_labels, object_weights=object_weights, lock=lock)
             denoising_steps = {"opt": [], "post-opt": []} if save_denoising_steps else None
             x = _nhwc(latents.to(self.device, torch.float32))
             for t_idx, t in enumerate(timesteps):

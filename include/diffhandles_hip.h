@@ -168,6 +168,17 @@ int dh_cells_from_correspondences(const int64_t* corr, int n, int img_res, int g
                                   int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Keep map of the background lock: keep [s][s] f32, 0 inside the region an edit touches, 1 far from it, a ramp between.
+ * A latent cell (res / s pixels square) is a REGION cell if one of its pixels is non-zero in mask or release (u8 [res][res],
+ * either may be NULL), or if it holds the source pixel of a correspondence, or its target pixel when 0 <= tx, ty < res
+ * (corr [n][4] i64 (ox, oy, tx, ty), n may be 0).  d = Chebyshev distance in cells to the nearest region cell, searched
+ * within dilate + feather + 1 cells (the window is clipped by the border): keep = 0 for d <= dilate, else
+ * min(1, float(d - dilate) / float(feather + 1)) by one f32 division, 1 where the window holds no region cell (an empty
+ * region: all ones).  workspace: s * s bytes.  A memset and at most three launches, nothing returns to the host.
+ * DH_ERR_ARG before any launch, outputs untouched: dilate < 0, feather < 0, dilate + feather > 31, res % s != 0. */
+int dh_keep_map(const int64_t* corr, int n, const uint8_t* mask, const uint8_t* release, int res, int s, int dilate,
+                int feather, float* keep, void* workspace, size_t workspace_bytes, void* stream);
+
 /* --------------------------------------------------------------------------------------
  * depth_transform_mode = 'mesh' (depth_transform.py:91-195 + depth_to_mesh :30-71 + the pytorch3d
  * renderer outputs 'world_position' / 'flat_vertex_color'): per-pixel-quad triangulation of the
@@ -405,6 +416,20 @@ int dh_latent_update_guarded(float* x_out, const float* x, const float* g, int g
 /* dh_ddim_cfg_step, plus bit 1 of status[i / n_edit] where output element i is not finite (n_edit: elements per edit) */
 int dh_ddim_cfg_step_flagged(float* x_out, const float* x, const float* eps_u, const float* eps_c, float scale, float alpha_t,
                              float alpha_prev, int n, int n_edit, int* status, int t_idx, int iteration, void* stream);
+/* Background lock: dh_ddim_cfg_step for n / n_edit edits (at most 16; more is an error), each blended with its
+ * reconstruction outside the region its edit touches.  items[e] = {keep [n_edit / channels] f32 (one value per latent cell, from
+ * dh_keep_map), ref [n_edit] f32 (the reconstruction's latent after THIS step, channels-last)}; keep == NULL: edit e is not
+ * locked.  With o = dh_ddim_cfg_step's value: x_out = o where keep == 0 and for an unlocked edit (bit-identical to
+ * dh_ddim_cfg_step), x_out = ref where keep == 1, x_out = o + keep (ref - o) in between.  status may be NULL (static
+ * guidance scale); otherwise bit 1 of status[e] is set as dh_ddim_cfg_step_flagged sets it, judged on o BEFORE the blend (a
+ * locked cell does not hide a step that went bad).  One launch; the table travels by value in the kernel arguments. */
+typedef struct dh_lock_item {
+  const float* keep;          /* NULL: not locked */
+  const float* ref;
+} dh_lock_item;
+int dh_ddim_cfg_step_locked(float* x_out, const float* x, const float* eps_u, const float* eps_c, float scale, float alpha_t,
+                            float alpha_prev, int n, int n_edit, int channels, const dh_lock_item* items, int n_items,
+                            int* status, int t_idx, int iteration, void* stream);
 /* dst[b][p][:] = concat(latent[b or 0][p][0:latent_channels], depth[b or 0][p][0:depth_channels]) for b < batch: the U-Net
  * input `torch.cat([latents (x batch), depth (x batch)], dim=1)` (guided_stable_diffuser.py:400-401, 451-455) in one launch.
  * latent_batch / depth_batch divide batch: item b reads latent[b mod latent_batch] (1 = broadcast, batch = one each, K of 2K =

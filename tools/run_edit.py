@@ -15,6 +15,11 @@ scene directory, writing PNGs and the .npz identity cache with the reference's k
                                                                  #   {name: {"objects": [M such entries], "object_weights":
                                                                  #   "equal" | [M floats]}} (scene_io.load_scene_geometry; pc mode)
   python tools/run_edit.py --scene tests/golden/scene_banana_fruits --out /tmp/edit   # a scene of the reference's test data
+  python tools/run_edit.py --scene DIR --out /tmp/edit --background-lock [--lock-dilate D] [--lock-feather F]
+                                                                 # hold the latents outside each edit's region to the
+                                                                 #   reconstruction (conf key background_lock): an optional
+                                                                 #   release.png in DIR sets extra area free, identity.npz
+                                                                 #   also keeps the key `trajectory`, <edit>_keep.png is written
 PNG / OpenEXR are read by diffusionhandles_amd.scene_io (no imaging library offline).
 Real weights: DIFFHANDLES_UNET_SAFETENSORS / DIFFHANDLES_VAE_SAFETENSORS / DIFFHANDLES_TEXT_ENCODER_DIR /
 DIFFHANDLES_TOKENIZER_DIR (otherwise seeded random U-Net weights and the synthetic side modules).
@@ -46,7 +51,7 @@ def load_config(path):
                 if kk not in conf.guided_diffuser and kk not in C.OPTIONAL_GUIDED_KEYS:
                     raise ValueError(f"{path}: unknown key guided_diffuser.{kk}")
                 conf.guided_diffuser[kk] = vv
-        elif k in conf:
+        elif k in conf or k in ("background_lock", "background_lock_dilate", "background_lock_feather"):
             conf[k] = v
         else:
             raise ValueError(f"{path}: unknown key {k}")
@@ -69,6 +74,26 @@ def apply_footprint_args(args, conf):
     fp, ratio = check_footprints(fp, ratio, "--footprints")
     args.footprint_report = dict(footprints=fp, footprint_max_ratio=ratio)
     return args.footprint_report
+
+
+def apply_lock_args(args, conf):
+    """--background-lock / --lock-dilate / --lock-feather -> the optional conf keys background_lock / background_lock_dilate /
+    background_lock_feather (DiffusionHandles reads them for --scene, --test-set and --edit-batch alike), checked as the
+    library checks them (ValueError) before any engine is built.  Sets args.background_lock (whether the lock is on, by the
+    arguments or by the configuration file) and returns what the report carries."""
+    from diffusionhandles_amd.background_lock import lock_conf
+    if args.background_lock:
+        conf["background_lock"] = True
+    if args.lock_dilate is not None:
+        conf["background_lock_dilate"] = args.lock_dilate
+    if args.lock_feather is not None:
+        conf["background_lock_feather"] = args.lock_feather
+    reach = lock_conf(conf, "--background-lock")
+    args.background_lock = reach is not None
+    # (nothing with the lock off: the reports of unlocked runs stay what they were)
+    args.lock_report = {} if reach is None else \
+        dict(background_lock=True, background_lock_dilate=reach[0], background_lock_feather=reach[1])
+    return args.lock_report
 
 
 def parse(argv=None):
@@ -110,6 +135,14 @@ def parse(argv=None):
     ap.add_argument("--footprint-max-ratio", type=float, default=None, metavar="R",
                     help="with --footprints: leave out triangles whose source depths differ by more than the factor R > 1 "
                          "(conf key depth_transform_footprint_max_ratio)")
+    ap.add_argument("--background-lock", action="store_true",
+                    help="hold every edit's latents to the reconstruction outside the region the edit touches (conf key "
+                         "background_lock); the identity cache then also keeps the reconstruction trajectory, a release.png in "
+                         "the scene directory sets extra area free, and every edit also writes <name>_keep.png")
+    ap.add_argument("--lock-dilate", type=int, default=None, metavar="D",
+                    help="with --background-lock: cells around the region that stay free (conf key background_lock_dilate, default 2)")
+    ap.add_argument("--lock-feather", type=int, default=None, metavar="F",
+                    help="with --background-lock: cells of the ramp from free to locked (conf key background_lock_feather, default 2)")
     args = ap.parse_args(argv)
     if args.edit_batch < 1 or (args.edit_batch > 1 and args.test_set is None):
         ap.error("--edit-batch K needs K >= 1, and K > 1 needs --test-set")
@@ -125,7 +158,8 @@ def main():
         conf.depth_transform_mode = args.mode
     args.mode = conf.depth_transform_mode
     apply_footprint_args(args, conf)
-    state = {"dh": None}            # the engine is built on first use: a run that skips every scene never touches the GPU
+    apply_lock_args(args, conf)
+    state = {"dh": None}           # the engine is built on first use: a run that skips every scene never touches the GPU
 
     def handles(res):
         from diffusionhandles_amd import DiffusionHandles
@@ -189,7 +223,7 @@ def main():
                 f"{len(reports)} scenes</h3><table border='1' cellspacing='0' cellpadding='4'><tr><th>scene</th><th>edits</th>"
                 f"<th>identity s</th></tr>{rows}</table></body></html>")
     total = dict(test_set=set_name, scenes=reports, config=args.config, depth_transform_mode=conf.depth_transform_mode,
-                 **args.footprint_report,
+                 **args.footprint_report, **args.lock_report,
                  edits_run=sum(1 for r in reports for e in r["edits"] if not e.get("skipped")),
                  edits_skipped=sum(1 for r in reports for e in r["edits"] if e.get("skipped")))
     if batch_seconds is not None:
@@ -203,7 +237,18 @@ def needs_identity(args, scene, out, transform_names):
     p = prepare_scene(args, scene, out, transform_names, warn=False)
     if args.skip_existing and p["transforms"] and all(p["exists"].values()):
         return False
-    return args.no_identity_cache or not os.path.exists(os.path.join(out, "identity.npz"))
+    return args.no_identity_cache or not cache_usable(args, os.path.join(out, "identity.npz"))
+
+
+def cache_usable(args, cache):
+    """Whether the identity cache file exists and serves this run: with --background-lock it must hold the reconstruction
+    trajectory (a cache written without the lock is recomputed, never used unlocked)."""
+    if not os.path.exists(cache):
+        return False
+    if not getattr(args, "background_lock", False):
+        return True
+    with np.load(cache) as z:
+        return "trajectory" in z.files
 
 
 def identity_chunk(args, handles, scenes):
@@ -232,6 +277,11 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
     from diffusionhandles_amd.scene_io import load_scene, object_transform_args, transform_args
     from diffusionhandles_amd.synthetic import TRANSFORMS, make_image, make_scene
     masks = None                    # a multi-object scene (mask_0.png ...): the list of its masks; `mask` is then their union
+    release = None                  # --background-lock: the scene's optional release.png, [res,res] in {0,1}, read like a mask
+    if scene and getattr(args, "background_lock", False) and os.path.exists(os.path.join(scene, "release.png")):
+        from diffusionhandles_amd.scene_io import crop_and_resize, load_image
+        release = load_image(os.path.join(scene, "release.png"))[None]
+        release = (crop_and_resize(release.mean(dim=1, keepdim=True), args.res) > 0.5).to(torch.float32)[0, 0]
     if scene:
         sc = load_scene(scene, args.res)
         img, depth, bg_depth, mask, prompt, res = sc["img"], sc["depth"], sc["bg_depth"], sc["fg_mask"], sc["prompt"], args.res
@@ -268,7 +318,7 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
                                           "scale, use --mode pc")
     exists = {tf["name"]: os.path.exists(os.path.join(out, tf["name"] + ".png")) for tf in transforms}
     return dict(img=img, depth=depth, bg_depth=bg_depth, mask=mask, masks=masks, prompt=prompt, res=res, transforms=transforms,
-                exists=exists)
+                exists=exists, release=release)
 
 
 def scene_identity(args, dh, p, out, identity=None):
@@ -280,7 +330,9 @@ def scene_identity(args, dh, p, out, identity=None):
     depth, bg_depth, mask, img = depth.to(dev), bg_depth.to(dev), mask.to(dev), img.to(dev)
     t0 = time.time()
     cache = None if args.no_identity_cache else (args.identity_cache or os.path.join(out, "identity.npz"))
-    identity_from_cache = identity is None and cache is not None and os.path.exists(cache)
+    lock = getattr(args, "background_lock", False)
+    # (--background-lock: a cache without the reconstruction trajectory is recomputed and rewritten, never used unlocked)
+    identity_from_cache = identity is None and cache is not None and cache_usable(args, cache)
     chunk_s = 0.0
     if identity is not None:
         null_text, noise, acts, latent, chunk_s = identity
@@ -292,6 +344,9 @@ def scene_identity(args, dh, p, out, identity=None):
             noise = torch.from_numpy(z["init_noise"]).to(dev)
             acts = [torch.from_numpy(z[f"activations{i + 1}"]).to(dev) for i in range(3)]
             latent = torch.from_numpy(z["latent_image"]).to(dev)
+            if lock:
+                from diffusionhandles_amd.background_lock import Activations
+                acts = Activations(acts, trajectory=torch.from_numpy(z["trajectory"]).to(dev))
     else:
         if identity is None:
             null_text, noise = (None, None)
@@ -300,10 +355,12 @@ def scene_identity(args, dh, p, out, identity=None):
             null_text, noise, acts, latent = dh.generate_input_image(depth, prompt, null_text, noise)
         if cache is not None:
             os.makedirs(os.path.dirname(os.path.abspath(cache)), exist_ok=True)
+            # (the key `trajectory` only with the lock on: an unlocked run writes the reference's keys and nothing else)
+            extra = dict(trajectory=acts.trajectory.float().cpu().numpy()) if lock else {}
             np.savez(cache, null_text_emb=null_text.float().cpu().numpy(),
                      init_noise=noise.float().cpu().numpy(), activations1=acts[0].float().cpu().numpy(),
                      activations2=acts[1].float().cpu().numpy(), activations3=acts[2].float().cpu().numpy(),
-                     latent_image=latent.float().cpu().numpy())
+                     latent_image=latent.float().cpu().numpy(), **extra)
     if p.get("masks") is not None:          # several objects: the blend runs over the union of the list
         p["masks_dev"] = [m.to(dev) for m in p["masks"]]
         bg_depth = dh.set_foreground(depth, p["masks_dev"], bg_depth)
@@ -314,7 +371,7 @@ def scene_identity(args, dh, p, out, identity=None):
     recon = dh.diffuser.decode_latent_image(latent)
     write_png(os.path.join(out, "recon.png"), recon[0].permute(1, 2, 0).float().cpu().numpy())
     report = dict(resolution=res, mode=args.mode, identity_s=round(t_identity, 2), identity_from_cache=bool(identity_from_cache),
-                  edits=[], **getattr(args, "footprint_report", {}))
+                  edits=[], **getattr(args, "footprint_report", {}), **getattr(args, "lock_report", {}))
     if args.identity_batch > 1:
         report["identity_batch"] = args.identity_batch
     return depth, bg_depth, mask, img, null_text, noise, acts, report
@@ -392,18 +449,23 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
             r = resident[s]
             common = dict(depth=r["depth"], prompt=r["prompt"], bg_depth=r["bg_depth"], null_text_emb=r["null_text_emb"],
                           init_noise=r["init_noise"], activations=r["activations"])
+            if prep[s].get("release") is not None:          # (--background-lock: the scene's release.png)
+                common["release_mask"] = prep[s]["release"]
             if r["fg_masks"] is not None:
                 edits.append(dict(common, fg_masks=r["fg_masks"], transforms=tf["transforms"], object_weights=tf["object_weights"]))
             else:
                 edits.append(dict(common, fg_mask=r["fg_mask"], rot_angle=tf["rot_angle"], rot_axis=tf["rot_axis"],
                                   translation=tf["translation"], scale=tf.get("scale"), pivot=tf.get("pivot")))
         t0 = time.time()
-        images, disparities = handles(prep[scenes[0]]["res"]).transform_foregrounds(edits)
+        dh = handles(prep[scenes[0]]["res"])
+        images, disparities = dh.transform_foregrounds(edits)
         torch.cuda.synchronize()
         dt = time.time() - t0
         seconds.append(round(dt, 3))
-        for (s, name), image, disparity in zip(batch, images, disparities):
+        for i, ((s, name), image, disparity) in enumerate(zip(batch, images, disparities)):
             out = os.path.join(args.out, s)
+            if getattr(args, "background_lock", False):
+                write_png(os.path.join(out, f"{name}_keep.png"), dh.last_keep_maps[i].float().cpu().numpy())
             write_png(os.path.join(out, f"{name}.png"), image.permute(1, 2, 0).float().cpu().numpy())
             write_png(os.path.join(out, f"{name}_disparity.png"), (disparity[0, 0] / disparity.max()).float().cpu().numpy())
             reports[s]["edits"].append(dict(name=name, seconds=round(dt / len(batch), 3), batch=bi))
@@ -439,8 +501,18 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
             continue
         t0 = time.time()
         if p.get("masks_dev") is not None:
+            rel = {} if p.get("release") is None else dict(release_mask=p["release"])
             res_ = dh.transform_foreground_objects(depth, prompt, p["masks_dev"], bg_depth, null_text, noise, acts,
-                                                   transforms=tf["transforms"], object_weights=tf["object_weights"])
+                                                   transforms=tf["transforms"], object_weights=tf["object_weights"], **rel)
+        elif p.get("release") is not None:
+            # (transform_foreground keeps the reference's parameter list: a release mask goes through the one-mask form of
+            #  transform_foreground_objects, the same edit in 'pc' mode)
+            if args.mode != "pc":
+                raise NotImplementedError(f"{scene}: release.png needs --mode pc (the mesh mode's transform_foreground takes no "
+                                          "release mask)")
+            tf5 = (tf["rot_angle"], tf["rot_axis"], tf["translation"], tf.get("scale"), tf.get("pivot"))
+            res_ = dh.transform_foreground_objects(depth, prompt, [mask], bg_depth, null_text, noise, acts, transforms=[tf5],
+                                                   release_mask=p["release"])
         else:
             res_ = dh.transform_foreground(depth, prompt, mask, bg_depth, null_text, noise, acts, rot_angle=tf["rot_angle"],
                                           rot_axis=tf["rot_axis"], translation=tf["translation"], scale=tf.get("scale"),
@@ -451,6 +523,8 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
         name = tf["name"]
         write_png(os.path.join(out, f"{name}.png"), edited[0].permute(1, 2, 0).float().cpu().numpy())
         write_png(os.path.join(out, f"{name}_disparity.png"), (disparity[0, 0] / disparity.max()).float().cpu().numpy())
+        if getattr(args, "background_lock", False):
+            write_png(os.path.join(out, f"{name}_keep.png"), dh.last_keep_maps[0].float().cpu().numpy())
         report["edits"].append(dict(name=name, seconds=round(dt, 3)))
     write_scene_pages(args, out, img, mask, depth, bg_depth, prompt, res, report)
     return report

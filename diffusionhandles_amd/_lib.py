@@ -57,11 +57,21 @@ class GemmPlanQuery(ctypes.Structure):
                 ("glub_f", ctypes.c_int32), ("xa_Nq", ctypes.c_int32), ("xa_Nk", ctypes.c_int32), ("xa_H", ctypes.c_int32)]
 
 
+class AttnPlanQuery(ctypes.Structure):
+    """dh_attn_plan_query: one attention launch described without pointers (dh_dbg_attn_plan)"""
+    _fields_ = [("kind", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("Nq", ctypes.c_int32), ("Nk", ctypes.c_int32),
+                ("causal", ctypes.c_int32), ("scratch_elems", ctypes.c_uint64), ("force_ks", ctypes.c_int32), ("force_qw", ctypes.c_int32),
+                ("force_dkv_ks", ctypes.c_int32), ("force_dkv_qw", ctypes.c_int32), ("cus", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/diffhandles_hip.h one to one
 SIGNATURES = {
     "dh_last_error": (ctypes.c_char_p, []),
     # host-only query of the GEMM dispatch (declared in the header; tests/test_gemm_plan.py)
     "dh_dbg_gemm_plan": (c_i, [ctypes.POINTER(GemmPlanQuery), ctypes.POINTER(ctypes.c_int32), c_i]),
+    # host-only query of the attention dispatch, and what the last launch of a kind passed (tests/test_attn_plan.py)
+    "dh_dbg_attn_plan": (c_i, [ctypes.POINTER(AttnPlanQuery), ctypes.POINTER(ctypes.c_int32), c_i]),
+    "dh_dbg_attn_last_launch": (c_i, [c_i, ctypes.POINTER(ctypes.c_int32), c_i]),
     "dh_version": (c_i, []),
     "dh_device_count": (c_i, []),
     "dh_reproject_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),

@@ -14,6 +14,9 @@
 // 16-byte store and every tile exists once.
 // The backward kernels use the same two product shapes (one with the roles of keys and
 // queries exchanged).  dQ and dK/dV are separate kernels (no atomics, deterministic).
+#include <stdlib.h>
+#include <string.h>
+#include <utility>
 #include "attn_tile.h"
 
 namespace dh {
@@ -875,28 +878,28 @@ __global__ void k_attn_dkv_reduce(const float* qpart, int qchunks, int rows_pad,
   *reinterpret_cast<uint2*>(out) = *reinterpret_cast<uint2*>(o);
 }
 
-// ---- launch shapes ------------------------------------------------------------------------------------------
+// ---- launch plan ("Attention plan") ----------------------------------------------------------------------
 // KS: key-range (query-range for dK/dV) split over wave groups inside a block (measured on MI355X, fp16, B=1 H=5
 //     N=4096: fwd 97 -> 57 us at KS=4, dq+dkv 244 -> 160 us at KS=2; still ahead at 9216 keys and B=2, so the choice
 //     depends on the loop length only)
 // QW: waves of 32 rows per wave group, i.e. the block owns 32*QW rows.  One image has only N/32 * H row-waves
 //     (640 at N=4096, H=5): the row tile is chosen so that the blocks cover the 256 CUs as evenly as possible
 //     (128-row tiles = 160 blocks leave 96 CUs idle, 96-row tiles = 215 blocks).
-static int attn_key_split(int tiles, int max_ks) {
+#ifndef DH_DKV_DB
+#define DH_DKV_DB 1       // 0: the register-staged tiles (same-box A/B builds, tools/lab.sh build-tuning with DH_DEFS=-DDH_DKV_DB=0)
+#endif
+
+// step: key split (`force`: AttnHooks::ks)
+static int attn_key_split(int tiles, int max_ks, int force) {
   // (two groups from 4 tiles on -- the 16x16-latent self-attention, 256 keys: forward + backward 30.6 -> 21.7 us, guided step
   //  +0.5 %, profiles/r03_ab_attn_ks_short.txt; four groups from 4 or 8 tiles, two from 2: no further gain)
   int ks = tiles >= 16 ? 4 : tiles >= 4 ? 2 : 1;
-#ifdef DH_TUNING
-  static const int force = getenv("DH_ATTN_KS") ? atoi(getenv("DH_ATTN_KS")) : 0;
   if (force == 1 || force == 2 || force == 4) ks = force;
-#endif
   return ks < max_ks ? ks : max_ks;
 }
-static int attn_row_waves(int rows, int hb, int loop_rows) {
-#ifdef DH_TUNING
-  static const int force = getenv("DH_ATTN_QW") ? atoi(getenv("DH_ATTN_QW")) : 0;
+// step: row waves (`force`: AttnHooks::qw)
+static int attn_row_waves(int rows, int hb, int loop_rows, int force, int cus) {
   if (force >= 1 && force <= 4) return force;
-#endif
   const int min_qw = loop_rows > 1024 ? 2 : 1;        // a 32-row block would stream the whole K/V per 32 rows
   // grids that fill the chip twice over with 128-row blocks (batched edits): the big block, whatever the rounding of the last
   // round -- it streams K / V once per 128 rows instead of once per 64 (batch 8, N = 1024, H = 10: forward 52.9 -> 42.8 us with
@@ -906,89 +909,149 @@ static int attn_row_waves(int rows, int hb, int loop_rows) {
   long best_cost = -1;
   for (int qw = 4; qw >= min_qw; --qw) {
     const long blocks = (long)cdiv(rows, 32 * qw) * hb;
-    const long cost = ((blocks + 255) / 256) * qw;    // rounds over the CUs x work per block
+    const long cost = ((blocks + cus - 1) / cus) * qw;    // rounds over the CUs x work per block
     if (best_cost < 0 || cost < best_cost) { best = qw; best_cost = cost; }
   }
   return best;
 }
+// step: the forward / dQ double buffer.  Key-split blocks of grids that fit the chip once or twice: LDS-DMA double buffer
+// (the 16-wave block has no registers to spare for the second fetch)
+static int attn_double_buffer(int ks, int qw, long workgroups) { return ks >= 2 && ks * qw < 16 && workgroups <= 512; }
+// step: dK/dV's few-key query chunks; returns qchunks, may set qw and re-split ks
+static int attn_dkv_query_chunks(const AttnQuery& q, const AttnHooks& h, int& ks, int& qw) {
+  // cross-attention shape (77 keys, thousands of queries): the key blocks alone are H*B workgroups; split the queries
+  // over workgroups too and sum f32 partials.  (All keys in ONE block for that: the even-coverage rule above would pick two
+  // 64-key blocks for 77 keys and leave 10 workgroups streaming 4096 queries each -- 72 us per layer in the null-text
+  // backward, profiles/r03_invert_kernel_types.txt.)
+  if (q.scratch_elems == 0 || q.Nq < 512) return 1;
+  if (q.Nk <= 128) qw = cdiv(q.Nk, 32);
+  if (q.Nk > 32 * qw) return 1;
+  const int tiles_all = (q.Nq + 63) / 64;
+  int qchunks = h.cus / (q.H * q.B);
+  if (qchunks > tiles_all / 2) qchunks = tiles_all / 2;
+  while (qchunks > 1 && (size_t)qchunks * q.B * q.H * 2 * 32 * qw * 64 > q.scratch_elems) --qchunks;
+  if (qchunks <= 1) return 1;
+  ks = attn_key_split(cdiv(tiles_all, qchunks), 2, h.ks);
+  return qchunks;
+}
 
-template <class T, int KS, int QW>
-static void attn_fwd_launch(int B, hipStream_t st, const void* q, long ldq, const void* k, const void* v, long ldk, void* o,
-                            long ldo, float* lse, int H, int Nq, int Nk, int causal) {
-  const dim3 grid(cdiv(Nq, 32 * QW), H, B);
-  if constexpr (KS >= 2 && KS * QW < 16) {      // (the 16-wave block has no registers to spare for the second fetch)
-    if ((long)grid.x * grid.y * grid.z <= 512) {
-      hipLaunchKernelGGL((k_attn_fwd<T, KS, QW, true>), grid, dim3(64 * QW * KS), 0, st, (const T*)q, ldq, (const T*)k, (const T*)v,
-                         ldk, (T*)o, ldo, lse, H, Nq, Nk, causal);
-      return;
+AttnPlan attn_plan(const AttnQuery& q, const AttnHooks& h) {
+  AttnPlan p = {};
+  if (q.B <= 0 || q.H <= 0 || q.Nq <= 0 || q.Nk <= 0) return p;      // (the tile fetch clamps rows to rows_total - 1: never with zero rows)
+  const int hb = q.H * q.B;
+  p.launch = 1;
+  p.qchunks = 1;
+  if (q.kind == ATTN_DKV) {           // blocks own keys, the loop runs over the queries
+    p.ks = attn_key_split((q.Nq + 63) / 64, 2, h.ks);
+    p.qw = attn_row_waves(q.Nk, hb, q.Nq, h.qw, h.cus);
+    if (h.dkv_qw >= 1 && h.dkv_qw <= 4 && q.Nk > 128) p.qw = h.dkv_qw;
+    if ((h.dkv_ks == 1 || h.dkv_ks == 2) && q.Nk > 128) p.ks = h.dkv_ks;
+    p.qchunks = attn_dkv_query_chunks(q, h, p.ks, p.qw);
+    p.reduce = p.qchunks > 1;
+    if (p.reduce) p.scratch_used = p.qchunks * hb * 2 * 32 * p.qw * 64;
+    // (the kernel's registers hold it to one workgroup per CU whatever the LDS: the double-buffered form serves every grid)
+    p.db = DH_DKV_DB != 0;
+    p.grid_x = p.reduce ? p.qchunks : cdiv(q.Nk, 32 * p.qw);
+  } else {
+    p.qw = attn_row_waves(q.Nq, hb, q.Nk, h.qw, h.cus);
+    const int tiles = (q.Nk + 63) / 64;
+    if (q.kind == ATTN_FWD) {
+      // causal: no key split.  A wave group whose whole key range lies after a query row would carry m = -inf into the merge
+      // (exp2(-inf - -inf) = NaN); with one group the first tile always holds key 0, visible to every row
+      p.ks = attn_key_split(tiles, q.causal ? 1 : 4, h.ks);
+      // ... and on such grids a short key loop (< 64 tiles) is not split over wave groups: there are blocks enough, the merge only costs
+      if ((long)cdiv(q.Nq, 128) * hb >= 512 && tiles < 64) p.ks = 1;
+    } else {
+      // four key groups like the forward (12 waves per CU instead of 6 at N = 4096: the loop is VALU-bound and one to two waves
+      // per SIMD leave the pipe idle across every LDS wait; guided step +0.45 %, profiles/r03_ab_dq_ks4.txt); the 16-wave block
+      // of the 128-row tile would spill, it keeps two
+      p.ks = attn_key_split(tiles, 4, h.ks);
+      if (p.ks == 4 && p.qw == 4) p.ks = 2;
     }
+    p.grid_x = cdiv(q.Nq, 32 * p.qw);
+    p.db = attn_double_buffer(p.ks, p.qw, (long)p.grid_x * hb);
   }
-  hipLaunchKernelGGL((k_attn_fwd<T, KS, QW, false>), grid, dim3(64 * QW * KS), 0, st, (const T*)q, ldq, (const T*)k, (const T*)v,
-                     ldk, (T*)o, ldo, lse, H, Nq, Nk, causal);
+  p.grid_y = q.H;
+  p.grid_z = q.B;
+  p.block = 64 * p.qw * p.ks;
+  return p;
 }
-template <class T, int KS, int QW>
-static void attn_dq_launch(int B, hipStream_t st, const void* q, long ldq, const void* k, const void* v, long ldk,
-                           const void* o, long ldo, const void* d_o, long lddo, const float* lse, float* delta, void* dq,
-                           long lddq, int H, int Nq, int Nk) {
-  // (the 16-wave shape is never chosen, launch_attention_bwd_dq: at 128 registers per lane it would spill; not instantiated)
-  if constexpr (KS * QW < 16) {
-    const dim3 grid(cdiv(Nq, 32 * QW), H, B);
-    if constexpr (KS >= 2) {      // key-split blocks of grids that fit the chip once or twice: LDS-DMA double buffer (as the forward)
-      if ((long)grid.x * grid.y * grid.z <= 512) {
-        hipLaunchKernelGGL((k_attn_bwd_dq<T, KS, QW, true>), grid, dim3(64 * QW * KS), 0, st, (const T*)q, ldq, (const T*)k, (const T*)v,
-                           ldk, (const T*)o, ldo, (const T*)d_o, lddo, lse, delta, (T*)dq, lddq, H, Nq, Nk);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((k_attn_bwd_dq<T, KS, QW, false>), grid, dim3(64 * QW * KS), 0, st, (const T*)q, ldq,
-                       (const T*)k, (const T*)v, ldk, (const T*)o, ldo, (const T*)d_o, lddo, lse, delta, (T*)dq, lddq, H, Nq, Nk);
-  }
+
+// ---- tuning island: the knobs of a -DDH_TUNING build, read once when the library loads; DH_ATTN_LOG=1: every launch's query and plan
+#ifdef DH_TUNING
+static int attn_env(const char* knob) {       // the integer in DH_ATTN_<knob>, 0 when unset
+  const char* v = getenv((std::string("DH_ATTN_") + knob).c_str());
+  return v ? atoi(v) : 0;
 }
-#ifndef DH_DKV_DB
-#define DH_DKV_DB 1       // 0: the register-staged tiles (same-box A/B builds, tools/lab.sh build-tuning with DH_DEFS=-DDH_DKV_DB=0)
+static const AttnHooks g_attn_hooks = {attn_env("KS"), attn_env("QW"), attn_env("DKV_KS"), attn_env("DKV_QW")};
+static const int g_attn_log = attn_env("LOG");
+static void attn_log(const AttnQuery& q, const AttnPlan& p) {
+  if (!g_attn_log) return;
+  int v[ATTN_PLAN_FIELDS];
+  memcpy(v, &p, sizeof(v));
+  fprintf(stderr, "ATTNPLAN q %d %d %d %d %d %d %zu |", q.kind, q.B, q.H, q.Nq, q.Nk, q.causal, q.scratch_elems);
+  for (int i = 0; i < ATTN_PLAN_FIELDS; ++i) fprintf(stderr, " %d", v[i]);
+  fprintf(stderr, "\n");
+}
+#else
+static const AttnHooks g_attn_hooks = {};
+static inline void attn_log(const AttnQuery&, const AttnPlan&) {}
 #endif
-template <class T, int KS, int QW>
-static void attn_dkv_launch(int B, hipStream_t st, const void* q, long ldq, const void* k, const void* v, long ldk,
-                            const void* d_o, long lddo, const float* lse, const float* delta, void* dk, void* dv, long lddk,
-                            int H, int Nq, int Nk, float* qpart, int qchunks) {
-  // (the kernel's registers hold it to one workgroup per CU whatever the LDS: the double-buffered form serves every grid)
-  hipLaunchKernelGGL((k_attn_bwd_dkv<T, KS, QW, DH_DKV_DB != 0>), dim3(qchunks > 1 ? qchunks : cdiv(Nk, 32 * QW), H, B), dim3(64 * QW * KS), 0,
-                     st, (const T*)q, ldq, (const T*)k, (const T*)v, ldk, (const T*)d_o, lddo, lse, delta, (T*)dk, (T*)dv, lddk,
-                     H, Nq, Nk, qpart, qchunks);
-  if (qchunks > 1) {
-    const long total = (long)B * H * 2 * Nk * 16;
-    hipLaunchKernelGGL((k_attn_dkv_reduce<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, qpart, qchunks, 32 * QW,
-                       (T*)dk, (T*)dv, lddk, B, H, Nk);
-  }
-}
 
-// (ks, qw) -> instantiation
-#define DH_ATTN_QW(FN, T_, KS_, ...)                                   \
-  do {                                                                  \
-    if (qw == 4) FN<T_, KS_, 4>(__VA_ARGS__);                           \
-    else if (qw == 3) FN<T_, KS_, 3>(__VA_ARGS__);                      \
-    else if (qw == 2) FN<T_, KS_, 2>(__VA_ARGS__);                      \
-    else FN<T_, KS_, 1>(__VA_ARGS__);                                   \
-  } while (0)
+// ---- launch: one switch for the three kernels ---------------------------------------------------------------------------------------
+// what the last launch of each kind on this thread passed to hipLaunchKernelGGL, written from the launcher's own template arguments
+// (dh_dbg_attn_last_launch: a wrong arm of the switch shows as launched != planned)
+struct AttnLaunched { int ks, qw, db, grid_x, grid_y, grid_z, block, qchunks, reduce; };
+static thread_local AttnLaunched g_attn_last[3];
+
+// a kernel family: its record slot and has(KS, QW, DB) = the instantiations that exist
+struct AttnFwd { static constexpr int kind = ATTN_FWD; static constexpr bool has(int KS, int QW, bool DB) { return !DB || (KS >= 2 && KS * QW < 16); } };
+// (dQ's 16-wave shape: at 128 registers per lane it would spill; not instantiated, attn_plan never names it)
+struct AttnDq { static constexpr int kind = ATTN_DQ; static constexpr bool has(int KS, int QW, bool DB) { return KS * QW < 16 && (!DB || KS >= 2); } };
+struct AttnDkv { static constexpr int kind = ATTN_DKV; static constexpr bool has(int KS, int QW, bool DB) { return KS <= 2 && DB == (DH_DKV_DB != 0); } };
+template <class T_, int KS_, int QW_, bool DB_> struct AttnVariant { using T = T_; static constexpr int KS = KS_, QW = QW_; static constexpr bool DB = DB_; };
+// arm I of the switch: (KS, QW, DB) = (1 << I / 8, I / 2 % 4 + 1, I & 1), compiled only where family K has the instantiation.
+// go(variant, grid, block) launches the kernel of the variant's template arguments; grid and block are the plan's
+template <class K, class T, int I, class F>
+static bool attn_launch_arm(const AttnPlan& p, F& go) {
+  constexpr int KS = 1 << (I / 8), QW = I / 2 % 4 + 1;
+  constexpr bool DB = I & 1;
+  if constexpr (K::has(KS, QW, DB)) {
+    if (p.ks == KS && p.qw == QW && (p.db != 0) == DB) {
+      const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.block);
+      const int reduced = go(AttnVariant<T, KS, QW, DB>{}, grid, block);
+      g_attn_last[K::kind] = {KS, QW, DB, (int)grid.x, (int)grid.y, (int)grid.z, (int)block.x, p.qchunks, reduced};
+      return true;
+    }
+  }
+  return false;
+}
+template <class K, class T, class F, int... I>
+static bool attn_launch_arms(const AttnPlan& p, F& go, std::integer_sequence<int, I...>) { return (attn_launch_arm<K, T, I>(p, go) || ...); }
+// launch from the plan, or abort: a plan that names a combination with no instantiation would run no kernel and leave the output stale
+template <class K, class F>
+static void attn_launch_planned(int dtype, const AttnPlan& p, F go) {
+  using Arms = std::make_integer_sequence<int, 24>;
+  if (dtype == DH_DTYPE_F16 ? attn_launch_arms<K, f16>(p, go, Arms{}) : attn_launch_arms<K, bf16>(p, go, Arms{})) return;
+  fprintf(stderr, "attn_launch_planned: no attention kernel (kind %d) instantiated for ks %d qw %d db %d\n", K::kind, p.ks, p.qw, p.db);
+  abort();
+}
+static AttnPlan attn_plan_logged(const AttnQuery& q) {
+  const AttnPlan p = attn_plan(q, g_attn_hooks);
+  if (p.launch) attn_log(q, p);
+  return p;
+}
 
 void launch_attention_fwd(int dtype, const void* q, long ldq, const void* k, const void* v, long ldk, void* o, long ldo,
                           float* lse, int B, int H, int Nq, int Nk, hipStream_t st, int causal) {
-  if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return;      // (the tile fetch clamps rows to rows_total - 1: never with zero rows)
-  // causal: no key split.  A wave group whose whole key range lies after a query row would carry m = -inf into the merge
-  // (exp2(-inf - -inf) = NaN); with one group the first tile always holds key 0, visible to every row
-  int ks = attn_key_split((Nk + 63) / 64, causal ? 1 : 4);
-  const int qw = attn_row_waves(Nq, H * B, Nk);
-  // ... and on such grids a short key loop (< 64 tiles) is not split over wave groups: there are blocks enough, the merge only costs
-  if ((long)cdiv(Nq, 128) * H * B >= 512 && (Nk + 63) / 64 < 64) ks = 1;
-#define DH_ATTN_FWD(T_)                                                                         \
-  do {                                                                                          \
-    if (ks == 4) DH_ATTN_QW(attn_fwd_launch, T_, 4, B, st, q, ldq, k, v, ldk, o, ldo, lse, H, Nq, Nk, causal);       \
-    else if (ks == 2) DH_ATTN_QW(attn_fwd_launch, T_, 2, B, st, q, ldq, k, v, ldk, o, ldo, lse, H, Nq, Nk, causal);  \
-    else DH_ATTN_QW(attn_fwd_launch, T_, 1, B, st, q, ldq, k, v, ldk, o, ldo, lse, H, Nq, Nk, causal);               \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_ATTN_FWD(f16);
-  else DH_ATTN_FWD(bf16);
-#undef DH_ATTN_FWD
+  const AttnPlan p = attn_plan_logged({ATTN_FWD, B, H, Nq, Nk, causal, 0});
+  if (!p.launch) return;
+  attn_launch_planned<AttnFwd>(dtype, p, [&](auto var, dim3 grid, dim3 block) {
+    using V = decltype(var); using T = typename V::T;
+    hipLaunchKernelGGL((k_attn_fwd<T, V::KS, V::QW, V::DB>), grid, block, 0, st, (const T*)q, ldq, (const T*)k, (const T*)v, ldk, (T*)o, ldo,
+                       lse, H, Nq, Nk, causal);
+    return 0;
+  });
 }
 
 void launch_attention_delta(int dtype, const void* o, long ldo, const void* d_o, long lddo, float* delta, int B, int H,
@@ -1004,62 +1067,61 @@ void launch_attention_delta(int dtype, const void* o, long ldo, const void* d_o,
 void launch_attention_bwd_dq(int dtype, const void* q, long ldq, const void* k, const void* v, long ldk, const void* o,
                              long ldo, const void* d_o, long lddo, const float* lse, float* delta, void* dq, long lddq,
                              int B, int H, int Nq, int Nk, hipStream_t st) {
-  if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return;
-  const int qw = attn_row_waves(Nq, H * B, Nk);
-  // four key groups like the forward (12 waves per CU instead of 6 at N = 4096: the loop is VALU-bound and one to two waves
-  // per SIMD leave the pipe idle across every LDS wait; guided step +0.45 %, profiles/r03_ab_dq_ks4.txt); the 16-wave block
-  // of the 128-row tile would spill, it keeps two
-  int ks = attn_key_split((Nk + 63) / 64, 4);
-  if (ks == 4 && qw == 4) ks = 2;
-#define DH_ATTN_DQ(T_)                                                                                                          \
-  do {                                                                                                                           \
-    if (ks == 4) DH_ATTN_QW(attn_dq_launch, T_, 4, B, st, q, ldq, k, v, ldk, o, ldo, d_o, lddo, lse, delta, dq, lddq, H, Nq, Nk); \
-    else if (ks == 2) DH_ATTN_QW(attn_dq_launch, T_, 2, B, st, q, ldq, k, v, ldk, o, ldo, d_o, lddo, lse, delta, dq, lddq, H, Nq, Nk); \
-    else DH_ATTN_QW(attn_dq_launch, T_, 1, B, st, q, ldq, k, v, ldk, o, ldo, d_o, lddo, lse, delta, dq, lddq, H, Nq, Nk);          \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_ATTN_DQ(f16);
-  else DH_ATTN_DQ(bf16);
-#undef DH_ATTN_DQ
+  const AttnPlan p = attn_plan_logged({ATTN_DQ, B, H, Nq, Nk, 0, 0});
+  if (!p.launch) return;
+  attn_launch_planned<AttnDq>(dtype, p, [&](auto var, dim3 grid, dim3 block) {
+    using V = decltype(var); using T = typename V::T;
+    hipLaunchKernelGGL((k_attn_bwd_dq<T, V::KS, V::QW, V::DB>), grid, block, 0, st, (const T*)q, ldq, (const T*)k, (const T*)v, ldk,
+                       (const T*)o, ldo, (const T*)d_o, lddo, lse, delta, (T*)dq, lddq, H, Nq, Nk);
+    return 0;
+  });
 }
 
 void launch_attention_bwd_dkv(int dtype, const void* q, long ldq, const void* k, const void* v, long ldk, const void* d_o,
                               long lddo, const float* lse, const float* delta, void* dk, void* dv, long lddk, int B,
                               int H, int Nq, int Nk, hipStream_t st, float* scratch, size_t scratch_elems) {
-  if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return;
-  int ks = attn_key_split((Nq + 63) / 64, 2);
-  int qw = attn_row_waves(Nk, H * B, Nq);
-#ifdef DH_TUNING
-  { static const int fq = getenv("DH_ATTN_DKV_QW") ? atoi(getenv("DH_ATTN_DKV_QW")) : 0;
-    static const int fk = getenv("DH_ATTN_DKV_KS") ? atoi(getenv("DH_ATTN_DKV_KS")) : 0;
-    if (fq >= 1 && fq <= 4 && Nk > 128) qw = fq;
-    if ((fk == 1 || fk == 2) && Nk > 128) ks = fk; }
-#endif
-  // cross-attention shape (77 keys, thousands of queries): the key blocks alone are H*B workgroups; split the queries
-  // over workgroups too and sum f32 partials.  (All keys in ONE block for that: the even-coverage rule above would pick two
-  // 64-key blocks for 77 keys and leave 10 workgroups streaming 4096 queries each -- 72 us per layer in the null-text
-  // backward, profiles/r03_invert_kernel_types.txt.)
-  int qchunks = 1;
-  float* qpart = nullptr;
-  if (scratch && Nk <= 128 && Nq >= 512) qw = cdiv(Nk, 32);
-  if (scratch && Nk <= 32 * qw && Nq >= 512) {
-    const int tiles_all = (Nq + 63) / 64;
-    qchunks = 256 / (H * B);
-    if (qchunks > tiles_all / 2) qchunks = tiles_all / 2;
-    while (qchunks > 1 && (size_t)qchunks * B * H * 2 * 32 * qw * 64 > scratch_elems) --qchunks;
-    if (qchunks > 1) { qpart = scratch; ks = attn_key_split(cdiv(tiles_all, qchunks), 2); } else qchunks = 1;
-  }
-#define DH_ATTN_DKV(T_)                                                                                                         \
-  do {                                                                                                                           \
-    if (ks == 2) DH_ATTN_QW(attn_dkv_launch, T_, 2, B, st, q, ldq, k, v, ldk, d_o, lddo, lse, delta, dk, dv, lddk, H, Nq, Nk, qpart, qchunks);    \
-    else DH_ATTN_QW(attn_dkv_launch, T_, 1, B, st, q, ldq, k, v, ldk, d_o, lddo, lse, delta, dk, dv, lddk, H, Nq, Nk, qpart, qchunks);             \
-  } while (0)
-  if (dtype == DH_DTYPE_F16) DH_ATTN_DKV(f16);
-  else DH_ATTN_DKV(bf16);
-#undef DH_ATTN_DKV
+  const AttnPlan p = attn_plan_logged({ATTN_DKV, B, H, Nq, Nk, 0, scratch ? scratch_elems : 0});
+  if (!p.launch) return;
+  attn_launch_planned<AttnDkv>(dtype, p, [&](auto var, dim3 grid, dim3 block) {
+    using V = decltype(var); using T = typename V::T;
+    hipLaunchKernelGGL((k_attn_bwd_dkv<T, V::KS, V::QW, V::DB>), grid, block, 0, st, (const T*)q, ldq, (const T*)k, (const T*)v, ldk,
+                       (const T*)d_o, lddo, lse, delta, (T*)dk, (T*)dv, lddk, H, Nq, Nk, p.reduce ? scratch : nullptr, p.qchunks);
+    if (!p.reduce) return 0;
+    const long total = (long)B * H * 2 * Nk * 16;
+    hipLaunchKernelGGL((k_attn_dkv_reduce<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, scratch, p.qchunks, 32 * V::QW,
+                       (T*)dk, (T*)dv, lddk, B, H, Nk);
+    return 1;
+  });
 }
-#undef DH_ATTN_QW
 
 }  // namespace dh
+
+// host-only query of the plan (no launch, no device needed): what the launcher of q->kind would decide.  out[0..10] = the AttnPlan
+// fields in their declared order (unet_kernels.h).  The force_* fields and cus stand in for the hooks (0 = those in force: none in the
+// product build, the environment's in a tuning build; the product's CU count).  tests/test_attn_plan.py pins the table of the passes.
+extern "C" int dh_dbg_attn_plan(const dh_attn_plan_query* q, int32_t* out, int n_out) {
+  using namespace dh;
+  static_assert(sizeof(AttnPlan) == ATTN_PLAN_FIELDS * sizeof(int32_t), "AttnPlan is ATTN_PLAN_FIELDS 32-bit fields");
+  DH_REQUIRE(q && out && n_out >= ATTN_PLAN_FIELDS, "null pointer, or fewer than 11 output slots");
+  DH_REQUIRE(q->kind >= ATTN_FWD && q->kind <= ATTN_DKV, "kind: 0 forward, 1 dQ, 2 dK/dV");
+  AttnHooks h = g_attn_hooks;
+  if (q->force_ks) h.ks = q->force_ks;
+  if (q->force_qw) h.qw = q->force_qw;
+  if (q->force_dkv_ks) h.dkv_ks = q->force_dkv_ks;
+  if (q->force_dkv_qw) h.dkv_qw = q->force_dkv_qw;
+  if (q->cus > 0) h.cus = q->cus;
+  const AttnPlan p = attn_plan(AttnQuery{q->kind, q->B, q->H, q->Nq, q->Nk, q->causal, (size_t)q->scratch_elems}, h);
+  memcpy(out, &p, sizeof(p));
+  return DH_OK;
+}
+
+// test hook: out[0..8] = ks, qw, db, grid x / y / z, block, qchunks, reduce of this thread's last launch of `kind` (zeros before the first)
+extern "C" int dh_dbg_attn_last_launch(int kind, int32_t* out, int n_out) {
+  DH_REQUIRE(out && n_out >= 9, "null pointer, or fewer than 9 output slots");
+  DH_REQUIRE(kind >= dh::ATTN_FWD && kind <= dh::ATTN_DKV, "kind: 0 forward, 1 dQ, 2 dK/dV");
+  memcpy(out, &dh::g_attn_last[kind], sizeof(dh::AttnLaunched));
+  return DH_OK;
+}
 
 #ifdef DH_ATTN_STAMP
 extern "C" int dh_dbg_attn_stamps_dkv(unsigned long long* out) {

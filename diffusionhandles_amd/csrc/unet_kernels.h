@@ -186,4 +186,26 @@ void launch_attention_bwd_dkv(int dtype, const void* q, long ldq, const void* k,
                               long lddk, int B, int H, int Nq, int Nk, hipStream_t st, float* scratch = nullptr,
                               size_t scratch_elems = 0);   // scratch (f32): lets the few-key case split the queries over workgroups
 
+// ---- the host-side plan of one attention launch (attention.hip: attn_plan decides, attn_launch launches; DESIGN.md, "Attention plan")
+enum { ATTN_FWD = 0, ATTN_DQ = 1, ATTN_DKV = 2 };
+constexpr int ATTN_CUS = 256;          // compute units the row-wave and query-chunk rules balance over (a constant of the policy, not asked of the device)
+struct AttnQuery {
+  int kind, B, H, Nq, Nk, causal;
+  size_t scratch_elems;                // f32 elements of workspace for dK/dV's query chunks; 0 = the caller gave none
+};
+struct AttnHooks {                     // a tuning build's forced values (0 = the policy's; all 0 in the product) and the CU count
+  int ks = 0, qw = 0, dkv_ks = 0, dkv_qw = 0;
+  int cus = ATTN_CUS;
+};
+constexpr int ATTN_PLAN_FIELDS = 11;   // dh_dbg_attn_plan writes the fields below in this order, one int32 each
+struct AttnPlan {
+  int launch;                          // 0: a dimension is <= 0, nothing is launched
+  int ks, qw, db;                      // wave groups over the loop range, waves of 32 rows per group, double-buffered form
+  int grid_x, grid_y, grid_z, block;
+  int qchunks, reduce;                 // dK/dV: query chunks over workgroups (1 = none); k_attn_dkv_reduce follows
+  int scratch_used;                    // f32 elements of the caller's scratch the chunks' partials take
+};
+// pure: no HIP call, no environment, no global, no pointer
+AttnPlan attn_plan(const AttnQuery& q, const AttnHooks& h);
+
 }  // namespace dh

@@ -555,6 +555,23 @@ typedef struct dh_gemm_plan_query {
 } dh_gemm_plan_query;
 int dh_dbg_gemm_plan(const dh_gemm_plan_query* q, int32_t* out, int n_out);
 
+/* --------------------------------------------------------------------------------------
+ * Host-only query of the attention dispatch (csrc/attention.hip: attn_plan): which variant of the flash-attention forward (kind 0),
+ * dQ (1) or dK/dV (2) kernel a launch of this description gets.  No launch, no device needed; the description carries no pointers.
+ * out receives 11 values: launch (0 = a dimension is <= 0, nothing would run), ks, qw, db, grid x, y, z, block, qchunks, reduce
+ * (1 = k_attn_dkv_reduce follows), scratch_used (f32 elements).  force_* and cus replace the dispatch's hooks for this query
+ * (0 = leave them: no forced value, 256 compute units).  tests/test_attn_plan.py pins the table of the SD-2-depth passes.
+ * dh_dbg_attn_last_launch: what this thread's last launch of `kind` passed to the device, written by the launcher from its own
+ * template arguments: out[0..8] = ks, qw, db, grid x, y, z, block, qchunks, reduce.
+ * ------------------------------------------------------------------------------------ */
+typedef struct dh_attn_plan_query {
+  int32_t kind, B, H, Nq, Nk, causal;
+  uint64_t scratch_elems;    /* f32 elements of dK/dV workspace; 0 = none */
+  int32_t force_ks, force_qw, force_dkv_ks, force_dkv_qw, cus;
+} dh_attn_plan_query;
+int dh_dbg_attn_plan(const dh_attn_plan_query* q, int32_t* out, int n_out);
+int dh_dbg_attn_last_launch(int kind, int32_t* out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -355,9 +355,18 @@ def test_gemm_geglu_epilogues(dtype, M, Fd, K):
     close(dx, gref, tol, tol, f"geglu-epilogue backward {M}x{Fd}x{K2}")
 
 
+def attention_shapes():
+    """nine shapes of long standing and the ones that complete the variants of the pinned plan table (tests/test_attn_plan.py, which
+    checks on the CPU that together they launch every (kind, ks, qw, db) of it)"""
+    import test_attn_plan as T
+    return T.PARITY_SHAPES + T.VARIANT_SHAPES
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("B,H,Nq,Nk", [(1, 5, 1024, 1024), (2, 2, 256, 256), (1, 20, 64, 64), (2, 5, 1024, 77), (1, 10, 200, 77), (1, 5, 4096, 77), (1, 2, 4096, 4096), (1, 3, 1000, 1000), (1, 2, 1100, 600)])
+@pytest.mark.parametrize("B,H,Nq,Nk", attention_shapes())
 def test_attention_forward_backward(dtype, B, H, Nq, Nk):
+    """forward, dQ and dK/dV against torch; and each launch is the one the host plan names for its query (dh_dbg_attn_last_launch,
+    written by the launcher from its own template arguments and grid, == dh_dbg_attn_plan)"""
     g = torch.Generator(device=dev()).manual_seed(Nq + Nk + H)
     C = H * 64
     q = torch.randn(B, Nq, C, generator=g, device=dev()).to(dtype)
@@ -382,6 +391,10 @@ def test_attention_forward_backward(dtype, B, H, Nq, Nk):
     close(lse, lse_ref, 1e-3, 2e-3, what + " lse")
     for got, r, nm in ((dq, gq, "dq"), (dk, gk, "dk"), (dv, gv, "dv")):
         close(got, r, 2 * tol, 2 * tol * max(1.0, r.abs().max().item()) * 0.2, what + " " + nm)
+    import test_attn_plan as T
+    for kind in (T.FWD, T.DQ, T.DKV):
+        planned = T.named(T.plan(kind, B, H, Nq, Nk, 0, T.DBG_SCRATCH if kind == T.DKV else 0))
+        assert planned["launch"] == 1 and T.last_launch(kind) == {f: planned[f] for f in T.LAST}, (what, kind, planned, T.last_launch(kind))
 
 
 def test_cross_lane_helpers():

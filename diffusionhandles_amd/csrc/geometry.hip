@@ -55,6 +55,50 @@ static ObjTable obj_table(int n_objects, const int* obj_start, int n_fg) {
   return t;
 }
 
+// Copies of an object (dh_reproject_instance_edits): an edit places N INSTANCES, instance n = (mask obj[n], row e * N + n).  The
+// point list holds the instances one after the other: instance n owns the positions start[n] .. start[n + 1) (entries past
+// the last instance hold n_pts), and position j of it is the source pixel fg_pix[j + off[n]] (off = the start of mask obj[n]
+// in fg_pix minus start[n]).  BY VALUE in the kernel arguments, like ObjTable; k_centroid keeps ObjTable (one chain per mask).
+// The identity table (N = M, obj[n] = n, off[n] = 0) is the call without copies.
+struct InstTable {
+  int start[MAX_OBJECTS + 1];
+  int off[MAX_OBJECTS];
+  int obj[MAX_OBJECTS];
+};
+static InstTable inst_table(int n_inst, const int* inst_obj, const int* obj_start, int* n_pts_out) {
+  InstTable t;
+  int at = 0;
+  for (int n = 0; n < MAX_OBJECTS; ++n) {
+    t.start[n] = at;
+    t.off[n] = 0;
+    t.obj[n] = 0;
+    if (n < n_inst) {
+      const int o = inst_obj[n];
+      t.off[n] = obj_start[o] - at;
+      t.obj[n] = o;
+      at += obj_start[o + 1] - obj_start[o];
+    }
+  }
+  t.start[MAX_OBJECTS] = at;
+  *n_pts_out = at;
+  return t;
+}
+// the instance of point-list position j: a compare chain against the table's scalars, the offset and the mask by selects along
+// it (no indexed read of the by-value table with a per-lane index: that would be a private copy of it)
+__device__ __forceinline__ int inst_of(int j, const InstTable& tab, int& off, int& obj) {
+  int n = 0;
+  off = tab.off[0];
+  obj = tab.obj[0];
+#pragma unroll
+  for (int k = 1; k < MAX_OBJECTS; ++k) {
+    const bool in = j >= tab.start[k];
+    n += in ? 1 : 0;
+    off = in ? tab.off[k] : off;
+    obj = in ? tab.obj[k] : obj;
+  }
+  return n;
+}
+
 constexpr int CEN_CHUNK = 1024;
 __global__ void __launch_bounds__(CEN_CHUNK) k_centroid(const float* depth, const int* fg_pix, const ObjTable tab, int res,
                                                          const float* gx, const float* gy, float ifx, float ify, float* cen) {
@@ -127,18 +171,19 @@ struct Xf {
 };
 static_assert(sizeof(Xf) == DH_SIMILARITY_ROW * sizeof(double), "Xf is the similarity row");
 
-// one thread per (edit, point): points [0,R2) are background pixels, [R2,R2+n_fg) foreground, object after object.
-// xf: n_obj rows per edit (edit-major), cen: 4 floats per object.  The object turns about its row's pivot when the row has
-// one (edits of one call may pivot one object differently), else about its centroid; q is scaled per camera axis BEFORE
+// one thread per (edit, point): points [0,R2) are background pixels, [R2,R2+n_pts) foreground, instance after instance
+// (InstTable; without copies an instance is an object).  xf: n_inst rows per edit (edit-major), cen: 4 floats per MASK -- a
+// copy does not recompute its mask's centroid.  The instance turns about its row's pivot when the row has
+// one (edits of one call may pivot one object differently), else about its mask's centroid; q is scaled per camera axis BEFORE
 // the rotation, one rounded f32 multiply per component (s = 1 leaves every bit of q as it was).
 // FP (footprint splatting, further down): the foreground points also leave (u, v, Z) -- u, v before the clamp and the
-// rounding -- in uvz, 3 doubles per point and edit, for the triangles between them.  FP = false is the kernel as it was.
+// rounding -- in uvz, 3 doubles per point-list position and edit, for the triangles between them.
 template <bool FP>
-__global__ void k_points(const float* depth, const float* bg_depth, const int* fg_pix, int n_fg, int res,
+__global__ void k_points(const float* depth, const float* bg_depth, const int* fg_pix, int n_pts, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
-                         const Xf* xf, const float* cen, const ObjTable tab, int n_obj, unsigned long long* zbuf,
+                         const Xf* xf, const float* cen, const InstTable tab, int n_inst, unsigned long long* zbuf,
                          int* pix_out, unsigned long long* key_out, double* uvz) {
-  const int R2 = res * res, P = R2 + n_fg;
+  const int R2 = res * res, P = R2 + n_pts;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
   if (i >= P) return;
@@ -148,16 +193,15 @@ __global__ void k_points(const float* depth, const float* bg_depth, const int* f
     unproject_px(bg_depth, i, res, gx, gy, ifx, ify, x, y, z);
     X = x; Y = y; Z = z;
   } else {
+    // the instance of this point (unused entries of the table hold n_pts: never passed), its source pixel and its mask
+    int off, o;
+    const int n = inst_of(i - R2, tab, off, o);
     float x, y, z;
-    unproject_px(depth, fg_pix[i - R2], res, gx, gy, ifx, ify, x, y, z);
-    // the object of this point: a compare chain against the table's scalars (unused entries hold n_fg: never passed)
-    int m = 0;
-#pragma unroll
-    for (int k = 1; k < MAX_OBJECTS; ++k) m += (i - R2 >= tab.start[k]) ? 1 : 0;
-    const Xf t = xf[e * n_obj + m];
+    unproject_px(depth, fg_pix[i - R2 + off], res, gx, gy, ifx, ify, x, y, z);
+    const Xf t = xf[e * n_inst + n];
     // (the centroid is read whether or not the row has a pivot: three selects, no divergent branch around dependent loads)
     const bool piv = t.has_pivot != 0.0;
-    const float g0 = cen[4 * m], g1 = cen[4 * m + 1], g2 = cen[4 * m + 2];
+    const float g0 = cen[4 * o], g1 = cen[4 * o + 1], g2 = cen[4 * o + 2];
     const float c0 = piv ? (float)t.px : g0, c1 = piv ? (float)t.py : g1, c2 = piv ? (float)t.pz : g2;
     const float q0 = (x - c0) * (float)t.sx, q1 = (y - c1) * (float)t.sy, q2 = (z - c2) * (float)t.sz;
     const float a0 = (float)t.ax, a1 = (float)t.ay, a2 = (float)t.az;
@@ -179,7 +223,7 @@ __global__ void k_points(const float* depth, const float* bg_depth, const int* f
   u = (u * 0.5 + 0.5) * m;
   v = (v * 0.5 + 0.5) * m;
   if (FP && i >= R2) {
-    double* o = uvz + ((size_t)e * n_fg + (i - R2)) * 3;
+    double* o = uvz + ((size_t)e * n_pts + (i - R2)) * 3;
     o[0] = u; o[1] = v; o[2] = Z;
   }
   u = fmin(fmax(u, 0.0), m);
@@ -221,32 +265,34 @@ __global__ void k_fp_inverse(const int* fg_pix, int n_fg, int* inv) {
   if (j < n_fg) inv[fg_pix[j]] = j;
 }
 
-__device__ __forceinline__ int fp_object(int j, const ObjTable& tab) {
-  int m = 0;
-#pragma unroll
-  for (int k = 1; k < MAX_OBJECTS; ++k) m += (j >= tab.start[k]) ? 1 : 0;
-  return m;
-}
-
-// false = the triangle does not exist or is dropped (a vertex outside the masks or of another object, the depth-ratio guard,
-// Z <= 0, non-finite u / v, area <= 0, an empty candidate box)
-__device__ __forceinline__ bool fp_setup(int t, int e, int res, int n_fg, const int* inv, const ObjTable& tab, const double* uvz,
-                                         const float* depth, float max_ratio, FpTri& T, int3& J) {
+// the part of a triangle that no instance changes: F = the fg_pix positions of its three source pixels.  false = a vertex outside
+// the masks, or the depth-ratio guard
+__device__ __forceinline__ bool fp_source(int t, int res, const int* inv, const float* depth, float max_ratio, int3& F) {
   const int q = t >> 1, h = t & 1, qy = q / (res - 1), qx = q - qy * (res - 1);
   const int p00 = qy * res + qx, p01 = p00 + 1, p10 = p00 + res, p11 = p10 + 1;
   const int s0 = p10, s1 = h ? p01 : p11, s2 = h ? p00 : p01;
-  const int j0 = inv[s0], j1 = inv[s1], j2 = inv[s2];
-  if ((j0 | j1 | j2) < 0) return false;
-  const int m0 = fp_object(j0, tab);
-  if (fp_object(j1, tab) != m0 || fp_object(j2, tab) != m0) return false;
+  F = make_int3(inv[s0], inv[s1], inv[s2]);
+  if ((F.x | F.y | F.z) < 0) return false;
   if (max_ratio > 0.f) {          // on the SOURCE depths, f32: a quad across a depth step inside one mask makes no sheet
     const float d0 = depth[s0], d1 = depth[s1], d2 = depth[s2];
     const float zmin = fminf(fminf(d0, d1), d2), zmax = fmaxf(fmaxf(d0, d1), d2);
     if (zmax > zmin * max_ratio) return false;
   }
-  const double* a = uvz + ((size_t)e * n_fg + j0) * 3;
-  const double* b = uvz + ((size_t)e * n_fg + j1) * 3;
-  const double* c = uvz + ((size_t)e * n_fg + j2) * 3;
+  return true;
+}
+
+// false = the triangle F does not exist for instance n or is dropped (a vertex outside the mask of the instance, Z <= 0,
+// non-finite u / v, area <= 0, an empty candidate box).  n is uniform where this is called (a loop counter, a wave's list
+// entry): the table is read with scalars.  J holds POINT-LIST positions.
+__device__ __forceinline__ bool fp_setup(const int3 F, int n, int e, int res, int n_pts, const InstTable& tab, const double* uvz,
+                                         FpTri& T, int3& J) {
+  // fg_pix position -> point-list position of instance n; inside the instance's slice = the pixel is of its mask
+  const int off = tab.off[n], lo = tab.start[n], hi = tab.start[n + 1];
+  const int j0 = F.x - off, j1 = F.y - off, j2 = F.z - off;
+  if (j0 < lo || j0 >= hi || j1 < lo || j1 >= hi || j2 < lo || j2 >= hi) return false;
+  const double* a = uvz + ((size_t)e * n_pts + j0) * 3;
+  const double* b = uvz + ((size_t)e * n_pts + j1) * 3;
+  const double* c = uvz + ((size_t)e * n_pts + j2) * 3;
   T.u0 = a[0]; T.v0 = a[1]; T.z0 = a[2];
   T.u1 = b[0]; T.v1 = b[1]; T.z1 = b[2];
   T.u2 = c[0]; T.v2 = c[1]; T.z2 = c[2];
@@ -295,41 +341,51 @@ constexpr int FP_TIER_DEFAULT = 64;
 static int g_fp_tier = 0;
 static inline int fp_tier() { return g_fp_tier > 0 ? g_fp_tier : FP_TIER_DEFAULT; }
 
-// thread tier: one thread per (edit, triangle).  A box of more than `tier` candidates goes to the edit's list for the wave
-// tier (appended in pass 1; pass 2 replays the list); the result does not depend on `tier`: atomicMin commutes.
-__global__ void k_fp_tri(int pass, int res, int n_fg, const int* inv, const ObjTable tab, const double* uvz, const float* depth,
-                         float max_ratio, int tier, unsigned long long* zbuf, int* owner, int* big_list, int* big_count) {
+// thread tier: one thread per (edit, triangle), walking the instances (a uniform loop; without copies exactly one of them has
+// the triangle).  A box of more than `tier` candidates goes to the edit's list for the wave tier as (triangle, instance)
+// (appended in pass 1; pass 2 replays the list); the result does not depend on `tier`: atomicMin commutes.
+// The list holds triangle * MAX_OBJECTS + instance (unsigned: 16 res^2 < 2^32 for every res the CLOSE element admits); an
+// instance has at most 2 |mask| triangles, so 2 n_pts entries per edit hold every list (and 2 (res - 1)^2 without copies).
+__global__ void k_fp_tri(int pass, int res, int n_pts, int n_inst, const int* inv, const InstTable tab, const double* uvz,
+                         const float* depth, float max_ratio, int tier, unsigned long long* zbuf, int* owner, unsigned* big_list,
+                         size_t big_stride, int* big_count) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
   const int nt = 2 * (res - 1) * (res - 1), R2 = res * res;
   if (t >= nt) return;
-  FpTri T;
-  int3 J;
-  if (!fp_setup(t, e, res, n_fg, inv, tab, uvz, depth, max_ratio, T, J)) return;
-  const long long cand = (long long)(T.c1 - T.c0 + 1) * (T.r1 - T.r0 + 1);
-  if (cand > tier) {
-    if (pass == 1) big_list[(size_t)e * nt + atomicAdd(&big_count[e], 1)] = t;
-    return;
-  }
+  int3 F;
+  if (!fp_source(t, res, inv, depth, max_ratio, F)) return;
   unsigned long long* zb = zbuf + (size_t)e * R2;
   int* ow = owner + (size_t)e * R2;
-  for (int r = T.r0; r <= T.r1; ++r)
-    for (int c = T.c0; c <= T.c1; ++c) fp_bid(T, J, c, r, pass, res, R2, zb, ow);
+  for (int n = 0; n < n_inst; ++n) {
+    FpTri T;
+    int3 J;
+    if (!fp_setup(F, n, e, res, n_pts, tab, uvz, T, J)) continue;
+    const long long cand = (long long)(T.c1 - T.c0 + 1) * (T.r1 - T.r0 + 1);
+    if (cand > tier) {
+      if (pass == 1) big_list[(size_t)e * big_stride + atomicAdd(&big_count[e], 1)] = (unsigned)t * MAX_OBJECTS + n;
+      continue;
+    }
+    for (int r = T.r0; r <= T.r1; ++r)
+      for (int c = T.c0; c <= T.c1; ++c) fp_bid(T, J, c, r, pass, res, R2, zb, ow);
+  }
 }
 
-// wave tier: one 64-lane wave per listed triangle, the lanes striding over its box
+// wave tier: one 64-lane wave per listed (triangle, instance), the lanes striding over its box
 constexpr int FP_WAVE_BLOCKS = 256;
-__global__ void __launch_bounds__(256) k_fp_wave(int pass, int res, int n_fg, const int* inv, const ObjTable tab, const double* uvz,
+__global__ void __launch_bounds__(256) k_fp_wave(int pass, int res, int n_pts, const int* inv, const InstTable tab, const double* uvz,
                                                  const float* depth, float max_ratio, unsigned long long* zbuf, int* owner,
-                                                 const int* big_list, const int* big_count) {
+                                                 const unsigned* big_list, size_t big_stride, const int* big_count) {
   const int e = blockIdx.y, lane = threadIdx.x & 63;
-  const int nt = 2 * (res - 1) * (res - 1), R2 = res * res;
+  const int R2 = res * res;
   const int n = big_count[e];
   unsigned long long* zb = zbuf + (size_t)e * R2;
   int* ow = owner + (size_t)e * R2;
   for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < n; k += FP_WAVE_BLOCKS * 4) {
     FpTri T;
-    int3 J;
-    if (!fp_setup(big_list[(size_t)e * nt + k], e, res, n_fg, inv, tab, uvz, depth, max_ratio, T, J)) continue;
+    int3 F, J;
+    const unsigned ent = __builtin_amdgcn_readfirstlane(big_list[(size_t)e * big_stride + k]);
+    if (!fp_source((int)(ent / MAX_OBJECTS), res, inv, depth, max_ratio, F)) continue;
+    if (!fp_setup(F, (int)(ent % MAX_OBJECTS), e, res, n_pts, tab, uvz, T, J)) continue;
     const int W = T.c1 - T.c0 + 1, cand = W * (T.r1 - T.r0 + 1);          // (<= res * res: the box lies inside the image)
     for (int i = lane; i < cand; i += 64) {
       const int dr = i / W;
@@ -340,27 +396,31 @@ __global__ void __launch_bounds__(256) k_fp_wave(int pass, int res, int n_fg, co
 
 // with footprints a point is visible when it owns at least one pixel (vis zeroed before); keep = foreground-owned target
 // pixel inside the cleaned mask; the correspondences are one row per kept TARGET pixel, row-major
-__global__ void k_fp_vis(int R2, int n_fg, const int* owner, const uint8_t* raw_mask, uint8_t* vis, const uint8_t* clean,
+__global__ void k_fp_vis(int R2, int n_pts, const int* owner, const uint8_t* raw_mask, uint8_t* vis, const uint8_t* clean,
                          uint8_t* keep) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
   if (p >= R2) return;
   const size_t o = (size_t)e * R2 + p;
   const bool fg = raw_mask[o] != 0;
-  if (vis && fg) vis[(size_t)e * n_fg + (owner[o] - R2)] = 1;
+  if (vis && fg) vis[(size_t)e * n_pts + (owner[o] - R2)] = 1;
   if (keep) keep[o] = (fg && clean[o]) ? 1 : 0;
 }
 
-__global__ void k_write_corr_target(int R2, int res, const int* fg_pix, const int* owner, const int* keep_idx, const int* counts,
-                                    int count_stride, size_t corr_stride, long long* corr) {
+__global__ void k_write_corr_target(int R2, int res, const int* fg_pix, const InstTable tab, const int* owner, const int* keep_idx,
+                                    const int* counts, int count_stride, size_t corr_stride, long long* corr, uint8_t* corr_inst) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
   if (r >= counts[e * count_stride]) return;
   const int t = keep_idx[(size_t)e * R2 + r];
-  const int p = fg_pix[owner[(size_t)e * R2 + t] - R2];
+  const int j = owner[(size_t)e * R2 + t] - R2;
+  int off, o;
+  const int n = inst_of(j, tab, off, o);
+  const int p = fg_pix[j + off];
   long long* c = corr + ((size_t)e * corr_stride + r) * 4;
   c[0] = p % res;
   c[1] = p / res;
   c[2] = t % res;
   c[3] = t / res;
+  if (corr_inst) corr_inst[(size_t)e * corr_stride + r] = (uint8_t)n;
 }
 
 __device__ __forceinline__ unsigned int sortable_f32(float x) {
@@ -415,16 +475,17 @@ __global__ void k_pixels(int R2, const unsigned long long* zbuf, const int* owne
   }
 }
 
-__global__ void k_fg_vis(int n_fg, int R2, int P, int res, const int* pix_arr, const int* owner, uint8_t* vis,
+// (j: a position in the foreground part of the point list, n_pts of them; with copies a source pixel has several)
+__global__ void k_fg_vis(int n_pts, int R2, int P, int res, const int* pix_arr, const int* owner, uint8_t* vis,
                          int* target_xy) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
-  if (j >= n_fg) return;
+  if (j >= n_pts) return;
   int i = R2 + j;
   int pix = pix_arr[(size_t)e * P + i];
-  vis[(size_t)e * n_fg + j] = owner[(size_t)e * R2 + pix] == i ? 1 : 0;
-  target_xy[((size_t)e * n_fg + j) * 2 + 0] = pix % res;
-  target_xy[((size_t)e * n_fg + j) * 2 + 1] = pix / res;
+  vis[(size_t)e * n_pts + j] = owner[(size_t)e * R2 + pix] == i ? 1 : 0;
+  target_xy[((size_t)e * n_pts + j) * 2 + 0] = pix % res;
+  target_xy[((size_t)e * n_pts + j) * 2 + 1] = pix / res;
 }
 
 // binary morphology with an explicit offset list; pixels outside the image are ignored.
@@ -500,27 +561,31 @@ __global__ void k_morph_bits(const unsigned* src, unsigned* dst, int res, const 
   dst[(size_t)blockIdx.y * wpr * res + idx] = inv_out ? ~acc : acc;
 }
 
-__global__ void k_keep_flags(int n_fg, int R2, int P, const int* pix_arr, const uint8_t* vis, const uint8_t* clean,
+__global__ void k_keep_flags(int n_pts, int R2, int P, const int* pix_arr, const uint8_t* vis, const uint8_t* clean,
                              uint8_t* keep) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
-  if (j >= n_fg) return;
+  if (j >= n_pts) return;
   int pix = pix_arr[(size_t)e * P + R2 + j];
-  keep[(size_t)e * n_fg + j] = (vis[(size_t)e * n_fg + j] && clean[(size_t)e * R2 + pix]) ? 1 : 0;
+  keep[(size_t)e * n_pts + j] = (vis[(size_t)e * n_pts + j] && clean[(size_t)e * R2 + pix]) ? 1 : 0;
 }
 
-__global__ void k_write_corr(int n_fg, int res, const int* fg_pix, const int* target_xy, const int* keep_idx,
-                             const int* counts, int count_stride, size_t corr_stride, long long* corr) {
+// row r of edit e: the r-th kept point-list position, its source pixel through the table, its instance beside it
+__global__ void k_write_corr(int n_pts, int res, const int* fg_pix, const InstTable tab, const int* target_xy, const int* keep_idx,
+                             const int* counts, int count_stride, size_t corr_stride, long long* corr, uint8_t* corr_inst) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
   if (r >= counts[e * count_stride]) return;
-  int j = keep_idx[(size_t)e * n_fg + r];
-  int p = fg_pix[j];
+  int j = keep_idx[(size_t)e * n_pts + r];
+  int off, o;
+  const int n = inst_of(j, tab, off, o);
+  int p = fg_pix[j + off];
   long long* c = corr + ((size_t)e * corr_stride + r) * 4;
   c[0] = p % res;
   c[1] = p / res;
-  c[2] = target_xy[((size_t)e * n_fg + j) * 2 + 0];
-  c[3] = target_xy[((size_t)e * n_fg + j) * 2 + 1];
+  c[2] = target_xy[((size_t)e * n_pts + j) * 2 + 0];
+  c[3] = target_xy[((size_t)e * n_pts + j) * 2 + 1];
+  if (corr_inst) corr_inst[(size_t)e * corr_stride + r] = (uint8_t)n;
 }
 
 __global__ void k_count_flags(const uint8_t* f, int n, int* out, int out_stride, int slot) {
@@ -1107,13 +1172,17 @@ struct ReprojectWs {
   // footprints only (nothing is taken without them: the workspace of the other entries is what it was)
   double* uvz;
   int* inv;
-  int* big_list;
+  unsigned* big_list;
   int* big_count;
+  size_t big_stride;
 };
 
-static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false) {
+// n_fg: the foreground points of the point list (with copies n_pts, the sum over the instances); M: masks; N: transform rows
+// per edit (instances; 0 = M, the call without copies, whose carving -- and so every workspace query that existed before the
+// copies -- is what it was: the wave tier's list then has a slot per triangle of the grid, else 2 n_pts per edit)
+static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false, int N = 0) {
   const size_t R2 = (size_t)res * res, P = R2 + n_fg;
-  w.xf = a.take<Xf>((size_t)K * M);
+  w.xf = a.take<Xf>((size_t)K * (N > 0 ? N : M));
   w.cen = a.take<float>(4 * M);
   w.zbuf = a.take<unsigned long long>(K * R2);
   w.owner = a.take<int>(K * R2);
@@ -1134,11 +1203,12 @@ static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, boo
   w.vp = a.take<double>(K * R2);
   w.vq = a.take<double>(K * R2);
   w.cgsync = a.take<CgSync>(K);
-  w.uvz = nullptr; w.inv = nullptr; w.big_list = nullptr; w.big_count = nullptr;
+  w.uvz = nullptr; w.inv = nullptr; w.big_list = nullptr; w.big_count = nullptr; w.big_stride = 0;
   if (footprints) {
     w.uvz = a.take<double>((size_t)K * n_fg * 3);
     w.inv = a.take<int>(R2);
-    w.big_list = a.take<int>((size_t)K * 2 * (res - 1) * (res - 1));
+    w.big_stride = N > 0 ? (size_t)2 * n_fg : (size_t)2 * (res - 1) * (res - 1);
+    w.big_list = a.take<unsigned>((size_t)K * w.big_stride);
     w.big_count = a.take<int>(K);
   }
   return a.ok();
@@ -1200,36 +1270,48 @@ extern "C" int dh_masked_centroid(const float* depth, const int32_t* fg_pix, int
   return DH_OK;
 }
 
-// n_objects bodies per edit: object m owns fg_pix[obj_start[m] .. obj_start[m + 1]) and row e * n_objects + m of xforms_host
-// (DH_SIMILARITY_ROW doubles: rotation, translation, scale, pivot).  Only k_centroid and k_points know about objects; from the
-// z-buffer on the point list is one list.  The one code path of the re-projection: dh_reproject_object_edits and
-// dh_reproject_edits are its scale-1 / no-pivot calls, and all three are the footprints = 0 call of this entry.
+// n_objects masks: mask m owns fg_pix[obj_start[m] .. obj_start[m + 1]).  n_inst instances per edit: instance n draws the points
+// of mask inst_obj[n] with row e * n_inst + n of xforms_host (DH_SIMILARITY_ROW doubles: rotation, translation, scale, pivot);
+// the point list holds them one after the other (InstTable), n_pts foreground points in all.  Only k_centroid (masks) and
+// k_points, the triangles and the row writers (instances) know about either; from the z-buffer on the point list is one list.
+// The one code path of the re-projection: identity_carve = the call without copies (inst_obj[n] = n) with the workspace
+// layout it always had -- dh_reproject_footprint_edits, and through it the similarity, object and single-object entries.
 //
-// footprints = 1 (point mode's footprint splatting): the triangles between neighbouring points of one object bid in the same
+// footprints = 1 (point mode's footprint splatting): the triangles between neighbouring points of one INSTANCE bid in the same
 // z-buffer, in both passes; vis, the kept set and the correspondences are then taken per TARGET pixel (corr_capacity rows per
-// edit: res * res; without footprints n_fg).  max_ratio: 0 = none, else the depth-ratio guard of the triangles (finite, > 1).
-extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                             const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                             uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                             int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                             void* stream, int footprints, float max_ratio, int corr_capacity) {
-  DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start, "null input");
+// edit: res * res; without footprints n_pts).  max_ratio: 0 = none, else the depth-ratio guard of the triangles (finite, > 1).
+static int reproject_instances(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg, int n_objects,
+                               const int32_t* obj_start, int n_inst, const int32_t* inst_obj, bool identity_carve, int res,
+                               const float* grid_x, const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                               int n_edits, const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                               uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy, int64_t* corr,
+                               uint8_t* corr_inst, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
+                               int footprints, float max_ratio, int corr_capacity) {
+  DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start && inst_obj, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
   DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
+  DH_REQUIRE(n_inst >= 1 && n_inst <= MAX_OBJECTS, "1 to 8 instances");
   DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
   DH_REQUIRE(max_ratio == 0.f || (max_ratio > 1.f && max_ratio <= 3.4028234663852886e38f),
              "footprint max_ratio must be 0 (none) or finite and > 1");
   DH_REQUIRE(max_ratio == 0.f || footprints, "footprint max_ratio without footprints");
-  DH_REQUIRE((long long)corr_capacity >= (footprints ? (long long)res * res : (long long)n_fg),
-             "correspondence capacity too small (n_fg rows per edit without footprints, res * res with)");
   DH_REQUIRE(obj_start[0] == 0 && obj_start[n_objects] == n_fg, "obj_start must run from 0 to n_fg");
   for (int m = 0; m < n_objects; ++m) DH_REQUIRE(obj_start[m] < obj_start[m + 1], "obj_start must increase (no empty object)");
+  long long n_pts_ll = 0;
+  unsigned named = 0;
+  for (int n = 0; n < n_inst; ++n) {
+    DH_REQUIRE(inst_obj[n] >= 0 && inst_obj[n] < n_objects, "inst_obj: an instance names a mask outside 0 .. n_objects - 1");
+    named |= 1u << inst_obj[n];
+    n_pts_ll += obj_start[inst_obj[n] + 1] - obj_start[inst_obj[n]];
+  }
+  DH_REQUIRE(named == (1u << n_objects) - 1u, "inst_obj: a mask without an instance (removing an object is not supported)");
+  DH_REQUIRE((long long)res * res + n_pts_ll <= 2147483647LL, "res * res + n_pts does not fit the int owner map");
+  DH_REQUIRE((long long)corr_capacity >= (footprints ? (long long)res * res : n_pts_ll),
+             "correspondence capacity too small (n_fg rows per edit without footprints, res * res with)");
   // every row before any launch: a scale that is not positive and finite would collapse or mirror the object or spread NaN over
   // the z-buffer; a pivot is checked whether or not the row's flag selects it
-  for (size_t r = 0; r < (size_t)n_edits * n_objects; ++r) {
+  for (size_t r = 0; r < (size_t)n_edits * n_inst; ++r) {
     const double* row = xforms_host + r * DH_SIMILARITY_ROW;
     for (int k = 8; k < 11; ++k)
       DH_REQUIRE((float)row[k] > 0.0f && row[k] <= 3.4028234663852886e38, "transform row: the scale must be positive and finite");
@@ -1238,11 +1320,14 @@ extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_
     DH_REQUIRE(row[14] == 0.0 || row[14] == 1.0, "transform row: the has-pivot flag must be 0 or 1");
   }
   hipStream_t st = (hipStream_t)stream;
-  const int K = n_edits, M = n_objects, R2 = res * res, P = R2 + n_fg;
+  const int K = n_edits, M = n_objects, N = n_inst;
   const ObjTable tab = obj_table(M, obj_start, n_fg);
+  int n_pts = 0;
+  const InstTable itab = inst_table(N, inst_obj, obj_start, &n_pts);
+  const int R2 = res * res, P = R2 + n_pts;
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
-  DH_REQUIRE(carve(a, res, n_fg, K, M, w, footprints != 0), "workspace too small");
+  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N), "workspace too small");
   const size_t corr_stride = (size_t)corr_capacity;
 
   int2 hc[MAX_OFFS], ho[MAX_OFFS];
@@ -1252,7 +1337,7 @@ extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_
   const int no = ellipse_offsets(ko < 1 ? 1 : ko, ho);
   DH_CHECK_HIP(hipMemcpyAsync(w.offs_close, hc, nc * sizeof(int2), hipMemcpyHostToDevice, st));
   DH_CHECK_HIP(hipMemcpyAsync(w.offs_open, ho, no * sizeof(int2), hipMemcpyHostToDevice, st));
-  DH_CHECK_HIP(hipMemcpyAsync(w.xf, xforms_host, (size_t)K * M * sizeof(Xf), hipMemcpyHostToDevice, st));
+  DH_CHECK_HIP(hipMemcpyAsync(w.xf, xforms_host, (size_t)K * N * sizeof(Xf), hipMemcpyHostToDevice, st));
   DH_CHECK_HIP(hipMemsetAsync(w.zbuf, 0xff, (size_t)K * R2 * sizeof(unsigned long long), st));
   DH_CHECK_HIP(hipMemsetAsync(w.owner, 0x7f, (size_t)K * R2 * sizeof(int), st));
   DH_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)K * 4 * sizeof(int), st));
@@ -1265,27 +1350,27 @@ extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_
   // footprints: the triangle kernels run once per z-buffer pass, thread tier then wave tier (the list is built in pass 1)
   const int n_tri = 2 * (res - 1) * (res - 1);
   auto footprint_pass = [&](int pass) {
-    hipLaunchKernelGGL(k_fp_tri, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_fg, w.inv, tab, w.uvz, depth, max_ratio,
-                       fp_tier(), w.zbuf, w.owner, w.big_list, w.big_count);
-    hipLaunchKernelGGL(k_fp_wave, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_fg, w.inv, tab, w.uvz, depth, max_ratio,
-                       w.zbuf, w.owner, w.big_list, w.big_count);
+    hipLaunchKernelGGL(k_fp_tri, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_pts, N, w.inv, itab, w.uvz, depth,
+                       max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count);
+    hipLaunchKernelGGL(k_fp_wave, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_pts, w.inv, itab, w.uvz, depth, max_ratio,
+                       w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count);
   };
   if (footprints) {
     DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
     hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
-    hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_fg, res, grid_x,
-                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, tab, M, w.zbuf, w.pix, w.key, w.uvz);
+    hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_pts, res, grid_x,
+                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz);
     footprint_pass(1);
   } else {
-    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_fg, res, grid_x,
-                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, tab, M, w.zbuf, w.pix, w.key, (double*)nullptr);
+    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_pts, res, grid_x,
+                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, (double*)nullptr);
   }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
   if (footprints) footprint_pass(2);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), K), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, raw_mask,
                      disparity, w.minmax);
-  hipLaunchKernelGGL(k_fg_vis, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, R2, P, res, w.pix, w.owner, vis,
+  hipLaunchKernelGGL(k_fg_vis, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, R2, P, res, w.pix, w.owner, vis,
                      target_xy);
   // CLOSE = dilate, erode ; OPEN = erode, dilate
   if (res % 32 == 0 && kc < 32 && ko < 32) {        // bit rows: pack, four passes (erode = NOT dilate NOT), unpack
@@ -1307,19 +1392,19 @@ extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_
   if (footprints) {
     // per TARGET pixel: vis = the point owns a pixel, keep = foreground-owned and inside the cleaned mask.  The flags and the
     // compacted list live in the in-fill's buffers (inpaint / unk: written again further down, after the rows are out)
-    DH_CHECK_HIP(hipMemsetAsync(vis, 0, (size_t)K * n_fg, st));
-    hipLaunchKernelGGL(k_fp_vis, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, n_fg, w.owner, raw_mask, vis, clean_mask, w.inpaint);
+    DH_CHECK_HIP(hipMemsetAsync(vis, 0, (size_t)K * n_pts, st));
+    hipLaunchKernelGGL(k_fp_vis, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, n_pts, w.owner, raw_mask, vis, clean_mask, w.inpaint);
     compact(w.inpaint, R2, K, R2, w.unk, R2, counts + 0, 4, w.block_counts, st);
-    hipLaunchKernelGGL(k_write_corr_target, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, res, fg_pix, w.owner, w.unk, counts, 4,
-                       corr_stride, (long long*)corr);
+    hipLaunchKernelGGL(k_write_corr_target, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, res, fg_pix, itab, w.owner, w.unk, counts,
+                       4, corr_stride, (long long*)corr, corr_inst);
   } else {
-    hipLaunchKernelGGL(k_keep_flags, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, R2, P, w.pix, vis, clean_mask,
+    hipLaunchKernelGGL(k_keep_flags, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, R2, P, w.pix, vis, clean_mask,
                        w.keep);
-    compact(w.keep, n_fg, K, n_fg, w.keep_idx, n_fg, counts + 0, 4, w.block_counts, st);
-    hipLaunchKernelGGL(k_write_corr, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, n_fg, res, fg_pix, target_xy,
-                       w.keep_idx, counts, 4, corr_stride, (long long*)corr);
+    compact(w.keep, n_pts, K, n_pts, w.keep_idx, n_pts, counts + 0, 4, w.block_counts, st);
+    hipLaunchKernelGGL(k_write_corr, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, res, fg_pix, itab, target_xy,
+                       w.keep_idx, counts, 4, corr_stride, (long long*)corr, corr_inst);
   }
-  hipLaunchKernelGGL(k_count_flags, dim3(cdiv(n_fg, 256), K), dim3(256), 0, st, vis, n_fg, counts, 4, 1);
+  hipLaunchKernelGGL(k_count_flags, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, vis, n_pts, counts, 4, 1);
   hipLaunchKernelGGL(k_normalize, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, disparity, w.minmax, bounds, raw_mask,
                      clean_mask, w.inpaint);
   compact(w.inpaint, R2, K, R2, w.unk, R2, counts + 2, 4, w.block_counts, st);
@@ -1340,6 +1425,47 @@ extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_
                      reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+extern "C" int dh_reproject_instances_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
+                                                      int footprints, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
+  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
+  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
+  Arena a(nullptr, (size_t)-1);
+  ReprojectWs w;
+  carve(a, res, n_pts, n_edits, n_objects, w, footprints != 0, n_instances);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_reproject_instance_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                            int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                            const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                            const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                            uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                            int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                            void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
+                                            const int32_t* inst_obj, uint8_t* corr_inst) {
+  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
+                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
+                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
+                             corr_capacity);
+}
+
+// the identity table: N = M, instance n draws mask n, no instance column
+extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                             const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                             uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                             int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                             void* stream, int footprints, float max_ratio, int corr_capacity) {
+  static const int32_t identity[MAX_OBJECTS] = {0, 1, 2, 3, 4, 5, 6, 7};
+  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_objects, identity, true, res, grid_x, grid_y,
+                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
+                             target_xy, corr, nullptr, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
+                             corr_capacity);
 }
 
 extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,

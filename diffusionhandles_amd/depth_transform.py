@@ -216,6 +216,30 @@ def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_
                                   footprint_max_ratio)
 
 
+def check_instances(instances, n_masks, what="instances"):
+    """The instance table of an edit with copies -> list of N mask indices (None -> None: one instance per mask).
+    ValueError naming `what` and the instance for more than 8 instances, an entry that is not an integer in 0 .. n_masks - 1,
+    or a mask that no instance names (removing an object is not supported).  Host only: no device work."""
+    if instances is None:
+        return None
+    try:
+        inst = list(instances)
+    except TypeError:
+        raise ValueError(f"{what}: expected a list of mask indices, got {instances!r}") from None
+    if not 1 <= len(inst) <= MAX_OBJECTS:
+        raise ValueError(f"{what}: expected 1 to {MAX_OBJECTS} instances, got {len(inst)}")
+    out = []
+    for n, o in enumerate(inst):
+        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not 0 <= int(o) < n_masks:
+            raise ValueError(f"{what}: instance {n} names mask {o!r}, expected an integer in 0..{n_masks - 1}")
+        out.append(int(o))
+    for m in range(n_masks):
+        if m not in out:
+            raise ValueError(f"{what}: mask {m} has no instance (removing an object is not supported; every mask needs at "
+                             f"least one instance)")
+    return out
+
+
 def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_input_depth_normalization=False,
                            return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None):
     """K edits of one image with M bodies each (not in the reference).  fg_masks: M pairwise disjoint [1,1,H,W] masks
@@ -245,17 +269,47 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
     ROW-MAJOR TARGET order, and there may be more of them than foreground points (at most H * W).  footprint_max_ratio: None
     or a finite float > 1; a triangle whose source depths differ by more than this factor is left out (no sheets across a
     depth step inside one mask).  ValueError for a bad ratio or a ratio without footprints, before any device work.
+    Copies of an object (several instances of one mask): `reproject_instance_edits`, of which this is the call without a table.
+    """
+    return reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, None, use_input_depth_normalization,
+                                    return_debug, device_correspondences, footprints, footprint_max_ratio)
+
+
+def reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, use_input_depth_normalization=False,
+                             return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None,
+                             return_instances=False):
+    """`reproject_object_edits` with an instance table (not in the reference): everything said there holds, and --
+
+    instances (copies of an object, DESIGN.md "Object copies"): None, or a list of N mask indices, M <= N <= 8, naming every
+    mask at least once.  Instance n draws the points of mask instances[n] with transform n of every edit (the edits are then K
+    lists of N transforms), about the centroid of that mask (computed once per mask) or its pivot.  The point list is the
+    background, then instance 0's points, instance 1's, ...: one z-buffer, equal depths to the earlier instance.  The
+    correspondences are in point-list order -- a source pixel once per visible, kept instance -- and with footprints the
+    triangles join neighbouring points of one instance.  One table serves all K edits.  ValueError naming the instance (or
+    the edit) for a bad table or an edit that does not have N transforms, before any device work.  The debug dict gains
+    corr_inst [K, capacity] uint8 (the caller's instance index of every correspondence row) and inst_start (the offsets of the
+    kept instances' slices in vis / target_xy); instances=None is `reproject_object_edits`, byte for byte.
+    return_instances=True: every result is (disparity, correspondences [R,4], instances [R] uint8 beside them); without
+    an instance table the instance of a row is the index of its mask.
     """
     footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
     fg_masks = list(fg_masks)
     M = len(fg_masks)
     if not 1 <= M <= MAX_OBJECTS:
         raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got {M}")
+    inst = check_instances(instances, M, "reproject_instance_edits: instances")
+    with_table = inst is not None or bool(return_instances)
+    if inst is None:
+        inst = list(range(M))
+    N = len(inst)
     edits = [list(tfs) for tfs in edits]
     for e, tfs in enumerate(edits):
-        if len(tfs) != M:
-            raise ValueError(f"Edit {e} has {len(tfs)} transforms for {M} foreground masks")
-    edits = [[check_transform(tf, f"edit {e}, object {m}") for m, tf in enumerate(tfs)] for e, tfs in enumerate(edits)]
+        if len(tfs) != N:
+            if instances is None:
+                raise ValueError(f"Edit {e} has {len(tfs)} transforms for {M} foreground masks")
+            raise ValueError(f"Edit {e} has {len(tfs)} transforms for {N} instances")
+    edits = [[check_transform(tf, f"edit {e}, {'object' if instances is None else 'instance'} {m}") for m, tf in enumerate(tfs)]
+             for e, tfs in enumerate(edits)]
     for fg_mask in fg_masks:
         if fg_mask.shape[-2] != fg_mask.shape[-1]:
             raise RuntimeError(f"Expected fg_mask to be square, got shape {fg_mask.shape[-2]} x {fg_mask.shape[-1]}.")
@@ -294,7 +348,7 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
         lo_hi = None if bounds is None else (bounds[0], bounds[1])
         disp = normalize_depth(1.0 / d, bounds=lo_hi).to(out_dev)
         empty = torch.zeros((0, 4), dtype=torch.int64)
-        res_list = [(disp, empty) for _ in range(K)]
+        res_list = [(disp, empty) + ((torch.zeros(0, dtype=torch.uint8),) if return_instances else ()) for _ in range(K)]
         return (res_list, {}) if return_debug else res_list
 
     gx, gy = _grids(res, res, dev)
@@ -309,36 +363,62 @@ def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_inp
     for j, m in enumerate(kept):              # disjoint masks: the slices fill fg_pix[0 .. n_fg), n_fg <= R2
         _lib.check(L.dh_fg_pixel_list(_lib.ptr(masks_u8[m]), res, _lib.ptr(fg_pix[int(obj_start[j]):]), _lib.ptr(n_dev[j:]),
                                       _lib.ptr(ws_small), ws_small.numel(), st), "dh_fg_pixel_list")
+    # the instances of the kept masks (empty masks are dropped with all of their instances); caller[n'] = the caller's index
+    caller = [n for n in range(N) if inst[n] in kept]
+    inst_obj = np.asarray([kept.index(inst[n]) for n in caller], dtype=np.int32)
+    Nk = len(caller)
+    sizes = [int(obj_start[o + 1] - obj_start[o]) for o in inst_obj]
+    inst_start = np.zeros(Nk + 1, dtype=np.int32)
+    inst_start[1:] = np.cumsum(sizes)
+    n_pts = int(inst_start[-1])                # = n_fg without copies
     nbytes = ctypes.c_size_t()
-    _lib.check(L.dh_reproject_footprints_workspace_bytes(res, n_fg, K, Mk, int(footprints), ctypes.byref(nbytes)),
-               "dh_reproject_footprints_workspace_bytes")
+    if with_table:
+        _lib.check(L.dh_reproject_instances_workspace_bytes(res, n_pts, K, Mk, Nk, int(footprints), ctypes.byref(nbytes)),
+                   "dh_reproject_instances_workspace_bytes")
+    else:
+        _lib.check(L.dh_reproject_footprints_workspace_bytes(res, n_fg, K, Mk, int(footprints), ctypes.byref(nbytes)),
+                   "dh_reproject_footprints_workspace_bytes")
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     zmap = torch.empty((K, res, res), dtype=torch.float32, device=dev)
     raw = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
     clean = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
     disp = torch.empty((K, res, res), dtype=torch.float32, device=dev)
-    vis = torch.empty((K, n_fg), dtype=torch.uint8, device=dev)
-    txy = torch.empty((K, n_fg, 2), dtype=torch.int32, device=dev)
-    cap = R2 if footprints else n_fg          # rows per edit: one per target pixel with footprints, one per point without
+    vis = torch.empty((K, n_pts), dtype=torch.uint8, device=dev)
+    txy = torch.empty((K, n_pts, 2), dtype=torch.int32, device=dev)
+    cap = R2 if footprints else n_pts         # rows per edit: one per target pixel with footprints, one per point without
     corr = torch.empty((K, cap, 4), dtype=torch.int64, device=dev)
     counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
-    rows = _similarity_rows([tfs[m] for tfs in edits for m in kept])      # edit-major, K x Mk rows (C-contiguous)
-    _lib.check(L.dh_reproject_footprint_edits(
-        _lib.ptr(d), _lib.ptr(bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
-        _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, K,
-        rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bounds),
-        _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
-        _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st, int(footprints), 0.0 if ratio is None else ratio, cap),
-        "dh_reproject_footprint_edits")
+    rows = _similarity_rows([tfs[n] for tfs in edits for n in caller])    # edit-major, K x Nk rows (C-contiguous)
+    args = (_lib.ptr(d), _lib.ptr(bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
+            _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, K,
+            rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bounds),
+            _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
+            _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st, int(footprints), 0.0 if ratio is None else ratio, cap)
+    corr_inst = None
+    if with_table:
+        corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
+        _lib.check(L.dh_reproject_instance_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                 _lib.ptr(corr_inst)), "dh_reproject_instance_edits")
+        if caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
+            lut = torch.zeros(256, dtype=torch.uint8)          # (256 entries: the rows past the counts are not written)
+            lut[:Nk] = torch.tensor(caller, dtype=torch.uint8)
+            corr_inst = lut.to(dev)[corr_inst.long()]
+    else:
+        _lib.check(L.dh_reproject_footprint_edits(*args), "dh_reproject_footprint_edits")
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
     out = []
     for e in range(K):
         n = int(counts_h[e, 0])
-        out.append((disp[e][None, None].to(out_dev), corr[e, :n] if device_correspondences else corr[e, :n].cpu()))
+        item = (disp[e][None, None].to(out_dev), corr[e, :n] if device_correspondences else corr[e, :n].cpu())
+        if return_instances:
+            item += (corr_inst[e, :n] if device_correspondences else corr_inst[e, :n].cpu(),)
+        out.append(item)
     if return_debug:
         dbg = dict(zmap=zmap, raw_mask=raw, clean_mask=clean, vis=vis, target_xy=txy, counts=counts_h,
                    fg_pix=fg_pix[:n_fg], corr_dev=corr, obj_start=obj_start)
+        if with_table:
+            dbg.update(corr_inst=corr_inst, inst_start=inst_start)
         return out, dbg
     return out
 

@@ -148,39 +148,58 @@ class DiffusionHandles:
                                                                             bg_weight, **lock))
         return imgs, [d for d, _ in edits]
 
-    def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences):
-        from .depth_transform import reproject_object_edits
+    def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences,
+                           instances=None):
+        """instances given: every result is (disparity, correspondences, instance of every row)."""
+        from .depth_transform import check_instances, reproject_instance_edits
         fp = self._footprints(what)
         if self.conf.depth_transform_mode != "pc":
+            if instances is not None:
+                raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no copies of an "
+                                          "object (instances; only 'pc')")
             raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no multi-object "
                                       "re-projection (only 'pc')")
+        inst = check_instances(instances, len(fg_masks), f"{what}: instances")
+        n_bodies, body = (len(fg_masks), "object") if inst is None else (len(inst), "instance")
         Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
         dflt = lambda v, d: d if v is None else v
-        if any(len(tfs) != len(fg_masks) for tfs in edits):          # (reproject_object_edits names the edit)
+        if any(len(tfs) != n_bodies for tfs in edits):          # (reproject_object_edits names the edit)
             defaulted = edits
         else:
             from .depth_transform import check_transform
             defaulted = []
             for e, tfs in enumerate(edits):
-                full = [check_transform(tf, f"{what}: edit {e}, object {m}") for m, tf in enumerate(tfs)]
+                full = [check_transform(tf, f"{what}: edit {e}, {body} {m}") for m, tf in enumerate(tfs)]
                 defaulted.append([(dflt(a, 0.0), dflt(ax, Y), dflt(tr, torch.zeros(3)), sc, pv) for a, ax, tr, sc, pv in full])
         edits = defaulted
-        return reproject_object_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
-                                      use_input_depth_normalization, device_correspondences=device_correspondences, **fp)
+        return reproject_instance_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
+                                        inst, use_input_depth_normalization, device_correspondences=device_correspondences, **fp,
+                                        return_instances=inst is not None)
 
     @staticmethod
-    def _object_labels(fg_masks, object_weights):
-        """Host checks of object_weights against the M masks (ValueError, before any launch) and the label image the
-        guidance needs; (None, None) for None: the unweighted path."""
+    def _object_labels(fg_masks, object_weights, instances=None, what="instances"):
+        """Host checks of object_weights against the M masks -- with an instance table, against its N instances (and of the
+        table itself) -- (ValueError, before any launch) and the label image the guidance needs; (None, None) for no weights:
+        the unweighted path.  With an instance table there is no label image: the re-projection's per-row instances say which
+        object of the energy a correspondence belongs to."""
+        n = len(fg_masks)
+        if instances is not None:
+            from .depth_transform import check_instances
+            n = len(check_instances(instances, len(fg_masks), what))
         if object_weights is None:
             return None, None
         from .losses import check_object_weights, object_label_image
-        weights = check_object_weights(object_weights, len(fg_masks))
-        return object_label_image(fg_masks), weights
+        try:
+            weights = check_object_weights(object_weights, n)
+        except ValueError as err:
+            if instances is None:
+                raise
+            raise ValueError(f"{what}: {err} (one weight per instance)") from None
+        return (object_label_image(fg_masks) if instances is None else None), weights
 
     def transform_foreground_objects(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                      transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                     object_weights=None, release_mask=None):
+                                     object_weights=None, instances=None, release_mask=None):
         """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
         rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.  Each object
@@ -191,14 +210,21 @@ class DiffusionHandles:
         objects without a visible correspondence drop out and the rest are renormalised (DESIGN.md "A weight per object";
         default configuration only).  Returns what transform_foreground returns.  'pc' re-projection only.  release_mask (conf
         background_lock only): a res x res image, non-zero = extra area the lock sets free beside the masks and the
-        correspondences, such as the shadow an object leaves behind."""
-        labels, object_weights = self._object_labels(fg_masks, object_weights)
-        lk = self._lock_setup("transform_foreground_objects", activations, depth, release_mask)
+        correspondences, such as the shadow an object leaves behind.
+        instances (copies of an object; DESIGN.md "Object copies"): None, or N mask indices (M <= N <= 8, every mask named) --
+        the edit places N instances, instance n the object of mask instances[n] under transforms[n] (N transforms); a mask
+        named twice appears twice.  object_weights then has N entries and "equal" holds every instance equally.  ValueError
+        naming the instance for a bad table, before any device work."""
+        what = "transform_foreground_objects"
+        labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
+        lk = self._lock_setup(what, activations, depth, release_mask)
         with torch.no_grad():
-            (edited_disparity, correspondences), = self._reproject_objects(
-                "transform_foreground_objects", depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False)
+            (edited_disparity, correspondences, *rows), = self._reproject_objects(
+                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances)
             self.last_keep_maps = []
             lock = {} if lk is None else dict(lock=self._edit_lock(lk, fg_masks, correspondences, depth))
+            if rows:
+                lock["pair_instances"] = rows[0]
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
@@ -211,25 +237,30 @@ class DiffusionHandles:
 
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                           object_weights=None, streams=1, batch=None, release_mask=None):
+                                           object_weights=None, streams=1, batch=None, instances=None, release_mask=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
         edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
         pivot).  Returns (images [K,3,H,W], [K disparities]) as
         transform_foreground_batch does.  object_weights: as in transform_foreground_objects, one list for all K edits.
         streams / batch: transform_foreground_batch's -- chunks of `batch` edits (default ceil(K / streams)) on `streams`
         lanes, batch = 1 runs single edits on the lanes; images are bit-identical to the one-stream result at the same batch.
-        release_mask: transform_foreground_objects', one for all K edits."""
-        labels, object_weights = self._object_labels(fg_masks, object_weights)
-        lk = self._lock_setup("transform_foreground_objects_batch", activations, depth, release_mask)
+        release_mask: transform_foreground_objects', one for all K edits.  instances: transform_foreground_objects', one table
+        for all K edits (the edits are then K lists of N transforms)."""
+        what = "transform_foreground_objects_batch"
+        labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
+        lk = self._lock_setup(what, activations, depth, release_mask)
         K = len(edits)
         with torch.no_grad():
-            res = self._reproject_objects("transform_foreground_objects_batch", depth, bg_depth, fg_masks, edits,
-                                          use_input_depth_normalization, True)
+            res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, instances)
+            rows = [r[2] for r in res] if instances is not None else None
+            res = [r[:2] for r in res]
             per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
             obj = dict(object_labels=labels, object_weights=object_weights)
             self.last_keep_maps = []
             if lk is not None:
                 obj["lock"] = [self._edit_lock(lk, fg_masks, c, depth) for _, c in res]
+            if rows is not None:          # per edit; the chunked call takes one list per chunk
+                obj["pair_instances"] = rows if streams <= 1 and per >= K or per <= 1 else [rows[i:i + per] for i in range(0, K, per)]
             if streams <= 1 and per >= K:
                 imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
                                                             [c for _, c in res], fg_weight, bg_weight, **obj)
@@ -250,7 +281,8 @@ class DiffusionHandles:
         transform_foreground (EDIT_FIELDS, rot_angle / rot_axis / translation / scale / pivot, optional fg_weight / bg_weight)
         -- or, for an edit that moves several objects (transform_foreground_objects), `fg_masks` (M masks) in place of fg_mask,
         `transforms` (M triples (rot_angle, rot_axis, translation) or 5-tuples (.., scale, pivot), None members defaulted) in
-        place of rot_angle / rot_axis / translation / scale / pivot, and optionally `object_weights`.  An edit with both forms
+        place of rot_angle / rot_axis / translation / scale / pivot, and optionally `object_weights` and `instances` (copies of an
+        object, transform_foreground_objects: N mask indices; `transforms` and the weights are then N long).  An edit with both forms
         or with neither, with a `transforms` list that is not M long, or with a malformed transform (check_transform) raises
         ValueError naming the edit, before any device work.  Edits that name the same image (the same depth, mask,
         background-depth and activation tensors) are re-projected together, once per image (multi-object edits: one label
@@ -258,7 +290,7 @@ class DiffusionHandles:
         Returns (images [K,3,H,W], [K disparities]) in input order.  'pc' re-projection only; one resolution; needs an engine
         with max_batch >= 2K.  With conf background_lock every edit is locked to its own image's reconstruction; an edit may
         carry a `release_mask` (transform_foreground_objects)."""
-        from .depth_transform import check_transform, reproject_edits
+        from .depth_transform import check_instances, check_transform, reproject_edits
         fp = self._footprints("transform_foregrounds")
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
@@ -268,7 +300,7 @@ class DiffusionHandles:
         if K < 1 or any(set(common) - set(e) for e in edits):
             raise ValueError(f"transform_foregrounds: needs at least one edit, each with {self.EDIT_FIELDS}")
         single_keys = ("fg_mask", "rot_angle", "rot_axis", "translation", "scale", "pivot")
-        multi_keys = ("fg_masks", "transforms", "object_weights")
+        multi_keys = ("fg_masks", "transforms", "object_weights", "instances")
         weights = [None] * K
         for i, e in enumerate(edits):
             single = any(e.get(k) is not None for k in single_keys)
@@ -282,15 +314,17 @@ class DiffusionHandles:
                 masks, tfs = e.get("fg_masks"), e.get("transforms")
                 if not isinstance(masks, (list, tuple)) or len(masks) < 1:
                     raise ValueError(f"transform_foregrounds: edit {i}: fg_masks must be a non-empty list of masks")
-                if tfs is None or len(tfs) != len(masks):
+                inst = check_instances(e.get("instances"), len(masks), f"transform_foregrounds: edit {i}: instances")
+                n_bodies, body = (len(masks), "masks") if inst is None else (len(inst), "instances")
+                if tfs is None or len(tfs) != n_bodies:
                     raise ValueError(f"transform_foregrounds: edit {i} has {0 if tfs is None else len(tfs)} transforms for "
-                                     f"{len(masks)} masks")
+                                     f"{n_bodies} {body}")
                 for m, tf in enumerate(tfs):
-                    check_transform(tf, f"transform_foregrounds: edit {i}, object {m}")
+                    check_transform(tf, f"transform_foregrounds: edit {i}, {'object' if inst is None else 'instance'} {m}")
                 if e.get("object_weights") is not None:
                     from .losses import check_object_weights
                     try:
-                        weights[i] = check_object_weights(e["object_weights"], len(masks))
+                        weights[i] = check_object_weights(e["object_weights"], n_bodies)
                     except ValueError as err:
                         raise ValueError(f"transform_foregrounds: edit {i}: {err}") from None
             else:
@@ -311,15 +345,22 @@ class DiffusionHandles:
         for i, e in enumerate(edits):
             masks = tuple(id(m) for m in e["fg_masks"]) if e.get("fg_masks") is not None else (id(e["fg_mask"]),)
             key = (id(e["depth"]), e.get("fg_masks") is not None) + masks + (id(e["bg_depth"]),) + tuple(id(a) for a in e["activations"])
+            if e.get("instances") is not None:          # one instance table per re-projection call
+                key += ("instances",) + tuple(int(o) for o in e["instances"])
             groups.setdefault(key, []).append(i)
-        reproj, labels = [None] * K, [None] * K
+        reproj, labels, rows = [None] * K, [None] * K, [None] * K
         with torch.no_grad():
             for idx in groups.values():
                 e0 = edits[idx[0]]
                 if e0.get("fg_masks") is not None:
                     res = self._reproject_objects("transform_foregrounds", e0["depth"], e0["bg_depth"], list(e0["fg_masks"]),
-                                                  [list(edits[i]["transforms"]) for i in idx], use_input_depth_normalization, True)
-                    if any(weights[i] is not None for i in idx):
+                                                  [list(edits[i]["transforms"]) for i in idx], use_input_depth_normalization, True,
+                                                  e0.get("instances"))
+                    if e0.get("instances") is not None:          # the rows' instances stand in for the label image
+                        for i, r in zip(idx, res):
+                            rows[i] = r[2]
+                        res = [r[:2] for r in res]
+                    elif any(weights[i] is not None for i in idx):
                         from .losses import object_label_image
                         label = object_label_image(list(e0["fg_masks"]))          # once per group
                         for i in idx:
@@ -336,7 +377,7 @@ class DiffusionHandles:
             self.last_keep_maps = []
             items = [dict(latents=e["init_noise"], depth=d, uncond_embeddings=e["null_text_emb"], prompt=e["prompt"],
                           activations_orig=e["activations"], correspondences=c, object_labels=labels[i], object_weights=weights[i],
-                          lock=self._edit_lock(lks[i], e["fg_masks"] if e.get("fg_masks") is not None else e["fg_mask"], c,
+                          pair_instances=rows[i], lock=self._edit_lock(lks[i], e["fg_masks"] if e.get("fg_masks") is not None else e["fg_mask"], c,
                                                e["depth"]))
                      for i, (e, (d, c)) in enumerate(zip(edits, reproj))]
             imgs = self.diffuser.guided_inference_items(items, [e.get("fg_weight") for e in edits],

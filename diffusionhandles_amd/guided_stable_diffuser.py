@@ -458,9 +458,11 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return [(_bl.Activations([a.permute(0, 3, 1, 2) for a in store[b]], trajectory=traj[:, b].permute(0, 3, 1, 2)),
                  x[b:b + 1].permute(0, 3, 1, 2), uncs[b], inits[b]) for b in range(K)]
 
-    def _check_object_weights(self, object_labels, object_weights, activations_orig):
+    def _check_object_weights(self, object_labels, object_weights, activations_orig, pair_instances=None):
         """Host checks of prepare_guidance's object weights, before any device work: labels present, default configuration."""
-        if object_labels is None:
+        if object_labels is not None and pair_instances is not None:
+            raise ValueError("object_labels and pair_instances are mutually exclusive")
+        if object_labels is None and pair_instances is None:
             raise ValueError("object_weights need object_labels (the label image of the object masks)")
         if self.conf.fg_patch_size != 1:
             raise NotImplementedError(f"object_weights with fg_patch_size = {self.conf.fg_patch_size} (only 1: the weighted "
@@ -477,7 +479,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
         _check_object_weights(object_weights, n)
 
     def prepare_guidance(self, depth, prompt, activations_orig, correspondences, fg_weight=None, bg_weight=None, orig=None,
-                         cond=None, object_labels=None, object_weights=None, lock=None):
+                         cond=None, object_labels=None, object_weights=None, pair_instances=None, lock=None):
         """Everything of guided_inference that is constant over the denoising loop.  `lock` (background lock): (keep [s,s],
         trajectory [T,4,s,s]) -- the keep map of this edit (background_lock.keep_map) and the reconstruction trajectory of its
         image (activations.trajectory) -- or a prepared background_lock.Lock (edits of one image share the channels-last copy
@@ -487,10 +489,15 @@ class GuidedStableDiffuser(GuidedDiffuser):
         prompt embedding when the caller already has it (lanes: the text tower is not run concurrently with itself).
         object_labels / object_weights (multi-object edits): the label image of the object masks (losses.object_label_image)
         and "equal" or one weight per object -- the foreground term then weighs the objects by omega_m instead of by their
-        pair counts (DESIGN.md "A weight per object").  None: the area weighting, on the unchanged path."""
+        pair counts (DESIGN.md "A weight per object").  None: the area weighting, on the unchanged path.
+        pair_instances (edits with copies of an object): the instance of every correspondence row, uint8 [N], IN PLACE OF the
+        label image (giving both is a ValueError) -- an object of the energy is then an instance, object_weights has one entry
+        per instance."""
         from types import SimpleNamespace
+        if object_labels is not None and pair_instances is not None:
+            raise ValueError("object_labels and pair_instances are mutually exclusive")
         if object_weights is not None:
-            self._check_object_weights(object_labels, object_weights, activations_orig)
+            self._check_object_weights(object_labels, object_weights, activations_orig, pair_instances)
         fg_weight = self.conf.fg_weight if fg_weight is None else fg_weight
         bg_weight = self.conf.bg_weight if bg_weight is None else bg_weight
         st = SimpleNamespace()
@@ -498,7 +505,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
             st.pc = self.process_correspondences(correspondences, img_res=depth.shape[-1], bg_erosion=self.conf.bg_erosion)
         else:
             st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
-                                             device=self.device, object_labels=object_labels)
+                                             device=self.device, object_labels=object_labels, pair_instances=pair_instances)
         st.depth_nhwc = _nhwc(self.init_depth(depth.to(self.device, torch.float32))) if self.conf.use_depth else None
         st.cond = self._encode([prompt]).contiguous() if cond is None else cond
         GuidedStableDiffuser._text_keys += 1
@@ -716,14 +723,17 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def _batch_edit_steps(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                           fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None,
-                          object_weights=None, lock=None):
+                          object_weights=None, pair_instances=None, lock=None):
         """The batched edit as a generator: yields after the preparation and after every denoising step (everything is only
         ENQUEUED on the current stream by then), returns the final latents [K,4,H,W] through StopIteration.  One body for the
         one-stream call below and for the lanes of guided_inference_batch_lanes.  fg_weight / bg_weight: one value, or one per
         edit.  status_out: a list that receives the device [K, 4] status ('auto') at the end.  object_labels / object_weights: one
         label image and one weight list for all K edits (prepare_guidance).  lock: one (keep, trajectory) for all K edits or a list
-        of K (prepare_guidance; None entries are unlocked edits)."""
+        of K (prepare_guidance; None entries are unlocked edits).  pair_instances: None or a list of K, the instances of every
+        edit's correspondence rows (prepare_guidance)."""
         K = len(depths)
+        if pair_instances is not None and len(pair_instances) != K:
+            raise ValueError(f"guided_inference_batch: pair_instances has {len(pair_instances)} entries for {K} edits")
         per = lambda w, i: w[i] if isinstance(w, (list, tuple)) else w
         if self.unet.max_batch < 2 * K:
             raise RuntimeError(f"engine max_batch {self.unet.max_batch} < 2*K = {2 * K}")
@@ -735,7 +745,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         for i, (d, c) in enumerate(zip(depths, correspondences_list)):
             sts.append(self.prepare_guidance(d, prompt, activations_orig, c, per(fg_weight, i), per(bg_weight, i),
                                              orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond,
-                                             object_labels=object_labels, object_weights=object_weights, lock=locks[i]))
+                                             object_labels=object_labels, object_weights=object_weights, lock=locks[i],
+                                             pair_instances=None if pair_instances is None else pair_instances[i]))
         x = _nhwc(latents.to(self.device, torch.float32)).expand(K, -1, -1, -1).contiguous()
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -746,17 +757,19 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_batch(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
-                               fg_weight=None, bg_weight=None, object_labels=None, object_weights=None, lock=None):
+                               fg_weight=None, bg_weight=None, object_labels=None, object_weights=None,
+                               pair_instances=None, lock=None):
         """K edits of one image at once.  depths: list of K edited disparities [1,1,H,W]; correspondences_list:
         K [N_k,4] tensors; fg_weight / bg_weight: one value or K.  Needs an engine built with max_batch >= 2K.  Returns images
         [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value.  object_labels / object_weights: one
         label image and one weight list for all K edits (prepare_guidance).  lock: the background lock, one (keep, trajectory)
-        for all K edits or a list of K (prepare_guidance)."""
+        for all K edits or a list of K (prepare_guidance).  pair_instances: None or a list of K, the instances of every edit's
+        correspondence rows, in place of the label image (prepare_guidance)."""
         status = []
         with torch.no_grad(), self.on_stream():
             gen = self._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                          fg_weight, bg_weight, status_out=status, object_labels=object_labels,
-                                         object_weights=object_weights, lock=lock)
+                                         object_weights=object_weights, lock=lock, pair_instances=pair_instances)
             try:
                 while True:
                     next(gen)
@@ -771,9 +784,9 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference_items(self, items, fg_weight=None, bg_weight=None):
         """K edits of DIFFERENT images at once.  items: K records (dicts with the keys ITEM_FIELDS, or tuples in that order), the
-        arguments of guided_inference per item, plus optional object_labels / object_weights (prepare_guidance: a multi-object
-        edit with a weight per object) and an optional lock ((keep, trajectory), prepare_guidance: locked and unlocked items may
-        share a batch); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
+        arguments of guided_inference per item, plus optional object_labels (or pair_instances: an edit with copies) /
+        object_weights (prepare_guidance: a multi-object edit with a weight per object) and an optional lock ((keep,
+        trajectory), prepare_guidance: locked and unlocked items may share a batch); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
         tensors share one channels-last copy of them, items with the same prompt one encoding.  One resolution (the
         engine's); needs max_batch >= 2K and max_diff_batch >= K, raises otherwise (never splits).  Returns images [K,3,H,W]
         in item order and sets last_latents; 'auto' grad_scale: FloatingPointError naming the items that met a non-finite
@@ -805,7 +818,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 st = self.prepare_guidance(it["depth"], it["prompt"], it["activations_orig"], it["correspondences"],
                                            per(fg_weight, i), per(bg_weight, i), orig=origs.get(okey), cond=conds.get(it["prompt"]),
                                            object_labels=it.get("object_labels"), object_weights=it.get("object_weights"),
-                                           lock=locks[i])
+                                           lock=locks[i], pair_instances=it.get("pair_instances"))
                 origs[okey], conds[it["prompt"]] = st.orig, st.cond
                 sts.append(st)
             x = torch.cat([_nhwc(it["latents"].to(self.device, torch.float32)) for it in items]).contiguous()
@@ -910,13 +923,17 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return results
 
     def guided_inference_batch_lanes(self, latents, chunks, uncond_embeddings, prompt, activations_orig, streams=2,
-                                     fg_weight=None, bg_weight=None, object_labels=None, object_weights=None, lock=None):
+                                     fg_weight=None, bg_weight=None, object_labels=None, object_weights=None,
+                                     pair_instances=None, lock=None):
         """Batched edits of one image on `streams` concurrent lanes.  chunks: list of (depths, correspondences_list), each the
         argument pair of one guided_inference_batch call; chunk i runs on lane i % streams.  Every lane executes exactly the
         passes the one-stream call executes for its chunk (same batch, same kernels, private arenas), so the images are
         bit-identical to guided_inference_batch chunk by chunk.  Returns one image tensor [K_i,3,H,W] per chunk.
         object_labels / object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one
-        (keep, trajectory) for every edit, or a list with one entry per edit over the chunks in order."""
+        (keep, trajectory) for every edit, or a list with one entry per edit over the chunks in order.  pair_instances: None or
+        one list per chunk (guided_inference_batch)."""
+        if pair_instances is not None and len(pair_instances) != len(chunks):
+            raise ValueError(f"guided_inference_batch_lanes: pair_instances has {len(pair_instances)} entries for {len(chunks)} chunks")
         kmax = max(len(d) for d, _ in chunks)
         if self.unet.max_batch < 2 * kmax:
             # lane 0 is THIS diffuser: it could not run its chunk, and forks sized 2 * kmax would be made for nothing
@@ -930,17 +947,18 @@ class GuidedStableDiffuser(GuidedDiffuser):
             offs = np.cumsum([0] + [len(d) for d, _ in chunks])
             locks = self._locks(lock, int(offs[-1]), "guided_inference_batch_lanes")
 
-            def make(depths, corrs, status, lk):
+            def make(depths, corrs, status, lk, inst):
                 def job(lane):
                     def body():
                         lat = yield from lane._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig,
                                                                 corrs, fg_weight, bg_weight, cond=cond, orig=orig,
                                                                 status_out=status, object_labels=object_labels,
-                                                                object_weights=object_weights, lock=lk)
+                                                                object_weights=object_weights, lock=lk, pair_instances=inst)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
-            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, locks[int(offs[i]):int(offs[i + 1])])
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, locks[int(offs[i]):int(offs[i + 1])],
+                                                                 None if pair_instances is None else pair_instances[i])
                                                             for i, ((d, c), s) in enumerate(zip(chunks, statuses))])
             if any(statuses):      # edits numbered over the chunks in order; read after every lane has finished
                 self.raise_on_status([(int(offs[i]) + b, row) for i, s in enumerate(statuses)
@@ -948,14 +966,16 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return images
 
     def _edit_steps(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences, fg_weight=None,
-                    bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None, object_weights=None, lock=None):
+                    bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None, object_weights=None,
+                    pair_instances=None, lock=None):
         """One edit as a generator (see _batch_edit_steps): yields after the preparation and after every denoising step,
         returns the final latents [1,4,H,W].  lock: the edit's background lock (prepare_guidance)."""
         torch.manual_seed(self.conf.seed)
         self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
         timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
         st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight, orig=orig, cond=cond,
-                                   object_labels=object_labels, object_weights=object_weights, lock=lock)
+                                   object_labels=object_labels, object_weights=object_weights, lock=lock,
+                                   pair_instances=pair_instances)
         x = _nhwc(latents.to(self.device, torch.float32))
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -966,12 +986,15 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_lanes(self, latents, edits, uncond_embeddings, prompt, activations_orig, streams=2, fg_weight=None,
-                               bg_weight=None, object_labels=None, object_weights=None, lock=None):
+                               bg_weight=None, object_labels=None, object_weights=None, pair_instances=None, lock=None):
         """Single (B = 1) edits of one image on `streams` concurrent lanes.  edits: list of (depth, correspondences), the
         argument pair of guided_inference; edit i runs on lane i % streams with exactly the passes guided_inference runs, so
         the images are bit-identical to the one-stream calls.  Returns a list of images [1,3,H,W].  object_labels /
         object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one (keep, trajectory)
-        for every edit, or a list with one entry per edit."""
+        for every edit, or a list with one entry per edit.  pair_instances: None or a list with one entry per edit
+        (prepare_guidance)."""
+        if pair_instances is not None and len(pair_instances) != len(edits):
+            raise ValueError(f"guided_inference_lanes: pair_instances has {len(pair_instances)} entries for {len(edits)} edits")
         lanes = self.lanes(min(int(streams), len(edits)))
         statuses = [[] for _ in edits]
         with torch.no_grad(), self.on_stream():
@@ -979,24 +1002,28 @@ class GuidedStableDiffuser(GuidedDiffuser):
             orig = [a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in activations_orig]
             locks = self._locks(lock, len(edits), "guided_inference_lanes")      # (on this stream, which every lane waits for)
 
-            def make(depth, corr, status, lk):
+            def make(depth, corr, status, lk, inst):
                 def job(lane):
                     def body():
                         lat = yield from lane._edit_steps(latents, depth, uncond_embeddings, prompt, activations_orig, corr,
                                                           fg_weight, bg_weight, cond=cond, orig=orig, status_out=status,
-                                                          object_labels=object_labels, object_weights=object_weights, lock=lk)
+                                                          object_labels=object_labels, object_weights=object_weights, lock=lk,
+                                                          pair_instances=inst)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
-            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, lk) for (d, c), s, lk in zip(edits, statuses, locks)])
+            insts = [None] * len(edits) if pair_instances is None else pair_instances
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, lk, n)
+                                                            for (d, c), s, lk, n in zip(edits, statuses, locks, insts)])
             if any(statuses):      # read after every lane has finished
                 self.raise_on_status([(i, s[0][0].cpu().tolist()) for i, s in enumerate(statuses)])
         return images
 
     def guided_inference(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences,
                          fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None, object_labels=None,
-                         object_weights=None, lock=None):
-        """object_labels / object_weights: a weight per object for the foreground term (prepare_guidance).  lock: (keep,
+                         object_weights=None, pair_instances=None, lock=None):
+        """object_labels (or pair_instances, the instance of every correspondence row of an edit with copies) / object_weights:
+        a weight per object for the foreground term (prepare_guidance).  lock: (keep,
         trajectory), the background lock -- after every DDIM step the latents are blended with the reconstruction's outside
         the edit's region (prepare_guidance; DESIGN.md "Background lock")."""
         with torch.no_grad(), self.on_stream():
@@ -1004,7 +1031,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
             self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
             timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
             st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight,
-                                       object_labels=object_labels, object_weights=object_weights, lock=lock)
+                                       object_labels=object_labels, object_weights=object_weights, lock=lock,
+                                       pair_instances=pair_instances)
             denoising_steps = {"opt": [], "post-opt": []} if save_denoising_steps else None
             x = _nhwc(latents.to(self.device, torch.float32))
             for t_idx, t in enumerate(timesteps):

@@ -77,10 +77,23 @@ def object_omegas(objects, weights):
     return counts, omega
 
 
-def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, object_labels=None):
+def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, object_labels=None,
+                            pair_instances=None):
     """[N,4] int64 (ox,oy,tx,ty) -> dict with original_x/y, transformed_x/y, background_x/y[_orig|_trans].
     object_labels ([H, W] uint8, object_label_image): adds "object", the 0-based object of every kept pair (int64, host), and
-    `pair_obj` (uint8, device) to device_lists."""
+    `pair_obj` (uint8, device) to device_lists.
+    pair_instances ([N] uint8, the instance of every correspondence row -- edits with copies of an object, where a source pixel
+    belongs to several instances and a label image cannot say which): filtered with the validity test of the rows, it fills the
+    same "object" / `pair_obj`; an "object" of the energy is then an instance.  ValueError when both are given or when it does
+    not have N entries, before any device work."""
+    if object_labels is not None and pair_instances is not None:
+        raise ValueError("process_correspondences: object_labels and pair_instances are mutually exclusive")
+    if pair_instances is not None:
+        n_rows = int(torch.as_tensor(correspondences).reshape(-1, 4).shape[0])
+        pair_instances = torch.as_tensor(pair_instances).reshape(-1)
+        if pair_instances.numel() != n_rows:
+            raise ValueError(f"process_correspondences: pair_instances has {pair_instances.numel()} entries for {n_rows} "
+                             f"correspondences")
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     L = _lib.lib()
@@ -124,6 +137,13 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
             raise ValueError("object labels: a correspondence starts outside every object mask")
         out["object"] = oh
         out.device_lists["pair_obj"] = obj.to(torch.uint8).contiguous()
+    if pair_instances is not None:
+        ok = (corr[:, 2] >= 0) & (corr[:, 2] < img_res) & (corr[:, 3] >= 0) & (corr[:, 3] < img_res)      # k_valid's test
+        obj = pair_instances.to(dev)[ok].to(torch.uint8).contiguous()
+        if obj.shape[0] != ph.shape[0]:
+            raise RuntimeError("pair instances: the kept correspondences do not match the cell pairs")
+        out["object"] = obj.cpu().numpy().astype(np.int64)
+        out.device_lists["pair_obj"] = obj
     return out
 
 

@@ -435,9 +435,35 @@ def load_image(path):
 MAX_SCENE_OBJECTS = 8          # losses.MAX_OBJECTS
 
 
+def entry_instances(objects, n_masks=None, where="objects"):
+    """The instance table of an "objects" list (copies of an object): None when no member carries "mask" (member n is then
+    the object of mask n, as always), else one mask index per member -- its "mask": m, or its own position when it has none.
+    ValueError naming `where` and the member for a "mask" that is not an integer >= 0 and, when n_masks is given, for more
+    than 8 members, an index outside 0..n_masks-1 or a mask that no member draws."""
+    if not any(isinstance(o, dict) and "mask" in o for o in objects):
+        return None
+    inst = []
+    for n, o in enumerate(objects):
+        m = o.get("mask", n) if isinstance(o, dict) else n
+        if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+            raise ValueError(f"{where}, object {n}: \"mask\" must be the index of a mask (an integer >= 0), got {m!r}")
+        inst.append(m)
+    if n_masks is not None:
+        if len(inst) > MAX_SCENE_OBJECTS:
+            raise ValueError(f"{where} lists {len(inst)} instances, at most {MAX_SCENE_OBJECTS} are supported")
+        for n, m in enumerate(inst):
+            if m >= n_masks:
+                raise ValueError(f"{where}, object {n}: mask {m} does not exist, the scene has {n_masks} object masks")
+        for m in range(n_masks):
+            if m not in inst:
+                raise ValueError(f"{where}: no object draws mask {m} (removing an object is not supported)")
+    return inst
+
+
 def _check_object_entries(scene_dir, transforms, n_masks):
     """transforms.json against the scene's masks: a multi-mask scene (n_masks >= 1 mask_m.png files) wants {"objects": [n_masks
-    entries]} everywhere, a single-mask scene (n_masks = 0) no "objects" at all.  ValueError naming the scene and the entry."""
+    entries]} everywhere -- or, when members carry "mask" (copies of an object, entry_instances), n_masks to 8 entries that
+    draw every mask -- a single-mask scene (n_masks = 0) no "objects" at all.  ValueError naming the scene and the entry."""
     for name, t in transforms.items():
         has = isinstance(t, dict) and "objects" in t
         if n_masks == 0:
@@ -447,6 +473,12 @@ def _check_object_entries(scene_dir, transforms, n_masks):
         if not has:
             raise ValueError(f"{scene_dir}: transform {name!r} has no \"objects\" list but the scene has {n_masks} object masks "
                              "(mask_0.png ...)")
+        if isinstance(t["objects"], (list, tuple)) and \
+                entry_instances(t["objects"], n_masks, f"{scene_dir}: transform {name!r}") is not None:
+            w = t.get("object_weights")
+            if isinstance(w, (list, tuple)) and len(w) != len(t["objects"]):
+                raise ValueError(f"{scene_dir}: transform {name!r} has {len(w)} object_weights for {len(t['objects'])} instances")
+            continue
         if not isinstance(t["objects"], (list, tuple)) or len(t["objects"]) != n_masks:
             n = len(t["objects"]) if isinstance(t["objects"], (list, tuple)) else "no"
             raise ValueError(f"{scene_dir}: transform {name!r} lists {n} objects, the scene has {n_masks} object masks")
@@ -498,7 +530,11 @@ def load_scene_geometry(scene_dir, img_res=512):
     (optional)} (object_transform_args).  The dict then also has fg_masks, the list of the M masks, and fg_mask is their union.
     An ordinary entry may also carry "scale" (a positive number, or 3 along the camera axes) and "pivot" (3 numbers, a point in
     the coordinates of depth_to_world_coords) (not in the reference; transform_args); malformed values raise ValueError naming
-    the scene and the entry here, when the scene is loaded."""
+    the scene and the entry here, when the scene is loaded.
+    A member of "objects" may carry "mask": m (not in the reference; copies of an object): it is then one more INSTANCE of mask
+    m, and the list may be longer than the number of masks (at most 8, every mask drawn by some member; members without "mask"
+    keep their own position's mask).  "object_weights" then has one entry per member.  Lists without any "mask" give exactly
+    what they gave before."""
     import torch
     j = os.path.join
     with open(j(scene_dir, "transforms.json")) as f:
@@ -581,7 +617,8 @@ def object_transform_args(entry):
     """One transforms.json entry of a multi-object scene, {"objects": [t_0 .. t_{M-1}], "object_weights": "equal" | [w ..]} ->
     the `transforms` / `object_weights` keyword arguments of `transform_foreground_objects`: M (rot_angle, rot_axis,
     translation) triples in mask order (`{}` leaves an object in place) and None, "equal" or a list of floats.  An object
-    whose entry has "scale" or "pivot" gives the 5-tuple (rot_angle, rot_axis, translation, scale, pivot) instead."""
+    whose entry has "scale" or "pivot" gives the 5-tuple (rot_angle, rot_axis, translation, scale, pivot) instead.  When a
+    member carries "mask" (entry_instances) the dict also has `instances`, the mask index of every member."""
     if not isinstance(entry, dict) or "objects" not in entry:
         raise ValueError("object_transform_args: the entry has no \"objects\" list")
     triples = []
@@ -592,4 +629,5 @@ def object_transform_args(entry):
     w = entry.get("object_weights")
     if w is not None and not isinstance(w, str):
         w = [float(v) for v in w]
-    return dict(transforms=triples, object_weights=w)
+    inst = entry_instances(entry["objects"], None, "object_transform_args")
+    return dict(transforms=triples, object_weights=w, **({} if inst is None else dict(instances=inst)))

@@ -135,6 +135,33 @@ int dh_reproject_footprint_edits(const float* depth, const float* bg_depth, cons
                                  uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
                                  void* workspace, size_t workspace_bytes, void* stream,
                                  int footprints, float max_ratio, int corr_capacity);
+/* Copies of an object (not in the reference; DESIGN.md, "Object copies"): dh_reproject_footprint_edits with n_instances
+ * INSTANCES per edit in place of one body per mask.  Instance n draws the points of mask inst_obj[n] (host array, values in
+ * 0 .. n_objects - 1, every mask named at least once, n_objects <= n_instances <= 8) with row e * n_instances + n of xforms_host,
+ * about the centroid of THAT MASK's points (computed once per mask) or the row's pivot.
+ *   point list     background, instance 0's points (row-major), instance 1's, ...: n_pts = sum over n of |mask inst_obj[n]|
+ *                  foreground points, which may exceed n_fg; ONE z-buffer, winner = min (z, point index): equal depths go to the
+ *                  earlier instance, so two instances with one mask and one transform give the one-instance outputs
+ *   vis, target_xy n_pts entries per edit, by point-list position
+ *   corr           point-list order without footprints (a source pixel once per visible, kept instance), capacity >= n_pts;
+ *                  with footprints as there (triangles between neighbouring points of ONE INSTANCE, bidder index = res * res +
+ *                  point-list position), capacity >= res * res
+ *   corr_inst      uint8, corr_capacity per edit, may be null: the instance n of every corr row
+ * Refused (DH_ERR_ARG before any launch, outputs untouched): n_instances outside 1 .. 8, an inst_obj entry outside
+ * 0 .. n_objects - 1, a mask without an instance, res * res + n_pts beyond INT_MAX, and what dh_reproject_footprint_edits refuses
+ * (the row checks on all n_edits * n_instances rows).  The workspace is dh_reproject_instances_workspace_bytes' (n_pts as above).
+ * dh_reproject_footprint_edits is the identity-table call of this entry (inst_obj[n] = n, corr_inst null) on its own workspace. */
+int dh_reproject_instances_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances, int footprints,
+                                           size_t* bytes);
+int dh_reproject_instance_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                                int n_edits, const double* xforms_host, const float* bounds,
+                                float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                                uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                                void* workspace, size_t workspace_bytes, void* stream,
+                                int footprints, float max_ratio, int corr_capacity,
+                                int n_instances, const int32_t* inst_obj, uint8_t* corr_inst);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);

@@ -6,7 +6,9 @@ DH_CALLS=n timed calls (default 5); the line reports their mean, median and mini
 DH_SCALE=s (default unset): a second line times the same call with the uniform scale s on every object (5-tuples).
 DH_FOOTPRINTS=1 (default unset; combinable with DH_SCALE / DH_OBJECTS): every timed call is followed by the same call with
 footprint splatting on (profiles/footprints/).  DH_STEP=1: instead of the spheres, K copies of the step-scene edit of
-tests/footprints_ref.py with footprints on, once per tier threshold of DH_TIERS (comma-separated; 0 = the default)."""
+tests/footprints_ref.py with footprints on, once per tier threshold of DH_TIERS (comma-separated; 0 = the default).
+DH_COPIES=c (default unset; M * c <= 8): a further line times the call with c instances of every sphere (object copies: copy k
+of an object takes another of the bench transforms and is lifted by 0.4 k, so the copies do not coincide)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -87,6 +89,19 @@ if os.environ.get("DH_STEP", "0") not in ("", "0"):
 report(call, "")
 if footprints:
     report(call, "", footprints=True)
+copies = int(os.environ.get("DH_COPIES", "0") or 0)
+if copies:
+    from diffusionhandles_amd.depth_transform import reproject_instance_edits
+    if not 1 <= M * copies <= 8:
+        sys.exit("DH_COPIES: objects * copies must be 1 to 8")
+    inst = [m for m in range(M) for _ in range(copies)]
+    lift = lambda tf, k: (tf[0], tf[1], tf[2] + torch.tensor([0.0, 0.4 * k, 0.0])) + tuple(tf[3:])
+    inst_edits = [[lift(tfs[(i + 3 * m + 5 * k) % 8], k) for m in range(M) for k in range(copies)] for i in range(K)]
+    inst_masks = [mask] if M == 1 else masks
+    inst_call = lambda **kw: reproject_instance_edits(depth, bg_depth, inst_masks, intr, inst_edits, inst, **kw)
+    report(inst_call, f" copies={copies} (instances {inst})")
+    if footprints:
+        report(inst_call, f" copies={copies} (instances {inst})", footprints=True)
 if scale is not None:
     if M == 1:
         tfs = [tf + (scale, None) for tf in tfs]

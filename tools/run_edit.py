@@ -287,6 +287,11 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
         img, depth, bg_depth, mask, prompt, res = sc["img"], sc["depth"], sc["bg_depth"], sc["fg_mask"], sc["prompt"], args.res
         masks = sc.get("fg_masks")
         if masks is not None and args.mode != "pc":
+            from diffusionhandles_amd.scene_io import entry_instances
+            for n, t in sc["transforms"].items():          # (copies of an object: named for what they are)
+                if entry_instances(t["objects"]) is not None:
+                    raise NotImplementedError(f"{scene}: transform {n!r} places copies of an object (\"mask\" in its objects); "
+                                              f"--mode {args.mode} has no copies, use --mode pc")
             raise NotImplementedError(f"{scene}: a multi-object scene ({len(masks)} masks) needs --mode pc; depth_transform_mode "
                                       f"{args.mode!r} has no multi-object re-projection")
         if masks is not None:       # entries {"objects": [...], "object_weights": ...}: transforms / object_weights per edit
@@ -452,7 +457,8 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
             if prep[s].get("release") is not None:          # (--background-lock: the scene's release.png)
                 common["release_mask"] = prep[s]["release"]
             if r["fg_masks"] is not None:
-                edits.append(dict(common, fg_masks=r["fg_masks"], transforms=tf["transforms"], object_weights=tf["object_weights"]))
+                edits.append(dict(common, fg_masks=r["fg_masks"], transforms=tf["transforms"], object_weights=tf["object_weights"],
+                                  instances=tf.get("instances")))
             else:
                 edits.append(dict(common, fg_mask=r["fg_mask"], rot_angle=tf["rot_angle"], rot_axis=tf["rot_axis"],
                                   translation=tf["translation"], scale=tf.get("scale"), pivot=tf.get("pivot")))
@@ -503,7 +509,8 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
         if p.get("masks_dev") is not None:
             rel = {} if p.get("release") is None else dict(release_mask=p["release"])
             res_ = dh.transform_foreground_objects(depth, prompt, p["masks_dev"], bg_depth, null_text, noise, acts,
-                                                   transforms=tf["transforms"], object_weights=tf["object_weights"], **rel)
+                                                   transforms=tf["transforms"], object_weights=tf["object_weights"],
+                                                   instances=tf.get("instances"), **rel)
         elif p.get("release") is not None:
             # (transform_foreground keeps the reference's parameter list: a release mask goes through the one-mask form of
             #  transform_foreground_objects, the same edit in 'pc' mode)

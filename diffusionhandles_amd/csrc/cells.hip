@@ -32,6 +32,17 @@ __global__ void k_pairs(const long long* corr, const int* idx, const int* count,
   bg_t[tc] = 0;
 }
 
+// object removal (dh_cells_from_correspondences_vacated): a cell that holds a vacated pixel leaves the original-background mask,
+// as if a kept correspondence started in it (one thread per pixel; racing byte stores all write 0)
+__global__ void k_vacated_cells(const uint8_t* vacated, int img_res, int grid, uint8_t* bg_o) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= img_res * img_res) return;
+  if (vacated[i]) {
+    const int cs = img_res / grid, y = i / img_res, x = i - y * img_res;
+    bg_o[(y / cs) * grid + x / cs] = 0;
+  }
+}
+
 // scipy.ndimage.binary_erosion: cross structuring element, border_value 0, `iters` passes.
 // blockIdx.x selects the mask (0 = orig, 1 = trans); one workgroup per mask, ping-pong in LDS.
 __global__ void __launch_bounds__(1024) k_erode(uint8_t* masks, int grid, int iters) {
@@ -139,11 +150,18 @@ extern "C" int dh_cells_workspace_bytes(int n, int grid, size_t* bytes) {
   return DH_OK;
 }
 
-extern "C" int dh_cells_from_correspondences(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
-                                             int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
-                                             void* workspace, size_t workspace_bytes, void* stream) {
+// vacated: NULL, or the [img_res][img_res] image of the pixels an edit's removed objects leave behind (non-zero = vacated); its
+// cells are cleared from the original-background mask between k_pairs and k_erode, so the erosion pushes the background away
+// from them as it does from an object.  The transformed-background mask and the pairs do not see it.  n == 0 with an image is
+// the pure removal.  NULL launches what dh_cells_from_correspondences always launched.
+extern "C" int dh_cells_from_correspondences_vacated(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                                     int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                                     void* workspace, size_t workspace_bytes, void* stream,
+                                                     const uint8_t* vacated) {
   DH_REQUIRE(pairs && bg_lists && bg_masks && counts && workspace, "null pointer");
   DH_REQUIRE(n >= 0 && grid >= 1 && img_res >= grid && img_res % grid == 0, "bad sizes");
+  DH_REQUIRE(n == 0 || corr, "null corr");
+  DH_REQUIRE(!vacated || img_res <= 32768, "img_res too large for a vacated image");
   DH_REQUIRE(2 * grid * grid <= 60000, "grid too large for the erosion kernel");
   size_t need;
   dh_cells_workspace_bytes(n, grid, &need);
@@ -158,16 +176,24 @@ extern "C" int dh_cells_from_correspondences(const int64_t* corr, int n, int img
   DH_CHECK_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int), st));
   hipLaunchKernelGGL(k_init_masks, dim3(cdiv(2 * G2, 256)), dim3(256), 0, st, two, 2 * G2);
   if (n > 0) {
-    DH_REQUIRE(corr, "null corr");
     hipLaunchKernelGGL(k_valid, dim3(cdiv(n, 256)), dim3(256), 0, st, (const long long*)corr, n, img_res, valid);
     compact(valid, n, 1, 0, idx, 0, counts, 1, bc, st);
     hipLaunchKernelGGL(k_pairs, dim3(cdiv(n, 256)), dim3(256), 0, st, (const long long*)corr, idx, counts, img_res,
                        grid, pairs, two, two + G2);
   }
+  if (vacated)
+    hipLaunchKernelGGL(k_vacated_cells, dim3(cdiv(img_res * img_res, 256)), dim3(256), 0, st, vacated, img_res, grid, two);
   if (bg_erosion > 0)
     hipLaunchKernelGGL(k_erode, dim3(2), dim3(1024), 2 * G2, st, two, grid, bg_erosion);
   hipLaunchKernelGGL(k_three_masks, dim3(cdiv(G2, 256)), dim3(256), 0, st, two, bg_masks, G2);
   compact(bg_masks, G2, 3, G2, bg_lists, G2, counts + 1, 1, bc, st);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+extern "C" int dh_cells_from_correspondences(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                             int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  return dh_cells_from_correspondences_vacated(corr, n, img_res, grid, bg_erosion, pairs, bg_lists, bg_masks, counts, workspace,
+                                               workspace_bytes, stream, nullptr);
 }

@@ -603,6 +603,14 @@ __global__ void k_count_flags(const uint8_t* f, int n, int* out, int out_stride,
   }
 }
 
+// object removal (dh_reproject_background): flag the pixels that no point of the list reached (the z-buffer still holds its
+// initial key); with a zero "clean" image k_normalize turns the flags into the in-fill set
+__global__ void k_unowned(int R2, const unsigned long long* zbuf, uint8_t* flag) {
+  int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= R2) return;
+  flag[p] = zbuf[p] == ~0ull ? 1 : 0;
+}
+
 // normalise disparity in place and flag the pixels to in-fill (cleaned xor raw)
 __global__ void k_normalize(int R2, float* disp, const unsigned int* minmax, const float* bounds,
                             const uint8_t* raw, const uint8_t* clean, uint8_t* inpaint) {
@@ -1518,6 +1526,59 @@ extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, con
   return dh_reproject_object_edits(depth, bg_depth, fg_pix, n_fg, 1, one, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, n_edits,
                                    xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
                                    workspace, workspace_bytes, stream);
+}
+
+// Object removal, the pure case (no foreground point left): the background part of the point list through the kernels of
+// reproject_instances -- k_points (n_pts = 0: every thread takes the background branch), k_resolve, k_pixels, k_normalize, the
+// in-fill solvers -- on the carving of a one-edit call without foreground.  Nothing is foreground, so raw and cleaned masks are
+// zero and stay in the workspace; the in-fill set is the pixels no point owns (k_unowned in the raw mask's place).
+extern "C" int dh_reproject_background_workspace_bytes(int res, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && res <= 32768 && bytes, "bad arguments");
+  Arena a(nullptr, (size_t)-1);
+  ReprojectWs w;
+  carve(a, res, 0, 1, 1, w);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_reproject_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y, float inv_fx,
+                                       float inv_fy, double fx, double fy, const float* bounds, float* zmap, float* disparity,
+                                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  DH_REQUIRE(bg_depth && grid_x && grid_y, "null input");
+  DH_REQUIRE(zmap && disparity && counts && workspace, "null output");
+  DH_REQUIRE(res >= 2 && res <= 32768, "bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  const int R2 = res * res;
+  Arena a(workspace, workspace_bytes);
+  ReprojectWs w;
+  DH_REQUIRE(carve(a, res, 0, 1, 1, w), "workspace too small");
+  const int32_t none[2] = {0, 0};
+  int n_pts = 0;
+  const InstTable itab = inst_table(0, none, none, &n_pts);
+  DH_CHECK_HIP(hipMemsetAsync(w.zbuf, 0xff, (size_t)R2 * sizeof(unsigned long long), st));
+  DH_CHECK_HIP(hipMemsetAsync(w.owner, 0x7f, (size_t)R2 * sizeof(int), st));
+  DH_CHECK_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int), st));
+  DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0, 2 * sizeof(unsigned int), st));
+  DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0xff, sizeof(unsigned int), st));
+  DH_CHECK_HIP(hipMemsetAsync(w.tmp_b, 0, (size_t)R2, st));
+  hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, (const int*)nullptr, 0, res,
+                     grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr);
+  hipLaunchKernelGGL(k_resolve, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.zbuf, w.pix, w.key, w.owner);
+  hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), 1), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, w.tmp_a,
+                     disparity, w.minmax);
+  hipLaunchKernelGGL(k_unowned, dim3(cdiv(R2, 256)), dim3(256), 0, st, R2, w.zbuf, w.tmp_a);
+  hipLaunchKernelGGL(k_normalize, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, disparity, w.minmax, bounds, w.tmp_a, w.tmp_b,
+                     w.inpaint);
+  compact(w.inpaint, R2, 1, R2, w.unk, R2, counts + 2, 4, w.block_counts, st);
+  DH_CHECK_HIP(hipMemsetAsync(w.cgsync, 0, sizeof(CgSync), st));
+  hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, 1), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
+                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CG_SLOTS * 1024, w.owner,
+                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2, w.cgsync);
+  hipLaunchKernelGGL(k_cg_fill, dim3(1), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
+                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CGM_WGS * CGM_EPT * 1024, w.owner,
+                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
 }
 
 extern "C" int dh_laplacian_blend_workspace_bytes(int res, size_t* bytes) {

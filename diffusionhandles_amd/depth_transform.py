@@ -291,10 +291,102 @@ def reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, insta
     kept instances' slices in vis / target_xy); instances=None is `reproject_object_edits`, byte for byte.
     return_instances=True: every result is (disparity, correspondences [R,4], instances [R] uint8 beside them); without
     an instance table the instance of a row is the index of its mask.
+    Removing an object: `reproject_removal_edits`, of which this is the call without removed masks.
     """
+    return reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, None, use_input_depth_normalization,
+                                   return_debug, device_correspondences, footprints, footprint_max_ratio, return_instances)
+
+
+def check_removed_masks(removed_masks, fg_masks, what="removed_masks"):
+    """The removed masks of an edit (object removal, DESIGN.md "Object removal") -> list of R >= 0 masks (None -> []).
+    ValueError naming `what` and the mask for something that is not a list of masks, or a mask that is not square or not of
+    the size of the foreground masks (of the first removed mask when there is no foreground mask).  Host only: it reads shapes.
+    Whether a removed mask overlaps a foreground mask or another removed mask is a question about pixels:
+    `reproject_removal_edits` answers it in the device-to-host copy that reads the pixel counts, `removed_overlap` on its own."""
+    if removed_masks is None:
+        return []
+    if isinstance(removed_masks, (torch.Tensor, np.ndarray)) or not isinstance(removed_masks, (list, tuple)):
+        raise ValueError(f"{what}: expected a list of masks, got {type(removed_masks).__name__}")
+    out = []
+    size = None if len(fg_masks) == 0 else tuple(fg_masks[0].shape[-2:])
+    for r, mask in enumerate(removed_masks):
+        if not isinstance(mask, torch.Tensor) or mask.dim() < 2:
+            raise ValueError(f"{what}: removed mask {r} is not a [.., H, W] tensor")
+        if mask.shape[-2] != mask.shape[-1] or mask.numel() != mask.shape[-1] * mask.shape[-1]:
+            raise ValueError(f"{what}: removed mask {r} is not one square image, got shape {tuple(mask.shape)}")
+        if size is None:
+            size = tuple(mask.shape[-2:])
+        if tuple(mask.shape[-2:]) != size:
+            raise ValueError(f"{what}: removed mask {r} is {mask.shape[-1]} x {mask.shape[-2]}, the other masks are "
+                             f"{size[1]} x {size[0]}")
+        out.append(mask)
+    return out
+
+
+def removed_overlap(removed_masks, fg_masks, what="removed_masks"):
+    """ValueError naming `what` and the masks when a removed mask shares a pixel with a foreground mask or with an earlier
+    removed mask.  Host arithmetic on the masks where they are (one copy per mask pair tested: the error path and host callers;
+    `reproject_removal_edits` carries one flag per removed mask in its own copy and calls this only to name the pair)."""
+    removed = check_removed_masks(removed_masks, fg_masks, what)
+    flat = lambda m: (m.detach() != 0).reshape(-1)
+    for r, mask in enumerate(removed):
+        mr = flat(mask)
+        for m, fg in enumerate(fg_masks):
+            if bool((mr & flat(fg).to(mr.device)).any()):
+                raise ValueError(f"{what}: removed mask {r} overlaps foreground mask {m}")
+        for q in range(r):
+            if bool((mr & flat(removed[q]).to(mr.device)).any()):
+                raise ValueError(f"{what}: removed mask {r} overlaps removed mask {q}")
+
+
+def vacated_image(removed_masks, device=None):
+    """[H, W] uint8 union of the removed masks (1 = vacated) on `device` (default: where the first mask is); None for no mask.
+    An all-zero image is the call without it, byte for byte, so nothing here reads a pixel back."""
+    removed = check_removed_masks(removed_masks, [], "vacated_image")
+    if not removed:
+        return None
+    dev = removed[0].device if device is None else device
+    res = removed[0].shape[-1]
+    out = torch.zeros((res, res), dtype=torch.bool, device=dev)
+    for mask in removed:
+        out |= (mask.detach().to(dev) != 0).reshape(res, res)
+    return out.to(torch.uint8).contiguous()
+
+
+def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None,
+                            use_input_depth_normalization=False, return_debug=False, device_correspondences=False,
+                            footprints=False, footprint_max_ratio=None, return_instances=False):
+    """`reproject_instance_edits` for an edit that also DELETES objects (not in the reference; DESIGN.md "Object removal"):
+    everything said there holds, and --
+
+    removed_masks: None, or a list of R >= 0 [1,1,H,W] masks of the objects the edit deletes, pairwise disjoint from each other
+    and from fg_masks; bg_depth has them removed as well (that is its definition).  transforms, instances and everything else
+    speak about fg_masks as before.  A removed object contributes no point: the point list is the background pixels from
+    bg_depth, then the instances of fg_masks, so with M >= 1 every output is byte for byte the output of the call without
+    removed masks.  Empty removed masks are dropped; None, [] and all-empty masks are `reproject_instance_edits`.
+    Pure removal -- fg_masks empty (M = 0) and at least one non-empty removed mask: the edits are K empty transform lists, and
+    every one of the K results is the re-projection of the background ALONE (z-buffer over the H * W background points, in-fill
+    of the pixels no point owns, normalisation with the optional input bounds; computed once), with no correspondences and zero
+    masks.  That is not the empty-mask result (the normalised INPUT disparity, object included), which stays what it is.
+    ValueError before any device work of the library, naming the mask: a removed mask of another size, one that overlaps a
+    foreground mask or another removed mask, M = 0 without a non-empty removed mask, transforms or instances given for M = 0.
+    The debug dict gains vacated ([H, W] uint8 on the device: the union of the removed masks).
+    """
+    what = "reproject_removal_edits"
     footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
     fg_masks = list(fg_masks)
+    removed = check_removed_masks(removed_masks, fg_masks, f"{what}: removed_masks")
     M = len(fg_masks)
+    if M == 0 and removed:
+        edits = [list(tfs) for tfs in edits]
+        for e, tfs in enumerate(edits):
+            if len(tfs) != 0:
+                raise ValueError(f"{what}: edit {e} has {len(tfs)} transforms, but there is no foreground mask (a pure removal "
+                                 f"moves nothing)")
+        if instances is not None and len(list(instances)) != 0:
+            raise ValueError(f"{what}: instances={instances!r} given without a foreground mask (a pure removal has no instance)")
+        return _reproject_pure_removal(depth, bg_depth, removed, intrinsics, len(edits), use_input_depth_normalization,
+                                       return_debug, device_correspondences, return_instances, instances is not None)
     if not 1 <= M <= MAX_OBJECTS:
         raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got {M}")
     inst = check_instances(instances, M, "reproject_instance_edits: instances")
@@ -324,9 +416,27 @@ def reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, insta
     stats = masks_u8.sum(dim=1)
     if M > 1:
         stats = torch.cat([stats, (masks_u8.sum(dim=0) > 1).any()[None].to(stats.dtype)])
+    vacated = None
+    if removed:
+        # the removed masks ride in the same copy: per mask its pixel count and whether it meets the union before it
+        seen = masks_u8.sum(dim=0) > 0
+        vacated = torch.zeros_like(seen)
+        extra = []
+        for mask in removed:
+            mr = (mask.detach() != 0).reshape(-1).to(seen.device)
+            extra += [mr.sum().to(stats.dtype), (mr & seen).any().to(stats.dtype)]
+            seen = seen | mr
+            vacated = vacated | mr
+        stats = torch.cat([stats, torch.stack(extra)])
     stats = stats.tolist()
     if M > 1 and stats[M]:
         raise ValueError("The foreground masks overlap")
+    if removed:
+        tail = stats[len(stats) - 2 * len(removed):]
+        if any(tail[1::2]):
+            removed_overlap(removed, fg_masks, f"{what}: removed_masks")
+            raise ValueError(f"{what}: removed_masks: removed mask {tail[1::2].index(1)} overlaps another mask")
+        n_vacated = sum(tail[0::2])
     kept = [m for m in range(M) if stats[m] > 0]
     obj_start = np.zeros(len(kept) + 1, dtype=np.int32)
     obj_start[1:] = np.cumsum([stats[m] for m in kept])
@@ -343,13 +453,19 @@ def reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, insta
     if use_input_depth_normalization:
         disp_in = 1.0 / d
         bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
+    if n_fg == 0 and removed and n_vacated > 0:
+        # every foreground mask is empty (dropped with its transforms) and an object is deleted: the pure removal
+        return _reproject_pure_removal(depth, bg_depth, removed, intrinsics, len(edits), use_input_depth_normalization,
+                                       return_debug, device_correspondences, return_instances, with_table)
     if n_fg == 0:
         # empty foreground: the input disparity and no correspondences (depth_transform.py:203-216)
         lo_hi = None if bounds is None else (bounds[0], bounds[1])
         disp = normalize_depth(1.0 / d, bounds=lo_hi).to(out_dev)
         empty = torch.zeros((0, 4), dtype=torch.int64)
         res_list = [(disp, empty) + ((torch.zeros(0, dtype=torch.uint8),) if return_instances else ()) for _ in range(K)]
-        return (res_list, {}) if return_debug else res_list
+        if return_debug:
+            return res_list, ({} if removed_masks is None else dict(vacated=_vacated_u8(vacated, res, dev)))
+        return res_list
 
     gx, gy = _grids(res, res, dev)
     ifx, ify = _inv_focal(intrinsics)
@@ -419,8 +535,78 @@ def reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, insta
                    fg_pix=fg_pix[:n_fg], corr_dev=corr, obj_start=obj_start)
         if with_table:
             dbg.update(corr_inst=corr_inst, inst_start=inst_start)
+        if removed_masks is not None:
+            dbg.update(vacated=_vacated_u8(vacated, res, dev))
         return out, dbg
     return out
+
+
+def _vacated_u8(vacated, res, dev):
+    if vacated is None:
+        return torch.zeros((res, res), dtype=torch.uint8, device=dev)
+    return vacated.to(dev).reshape(res, res).to(torch.uint8)
+
+
+def _reproject_pure_removal(depth, bg_depth, removed, intrinsics, K, use_input_depth_normalization, return_debug,
+                            device_correspondences, return_instances, with_table):
+    """The pure removal of `reproject_removal_edits`: dh_reproject_background once, its result K times."""
+    what = "reproject_removal_edits"
+    if depth.dim() != 4 or depth.shape[0] != 1:
+        raise ValueError("Only batch size 1 is supported")
+    res = removed[0].shape[-1]
+    if depth.shape[-1] != res or depth.shape[-2] != res:
+        raise ValueError(f"{what}: removed_masks: removed mask 0 is {res} x {res}, the depth {depth.shape[-1]} x {depth.shape[-2]}")
+    # the pixel counts and the overlap flags: ONE device-to-host copy (none for host masks), before any launch of the library
+    seen = torch.zeros(res * res, dtype=torch.bool, device=removed[0].device)
+    extra = []
+    for mask in removed:
+        mr = (mask.detach() != 0).reshape(-1).to(seen.device)
+        extra += [mr.sum(), (mr & seen).any().to(torch.int64)]
+        seen = seen | mr
+    tail = torch.stack(extra).tolist()
+    if any(tail[1::2]):
+        removed_overlap(removed, [], f"{what}: removed_masks")
+    if sum(tail[0::2]) == 0:
+        raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got 0")
+    out_dev = depth.device
+    dev = _compute_device(depth)
+    L = _lib.lib()
+    st = _lib.stream_ptr()
+    bg = bg_depth.detach().to(dev, torch.float32).contiguous()
+    bounds = None
+    if use_input_depth_normalization:
+        disp_in = 1.0 / depth.detach().to(dev, torch.float32)
+        bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
+    gx, gy = _grids(res, res, dev)
+    ifx, ify = _inv_focal(intrinsics)
+    kcpu = intrinsics.detach().to("cpu", torch.float32)
+    fx, fy = float(kcpu[0, 0]), float(kcpu[1, 1])
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.dh_reproject_background_workspace_bytes(res, ctypes.byref(nbytes)), "dh_reproject_background_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    zmap = torch.empty((res, res), dtype=torch.float32, device=dev)
+    disp = torch.empty((res, res), dtype=torch.float32, device=dev)
+    counts = torch.zeros(4, dtype=torch.int32, device=dev)
+    _lib.check(L.dh_reproject_background(_lib.ptr(bg), res, _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, _lib.ptr(bounds),
+                                         _lib.ptr(zmap), _lib.ptr(disp), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st),
+               "dh_reproject_background")
+    counts_h = counts.cpu()
+    _check_infill(counts_h[3:4])
+    disp_out = disp[None, None].to(out_dev)
+    empty = torch.zeros((0, 4), dtype=torch.int64, device=dev if device_correspondences else "cpu")
+    no_inst = torch.zeros(0, dtype=torch.uint8, device=empty.device)
+    out = [(disp_out, empty) + ((no_inst,) if return_instances else ()) for _ in range(K)]
+    if not return_debug:
+        return out
+    zeros = torch.zeros((K, res, res), dtype=torch.uint8, device=dev)
+    dbg = dict(zmap=zmap[None].expand(K, -1, -1), raw_mask=zeros, clean_mask=zeros.clone(),
+               vis=torch.zeros((K, 0), dtype=torch.uint8, device=dev), target_xy=torch.zeros((K, 0, 2), dtype=torch.int32, device=dev),
+               counts=counts_h[None].expand(K, -1).contiguous(), fg_pix=torch.zeros(0, dtype=torch.int32, device=dev),
+               corr_dev=torch.zeros((K, 0, 4), dtype=torch.int64, device=dev), obj_start=np.zeros(1, dtype=np.int32),
+               vacated=seen.to(dev).reshape(res, res).to(torch.uint8))
+    if with_table or return_instances:
+        dbg.update(corr_inst=torch.zeros((K, 0), dtype=torch.uint8, device=dev), inst_start=np.zeros(1, dtype=np.int32))
+    return out, dbg
 
 
 INFILL_BARRIER_TIMEOUT, INFILL_NOT_CONVERGED, INFILL_BREAKDOWN = -1, -2, -3      # counts[..., 3] < 0 (geometry.hip)

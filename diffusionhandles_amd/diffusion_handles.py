@@ -65,7 +65,8 @@ class DiffusionHandles:
     def set_foreground(self, depth, fg_mask, bg_depth):
         """Background depth = input depth with the hole of the (15x cross-dilated) foreground mask in-filled
         from the background depth's Laplacian (reference diffusion_handles.py:90-111).  fg_mask may be a list of masks
-        (several objects, transform_foreground_objects): the blend runs over their union."""
+        (several objects, transform_foreground_objects): the blend runs over their union.  The masks of objects an edit DELETES
+        (removed_masks of transform_foreground_objects) belong in that list too: bg_depth is the depth with all of them removed."""
         if isinstance(fg_mask, (list, tuple)):
             union = fg_mask[0] != 0
             for m in fg_mask[1:]:
@@ -149,16 +150,35 @@ class DiffusionHandles:
         return imgs, [d for d, _ in edits]
 
     def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences,
-                           instances=None):
-        """instances given: every result is (disparity, correspondences, instance of every row)."""
-        from .depth_transform import check_instances, reproject_instance_edits
+                           instances=None, removed_masks=None):
+        """instances given: every result is (disparity, correspondences, instance of every row).  removed_masks: the masks of the
+        objects the edits delete (object removal); fg_masks may then be empty and the edits K empty lists."""
+        from .depth_transform import check_instances, check_removed_masks, reproject_removal_edits
         fp = self._footprints(what)
         if self.conf.depth_transform_mode != "pc":
+            if removed_masks is not None:
+                raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no object removal "
+                                          "(removed_masks; only 'pc')")
             if instances is not None:
                 raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no copies of an "
                                           "object (instances; only 'pc')")
             raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no multi-object "
                                       "re-projection (only 'pc')")
+        if removed_masks is not None:
+            removed = check_removed_masks(removed_masks, list(fg_masks), f"{what}: removed_masks")
+            if len(fg_masks) == 0:
+                if not removed:
+                    raise ValueError(f"Expected 1 to 8 foreground masks, got 0 ({what}: no removed mask either)")
+                if instances is not None and len(list(instances)) != 0:
+                    raise ValueError(f"{what}: instances={instances!r} given without a foreground mask (a pure removal has no "
+                                     "instance)")
+                for e, tfs in enumerate(edits):
+                    if len(tfs) != 0:
+                        raise ValueError(f"{what}: edit {e} has {len(tfs)} transforms, but there is no foreground mask (a pure "
+                                         "removal moves nothing)")
+                return reproject_removal_edits(depth, bg_depth, [], self.diffuser.get_depth_intrinsics(device=depth.device),
+                                               [[] for _ in edits], None, removed, use_input_depth_normalization,
+                                               device_correspondences=device_correspondences, **fp)
         inst = check_instances(instances, len(fg_masks), f"{what}: instances")
         n_bodies, body = (len(fg_masks), "object") if inst is None else (len(inst), "instance")
         Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
@@ -172,9 +192,32 @@ class DiffusionHandles:
                 full = [check_transform(tf, f"{what}: edit {e}, {body} {m}") for m, tf in enumerate(tfs)]
                 defaulted.append([(dflt(a, 0.0), dflt(ax, Y), dflt(tr, torch.zeros(3)), sc, pv) for a, ax, tr, sc, pv in full])
         edits = defaulted
-        return reproject_instance_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
-                                        inst, use_input_depth_normalization, device_correspondences=device_correspondences, **fp,
-                                        return_instances=inst is not None)
+        return reproject_removal_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
+                                       inst, removed_masks, use_input_depth_normalization,
+                                       device_correspondences=device_correspondences, **fp, return_instances=inst is not None)
+
+    @staticmethod
+    def _vacated(removed_masks, what):
+        """The guidance's keyword of an edit that deletes objects: {} for none, else dict(vacated=[res, res] uint8 union)."""
+        if removed_masks is None:
+            return {}
+        from .depth_transform import vacated_image
+        image = vacated_image(removed_masks)
+        return {} if image is None else dict(vacated=image)
+
+    def _check_removal(self, what, fg_masks, removed_masks):
+        """The host checks of an edit call's removed_masks, before any device work: mesh mode has none (NotImplementedError naming
+        the setting); a mask of another size raises ValueError naming `what` and the mask (check_removed_masks; an overlap is
+        found by the re-projection, in the copy that reads the pixel counts, before its first launch)."""
+        if removed_masks is None:
+            return
+        if self.conf.depth_transform_mode != "pc":
+            raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no object removal "
+                                      "(removed_masks; only 'pc')")
+        from .depth_transform import check_removed_masks
+        removed = check_removed_masks(removed_masks, fg_masks, f"{what}: removed_masks")
+        if len(fg_masks) == 0 and not removed:
+            raise ValueError(f"Expected 1 to 8 foreground masks, got 0 ({what}: no removed mask either)")
 
     @staticmethod
     def _object_labels(fg_masks, object_weights, instances=None, what="instances"):
@@ -183,6 +226,10 @@ class DiffusionHandles:
         the unweighted path.  With an instance table there is no label image: the re-projection's per-row instances say which
         object of the energy a correspondence belongs to."""
         n = len(fg_masks)
+        if n == 0:              # a pure removal (its refusals are _reproject_objects'): no object, so no weights
+            if object_weights is not None:
+                raise ValueError(f"{what.split(':')[0]}: object_weights={object_weights!r} given without a foreground mask")
+            return None, None
         if instances is not None:
             from .depth_transform import check_instances
             n = len(check_instances(instances, len(fg_masks), what))
@@ -199,7 +246,7 @@ class DiffusionHandles:
 
     def transform_foreground_objects(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                      transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                     object_weights=None, instances=None, release_mask=None):
+                                     object_weights=None, removed_masks=None, instances=None, release_mask=None):
         """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
         rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.  Each object
@@ -214,15 +261,25 @@ class DiffusionHandles:
         instances (copies of an object; DESIGN.md "Object copies"): None, or N mask indices (M <= N <= 8, every mask named) --
         the edit places N instances, instance n the object of mask instances[n] under transforms[n] (N transforms); a mask
         named twice appears twice.  object_weights then has N entries and "equal" holds every instance equally.  ValueError
-        naming the instance for a bad table, before any device work."""
+        naming the instance for a bad table, before any device work.
+        removed_masks (object removal; DESIGN.md "Object removal"): None, or the masks of the objects the edit DELETES, disjoint
+        from each other and from fg_masks; bg_depth has them removed too.  They contribute no point to the re-projection, their
+        cells leave the guidance's original-background list, and the background lock sets them free (release_mask stays the
+        tool for the shadow).  fg_masks may then be empty with transforms [] -- a pure removal: the disparity is the
+        re-projection of the background alone.  Meant to run with conf background_lock: true.  ValueError naming the mask for
+        an overlap or another size, for no mask at all, and for transforms without a foreground mask, before any device work."""
         what = "transform_foreground_objects"
+        fg_masks = list(fg_masks)
+        self._check_removal(what, fg_masks, removed_masks)
         labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
         lk = self._lock_setup(what, activations, depth, release_mask)
         with torch.no_grad():
             (edited_disparity, correspondences, *rows), = self._reproject_objects(
-                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances)
+                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances, removed_masks)
             self.last_keep_maps = []
-            lock = {} if lk is None else dict(lock=self._edit_lock(lk, fg_masks, correspondences, depth))
+            freed = fg_masks + list(removed_masks or [])
+            lock = {} if lk is None else dict(lock=self._edit_lock(lk, freed, correspondences, depth))
+            lock.update(self._vacated(removed_masks, what))
             if rows:
                 lock["pair_instances"] = rows[0]
             results = self.diffuser.guided_inference(
@@ -237,7 +294,8 @@ class DiffusionHandles:
 
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                           object_weights=None, streams=1, batch=None, instances=None, release_mask=None):
+                                           object_weights=None, streams=1, batch=None, removed_masks=None, instances=None,
+                                           release_mask=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
         edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
         pivot).  Returns (images [K,3,H,W], [K disparities]) as
@@ -245,20 +303,24 @@ class DiffusionHandles:
         streams / batch: transform_foreground_batch's -- chunks of `batch` edits (default ceil(K / streams)) on `streams`
         lanes, batch = 1 runs single edits on the lanes; images are bit-identical to the one-stream result at the same batch.
         release_mask: transform_foreground_objects', one for all K edits.  instances: transform_foreground_objects', one table
-        for all K edits (the edits are then K lists of N transforms)."""
+        for all K edits (the edits are then K lists of N transforms).  removed_masks: transform_foreground_objects', one list for
+        all K edits (with fg_masks empty the edits are K empty lists: K identical pure removals)."""
         what = "transform_foreground_objects_batch"
+        fg_masks = list(fg_masks)
+        self._check_removal(what, fg_masks, removed_masks)
         labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
         lk = self._lock_setup(what, activations, depth, release_mask)
         K = len(edits)
         with torch.no_grad():
-            res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, instances)
+            res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, instances,
+                                          removed_masks)
             rows = [r[2] for r in res] if instances is not None else None
             res = [r[:2] for r in res]
             per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
-            obj = dict(object_labels=labels, object_weights=object_weights)
+            obj = dict(object_labels=labels, object_weights=object_weights, **self._vacated(removed_masks, what))
             self.last_keep_maps = []
             if lk is not None:
-                obj["lock"] = [self._edit_lock(lk, fg_masks, c, depth) for _, c in res]
+                obj["lock"] = [self._edit_lock(lk, fg_masks + list(removed_masks or []), c, depth) for _, c in res]
             if rows is not None:          # per edit; the chunked call takes one list per chunk
                 obj["pair_instances"] = rows if streams <= 1 and per >= K or per <= 1 else [rows[i:i + per] for i in range(0, K, per)]
             if streams <= 1 and per >= K:
@@ -289,8 +351,10 @@ class DiffusionHandles:
         image per image); then one GuidedStableDiffuser.guided_inference_items for single- and multi-object edits alike.
         Returns (images [K,3,H,W], [K disparities]) in input order.  'pc' re-projection only; one resolution; needs an engine
         with max_batch >= 2K.  With conf background_lock every edit is locked to its own image's reconstruction; an edit may
-        carry a `release_mask` (transform_foreground_objects)."""
-        from .depth_transform import check_instances, check_transform, reproject_edits
+        carry a `release_mask` (transform_foreground_objects).  A multi-object edit may carry `removed_masks` (object removal,
+        transform_foreground_objects; fg_masks may then be [] with no transforms): edits of one image that differ in it are
+        re-projected in separate calls, and edits with and without it share the batch."""
+        from .depth_transform import check_instances, check_removed_masks, check_transform, reproject_edits
         fp = self._footprints("transform_foregrounds")
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
@@ -300,7 +364,7 @@ class DiffusionHandles:
         if K < 1 or any(set(common) - set(e) for e in edits):
             raise ValueError(f"transform_foregrounds: needs at least one edit, each with {self.EDIT_FIELDS}")
         single_keys = ("fg_mask", "rot_angle", "rot_axis", "translation", "scale", "pivot")
-        multi_keys = ("fg_masks", "transforms", "object_weights", "instances")
+        multi_keys = ("fg_masks", "transforms", "object_weights", "instances", "removed_masks")
         weights = [None] * K
         for i, e in enumerate(edits):
             single = any(e.get(k) is not None for k in single_keys)
@@ -312,8 +376,17 @@ class DiffusionHandles:
                 raise ValueError(f"transform_foregrounds: edit {i} has neither fg_mask nor fg_masks")
             if multi:
                 masks, tfs = e.get("fg_masks"), e.get("transforms")
-                if not isinstance(masks, (list, tuple)) or len(masks) < 1:
+                removed = e.get("removed_masks")
+                if removed is not None:
+                    removed = check_removed_masks(removed, list(masks) if isinstance(masks, (list, tuple)) else [],
+                                                  f"transform_foregrounds: edit {i}: removed_masks")
+                if not isinstance(masks, (list, tuple)) or (len(masks) < 1 and not removed):
                     raise ValueError(f"transform_foregrounds: edit {i}: fg_masks must be a non-empty list of masks")
+                if len(masks) == 0:          # a pure removal: no transform, no table, no weights
+                    if tfs or e.get("instances") or e.get("object_weights") is not None:
+                        raise ValueError(f"transform_foregrounds: edit {i} has no foreground mask (a pure removal), but gives "
+                                         "transforms, instances or object_weights")
+                    continue
                 inst = check_instances(e.get("instances"), len(masks), f"transform_foregrounds: edit {i}: instances")
                 n_bodies, body = (len(masks), "masks") if inst is None else (len(inst), "instances")
                 if tfs is None or len(tfs) != n_bodies:
@@ -347,6 +420,8 @@ class DiffusionHandles:
             key = (id(e["depth"]), e.get("fg_masks") is not None) + masks + (id(e["bg_depth"]),) + tuple(id(a) for a in e["activations"])
             if e.get("instances") is not None:          # one instance table per re-projection call
                 key += ("instances",) + tuple(int(o) for o in e["instances"])
+            if e.get("removed_masks") is not None:      # one list of removed masks per re-projection call
+                key += ("removed",) + tuple(id(m) for m in e["removed_masks"])
             groups.setdefault(key, []).append(i)
         reproj, labels, rows = [None] * K, [None] * K, [None] * K
         with torch.no_grad():
@@ -354,8 +429,8 @@ class DiffusionHandles:
                 e0 = edits[idx[0]]
                 if e0.get("fg_masks") is not None:
                     res = self._reproject_objects("transform_foregrounds", e0["depth"], e0["bg_depth"], list(e0["fg_masks"]),
-                                                  [list(edits[i]["transforms"]) for i in idx], use_input_depth_normalization, True,
-                                                  e0.get("instances"))
+                                                  [list(edits[i].get("transforms") or []) for i in idx],
+                                                  use_input_depth_normalization, True, e0.get("instances"), e0.get("removed_masks"))
                     if e0.get("instances") is not None:          # the rows' instances stand in for the label image
                         for i, r in zip(idx, res):
                             rows[i] = r[2]
@@ -377,8 +452,9 @@ class DiffusionHandles:
             self.last_keep_maps = []
             items = [dict(latents=e["init_noise"], depth=d, uncond_embeddings=e["null_text_emb"], prompt=e["prompt"],
                           activations_orig=e["activations"], correspondences=c, object_labels=labels[i], object_weights=weights[i],
-                          pair_instances=rows[i], lock=self._edit_lock(lks[i], e["fg_masks"] if e.get("fg_masks") is not None else e["fg_mask"], c,
-                                               e["depth"]))
+                          pair_instances=rows[i], **self._vacated(e.get("removed_masks"), "transform_foregrounds"),
+                          lock=self._edit_lock(lks[i], list(e["fg_masks"]) + list(e.get("removed_masks") or [])
+                                               if e.get("fg_masks") is not None else e["fg_mask"], c, e["depth"]))
                      for i, (e, (d, c)) in enumerate(zip(edits, reproj))]
             imgs = self.diffuser.guided_inference_items(items, [e.get("fg_weight") for e in edits],
                                                         [e.get("bg_weight") for e in edits])

@@ -479,7 +479,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
         _check_object_weights(object_weights, n)
 
     def prepare_guidance(self, depth, prompt, activations_orig, correspondences, fg_weight=None, bg_weight=None, orig=None,
-                         cond=None, object_labels=None, object_weights=None, pair_instances=None, lock=None):
+                         cond=None, object_labels=None, object_weights=None, pair_instances=None, vacated=None, lock=None):
         """Everything of guided_inference that is constant over the denoising loop.  `lock` (background lock): (keep [s,s],
         trajectory [T,4,s,s]) -- the keep map of this edit (background_lock.keep_map) and the reconstruction trajectory of its
         image (activations.trajectory) -- or a prepared background_lock.Lock (edits of one image share the channels-last copy
@@ -492,8 +492,12 @@ class GuidedStableDiffuser(GuidedDiffuser):
         pair counts (DESIGN.md "A weight per object").  None: the area weighting, on the unchanged path.
         pair_instances (edits with copies of an object): the instance of every correspondence row, uint8 [N], IN PLACE OF the
         label image (giving both is a ValueError) -- an object of the energy is then an instance, object_weights has one entry
-        per instance."""
+        per instance.
+        vacated (edits that DELETE objects, DESIGN.md "Object removal"): the [H, W] image of the pixels the removed objects
+        leave behind; their cells leave the original-background list of the energy (losses.process_correspondences).  The
+        correspondences may then be empty (a pure removal: the background term runs alone).  None: the call without it."""
         from types import SimpleNamespace
+        vacated = _losses.check_vacated(vacated, depth.shape[-1], "prepare_guidance")
         if object_labels is not None and pair_instances is not None:
             raise ValueError("object_labels and pair_instances are mutually exclusive")
         if object_weights is not None:
@@ -501,11 +505,15 @@ class GuidedStableDiffuser(GuidedDiffuser):
         fg_weight = self.conf.fg_weight if fg_weight is None else fg_weight
         bg_weight = self.conf.bg_weight if bg_weight is None else bg_weight
         st = SimpleNamespace()
-        if object_weights is None:
+        if object_weights is None and vacated is None:
             st.pc = self.process_correspondences(correspondences, img_res=depth.shape[-1], bg_erosion=self.conf.bg_erosion)
+        elif object_weights is None:
+            st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
+                                             device=self.device, vacated=vacated)
         else:
             st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
-                                             device=self.device, object_labels=object_labels, pair_instances=pair_instances)
+                                             device=self.device, vacated=vacated, object_labels=object_labels,
+                                             pair_instances=pair_instances)
         st.depth_nhwc = _nhwc(self.init_depth(depth.to(self.device, torch.float32))) if self.conf.use_depth else None
         st.cond = self._encode([prompt]).contiguous() if cond is None else cond
         GuidedStableDiffuser._text_keys += 1
@@ -723,18 +731,21 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def _batch_edit_steps(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                           fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None,
-                          object_weights=None, pair_instances=None, lock=None):
+                          object_weights=None, pair_instances=None, vacated=None, lock=None):
         """The batched edit as a generator: yields after the preparation and after every denoising step (everything is only
         ENQUEUED on the current stream by then), returns the final latents [K,4,H,W] through StopIteration.  One body for the
         one-stream call below and for the lanes of guided_inference_batch_lanes.  fg_weight / bg_weight: one value, or one per
         edit.  status_out: a list that receives the device [K, 4] status ('auto') at the end.  object_labels / object_weights: one
         label image and one weight list for all K edits (prepare_guidance).  lock: one (keep, trajectory) for all K edits or a list
         of K (prepare_guidance; None entries are unlocked edits).  pair_instances: None or a list of K, the instances of every
-        edit's correspondence rows (prepare_guidance)."""
+        edit's correspondence rows (prepare_guidance).  vacated: None, one image for all K edits or a list of K (None entries: edits that
+        delete nothing)."""
         K = len(depths)
         if pair_instances is not None and len(pair_instances) != K:
             raise ValueError(f"guided_inference_batch: pair_instances has {len(pair_instances)} entries for {K} edits")
         per = lambda w, i: w[i] if isinstance(w, (list, tuple)) else w
+        if isinstance(vacated, (list, tuple)) and len(vacated) != K:
+            raise ValueError(f"guided_inference_batch: vacated has {len(vacated)} entries for {K} edits")
         if self.unet.max_batch < 2 * K:
             raise RuntimeError(f"engine max_batch {self.unet.max_batch} < 2*K = {2 * K}")
         locks = self._locks(lock, K, "guided_inference_batch")
@@ -746,7 +757,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
             sts.append(self.prepare_guidance(d, prompt, activations_orig, c, per(fg_weight, i), per(bg_weight, i),
                                              orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond,
                                              object_labels=object_labels, object_weights=object_weights, lock=locks[i],
-                                             pair_instances=None if pair_instances is None else pair_instances[i]))
+                                             pair_instances=None if pair_instances is None else pair_instances[i],
+                                             vacated=per(vacated, i)))
         x = _nhwc(latents.to(self.device, torch.float32)).expand(K, -1, -1, -1).contiguous()
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -758,18 +770,20 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference_batch(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                fg_weight=None, bg_weight=None, object_labels=None, object_weights=None,
-                               pair_instances=None, lock=None):
+                               pair_instances=None, vacated=None, lock=None):
         """K edits of one image at once.  depths: list of K edited disparities [1,1,H,W]; correspondences_list:
         K [N_k,4] tensors; fg_weight / bg_weight: one value or K.  Needs an engine built with max_batch >= 2K.  Returns images
         [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value.  object_labels / object_weights: one
         label image and one weight list for all K edits (prepare_guidance).  lock: the background lock, one (keep, trajectory)
         for all K edits or a list of K (prepare_guidance).  pair_instances: None or a list of K, the instances of every edit's
-        correspondence rows, in place of the label image (prepare_guidance)."""
+        correspondence rows, in place of the label image (prepare_guidance).  vacated: None, one vacated image for all K edits
+        or a list of K with None for the edits that delete nothing (prepare_guidance; DESIGN.md "Object removal")."""
         status = []
         with torch.no_grad(), self.on_stream():
             gen = self._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                          fg_weight, bg_weight, status_out=status, object_labels=object_labels,
-                                         object_weights=object_weights, lock=lock, pair_instances=pair_instances)
+                                         object_weights=object_weights, lock=lock, pair_instances=pair_instances,
+                                         vacated=vacated)
             try:
                 while True:
                     next(gen)
@@ -786,7 +800,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         """K edits of DIFFERENT images at once.  items: K records (dicts with the keys ITEM_FIELDS, or tuples in that order), the
         arguments of guided_inference per item, plus optional object_labels (or pair_instances: an edit with copies) /
         object_weights (prepare_guidance: a multi-object edit with a weight per object) and an optional lock ((keep,
-        trajectory), prepare_guidance: locked and unlocked items may share a batch); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
+        trajectory), prepare_guidance: locked and unlocked items may share a batch) and an optional vacated (the image of the pixels the
+        item's removed objects leave behind, prepare_guidance: items with and without it share a batch); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
         tensors share one channels-last copy of them, items with the same prompt one encoding.  One resolution (the
         engine's); needs max_batch >= 2K and max_diff_batch >= K, raises otherwise (never splits).  Returns images [K,3,H,W]
         in item order and sets last_latents; 'auto' grad_scale: FloatingPointError naming the items that met a non-finite
@@ -818,7 +833,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 st = self.prepare_guidance(it["depth"], it["prompt"], it["activations_orig"], it["correspondences"],
                                            per(fg_weight, i), per(bg_weight, i), orig=origs.get(okey), cond=conds.get(it["prompt"]),
                                            object_labels=it.get("object_labels"), object_weights=it.get("object_weights"),
-                                           lock=locks[i], pair_instances=it.get("pair_instances"))
+                                           lock=locks[i], pair_instances=it.get("pair_instances"), vacated=it.get("vacated"))
                 origs[okey], conds[it["prompt"]] = st.orig, st.cond
                 sts.append(st)
             x = torch.cat([_nhwc(it["latents"].to(self.device, torch.float32)) for it in items]).contiguous()
@@ -924,16 +939,19 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference_batch_lanes(self, latents, chunks, uncond_embeddings, prompt, activations_orig, streams=2,
                                      fg_weight=None, bg_weight=None, object_labels=None, object_weights=None,
-                                     pair_instances=None, lock=None):
+                                     pair_instances=None, vacated=None, lock=None):
         """Batched edits of one image on `streams` concurrent lanes.  chunks: list of (depths, correspondences_list), each the
         argument pair of one guided_inference_batch call; chunk i runs on lane i % streams.  Every lane executes exactly the
         passes the one-stream call executes for its chunk (same batch, same kernels, private arenas), so the images are
         bit-identical to guided_inference_batch chunk by chunk.  Returns one image tensor [K_i,3,H,W] per chunk.
         object_labels / object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one
         (keep, trajectory) for every edit, or a list with one entry per edit over the chunks in order.  pair_instances: None or
-        one list per chunk (guided_inference_batch)."""
+        one list per chunk (guided_inference_batch).  vacated: None, one image for every edit, or one entry per chunk (each None, an
+        image or a list, as guided_inference_batch takes it)."""
         if pair_instances is not None and len(pair_instances) != len(chunks):
             raise ValueError(f"guided_inference_batch_lanes: pair_instances has {len(pair_instances)} entries for {len(chunks)} chunks")
+        if isinstance(vacated, (list, tuple)) and len(vacated) != len(chunks):
+            raise ValueError(f"guided_inference_batch_lanes: vacated has {len(vacated)} entries for {len(chunks)} chunks")
         kmax = max(len(d) for d, _ in chunks)
         if self.unet.max_batch < 2 * kmax:
             # lane 0 is THIS diffuser: it could not run its chunk, and forks sized 2 * kmax would be made for nothing
@@ -947,18 +965,20 @@ class GuidedStableDiffuser(GuidedDiffuser):
             offs = np.cumsum([0] + [len(d) for d, _ in chunks])
             locks = self._locks(lock, int(offs[-1]), "guided_inference_batch_lanes")
 
-            def make(depths, corrs, status, lk, inst):
+            def make(depths, corrs, status, lk, inst, vac):
                 def job(lane):
                     def body():
                         lat = yield from lane._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig,
                                                                 corrs, fg_weight, bg_weight, cond=cond, orig=orig,
                                                                 status_out=status, object_labels=object_labels,
-                                                                object_weights=object_weights, lock=lk, pair_instances=inst)
+                                                                object_weights=object_weights, lock=lk, pair_instances=inst,
+                                                                vacated=vac)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
+            vac_of = lambda i: vacated[i] if isinstance(vacated, (list, tuple)) else vacated
             images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, locks[int(offs[i]):int(offs[i + 1])],
-                                                                 None if pair_instances is None else pair_instances[i])
+                                                                 None if pair_instances is None else pair_instances[i], vac_of(i))
                                                             for i, ((d, c), s) in enumerate(zip(chunks, statuses))])
             if any(statuses):      # edits numbered over the chunks in order; read after every lane has finished
                 self.raise_on_status([(int(offs[i]) + b, row) for i, s in enumerate(statuses)
@@ -967,7 +987,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def _edit_steps(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences, fg_weight=None,
                     bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None, object_weights=None,
-                    pair_instances=None, lock=None):
+                    pair_instances=None, vacated=None, lock=None):
         """One edit as a generator (see _batch_edit_steps): yields after the preparation and after every denoising step,
         returns the final latents [1,4,H,W].  lock: the edit's background lock (prepare_guidance)."""
         torch.manual_seed(self.conf.seed)
@@ -975,7 +995,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
         timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
         st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight, orig=orig, cond=cond,
                                    object_labels=object_labels, object_weights=object_weights, lock=lock,
-                                   pair_instances=pair_instances)
+                                   pair_instances=pair_instances, vacated=vacated)
         x = _nhwc(latents.to(self.device, torch.float32))
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -986,15 +1006,17 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_lanes(self, latents, edits, uncond_embeddings, prompt, activations_orig, streams=2, fg_weight=None,
-                               bg_weight=None, object_labels=None, object_weights=None, pair_instances=None, lock=None):
+                               bg_weight=None, object_labels=None, object_weights=None, pair_instances=None, vacated=None, lock=None):
         """Single (B = 1) edits of one image on `streams` concurrent lanes.  edits: list of (depth, correspondences), the
         argument pair of guided_inference; edit i runs on lane i % streams with exactly the passes guided_inference runs, so
         the images are bit-identical to the one-stream calls.  Returns a list of images [1,3,H,W].  object_labels /
         object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one (keep, trajectory)
         for every edit, or a list with one entry per edit.  pair_instances: None or a list with one entry per edit
-        (prepare_guidance)."""
+        (prepare_guidance).  vacated: None, one image for every edit, or a list with one entry per edit (prepare_guidance)."""
         if pair_instances is not None and len(pair_instances) != len(edits):
             raise ValueError(f"guided_inference_lanes: pair_instances has {len(pair_instances)} entries for {len(edits)} edits")
+        if isinstance(vacated, (list, tuple)) and len(vacated) != len(edits):
+            raise ValueError(f"guided_inference_lanes: vacated has {len(vacated)} entries for {len(edits)} edits")
         lanes = self.lanes(min(int(streams), len(edits)))
         statuses = [[] for _ in edits]
         with torch.no_grad(), self.on_stream():
@@ -1002,37 +1024,39 @@ class GuidedStableDiffuser(GuidedDiffuser):
             orig = [a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in activations_orig]
             locks = self._locks(lock, len(edits), "guided_inference_lanes")      # (on this stream, which every lane waits for)
 
-            def make(depth, corr, status, lk, inst):
+            def make(depth, corr, status, lk, inst, vac):
                 def job(lane):
                     def body():
                         lat = yield from lane._edit_steps(latents, depth, uncond_embeddings, prompt, activations_orig, corr,
                                                           fg_weight, bg_weight, cond=cond, orig=orig, status_out=status,
                                                           object_labels=object_labels, object_weights=object_weights, lock=lk,
-                                                          pair_instances=inst)
+                                                          pair_instances=inst, vacated=vac)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
             insts = [None] * len(edits) if pair_instances is None else pair_instances
-            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, lk, n)
-                                                            for (d, c), s, lk, n in zip(edits, statuses, locks, insts)])
+            vacs = list(vacated) if isinstance(vacated, (list, tuple)) else [vacated] * len(edits)
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, lk, n, v)
+                                                            for (d, c), s, lk, n, v in zip(edits, statuses, locks, insts, vacs)])
             if any(statuses):      # read after every lane has finished
                 self.raise_on_status([(i, s[0][0].cpu().tolist()) for i, s in enumerate(statuses)])
         return images
 
     def guided_inference(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences,
                          fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None, object_labels=None,
-                         object_weights=None, pair_instances=None, lock=None):
+                         object_weights=None, pair_instances=None, vacated=None, lock=None):
         """object_labels (or pair_instances, the instance of every correspondence row of an edit with copies) / object_weights:
         a weight per object for the foreground term (prepare_guidance).  lock: (keep,
         trajectory), the background lock -- after every DDIM step the latents are blended with the reconstruction's outside
-        the edit's region (prepare_guidance; DESIGN.md "Background lock")."""
+        the edit's region (prepare_guidance; DESIGN.md "Background lock").  vacated: the image of the pixels the edit's removed
+        objects leave behind (prepare_guidance; DESIGN.md "Object removal")."""
         with torch.no_grad(), self.on_stream():
             torch.manual_seed(self.conf.seed)
             self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
             timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
             st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight,
                                        object_labels=object_labels, object_weights=object_weights, lock=lock,
-                                       pair_instances=pair_instances)
+                                       pair_instances=pair_instances, vacated=vacated)
             denoising_steps = {"opt": [], "post-opt": []} if save_denoising_steps else None
             x = _nhwc(latents.to(self.device, torch.float32))
             for t_idx, t in enumerate(timesteps):

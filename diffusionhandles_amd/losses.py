@@ -77,7 +77,18 @@ def object_omegas(objects, weights):
     return counts, omega
 
 
-def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, object_labels=None,
+def check_vacated(vacated, img_res, what="process_correspondences"):
+    """The vacated image of an edit that deletes objects -> None or an [img_res, img_res] tensor (non-zero = vacated).
+    ValueError naming `what` for another shape.  Host only: it reads the shape."""
+    if vacated is None:
+        return None
+    v = torch.as_tensor(vacated)
+    if v.numel() != int(img_res) * int(img_res) or v.shape[-1] != int(img_res):
+        raise ValueError(f"{what}: vacated has shape {tuple(v.shape)}, expected one {img_res} x {img_res} image")
+    return v.reshape(int(img_res), int(img_res))
+
+
+def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, vacated=None, object_labels=None,
                             pair_instances=None):
     """[N,4] int64 (ox,oy,tx,ty) -> dict with original_x/y, transformed_x/y, background_x/y[_orig|_trans].
     object_labels ([H, W] uint8, object_label_image): adds "object", the 0-based object of every kept pair (int64, host), and
@@ -85,7 +96,12 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
     pair_instances ([N] uint8, the instance of every correspondence row -- edits with copies of an object, where a source pixel
     belongs to several instances and a label image cannot say which): filtered with the validity test of the rows, it fills the
     same "object" / `pair_obj`; an "object" of the energy is then an instance.  ValueError when both are given or when it does
-    not have N entries, before any device work."""
+    not have N entries, before any device work.
+    vacated ([img_res, img_res], non-zero on the pixels of the objects the edit DELETES; DESIGN.md "Object removal"): a cell that
+    holds a vacated pixel leaves the original-background list as if a kept correspondence started in it, before the erosion;
+    the transformed-background list and the pairs do not see it.  None is the call without it (an all-zero image gives the
+    same lists); the correspondences may then be empty (the pure removal).  The keys of the dict do not change."""
+    vacated = check_vacated(vacated, img_res)
     if object_labels is not None and pair_instances is not None:
         raise ValueError("process_correspondences: object_labels and pair_instances are mutually exclusive")
     if pair_instances is not None:
@@ -107,10 +123,13 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
     nbytes = ctypes.c_size_t()
     _lib.check(L.dh_cells_workspace_bytes(n, grid, ctypes.byref(nbytes)), "dh_cells_workspace_bytes")
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-    _lib.check(L.dh_cells_from_correspondences(_lib.ptr(corr) if n else _lib.c_p(0), n, int(img_res), grid,
-                                               int(bg_erosion), _lib.ptr(pairs), _lib.ptr(bg_lists),
-                                               _lib.ptr(bg_masks), _lib.ptr(counts), _lib.ptr(ws), nbytes.value,
-                                               _lib.stream_ptr()), "dh_cells_from_correspondences")
+    args = (_lib.ptr(corr) if n else _lib.c_p(0), n, int(img_res), grid, int(bg_erosion), _lib.ptr(pairs), _lib.ptr(bg_lists),
+            _lib.ptr(bg_masks), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, _lib.stream_ptr())
+    if vacated is None:
+        _lib.check(L.dh_cells_from_correspondences(*args), "dh_cells_from_correspondences")
+    else:
+        vac = (vacated.to(dev) != 0).to(torch.uint8).contiguous()
+        _lib.check(L.dh_cells_from_correspondences_vacated(*args, _lib.ptr(vac)), "dh_cells_from_correspondences_vacated")
     c = counts.cpu().tolist()
     pairs = pairs[:c[0]].contiguous()
     lists = [bg_lists[k, :c[1 + k]].contiguous() for k in range(3)]

@@ -460,12 +460,76 @@ def entry_instances(objects, n_masks=None, where="objects"):
     return inst
 
 
+def _is_removal(o):
+    return isinstance(o, dict) and "remove" in o
+
+
+def entry_removal(objects, n_masks=None, where="objects"):
+    """Object removal in an "objects" list (not in the reference): a member {"remove": true} deletes the mask of its own position.
+    Returns None when no member carries "remove" (the list is then read as always), else (removed, members, instances):
+    the removed mask indices in order, the remaining members in order, and the mask index of every remaining member COUNTED
+    AMONG THE REMAINING MASKS (its "mask", or its own position) -- None when that is 0, 1, 2 ... (no table needed).
+    ValueError naming `where` and the member: "remove" that is not true, a removing member with any other key (a transform
+    key, "mask"), a member that names a removed mask, and, when n_masks is given, a removing member beyond the masks, more than
+    8 remaining members, a mask index outside the scene's or a remaining mask that no member draws."""
+    if not any(_is_removal(o) for o in objects):
+        return None
+    removed, members, inst = [], [], []
+    for n, o in enumerate(objects):
+        if _is_removal(o):
+            if o["remove"] is not True:
+                raise ValueError(f"{where}, object {n}: \"remove\" must be true, got {o['remove']!r}")
+            if len(o) != 1:
+                other = sorted(k for k in o if k != "remove")
+                raise ValueError(f"{where}, object {n}: a removed object takes no other key, got {other}")
+            if n_masks is not None and n >= n_masks:
+                raise ValueError(f"{where}, object {n}: \"remove\" deletes the mask of its own position, the scene has "
+                                 f"{n_masks} object masks")
+            removed.append(n)
+    for n, o in enumerate(objects):
+        if _is_removal(o):
+            continue
+        m = o.get("mask", n) if isinstance(o, dict) else n
+        if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+            raise ValueError(f"{where}, object {n}: \"mask\" must be the index of a mask (an integer >= 0), got {m!r}")
+        if m in removed:
+            raise ValueError(f"{where}, object {n}: draws mask {m}, which object {m} removes")
+        members.append(o)
+        inst.append(m)
+    if n_masks is not None:
+        if len(inst) > MAX_SCENE_OBJECTS:
+            raise ValueError(f"{where} lists {len(inst)} instances, at most {MAX_SCENE_OBJECTS} are supported")
+        for o, m in zip(members, inst):
+            if m >= n_masks:
+                raise ValueError(f"{where}: mask {m} does not exist, the scene has {n_masks} object masks")
+        for m in range(n_masks):
+            if m not in inst and m not in removed:
+                raise ValueError(f"{where}: no object draws mask {m} (an object is removed by {{\"remove\": true}} at its position)")
+    inst = [m - sum(1 for r in removed if r < m) for m in inst]
+    return removed, members, (None if inst == list(range(len(inst))) else inst)
+
+
 def _check_object_entries(scene_dir, transforms, n_masks):
     """transforms.json against the scene's masks: a multi-mask scene (n_masks >= 1 mask_m.png files) wants {"objects": [n_masks
     entries]} everywhere -- or, when members carry "mask" (copies of an object, entry_instances), n_masks to 8 entries that
     draw every mask -- a single-mask scene (n_masks = 0) no "objects" at all.  ValueError naming the scene and the entry."""
     for name, t in transforms.items():
         has = isinstance(t, dict) and "objects" in t
+        if n_masks == 0 and _is_removal(t):          # a single-mask scene: {"remove": true} deletes the one object
+            if t["remove"] is not True or len(t) != 1:
+                raise ValueError(f"{scene_dir}: transform {name!r}: an entry that removes the object is exactly "
+                                 f"{{\"remove\": true}}, got {dict(t)!r}")
+            continue
+        if n_masks > 0 and has and isinstance(t["objects"], (list, tuple)):
+            rem = entry_removal(t["objects"], n_masks, f"{scene_dir}: transform {name!r}")
+            if rem is not None:
+                w = t.get("object_weights")
+                if isinstance(w, (list, tuple)) and len(w) != len(rem[1]):
+                    raise ValueError(f"{scene_dir}: transform {name!r} has {len(w)} object_weights for {len(rem[1])} remaining "
+                                     "objects")
+                if not rem[1] and w is not None:
+                    raise ValueError(f"{scene_dir}: transform {name!r} removes every object and gives object_weights")
+                continue
         if n_masks == 0:
             if has:
                 raise ValueError(f"{scene_dir}: transform {name!r} has \"objects\" but the scene has one mask (mask.png, no mask_0.png)")
@@ -514,6 +578,8 @@ def _check_similarity_entry(where, t):
 def _check_similarity_entries(scene_dir, transforms):
     """Every entry of transforms.json, and every member of its "objects" list."""
     for name, t in transforms.items():
+        if isinstance(t, dict) and "remove" in t and "objects" in t:
+            raise ValueError(f"{scene_dir}: transform {name!r}: \"remove\" belongs inside a member of \"objects\"")
         _check_similarity_entry(f"{scene_dir}: transform {name!r}", t)
         if isinstance(t, dict) and isinstance(t.get("objects"), (list, tuple)):
             for m, o in enumerate(t["objects"]):
@@ -534,7 +600,11 @@ def load_scene_geometry(scene_dir, img_res=512):
     A member of "objects" may carry "mask": m (not in the reference; copies of an object): it is then one more INSTANCE of mask
     m, and the list may be longer than the number of masks (at most 8, every mask drawn by some member; members without "mask"
     keep their own position's mask).  "object_weights" then has one entry per member.  Lists without any "mask" give exactly
-    what they gave before."""
+    what they gave before.
+    A member of "objects" may be {"remove": true} (not in the reference; object removal): it deletes the mask of its own position
+    -- it carries no transform key and no "mask", and no other member may name its mask; "object_weights" lists have one entry
+    per remaining member.  In a single-mask scene the entry {"remove": true} deletes the one object.  bg_depth has the removed
+    objects removed, as it has all objects.  Files without "remove" load to exactly what they loaded to."""
     import torch
     j = os.path.join
     with open(j(scene_dir, "transforms.json")) as f:
@@ -600,8 +670,13 @@ def load_scene(scene_dir, img_res=512):
 
 def transform_args(t):
     """One transforms.json entry -> keyword arguments of `transform_foreground` (test_diffusion_handles.py:137-150).  `scale`
-    (a float or three) / `pivot` (three floats) only when the entry has "scale" / "pivot" (not in the reference)."""
+    (a float or three) / `pivot` (three floats) only when the entry has "scale" / "pivot" (not in the reference).  The entry
+    {"remove": true} (object removal) gives dict(remove=True) and nothing else."""
     import torch
+    if _is_removal(t):          # a single-mask scene's {"remove": true}: the edit deletes the object (no transform)
+        if t["remove"] is not True or len(t) != 1:
+            raise ValueError(f"transform_args: an entry that removes the object is exactly {{\"remove\": true}}, got {dict(t)!r}")
+        return dict(remove=True)
     _check_similarity_entry("transform_args", t)
     args = dict(rot_angle=float(t.get("rotation_angle", 0.0)),
                 rot_axis=torch.tensor(t.get("rotation_axis", [0.0, 1.0, 0.0]), dtype=torch.float32),
@@ -618,16 +693,22 @@ def object_transform_args(entry):
     the `transforms` / `object_weights` keyword arguments of `transform_foreground_objects`: M (rot_angle, rot_axis,
     translation) triples in mask order (`{}` leaves an object in place) and None, "equal" or a list of floats.  An object
     whose entry has "scale" or "pivot" gives the 5-tuple (rot_angle, rot_axis, translation, scale, pivot) instead.  When a
-    member carries "mask" (entry_instances) the dict also has `instances`, the mask index of every member."""
+    member carries "mask" (entry_instances) the dict also has `instances`, the mask index of every member.  When a member is
+    {"remove": true} (entry_removal) the dict also has `remove`, the mask indices the edit deletes; transforms, weights and
+    `instances` then speak about the remaining members and the remaining masks."""
     if not isinstance(entry, dict) or "objects" not in entry:
         raise ValueError("object_transform_args: the entry has no \"objects\" list")
+    rem = entry_removal(entry["objects"], None, "object_transform_args")
+    members = entry["objects"] if rem is None else rem[1]
     triples = []
-    for t in entry["objects"]:
+    for t in members:
         a = transform_args(t)
         triple = (a["rot_angle"], a["rot_axis"], a["translation"])
         triples.append(triple + (a.get("scale"), a.get("pivot")) if "scale" in a or "pivot" in a else triple)
     w = entry.get("object_weights")
     if w is not None and not isinstance(w, str):
         w = [float(v) for v in w]
+    if rem is not None:          # `remove`: the scene's mask indices the edit deletes; `instances` counts among the remaining masks
+        return dict(transforms=triples, object_weights=w, remove=rem[0], **({} if rem[2] is None else dict(instances=rem[2])))
     inst = entry_instances(entry["objects"], None, "object_transform_args")
     return dict(transforms=triples, object_weights=w, **({} if inst is None else dict(instances=inst)))

@@ -162,6 +162,21 @@ int dh_reproject_instance_edits(const float* depth, const float* bg_depth, const
                                 void* workspace, size_t workspace_bytes, void* stream,
                                 int footprints, float max_ratio, int corr_capacity,
                                 int n_instances, const int32_t* inst_obj, uint8_t* corr_inst);
+/* Object removal, the pure case (not in the reference; DESIGN.md, "Object removal"): the re-projection of the background
+ * alone, for an edit that deletes its objects and moves none.  The point list is the res * res pixels of bg_depth; it runs the
+ * kernels of the entries above on that part of the list: z-buffer (winner = min (z, point index)), zmap (+inf where no point
+ * landed), disparity 1 / z normalised with bounds (device f32[2]) or, bounds NULL, with its own min and max, and the harmonic
+ * in-fill of the pixels NO point owns (nothing is foreground: the raw and the cleaned mask are zero and are not written).
+ *   zmap, disparity [res][res] f32;  counts [4] i32: {0, 0, pixels in-filled, CG iterations (negative: the in-fill failed,
+ *   as in the entries above)}
+ * It is NOT the empty-mask result (the normalised INPUT disparity), which the host computes without this library.
+ * DH_ERR_ARG before any launch, outputs untouched: a null pointer, res outside 2 .. 32768, a workspace smaller than
+ * dh_reproject_background_workspace_bytes'. */
+int dh_reproject_background_workspace_bytes(int res, size_t* bytes);
+int dh_reproject_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                            float inv_fx, float inv_fy, double fx, double fy, const float* bounds,
+                            float* zmap, float* disparity, int32_t* counts,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);
@@ -194,6 +209,16 @@ int dh_cells_workspace_bytes(int n, int grid, size_t* bytes);
 int dh_cells_from_correspondences(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
                                   int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
                                   void* workspace, size_t workspace_bytes, void* stream);
+/* Object removal (not in the reference; DESIGN.md, "Object removal"): dh_cells_from_correspondences with
+ * vacated [img_res][img_res] u8 (may be NULL), non-zero on the pixels of the objects an edit deletes.  A cell that holds a
+ * vacated pixel is cleared from the ORIGINAL-background mask, as if a kept correspondence started in it, BEFORE the erosion;
+ * the transformed-background mask and the pairs do not see it, both = orig & trans as before.  n = 0 with an image is the
+ * pure removal.  vacated NULL (and an all-zero image) is dh_cells_from_correspondences in every output byte, which is this
+ * entry's NULL call; the workspace is dh_cells_workspace_bytes'.  DH_ERR_ARG before any launch, outputs untouched. */
+int dh_cells_from_correspondences_vacated(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                          int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                          void* workspace, size_t workspace_bytes, void* stream,
+                                          const uint8_t* vacated);
 
 /* Keep map of the background lock: keep [s][s] f32, 0 inside the region an edit touches, 1 far from it, a ramp between.
  * A latent cell (res / s pixels square) is a REGION cell if one of its pixels is non-zero in mask or release (u8 [res][res],

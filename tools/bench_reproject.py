@@ -8,7 +8,10 @@ DH_FOOTPRINTS=1 (default unset; combinable with DH_SCALE / DH_OBJECTS): every ti
 footprint splatting on (profiles/footprints/).  DH_STEP=1: instead of the spheres, K copies of the step-scene edit of
 tests/footprints_ref.py with footprints on, once per tier threshold of DH_TIERS (comma-separated; 0 = the default).
 DH_COPIES=c (default unset; M * c <= 8): a further line times the call with c instances of every sphere (object copies: copy k
-of an object takes another of the bench transforms and is lifted by 0.4 k, so the copies do not coincide)."""
+of an object takes another of the bench transforms and is lifted by 0.4 k, so the copies do not coincide).
+DH_REMOVE=1 (default unset; the two-sphere scene whatever DH_OBJECTS says): two further lines time the K = 8 call with sphere 1
+removed and sphere 0 moved (reproject_removal_edits), and the pure removal of both spheres (the background alone, computed
+once for the K edits)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -102,6 +105,19 @@ if copies:
     report(inst_call, f" copies={copies} (instances {inst})")
     if footprints:
         report(inst_call, f" copies={copies} (instances {inst})", footprints=True)
+if os.environ.get("DH_REMOVE", "0") not in ("", "0"):
+    from diffusionhandles_amd.depth_transform import reproject_removal_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    r_depth, r_bg, r_masks = R.two_spheres(res)
+    r_depth, r_bg, r_masks = r_depth.to(dev), r_bg.to(dev), [m.to(dev) for m in r_masks]
+    M_shown, M = M, 1
+    report(lambda **kw: reproject_removal_edits(r_depth, r_bg, r_masks[:1], intr, [[tf] for tf in tfs], removed_masks=r_masks[1:], **kw),
+           " two spheres, sphere 1 removed")
+    M = 0
+    report(lambda **kw: reproject_removal_edits(r_depth, r_bg, [], intr, [[]] * K, removed_masks=r_masks, **kw),
+           " two spheres, pure removal")
+    M = M_shown
 if scale is not None:
     if M == 1:
         tfs = [tf + (scale, None) for tf in tfs]

@@ -286,6 +286,12 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
         sc = load_scene(scene, args.res)
         img, depth, bg_depth, mask, prompt, res = sc["img"], sc["depth"], sc["bg_depth"], sc["fg_mask"], sc["prompt"], args.res
         masks = sc.get("fg_masks")
+        if args.mode != "pc":           # object removal: before the identity is computed
+            for n, t in sc["transforms"].items():
+                objs = t.get("objects") if isinstance(t, dict) else None
+                if (isinstance(t, dict) and "remove" in t) or any(isinstance(o, dict) and "remove" in o for o in objs or []):
+                    raise NotImplementedError(f"{scene}: transform {n!r} removes an object (\"remove\"); --mode {args.mode} has "
+                                              "no object removal, use --mode pc")
         if masks is not None and args.mode != "pc":
             from diffusionhandles_amd.scene_io import entry_instances
             for n, t in sc["transforms"].items():          # (copies of an object: named for what they are)
@@ -406,6 +412,14 @@ def write_scene_pages(args, out, img, mask, depth, bg_depth, prompt, res, report
                 f"({res}x{res}, {args.mode})</h3><table border='1' cellspacing='0' cellpadding='4'><tr>{head}</tr>{''.join(rows)}</table></body></html>")
 
 
+def split_removed(masks, remove):
+    """The masks of a multi-object scene as the keywords of an edit call: fg_masks (what the entry leaves) and, for an entry
+    with {"remove": true} members (object_transform_args' `remove`), removed_masks."""
+    if not remove:
+        return dict(fg_masks=masks)
+    return dict(fg_masks=[m for i, m in enumerate(masks) if i not in remove], removed_masks=[masks[i] for i in remove])
+
+
 def run_test_set_batched(args, conf, handles, names, input_dir):
     """--edit-batch K: the edits of every scene that are still to do (--skip-existing), packed K at a time over the scenes in
     test-set order; a batch's scenes keep their identities resident while it runs, a finished scene's identity is dropped.
@@ -457,8 +471,10 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
             if prep[s].get("release") is not None:          # (--background-lock: the scene's release.png)
                 common["release_mask"] = prep[s]["release"]
             if r["fg_masks"] is not None:
-                edits.append(dict(common, fg_masks=r["fg_masks"], transforms=tf["transforms"], object_weights=tf["object_weights"],
-                                  instances=tf.get("instances")))
+                edits.append(dict(common, **split_removed(r["fg_masks"], tf.get("remove")), transforms=tf["transforms"],
+                                  object_weights=tf["object_weights"], instances=tf.get("instances")))
+            elif tf.get("remove"):          # a single-mask scene's {"remove": true}: a pure removal
+                edits.append(dict(common, fg_masks=[], transforms=[], removed_masks=[r["fg_mask"]]))
             else:
                 edits.append(dict(common, fg_mask=r["fg_mask"], rot_angle=tf["rot_angle"], rot_axis=tf["rot_axis"],
                                   translation=tf["translation"], scale=tf.get("scale"), pivot=tf.get("pivot")))
@@ -508,9 +524,14 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
         t0 = time.time()
         if p.get("masks_dev") is not None:
             rel = {} if p.get("release") is None else dict(release_mask=p["release"])
-            res_ = dh.transform_foreground_objects(depth, prompt, p["masks_dev"], bg_depth, null_text, noise, acts,
+            sp = split_removed(p["masks_dev"], tf.get("remove"))
+            res_ = dh.transform_foreground_objects(depth, prompt, sp["fg_masks"], bg_depth, null_text, noise, acts,
                                                    transforms=tf["transforms"], object_weights=tf["object_weights"],
-                                                   instances=tf.get("instances"), **rel)
+                                                   removed_masks=sp.get("removed_masks"), instances=tf.get("instances"), **rel)
+        elif tf.get("remove"):          # a single-mask scene's {"remove": true}: a pure removal
+            rel = {} if p.get("release") is None else dict(release_mask=p["release"])
+            res_ = dh.transform_foreground_objects(depth, prompt, [], bg_depth, null_text, noise, acts, transforms=[],
+                                                   removed_masks=[mask], **rel)
         elif p.get("release") is not None:
             # (transform_foreground keeps the reference's parameter list: a release mask goes through the one-mask form of
             #  transform_foreground_objects, the same edit in 'pc' mode)

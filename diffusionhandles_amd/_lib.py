@@ -239,6 +239,26 @@ DEBUG_SIGNATURES = {
     "dh_dbg_cg_limits": (c_i, [ctypes.POINTER(c_i)]),
     "dh_dbg_cg_max_iter": (c_i, [c_i]),
     "dh_dbg_footprint_tier": (c_i, [c_i]),
+    # hooks of the kernels only the engines launch (tests/test_engine_kernels_gpu.py)
+    # dh_dbg_gemm's arguments with `pad` behind `up`
+    "dh_dbg_gemm_pad": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i,
+                              c_p, c_l, c_p, c_l, c_i, c_p, c_sz, c_p]),
+    # (dtype, q, ldq, k, v, ldk, o, ldo, lse, B, H, Nq, Nk, stream)
+    "dh_dbg_attention_causal": (c_i, [c_i, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_p]),
+    # (dtype, qkv, ld, N, C, out, tiled, scores, partial, partial_elems, stream)
+    "dh_dbg_vae_attention": (c_i, [c_i, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "dh_dbg_softmax_rows": (c_i, [c_i, c_p, c_i, c_i, c_p]),
+    # (dtype, bwd, x, x_is_f32, w, bias, y, y_is_f32, accumulate, B, H, W, Cin, Cout, stream)
+    "dh_dbg_conv_small": (c_i, [c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    # dh_dbg_groupnorm's arguments, then (out0, out1, split_c, stream)
+    "dh_dbg_groupnorm_split": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_i, c_p]),
+    "dh_dbg_gelu": (c_i, [c_i, c_p, c_p, c_sz, c_p]),
+    "dh_dbg_copy_cols": (c_i, [c_i, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p]),
+    # (dtype, src, lds, dstA, ldA, colsA, accA, dstB, ldB, colsB, accB, rows, stream)
+    "dh_dbg_split_cols": (c_i, [c_i, c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_l, c_i, c_i, c_i, c_p]),
+    # (dtype, to_f32, src, dst, n, accumulate, stream)
+    "dh_dbg_convert": (c_i, [c_i, c_i, c_p, c_p, c_sz, c_i, c_p]),
+    "dh_dbg_timestep": (c_i, [c_i, c_p, c_i, c_i, c_p, c_p]),
 }
 
 

@@ -21,10 +21,12 @@ extern "C" int dh_dbg_touch_tiled(size_t bytes, void* stream) {
   return DH_OK;
 }
 
-extern "C" int dh_dbg_gemm(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
-                           int Win, int Cin, int Hout, int Wout, int stride, int up, const float* bias,
-                           const float* rowvec, int rowvec_ld, int rows_per_batch, const void* R, long ldr, void* C,
-                           long ldc, int act_silu, float* partial, size_t partial_elems, void* stream) {
+// dh_dbg_gemm with the convolution's top / left zero padding as an argument (GemmArgs::pad; 0 with stride 2 = the VAE encoder's
+// down-sampler, which pads bottom / right only)
+extern "C" int dh_dbg_gemm_pad(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
+                               int Win, int Cin, int Hout, int Wout, int stride, int up, int pad, const float* bias,
+                               const float* rowvec, int rowvec_ld, int rows_per_batch, const void* R, long ldr, void* C,
+                               long ldc, int act_silu, float* partial, size_t partial_elems, void* stream) {
   DH_REQUIRE(A && W && C && K % 64 == 0 && N % 64 == 0, "bad arguments (N, K must be multiples of 64)");
   // the hook takes plain [N][K] weights and tiles them into a scratch buffer first
   void*& tiled = g_dbg_tiled;
@@ -42,12 +44,20 @@ extern "C" int dh_dbg_gemm(int dtype, const void* A, long lda, const void* W, in
   tiled_from = W;
   GemmArgs g;
   g.A = A; g.lda = lda; g.W = tiled; g.M = M; g.N = N; g.K = K; g.mode = mode; g.Hin = Hin; g.Win = Win; g.Cin = Cin;
-  g.Hout = Hout; g.Wout = Wout; g.stride = stride; g.up = up; g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld;
+  g.Hout = Hout; g.Wout = Wout; g.stride = stride; g.up = up; g.pad = pad; g.bias = bias; g.rowvec = rowvec; g.rowvec_ld = rowvec_ld;
   g.rows_per_batch = rows_per_batch; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc; g.act_silu = act_silu;
   g.partial = partial; g.partial_elems = partial_elems;
   launch_gemm(dtype, g, (hipStream_t)stream);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+// ... with the usual padding of 1 (the hook's original signature, kept for its existing callers)
+extern "C" int dh_dbg_gemm(int dtype, const void* A, long lda, const void* W, int M, int N, int K, int mode, int Hin,
+                           int Win, int Cin, int Hout, int Wout, int stride, int up, const float* bias,
+                           const float* rowvec, int rowvec_ld, int rows_per_batch, const void* R, long ldr, void* C,
+                           long ldc, int act_silu, float* partial, size_t partial_elems, void* stream) {
+  return dh_dbg_gemm_pad(dtype, A, lda, W, M, N, K, mode, Hin, Win, Cin, Hout, Wout, stride, up, 1, bias, rowvec, rowvec_ld,
+                         rows_per_batch, R, ldr, C, ldc, act_silu, partial, partial_elems, stream);
 }
 // GEMM (dense or 3x3 convolution) followed by the GroupNorm(+SiLU) of its output, the way the engine's forward runs the pair: the
 // GroupNorm's slice statistics come from the GEMM launch when it can leave them (split-K reduce, or -- round 6 -- the epilogue of an
@@ -419,6 +429,78 @@ extern "C" int dh_dbg_pool2x2(int dtype, const void* src, void* dst, int B, int 
 }
 extern "C" int dh_dbg_lane_ops(const float* in, float* out, unsigned* ex, void* stream) {
   launch_lane_ops_probe(in, out, ex, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// ---- hooks for the kernels that only the engines launch (tests/test_engine_kernels_gpu.py)
+// the forward with the causal mask (text tower: key j visible to query i for j <= i); lse may be NULL, as the text engine passes it
+extern "C" int dh_dbg_attention_causal(int dtype, const void* q, long ldq, const void* k, const void* v, long ldk, void* o, long ldo,
+                                       float* lse, int B, int H, int Nq, int Nk, void* stream) {
+  DH_REQUIRE(q && k && v && o, "bad arguments");
+  launch_attention_fwd(dtype, q, ldq, k, v, ldk, o, ldo, lse, B, H, Nq, Nk, (hipStream_t)stream, 1);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// the two tiny-channel convolutions through their launchers: bwd = 0 launch_conv_small_fwd (x_is_f32 picks few-in, else few-out),
+// bwd = 1 launch_conv_small_bwd (x = dy, y = dx, w = the gradient convolution's weights, Cin / Cout those of that convolution;
+// bias and y_is_f32 as the kernel implies).  A shape the launcher refuses comes back as DH_ERR_ARG with its message, nothing launched.
+extern "C" int dh_dbg_conv_small(int dtype, int bwd, const void* x, int x_is_f32, const float* w, const float* bias, void* y,
+                                 int y_is_f32, int accumulate, int B, int H, int W, int Cin, int Cout, void* stream) {
+  DH_REQUIRE(x && w && y && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "bad arguments");
+  DH_REQUIRE(x_is_f32 ? (!y_is_f32 && Cin <= 8) : y_is_f32 != 0, "few-in: f32 -> 16-bit, Cin <= 8; few-out: 16-bit -> f32");
+  set_error("");
+  if (bwd) launch_conv_small_bwd(dtype, x, x_is_f32, w, y, y_is_f32, accumulate, B, H, W, Cin, Cout, (hipStream_t)stream);
+  else launch_conv_small_fwd(dtype, x, x_is_f32, w, bias, y, y_is_f32, B, H, W, Cin, Cout, (hipStream_t)stream);
+  if (dh_last_error()[0]) return DH_ERR_ARG;
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// dh_dbg_groupnorm with the backward's split form: out0 != NULL sends columns [0, split_c) of the gradient to out0 (row pitch
+// split_c) and the rest to out1 (row pitch C - split_c) instead of dx (engine: the gradient of a concatenation)
+extern "C" int dh_dbg_groupnorm_split(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats,
+                                      const void* dy, void* dx, float* scratch, int B, int HW, int C, int G, float eps, int silu,
+                                      int accumulate, void* out0, void* out1, int split_c, void* stream) {
+  DH_REQUIRE(x && y && stats && dy && dx && scratch && (!out0 || (out1 && split_c > 0 && split_c < C && split_c % 8 == 0)), "bad arguments");
+  launch_groupnorm_fwd(dtype, x, gamma, beta, y, stats, scratch, B, HW, C, G, eps, silu, (hipStream_t)stream);
+  GnBwdSplit split;
+  split.out0 = out0; split.out1 = out1; split.split_c = split_c;
+  launch_groupnorm_bwd(dtype, x, dy, gamma, beta, stats, dx, scratch, B, HW, C, G, silu, accumulate, (hipStream_t)stream, 0, split);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+extern "C" int dh_dbg_gelu(int dtype, const void* x, void* y, size_t n, void* stream) {
+  DH_REQUIRE(x && y && n % 8 == 0, "bad arguments (n % 8)");
+  launch_gelu(dtype, x, y, n, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+extern "C" int dh_dbg_copy_cols(int dtype, const void* src, long lds, void* dst, long ldd, int rows, int cols, int accumulate,
+                                void* stream) {
+  DH_REQUIRE(src && dst && cols % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0, "bad arguments (cols, pitches % 8)");
+  launch_copy_cols(dtype, src, lds, dst, ldd, rows, cols, accumulate, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+extern "C" int dh_dbg_split_cols(int dtype, const void* src, long lds, void* dstA, long ldA, int colsA, int accA, void* dstB, long ldB,
+                                 int colsB, int accB, int rows, void* stream) {
+  DH_REQUIRE(src && dstA && dstB && colsA % 8 == 0 && colsB % 8 == 0 && lds % 8 == 0 && ldA % 8 == 0 && ldB % 8 == 0,
+             "bad arguments (cols, pitches % 8)");
+  launch_split_cols(dtype, src, lds, dstA, ldA, colsA, accA, dstB, ldB, colsB, accB, rows, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// to_f32 = 0: dst (16-bit) = src (f32); to_f32 = 1: dst (f32) (=|+=) src (16-bit)
+extern "C" int dh_dbg_convert(int dtype, int to_f32, const void* src, void* dst, size_t n, int accumulate, void* stream) {
+  DH_REQUIRE(src && dst && (to_f32 || !accumulate), "bad arguments (only the conversion to f32 accumulates)");
+  if (to_f32) launch_t_to_f32(dtype, src, (float*)dst, n, accumulate, (hipStream_t)stream);
+  else launch_f32_to_t(dtype, (const float*)src, dst, n, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// out [B][dim] = [cos(t f_i) | sin(t f_i)] of the one timestep at t_dev
+extern "C" int dh_dbg_timestep(int dtype, const float* t_dev, int dim, int B, void* out, void* stream) {
+  DH_REQUIRE(t_dev && out && dim > 0 && dim % 2 == 0 && B > 0, "bad arguments");
+  launch_timestep_embedding(dtype, t_dev, dim, B, out, (hipStream_t)stream);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

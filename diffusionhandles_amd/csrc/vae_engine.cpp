@@ -62,6 +62,30 @@ __global__ void __launch_bounds__(256) k_softmax_rows(T* s, int rows, int cols) 
   }
 }
 
+static void launch_softmax_rows(int dt, void* s, int rows, int cols, hipStream_t st) {
+  if (dt == DH_DTYPE_F16) hipLaunchKernelGGL((k_softmax_rows<f16>), dim3(cdiv(rows, 4)), dim3(256), 0, st, (f16*)s, rows, cols);
+  else hipLaunchKernelGGL((k_softmax_rows<bf16>), dim3(cdiv(rows, 4)), dim3(256), 0, st, (bf16*)s, rows, cols);
+}
+
+// the single-head attention of the mid block (tape op V_ATTN; also dh_dbg_vae_attention): qkv [N][ld] holds q | k | v of C columns
+// each, out [N][C] = softmax(q k^T) v.  tiled: N * C halves, scores: N * N halves, partial: the split-K workspace of the P V GEMM.
+static void vae_attention(int dt, const unsigned short* qkv, long ld, int N, int C, unsigned short* out, unsigned short* tiled,
+                          unsigned short* scores, float* partial, size_t partial_elems, hipStream_t st) {
+  const unsigned nb = (unsigned)(((size_t)N * C + 255) / 256);
+  // S = Q K^T (the scale sits in the q projection): K rows tiled as the GEMM's weight operand
+  hipLaunchKernelGGL((k_tile_rows<unsigned short>), dim3(nb), dim3(256), 0, st, qkv, ld, C, tiled, N, C, 0);
+  GemmArgs g;
+  g.A = qkv; g.lda = ld; g.W = tiled; g.M = N; g.N = N; g.K = C; g.C = scores; g.ldc = N;
+  launch_gemm(dt, g, st);
+  launch_softmax_rows(dt, scores, N, N, st);
+  // O = P V: V^T tiled as the weight operand ([C][N])
+  hipLaunchKernelGGL((k_tile_rows<unsigned short>), dim3(nb), dim3(256), 0, st, qkv, ld, 2 * C, tiled, C, N, 1);
+  GemmArgs h;
+  h.A = scores; h.lda = N; h.W = tiled; h.M = N; h.N = C; h.K = N; h.C = out; h.ldc = C;
+  h.partial = partial; h.partial_elems = partial_elems;
+  launch_gemm(dt, h, st);
+}
+
 enum VOp { V_CONV_IN, V_CONV_OUT, V_CONV, V_LINEAR, V_GN, V_ATTN };
 
 struct VTen { size_t off; int H, C; };     // [H*H][C] per image
@@ -458,22 +482,7 @@ static int vae_run(dh_vae_decoder* v, const float* z, int batch, float* image, v
         }
         case V_ATTN: {
           const VTen& t = v->tens[o.in0];
-          const int N = t.H * t.H, C = t.C / 3;
-          const unsigned short* qkv = aptr(o.in0);
-          const unsigned nb = (unsigned)(((size_t)N * C + 255) / 256);
-          // S = Q K^T (the scale sits in the q projection): K rows tiled as the GEMM's weight operand
-          hipLaunchKernelGGL((k_tile_rows<unsigned short>), dim3(nb), dim3(256), 0, st, qkv, (long)t.C, C, v->tiled, N, C, 0);
-          GemmArgs g;
-          g.A = qkv; g.lda = t.C; g.W = v->tiled; g.M = N; g.N = N; g.K = C; g.C = v->scores; g.ldc = N;
-          launch_gemm(dt, g, st);
-          if (dt == DH_DTYPE_F16) hipLaunchKernelGGL((k_softmax_rows<f16>), dim3(cdiv(N, 4)), dim3(256), 0, st, (f16*)v->scores, N, N);
-          else hipLaunchKernelGGL((k_softmax_rows<bf16>), dim3(cdiv(N, 4)), dim3(256), 0, st, (bf16*)v->scores, N, N);
-          // O = P V: V^T tiled as the weight operand ([C][N])
-          hipLaunchKernelGGL((k_tile_rows<unsigned short>), dim3(nb), dim3(256), 0, st, qkv, (long)t.C, 2 * C, v->tiled, C, N, 1);
-          GemmArgs h;
-          h.A = v->scores; h.lda = N; h.W = v->tiled; h.M = N; h.N = C; h.K = N; h.C = aptr(o.out); h.ldc = C;
-          h.partial = v->partial; h.partial_elems = v->partial_elems;
-          launch_gemm(dt, h, st);
+          vae_attention(dt, aptr(o.in0), t.C, t.H * t.H, t.C / 3, aptr(o.out), v->tiled, v->scores, v->partial, v->partial_elems, st);
           break;
         }
       }
@@ -493,4 +502,24 @@ extern "C" int dh_vae_encoder_encode(dh_vae_decoder* v, const float* image, int 
   DH_REQUIRE(v && image && moments && batch >= 1, "bad arguments");
   DH_REQUIRE(v->encoder, "this handle is a decoder (dh_vae_decoder_create)");
   return vae_run(v, image, batch, moments, stream);
+}
+
+// Test hooks for the kernels that are local to this file (the other hooks: debug_api.cpp).
+// the attention block exactly as the tape runs it; the caller owns the buffers the engine holds (tiled: N * C halves, scores: N * N
+// halves, partial: f32 split-K workspace)
+extern "C" int dh_dbg_vae_attention(int dtype, const void* qkv, long ld, int N, int C, void* out, void* tiled, void* scores,
+                                    float* partial, size_t partial_elems, void* stream) {
+  DH_REQUIRE(qkv && out && tiled && scores && N > 0 && C > 0 && N % 64 == 0 && C % 64 == 0 && ld >= 3L * C && ld % 8 == 0,
+             "bad arguments (N, C multiples of 64; ld >= 3 C)");
+  vae_attention(dtype, (const unsigned short*)qkv, ld, N, C, (unsigned short*)out, (unsigned short*)tiled, (unsigned short*)scores,
+                partial, partial_elems, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+// in-place row softmax of s [rows][cols] (cols % 8 == 0: the kernel reads 16-byte chunks)
+extern "C" int dh_dbg_softmax_rows(int dtype, void* s, int rows, int cols, void* stream) {
+  DH_REQUIRE(s && rows > 0 && cols > 0 && cols % 8 == 0, "bad arguments (cols % 8)");
+  launch_softmax_rows(dtype, s, rows, cols, (hipStream_t)stream);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
 }

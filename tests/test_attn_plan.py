@@ -346,3 +346,22 @@ def test_parity_shapes_launch_exactly_the_variants_of_the_table():
     # the text tower's causal launch cannot go through dh_dbg_attention (no causal argument): its variant through the query only
     p = named(plan(FWD, 1, 16, 77, 77, causal=1))
     assert (FWD, p["ks"], p["qw"], p["db"]) in table and p["ks"] == 1
+
+
+# (B, H, N) with Nq = Nk = N of the causal parity test (tests/test_engine_kernels_gpu.py: test_attention_causal, through
+# dh_dbg_attention_causal): the text tower's two launches, one partial tile, both sides of a 64-key tile edge, three tiles with a ragged
+# last one, and 576 rows at two batch sizes (nine key tiles, most of them hidden from the first rows)
+CAUSAL_SHAPES = [(1, 16, 77), (2, 16, 77), (1, 4, 20), (1, 2, 64), (1, 2, 65), (1, 3, 129), (1, 16, 576), (4, 16, 576)]
+
+
+def test_causal_parity_shapes_plan_one_key_group_and_two_block_sizes():
+    """a causal launch never splits the keys (a wave group whose keys all lie behind a row would merge m = -inf), and the shapes of the
+    parity test run the mask under at least two row-wave counts"""
+    plans = []
+    for B, H, N in CAUSAL_SHAPES:
+        q = (FWD, B, H, N, N, 1, 0)
+        p = named(plan(*q))
+        check_derived(q, p)
+        assert p["launch"] == 1 and p["ks"] == 1 and p["db"] == 0, (q, p)
+        plans.append(p)
+    assert len({p["qw"] for p in plans}) >= 2, [p["qw"] for p in plans]

@@ -44,6 +44,11 @@ class EnergyItem(ctypes.Structure):
                 ("fg_w", c_f), ("bg_w", c_f), ("grad_scale", c_f)]
 
 
+class EnergyDonorItem(ctypes.Structure):
+    """dh_energy_donor_item: one item of dh_energy_fwd_bwd_planned_donor_batch"""
+    _fields_ = [("item", EnergyItem), ("donor", c_p), ("donor_objects", ctypes.c_uint32)]
+
+
 class LockItem(ctypes.Structure):
     """dh_lock_item: one edit of dh_ddim_cfg_step_locked"""
     _fields_ = [("keep", c_p), ("ref", c_p)]
@@ -92,6 +97,10 @@ SIGNATURES = {
     "dh_reproject_instance_edits": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_p, c_p, c_f, c_f, c_d,
                                           c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
                                           c_p, c_i, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p]),
+    "dh_reproject_donor_workspace_bytes": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
+    "dh_reproject_donor_edits": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_p, c_p, c_f, c_f, c_d,
+                                       c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                       c_p, c_i, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p, c_p, c_i]),
     "dh_reproject_background_workspace_bytes": (c_i, [c_i, ctypes.POINTER(c_sz)]),
     "dh_reproject_background": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "dh_unproject": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_p, c_p]),
@@ -101,6 +110,7 @@ SIGNATURES = {
     "dh_cells_workspace_bytes": (c_i, [c_i, c_i, ctypes.POINTER(c_sz)]),
     "dh_cells_from_correspondences": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "dh_cells_from_correspondences_vacated": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
+    "dh_cells_from_correspondences_donor": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p, c_p]),
     "dh_energy_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
     "dh_energy_fwd_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i,
                                 c_f, c_f, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_p, c_sz, c_p]),
@@ -123,6 +133,9 @@ SIGNATURES = {
     "dh_energy_fwd_bwd_planned_objects_batch": (c_i, [ctypes.POINTER(EnergyItem), c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "dh_energy_fwd_bwd_planned_mixed_batch": (c_i, [ctypes.POINTER(EnergyItem), ctypes.POINTER(ctypes.c_uint8), c_i, c_i, c_i, c_i, c_i,
                                               c_p, c_sz, c_p]),
+    "dh_energy_fwd_bwd_planned_donor": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_i, c_p, c_i, c_p, c_i, c_f, c_f, c_f,
+                                              c_p, c_p, c_i, c_p, c_sz, c_p, c_p, ctypes.c_uint32]),
+    "dh_energy_fwd_bwd_planned_donor_batch": (c_i, [ctypes.POINTER(EnergyDonorItem), c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "dh_unet_create": (c_i, [ctypes.POINTER(UNetConfig), ctypes.POINTER(c_p)]),
     "dh_unet_create_shared": (c_i, [c_p, c_i, c_p, ctypes.POINTER(c_p)]),
     "dh_unet_destroy": (None, [c_p]),

@@ -18,17 +18,20 @@ __global__ void k_init_masks(uint8_t* m, int n) {
   if (i < n) m[i] = 1;
 }
 
+// row_donor (dh_cells_from_correspondences_donor): NULL, or one byte per correspondence row; a flagged row's source cell lies in
+// another image, so it forms its pair and clears its target cell but leaves the original-background mask alone
 __global__ void k_pairs(const long long* corr, const int* idx, const int* count, int img_res, int grid, int* pairs,
-                        uint8_t* bg_o, uint8_t* bg_t) {
+                        uint8_t* bg_o, uint8_t* bg_t, const uint8_t* row_donor) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= *count) return;
-  const long long* c = corr + 4 * (size_t)idx[r];
+  const int row = idx[r];
+  const long long* c = corr + 4 * (size_t)row;
   const int cs = img_res / grid;
   int oc = (int)(c[1] / cs) * grid + (int)(c[0] / cs);
   int tc = (int)(c[3] / cs) * grid + (int)(c[2] / cs);
   pairs[2 * (size_t)r + 0] = oc;
   pairs[2 * (size_t)r + 1] = tc;
-  bg_o[oc] = 0;
+  if (!row_donor || !row_donor[row]) bg_o[oc] = 0;
   bg_t[tc] = 0;
 }
 
@@ -154,10 +157,13 @@ extern "C" int dh_cells_workspace_bytes(int n, int grid, size_t* bytes) {
 // cells are cleared from the original-background mask between k_pairs and k_erode, so the erosion pushes the background away
 // from them as it does from an object.  The transformed-background mask and the pairs do not see it.  n == 0 with an image is
 // the pure removal.  NULL launches what dh_cells_from_correspondences always launched.
-extern "C" int dh_cells_from_correspondences_vacated(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
-                                                     int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
-                                                     void* workspace, size_t workspace_bytes, void* stream,
-                                                     const uint8_t* vacated) {
+// row_donor: NULL, or [n] u8 on the device, one byte per correspondence row (non-zero = the row's source pixel lies in a donor
+// image): such a row keeps its pair and clears its target cell, and does not clear a cell of the original-background mask.
+// NULL or all zero gives the bytes of the _vacated entry, with the same launches.
+extern "C" int dh_cells_from_correspondences_donor(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                                   int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                                   void* workspace, size_t workspace_bytes, void* stream,
+                                                   const uint8_t* vacated, const uint8_t* row_donor) {
   DH_REQUIRE(pairs && bg_lists && bg_masks && counts && workspace, "null pointer");
   DH_REQUIRE(n >= 0 && grid >= 1 && img_res >= grid && img_res % grid == 0, "bad sizes");
   DH_REQUIRE(n == 0 || corr, "null corr");
@@ -179,7 +185,7 @@ extern "C" int dh_cells_from_correspondences_vacated(const int64_t* corr, int n,
     hipLaunchKernelGGL(k_valid, dim3(cdiv(n, 256)), dim3(256), 0, st, (const long long*)corr, n, img_res, valid);
     compact(valid, n, 1, 0, idx, 0, counts, 1, bc, st);
     hipLaunchKernelGGL(k_pairs, dim3(cdiv(n, 256)), dim3(256), 0, st, (const long long*)corr, idx, counts, img_res,
-                       grid, pairs, two, two + G2);
+                       grid, pairs, two, two + G2, row_donor);
   }
   if (vacated)
     hipLaunchKernelGGL(k_vacated_cells, dim3(cdiv(img_res * img_res, 256)), dim3(256), 0, st, vacated, img_res, grid, two);
@@ -189,6 +195,14 @@ extern "C" int dh_cells_from_correspondences_vacated(const int64_t* corr, int n,
   compact(bg_masks, G2, 3, G2, bg_lists, G2, counts + 1, 1, bc, st);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+extern "C" int dh_cells_from_correspondences_vacated(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                                     int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                                     void* workspace, size_t workspace_bytes, void* stream,
+                                                     const uint8_t* vacated) {
+  return dh_cells_from_correspondences_donor(corr, n, img_res, grid, bg_erosion, pairs, bg_lists, bg_masks, counts, workspace,
+                                             workspace_bytes, stream, vacated, nullptr);
 }
 
 extern "C" int dh_cells_from_correspondences(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,

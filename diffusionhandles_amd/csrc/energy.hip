@@ -547,6 +547,8 @@ __global__ void __launch_bounds__(256) k_dedupe_sources_obj(const int* off, cons
   if (threadIdx.x == 0) ucnt[t] = base - b;
 }
 
+// the source rows of every object are the host image's in these three kernels (energy_grad_obj_body.inc)
+#define DH_ENERGY_SRC(m) orig
 // k_energy_grad with a weight per object: thread = (target cell, 8-channel chunk); block = 256 / (C/8) cells
 template <class T, class TG>
 __global__ void __launch_bounds__(256) k_energy_grad_obj(const T* orig, const T* cur, const int* off, const int* ucnt,
@@ -601,6 +603,46 @@ __global__ void __launch_bounds__(256) k_energy_grad_mixed_batch(const EnergyBat
 #include "energy_grad_body.inc"
   }
 }
+#undef DH_ENERGY_SRC
+
+// ---- donor objects (dh_energy_fwd_bwd_planned_donor[_batch]) ---------------------------------------------------------------
+// An object whose bit is set in donor_bits was brought in from another image: the source rows of its pairs are rows of that
+// image's activations (donor), not of orig.  The plan, the entries' order and the coefficients are the weighted plan's; only the
+// base pointer of an entry's source row is chosen per entry, by a select on the entry's object (both pointers and the bits are
+// kernel arguments: scalars).  The background term reads orig, as it always did.
+#define DH_ENERGY_SRC(m) (((donor_bits >> (m)) & 1u) ? donor : orig)
+template <class T, class TG>
+__global__ void __launch_bounds__(256) k_energy_grad_donor(const T* orig, const T* donor, unsigned donor_bits, const T* cur,
+                                                           const int* off, const int* ucnt, const int* src, const int* mult,
+                                                           const uint8_t* objp, const uint8_t* bgflag, const float* partq, int n1,
+                                                           int n2, int C, int G2, float fg_w, float coef_bg, int use_bg,
+                                                           float scale, TG* grad, double* loss_part, double* bg_loss) {
+#include "energy_grad_obj_body.inc"
+}
+
+// K items: the tables of k_energy_grad_obj_batch and, next to them, the donor pointer and the bits of every item -- by value
+struct EnergyDonorTab {
+  const void* donor[ENERGY_MAX_ITEMS];
+  unsigned bits[ENERGY_MAX_ITEMS];
+};
+template <class T, class TG>
+__global__ void __launch_bounds__(256) k_energy_grad_donor_batch(const EnergyBatch tab, const EnergyObjPtrs ot,
+                                                                 const EnergyDonorTab dt, int C, int G2) {
+  const EnergyItem& it = tab.it[blockIdx.y];
+  const T *orig = (const T*)it.orig, *cur = (const T*)it.cur;
+  const T* donor = (const T*)dt.donor[blockIdx.y];
+  const unsigned donor_bits = dt.bits[blockIdx.y];
+  const int *off = it.off, *ucnt = it.ucnt, *src = it.src, *mult = it.mult;
+  const uint8_t* objp = ot.p[blockIdx.y];
+  const uint8_t* bgflag = it.bgflag;
+  const float* partq = it.partq;
+  const int n1 = it.n1, n2 = it.n2, use_bg = it.use_bg;
+  const float fg_w = it.coef_fg, coef_bg = it.coef_bg, scale = it.scale;
+  TG* grad = (TG*)it.grad;
+  double *loss_part = it.loss_part, *bg_loss = it.bg_loss;
+#include "energy_grad_obj_body.inc"
+}
+#undef DH_ENERGY_SRC
 
 }  // namespace dh
 
@@ -856,9 +898,19 @@ static int fill_item(const char* who, const dh_energy_item& in, bool weighted, c
 }
 
 // ---- one evaluation: the single kernels, their scalar arguments read from the item's row ------------------------------------
+// the donor of an item: bits only below the object limit of a plan, and only with a donor pointer
+static int check_donor(const char* who, const void* donor, uint32_t donor_objects) {
+  if (donor_objects >> ENERGY_MAX_OBJECTS) return refuse(who, "a donor bit at or above the object count of a plan (8 at the most)");
+  if (donor_objects && !donor) return refuse(who, "donor objects without donor activations");
+  return DH_OK;
+}
+
+// donor_objects != 0: the weighted kernel that picks the source rows of the flagged objects from donor (weighted plans only)
 static int run_planned_single(const char* who, bool weighted, const dh_energy_item& in, int dtype, int C, int grid, int grad_dtype,
-                              void* workspace, size_t workspace_bytes, hipStream_t st) {
+                              void* workspace, size_t workspace_bytes, hipStream_t st, const void* donor = nullptr,
+                              uint32_t donor_objects = 0) {
   if (!(in.cur && in.orig && in.grad && in.plan && workspace)) return refuse(who, "null pointer");
+  if (const int rc = check_donor(who, donor, donor_objects)) return rc;
   if (!(dtype == DH_DTYPE_F16 || dtype == DH_DTYPE_BF16)) return refuse(who, "the planned path takes 16-bit activations");
   if (!(grad_dtype >= 0 && grad_dtype <= 2)) return refuse(who, "bad dtype");
   if (!(C >= 8 && C % 8 == 0 && C <= 2048 && grid >= 1 && in.n_pairs >= 0)) return refuse(who, "bad sizes");
@@ -876,7 +928,11 @@ static int run_planned_single(const char* who, bool weighted, const dh_energy_it
   with_dtypes(dtype, grad_dtype, [&](auto t, auto tg) {
     using T = typename decltype(t)::type;
     using TG = typename decltype(tg)::type;
-    if (weighted)
+    if (weighted && donor_objects)
+      hipLaunchKernelGGL((k_energy_grad_donor<T, TG>), dim3(nblocks), dim3(256), 0, st, (const T*)it.orig, (const T*)donor,
+                         (unsigned)donor_objects, (const T*)it.cur, it.off, it.ucnt, it.src, it.mult, objp, it.bgflag, it.partq, it.n1,
+                         it.n2, C, G2, it.coef_fg, it.coef_bg, it.use_bg, it.scale, (TG*)it.grad, it.loss_part, it.bg_loss);
+    else if (weighted)
       hipLaunchKernelGGL((k_energy_grad_obj<T, TG>), dim3(nblocks), dim3(256), 0, st, (const T*)it.orig, (const T*)it.cur, it.off,
                          it.ucnt, it.src, it.mult, objp, it.bgflag, it.partq, it.n1, it.n2, C, G2, it.coef_fg, it.coef_bg, it.use_bg,
                          it.scale, (TG*)it.grad, it.loss_part, it.bg_loss);
@@ -911,12 +967,26 @@ extern "C" int dh_energy_fwd_bwd_planned_objects(const void* cur, const void* or
   return run_planned_single(__func__, true, in, dtype, C, grid, grad_dtype, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// donor_objects = 0 launches what dh_energy_fwd_bwd_planned_objects launches
+extern "C" int dh_energy_fwd_bwd_planned_donor(const void* cur, const void* orig, int dtype, int C, int grid, const void* plan,
+                                               size_t plan_bytes, int n_pairs, const int32_t* bg_orig, int n_bg_orig,
+                                               const int32_t* bg_trans, int n_bg_trans, float fg_w, float bg_w, float grad_scale,
+                                               float* loss_out, void* grad, int grad_dtype, void* workspace,
+                                               size_t workspace_bytes, void* stream, const void* donor, uint32_t donor_objects) {
+  const dh_energy_item in = {cur, orig, plan, plan_bytes, bg_orig, bg_trans, loss_out, grad, n_pairs, n_bg_orig, n_bg_trans,
+                             fg_w, bg_w, grad_scale};      // (the field order of dh_energy_item)
+  return run_planned_single(__func__, true, in, dtype, C, grid, grad_dtype, workspace, workspace_bytes, (hipStream_t)stream, donor,
+                            donor_objects);
+}
+
 // ---- K items: one launch pair (plus the loss launch), whichever of the three gradient kernels the entry names ----------------
-enum class BatchKernel { PLAIN, OBJECTS, MIXED };      // k_energy_grad_batch, k_energy_grad_obj_batch, k_energy_grad_mixed_batch
+// k_energy_grad_batch, k_energy_grad_obj_batch, k_energy_grad_mixed_batch, k_energy_grad_donor_batch
+enum class BatchKernel { PLAIN, OBJECTS, MIXED, DONOR };
 
 // weighted: one byte per item, non-zero where its plan buffer is a weighted plan (all 0 / all 1 for the two pure entries)
 static int run_planned_batch(const char* who, BatchKernel kernel, const dh_energy_item* items, const uint8_t* weighted, int n_items,
-                             int dtype, int C, int grid, int grad_dtype, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                             int dtype, int C, int grid, int grad_dtype, void* workspace, size_t workspace_bytes, hipStream_t st,
+                             const EnergyDonorTab* donors = nullptr) {
   if (!(items && weighted && workspace)) return refuse(who, "null pointer");
   if (!(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS))
     return refuse(who, "the batched energy takes 1..16 items (larger batches are not split)");
@@ -947,6 +1017,7 @@ static int run_planned_batch(const char* who, BatchKernel kernel, const dh_energ
     const dim3 blocks(nblocks, n_items);
     if (kernel == BatchKernel::PLAIN) hipLaunchKernelGGL((k_energy_grad_batch<T, TG>), blocks, dim3(256), 0, st, tab, C, G2);
     else if (kernel == BatchKernel::OBJECTS) hipLaunchKernelGGL((k_energy_grad_obj_batch<T, TG>), blocks, dim3(256), 0, st, tab, ot, C, G2);
+    else if (kernel == BatchKernel::DONOR) hipLaunchKernelGGL((k_energy_grad_donor_batch<T, TG>), blocks, dim3(256), 0, st, tab, ot, *donors, C, G2);
     else hipLaunchKernelGGL((k_energy_grad_mixed_batch<T, TG>), blocks, dim3(256), 0, st, tab, ot, C, G2);
   });
   if (any_loss) hipLaunchKernelGGL(k_final_loss_batch, dim3(n_items), dim3(256), 0, st, tab);
@@ -973,4 +1044,24 @@ extern "C" int dh_energy_fwd_bwd_planned_mixed_batch(const dh_energy_item* items
                                                      void* stream) {
   return run_planned_batch(__func__, BatchKernel::MIXED, items, weighted, n_items, dtype, C, grid, grad_dtype, workspace, workspace_bytes,
                            (hipStream_t)stream);
+}
+
+// K weighted items, each with its donor (null with no bit set: that item computes what the objects batch computes for it)
+extern "C" int dh_energy_fwd_bwd_planned_donor_batch(const dh_energy_donor_item* items, int n_items, int dtype, int C, int grid,
+                                                     int grad_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  static const uint8_t all[ENERGY_MAX_ITEMS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+  if (!items) return refuse(__func__, "null pointer");
+  if (!(n_items >= 1 && n_items <= ENERGY_MAX_ITEMS))
+    return refuse(__func__, "the batched energy takes 1..16 items (larger batches are not split)");
+  dh_energy_item plain[ENERGY_MAX_ITEMS];
+  EnergyDonorTab dt;
+  for (int e = 0; e < ENERGY_MAX_ITEMS; ++e) {
+    const dh_energy_donor_item& in = items[e < n_items ? e : 0];      // (rows past n_items are never indexed: defined arguments)
+    if (const int rc = check_donor(__func__, in.donor, in.donor_objects)) return rc;
+    plain[e] = in.item;
+    dt.donor[e] = in.donor_objects ? in.donor : in.item.orig;
+    dt.bits[e] = in.donor_objects;
+  }
+  return run_planned_batch(__func__, BatchKernel::DONOR, plain, all, n_items, dtype, C, grid, grad_dtype, workspace, workspace_bytes,
+                           (hipStream_t)stream, &dt);
 }

@@ -6,6 +6,8 @@
 // the object changes the run is folded into an f32 accumulator with that object's coefficient fg_w * omega_m / (C N_m), written
 // as dh_energy_fwd_bwd_planned writes fg_w / (C N): with one object of weight 1 the element is the unweighted kernel's, bit for
 // bit.  Fixed order (objects ascending), one writer per element, no atomics: reproducible from run to run.
+// DH_ENERGY_SRC(m): the base pointer of the source rows of object m, defined by the including kernel -- orig in the kernels above,
+// a select between orig and the donor image's activations by the object's bit in k_energy_grad_donor[_batch].
   __shared__ double sm[4];
   const float* omega = reinterpret_cast<const float*>(objp);
   const int* nobj = reinterpret_cast<const int*>(objp + 32);
@@ -62,7 +64,7 @@
 #pragma unroll
       for (int j = 0; j < 8; ++j) { id[j] = src[k + j]; mu[j] = mult[k + j]; ob[j] = (int)obj[k + j]; }
 #pragma unroll
-      for (int j = 0; j < 8; ++j) ro[j] = *reinterpret_cast<const uint4*>(orig + (size_t)id[j] * C + ch * 8);
+      for (int j = 0; j < 8; ++j) ro[j] = *reinterpret_cast<const uint4*>(DH_ENERGY_SRC(ob[j]) + (size_t)id[j] * C + ch * 8);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (ob[j] != m) { DH_FOLD_OBJECT(); m = ob[j]; }
@@ -76,8 +78,8 @@
       }
     }
     for (; k < e; ++k) {
-      const uint4 ro = *reinterpret_cast<const uint4*>(orig + (size_t)src[k] * C + ch * 8);
       const int mu = mult[k], ob = (int)obj[k];
+      const uint4 ro = *reinterpret_cast<const uint4*>(DH_ENERGY_SRC(ob) + (size_t)src[k] * C + ch * 8);
       if (ob != m) { DH_FOLD_OBJECT(); m = ob; }
       const T* ov = reinterpret_cast<const T*>(&ro);
 #pragma unroll

@@ -99,11 +99,16 @@ __device__ __forceinline__ int inst_of(int j, const InstTable& tab, int& off, in
   return n;
 }
 
+// Donor objects (dh_reproject_donor_edits): masks n_host .. draw their points from donor_depth, the depth of another image of
+// the same resolution and intrinsics.  One workgroup folds one mask, so the select is uniform over the workgroup.  Without a
+// donor the entry hands in donor_depth = depth and n_host = the number of masks.
 constexpr int CEN_CHUNK = 1024;
-__global__ void __launch_bounds__(CEN_CHUNK) k_centroid(const float* depth, const int* fg_pix, const ObjTable tab, int res,
+__global__ void __launch_bounds__(CEN_CHUNK) k_centroid(const float* depth, const float* donor_depth, int n_host,
+                                                         const int* fg_pix, const ObjTable tab, int res,
                                                          const float* gx, const float* gy, float ifx, float ify, float* cen) {
   __shared__ float sv[2][3][CEN_CHUNK];
   const int t = threadIdx.x;
+  depth = (int)blockIdx.x >= n_host ? donor_depth : depth;
   const int n = tab.start[blockIdx.x + 1] - tab.start[blockIdx.x];
   fg_pix += tab.start[blockIdx.x];
   cen += 4 * blockIdx.x;
@@ -178,8 +183,10 @@ static_assert(sizeof(Xf) == DH_SIMILARITY_ROW * sizeof(double), "Xf is the simil
 // the rotation, one rounded f32 multiply per component (s = 1 leaves every bit of q as it was).
 // FP (footprint splatting, further down): the foreground points also leave (u, v, Z) -- u, v before the clamp and the
 // rounding -- in uvz, 3 doubles per point-list position and edit, for the triangles between them.
+// donor_depth, n_host: a point of mask o >= n_host reads the donor's depth (a pointer select beside the inst_of chain).
 template <bool FP>
-__global__ void k_points(const float* depth, const float* bg_depth, const int* fg_pix, int n_pts, int res,
+__global__ void k_points(const float* depth, const float* donor_depth, int n_host, const float* bg_depth, const int* fg_pix,
+                         int n_pts, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
                          const Xf* xf, const float* cen, const InstTable tab, int n_inst, unsigned long long* zbuf,
                          int* pix_out, unsigned long long* key_out, double* uvz) {
@@ -197,7 +204,7 @@ __global__ void k_points(const float* depth, const float* bg_depth, const int* f
     int off, o;
     const int n = inst_of(i - R2, tab, off, o);
     float x, y, z;
-    unproject_px(depth, fg_pix[i - R2 + off], res, gx, gy, ifx, ify, x, y, z);
+    unproject_px(o >= n_host ? donor_depth : depth, fg_pix[i - R2 + off], res, gx, gy, ifx, ify, x, y, z);
     const Xf t = xf[e * n_inst + n];
     // (the centroid is read whether or not the row has a pivot: three selects, no divergent branch around dependent loads)
     const bool piv = t.has_pivot != 0.0;
@@ -1272,7 +1279,7 @@ extern "C" int dh_masked_centroid(const float* depth, const int32_t* fg_pix, int
                                   const float* grid_y, float inv_fx, float inv_fy, float* centroid, void* stream) {
   DH_REQUIRE(depth && fg_pix && centroid && n_fg > 0, "bad arguments");
   const int one[2] = {0, n_fg};
-  hipLaunchKernelGGL(k_centroid, dim3(1), dim3(CEN_CHUNK), 0, (hipStream_t)stream, depth, fg_pix, obj_table(1, one, n_fg), res,
+  hipLaunchKernelGGL(k_centroid, dim3(1), dim3(CEN_CHUNK), 0, (hipStream_t)stream, depth, depth, 1, fg_pix, obj_table(1, one, n_fg), res,
                      grid_x, grid_y, inv_fx, inv_fy, centroid);
   DH_LAUNCH_CHECK();
   return DH_OK;
@@ -1294,13 +1301,23 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
                                int n_edits, const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
                                uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy, int64_t* corr,
                                uint8_t* corr_inst, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
-                               int footprints, float max_ratio, int corr_capacity) {
+                               int footprints, float max_ratio, int corr_capacity, const float* donor_depth = nullptr,
+                               int n_host_objects = -1) {
   DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start && inst_obj, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
   DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
   DH_REQUIRE(n_inst >= 1 && n_inst <= MAX_OBJECTS, "1 to 8 instances");
   DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
+  // the donor: masks n_host_objects .. n_objects - 1 draw from donor_depth (-1 = the call of an entry without the argument)
+  if (n_host_objects == -1) n_host_objects = n_objects;
+  DH_REQUIRE(n_host_objects >= 0 && n_host_objects <= n_objects, "n_host_objects must lie in 0 .. n_objects");
+  if (n_host_objects < n_objects) {
+    DH_REQUIRE(donor_depth, "donor objects without a donor depth");
+    DH_REQUIRE(!footprints, "footprints with a donor are not supported (two images share pixel indices)");
+    DH_REQUIRE(corr_inst, "a donor needs the instance column (corr_inst)");
+  }
+  if (!donor_depth) donor_depth = depth;
   DH_REQUIRE(max_ratio == 0.f || (max_ratio > 1.f && max_ratio <= 3.4028234663852886e38f),
              "footprint max_ratio must be 0 (none) or finite and > 1");
   DH_REQUIRE(max_ratio == 0.f || footprints, "footprint max_ratio without footprints");
@@ -1353,8 +1370,8 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0, (size_t)2 * K * sizeof(unsigned int), st));
   for (int e = 0; e < K; ++e) DH_CHECK_HIP(hipMemsetAsync(w.minmax + 2 * e, 0xff, sizeof(unsigned int), st));
 
-  hipLaunchKernelGGL(k_centroid, dim3(M), dim3(CEN_CHUNK), 0, st, depth, fg_pix, tab, res, grid_x, grid_y, inv_fx, inv_fy,
-                     w.cen);
+  hipLaunchKernelGGL(k_centroid, dim3(M), dim3(CEN_CHUNK), 0, st, depth, donor_depth, n_host_objects, fg_pix, tab, res, grid_x,
+                     grid_y, inv_fx, inv_fy, w.cen);
   // footprints: the triangle kernels run once per z-buffer pass, thread tier then wave tier (the list is built in pass 1)
   const int n_tri = 2 * (res - 1) * (res - 1);
   auto footprint_pass = [&](int pass) {
@@ -1367,12 +1384,13 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
     DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
     hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
-    hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_pts, res, grid_x,
-                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz);
+    hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth, fg_pix,
+                       n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz);
     footprint_pass(1);
   } else {
-    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, bg_depth, fg_pix, n_pts, res, grid_x,
-                       grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, (double*)nullptr);
+    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth, fg_pix,
+                       n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key,
+                       (double*)nullptr);
   }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
   if (footprints) footprint_pass(2);
@@ -1447,6 +1465,32 @@ extern "C" int dh_reproject_instances_workspace_bytes(int res, int n_pts, int n_
   return DH_OK;
 }
 
+// Donor objects: masks n_host_objects .. n_objects - 1 of fg_pix / obj_start are masks of ANOTHER image of the same resolution
+// and intrinsics, and their points are the unprojection of donor_depth.  Only k_centroid and k_points read a depth, so only they
+// know; a correspondence row of a donor instance carries its source pixel in the donor image, and corr_inst tells which rows
+// those are.  The workspace is the instance entry's.
+extern "C" int dh_reproject_donor_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
+                                                  int footprints, size_t* bytes) {
+  return dh_reproject_instances_workspace_bytes(res, n_pts, n_edits, n_objects, n_instances, footprints, bytes);
+}
+
+extern "C" int dh_reproject_donor_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                         int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                         const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                         const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                         uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                         int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                         void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
+                                         const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
+                                         int n_host_objects) {
+  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
+  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
+                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
+                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
+                             corr_capacity, donor_depth, n_host_objects);
+}
+
+// the call without a donor: donor_depth = NULL, every mask is the host's
 extern "C" int dh_reproject_instance_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
                                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
                                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
@@ -1455,10 +1499,10 @@ extern "C" int dh_reproject_instance_edits(const float* depth, const float* bg_d
                                             int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
                                             void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
                                             const int32_t* inst_obj, uint8_t* corr_inst) {
-  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
-                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
-                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
-                             corr_capacity);
+  return dh_reproject_donor_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx,
+                                  fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr,
+                                  counts, workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances,
+                                  inst_obj, corr_inst, nullptr, n_objects);
 }
 
 // the identity table: N = M, instance n draws mask n, no instance column
@@ -1561,7 +1605,7 @@ extern "C" int dh_reproject_background(const float* bg_depth, int res, const flo
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0, 2 * sizeof(unsigned int), st));
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0xff, sizeof(unsigned int), st));
   DH_CHECK_HIP(hipMemsetAsync(w.tmp_b, 0, (size_t)R2, st));
-  hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, (const int*)nullptr, 0, res,
+  hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth, (const int*)nullptr, 0, res,
                      grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr);
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.zbuf, w.pix, w.key, w.owner);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), 1), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, w.tmp_a,

@@ -353,9 +353,61 @@ def vacated_image(removed_masks, device=None):
     return out.to(torch.uint8).contiguous()
 
 
+def check_donor(donor_depth, donor_masks, res, n_host, what="donor"):
+    """The donor of an edit (object insertion, DESIGN.md "Object insertion") -> None, or (donor depth, list of D >= 1 masks).
+    The one validator of a donor: ValueError naming `what` and the member for a donor without depth or without masks, a depth
+    or a mask that is not one res x res image (the donor has the host's resolution), an empty mask beside non-empty ones,
+    overlapping donor masks, and n_host + D > 8.  None for no donor: both arguments None, or every mask empty -- that is the
+    call without the keyword.  It reads the masks' pixel counts (one device-to-host copy), before any launch of the library."""
+    if donor_depth is None and donor_masks is None:
+        return None
+    if donor_depth is None:
+        raise ValueError(f"{what}: donor: masks without a depth")
+    if donor_masks is None:
+        raise ValueError(f"{what}: donor: a depth without masks")
+    if isinstance(donor_masks, (torch.Tensor, np.ndarray)) or not isinstance(donor_masks, (list, tuple)):
+        raise ValueError(f"{what}: donor: masks: expected a list of masks, got {type(donor_masks).__name__}")
+    if len(donor_masks) == 0:
+        raise ValueError(f"{what}: donor: masks: the list is empty (a donor brings at least one mask)")
+    res = int(res)
+    if not isinstance(donor_depth, torch.Tensor) or donor_depth.numel() != res * res or tuple(donor_depth.shape[-2:]) != (res, res):
+        raise ValueError(f"{what}: donor: depth has shape {tuple(getattr(donor_depth, 'shape', ()))}, the host is {res} x {res} "
+                         "(a donor of another resolution is not supported)")
+    for d, mask in enumerate(donor_masks):
+        if not isinstance(mask, torch.Tensor) or mask.numel() != res * res or tuple(mask.shape[-2:]) != (res, res):
+            raise ValueError(f"{what}: donor: mask {d} has shape {tuple(getattr(mask, 'shape', ()))}, the host is {res} x {res} "
+                             "(a donor of another resolution is not supported)")
+    flat = torch.stack([(m.detach() != 0).reshape(-1) for m in donor_masks]).to(torch.uint8)
+    stats = torch.cat([flat.sum(dim=1), (flat.sum(dim=0) > 1).any()[None].to(torch.int64)]).tolist()
+    counts, overlap = stats[:-1], stats[-1]
+    if not any(counts):
+        return None
+    for d, c in enumerate(counts):
+        if c == 0:
+            raise ValueError(f"{what}: donor: mask {d} is empty (drop it, and renumber what names the masks behind it)")
+    if overlap:
+        for d in range(len(donor_masks)):
+            for q in range(d):
+                if bool((flat[d] & flat[q]).any()):
+                    raise ValueError(f"{what}: donor: mask {d} overlaps donor mask {q}")
+    if int(n_host) + len(donor_masks) > MAX_OBJECTS:
+        raise ValueError(f"{what}: donor: {n_host} host masks and {len(donor_masks)} donor masks, at most {MAX_OBJECTS} in all")
+    return donor_depth, list(donor_masks)
+
+
 def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None,
                             use_input_depth_normalization=False, return_debug=False, device_correspondences=False,
                             footprints=False, footprint_max_ratio=None, return_instances=False):
+    """`reproject_instance_edits` for an edit that also DELETES objects (not in the reference; DESIGN.md "Object removal"); the
+    text is `reproject_donor_edits`', of which this is the call without a donor."""
+    return reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, removed_masks, None, None,
+                                 use_input_depth_normalization, return_debug, device_correspondences, footprints,
+                                 footprint_max_ratio, return_instances)
+
+
+def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
+                          donor_masks=None, use_input_depth_normalization=False, return_debug=False,
+                          device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False):
     """`reproject_instance_edits` for an edit that also DELETES objects (not in the reference; DESIGN.md "Object removal"):
     everything said there holds, and --
 
@@ -371,13 +423,40 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
     ValueError before any device work of the library, naming the mask: a removed mask of another size, one that overlaps a
     foreground mask or another removed mask, M = 0 without a non-empty removed mask, transforms or instances given for M = 0.
     The debug dict gains vacated ([H, W] uint8 on the device: the union of the removed masks).
+
+    Object insertion (DESIGN.md "Object insertion") -- donor_depth, donor_masks: the [1,1,H,W] depth of a SECOND image of the
+    host's resolution and intrinsics, and D >= 1 pairwise disjoint masks of objects in it.  The edit's objects are then the
+    host's M masks (0 .. M - 1) followed by the donor's D masks (M .. M + D - 1), M + D <= 8: transforms and instances speak
+    about that list as they speak about fg_masks.  A donor object's points are the unprojection of donor_depth at its mask's
+    pixels, its centroid the sequential-f32 centroid of those points; a pivot is a point of the shared camera coordinates.  From
+    there on everything is shared (one z-buffer, masks, visibility, in-fill, normalisation).  Donor masks may overlap host
+    masks, removed masks and each other's image position freely -- they are pixels of another image.  M = 0 with a donor is the
+    pure insertion (bg_depth: the host depth, or the depth with the removed masks removed).  A row of a donor instance carries
+    its source pixel IN THE DONOR IMAGE; a donor call always returns the instance array (return_instances is implied), and "row
+    r is a donor row" means instances[corr_inst[r]] >= M.  The debug dict gains row_donor [K, capacity] uint8 (device).
+    No relative depth scale is estimated: the caller brings `scale`.  ValueError (check_donor) before any launch;
+    NotImplementedError for footprints with a donor (the pixel -> list-position inverse of the triangles is ambiguous when two
+    images share pixel indices).  No donor -- None, or donor masks that are all empty -- is the call without the keywords,
+    byte for byte, with the same launches.
     """
     what = "reproject_removal_edits"
     footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
     fg_masks = list(fg_masks)
     removed = check_removed_masks(removed_masks, fg_masks, f"{what}: removed_masks")
     M = len(fg_masks)
-    if M == 0 and removed:
+    donor = None
+    if donor_depth is not None or donor_masks is not None:
+        donor = check_donor(donor_depth, donor_masks, depth.shape[-1], M, "reproject_donor_edits")
+    if donor is not None:
+        if footprints:
+            raise NotImplementedError("reproject_donor_edits: footprints with a donor are not supported (depth_transform_footprints; "
+                                      "two images share pixel indices)")
+        if fg_masks and fg_masks[0].shape[-1] != depth.shape[-1]:
+            raise ValueError("reproject_donor_edits: donor: the foreground masks and the depth differ in size")
+        return_instances = True
+    donor_list = [] if donor is None else donor[1]
+    D = len(donor_list)
+    if M == 0 and removed and donor is None:
         edits = [list(tfs) for tfs in edits]
         for e, tfs in enumerate(edits):
             if len(tfs) != 0:
@@ -387,18 +466,20 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
             raise ValueError(f"{what}: instances={instances!r} given without a foreground mask (a pure removal has no instance)")
         return _reproject_pure_removal(depth, bg_depth, removed, intrinsics, len(edits), use_input_depth_normalization,
                                        return_debug, device_correspondences, return_instances, instances is not None)
-    if not 1 <= M <= MAX_OBJECTS:
+    if not 1 <= M <= MAX_OBJECTS and donor is None:
         raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got {M}")
-    inst = check_instances(instances, M, "reproject_instance_edits: instances")
+    # (with a donor the table names every mask of the concatenated list: the host's M, then the donor's D)
+    inst = check_instances(instances, M + D, "reproject_donor_edits: instances" if donor is not None else
+                           "reproject_instance_edits: instances")
     with_table = inst is not None or bool(return_instances)
     if inst is None:
-        inst = list(range(M))
+        inst = list(range(M + D))
     N = len(inst)
     edits = [list(tfs) for tfs in edits]
     for e, tfs in enumerate(edits):
         if len(tfs) != N:
             if instances is None:
-                raise ValueError(f"Edit {e} has {len(tfs)} transforms for {M} foreground masks")
+                raise ValueError(f"Edit {e} has {len(tfs)} transforms for {M + D} foreground masks")
             raise ValueError(f"Edit {e} has {len(tfs)} transforms for {N} instances")
     edits = [[check_transform(tf, f"edit {e}, {'object' if instances is None else 'instance'} {m}") for m, tf in enumerate(tfs)]
              for e, tfs in enumerate(edits)]
@@ -409,17 +490,19 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
             raise ValueError("Expected all foreground masks to have one size")
     if depth.dim() != 4 or depth.shape[0] != 1:
         raise ValueError("Only batch size 1 is supported")
-    res = fg_masks[0].shape[-1]
+    res = fg_masks[0].shape[-1] if M else int(depth.shape[-1])
     # the M pixel counts and the overlap flag: ONE device-to-host copy (none for host masks), before any launch of the library
     flat = [(fg_mask.detach() != 0).reshape(-1) for fg_mask in fg_masks]
-    masks_u8 = (flat[0][None] if M == 1 else torch.stack(flat)).to(torch.uint8)
+    if donor is not None:          # the donor's masks behind the host's (they were checked, and are on the first mask's device)
+        flat += [(m.detach() != 0).reshape(-1).to(flat[0].device if flat else m.device) for m in donor_list]
+    masks_u8 = (flat[0][None] if M + D == 1 else torch.stack(flat)).to(torch.uint8)
     stats = masks_u8.sum(dim=1)
     if M > 1:
-        stats = torch.cat([stats, (masks_u8.sum(dim=0) > 1).any()[None].to(stats.dtype)])
+        stats = torch.cat([stats, (masks_u8[:M].sum(dim=0) > 1).any()[None].to(stats.dtype)])
     vacated = None
     if removed:
         # the removed masks ride in the same copy: per mask its pixel count and whether it meets the union before it
-        seen = masks_u8.sum(dim=0) > 0
+        seen = masks_u8[:M].sum(dim=0) > 0
         vacated = torch.zeros_like(seen)
         extra = []
         for mask in removed:
@@ -429,7 +512,7 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
             vacated = vacated | mr
         stats = torch.cat([stats, torch.stack(extra)])
     stats = stats.tolist()
-    if M > 1 and stats[M]:
+    if M > 1 and stats[M + D]:
         raise ValueError("The foreground masks overlap")
     if removed:
         tail = stats[len(stats) - 2 * len(removed):]
@@ -437,7 +520,8 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
             removed_overlap(removed, fg_masks, f"{what}: removed_masks")
             raise ValueError(f"{what}: removed_masks: removed mask {tail[1::2].index(1)} overlaps another mask")
         n_vacated = sum(tail[0::2])
-    kept = [m for m in range(M) if stats[m] > 0]
+    kept = [m for m in range(M + D) if stats[m] > 0]
+    n_host_kept = sum(1 for m in kept if m < M)
     obj_start = np.zeros(len(kept) + 1, dtype=np.int32)
     obj_start[1:] = np.cumsum([stats[m] for m in kept])
     n_fg = int(obj_start[-1])
@@ -473,7 +557,7 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
     fx, fy = float(kcpu[0, 0]), float(kcpu[1, 1])
     R2 = res * res
     Mk = len(kept)
-    fg_pix = torch.empty(R2, dtype=torch.int32, device=dev)
+    fg_pix = torch.empty(max(R2, n_fg), dtype=torch.int32, device=dev)      # (beyond R2 only with a donor: its pixels are another image's)
     n_dev = torch.zeros(Mk, dtype=torch.int32, device=dev)
     ws_small = torch.empty(4096, dtype=torch.uint8, device=dev)
     for j, m in enumerate(kept):              # disjoint masks: the slices fill fg_pix[0 .. n_fg), n_fg <= R2
@@ -511,10 +595,20 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
             _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
             _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st, int(footprints), 0.0 if ratio is None else ratio, cap)
     corr_inst = None
+    row_donor = None
     if with_table:
         corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
-        _lib.check(L.dh_reproject_instance_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                 _lib.ptr(corr_inst)), "dh_reproject_instance_edits")
+        if donor is not None:
+            dd = donor[0].detach().to(dev, torch.float32).contiguous()
+            _lib.check(L.dh_reproject_donor_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                  _lib.ptr(corr_inst), _lib.ptr(dd), n_host_kept), "dh_reproject_donor_edits")
+            # one byte per row: whether the row's instance draws a donor mask (256 entries: rows past the counts are not written)
+            flags = torch.zeros(256, dtype=torch.uint8)
+            flags[:Nk] = torch.tensor([1 if inst[n] >= M else 0 for n in caller], dtype=torch.uint8)
+            row_donor = flags.to(dev)[corr_inst.long()]
+        else:
+            _lib.check(L.dh_reproject_instance_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                     _lib.ptr(corr_inst)), "dh_reproject_instance_edits")
         if caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
             lut = torch.zeros(256, dtype=torch.uint8)          # (256 entries: the rows past the counts are not written)
             lut[:Nk] = torch.tensor(caller, dtype=torch.uint8)
@@ -537,6 +631,8 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
             dbg.update(corr_inst=corr_inst, inst_start=inst_start)
         if removed_masks is not None:
             dbg.update(vacated=_vacated_u8(vacated, res, dev))
+        if row_donor is not None:
+            dbg.update(row_donor=row_donor)
         return out, dbg
     return out
 

@@ -1,4 +1,6 @@
 """DiffusionHandles facade (reference diffusion_handles.py:15-166) on the native MI355X path."""
+import functools
+
 import torch
 
 from . import conf as _conf
@@ -150,10 +152,14 @@ class DiffusionHandles:
         return imgs, [d for d, _ in edits]
 
     def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences,
-                           instances=None, removed_masks=None):
+                           instances=None, removed_masks=None, donor=None):
         """instances given: every result is (disparity, correspondences, instance of every row).  removed_masks: the masks of the
-        objects the edits delete (object removal); fg_masks may then be empty and the edits K empty lists."""
-        from .depth_transform import check_instances, check_removed_masks, reproject_removal_edits
+        objects the edits delete (object removal); fg_masks may then be empty and the edits K empty lists.  donor: None or the
+        checked donor (_donor_setup): its masks follow fg_masks in the object list, and an instance table is always given."""
+        from .depth_transform import check_instances, check_removed_masks, reproject_donor_edits, reproject_removal_edits
+        if donor is not None:
+            reproject_removal_edits = functools.partial(self._reproject_donor, reproject_donor_edits, donor)
+        n_donor = 0 if donor is None else len(donor[1])
         fp = self._footprints(what)
         if self.conf.depth_transform_mode != "pc":
             if removed_masks is not None:
@@ -166,7 +172,7 @@ class DiffusionHandles:
                                       "re-projection (only 'pc')")
         if removed_masks is not None:
             removed = check_removed_masks(removed_masks, list(fg_masks), f"{what}: removed_masks")
-            if len(fg_masks) == 0:
+            if len(fg_masks) == 0 and donor is None:
                 if not removed:
                     raise ValueError(f"Expected 1 to 8 foreground masks, got 0 ({what}: no removed mask either)")
                 if instances is not None and len(list(instances)) != 0:
@@ -179,7 +185,7 @@ class DiffusionHandles:
                 return reproject_removal_edits(depth, bg_depth, [], self.diffuser.get_depth_intrinsics(device=depth.device),
                                                [[] for _ in edits], None, removed, use_input_depth_normalization,
                                                device_correspondences=device_correspondences, **fp)
-        inst = check_instances(instances, len(fg_masks), f"{what}: instances")
+        inst = check_instances(instances, len(fg_masks) + n_donor, f"{what}: instances")
         n_bodies, body = (len(fg_masks), "object") if inst is None else (len(inst), "instance")
         Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
         dflt = lambda v, d: d if v is None else v
@@ -195,6 +201,63 @@ class DiffusionHandles:
         return reproject_removal_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
                                        inst, removed_masks, use_input_depth_normalization,
                                        device_correspondences=device_correspondences, **fp, return_instances=inst is not None)
+
+    @staticmethod
+    def _reproject_donor(reproject, donor, depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks, *args, **kw):
+        """reproject_donor_edits' positional list without the donor pair, which goes behind removed_masks."""
+        return reproject(depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks, donor[0], donor[1], *args, **kw)
+
+    def _donor_setup(self, what, donor, fg_masks, depth, activations):
+        """The host checks of an edit call's donor, before any library launch -> None (no donor: None, or every donor mask empty)
+        or (donor depth, donor masks, donor activations).  ValueError naming `what`, the edit's donor and the member: a donor
+        that is no dict with depth, masks and activations, what depth_transform.check_donor refuses (another resolution,
+        overlapping or empty masks, M + D > 8), activations with another number of layers or timesteps than the host's.
+        NotImplementedError naming the setting for mesh mode and for footprints."""
+        if donor is None:
+            return None
+        if not isinstance(donor, dict):
+            raise ValueError(f"{what}: donor: expected a dict with depth, masks and activations, got {type(donor).__name__}")
+        for member in ("depth", "masks", "activations"):
+            if donor.get(member) is None:
+                raise ValueError(f"{what}: donor: no {member}")
+        extra = set(donor) - {"depth", "masks", "activations"}
+        if extra:
+            raise ValueError(f"{what}: donor: unknown members {sorted(extra)}")
+        if self.conf.depth_transform_mode != "pc":
+            raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no object insertion "
+                                      "(donor; only 'pc')")
+        if self._footprints(what)["footprints"]:
+            raise NotImplementedError(f"{what}: depth_transform_footprints: true has no object insertion (donor; two images "
+                                      "share pixel indices)")
+        from .depth_transform import check_donor
+        acts = donor["activations"]
+        try:
+            n_layers = len(acts)
+        except TypeError:
+            raise ValueError(f"{what}: donor: activations: expected the activations of an identity") from None
+        if n_layers != len(activations):
+            raise ValueError(f"{what}: donor: activations of {n_layers} layers, the host's have {len(activations)}")
+        for k, (a, o) in enumerate(zip(acts, activations)):
+            if a.shape[0] != o.shape[0]:
+                raise ValueError(f"{what}: donor: activations of layer {k} hold {a.shape[0]} timesteps, the host's {o.shape[0]}")
+        checked = check_donor(donor["depth"], donor["masks"], depth.shape[-1], len(fg_masks), what)
+        return None if checked is None else checked + (acts,)
+
+    @staticmethod
+    def _donor_rows(rows, instances, n_host):
+        """One byte per correspondence row: 1 where the row's instance draws a donor mask (instances[row] >= n_host)."""
+        lut = torch.zeros(256, dtype=torch.uint8)
+        lut[:len(instances)] = torch.tensor([1 if o >= n_host else 0 for o in instances], dtype=torch.uint8)
+        return lut.to(rows.device)[rows.long()]
+
+    @staticmethod
+    def _lock_rows(correspondences, row_donor):
+        """The correspondences the background lock sees: a donor row's source pixel lies in another image, so it is overwritten
+        with the row's target pixel (where the tensor lives: on the device for the batched calls)."""
+        corr = torch.as_tensor(correspondences).clone()
+        flagged = row_donor.to(corr.device) != 0
+        corr[:, 0:2] = torch.where(flagged[:, None], corr[:, 2:4], corr[:, 0:2])
+        return corr
 
     @staticmethod
     def _vacated(removed_masks, what):
@@ -246,7 +309,7 @@ class DiffusionHandles:
 
     def transform_foreground_objects(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                      transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                     object_weights=None, removed_masks=None, instances=None, release_mask=None):
+                                     object_weights=None, donor=None, removed_masks=None, instances=None, release_mask=None):
         """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
         rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.  Each object
@@ -267,21 +330,46 @@ class DiffusionHandles:
         cells leave the guidance's original-background list, and the background lock sets them free (release_mask stays the
         tool for the shadow).  fg_masks may then be empty with transforms [] -- a pure removal: the disparity is the
         re-projection of the background alone.  Meant to run with conf background_lock: true.  ValueError naming the mask for
-        an overlap or another size, for no mask at all, and for transforms without a foreground mask, before any device work."""
+        an overlap or another size, for no mask at all, and for transforms without a foreground mask, before any device work.
+        donor (object insertion; DESIGN.md "Object insertion"): None, or a dict {"depth", "masks", "activations"} -- the depth of
+        a SECOND image of this image's resolution and intrinsics, D >= 1 pairwise disjoint masks of objects in it, and that
+        image's identity activations (set_foreground / invert_input_image on the donor image).  The edit's objects are then the
+        M masks of fg_masks (0 .. M - 1) followed by the donor's D masks (M .. M + D - 1), M + D <= 8: transforms, instances,
+        object_weights and "equal" speak about that list.  fg_masks may be [] (a pure insertion; bg_depth is then the depth, or
+        the depth with the removed masks removed).  The inserted object's features come from the donor's activations; it
+        occludes and is occluded like any object.  No relative depth scale is estimated: two monocular depth estimates
+        disagree by a factor, which the caller brings as the transform's `scale`.  Donor edits run on the weighted energy:
+        object_weights=None weighs every instance by its pair count, which gives every pair the unweighted coefficient
+        fg_w / (C N) up to rounding.  Default guidance configuration only; 'pc' mode without footprints
+        (NotImplementedError naming the setting).  ValueError naming the call, the donor and the member before any launch
+        (_donor_setup).  A donor whose masks are all empty is the call without the keyword."""
         what = "transform_foreground_objects"
         fg_masks = list(fg_masks)
-        self._check_removal(what, fg_masks, removed_masks)
-        labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
+        dn = self._donor_setup(what, donor, fg_masks, depth, activations)
+        if dn is not None:
+            if removed_masks is not None:
+                self._check_removal(what, fg_masks or list(dn[1]), removed_masks)
+            instances = list(range(len(fg_masks) + len(dn[1]))) if instances is None else instances
+            labels, object_weights = self._object_labels(fg_masks + list(dn[1]), object_weights, instances, f"{what}: instances")
+        else:
+            self._check_removal(what, fg_masks, removed_masks)
+            labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
         lk = self._lock_setup(what, activations, depth, release_mask)
         with torch.no_grad():
             (edited_disparity, correspondences, *rows), = self._reproject_objects(
-                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances, removed_masks)
+                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances, removed_masks, dn)
             self.last_keep_maps = []
             freed = fg_masks + list(removed_masks or [])
-            lock = {} if lk is None else dict(lock=self._edit_lock(lk, freed, correspondences, depth))
+            lock_corr = correspondences
+            if dn is not None:
+                row_donor = self._donor_rows(rows[0], instances, len(fg_masks))
+                lock_corr = self._lock_rows(correspondences, row_donor)
+            lock = {} if lk is None else dict(lock=self._edit_lock(lk, freed, lock_corr, depth))
             lock.update(self._vacated(removed_masks, what))
             if rows:
                 lock["pair_instances"] = rows[0]
+            if dn is not None:
+                lock["donor"] = (dn[2], row_donor)
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
@@ -294,8 +382,8 @@ class DiffusionHandles:
 
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                           object_weights=None, streams=1, batch=None, removed_masks=None, instances=None,
-                                           release_mask=None):
+                                           object_weights=None, streams=1, batch=None, donor=None, removed_masks=None,
+                                           instances=None, release_mask=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
         edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
         pivot).  Returns (images [K,3,H,W], [K disparities]) as
@@ -304,25 +392,39 @@ class DiffusionHandles:
         lanes, batch = 1 runs single edits on the lanes; images are bit-identical to the one-stream result at the same batch.
         release_mask: transform_foreground_objects', one for all K edits.  instances: transform_foreground_objects', one table
         for all K edits (the edits are then K lists of N transforms).  removed_masks: transform_foreground_objects', one list for
-        all K edits (with fg_masks empty the edits are K empty lists: K identical pure removals)."""
+        all K edits (with fg_masks empty the edits are K empty lists: K identical pure removals).  donor:
+        transform_foreground_objects', one donor for all K edits (they share the channels-last copy of its activations)."""
         what = "transform_foreground_objects_batch"
         fg_masks = list(fg_masks)
-        self._check_removal(what, fg_masks, removed_masks)
-        labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
+        dn = self._donor_setup(what, donor, fg_masks, depth, activations)
+        if dn is not None:
+            if removed_masks is not None:
+                self._check_removal(what, fg_masks or list(dn[1]), removed_masks)
+            instances = list(range(len(fg_masks) + len(dn[1]))) if instances is None else instances
+            labels, object_weights = self._object_labels(fg_masks + list(dn[1]), object_weights, instances, f"{what}: instances")
+        else:
+            self._check_removal(what, fg_masks, removed_masks)
+            labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
         lk = self._lock_setup(what, activations, depth, release_mask)
         K = len(edits)
         with torch.no_grad():
             res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, instances,
-                                          removed_masks)
+                                          removed_masks, dn)
             rows = [r[2] for r in res] if instances is not None else None
             res = [r[:2] for r in res]
             per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
             obj = dict(object_labels=labels, object_weights=object_weights, **self._vacated(removed_masks, what))
             self.last_keep_maps = []
+            whole = streams <= 1 and per >= K or per <= 1          # per edit; the chunked call takes one list per chunk
+            lock_corrs = [c for _, c in res]
+            if dn is not None:
+                flags = [self._donor_rows(r, instances, len(fg_masks)) for r in rows]
+                lock_corrs = [self._lock_rows(c, f) for c, f in zip(lock_corrs, flags)]
+                obj["donor"] = (dn[2], flags if whole else [flags[i:i + per] for i in range(0, K, per)])
             if lk is not None:
-                obj["lock"] = [self._edit_lock(lk, fg_masks + list(removed_masks or []), c, depth) for _, c in res]
-            if rows is not None:          # per edit; the chunked call takes one list per chunk
-                obj["pair_instances"] = rows if streams <= 1 and per >= K or per <= 1 else [rows[i:i + per] for i in range(0, K, per)]
+                obj["lock"] = [self._edit_lock(lk, fg_masks + list(removed_masks or []), c, depth) for c in lock_corrs]
+            if rows is not None:
+                obj["pair_instances"] = rows if whole else [rows[i:i + per] for i in range(0, K, per)]
             if streams <= 1 and per >= K:
                 imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
                                                             [c for _, c in res], fg_weight, bg_weight, **obj)
@@ -360,6 +462,10 @@ class DiffusionHandles:
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
                                       "batched re-projection (only 'pc')")
         K = len(edits)
+        for i, e in enumerate(edits):
+            if isinstance(e, dict) and "donor" in e:
+                raise NotImplementedError(f"transform_foregrounds: edit {i}: donor (object insertion is not supported in "
+                                          "mixed-image batches; transform_foreground_objects[_batch])")
         common = tuple(f for f in self.EDIT_FIELDS if f != "fg_mask")
         if K < 1 or any(set(common) - set(e) for e in edits):
             raise ValueError(f"transform_foregrounds: needs at least one edit, each with {self.EDIT_FIELDS}")

@@ -88,6 +88,11 @@ def build_weight_schedule(fg_weight, bg_weight, max_step, kind):
     return StepGuidanceWeightSchedule(den, opt)
 
 
+class DonorActivations(list):
+    """The channels-last engine-dtype copies [T,h,w,C] of a donor image's activations, one per captured layer (prepare_guidance
+    makes them; K edits of one image share one instance, as they share `orig`)."""
+
+
 def _nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
@@ -479,7 +484,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         _check_object_weights(object_weights, n)
 
     def prepare_guidance(self, depth, prompt, activations_orig, correspondences, fg_weight=None, bg_weight=None, orig=None,
-                         cond=None, object_labels=None, object_weights=None, pair_instances=None, vacated=None, lock=None):
+                         cond=None, object_labels=None, object_weights=None, pair_instances=None, donor=None, vacated=None,
+                         lock=None):
         """Everything of guided_inference that is constant over the denoising loop.  `lock` (background lock): (keep [s,s],
         trajectory [T,4,s,s]) -- the keep map of this edit (background_lock.keep_map) and the reconstruction trajectory of its
         image (activations.trajectory) -- or a prepared background_lock.Lock (edits of one image share the channels-last copy
@@ -495,9 +501,21 @@ class GuidedStableDiffuser(GuidedDiffuser):
         per instance.
         vacated (edits that DELETE objects, DESIGN.md "Object removal"): the [H, W] image of the pixels the removed objects
         leave behind; their cells leave the original-background list of the energy (losses.process_correspondences).  The
-        correspondences may then be empty (a pure removal: the background term runs alone).  None: the call without it."""
+        correspondences may then be empty (a pure removal: the background term runs alone).  None: the call without it.
+        donor (edits that bring in objects of ANOTHER image, DESIGN.md "Object insertion"): (activations_donor, row_donor) -- the
+        donor image's identity activations (as activations_orig, with its numbers of timesteps and layers; or the
+        DonorActivations another guidance state of the same edit batch made of them) and one byte per correspondence row,
+        non-zero where the row's source pixel lies in the donor image.  pair_instances is then required (an object of the
+        energy is an instance, and a donor row's instance is a donor object).  A donor row's pair reads its source feature from
+        the donor's activations, clears its target cell and leaves the original-background list alone.  Donor edits always run
+        on the weighted plan: object_weights=None means w_m = N_m, which gives every pair the unweighted coefficient
+        fg_w / (C N) up to rounding.  Default configuration only (planned path, fg_patch_size 1, global_avg; NotImplementedError
+        naming the setting otherwise); grad_scale 'auto' takes its bound from the weighted plan, as it does for weights.
+        None: the call without it."""
         from types import SimpleNamespace
         vacated = _losses.check_vacated(vacated, depth.shape[-1], "prepare_guidance")
+        if donor is not None:
+            donor = self._check_donor(donor, activations_orig, correspondences, pair_instances, object_labels)
         if object_labels is not None and pair_instances is not None:
             raise ValueError("object_labels and pair_instances are mutually exclusive")
         if object_weights is not None:
@@ -505,7 +523,11 @@ class GuidedStableDiffuser(GuidedDiffuser):
         fg_weight = self.conf.fg_weight if fg_weight is None else fg_weight
         bg_weight = self.conf.bg_weight if bg_weight is None else bg_weight
         st = SimpleNamespace()
-        if object_weights is None and vacated is None:
+        if donor is not None:
+            st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
+                                             device=self.device, vacated=vacated, pair_instances=pair_instances,
+                                             row_donor=donor[1])
+        elif object_weights is None and vacated is None:
             st.pc = self.process_correspondences(correspondences, img_res=depth.shape[-1], bg_erosion=self.conf.bg_erosion)
         elif object_weights is None:
             st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
@@ -529,7 +551,10 @@ class GuidedStableDiffuser(GuidedDiffuser):
         st.plan = None
         if (self.conf.fg_patch_size == 1 and self.conf.bg_loss_type == "global_avg"
                 and all(o.shape[1] == st.size[0] and o.shape[2] == st.size[1] for o in st.orig[1:])):
-            st.plan = EnergyPlan(st.pc, st.size[0], self.device, object_weights=object_weights)
+            st.plan = EnergyPlan(st.pc, st.size[0], self.device, object_weights=object_weights, force_weighted=donor is not None)
+        elif donor is not None:
+            raise NotImplementedError("donor: guided layers off the cell grid (a donor edit needs the planned energy: default "
+                                      "configuration, layers on the cell grid)")
         elif object_weights is not None:
             raise NotImplementedError("object_weights need the planned energy (default configuration, layers on the cell grid)")
         weighted = st.plan is not None and st.plan.weighted
@@ -544,7 +569,46 @@ class GuidedStableDiffuser(GuidedDiffuser):
             st.scale_dev = torch.tensor(st.scale_host, dtype=torch.float32).to(self.device)[None].contiguous()
             st.status = torch.zeros((1, 4), dtype=torch.int32, device=self.device)
         st.lock = self._locks(lock, 1, "prepare_guidance")[0]
+        st.donor, st.donor_bits = None, 0
+        if donor is not None:
+            # the donor objects of the energy: the instances of the flagged rows (one host read per edit, outside the loop)
+            flagged = torch.as_tensor(pair_instances).reshape(-1).cpu()[torch.as_tensor(donor[1]).reshape(-1).cpu() != 0]
+            for m in set(flagged.tolist()):
+                st.donor_bits |= 1 << int(m)
+            st.donor_bits &= (1 << st.plan.n_objects) - 1          # (an instance past the last one with kept pairs has none)
+            acts = donor[0]
+            st.donor = acts if isinstance(acts, DonorActivations) else DonorActivations(
+                a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in acts)
         return st
+
+    def _check_donor(self, donor, activations_orig, correspondences, pair_instances, object_labels):
+        """Host checks of prepare_guidance's donor, before any device work: the pair, the row flags' length, the instance
+        column, the donor activations' layers and timesteps against the host's, the default configuration."""
+        what = "prepare_guidance: donor"
+        if not isinstance(donor, (tuple, list)) or len(donor) != 2:
+            raise ValueError(f"{what}: expected (activations_donor, row_donor)")
+        acts, row_donor = donor
+        if acts is None or row_donor is None:
+            raise ValueError(f"{what}: {'activations' if acts is None else 'row_donor'} missing")
+        if pair_instances is None or object_labels is not None:
+            raise ValueError(f"{what}: needs pair_instances (the instance of every correspondence row), not a label image")
+        n_rows = int(torch.as_tensor(correspondences).reshape(-1, 4).shape[0])
+        row_donor = _losses.check_row_donor(row_donor, n_rows, what)
+        if len(acts) != len(activations_orig):
+            raise ValueError(f"{what}: activations of {len(acts)} layers, the host's have {len(activations_orig)}")
+        for k, (a, o) in enumerate(zip(acts, activations_orig)):
+            if a.shape[0] != o.shape[0]:
+                raise ValueError(f"{what}: activations of layer {k} hold {a.shape[0]} timesteps, the host's {o.shape[0]}")
+            # (prepared copies are channels-last [T,h,w,C], identity activations [T,C,h,w])
+            host_shape = (o.shape[2], o.shape[3], o.shape[1]) if isinstance(acts, DonorActivations) else tuple(o.shape[1:])
+            if tuple(a.shape[1:]) != host_shape:
+                raise ValueError(f"{what}: activations of layer {k} have shape {tuple(a.shape)}, the host's {tuple(o.shape)}")
+        if self.conf.fg_patch_size != 1:
+            raise NotImplementedError(f"donor with fg_patch_size = {self.conf.fg_patch_size} (only 1: the weighted energy has no "
+                                      "pooled form)")
+        if self.conf.bg_loss_type != "global_avg":
+            raise NotImplementedError(f"donor with bg_loss_type = {self.conf.bg_loss_type!r} (only 'global_avg')")
+        return acts, row_donor
 
     def _locks(self, lock, K, what):
         """`lock` of a loop call as K prepared background_lock.Lock / None (edits of one image share the trajectory's copy)."""
@@ -553,6 +617,9 @@ class GuidedStableDiffuser(GuidedDiffuser):
     def _energy_grad(self, st, k, act, t_idx, fgw, bgw, out=None, scale=None):
         """d(energy of layer k)/d(act) * scale (default grad_scale), act [h,w,C] channels-last; `out`: where to write it."""
         scale = self.grad_scale if scale is None else scale
+        if st.plan is not None and st.donor_bits:          # (prepare_guidance made sure the plan covers every guided layer)
+            return _losses.energy_and_grad_planned_donor(act, st.orig[k][t_idx], st.plan, fgw, bgw, st.donor[k][t_idx],
+                                                         st.donor_bits, grad_scale=scale, out=out)[1]
         if st.plan is not None and act.shape[0] == st.plan.grid and act.shape[1] == st.plan.grid:
             return energy_and_grad_planned(act, st.orig[k][t_idx], st.plan, fgw, bgw, grad_scale=scale, out=out)[1]
         return energy_and_grad(act, st.orig[k][t_idx], st.pc, fgw, bgw, self.conf.fg_patch_size, self.conf.bg_patch_size,
@@ -656,7 +723,17 @@ class GuidedStableDiffuser(GuidedDiffuser):
         planned = [e for e, st in enumerate(sts) if st.plan is not None and g == st.plan.grid and acts_k.shape[2] == g]
         if not (self._batch_energy and 2 <= len(planned) <= MAX_BATCH_ITEMS):
             planned = []
-        if planned:
+        if planned and any(sts[e].donor_bits for e in planned):
+            # donor edits: the donor batch takes weighted plans only; with an unweighted one among them, one by one
+            if all(sts[e].plan.weighted for e in planned):
+                _losses.energy_and_grad_planned_donor_batch(
+                    [acts_k[e] for e in planned], [sts[e].orig[k][t_idx] for e in planned], [sts[e].plan for e in planned],
+                    [fw[e] for e in planned], [bw[e] for e in planned], [S[e] for e in planned],
+                    [sts[e].donor[k][t_idx] if sts[e].donor_bits else None for e in planned],
+                    [sts[e].donor_bits for e in planned], outs=[out[e] for e in planned])
+            else:
+                planned = []
+        elif planned:
             # weighted and unweighted plans together: the mixed entry, still one launch pair; a set of one kind keeps its entry
             mixed = len({sts[e].plan.weighted for e in planned}) > 1
             entry = _losses.energy_and_grad_planned_mixed if mixed else energy_and_grad_planned_batch
@@ -731,7 +808,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def _batch_edit_steps(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                           fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None,
-                          object_weights=None, pair_instances=None, vacated=None, lock=None):
+                          object_weights=None, pair_instances=None, donor=None, vacated=None, lock=None):
         """The batched edit as a generator: yields after the preparation and after every denoising step (everything is only
         ENQUEUED on the current stream by then), returns the final latents [K,4,H,W] through StopIteration.  One body for the
         one-stream call below and for the lanes of guided_inference_batch_lanes.  fg_weight / bg_weight: one value, or one per
@@ -739,8 +816,12 @@ class GuidedStableDiffuser(GuidedDiffuser):
         label image and one weight list for all K edits (prepare_guidance).  lock: one (keep, trajectory) for all K edits or a list
         of K (prepare_guidance; None entries are unlocked edits).  pair_instances: None or a list of K, the instances of every
         edit's correspondence rows (prepare_guidance).  vacated: None, one image for all K edits or a list of K (None entries: edits that
-        delete nothing)."""
+        delete nothing).  donor: None or (activations_donor, list of K row_donor) -- one donor image for all K edits, whose
+        channels-last copy they share (prepare_guidance)."""
         K = len(depths)
+        if donor is not None and (not isinstance(donor, (tuple, list)) or len(donor) != 2 or not isinstance(donor[1], (list, tuple))
+                                  or len(donor[1]) != K):
+            raise ValueError(f"guided_inference_batch: donor must be (activations_donor, a list of {K} row_donor arrays)")
         if pair_instances is not None and len(pair_instances) != K:
             raise ValueError(f"guided_inference_batch: pair_instances has {len(pair_instances)} entries for {K} edits")
         per = lambda w, i: w[i] if isinstance(w, (list, tuple)) else w
@@ -758,6 +839,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
                                              orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond,
                                              object_labels=object_labels, object_weights=object_weights, lock=locks[i],
                                              pair_instances=None if pair_instances is None else pair_instances[i],
+                                             donor=None if donor is None else (sts[0].donor if sts else donor[0], donor[1][i]),
                                              vacated=per(vacated, i)))
         x = _nhwc(latents.to(self.device, torch.float32)).expand(K, -1, -1, -1).contiguous()
         yield None
@@ -770,20 +852,22 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference_batch(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                fg_weight=None, bg_weight=None, object_labels=None, object_weights=None,
-                               pair_instances=None, vacated=None, lock=None):
+                               pair_instances=None, donor=None, vacated=None, lock=None):
         """K edits of one image at once.  depths: list of K edited disparities [1,1,H,W]; correspondences_list:
         K [N_k,4] tensors; fg_weight / bg_weight: one value or K.  Needs an engine built with max_batch >= 2K.  Returns images
         [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value.  object_labels / object_weights: one
         label image and one weight list for all K edits (prepare_guidance).  lock: the background lock, one (keep, trajectory)
         for all K edits or a list of K (prepare_guidance).  pair_instances: None or a list of K, the instances of every edit's
         correspondence rows, in place of the label image (prepare_guidance).  vacated: None, one vacated image for all K edits
-        or a list of K with None for the edits that delete nothing (prepare_guidance; DESIGN.md "Object removal")."""
+        or a list of K with None for the edits that delete nothing (prepare_guidance; DESIGN.md "Object removal").  donor: None or
+        (activations_donor, list of K row_donor), one donor image for all K edits (prepare_guidance; DESIGN.md "Object
+        insertion")."""
         status = []
         with torch.no_grad(), self.on_stream():
             gen = self._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                          fg_weight, bg_weight, status_out=status, object_labels=object_labels,
                                          object_weights=object_weights, lock=lock, pair_instances=pair_instances,
-                                         vacated=vacated)
+                                         donor=donor, vacated=vacated)
             try:
                 while True:
                     next(gen)
@@ -939,7 +1023,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference_batch_lanes(self, latents, chunks, uncond_embeddings, prompt, activations_orig, streams=2,
                                      fg_weight=None, bg_weight=None, object_labels=None, object_weights=None,
-                                     pair_instances=None, vacated=None, lock=None):
+                                     pair_instances=None, donor=None, vacated=None, lock=None):
         """Batched edits of one image on `streams` concurrent lanes.  chunks: list of (depths, correspondences_list), each the
         argument pair of one guided_inference_batch call; chunk i runs on lane i % streams.  Every lane executes exactly the
         passes the one-stream call executes for its chunk (same batch, same kernels, private arenas), so the images are
@@ -947,7 +1031,10 @@ class GuidedStableDiffuser(GuidedDiffuser):
         object_labels / object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one
         (keep, trajectory) for every edit, or a list with one entry per edit over the chunks in order.  pair_instances: None or
         one list per chunk (guided_inference_batch).  vacated: None, one image for every edit, or one entry per chunk (each None, an
-        image or a list, as guided_inference_batch takes it)."""
+        image or a list, as guided_inference_batch takes it).  donor: None or (activations_donor, one list of row_donor per
+        chunk); the lanes share the channels-last copy of the donor's activations."""
+        if donor is not None and (len(donor) != 2 or len(donor[1]) != len(chunks)):
+            raise ValueError(f"guided_inference_batch_lanes: donor must be (activations_donor, one row_donor list per chunk)")
         if pair_instances is not None and len(pair_instances) != len(chunks):
             raise ValueError(f"guided_inference_batch_lanes: pair_instances has {len(pair_instances)} entries for {len(chunks)} chunks")
         if isinstance(vacated, (list, tuple)) and len(vacated) != len(chunks):
@@ -964,21 +1051,24 @@ class GuidedStableDiffuser(GuidedDiffuser):
             # (prepared here, on this stream, which every lane waits for: the lanes share the copies)
             offs = np.cumsum([0] + [len(d) for d, _ in chunks])
             locks = self._locks(lock, int(offs[-1]), "guided_inference_batch_lanes")
+            dacts = None if donor is None else DonorActivations(
+                a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in donor[0])
 
-            def make(depths, corrs, status, lk, inst, vac):
+            def make(depths, corrs, status, lk, inst, vac, dn):
                 def job(lane):
                     def body():
                         lat = yield from lane._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig,
                                                                 corrs, fg_weight, bg_weight, cond=cond, orig=orig,
                                                                 status_out=status, object_labels=object_labels,
                                                                 object_weights=object_weights, lock=lk, pair_instances=inst,
-                                                                vacated=vac)
+                                                                donor=dn, vacated=vac)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
             vac_of = lambda i: vacated[i] if isinstance(vacated, (list, tuple)) else vacated
             images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, locks[int(offs[i]):int(offs[i + 1])],
-                                                                 None if pair_instances is None else pair_instances[i], vac_of(i))
+                                                                 None if pair_instances is None else pair_instances[i], vac_of(i),
+                                                                 None if donor is None else (dacts, donor[1][i]))
                                                             for i, ((d, c), s) in enumerate(zip(chunks, statuses))])
             if any(statuses):      # edits numbered over the chunks in order; read after every lane has finished
                 self.raise_on_status([(int(offs[i]) + b, row) for i, s in enumerate(statuses)
@@ -987,7 +1077,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def _edit_steps(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences, fg_weight=None,
                     bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None, object_weights=None,
-                    pair_instances=None, vacated=None, lock=None):
+                    pair_instances=None, donor=None, vacated=None, lock=None):
         """One edit as a generator (see _batch_edit_steps): yields after the preparation and after every denoising step,
         returns the final latents [1,4,H,W].  lock: the edit's background lock (prepare_guidance)."""
         torch.manual_seed(self.conf.seed)
@@ -995,7 +1085,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
         timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
         st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight, orig=orig, cond=cond,
                                    object_labels=object_labels, object_weights=object_weights, lock=lock,
-                                   pair_instances=pair_instances, vacated=vacated)
+                                   pair_instances=pair_instances, donor=donor, vacated=vacated)
         x = _nhwc(latents.to(self.device, torch.float32))
         yield None
         for t_idx, t in enumerate(timesteps):
@@ -1006,13 +1096,17 @@ class GuidedStableDiffuser(GuidedDiffuser):
         return x.permute(0, 3, 1, 2)
 
     def guided_inference_lanes(self, latents, edits, uncond_embeddings, prompt, activations_orig, streams=2, fg_weight=None,
-                               bg_weight=None, object_labels=None, object_weights=None, pair_instances=None, vacated=None, lock=None):
+                               bg_weight=None, object_labels=None, object_weights=None, pair_instances=None, donor=None,
+                               vacated=None, lock=None):
         """Single (B = 1) edits of one image on `streams` concurrent lanes.  edits: list of (depth, correspondences), the
         argument pair of guided_inference; edit i runs on lane i % streams with exactly the passes guided_inference runs, so
         the images are bit-identical to the one-stream calls.  Returns a list of images [1,3,H,W].  object_labels /
         object_weights: one label image and one weight list for every edit (prepare_guidance).  lock: one (keep, trajectory)
         for every edit, or a list with one entry per edit.  pair_instances: None or a list with one entry per edit
-        (prepare_guidance).  vacated: None, one image for every edit, or a list with one entry per edit (prepare_guidance)."""
+        (prepare_guidance).  vacated: None, one image for every edit, or a list with one entry per edit (prepare_guidance).
+        donor: None or (activations_donor, a list with one row_donor per edit); the lanes share the donor's channels-last copy."""
+        if donor is not None and (len(donor) != 2 or len(donor[1]) != len(edits)):
+            raise ValueError(f"guided_inference_lanes: donor must be (activations_donor, one row_donor per edit)")
         if pair_instances is not None and len(pair_instances) != len(edits):
             raise ValueError(f"guided_inference_lanes: pair_instances has {len(pair_instances)} entries for {len(edits)} edits")
         if isinstance(vacated, (list, tuple)) and len(vacated) != len(edits):
@@ -1023,40 +1117,44 @@ class GuidedStableDiffuser(GuidedDiffuser):
             cond = self._encode([prompt]).contiguous()
             orig = [a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in activations_orig]
             locks = self._locks(lock, len(edits), "guided_inference_lanes")      # (on this stream, which every lane waits for)
+            dacts = None if donor is None else DonorActivations(
+                a.to(self.device).permute(0, 2, 3, 1).to(self.dtype).contiguous() for a in donor[0])
 
-            def make(depth, corr, status, lk, inst, vac):
+            def make(depth, corr, status, lk, inst, vac, dn):
                 def job(lane):
                     def body():
                         lat = yield from lane._edit_steps(latents, depth, uncond_embeddings, prompt, activations_orig, corr,
                                                           fg_weight, bg_weight, cond=cond, orig=orig, status_out=status,
                                                           object_labels=object_labels, object_weights=object_weights, lock=lk,
-                                                          pair_instances=inst, vacated=vac)
+                                                          pair_instances=inst, donor=dn, vacated=vac)
                         return lane._decode_serialized(lat)
                     return body()
                 return job
             insts = [None] * len(edits) if pair_instances is None else pair_instances
             vacs = list(vacated) if isinstance(vacated, (list, tuple)) else [vacated] * len(edits)
-            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, lk, n, v)
-                                                            for (d, c), s, lk, n, v in zip(edits, statuses, locks, insts, vacs)])
+            dns = [None] * len(edits) if donor is None else [(dacts, r) for r in donor[1]]
+            images = GuidedStableDiffuser.run_lanes(lanes, [make(d, c, s, lk, n, v, dn)
+                                                            for (d, c), s, lk, n, v, dn in zip(edits, statuses, locks, insts, vacs, dns)])
             if any(statuses):      # read after every lane has finished
                 self.raise_on_status([(i, s[0][0].cpu().tolist()) for i, s in enumerate(statuses)])
         return images
 
     def guided_inference(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences,
                          fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None, object_labels=None,
-                         object_weights=None, pair_instances=None, vacated=None, lock=None):
+                         object_weights=None, pair_instances=None, donor=None, vacated=None, lock=None):
         """object_labels (or pair_instances, the instance of every correspondence row of an edit with copies) / object_weights:
         a weight per object for the foreground term (prepare_guidance).  lock: (keep,
         trajectory), the background lock -- after every DDIM step the latents are blended with the reconstruction's outside
         the edit's region (prepare_guidance; DESIGN.md "Background lock").  vacated: the image of the pixels the edit's removed
-        objects leave behind (prepare_guidance; DESIGN.md "Object removal")."""
+        objects leave behind (prepare_guidance; DESIGN.md "Object removal").  donor: (activations_donor, row_donor) of an edit
+        that brings in objects of another image (prepare_guidance; DESIGN.md "Object insertion")."""
         with torch.no_grad(), self.on_stream():
             torch.manual_seed(self.conf.seed)
             self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
             timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
             st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight,
                                        object_labels=object_labels, object_weights=object_weights, lock=lock,
-                                       pair_instances=pair_instances, vacated=vacated)
+                                       pair_instances=pair_instances, donor=donor, vacated=vacated)
             denoising_steps = {"opt": [], "post-opt": []} if save_denoising_steps else None
             x = _nhwc(latents.to(self.device, torch.float32))
             for t_idx, t in enumerate(timesteps):

@@ -88,8 +88,19 @@ def check_vacated(vacated, img_res, what="process_correspondences"):
     return v.reshape(int(img_res), int(img_res))
 
 
-def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, vacated=None, object_labels=None,
-                            pair_instances=None):
+def check_row_donor(row_donor, n_rows, what="process_correspondences"):
+    """The donor flags of an edit's correspondence rows -> None or a flat uint8 tensor of n_rows entries (non-zero = the row's
+    source pixel lies in the donor image).  ValueError naming `what` for another length.  Host only: it reads the shape."""
+    if row_donor is None:
+        return None
+    r = torch.as_tensor(row_donor).reshape(-1)
+    if r.numel() != int(n_rows):
+        raise ValueError(f"{what}: row_donor has {r.numel()} entries for {n_rows} correspondences")
+    return r
+
+
+def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, row_donor=None, vacated=None,
+                            object_labels=None, pair_instances=None):
     """[N,4] int64 (ox,oy,tx,ty) -> dict with original_x/y, transformed_x/y, background_x/y[_orig|_trans].
     object_labels ([H, W] uint8, object_label_image): adds "object", the 0-based object of every kept pair (int64, host), and
     `pair_obj` (uint8, device) to device_lists.
@@ -100,8 +111,12 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
     vacated ([img_res, img_res], non-zero on the pixels of the objects the edit DELETES; DESIGN.md "Object removal"): a cell that
     holds a vacated pixel leaves the original-background list as if a kept correspondence started in it, before the erosion;
     the transformed-background list and the pairs do not see it.  None is the call without it (an all-zero image gives the
-    same lists); the correspondences may then be empty (the pure removal).  The keys of the dict do not change."""
+    same lists); the correspondences may then be empty (the pure removal).  The keys of the dict do not change.
+    row_donor ([N] uint8, non-zero = the row's source pixel lies in a DONOR image; DESIGN.md "Object insertion"): such a row
+    forms its pair and clears its target cell like any row, and leaves the original-background list alone -- nothing of the
+    host started there.  None is the call without it, with the launches it had (all zeros give the same lists)."""
     vacated = check_vacated(vacated, img_res)
+    row_donor = check_row_donor(row_donor, int(torch.as_tensor(correspondences).reshape(-1, 4).shape[0]))
     if object_labels is not None and pair_instances is not None:
         raise ValueError("process_correspondences: object_labels and pair_instances are mutually exclusive")
     if pair_instances is not None:
@@ -125,7 +140,12 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     args = (_lib.ptr(corr) if n else _lib.c_p(0), n, int(img_res), grid, int(bg_erosion), _lib.ptr(pairs), _lib.ptr(bg_lists),
             _lib.ptr(bg_masks), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, _lib.stream_ptr())
-    if vacated is None:
+    if row_donor is not None:
+        vac = None if vacated is None else (vacated.to(dev) != 0).to(torch.uint8).contiguous()
+        flags = (row_donor.to(dev) != 0).to(torch.uint8).contiguous()
+        _lib.check(L.dh_cells_from_correspondences_donor(*args, _lib.ptr(vac), _lib.ptr(flags) if n else _lib.c_p(0)),
+                   "dh_cells_from_correspondences_donor")
+    elif vacated is None:
         _lib.check(L.dh_cells_from_correspondences(*args), "dh_cells_from_correspondences")
     else:
         vac = (vacated.to(dev) != 0).to(torch.uint8).contiguous()
@@ -189,16 +209,25 @@ class EnergyPlan:
     target-cell -> source-cells CSR and the transformed-background flags (dh_energy_plan_build).
     object_weights ("equal" or one weight per object; the correspondences must carry "object", process_correspondences with
     object_labels): the weighted plan of dh_energy_plan_build_objects -- `weighted` is then True, `omega` / `counts` hold
-    omega_m and N_m, and the planned calls route to the _objects entries.  None, or a single object: the plan above."""
+    omega_m and N_m, and the planned calls route to the _objects entries.  None, or a single object: the plan above --
+    unless force_weighted (donor edits, whose kernels read the object of every entry: a weighted plan even for one object;
+    object_weights None then means w_m = N_m, which gives every pair the unweighted coefficient fg_w / (C N) up to rounding).
+    `n_objects` is the object count a weighted plan was built for."""
 
     weighted = False
+    n_objects = 0
 
-    def __init__(self, processed_correspondences, grid, device, object_weights=None):
+    def __init__(self, processed_correspondences, grid, device, object_weights=None, force_weighted=False):
         L = _lib.lib()
         self.grid = int(grid)
         self.dl = _device_lists(processed_correspondences, device, self.grid)
         self.n_pairs = int(self.dl["pairs"].shape[0])
         self._ws = {}
+        if force_weighted and object_weights is None:
+            if "object" not in processed_correspondences:
+                raise ValueError("EnergyPlan: a forced weighted plan needs correspondences processed with pair_instances")
+            objects = np.asarray(processed_correspondences["object"], dtype=np.int64)
+            object_weights = [float(c) for c in np.bincount(objects, minlength=1)] if objects.size else [1.0]
         if object_weights is not None:
             if "object" not in processed_correspondences:
                 raise ValueError("EnergyPlan: object_weights need correspondences processed with object_labels")
@@ -208,7 +237,7 @@ class EnergyPlan:
             if not 1 <= M <= MAX_OBJECTS:
                 raise ValueError(f"EnergyPlan: {M} objects, 1 to {MAX_OBJECTS} are supported")
             counts, omega = object_omegas(objects, w)
-            if M > 1:
+            if M > 1 or force_weighted:
                 self._build_weighted(L, w, counts, omega, device)
                 return
         nb = ctypes.c_size_t()
@@ -223,7 +252,7 @@ class EnergyPlan:
         M = len(w)
         if self.dl.get("pair_obj") is None or self.dl["pair_obj"].numel() != self.n_pairs:
             raise ValueError("EnergyPlan: the device lists carry no object per pair")
-        self.weighted, self.counts, self.omega = True, counts, omega
+        self.weighted, self.counts, self.omega, self.n_objects = True, counts, omega, M
         nb = ctypes.c_size_t()
         _lib.check(L.dh_energy_plan_objects_bytes(self.grid, self.n_pairs, ctypes.byref(nb)), "dh_energy_plan_objects_bytes")
         self.nbytes = nb.value
@@ -271,6 +300,51 @@ def energy_and_grad_planned(act, act_orig, plan, fg_weight, bg_weight, grad_scal
     return loss, grad
 
 
+def check_donor_objects(donor_objects, plan, what):
+    """The donor bits of one evaluation against its plan (host only): a weighted plan, no bit at or above its object count."""
+    bits = int(donor_objects)
+    if bits < 0 or bits >> 32:
+        raise ValueError(f"{what}: donor_objects={donor_objects!r} is not a 32-bit mask")
+    if not plan.weighted:
+        raise ValueError(f"{what}: donor objects need a weighted plan (EnergyPlan with object_weights or force_weighted)")
+    if bits >> plan.n_objects:
+        raise ValueError(f"{what}: donor_objects={bits:#x} names an object at or above the plan's {plan.n_objects}")
+    return bits
+
+
+def energy_and_grad_planned_donor(act, act_orig, plan, fg_weight, bg_weight, act_donor, donor_objects, grad_scale=1.0,
+                                  want_loss=False, out=None, grad_dtype=None):
+    """energy_and_grad_planned for an edit with objects of another image (dh_energy_fwd_bwd_planned_donor; DESIGN.md "Object
+    insertion"): the foreground term of a pair of object m reads act_donor where bit m of donor_objects is set, act_orig
+    otherwise; act_donor is laid out like act_orig (None only with donor_objects = 0).  The plan is a weighted EnergyPlan;
+    with object_weights None (force_weighted) w_m = N_m, the unweighted coefficient up to rounding.  donor_objects = 0 gives the
+    bytes of energy_and_grad_planned.  ValueError before any launch for a bit at or above the plan's object count."""
+    what = "energy_and_grad_planned_donor"
+    _lib.require_gpu(act)
+    bits = check_donor_objects(donor_objects, plan, what)
+    h, w, C = act.shape
+    if h != plan.grid or w != plan.grid or act.dtype not in (torch.float16, torch.bfloat16) or act_orig.dtype != act.dtype:
+        raise ValueError("planned energy: maps must be 16-bit [grid, grid, C] of one dtype")
+    if bits and (act_donor is None or act_donor.dtype != act.dtype or tuple(act_donor.shape) != tuple(act.shape)):
+        raise ValueError(f"{what}: act_donor must be a map like act_orig")
+    a = act.detach().contiguous()
+    o = act_orig.detach().contiguous()
+    dn = None if act_donor is None else act_donor.detach().contiguous()
+    gdt = a.dtype if grad_dtype is None else grad_dtype
+    if out is not None and (out.shape != a.shape or out.dtype != gdt or not out.is_contiguous()):
+        raise ValueError("planned energy: `out` must be a contiguous tensor like the activation")
+    grad = torch.empty(a.shape, dtype=gdt, device=a.device) if out is None else out
+    loss = torch.zeros(3, dtype=torch.float32, device=a.device) if want_loss else None
+    ws, wsb = plan.workspace(C)
+    dl = plan.dl
+    _lib.check(_lib.lib().dh_energy_fwd_bwd_planned_donor(
+        _lib.ptr(a), _lib.ptr(o), _lib.DTYPE_CODE[a.dtype], C, plan.grid, _lib.ptr(plan.buf), plan.nbytes, plan.n_pairs,
+        _lib.ptr(dl["bg_orig"]), dl["bg_orig"].numel(), _lib.ptr(dl["bg_trans"]), dl["bg_trans"].numel(),
+        float(fg_weight), float(bg_weight), float(grad_scale), _lib.ptr(loss), _lib.ptr(grad),
+        _lib.DTYPE_CODE[grad.dtype], _lib.ptr(ws), wsb, _lib.stream_ptr(), _lib.ptr(dn), bits), "dh_energy_fwd_bwd_planned_donor")
+    return loss, grad
+
+
 MAX_BATCH_ITEMS = 16      # ENERGY_MAX_ITEMS of csrc/energy.hip: the item table travels in the kernel arguments
 
 
@@ -295,7 +369,8 @@ def _batch_state(plans, C):
     return cache[key][:3]
 
 
-def _planned_batch_call(entry_name, flags, acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss, outs, grad_dtype):
+def _planned_batch_call(entry_name, flags, acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss, outs, grad_dtype,
+                        call=None):
     """The argument checks and the item table of the batched planned entries, then the call: `entry_name` with the per-item
     flags of the mixed entry (flags = True) or without them."""
     K = len(acts)
@@ -325,9 +400,35 @@ def _planned_batch_call(entry_name, flags, acts, acts_orig, plans, fg_weights, b
         it.fg_w, it.bg_w, it.grad_scale = float(fg_weights[e]), float(bg_weights[e]), float(grad_scales[e])
     # the flags are host bytes: the entry reads them while it fills the kernels' by-value tables, no kernel does
     head = (items, (ctypes.c_uint8 * K)(*[1 if p.weighted else 0 for p in plans])) if flags else (items,)
-    _lib.check(getattr(_lib.lib(), entry_name)(*head, K, _lib.DTYPE_CODE[dt], C, grid, _lib.DTYPE_CODE[gdt], _lib.ptr(ws), wsb,
+    _lib.check((call or getattr(_lib.lib(), entry_name))(*head, K, _lib.DTYPE_CODE[dt], C, grid, _lib.DTYPE_CODE[gdt], _lib.ptr(ws), wsb,
                                                _lib.stream_ptr()), entry_name)
     return loss, outs
+
+
+def energy_and_grad_planned_donor_batch(acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, acts_donor, donor_objects,
+                                        want_loss=False, outs=None, grad_dtype=None):
+    """energy_and_grad_planned_donor for K <= 16 items in one launch pair (dh_energy_fwd_bwd_planned_donor_batch): the arguments
+    of energy_and_grad_planned_batch, then per item the donor map (None with no bit set) and the donor bits.  Weighted plans
+    only.  Item e is bit-identical to the single call."""
+    what = "energy_and_grad_planned_donor_batch"
+    K = len(acts)
+    if len(acts_donor) != K or len(donor_objects) != K:
+        raise ValueError("planned energy batch: the per-item lists must be non-empty and of one length")
+    bits = [check_donor_objects(b, p, f"{what}: item {e}") for e, (b, p) in enumerate(zip(donor_objects, plans))]
+    for e, (dn, a) in enumerate(zip(acts_donor, acts)):
+        if bits[e] and (dn is None or dn.dtype != a.dtype or tuple(dn.shape) != tuple(a.shape) or not dn.is_contiguous()):
+            raise ValueError(f"{what}: item {e}: the donor map must be a contiguous map like the activation")
+
+    def call(items, *tail):
+        donor_items = (_lib.EnergyDonorItem * K)()
+        for e in range(K):
+            donor_items[e].item = items[e]
+            donor_items[e].donor = acts_donor[e].data_ptr() if acts_donor[e] is not None else None
+            donor_items[e].donor_objects = bits[e]
+        return _lib.lib().dh_energy_fwd_bwd_planned_donor_batch(donor_items, *tail)
+
+    return _planned_batch_call("dh_energy_fwd_bwd_planned_donor_batch", False, acts, acts_orig, plans, fg_weights, bg_weights,
+                               grad_scales, want_loss, outs, grad_dtype, call=call)
 
 
 def energy_and_grad_planned_batch(acts, acts_orig, plans, fg_weights, bg_weights, grad_scales, want_loss=False, outs=None,

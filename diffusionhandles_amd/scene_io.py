@@ -460,6 +460,50 @@ def entry_instances(objects, n_masks=None, where="objects"):
     return inst
 
 
+def _is_donor(o):
+    return isinstance(o, dict) and "donor" in o
+
+
+def entry_donor(objects, n_donor=None, where="objects"):
+    """Object insertion in an "objects" list (not in the reference): a member {"donor": d, ...transform keys} is an instance of
+    mask d of the scene's donor image (donor/mask_d.png).  Returns None when no member carries "donor" (the list is then read as
+    always), else (host members, donor members, the donor mask index of every donor member).  The donor members stand BEHIND the
+    host's, as the donor's masks stand behind the host's in the edit's object list.  ValueError naming `where` and the member:
+    a "donor" that is not an integer >= 0, a donor member that also carries "mask" or "remove", a host member behind a donor
+    member, and, when n_donor is given, a scene without donor/ masks, an index outside 0..n_donor-1 or a donor mask that no
+    member draws."""
+    if not any(_is_donor(o) for o in objects):
+        return None
+    host, members, index = [], [], []
+    for n, o in enumerate(objects):
+        if not _is_donor(o):
+            if members:
+                raise ValueError(f"{where}, object {n}: a member of the host image stands behind a donor member (donor members "
+                                 "come last)")
+            host.append(o)
+            continue
+        d = o["donor"]
+        if isinstance(d, bool) or not isinstance(d, int) or d < 0:
+            raise ValueError(f"{where}, object {n}: \"donor\" must be the index of a donor mask (an integer >= 0), got {d!r}")
+        for key in ("mask", "remove"):
+            if key in o:
+                raise ValueError(f"{where}, object {n}: a donor member takes no \"{key}\"")
+        members.append(OrderedDict((k, v) for k, v in o.items() if k != "donor"))
+        index.append(d)
+    if n_donor is not None:
+        if n_donor == 0:
+            raise ValueError(f"{where}: a member carries \"donor\" but the scene has no donor/ directory with mask_0.png")
+        if len(host) + len(members) > MAX_SCENE_OBJECTS:
+            raise ValueError(f"{where} lists {len(host) + len(members)} instances, at most {MAX_SCENE_OBJECTS} are supported")
+        for d in index:
+            if d >= n_donor:
+                raise ValueError(f"{where}: donor mask {d} does not exist, the scene's donor has {n_donor} masks")
+        for d in range(n_donor):
+            if d not in index:
+                raise ValueError(f"{where}: no member draws donor mask {d} (an edit with a donor places every donor mask)")
+    return host, members, index
+
+
 def _is_removal(o):
     return isinstance(o, dict) and "remove" in o
 
@@ -509,12 +553,29 @@ def entry_removal(objects, n_masks=None, where="objects"):
     return removed, members, (None if inst == list(range(len(inst))) else inst)
 
 
-def _check_object_entries(scene_dir, transforms, n_masks):
+def _check_object_entries(scene_dir, transforms, n_masks, n_donor=0):
     """transforms.json against the scene's masks: a multi-mask scene (n_masks >= 1 mask_m.png files) wants {"objects": [n_masks
     entries]} everywhere -- or, when members carry "mask" (copies of an object, entry_instances), n_masks to 8 entries that
     draw every mask -- a single-mask scene (n_masks = 0) no "objects" at all.  ValueError naming the scene and the entry."""
     for name, t in transforms.items():
         has = isinstance(t, dict) and "objects" in t
+        if has and isinstance(t["objects"], (list, tuple)) and any(_is_donor(o) for o in t["objects"]):
+            # donor members are checked by entry_donor; what is left is an ordinary entry of the host's members
+            where = f"{scene_dir}: transform {name!r}"
+            if n_masks == 0:
+                raise ValueError(f"{where}: donor members need a multi-object scene (mask_0.png ...)")
+            host, members, _ = entry_donor(t["objects"], n_donor, where)
+            w = t.get("object_weights")
+            rem = entry_removal(host, n_masks, where)
+            n_left = len(host) - (0 if rem is None else len(rem[0]))
+            if isinstance(w, (list, tuple)) and len(w) != n_left + len(members):
+                raise ValueError(f"{where} has {len(w)} object_weights for {n_left + len(members)} instances")
+            if n_masks + n_donor - (0 if rem is None else len(rem[0])) > MAX_SCENE_OBJECTS:
+                raise ValueError(f"{where}: {n_masks} masks and {n_donor} donor masks, at most {MAX_SCENE_OBJECTS} in all")
+            rest = OrderedDict((k, v) for k, v in t.items() if k != "object_weights")
+            rest["objects"] = host
+            _check_object_entries(scene_dir, {name: rest}, n_masks)
+            continue
         if n_masks == 0 and _is_removal(t):          # a single-mask scene: {"remove": true} deletes the one object
             if t["remove"] is not True or len(t) != 1:
                 raise ValueError(f"{scene_dir}: transform {name!r}: an entry that removes the object is exactly "
@@ -604,7 +665,12 @@ def load_scene_geometry(scene_dir, img_res=512):
     A member of "objects" may be {"remove": true} (not in the reference; object removal): it deletes the mask of its own position
     -- it carries no transform key and no "mask", and no other member may name its mask; "object_weights" lists have one entry
     per remaining member.  In a single-mask scene the entry {"remove": true} deletes the one object.  bg_depth has the removed
-    objects removed, as it has all objects.  Files without "remove" load to exactly what they loaded to."""
+    objects removed, as it has all objects.  Files without "remove" load to exactly what they loaded to.
+    A scene directory may hold donor/ (not in the reference; object insertion): depth.exr / .npy and mask_0.png .. mask_{D-1}.png
+    of a SECOND image (and, for load_scene, its input.png and prompt.txt).  The dict then also has donor = dict(depth, masks).
+    A member of "objects" may carry "donor": d: it is an instance of donor mask d, stands behind the host's members, carries
+    no "mask" and no "remove", and an entry with donor members draws every donor mask (entry_donor).  The depth scale between
+    the two images is not estimated: the member's "scale" brings it.  Files without the key load to what they loaded to."""
     import torch
     j = os.path.join
     with open(j(scene_dir, "transforms.json")) as f:
@@ -617,6 +683,13 @@ def load_scene_geometry(scene_dir, img_res=512):
             mask = mask.mean(dim=1, keepdim=True)
         return (crop_and_resize(mask, img_res) > 0.5).to(torch.float32)
 
+    n_donor = 0
+    while os.path.exists(j(scene_dir, "donor", f"mask_{n_donor}.png")):
+        n_donor += 1
+    if os.path.isdir(j(scene_dir, "donor")) and n_donor == 0:
+        raise ValueError(f"{scene_dir}: donor/ holds no mask_0.png")
+    if n_donor > MAX_SCENE_OBJECTS:
+        raise ValueError(f"{scene_dir}: {n_donor} donor masks, at most {MAX_SCENE_OBJECTS} are supported")
     masks = None
     if os.path.exists(j(scene_dir, "mask_0.png")):
         M = 1
@@ -624,14 +697,14 @@ def load_scene_geometry(scene_dir, img_res=512):
             M += 1
         if M > MAX_SCENE_OBJECTS:
             raise ValueError(f"{scene_dir}: {M} object masks, at most {MAX_SCENE_OBJECTS} are supported")
-        _check_object_entries(scene_dir, transforms, M)
+        _check_object_entries(scene_dir, transforms, M, n_donor)
         masks = [mask_of(f"mask_{m}.png") for m in range(M)]
         union = masks[0] != 0
         for m in masks[1:]:
             union = union | (m != 0)
         mask = union.to(torch.float32)
     else:
-        _check_object_entries(scene_dir, transforms, 0)
+        _check_object_entries(scene_dir, transforms, 0, n_donor)
         mask = mask_of("mask.png")
 
     def depth_of(stem):
@@ -646,6 +719,8 @@ def load_scene_geometry(scene_dir, img_res=512):
     geo = dict(transforms=transforms, fg_mask=mask, depth=depth_of("depth"), bg_depth=depth_of("bg_depth"))
     if masks is not None:
         geo["fg_masks"] = masks
+    if n_donor:
+        geo["donor"] = dict(depth=depth_of(j("donor", "depth")), masks=[mask_of(j("donor", f"mask_{d}.png")) for d in range(n_donor)])
     return geo
 
 
@@ -665,6 +740,13 @@ def load_scene(scene_dir, img_res=512):
               bg_depth=geo["bg_depth"])
     if "fg_masks" in geo:          # a multi-object scene (load_scene_geometry)
         sc["fg_masks"] = geo["fg_masks"]
+    if "donor" in geo:             # the second image of an insertion: its own picture and prompt beside its depth and masks
+        with open(j(scene_dir, "donor", "prompt.txt")) as f:
+            lines = [ln for ln in f.read().splitlines() if len(ln) > 0]
+        if not lines:
+            raise ValueError(f"{scene_dir}: donor: empty prompt")
+        dimg = crop_and_resize(load_image(j(scene_dir, "donor", "input.png"))[None][:, :3], img_res)
+        sc["donor"] = dict(geo["donor"], img=dimg, prompt=lines[0])
     return sc
 
 
@@ -695,9 +777,24 @@ def object_transform_args(entry):
     whose entry has "scale" or "pivot" gives the 5-tuple (rot_angle, rot_axis, translation, scale, pivot) instead.  When a
     member carries "mask" (entry_instances) the dict also has `instances`, the mask index of every member.  When a member is
     {"remove": true} (entry_removal) the dict also has `remove`, the mask indices the edit deletes; transforms, weights and
-    `instances` then speak about the remaining members and the remaining masks."""
+    `instances` then speak about the remaining members and the remaining masks.  When a member carries "donor" (entry_donor)
+    the dict also has `donor`, the donor mask index of every donor member: `transforms` and the weights list the host's
+    (remaining) members and then the donor's, and `instances` is always there -- the host's table (or 0, 1, ...), then
+    M' + d for a member of donor mask d, M' the number of (remaining) host masks."""
     if not isinstance(entry, dict) or "objects" not in entry:
         raise ValueError("object_transform_args: the entry has no \"objects\" list")
+    dn = entry_donor(entry["objects"], None, "object_transform_args")
+    if dn is not None:
+        host, members, index = dn
+        out = object_transform_args({"objects": host}) if host else dict(transforms=[], object_weights=None)
+        n_host = max(out["instances"]) + 1 if "instances" in out else len(out["transforms"])
+        more = object_transform_args({"objects": members})
+        out["transforms"] = out["transforms"] + more["transforms"]
+        out["instances"] = out.get("instances", list(range(n_host))) + [n_host + d for d in index]
+        w = entry.get("object_weights")
+        out["object_weights"] = w if w is None or isinstance(w, str) else [float(v) for v in w]
+        out["donor"] = index
+        return out
     rem = entry_removal(entry["objects"], None, "object_transform_args")
     members = entry["objects"] if rem is None else rem[1]
     triples = []

@@ -162,6 +162,30 @@ int dh_reproject_instance_edits(const float* depth, const float* bg_depth, const
                                 void* workspace, size_t workspace_bytes, void* stream,
                                 int footprints, float max_ratio, int corr_capacity,
                                 int n_instances, const int32_t* inst_obj, uint8_t* corr_inst);
+/* Object insertion (not in the reference; DESIGN.md, "Object insertion"): dh_reproject_instance_edits with masks of a second
+ * image.  Masks n_host_objects .. n_objects - 1 of fg_pix / obj_start are masks of the DONOR image (same resolution, same
+ * intrinsics): their points are the unprojection of donor_depth [res][res] f32 at their pixels, their centroid the sequential
+ * f32 centroid of those points.  Everything from the transform row on is shared: one z-buffer over the background and all
+ * instances, masks, visibility, in-fill, normalisation.  A correspondence row of a donor instance carries its source pixel in
+ * the donor image; corr_inst (required with a donor) tells which rows those are: inst_obj[corr_inst[r]] >= n_host_objects.
+ * Donor pixels may coincide with host pixels.  n_host_objects = 0 is the pure insertion.
+ * Refused (DH_ERR_ARG before any launch, outputs untouched), beyond what dh_reproject_instance_edits refuses: n_host_objects
+ * outside 0 .. n_objects; with n_host_objects < n_objects a null donor_depth, footprints != 0 (the pixel -> list-position
+ * inverse of the triangles is ambiguous when two images share pixel indices) or a null corr_inst.
+ * dh_reproject_instance_edits is this entry's donor_depth = NULL, n_host_objects = n_objects call; the workspace is
+ * dh_reproject_instances_workspace_bytes' under a name of its own. */
+int dh_reproject_donor_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances, int footprints,
+                                       size_t* bytes);
+int dh_reproject_donor_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                             int n_edits, const double* xforms_host, const float* bounds,
+                             float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                             uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                             void* workspace, size_t workspace_bytes, void* stream,
+                             int footprints, float max_ratio, int corr_capacity,
+                             int n_instances, const int32_t* inst_obj, uint8_t* corr_inst,
+                             const float* donor_depth, int n_host_objects);
 /* Object removal, the pure case (not in the reference; DESIGN.md, "Object removal"): the re-projection of the background
  * alone, for an edit that deletes its objects and moves none.  The point list is the res * res pixels of bg_depth; it runs the
  * kernels of the entries above on that part of the list: z-buffer (winner = min (z, point index)), zmap (+inf where no point
@@ -219,6 +243,15 @@ int dh_cells_from_correspondences_vacated(const int64_t* corr, int n, int img_re
                                           int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
                                           void* workspace, size_t workspace_bytes, void* stream,
                                           const uint8_t* vacated);
+/* Object insertion (not in the reference; DESIGN.md, "Object insertion"): the _vacated entry with row_donor [n] u8 on the
+ * device (may be NULL), non-zero on the correspondence rows whose source pixel lies in a donor image.  Such a row forms its
+ * pair and clears its target cell from the transformed-background mask like any row, and does NOT clear a cell of the
+ * original-background mask: nothing of the host started there.  NULL (and an all-zero array) is the _vacated entry in every
+ * output byte, which is this entry's NULL call; same workspace, same refusals. */
+int dh_cells_from_correspondences_donor(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                        int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                        void* workspace, size_t workspace_bytes, void* stream,
+                                        const uint8_t* vacated, const uint8_t* row_donor);
 
 /* Keep map of the background lock: keep [s][s] f32, 0 inside the region an edit touches, 1 far from it, a ramp between.
  * A latent cell (res / s pixels square) is a REGION cell if one of its pixels is non-zero in mask or release (u8 [res][res],
@@ -348,6 +381,29 @@ int dh_energy_fwd_bwd_planned_objects_batch(const dh_energy_item* items, int n_i
  * its kind needs (so a weighted flag on a plain plan's buffer is refused). */
 int dh_energy_fwd_bwd_planned_mixed_batch(const dh_energy_item* items, const uint8_t* weighted, int n_items, int dtype, int C,
                                           int grid, int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Donor objects (not in the reference; DESIGN.md, "Object insertion"): dh_energy_fwd_bwd_planned_objects[_batch] for edits
+ * that bring in objects of another image.  donor: that image's activations, [grid * grid][C] channels-last in the dtype of
+ * orig; donor_objects: bit m set = the foreground term of a pair of object m reads A_donor[c, o_n] in place of A_orig[c, o_n].
+ * The plan is dh_energy_plan_build_objects', unchanged; the background term and its lists read orig.  One writer per gradient
+ * element, objects ascending, no atomics.  donor_objects = 0 (donor may then be NULL) launches and computes what the _objects
+ * entry does; donor == orig with any bits gives its bytes too.  The batch takes K <= 16 weighted items, each with its donor;
+ * item e is bit-identical to the single call.  Workspaces are the _objects entries'.  Refused before any launch: a bit at
+ * or above 8 (the most objects a plan holds; the plan's own count lives on the device, so the caller checks bits against
+ * it), bits set with a null donor, and what the _objects entries refuse. */
+int dh_energy_fwd_bwd_planned_donor(const void* cur, const void* orig, int dtype, int C, int grid,
+                                    const void* plan, size_t plan_bytes, int n_pairs,
+                                    const int32_t* bg_orig, int n_bg_orig, const int32_t* bg_trans, int n_bg_trans,
+                                    float fg_w, float bg_w, float grad_scale, float* loss_out, void* grad,
+                                    int grad_dtype, void* workspace, size_t workspace_bytes, void* stream,
+                                    const void* donor, uint32_t donor_objects);
+typedef struct dh_energy_donor_item {
+  dh_energy_item item;
+  const void* donor;          /* NULL allowed with donor_objects = 0 */
+  uint32_t donor_objects;
+} dh_energy_donor_item;
+int dh_energy_fwd_bwd_planned_donor_batch(const dh_energy_donor_item* items, int n_items, int dtype, int C, int grid,
+                                          int grad_dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * SD-2-depth U-Net engine (model/unet_2d_condition.py:809-1198 and the block files it

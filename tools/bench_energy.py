@@ -13,7 +13,12 @@ DH_MIXED=1: instead, a batch of K = 8 items of which 4 carry a weighted plan and
 edit of the two-sphere scene, interleaved), C = 320, 640 and 1280, three ways: the one launch pair of
 dh_energy_fwd_bwd_planned_mixed_batch, the item-by-item route (8 single calls) and the all-unweighted batch of 8
 (dh_energy_fwd_bwd_planned_batch) -- same timing scheme; one JSON line, also written to
-profiles/mixed_objects/bench_energy_res<res>.json (DH_OUT: another directory)."""
+profiles/mixed_objects/bench_energy_res<res>.json (DH_OUT: another directory).
+
+DH_DONOR=1: instead, the weighted evaluation of DH_OBJECT_WEIGHTS=equal (what the parent commit runs too) next to the donor
+evaluation on the same plan with object 1 read from a second map (dh_energy_fwd_bwd_planned_donor: object insertion) -- same
+scene, sizes and timing scheme; one JSON line, also written to profiles/object_insertion/bench_energy_res<res>.json (DH_OUT:
+another directory)."""
 import json
 import os
 import sys
@@ -82,6 +87,51 @@ def object_weights_bench(ow):
     print(line)
 
 
+def donor_bench():
+    from diffusionhandles_amd.depth_transform import reproject_object_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    depth, bg_depth, masks = R.two_spheres(res)
+    depth, bg_depth, masks = depth.to(dev), bg_depth.to(dev), [m.to(dev) for m in masks]
+    tfs = [(tf[0], torch.tensor(tf[1]), torch.tensor(tf[2])) for tf in R.OCCLUDING]
+    (_, corr), = reproject_object_edits(depth, bg_depth, masks, GuidedStableDiffuser.get_depth_intrinsics(dev), [tfs])
+    pc = LS.process_correspondences(corr, res, 0, grid=grid, device=dev, object_labels=LS.object_label_image(masks))
+    plan = LS.EnergyPlan(pc, grid, dev, object_weights="equal")
+    assert plan.weighted
+    info = dict(res=res, grid=grid, correspondences=int(corr.shape[0]), pairs_per_object=[int(c) for c in plan.counts],
+                donor_objects=2, layers=[])
+    n = int(os.environ.get("DH_CALLS", "200"))
+    gen = torch.Generator().manual_seed(1)
+    for C in (640, 1280):
+        cur, org, dnr = (torch.randn(grid, grid, C, generator=gen).half().to(dev) for _ in range(3))
+        out = torch.empty_like(cur)
+        runs = {"weighted": lambda: LS.energy_and_grad_planned(cur, org, plan, 3.0, 2.0, grad_scale=256.0, out=out),
+                "donor": lambda: LS.energy_and_grad_planned_donor(cur, org, plan, 3.0, 2.0, dnr, 2, grad_scale=256.0, out=out)}
+        for run in runs.values():
+            for _ in range(20):
+                run()
+        torch.cuda.synchronize()
+        best = {k: [] for k in runs}
+        for _ in range(5):                                   # alternating blocks of n calls
+            for name, run in runs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
+                best[name].append(e0.elapsed_time(e1) * 1e3 / n)
+        med = {k: sorted(v)[len(v) // 2] for k, v in best.items()}
+        info["layers"].append(dict(C=C, us_per_evaluation_median=med, us_per_evaluation_blocks=best,
+                                   donor_over_weighted=med["donor"] / med["weighted"]))
+    line = json.dumps(info)
+    out_dir = os.environ.get("DH_OUT") or os.path.join(ROOT, "profiles", "object_insertion")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, f"bench_energy_res{res}.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def mixed_bench():
     from diffusionhandles_amd.depth_transform import reproject_object_edits
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -143,6 +193,9 @@ def mixed_bench():
     print(line)
 
 
+if os.environ.get("DH_DONOR"):
+    donor_bench()
+    sys.exit(0)
 if os.environ.get("DH_MIXED"):
     mixed_bench()
     sys.exit(0)

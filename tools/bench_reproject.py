@@ -11,7 +11,10 @@ DH_COPIES=c (default unset; M * c <= 8): a further line times the call with c in
 of an object takes another of the bench transforms and is lifted by 0.4 k, so the copies do not coincide).
 DH_REMOVE=1 (default unset; the two-sphere scene whatever DH_OBJECTS says): two further lines time the K = 8 call with sphere 1
 removed and sphere 0 moved (reproject_removal_edits), and the pure removal of both spheres (the background alone, computed
-once for the K edits)."""
+once for the K edits).
+DH_DONOR=1 (default unset; the two-sphere scene whatever DH_OBJECTS says): two further lines time the K = 8 instance call on the
+two spheres (reproject_instance_edits, instances [0, 1]: what the parent commit runs too) and the same call with one donor
+sphere of tests/object_insertion_ref.py beside them (reproject_donor_edits: object insertion; profiles/object_insertion/)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -117,6 +120,27 @@ if os.environ.get("DH_REMOVE", "0") not in ("", "0"):
     M = 0
     report(lambda **kw: reproject_removal_edits(r_depth, r_bg, [], intr, [[]] * K, removed_masks=r_masks, **kw),
            " two spheres, pure removal")
+    M = M_shown
+if os.environ.get("DH_DONOR", "0") not in ("", "0"):
+    from diffusionhandles_amd.depth_transform import reproject_donor_edits, reproject_instance_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    import object_insertion_ref as I
+    d_depth, d_bg, d_masks = R.two_spheres(res)
+    d_depth, d_bg, d_masks = d_depth.to(dev), d_bg.to(dev), [m.to(dev) for m in d_masks]
+    donor_depth, donor_masks = I.donor_scene(res, "disjoint")
+    donor_depth, donor_masks = donor_depth.to(dev), [m.to(dev) for m in donor_masks]
+    M_shown, M = M, 2
+    two = [[tfs[i], tfs[(i + 3) % 8]] for i in range(K)]
+    report(lambda **kw: reproject_instance_edits(d_depth, d_bg, d_masks, intr, two, [0, 1], **kw), " two spheres, instances [0, 1]")
+    M = 3
+    three = [e + [tfs[(i + 5) % 8] + (0.8, None)] for i, e in enumerate(two)]
+
+    def donor_call(**kw):          # (a donor call returns the instance array beside every result: report() reads pairs)
+        out = reproject_donor_edits(d_depth, d_bg, d_masks, intr, three, [0, 1, 2], donor_depth=donor_depth,
+                                    donor_masks=donor_masks, **kw)
+        return ([r[:2] for r in out[0]], out[1]) if kw.get("return_debug") else [r[:2] for r in out]
+    report(donor_call, " two spheres and one donor sphere")
     M = M_shown
 if scale is not None:
     if M == 1:

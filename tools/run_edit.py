@@ -120,7 +120,8 @@ def parse(argv=None):
     ap.add_argument("--config", default=None, help="configuration YAML (the reference's --config_path, test/config/*.yaml)")
     ap.add_argument("--max-scenes", type=int, default=0, help="--test-set: only the first N scenes")
     ap.add_argument("--identity-batch", type=int, default=1,
-                    help="--test-set: the scenes that need an identity (not skipped, no cache file) are inverted and initially "
+                    help="--scene with a donor/ directory: 2 takes the host's and the donor's identity in one pass.  "
+                         "--test-set: the scenes that need an identity (not skipped, no cache file) are inverted and initially "
                          "inferred K at a time (DiffusionHandles.invert_input_images / generate_input_images; the engine is "
                          "built with max_batch >= 2K); 1 = one scene at a time")
     ap.add_argument("--edit-batch", type=int, default=1,
@@ -146,8 +147,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.edit_batch < 1 or (args.edit_batch > 1 and args.test_set is None):
         ap.error("--edit-batch K needs K >= 1, and K > 1 needs --test-set")
-    if args.identity_batch < 1 or (args.identity_batch > 1 and args.test_set is None):
-        ap.error("--identity-batch K needs K >= 1, and K > 1 needs --test-set")
+    if args.identity_batch < 1 or (args.identity_batch > 1 and args.test_set is None and args.scene is None):
+        ap.error("--identity-batch K needs K >= 1, and K > 1 needs --test-set (or a --scene with a donor)")
     return args
 
 
@@ -286,6 +287,18 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
         sc = load_scene(scene, args.res)
         img, depth, bg_depth, mask, prompt, res = sc["img"], sc["depth"], sc["bg_depth"], sc["fg_mask"], sc["prompt"], args.res
         masks = sc.get("fg_masks")
+        # object insertion: refused before any identity is computed where the re-projection has none
+        for n, t in sc["transforms"].items():
+            if isinstance(t, dict) and any(isinstance(o, dict) and "donor" in o for o in t.get("objects") or []):
+                if args.mode != "pc":
+                    raise NotImplementedError(f"{scene}: transform {n!r} inserts a donor object (\"donor\"); --mode {args.mode} has "
+                                              "no object insertion, use --mode pc")
+                if getattr(args, "footprint_report", {}).get("footprints"):
+                    raise NotImplementedError(f"{scene}: transform {n!r} inserts a donor object (\"donor\"); --footprints "
+                                              "(depth_transform_footprints) has no object insertion")
+                if getattr(args, "edit_batch", 1) > 1:
+                    raise NotImplementedError(f"{scene}: transform {n!r} inserts a donor object (\"donor\"); --edit-batch "
+                                              "(mixed-image batches) has no object insertion")
         if args.mode != "pc":           # object removal: before the identity is computed
             for n, t in sc["transforms"].items():
                 objs = t.get("objects") if isinstance(t, dict) else None
@@ -328,8 +341,9 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
                 raise NotImplementedError(f"{scene}: transform {tf['name']!r} has a scale ({tf['scale']!r}); --mode mesh has no "
                                           "scale, use --mode pc")
     exists = {tf["name"]: os.path.exists(os.path.join(out, tf["name"] + ".png")) for tf in transforms}
+    donor = sc.get("donor") if scene and any(tf.get("donor") for tf in transforms) else None
     return dict(img=img, depth=depth, bg_depth=bg_depth, mask=mask, masks=masks, prompt=prompt, res=res, transforms=transforms,
-                exists=exists, release=release)
+                exists=exists, release=release, donor=donor)
 
 
 def scene_identity(args, dh, p, out, identity=None):
@@ -386,6 +400,43 @@ def scene_identity(args, dh, p, out, identity=None):
     if args.identity_batch > 1:
         report["identity_batch"] = args.identity_batch
     return depth, bg_depth, mask, img, null_text, noise, acts, report
+
+
+def donor_identity(args, dh, p, out, host=None):
+    """The identity of the scene's donor image (object insertion): its activations, from the cache donor_identity.npz beside the
+    host's, or by inversion + initial inference -- with `host` = (img, depth, prompt) and --identity-batch >= 2 in ONE batched
+    pass with the host's, whose identity tuple is then returned too.  Returns (donor dict for transform_foreground_objects,
+    host identity or None)."""
+    dev = torch.device("cuda:0")
+    d = p["donor"]
+    img, depth, prompt = d["img"].to(dev), d["depth"].to(dev), d["prompt"]
+    host_cache = args.identity_cache or os.path.join(out, "identity.npz")
+    cache = None if args.no_identity_cache else os.path.join(os.path.dirname(os.path.abspath(host_cache)), "donor_identity.npz")
+    host_identity = None
+    if cache is not None and os.path.exists(cache):
+        with np.load(cache) as z:
+            acts = [torch.from_numpy(z[f"activations{i + 1}"]).to(dev) for i in range(3)]
+    else:
+        t0 = time.time()
+        if host is not None and args.identity_batch >= 2:
+            imgs, depths, prompts = [host[0], img], [host[1], depth], [host[2], prompt]
+            null_texts, noises = [None, None], [None, None]
+            if not args.skip_inversion:
+                null_texts, noises = map(list, zip(*dh.invert_input_images(imgs, depths, prompts)))
+            both = dh.generate_input_images(depths, prompts, null_texts, noises)
+            torch.cuda.synchronize()
+            host_identity = both[0] + ((time.time() - t0) / 2,)
+            acts = both[1][2]
+        else:
+            null_text, noise = (None, None)
+            if not args.skip_inversion:
+                null_text, noise = dh.invert_input_image(img, depth, prompt)
+            acts = dh.generate_input_image(depth, prompt, null_text, noise)[2]
+        if cache is not None:
+            os.makedirs(os.path.dirname(cache), exist_ok=True)
+            np.savez(cache, activations1=acts[0].float().cpu().numpy(), activations2=acts[1].float().cpu().numpy(),
+                     activations3=acts[2].float().cpu().numpy())
+    return dict(depth=depth, masks=[m.to(dev) for m in d["masks"]], activations=acts), host_identity
 
 
 def write_scene_pages(args, out, img, mask, depth, bg_depth, prompt, res, report):
@@ -516,6 +567,11 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
     if args.skip_existing and transforms and all(exists.values()):
         return dict(resolution=res, mode=args.mode, skipped_scene=True, edits=[dict(name=n, skipped=True) for n in exists])
     dh = handles(res)
+    donor = None
+    if p.get("donor") is not None:          # both identities; --identity-batch 2 takes them in one pass when neither is cached
+        fresh = identity is None and (args.no_identity_cache or not cache_usable(args, args.identity_cache or os.path.join(out, "identity.npz")))
+        donor, both = donor_identity(args, dh, p, out, (img.to(dev), depth.to(dev), prompt) if fresh else None)
+        identity = both if both is not None else identity
     depth, bg_depth, mask, img, null_text, noise, acts, report = scene_identity(args, dh, p, out, identity)
     for tf in transforms:
         if args.skip_existing and exists[tf["name"]]:
@@ -527,7 +583,8 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
             sp = split_removed(p["masks_dev"], tf.get("remove"))
             res_ = dh.transform_foreground_objects(depth, prompt, sp["fg_masks"], bg_depth, null_text, noise, acts,
                                                    transforms=tf["transforms"], object_weights=tf["object_weights"],
-                                                   removed_masks=sp.get("removed_masks"), instances=tf.get("instances"), **rel)
+                                                   removed_masks=sp.get("removed_masks"), instances=tf.get("instances"),
+                                                   **(dict(donor=donor) if tf.get("donor") else {}), **rel)
         elif tf.get("remove"):          # a single-mask scene's {"remove": true}: a pure removal
             rel = {} if p.get("release") is None else dict(release_mask=p["release"])
             res_ = dh.transform_foreground_objects(depth, prompt, [], bg_depth, null_text, noise, acts, transforms=[],

@@ -5,25 +5,30 @@ mask's pixel count.
 Reference, built here and never taken from the library: the same linear system on the CPU in float64 (diagonal 4, -1
 towards every masked 4-neighbour inside the image, right-hand side = known neighbours - laplacian(bg), the Laplacian an
 f64 sum rounded to f32 as k_laplacian defines it), solved by a sparse direct solve (x_ref) and by a plain classic CG with
-the kernels' stop rule (its_ref).
+the kernels' stop rule (its_ref).  The system, the classic CG and the solver-class rule live in tests/infill_ref.py, which the
+re-projection's in-fill tests (tests/test_infill_reproject_gpu.py) share.
 
 What an accuracy bound alone cannot see: a recurrence that has lost its orthogonality still reaches the fixed point, only
 in several times the iterations (each one a grid-wide seam in the sixteen-workgroup kernel), or leaves at the cap with
 an ordinary count.  So every case also gates the ITERATION COUNT against classic CG: <= 1.05 * its_ref + 5 (a healthy
 pipelined recurrence stays within 2 % of classic in an f64 model, every degraded one is >= 9 % above it)."""
-import ctypes
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from diffusionhandles_amd.synthetic import make_scene
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import infill_ref as I  # noqa: E402
+from infill_ref import limits as _limits, solver_of as _solver_of  # noqa: E402
+
+from diffusionhandles_amd.synthetic import make_scene  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 RES = 512
-TOL2 = 1e-24           # the kernels' stop rule: iterate while (r, r) > TOL2 * (b, b)
 
 
 def _dev():
@@ -83,82 +88,15 @@ def _fields():
     return depth[0, 0].numpy().copy(), bg
 
 
-def _system(depth, bg, mask):
-    """A (csr, f64), b (f64) and the unknowns' pixel coordinates, row-major like the library's compaction."""
-    import scipy.sparse
-    h, w = mask.shape
-    bgd = bg.astype(np.float64)
-    pad = np.pad(bgd, 1)
-    lap = (pad[:-2, 1:-1] + pad[2:, 1:-1] + pad[1:-1, :-2] + pad[1:-1, 2:] - 4.0 * bgd).astype(np.float32).astype(np.float64)
-    ys, xs = np.nonzero(mask)
-    n = ys.size
-    idx = -np.ones((h, w), dtype=np.int64)
-    idx[ys, xs] = np.arange(n)
-    rows, cols = [np.arange(n)], [np.arange(n)]
-    vals = [np.full(n, 4.0)]
-    b = np.zeros(n)
-    for dy, dx in ((-1, 0), (1, 0), (0, -1), (0, 1)):
-        yy, xx = ys + dy, xs + dx
-        inside = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
-        yc, xc = np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)
-        unk = inside & mask[yc, xc]
-        known = inside & ~mask[yc, xc]
-        rows.append(np.nonzero(unk)[0])
-        cols.append(idx[yc[unk], xc[unk]])
-        vals.append(np.full(int(unk.sum()), -1.0))
-        b[known] += depth[yc[known], xc[known]].astype(np.float64)
-    b -= lap[ys, xs]
-    A = scipy.sparse.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
-    return A, b, ys, xs
-
-
-def _classic_cg_iterations(A, b, cap=50000):
-    """textbook CG in numpy f64 from x = 0; the number of iterations taken while (r, r) > TOL2 * (b, b)"""
-    x = np.zeros_like(b)
-    r = b.copy()
-    p = b.copy()
-    rs = float(r @ r)
-    bnorm = rs
-    it = 0
-    while it < cap and rs > TOL2 * bnorm:
-        q = A @ p
-        alpha = rs / float(p @ q)
-        x += alpha * p
-        r -= alpha * q
-        rsn = float(r @ r)
-        p = r + (rsn / rs) * p
-        rs = rsn
-        it += 1
-    return it
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(name):
     """(mask, x_ref as a full f64 image, its_ref) of a case, computed once and shared"""
-    import scipy.sparse.linalg
     depth, bg = _fields()
     mask = CASES[name][0]()
-    A, b, ys, xs = _system(depth, bg, mask)
-    x = scipy.sparse.linalg.spsolve(A.tocsc(), b)
-    assert float(np.abs(A @ x - b).max()) <= 1e-11 * float(np.abs(b).max())      # the direct solve itself
-    ref = depth.astype(np.float64)
-    ref[ys, xs] = x
+    ref, its_ref = I.solve(depth, mask, I.laplacian_f32(bg))
     ref.setflags(write=False)
     mask.setflags(write=False)
-    return mask, ref, _classic_cg_iterations(A, b)
-
-
-def _limits():
-    """(largest n solved on chip, largest n of the sixteen-workgroup kernel, its workgroups), from the library's constants"""
-    from diffusionhandles_amd import _lib
-    v = (ctypes.c_int * 3)()
-    _lib.check(_lib.lib().dh_dbg_cg_limits(v), "dh_dbg_cg_limits")
-    return int(v[0]), int(v[1]), int(v[2])
-
-
-def _solver_of(n):
-    lds_max, multi_max, _ = _limits()
-    return "lds" if n <= lds_max else "multi" if n <= multi_max else "single"
+    return mask, ref, its_ref
 
 
 def _blend(mask):

@@ -101,6 +101,13 @@ SIGNATURES = {
     "dh_reproject_donor_edits": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_p, c_p, c_f, c_f, c_d,
                                        c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
                                        c_p, c_i, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p, c_p, c_i]),
+    "dh_reproject_camera_workspace_bytes": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
+    "dh_reproject_camera_edits": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_p, c_p, c_f, c_f, c_d,
+                                        c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                        c_p, c_i, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p, c_p, c_i,
+                                        ctypes.POINTER(c_d), ctypes.POINTER(ctypes.c_uint8), c_p, c_p, c_p]),
+    "dh_reproject_camera_background": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_sz, c_p,
+                                             ctypes.POINTER(c_d), c_p, c_p, c_p]),
     "dh_reproject_background_workspace_bytes": (c_i, [c_i, ctypes.POINTER(c_sz)]),
     "dh_reproject_background": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "dh_unproject": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_p, c_p]),
@@ -111,6 +118,7 @@ SIGNATURES = {
     "dh_cells_from_correspondences": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "dh_cells_from_correspondences_vacated": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
     "dh_cells_from_correspondences_donor": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p, c_p]),
+    "dh_cells_from_correspondences_rows": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p, c_p]),
     "dh_energy_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
     "dh_energy_fwd_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i,
                                 c_f, c_f, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_p, c_sz, c_p]),

@@ -19,9 +19,11 @@ __global__ void k_init_masks(uint8_t* m, int n) {
 }
 
 // row_donor (dh_cells_from_correspondences_donor): NULL, or one byte per correspondence row; a flagged row's source cell lies in
-// another image, so it forms its pair and clears its target cell but leaves the original-background mask alone
+// another image, so it forms its pair and clears its target cell but leaves the original-background mask alone.
+// three_kinds (dh_cells_from_correspondences_rows): the byte is the row's KIND -- 0 a host row, 1 a donor row, 2 a background
+// row of a camera move, which forms its pair and clears NEITHER mask (the background stays background on both sides).
 __global__ void k_pairs(const long long* corr, const int* idx, const int* count, int img_res, int grid, int* pairs,
-                        uint8_t* bg_o, uint8_t* bg_t, const uint8_t* row_donor) {
+                        uint8_t* bg_o, uint8_t* bg_t, const uint8_t* row_donor, int three_kinds) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= *count) return;
   const int row = idx[r];
@@ -31,8 +33,9 @@ __global__ void k_pairs(const long long* corr, const int* idx, const int* count,
   int tc = (int)(c[3] / cs) * grid + (int)(c[2] / cs);
   pairs[2 * (size_t)r + 0] = oc;
   pairs[2 * (size_t)r + 1] = tc;
-  if (!row_donor || !row_donor[row]) bg_o[oc] = 0;
-  bg_t[tc] = 0;
+  const int kind = row_donor ? row_donor[row] : 0;
+  if (kind == 0) bg_o[oc] = 0;
+  if (!(three_kinds && kind == 2)) bg_t[tc] = 0;
 }
 
 // object removal (dh_cells_from_correspondences_vacated): a cell that holds a vacated pixel leaves the original-background mask,
@@ -160,10 +163,12 @@ extern "C" int dh_cells_workspace_bytes(int n, int grid, size_t* bytes) {
 // row_donor: NULL, or [n] u8 on the device, one byte per correspondence row (non-zero = the row's source pixel lies in a donor
 // image): such a row keeps its pair and clears its target cell, and does not clear a cell of the original-background mask.
 // NULL or all zero gives the bytes of the _vacated entry, with the same launches.
-extern "C" int dh_cells_from_correspondences_donor(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
-                                                   int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
-                                                   void* workspace, size_t workspace_bytes, void* stream,
-                                                   const uint8_t* vacated, const uint8_t* row_donor) {
+// row_kind (dh_cells_from_correspondences_rows): NULL, or [n] u8 on the device: 0 = a host row, 1 = a donor row, 2 = a background
+// row (camera moves): it forms its pair and clears neither mask.  The _donor entry is this code with the byte read as a flag
+// (any non-zero value = a donor row), so kinds 0 and 1 give its bytes with its launches.
+static int cells_rows(const int64_t* corr, int n, int img_res, int grid, int bg_erosion, int32_t* pairs, int32_t* bg_lists,
+                      uint8_t* bg_masks, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
+                      const uint8_t* vacated, const uint8_t* row_donor, int three_kinds) {
   DH_REQUIRE(pairs && bg_lists && bg_masks && counts && workspace, "null pointer");
   DH_REQUIRE(n >= 0 && grid >= 1 && img_res >= grid && img_res % grid == 0, "bad sizes");
   DH_REQUIRE(n == 0 || corr, "null corr");
@@ -185,7 +190,7 @@ extern "C" int dh_cells_from_correspondences_donor(const int64_t* corr, int n, i
     hipLaunchKernelGGL(k_valid, dim3(cdiv(n, 256)), dim3(256), 0, st, (const long long*)corr, n, img_res, valid);
     compact(valid, n, 1, 0, idx, 0, counts, 1, bc, st);
     hipLaunchKernelGGL(k_pairs, dim3(cdiv(n, 256)), dim3(256), 0, st, (const long long*)corr, idx, counts, img_res,
-                       grid, pairs, two, two + G2, row_donor);
+                       grid, pairs, two, two + G2, row_donor, three_kinds);
   }
   if (vacated)
     hipLaunchKernelGGL(k_vacated_cells, dim3(cdiv(img_res * img_res, 256)), dim3(256), 0, st, vacated, img_res, grid, two);
@@ -195,6 +200,22 @@ extern "C" int dh_cells_from_correspondences_donor(const int64_t* corr, int n, i
   compact(bg_masks, G2, 3, G2, bg_lists, G2, counts + 1, 1, bc, st);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+extern "C" int dh_cells_from_correspondences_rows(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                                  int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                                  void* workspace, size_t workspace_bytes, void* stream,
+                                                  const uint8_t* vacated, const uint8_t* row_kind) {
+  return cells_rows(corr, n, img_res, grid, bg_erosion, pairs, bg_lists, bg_masks, counts, workspace, workspace_bytes, stream,
+                    vacated, row_kind, 1);
+}
+
+extern "C" int dh_cells_from_correspondences_donor(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                                   int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                                   void* workspace, size_t workspace_bytes, void* stream,
+                                                   const uint8_t* vacated, const uint8_t* row_donor) {
+  return cells_rows(corr, n, img_res, grid, bg_erosion, pairs, bg_lists, bg_masks, counts, workspace, workspace_bytes, stream,
+                    vacated, row_donor, 0);
 }
 
 extern "C" int dh_cells_from_correspondences_vacated(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,

@@ -176,6 +176,30 @@ struct Xf {
 };
 static_assert(sizeof(Xf) == DH_SIMILARITY_ROW * sizeof(double), "Xf is the similarity row");
 
+// The arithmetic of one transform row, the ONE statement of it (instances and views): q = fl32(P - c) scaled per camera axis by
+// one rounded f32 multiply, f32 cross products and dot, the f64 combination, then (r + (double)c) + t.
+__device__ __forceinline__ void xf_apply(const Xf& t, float x, float y, float z, float c0, float c1, float c2, double& X, double& Y,
+                                         double& Z) {
+  const float q0 = (x - c0) * (float)t.sx, q1 = (y - c1) * (float)t.sy, q2 = (z - c2) * (float)t.sz;
+  const float a0 = (float)t.ax, a1 = (float)t.ay, a2 = (float)t.az;
+  const float cr0 = a1 * q2 - a2 * q1;
+  const float cr1 = a2 * q0 - a0 * q2;
+  const float cr2 = a0 * q1 - a1 * q0;
+  const float dt = (q0 * a0 + q1 * a1) + q2 * a2;
+  const double omc = 1.0 - t.c;
+  const double r0 = ((double)q0 * t.c + (double)cr0 * t.s) + (double)(a0 * dt) * omc;
+  const double r1 = ((double)q1 * t.c + (double)cr1 * t.s) + (double)(a1 * dt) * omc;
+  const double r2 = ((double)q2 * t.c + (double)cr2 * t.s) + (double)(a2 * dt) * omc;
+  X = (r0 + (double)c0) + t.tx;
+  Y = (r1 + (double)c1) + t.ty;
+  Z = (r2 + (double)c2) + t.tz;
+}
+
+// Camera moves (dh_reproject_camera_edits; DESIGN.md, "Camera moves"): views = NULL, or one row per edit on the device, the
+// INVERSE motion of the edit's camera as a similarity row (scale 1, the pivot always selected); its last double is the edit's
+// flag (0 = the edit has no view).  The flag is uniform over a workgroup (blockIdx.y is the edit).
+__device__ __forceinline__ bool has_view(const Xf* views, int e) { return views != nullptr && views[e].reserved != 0.0; }
+
 // one thread per (edit, point): points [0,R2) are background pixels, [R2,R2+n_pts) foreground, instance after instance
 // (InstTable; without copies an instance is an object).  xf: n_inst rows per edit (edit-major), cen: 4 floats per MASK -- a
 // copy does not recompute its mask's centroid.  The instance turns about its row's pivot when the row has
@@ -184,12 +208,16 @@ static_assert(sizeof(Xf) == DH_SIMILARITY_ROW * sizeof(double), "Xf is the simil
 // FP (footprint splatting, further down): the foreground points also leave (u, v, Z) -- u, v before the clamp and the
 // rounding -- in uvz, 3 doubles per point-list position and edit, for the triangles between them.
 // donor_depth, n_host: a point of mask o >= n_host reads the donor's depth (a pointer select beside the inst_of chain).
+// views (never with FP): in an edit with a view EVERY point of the list then goes through the view row with the same
+// arithmetic, its input the f32 background point or the instance's (X, Y, Z) rounded to f32; such an edit has no clamp: a
+// point whose rint(u) or rint(v) (half to even, before any clamp) leaves 0 .. res - 1, or whose Z is not > 0, bids for no
+// pixel and leaves pix = -1.  An edit without a view skips all of it behind the uniform flag.
 template <bool FP>
 __global__ void k_points(const float* depth, const float* donor_depth, int n_host, const float* bg_depth, const int* fg_pix,
                          int n_pts, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
                          const Xf* xf, const float* cen, const InstTable tab, int n_inst, unsigned long long* zbuf,
-                         int* pix_out, unsigned long long* key_out, double* uvz) {
+                         int* pix_out, unsigned long long* key_out, double* uvz, const Xf* views) {
   const int R2 = res * res, P = R2 + n_pts;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
@@ -210,19 +238,15 @@ __global__ void k_points(const float* depth, const float* donor_depth, int n_hos
     const bool piv = t.has_pivot != 0.0;
     const float g0 = cen[4 * o], g1 = cen[4 * o + 1], g2 = cen[4 * o + 2];
     const float c0 = piv ? (float)t.px : g0, c1 = piv ? (float)t.py : g1, c2 = piv ? (float)t.pz : g2;
-    const float q0 = (x - c0) * (float)t.sx, q1 = (y - c1) * (float)t.sy, q2 = (z - c2) * (float)t.sz;
-    const float a0 = (float)t.ax, a1 = (float)t.ay, a2 = (float)t.az;
-    const float cr0 = a1 * q2 - a2 * q1;
-    const float cr1 = a2 * q0 - a0 * q2;
-    const float cr2 = a0 * q1 - a1 * q0;
-    const float dt = (q0 * a0 + q1 * a1) + q2 * a2;
-    const double omc = 1.0 - t.c;
-    const double r0 = ((double)q0 * t.c + (double)cr0 * t.s) + (double)(a0 * dt) * omc;
-    const double r1 = ((double)q1 * t.c + (double)cr1 * t.s) + (double)(a1 * dt) * omc;
-    const double r2 = ((double)q2 * t.c + (double)cr2 * t.s) + (double)(a2 * dt) * omc;
-    X = (r0 + (double)c0) + t.tx;
-    Y = (r1 + (double)c1) + t.ty;
-    Z = (r2 + (double)c2) + t.tz;
+    xf_apply(t, x, y, z, c0, c1, c2, X, Y, Z);
+  }
+  bool view = false;
+  if (!FP) {
+    view = has_view(views, e);
+    if (view) {
+      const Xf v = views[e];
+      xf_apply(v, (float)X, (float)Y, (float)Z, (float)v.px, (float)v.py, (float)v.pz, X, Y, Z);
+    }
   }
   const double m = (double)(res - 1);
   double u = (fx * (-X)) / Z;
@@ -233,22 +257,33 @@ __global__ void k_points(const float* depth, const float* donor_depth, int n_hos
     double* o = uvz + ((size_t)e * n_pts + (i - R2)) * 3;
     o[0] = u; o[1] = v; o[2] = Z;
   }
+  const unsigned long long key = sortable_f64(Z);
+  if (view) {
+    // out of frame: no bid, no row (a NaN fails every comparison).  Inside the frame the clamp below changes nothing.
+    const double ru = rint(u), rv = rint(v);
+    if (!(ru >= 0.0 && ru <= m && rv >= 0.0 && rv <= m && Z > 0.0)) {
+      pix_out[(size_t)e * P + i] = -1;
+      key_out[(size_t)e * P + i] = key;
+      return;
+    }
+  }
   u = fmin(fmax(u, 0.0), m);
   v = fmin(fmax(v, 0.0), m);
   const int ui = (int)rint(u), vi = (int)rint(v);
   const int pix = vi * res + ui;
-  const unsigned long long key = sortable_f64(Z);
   pix_out[(size_t)e * P + i] = pix;
   key_out[(size_t)e * P + i] = key;
   atomicMin(&zbuf[(size_t)e * R2 + pix], key);
 }
 
+// (pix < 0: a point a view put out of frame -- it bid for nothing and owns nothing)
 __global__ void k_resolve(int P, int R2, const unsigned long long* zbuf, const int* pix_arr,
                           const unsigned long long* key_arr, int* owner) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
   if (i >= P) return;
   int pix = pix_arr[(size_t)e * P + i];
+  if (pix < 0) return;
   if (key_arr[(size_t)e * P + i] == zbuf[(size_t)e * R2 + pix]) atomicMin(&owner[(size_t)e * R2 + pix], i);
 }
 
@@ -439,12 +474,14 @@ __device__ __forceinline__ float unsort_f32(unsigned int k) {
   return __uint_as_float(b);
 }
 
-// per pixel: depth map, raw fg mask, raw disparity 1/z and its min/max keys
+// per pixel: depth map, raw fg mask, raw disparity 1/z and its min/max keys.  In an edit with a view a pixel no point reached
+// stays out of the min / max (its 1 / inf = 0 would become the minimum); it joins the in-fill set in k_normalize.
 constexpr int PIX_PER_THREAD = 16;
 __global__ void k_pixels(int R2, const unsigned long long* zbuf, const int* owner, float* zmap, uint8_t* raw_mask,
-                         float* disp, unsigned int* minmax) {
+                         float* disp, unsigned int* minmax, const Xf* views) {
   __shared__ unsigned int smin[4], smax[4];
   int e = blockIdx.y;
+  const bool view = has_view(views, e);
   unsigned int kmin = 0xffffffffu, kmax = 0u;
   // PIX_PER_THREAD pixels per thread: 16x fewer workgroups contend on the two min / max words of the edit
 #pragma unroll 4
@@ -460,8 +497,9 @@ __global__ void k_pixels(int R2, const unsigned long long* zbuf, const int* owne
     float d = (float)(1.0 / (double)z);
     disp[o] = d;
     const unsigned int kd = sortable_f32(d);
-    kmin = kd < kmin ? kd : kmin;
-    kmax = kd > kmax ? kd : kmax;
+    const bool counted = !(view && k == ~0ull);
+    kmin = counted && kd < kmin ? kd : kmin;
+    kmax = counted && kd > kmax ? kd : kmax;
   }
 #pragma unroll
   for (int s = 32; s > 0; s >>= 1) {
@@ -490,9 +528,10 @@ __global__ void k_fg_vis(int n_pts, int R2, int P, int res, const int* pix_arr, 
   if (j >= n_pts) return;
   int i = R2 + j;
   int pix = pix_arr[(size_t)e * P + i];
-  vis[(size_t)e * n_pts + j] = owner[(size_t)e * R2 + pix] == i ? 1 : 0;
-  target_xy[((size_t)e * n_pts + j) * 2 + 0] = pix % res;
-  target_xy[((size_t)e * n_pts + j) * 2 + 1] = pix / res;
+  const bool gone = pix < 0;          // out of frame under a view: not visible, target (-1, -1)
+  vis[(size_t)e * n_pts + j] = !gone && owner[(size_t)e * R2 + pix] == i ? 1 : 0;
+  target_xy[((size_t)e * n_pts + j) * 2 + 0] = gone ? -1 : pix % res;
+  target_xy[((size_t)e * n_pts + j) * 2 + 1] = gone ? -1 : pix / res;
 }
 
 // binary morphology with an explicit offset list; pixels outside the image are ignored.
@@ -574,7 +613,7 @@ __global__ void k_keep_flags(int n_pts, int R2, int P, const int* pix_arr, const
   int e = blockIdx.y;
   if (j >= n_pts) return;
   int pix = pix_arr[(size_t)e * P + R2 + j];
-  keep[(size_t)e * n_pts + j] = (vis[(size_t)e * n_pts + j] && clean[(size_t)e * R2 + pix]) ? 1 : 0;
+  keep[(size_t)e * n_pts + j] = (pix >= 0 && vis[(size_t)e * n_pts + j] && clean[(size_t)e * R2 + pix]) ? 1 : 0;
 }
 
 // row r of edit e: the r-th kept point-list position, its source pixel through the table, its instance beside it
@@ -618,20 +657,52 @@ __global__ void k_unowned(int R2, const unsigned long long* zbuf, uint8_t* flag)
   flag[p] = zbuf[p] == ~0ull ? 1 : 0;
 }
 
-// normalise disparity in place and flag the pixels to in-fill (cleaned xor raw)
+// Background rows of an edit with a view: background point i (its source pixel is i) yields a row when bg_valid[i] != 0 (the
+// pixel shows the background, not the in-painted depth under a mask), the point owns its target pixel, and that pixel lies
+// outside the cleaned foreground mask.  Flagged here, listed in ascending source pixel order by compact(), written below.
+// clean_stride: R2, or 0 for one zero image shared by every edit (the background entry).
+__global__ void k_bg_row_flags(int R2, int P, const int* pix_arr, const int* owner, const uint8_t* clean, size_t clean_stride,
+                               const uint8_t* bg_valid, const Xf* views, uint8_t* flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  if (i >= R2) return;
+  uint8_t f = 0;
+  if (has_view(views, e) && bg_valid[i]) {
+    const int pix = pix_arr[(size_t)e * P + i];
+    if (pix >= 0 && owner[(size_t)e * R2 + pix] == i && !clean[(size_t)e * clean_stride + pix]) f = 1;
+  }
+  flag[(size_t)e * R2 + i] = f;
+}
+
+__global__ void k_write_bg_corr(int R2, int P, int res, const int* pix_arr, const int* row_idx, const int* bg_counts,
+                                long long* bg_corr) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  if (r >= bg_counts[e]) return;
+  const int i = row_idx[(size_t)e * R2 + r];
+  const int t = pix_arr[(size_t)e * P + i];
+  long long* c = bg_corr + ((size_t)e * R2 + r) * 4;
+  c[0] = i % res;
+  c[1] = i / res;
+  c[2] = t % res;
+  c[3] = t / res;
+}
+
+// normalise disparity in place and flag the pixels to in-fill (cleaned xor raw; in an edit with a view also the pixels no point
+// reached: zbuf still holds its initial key there)
 __global__ void k_normalize(int R2, float* disp, const unsigned int* minmax, const float* bounds,
-                            const uint8_t* raw, const uint8_t* clean, uint8_t* inpaint) {
+                            const uint8_t* raw, const uint8_t* clean, uint8_t* inpaint, const unsigned long long* zbuf,
+                            const Xf* views) {
   int p = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
   if (p >= R2) return;
   size_t o = (size_t)e * R2 + p;
+  const bool unowned = has_view(views, e) && zbuf[o] == ~0ull;
   float lo = bounds ? bounds[0] : unsort_f32(minmax[2 * e]);
   float hi = bounds ? bounds[1] : unsort_f32(minmax[2 * e + 1]);
   float t = disp[o] - lo;
   t = 255.0f * t;
   float den = hi - lo;
   disp[o] = (float)((double)t / (double)den);
-  inpaint[o] = (clean[o] != 0) != (raw[o] != 0) ? 1 : 0;
+  inpaint[o] = ((clean[o] != 0) != (raw[o] != 0)) || unowned ? 1 : 0;
 }
 
 // What the in-fill solvers publish in the iteration slot instead of a count when the field is not valid (the host raises):
@@ -1190,12 +1261,15 @@ struct ReprojectWs {
   unsigned* big_list;
   int* big_count;
   size_t big_stride;
+  // camera moves only (a call in which no edit has a view takes nothing: its workspace is what it was)
+  Xf* views;
 };
 
 // n_fg: the foreground points of the point list (with copies n_pts, the sum over the instances); M: masks; N: transform rows
 // per edit (instances; 0 = M, the call without copies, whose carving -- and so every workspace query that existed before the
 // copies -- is what it was: the wave tier's list then has a slot per triangle of the grid, else 2 n_pts per edit)
-static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false, int N = 0) {
+static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false, int N = 0,
+                  bool camera = false) {
   const size_t R2 = (size_t)res * res, P = R2 + n_fg;
   w.xf = a.take<Xf>((size_t)K * (N > 0 ? N : M));
   w.cen = a.take<float>(4 * M);
@@ -1226,6 +1300,7 @@ static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, boo
     w.big_list = a.take<unsigned>((size_t)K * w.big_stride);
     w.big_count = a.take<int>(K);
   }
+  w.views = camera ? a.take<Xf>(K) : nullptr;
   return a.ok();
 }
 
@@ -1285,6 +1360,33 @@ extern "C" int dh_masked_centroid(const float* depth, const int32_t* fg_pix, int
   return DH_OK;
 }
 
+// Camera moves: the view rows of a call as the device takes them -- the caller's rows with has_view[e] in the last double
+// (a row without a view is all zero).  NULL when no edit has a view: that call is the call of the entries without the
+// arguments, launch for launch.  ok = false: a view row is malformed (checked as the transform rows are).  The buffer
+// outlives the call (the copy to the device is asynchronous), one per calling thread.
+static const double* view_rows(const double* views, const uint8_t* has_view, int K, bool* ok) {
+  thread_local std::vector<double> rows;
+  *ok = true;
+  bool any = false;
+  if (views && has_view)
+    for (int e = 0; e < K; ++e) any = any || has_view[e] != 0;
+  if (!any) return nullptr;
+  rows.assign((size_t)K * DH_SIMILARITY_ROW, 0.0);
+  for (int e = 0; e < K; ++e) {
+    if (!has_view[e]) continue;
+    const double* row = views + (size_t)e * DH_SIMILARITY_ROW;
+    double* w = rows.data() + (size_t)e * DH_SIMILARITY_ROW;
+    const double big = 3.4028234663852886e38;
+    for (int k = 0; k < 8; ++k) *ok = *ok && row[k] >= -big && row[k] <= big;          // axis, cos, sin, translation: finite
+    for (int k = 8; k < 11; ++k) *ok = *ok && (float)row[k] > 0.0f && row[k] <= big;
+    for (int k = 11; k < 14; ++k) *ok = *ok && row[k] >= -big && row[k] <= big;
+    *ok = *ok && (row[14] == 0.0 || row[14] == 1.0);
+    for (int k = 0; k < DH_SIMILARITY_ROW - 1; ++k) w[k] = row[k];
+    w[DH_SIMILARITY_ROW - 1] = 1.0;
+  }
+  return rows.data();
+}
+
 // n_objects masks: mask m owns fg_pix[obj_start[m] .. obj_start[m + 1]).  n_inst instances per edit: instance n draws the points
 // of mask inst_obj[n] with row e * n_inst + n of xforms_host (DH_SIMILARITY_ROW doubles: rotation, translation, scale, pivot);
 // the point list holds them one after the other (InstTable), n_pts foreground points in all.  Only k_centroid (masks) and
@@ -1302,7 +1404,8 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
                                uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy, int64_t* corr,
                                uint8_t* corr_inst, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
                                int footprints, float max_ratio, int corr_capacity, const float* donor_depth = nullptr,
-                               int n_host_objects = -1) {
+                               int n_host_objects = -1, const double* views = nullptr, const uint8_t* has_view = nullptr,
+                               const uint8_t* bg_valid = nullptr, int64_t* bg_corr = nullptr, int32_t* bg_counts = nullptr) {
   DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start && inst_obj, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
@@ -1344,6 +1447,14 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
       DH_REQUIRE(row[k] >= -3.4028234663852886e38 && row[k] <= 3.4028234663852886e38, "transform row: the pivot must be finite");
     DH_REQUIRE(row[14] == 0.0 || row[14] == 1.0, "transform row: the has-pivot flag must be 0 or 1");
   }
+  // camera moves: every view row before any launch; without a view in any edit the call is the call without the arguments
+  bool views_ok = true;
+  const double* view_host = view_rows(views, has_view, n_edits, &views_ok);
+  DH_REQUIRE(views_ok, "view row: malformed (finite members, scale positive, has-pivot flag 0 or 1)");
+  if (view_host) {
+    DH_REQUIRE(!footprints, "footprints with a view are not supported");
+    DH_REQUIRE(bg_valid && bg_corr && bg_counts, "a view needs bg_valid, bg_corr and bg_counts");
+  }
   hipStream_t st = (hipStream_t)stream;
   const int K = n_edits, M = n_objects, N = n_inst;
   const ObjTable tab = obj_table(M, obj_start, n_fg);
@@ -1352,8 +1463,9 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   const int R2 = res * res, P = R2 + n_pts;
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
-  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N), "workspace too small");
+  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N, view_host != nullptr), "workspace too small");
   const size_t corr_stride = (size_t)corr_capacity;
+  if (view_host) DH_CHECK_HIP(hipMemcpyAsync(w.views, view_host, (size_t)K * sizeof(Xf), hipMemcpyHostToDevice, st));
 
   int2 hc[MAX_OFFS], ho[MAX_OFFS];
   const int kc = res / 50, ko = res / 250;
@@ -1385,17 +1497,18 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
     hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
     hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth, fg_pix,
-                       n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz);
+                       n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz,
+                       (const Xf*)nullptr);
     footprint_pass(1);
   } else {
     hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth, fg_pix,
                        n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key,
-                       (double*)nullptr);
+                       (double*)nullptr, (const Xf*)w.views);
   }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
   if (footprints) footprint_pass(2);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), K), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, raw_mask,
-                     disparity, w.minmax);
+                     disparity, w.minmax, (const Xf*)w.views);
   hipLaunchKernelGGL(k_fg_vis, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, R2, P, res, w.pix, w.owner, vis,
                      target_xy);
   // CLOSE = dilate, erode ; OPEN = erode, dilate
@@ -1431,8 +1544,16 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
                        w.keep_idx, counts, 4, corr_stride, (long long*)corr, corr_inst);
   }
   hipLaunchKernelGGL(k_count_flags, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, vis, n_pts, counts, 4, 1);
+  if (w.views) {
+    // the background rows: flags and the compacted list live in the in-fill's buffers (inpaint / unk: written just below)
+    hipLaunchKernelGGL(k_bg_row_flags, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, P, w.pix, w.owner, clean_mask, (size_t)R2,
+                       bg_valid, (const Xf*)w.views, w.inpaint);
+    compact(w.inpaint, R2, K, R2, w.unk, R2, bg_counts, 1, w.block_counts, st);
+    hipLaunchKernelGGL(k_write_bg_corr, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, P, res, w.pix, w.unk, bg_counts,
+                       (long long*)bg_corr);
+  }
   hipLaunchKernelGGL(k_normalize, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, disparity, w.minmax, bounds, raw_mask,
-                     clean_mask, w.inpaint);
+                     clean_mask, w.inpaint, w.zbuf, (const Xf*)w.views);
   compact(w.inpaint, R2, K, R2, w.unk, R2, counts + 2, 4, w.block_counts, st);
 #ifdef DH_TUNING
   static const bool cg_lds = !(getenv("DH_CG_LDS") && atoi(getenv("DH_CG_LDS")) == 0);
@@ -1474,6 +1595,40 @@ extern "C" int dh_reproject_donor_workspace_bytes(int res, int n_pts, int n_edit
   return dh_reproject_instances_workspace_bytes(res, n_pts, n_edits, n_objects, n_instances, footprints, bytes);
 }
 
+// Camera moves: the donor entry with one view row per edit (views, has_view: host), the image of the pixels that show the
+// background (bg_valid) and the background rows (bg_corr [K][res * res][4], bg_counts [K]).  The one code path: without a
+// view in any edit nothing of the three is read or written and the workspace is the donor entry's.
+extern "C" int dh_reproject_camera_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
+                                                   int footprints, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
+  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
+  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
+  Arena a(nullptr, (size_t)-1);
+  ReprojectWs w;
+  carve(a, res, n_pts, n_edits, n_objects, w, footprints != 0, n_instances, true);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_reproject_camera_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                          int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                          const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                          const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                          uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                          int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                          void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
+                                          const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
+                                          int n_host_objects, const double* views, const uint8_t* has_view,
+                                          const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts) {
+  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
+  DH_REQUIRE(n_edits >= 1, "bad sizes");
+  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
+                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
+                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
+                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts);
+}
+
+// the call without a view
 extern "C" int dh_reproject_donor_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
                                          int n_objects, const int32_t* obj_start, int res, const float* grid_x,
                                          const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
@@ -1585,17 +1740,33 @@ extern "C" int dh_reproject_background_workspace_bytes(int res, size_t* bytes) {
   return DH_OK;
 }
 
-extern "C" int dh_reproject_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y, float inv_fx,
-                                       float inv_fy, double fx, double fy, const float* bounds, float* zmap, float* disparity,
-                                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+// Camera moves, the pure case: the background entry with one view row (view NULL = no view: dh_reproject_background, launch for
+// launch).  The view lives in the one transform row the carving holds and the background never reads; with it the points go
+// through k_points' view path (no clamp: points out of frame bid for nothing), the pixels no point reached stay out of the
+// min / max, and every owned background point with bg_valid != 0 yields a row (bg_corr [res * res][4], bg_counts [1]).
+extern "C" int dh_reproject_camera_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                                               float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
+                                               float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                               void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
+                                               int32_t* bg_counts) {
   DH_REQUIRE(bg_depth && grid_x && grid_y, "null input");
   DH_REQUIRE(zmap && disparity && counts && workspace, "null output");
   DH_REQUIRE(res >= 2 && res <= 32768, "bad sizes");
+  const uint8_t one = 1;
+  bool view_ok = true;
+  const double* view_host = view_rows(view, &one, 1, &view_ok);
+  DH_REQUIRE(view_ok, "view row: malformed (finite members, scale positive, has-pivot flag 0 or 1)");
+  if (view_host) DH_REQUIRE(bg_valid && bg_corr && bg_counts, "a view needs bg_valid, bg_corr and bg_counts");
   hipStream_t st = (hipStream_t)stream;
   const int R2 = res * res;
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
   DH_REQUIRE(carve(a, res, 0, 1, 1, w), "workspace too small");
+  const Xf* dview = nullptr;
+  if (view_host) {
+    DH_CHECK_HIP(hipMemcpyAsync(w.xf, view_host, sizeof(Xf), hipMemcpyHostToDevice, st));
+    dview = w.xf;
+  }
   const int32_t none[2] = {0, 0};
   int n_pts = 0;
   const InstTable itab = inst_table(0, none, none, &n_pts);
@@ -1606,13 +1777,20 @@ extern "C" int dh_reproject_background(const float* bg_depth, int res, const flo
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0xff, sizeof(unsigned int), st));
   DH_CHECK_HIP(hipMemsetAsync(w.tmp_b, 0, (size_t)R2, st));
   hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth, (const int*)nullptr, 0, res,
-                     grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr);
+                     grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr, dview);
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.zbuf, w.pix, w.key, w.owner);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), 1), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, w.tmp_a,
-                     disparity, w.minmax);
+                     disparity, w.minmax, dview);
+  if (dview) {
+    hipLaunchKernelGGL(k_bg_row_flags, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.pix, w.owner, w.tmp_b, (size_t)0, bg_valid,
+                       dview, w.inpaint);
+    compact(w.inpaint, R2, 1, R2, w.unk, R2, bg_counts, 1, w.block_counts, st);
+    hipLaunchKernelGGL(k_write_bg_corr, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, res, w.pix, w.unk, bg_counts,
+                       (long long*)bg_corr);
+  }
   hipLaunchKernelGGL(k_unowned, dim3(cdiv(R2, 256)), dim3(256), 0, st, R2, w.zbuf, w.tmp_a);
   hipLaunchKernelGGL(k_normalize, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, disparity, w.minmax, bounds, w.tmp_a, w.tmp_b,
-                     w.inpaint);
+                     w.inpaint, w.zbuf, dview);
   compact(w.inpaint, R2, 1, R2, w.unk, R2, counts + 2, 4, w.block_counts, st);
   DH_CHECK_HIP(hipMemsetAsync(w.cgsync, 0, sizeof(CgSync), st));
   hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, 1), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
@@ -1623,6 +1801,14 @@ extern "C" int dh_reproject_background(const float* bg_depth, int res, const flo
                      reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+// the call without a view
+extern "C" int dh_reproject_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y, float inv_fx,
+                                       float inv_fy, double fx, double fy, const float* bounds, float* zmap, float* disparity,
+                                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  return dh_reproject_camera_background(bg_depth, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, bounds, zmap, disparity, counts,
+                                        workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr);
 }
 
 extern "C" int dh_laplacian_blend_workspace_bytes(int res, size_t* bytes) {

@@ -171,6 +171,82 @@ def _rigid_rows(transforms, rows):
 MAX_OBJECTS = 8              # csrc/geometry.hip: the object table travels in the kernel arguments
 
 
+def check_camera(camera, what="camera"):
+    """One camera of an edit (camera moves, DESIGN.md "Camera moves"): None (no camera), or (rot_angle_deg, rot_axis[3],
+    translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], pivot) -> None, or (angle as a float, axis, translation
+    and pivot as three float32 values each, the pivot None for the camera centre).  It is the motion of the CAMERA in the
+    coordinates of `depth_to_world_coords`: turned about rot_axis through pivot (None = the origin: a pan or tilt;
+    `pivot_at_pixel` gives an orbit centre), then translated.  The one validator: ValueError naming `what` (the call and the
+    edit) for another tuple length, a member that is not finite (as float32), an axis or a translation or a pivot that is not
+    three numbers, a zero axis.  Host only: no device work."""
+    if camera is None:
+        return None
+    try:
+        n = len(camera)
+    except TypeError:
+        n = -1
+    if n not in (3, 4):
+        raise ValueError(f"{what}: camera: expected (rot_angle, rot_axis, translation[, pivot]), got "
+                         f"{n if n >= 0 else 'no'} members")
+    angle, axis, trans = camera[0], camera[1], camera[2]
+    pivot = camera[3] if n == 4 else None
+    try:
+        ang = float(angle.item() if isinstance(angle, torch.Tensor) else angle)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: camera: rot_angle must be a number, got {angle!r}") from None
+    if not np.isfinite(ang):
+        raise ValueError(f"{what}: camera: rot_angle must be finite, got {angle!r}")
+    out = []
+    for name, v in (("rot_axis", axis), ("translation", trans), ("pivot", pivot)):
+        if v is None and name == "pivot":
+            out.append(None)
+            continue
+        try:
+            with np.errstate(over="ignore"):
+                f = _f32_list(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: camera: {name} must be three numbers, got {v!r}") from None
+        if len(f) != 3:
+            raise ValueError(f"{what}: camera: {name} must be three numbers, got {len(f)}")
+        if not all(np.isfinite(x) for x in f):
+            raise ValueError(f"{what}: camera: {name} must be finite (as float32), got {f}")
+        out.append(f)
+    ax = np.asarray(out[0], dtype=np.float32)
+    with np.errstate(all="ignore"):
+        unit = ax / np.linalg.norm(ax)
+    if not float(np.linalg.norm(ax)) > 0.0 or not np.all(np.isfinite(unit)):
+        raise ValueError(f"{what}: camera: rot_axis must not be zero, got {out[0]}")
+    return ang, out[0], out[1], out[2]
+
+
+def view_row(camera):
+    """The one builder of a view row: a camera that went through `check_camera` -> the DH_SIMILARITY_ROW doubles of the INVERSE
+    motion (include/diffhandles_hip.h, dh_reproject_camera_edits): the f32-normalised axis, cos / sin of -rot_angle as
+    `_rigid_rows` computes them, scale 1, the pivot (f32) or zeros with the has-pivot flag 1, and the translation
+    t' = -(t cos + (a x t) sin + a (a . t)(1 - cos)) computed in f64 from the f32 axis and translation and rounded to f32."""
+    ang, axis, trans, pivot = camera
+    row = np.zeros((1, SIMILARITY_ROW), dtype=np.float64)
+    _rigid_rows([(-ang, axis, [0.0, 0.0, 0.0])], row)
+    row = row[0]
+    a, c, s = row[0:3].copy(), row[3], row[4]
+    t = np.asarray(trans, dtype=np.float32).astype(np.float64)
+    tp = -(t * c + np.cross(a, t) * s + a * np.dot(a, t) * (1.0 - c))
+    row[5:8] = tp.astype(np.float32).astype(np.float64)
+    row[8:11] = 1.0
+    if pivot is not None:
+        row[11:14] = np.asarray(pivot, dtype=np.float32).astype(np.float64)
+    row[14] = 1.0
+    return row
+
+
+def orbit_cameras(depth, intrinsics, x, y, angles, axis=(0.0, 1.0, 0.0)):
+    """Cameras that turn about the point of pixel (x, y) = (column, row) of `depth` by each of `angles` (degrees) about `axis`,
+    without translation: a turntable of K views for `reproject_camera_edits` / `transform_foreground_objects_batch`."""
+    pivot = [float(v) for v in pivot_at_pixel(depth, intrinsics, x, y)]
+    axis = [float(v) for v in _f32_list(axis)]
+    return [check_camera((float(a), axis, (0.0, 0.0, 0.0), pivot), f"orbit_cameras: angle {k}") for k, a in enumerate(angles)]
+
+
 def check_footprints(footprints, footprint_max_ratio, what="footprints"):
     """The footprint settings of a point-mode call -> (bool, None or the ratio as a float32 value).  ValueError for a ratio that
     is not a finite float > 1 (as float32) and for a ratio without footprints.  Host only: no device work."""
@@ -408,6 +484,16 @@ def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
 def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
                           donor_masks=None, use_input_depth_normalization=False, return_debug=False,
                           device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False):
+    """`reproject_camera_edits` without cameras: the text is there."""
+    return reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, removed_masks, donor_depth, donor_masks,
+                                  use_input_depth_normalization, return_debug, device_correspondences, footprints,
+                                  footprint_max_ratio, return_instances, None)
+
+
+def reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
+                           donor_masks=None, use_input_depth_normalization=False, return_debug=False,
+                           device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
+                           cameras=None):
     """`reproject_instance_edits` for an edit that also DELETES objects (not in the reference; DESIGN.md "Object removal"):
     everything said there holds, and --
 
@@ -438,10 +524,37 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
     NotImplementedError for footprints with a donor (the pixel -> list-position inverse of the triangles is ambiguous when two
     images share pixel indices).  No donor -- None, or donor masks that are all empty -- is the call without the keywords,
     byte for byte, with the same launches.
+
+    Camera moves (DESIGN.md "Camera moves") -- cameras: None, or a list of K entries, one camera (`check_camera`) or None per
+    edit.  In an edit with a camera every point of the list, background included, is seen from the moved viewpoint: the points
+    that leave the frame are dropped (no clamp onto the border), the pixels no point reaches are in-filled (zero beyond the image
+    border: a known limit of the strip a move uncovers there), and the background yields correspondence rows of its own -- a
+    background pixel outside the host's foreground and removed masks whose point owns a target pixel outside the cleaned mask.
+    A camera call returns the instance array (return_instances is implied): the instance rows first, in the order they always
+    had, then the background rows in ascending source pixel order with instance index N (the number of instances).  An edit
+    without a camera in the same call is what it is in a call of its own, byte for byte, and has no background rows.  The pure
+    camera move is fg_masks = [] with K empty transform lists (bg_depth: the depth, or the depth with the removed masks
+    removed): every row is a background row.  The debug dict gains row_background (K uint8 tensors beside the returned rows: 1 =
+    a background row) and n_background (K ints), bg_corr and bg_counts.  ValueError (`check_camera`) naming the call and the
+    edit, NotImplementedError for footprints with a camera, both before any launch.  cameras=None, or all None, is the call
+    without the keyword, byte for byte, with the same launches.
     """
     what = "reproject_removal_edits"
     footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
     fg_masks = list(fg_masks)
+    edits = [list(tfs) for tfs in edits]
+    cams = None
+    if cameras is not None:
+        cameras = list(cameras)
+        if len(cameras) != len(edits):
+            raise ValueError(f"reproject_camera_edits: cameras has {len(cameras)} entries for {len(edits)} edits")
+        cams = [check_camera(c, f"reproject_camera_edits: edit {e}") for e, c in enumerate(cameras)]
+        if all(c is None for c in cams):
+            cams = None
+    if cams is not None:
+        if footprints:
+            raise NotImplementedError("reproject_camera_edits: footprints with a camera are not supported (depth_transform_footprints)")
+        return_instances = True
     removed = check_removed_masks(removed_masks, fg_masks, f"{what}: removed_masks")
     M = len(fg_masks)
     donor = None
@@ -456,14 +569,16 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
         return_instances = True
     donor_list = [] if donor is None else donor[1]
     D = len(donor_list)
-    if M == 0 and removed and donor is None:
-        edits = [list(tfs) for tfs in edits]
+    if M == 0 and (removed or cams is not None) and donor is None:
         for e, tfs in enumerate(edits):
             if len(tfs) != 0:
                 raise ValueError(f"{what}: edit {e} has {len(tfs)} transforms, but there is no foreground mask (a pure removal "
                                  f"moves nothing)")
         if instances is not None and len(list(instances)) != 0:
             raise ValueError(f"{what}: instances={instances!r} given without a foreground mask (a pure removal has no instance)")
+        if cams is not None:
+            return _reproject_pure_camera(depth, bg_depth, removed, intrinsics, cams, use_input_depth_normalization, return_debug,
+                                          device_correspondences)
         return _reproject_pure_removal(depth, bg_depth, removed, intrinsics, len(edits), use_input_depth_normalization,
                                        return_debug, device_correspondences, return_instances, instances is not None)
     if not 1 <= M <= MAX_OBJECTS and donor is None:
@@ -475,7 +590,6 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
     if inst is None:
         inst = list(range(M + D))
     N = len(inst)
-    edits = [list(tfs) for tfs in edits]
     for e, tfs in enumerate(edits):
         if len(tfs) != N:
             if instances is None:
@@ -537,6 +651,10 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
     if use_input_depth_normalization:
         disp_in = 1.0 / d
         bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
+    if n_fg == 0 and cams is not None:
+        # every mask is empty (dropped with its transforms): the pure camera move
+        return _reproject_pure_camera(depth, bg_depth, removed, intrinsics, cams, use_input_depth_normalization, return_debug,
+                                      device_correspondences, N)
     if n_fg == 0 and removed and n_vacated > 0:
         # every foreground mask is empty (dropped with its transforms) and an object is deleted: the pure removal
         return _reproject_pure_removal(depth, bg_depth, removed, intrinsics, len(edits), use_input_depth_normalization,
@@ -572,7 +690,10 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
     inst_start[1:] = np.cumsum(sizes)
     n_pts = int(inst_start[-1])                # = n_fg without copies
     nbytes = ctypes.c_size_t()
-    if with_table:
+    if cams is not None:
+        _lib.check(L.dh_reproject_camera_workspace_bytes(res, n_pts, K, Mk, Nk, 0, ctypes.byref(nbytes)),
+                   "dh_reproject_camera_workspace_bytes")
+    elif with_table:
         _lib.check(L.dh_reproject_instances_workspace_bytes(res, n_pts, K, Mk, Nk, int(footprints), ctypes.byref(nbytes)),
                    "dh_reproject_instances_workspace_bytes")
     else:
@@ -598,7 +719,31 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
     row_donor = None
     if with_table:
         corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
-        if donor is not None:
+        if cams is not None:
+            # the view rows (host), the pixels that show the background (the union of the host's masks and the removed masks is
+            # in-painted in bg_depth), and the background rows' buffers
+            views = np.zeros((K, SIMILARITY_ROW), dtype=np.float64)
+            has_view = np.zeros(K, dtype=np.uint8)
+            for e, c in enumerate(cams):
+                if c is not None:
+                    views[e], has_view[e] = view_row(c), 1
+            covered = masks_u8[:M].sum(dim=0) > 0
+            if vacated is not None:
+                covered = covered | vacated.to(dev)
+            bg_valid = (~covered).to(torch.uint8).contiguous()
+            bg_corr = torch.empty((K, R2, 4), dtype=torch.int64, device=dev)
+            bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
+            dd = None if donor is None else donor[0].detach().to(dev, torch.float32).contiguous()
+            _lib.check(L.dh_reproject_camera_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                   _lib.ptr(corr_inst), _lib.ptr(dd), n_host_kept,
+                                                   views.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                   has_view.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _lib.ptr(bg_valid),
+                                                   _lib.ptr(bg_corr), _lib.ptr(bg_counts)), "dh_reproject_camera_edits")
+            if donor is not None:
+                flags = torch.zeros(256, dtype=torch.uint8)
+                flags[:Nk] = torch.tensor([1 if inst[n] >= M else 0 for n in caller], dtype=torch.uint8)
+                row_donor = flags.to(dev)[corr_inst.long()]
+        elif donor is not None:
             dd = donor[0].detach().to(dev, torch.float32).contiguous()
             _lib.check(L.dh_reproject_donor_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                                   _lib.ptr(corr_inst), _lib.ptr(dd), n_host_kept), "dh_reproject_donor_edits")
@@ -618,11 +763,20 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
     out = []
+    bg_h = bg_counts.cpu().tolist() if cams is not None else None
+    row_background = []
     for e in range(K):
         n = int(counts_h[e, 0])
-        item = (disp[e][None, None].to(out_dev), corr[e, :n] if device_correspondences else corr[e, :n].cpu())
+        rows_e, inst_e = corr[e, :n], (corr_inst[e, :n] if return_instances else None)
+        if cams is not None:
+            # the background rows behind the instance rows, instance index N
+            nb = int(bg_h[e])
+            rows_e = torch.cat([rows_e, bg_corr[e, :nb]])
+            inst_e = torch.cat([inst_e, torch.full((nb,), N, dtype=torch.uint8, device=dev)])
+            row_background.append(torch.cat([torch.zeros(n, dtype=torch.uint8, device=dev), torch.ones(nb, dtype=torch.uint8, device=dev)]))
+        item = (disp[e][None, None].to(out_dev), rows_e if device_correspondences else rows_e.cpu())
         if return_instances:
-            item += (corr_inst[e, :n] if device_correspondences else corr_inst[e, :n].cpu(),)
+            item += (inst_e if device_correspondences else inst_e.cpu(),)
         out.append(item)
     if return_debug:
         dbg = dict(zmap=zmap, raw_mask=raw, clean_mask=clean, vis=vis, target_xy=txy, counts=counts_h,
@@ -633,8 +787,83 @@ def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instance
             dbg.update(vacated=_vacated_u8(vacated, res, dev))
         if row_donor is not None:
             dbg.update(row_donor=row_donor)
+        if cams is not None:
+            dbg.update(row_background=row_background, n_background=[int(v) for v in bg_h], bg_corr=bg_corr, bg_counts=bg_counts,
+                       bg_valid=bg_valid)
         return out, dbg
     return out
+
+
+def _reproject_pure_camera(depth, bg_depth, removed, intrinsics, cams, use_input_depth_normalization, return_debug,
+                           device_correspondences, N=0):
+    """The pure camera move of `reproject_camera_edits`: dh_reproject_camera_background once per edit, with the edit's view (an
+    edit without a camera: without a view, the pure removal's result).  Every row is a background row, instance index N."""
+    what = "reproject_camera_edits"
+    if depth.dim() != 4 or depth.shape[0] != 1:
+        raise ValueError("Only batch size 1 is supported")
+    res = int(depth.shape[-1])
+    if depth.shape[-2] != res:
+        raise RuntimeError("square depth maps only")
+    for r, mask in enumerate(removed):
+        if mask.shape[-1] != res:
+            raise ValueError(f"{what}: removed_masks: removed mask {r} is {mask.shape[-1]} x {mask.shape[-2]}, the depth {res} x {res}")
+    if removed:
+        removed_overlap(removed, [], f"{what}: removed_masks")
+    out_dev = depth.device
+    dev = _compute_device(depth)
+    L = _lib.lib()
+    st = _lib.stream_ptr()
+    bg = bg_depth.detach().to(dev, torch.float32).contiguous()
+    bounds = None
+    if use_input_depth_normalization:
+        disp_in = 1.0 / depth.detach().to(dev, torch.float32)
+        bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
+    gx, gy = _grids(res, res, dev)
+    ifx, ify = _inv_focal(intrinsics)
+    kcpu = intrinsics.detach().to("cpu", torch.float32)
+    fx, fy = float(kcpu[0, 0]), float(kcpu[1, 1])
+    covered = torch.zeros(res * res, dtype=torch.bool, device=dev)
+    for mask in removed:
+        covered |= (mask.detach() != 0).reshape(-1).to(dev)
+    bg_valid = (~covered).to(torch.uint8).contiguous()
+    K, R2 = len(cams), res * res
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.dh_reproject_background_workspace_bytes(res, ctypes.byref(nbytes)), "dh_reproject_background_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    zmap = torch.empty((K, res, res), dtype=torch.float32, device=dev)
+    disp = torch.empty((K, res, res), dtype=torch.float32, device=dev)
+    counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
+    bg_corr = torch.empty((K, R2, 4), dtype=torch.int64, device=dev)
+    bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
+    for e, c in enumerate(cams):
+        view = None if c is None else view_row(c)
+        _lib.check(L.dh_reproject_camera_background(
+            _lib.ptr(bg), res, _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, _lib.ptr(bounds), _lib.ptr(zmap[e]), _lib.ptr(disp[e]),
+            _lib.ptr(counts[e]), _lib.ptr(ws), nbytes.value, st,
+            None if view is None else view.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bg_valid), _lib.ptr(bg_corr[e]),
+            _lib.ptr(bg_counts[e:])), "dh_reproject_camera_background")
+    counts_h = counts.cpu()
+    _check_infill(counts_h[:, 3])
+    bg_h = bg_counts.cpu().tolist()
+    out, row_background = [], []
+    for e in range(K):
+        nb = int(bg_h[e])
+        rows_e = bg_corr[e, :nb]
+        inst_e = torch.full((nb,), N, dtype=torch.uint8, device=dev)
+        out.append((disp[e][None, None].to(out_dev), rows_e if device_correspondences else rows_e.cpu(),
+                    inst_e if device_correspondences else inst_e.cpu()))
+        row_background.append(torch.ones(nb, dtype=torch.uint8, device=dev))
+    if not return_debug:
+        return out
+    zeros = torch.zeros((K, res, res), dtype=torch.uint8, device=dev)
+    dbg = dict(zmap=zmap, raw_mask=zeros, clean_mask=zeros.clone(), vis=torch.zeros((K, 0), dtype=torch.uint8, device=dev),
+               target_xy=torch.zeros((K, 0, 2), dtype=torch.int32, device=dev), counts=counts_h,
+               fg_pix=torch.zeros(0, dtype=torch.int32, device=dev), corr_dev=torch.zeros((K, 0, 4), dtype=torch.int64, device=dev),
+               obj_start=np.zeros(1, dtype=np.int32), vacated=covered.reshape(res, res).to(torch.uint8),
+               corr_inst=torch.zeros((K, 0), dtype=torch.uint8, device=dev), inst_start=np.zeros(1, dtype=np.int32),
+               row_background=row_background, n_background=[int(v) for v in bg_h], bg_corr=bg_corr, bg_counts=bg_counts,
+               bg_valid=bg_valid)
+    return out, dbg
 
 
 def _vacated_u8(vacated, res, dev):

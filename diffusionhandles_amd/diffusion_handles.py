@@ -151,12 +151,55 @@ class DiffusionHandles:
                                                                             bg_weight, **lock))
         return imgs, [d for d, _ in edits]
 
+    def _camera_setup(self, what, cameras, donor):
+        """The host checks of an edit call's cameras (camera moves; DESIGN.md "Camera moves"), before any identity or launch ->
+        None (no camera: None, or every entry None: the call without the keyword) or the list of checked cameras / None.
+        ValueError (depth_transform.check_camera) naming `what` and the edit; NotImplementedError naming the setting for mesh
+        mode, footprints, conf background_lock: true (the reconstruction's latents belong to another view) and a donor."""
+        if cameras is None:
+            return None
+        from .depth_transform import check_camera
+        cams = [check_camera(c, f"{what}: edit {e}") for e, c in enumerate(cameras)]
+        if all(c is None for c in cams):
+            return None
+        if self.conf.depth_transform_mode != "pc":
+            raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no camera moves "
+                                      "(camera; only 'pc')")
+        if self._footprints(what)["footprints"]:
+            raise NotImplementedError(f"{what}: depth_transform_footprints: true has no camera moves (camera)")
+        from . import background_lock as BL
+        if BL.lock_conf(self.conf, what) is not None:
+            raise NotImplementedError(f"{what}: background_lock: true has no camera moves (camera; the reconstruction's latents "
+                                      "belong to another view)")
+        if donor is not None:
+            raise NotImplementedError(f"{what}: donor together with a camera is not supported (camera)")
+        return cams
+
+    @staticmethod
+    def _camera_weights(what, object_weights, n_instances):
+        """object_weights of a camera edit: the background is instance N, so N + 1 entries, N + 1 <= 8 (ValueError)."""
+        if object_weights is None:
+            return None
+        from .losses import MAX_OBJECTS, check_object_weights
+        if n_instances + 1 > MAX_OBJECTS:
+            raise ValueError(f"{what}: a camera edit with object_weights takes at most {MAX_OBJECTS - 1} instances (the background "
+                             f"is instance N), got {n_instances}")
+        try:
+            return check_object_weights(object_weights, n_instances + 1)
+        except ValueError as err:
+            raise ValueError(f"{what}: {err} (one weight per instance and one for the background)") from None
+
     def _reproject_objects(self, what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, device_correspondences,
-                           instances=None, removed_masks=None, donor=None):
+                           instances=None, removed_masks=None, donor=None, cameras=None):
         """instances given: every result is (disparity, correspondences, instance of every row).  removed_masks: the masks of the
         objects the edits delete (object removal); fg_masks may then be empty and the edits K empty lists.  donor: None or the
         checked donor (_donor_setup): its masks follow fg_masks in the object list, and an instance table is always given."""
-        from .depth_transform import check_instances, check_removed_masks, reproject_donor_edits, reproject_removal_edits
+        from .depth_transform import (check_instances, check_removed_masks, reproject_camera_edits, reproject_donor_edits,
+                                      reproject_removal_edits)
+        if cameras is not None:          # (checked by _camera_setup: no donor, no footprints, 'pc' mode)
+            reproject_removal_edits = functools.partial(self._reproject_camera, reproject_camera_edits, cameras)
+            if len(fg_masks) == 0 and removed_masks is None:
+                removed_masks = []
         if donor is not None:
             reproject_removal_edits = functools.partial(self._reproject_donor, reproject_donor_edits, donor)
         n_donor = 0 if donor is None else len(donor[1])
@@ -173,7 +216,7 @@ class DiffusionHandles:
         if removed_masks is not None:
             removed = check_removed_masks(removed_masks, list(fg_masks), f"{what}: removed_masks")
             if len(fg_masks) == 0 and donor is None:
-                if not removed:
+                if not removed and cameras is None:
                     raise ValueError(f"Expected 1 to 8 foreground masks, got 0 ({what}: no removed mask either)")
                 if instances is not None and len(list(instances)) != 0:
                     raise ValueError(f"{what}: instances={instances!r} given without a foreground mask (a pure removal has no "
@@ -201,6 +244,14 @@ class DiffusionHandles:
         return reproject_removal_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
                                        inst, removed_masks, use_input_depth_normalization,
                                        device_correspondences=device_correspondences, **fp, return_instances=inst is not None)
+
+    @staticmethod
+    def _reproject_camera(reproject, cameras, depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks,
+                          use_input_depth_normalization, device_correspondences=False, footprints=False, footprint_max_ratio=None,
+                          return_instances=False):
+        """reproject_camera_edits behind reproject_removal_edits' list: the cameras go last."""
+        return reproject(depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks, None, None,
+                         use_input_depth_normalization, False, device_correspondences, False, None, True, cameras)
 
     @staticmethod
     def _reproject_donor(reproject, donor, depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks, *args, **kw):
@@ -309,7 +360,8 @@ class DiffusionHandles:
 
     def transform_foreground_objects(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                      transforms, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                     object_weights=None, donor=None, removed_masks=None, instances=None, release_mask=None):
+                                     object_weights=None, camera=None, donor=None, removed_masks=None, instances=None,
+                                     release_mask=None):
         """One edit that moves M objects of one image (not in the reference).  fg_masks: M pairwise disjoint masks (at most 8);
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
         rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.  Each object
@@ -342,9 +394,23 @@ class DiffusionHandles:
         object_weights=None weighs every instance by its pair count, which gives every pair the unweighted coefficient
         fg_w / (C N) up to rounding.  Default guidance configuration only; 'pc' mode without footprints
         (NotImplementedError naming the setting).  ValueError naming the call, the donor and the member before any launch
-        (_donor_setup).  A donor whose masks are all empty is the call without the keyword."""
+        (_donor_setup).  A donor whose masks are all empty is the call without the keyword.
+        camera (camera moves; DESIGN.md "Camera moves"): None, or (rot_angle_deg, rot_axis, translation[, pivot]) -- the motion
+        of the CAMERA in the coordinates of depth_to_world_coords: turned about rot_axis through pivot (None = the camera centre:
+        a pan or tilt; depth_transform.pivot_at_pixel gives an orbit centre), then translated.  The whole image is then seen
+        from the moved viewpoint, and the background yields correspondences of its own, which join the guidance's pairs.  With
+        object_weights the background is instance N: the list has N + 1 entries (N + 1 <= 8) and "equal" includes the
+        background; under the default area weighting the background's rows outnumber the objects' by roughly ten to one.
+        fg_masks = [] with transforms = [] is the pure camera move.  ValueError (depth_transform.check_camera) before any
+        launch; NotImplementedError naming the setting for mesh mode, footprints, background_lock: true and a donor.
+        camera=None is the call without the keyword, byte for byte."""
         what = "transform_foreground_objects"
         fg_masks = list(fg_masks)
+        cams = self._camera_setup(what, None if camera is None else [camera], donor)
+        if cams is not None:
+            return self._camera_edit(what, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations, transforms,
+                                     fg_weight, bg_weight, use_input_depth_normalization, object_weights, cams, removed_masks,
+                                     instances)
         dn = self._donor_setup(what, donor, fg_masks, depth, activations)
         if dn is not None:
             if removed_masks is not None:
@@ -380,10 +446,42 @@ class DiffusionHandles:
             return edited_img, edited_disparity, denoising_steps
         return results, edited_disparity
 
+    def _camera_rows(self, what, fg_masks, instances, object_weights):
+        """(N, the checked weights or None) of a camera edit: N instances, the background's rows carry instance index N."""
+        from .depth_transform import check_instances
+        inst = check_instances(instances, len(fg_masks), f"{what}: instances") if fg_masks else None
+        N = len(fg_masks) if inst is None else len(inst)
+        if not fg_masks and object_weights is not None:
+            raise ValueError(f"{what}: object_weights={object_weights!r} given without a foreground mask")
+        return N, self._camera_weights(what, object_weights, N)
+
+    def _camera_edit(self, what, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations, transforms, fg_weight,
+                     bg_weight, use_input_depth_normalization, object_weights, cams, removed_masks, instances):
+        """transform_foreground_objects with a camera: the re-projection's rows (instance rows, then background rows with
+        instance index N) go to guided_inference with their kinds; with weights the instance column is the energy's object."""
+        self._check_removal(what, fg_masks, removed_masks)
+        N, weights = self._camera_rows(what, fg_masks, instances, object_weights)
+        with torch.no_grad():
+            (edited_disparity, correspondences, rows), = self._reproject_objects(
+                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances, removed_masks, None,
+                cams)
+            self.last_keep_maps = []
+            kw = dict(row_kind=(rows == N).to(torch.uint8) * 2, **self._vacated(removed_masks, what))
+            if weights is not None:
+                kw.update(pair_instances=rows, object_weights=weights)
+            results = self.diffuser.guided_inference(
+                latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
+                activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
+                bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps, **kw)
+        if self.conf.guided_diffuser.save_denoising_steps:
+            edited_img, denoising_steps = results
+            return edited_img, edited_disparity, denoising_steps
+        return results, edited_disparity
+
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
-                                           object_weights=None, streams=1, batch=None, donor=None, removed_masks=None,
-                                           instances=None, release_mask=None):
+                                           object_weights=None, streams=1, batch=None, cameras=None, donor=None,
+                                           removed_masks=None, instances=None, release_mask=None):
         """K edits of one image, each moving the M objects of fg_masks (transform_foreground_objects), in batched passes.
         edits: K lists of M (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale,
         pivot).  Returns (images [K,3,H,W], [K disparities]) as
@@ -393,9 +491,34 @@ class DiffusionHandles:
         release_mask: transform_foreground_objects', one for all K edits.  instances: transform_foreground_objects', one table
         for all K edits (the edits are then K lists of N transforms).  removed_masks: transform_foreground_objects', one list for
         all K edits (with fg_masks empty the edits are K empty lists: K identical pure removals).  donor:
-        transform_foreground_objects', one donor for all K edits (they share the channels-last copy of its activations)."""
+        transform_foreground_objects', one donor for all K edits (they share the channels-last copy of its activations).
+        cameras (camera moves): None, or a list of K, one camera (transform_foreground_objects) or None per edit -- K views of
+        one image are a turntable (depth_transform.orbit_cameras).  Edits with and without a camera share the call; the camera
+        call runs as one batch on one stream (NotImplementedError for streams > 1 or a smaller batch)."""
         what = "transform_foreground_objects_batch"
         fg_masks = list(fg_masks)
+        if cameras is not None and len(cameras) != len(edits):
+            raise ValueError(f"{what}: cameras has {len(cameras)} entries for {len(edits)} edits")
+        cams = self._camera_setup(what, cameras, donor)
+        if cams is not None:
+            K = len(edits)
+            if streams > 1 or (batch is not None and int(batch) < K):
+                raise NotImplementedError(f"{what}: cameras run as one batch on one stream (streams={streams}, batch={batch})")
+            if release_mask is not None:
+                raise ValueError(f"{what}: release_mask needs conf background_lock: true")
+            self._check_removal(what, fg_masks, removed_masks)
+            N, weights = self._camera_rows(what, fg_masks, instances, object_weights)
+            with torch.no_grad():
+                res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, instances,
+                                              removed_masks, None, cams)
+                self.last_keep_maps = []
+                # (an edit without a camera has no background row: its kinds are all zero, which is the call without them)
+                kw = dict(row_kind=[(r[2] == N).to(torch.uint8) * 2 for r in res], **self._vacated(removed_masks, what))
+                if weights is not None:
+                    kw.update(pair_instances=[r[2] for r in res], object_weights=weights)
+                imgs = self.diffuser.guided_inference_batch(init_noise, [r[0] for r in res], null_text_emb, prompt, activations,
+                                                            [r[1] for r in res], fg_weight, bg_weight, **kw)
+            return imgs, [r[0] for r in res]
         dn = self._donor_setup(what, donor, fg_masks, depth, activations)
         if dn is not None:
             if removed_masks is not None:
@@ -455,7 +578,9 @@ class DiffusionHandles:
         with max_batch >= 2K.  With conf background_lock every edit is locked to its own image's reconstruction; an edit may
         carry a `release_mask` (transform_foreground_objects).  A multi-object edit may carry `removed_masks` (object removal,
         transform_foreground_objects; fg_masks may then be [] with no transforms): edits of one image that differ in it are
-        re-projected in separate calls, and edits with and without it share the batch."""
+        re-projected in separate calls, and edits with and without it share the batch.  A multi-object edit may carry `camera`
+        (camera moves, transform_foreground_objects; fg_masks may then be [] with no transforms: a pure camera move): edits with
+        and without a camera share the batch, and edits of one image share its re-projection call."""
         from .depth_transform import check_instances, check_removed_masks, check_transform, reproject_edits
         fp = self._footprints("transform_foregrounds")
         if self.conf.depth_transform_mode != "pc":
@@ -470,8 +595,13 @@ class DiffusionHandles:
         if K < 1 or any(set(common) - set(e) for e in edits):
             raise ValueError(f"transform_foregrounds: needs at least one edit, each with {self.EDIT_FIELDS}")
         single_keys = ("fg_mask", "rot_angle", "rot_axis", "translation", "scale", "pivot")
-        multi_keys = ("fg_masks", "transforms", "object_weights", "instances", "removed_masks")
+        multi_keys = ("fg_masks", "transforms", "object_weights", "instances", "removed_masks", "camera")
         weights = [None] * K
+        cams = [None] * K
+        for i, e in enumerate(edits):
+            if isinstance(e, dict) and e.get("camera") is not None:
+                cams[i] = self._camera_setup(f"transform_foregrounds: edit {i}", [e["camera"]], None)
+                cams[i] = None if cams[i] is None else cams[i][0]
         for i, e in enumerate(edits):
             single = any(e.get(k) is not None for k in single_keys)
             multi = any(e.get(k) is not None for k in multi_keys)
@@ -486,9 +616,9 @@ class DiffusionHandles:
                 if removed is not None:
                     removed = check_removed_masks(removed, list(masks) if isinstance(masks, (list, tuple)) else [],
                                                   f"transform_foregrounds: edit {i}: removed_masks")
-                if not isinstance(masks, (list, tuple)) or (len(masks) < 1 and not removed):
+                if not isinstance(masks, (list, tuple)) or (len(masks) < 1 and not removed and cams[i] is None):
                     raise ValueError(f"transform_foregrounds: edit {i}: fg_masks must be a non-empty list of masks")
-                if len(masks) == 0:          # a pure removal: no transform, no table, no weights
+                if len(masks) == 0:          # a pure removal or a pure camera move: no transform, no table, no weights
                     if tfs or e.get("instances") or e.get("object_weights") is not None:
                         raise ValueError(f"transform_foregrounds: edit {i} has no foreground mask (a pure removal), but gives "
                                          "transforms, instances or object_weights")
@@ -500,7 +630,9 @@ class DiffusionHandles:
                                      f"{n_bodies} {body}")
                 for m, tf in enumerate(tfs):
                     check_transform(tf, f"transform_foregrounds: edit {i}, {'object' if inst is None else 'instance'} {m}")
-                if e.get("object_weights") is not None:
+                if e.get("object_weights") is not None and cams[i] is not None:
+                    weights[i] = self._camera_weights(f"transform_foregrounds: edit {i}", e["object_weights"], n_bodies)
+                elif e.get("object_weights") is not None:
                     from .losses import check_object_weights
                     try:
                         weights[i] = check_object_weights(e["object_weights"], n_bodies)
@@ -529,15 +661,27 @@ class DiffusionHandles:
             if e.get("removed_masks") is not None:      # one list of removed masks per re-projection call
                 key += ("removed",) + tuple(id(m) for m in e["removed_masks"])
             groups.setdefault(key, []).append(i)
-        reproj, labels, rows = [None] * K, [None] * K, [None] * K
+        reproj, labels, rows, kinds = [None] * K, [None] * K, [None] * K, [None] * K
         with torch.no_grad():
             for idx in groups.values():
                 e0 = edits[idx[0]]
                 if e0.get("fg_masks") is not None:
                     res = self._reproject_objects("transform_foregrounds", e0["depth"], e0["bg_depth"], list(e0["fg_masks"]),
                                                   [list(edits[i].get("transforms") or []) for i in idx],
-                                                  use_input_depth_normalization, True, e0.get("instances"), e0.get("removed_masks"))
-                    if e0.get("instances") is not None:          # the rows' instances stand in for the label image
+                                                  use_input_depth_normalization, True, e0.get("instances"), e0.get("removed_masks"),
+                                                  None, [cams[i] for i in idx] if any(cams[i] is not None for i in idx) else None)
+                    if any(cams[i] is not None for i in idx):
+                        # a camera call: the instance column always; the background's rows carry N.  The weighted edits of the
+                        # group read their objects from it (a label image cannot name the background).
+                        n_inst = len(e0["instances"]) if e0.get("instances") is not None else len(e0["fg_masks"])
+                        for i, r in zip(idx, res):
+                            kinds[i] = (r[2] == n_inst).to(torch.uint8) * 2 if cams[i] is not None else None
+                            rows[i] = r[2] if weights[i] is not None or e0.get("instances") is not None else None
+                            if cams[i] is None and weights[i] is not None and len(weights[i]) != n_inst:
+                                raise ValueError(f"transform_foregrounds: edit {i}: object_weights has {len(weights[i])} entries "
+                                                 f"for {n_inst} instances")
+                        res = [r[:2] for r in res]
+                    elif e0.get("instances") is not None:          # the rows' instances stand in for the label image
                         for i, r in zip(idx, res):
                             rows[i] = r[2]
                         res = [r[:2] for r in res]
@@ -558,7 +702,7 @@ class DiffusionHandles:
             self.last_keep_maps = []
             items = [dict(latents=e["init_noise"], depth=d, uncond_embeddings=e["null_text_emb"], prompt=e["prompt"],
                           activations_orig=e["activations"], correspondences=c, object_labels=labels[i], object_weights=weights[i],
-                          pair_instances=rows[i], **self._vacated(e.get("removed_masks"), "transform_foregrounds"),
+                          pair_instances=rows[i], row_kind=kinds[i], **self._vacated(e.get("removed_masks"), "transform_foregrounds"),
                           lock=self._edit_lock(lks[i], list(e["fg_masks"]) + list(e.get("removed_masks") or [])
                                                if e.get("fg_masks") is not None else e["fg_mask"], c, e["depth"]))
                      for i, (e, (d, c)) in enumerate(zip(edits, reproj))]

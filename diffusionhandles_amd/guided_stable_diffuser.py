@@ -484,7 +484,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
         _check_object_weights(object_weights, n)
 
     def prepare_guidance(self, depth, prompt, activations_orig, correspondences, fg_weight=None, bg_weight=None, orig=None,
-                         cond=None, object_labels=None, object_weights=None, pair_instances=None, donor=None, vacated=None,
+                         cond=None, object_labels=None, object_weights=None, pair_instances=None, row_kind=None, donor=None, vacated=None,
                          lock=None):
         """Everything of guided_inference that is constant over the denoising loop.  `lock` (background lock): (keep [s,s],
         trajectory [T,4,s,s]) -- the keep map of this edit (background_lock.keep_map) and the reconstruction trajectory of its
@@ -511,9 +511,22 @@ class GuidedStableDiffuser(GuidedDiffuser):
         on the weighted plan: object_weights=None means w_m = N_m, which gives every pair the unweighted coefficient
         fg_w / (C N) up to rounding.  Default configuration only (planned path, fg_patch_size 1, global_avg; NotImplementedError
         naming the setting otherwise); grad_scale 'auto' takes its bound from the weighted plan, as it does for weights.
-        None: the call without it."""
+        None: the call without it.
+        row_kind (edits that move the CAMERA, DESIGN.md "Camera moves"): one byte per correspondence row, 2 on the background
+        rows of the re-projection (0 on an object's).  A background row forms its pair and clears neither background list
+        (losses.process_correspondences).  Without object_weights the rows join the pairs of the unweighted plan; with them
+        pair_instances is required and the background is its instance N (object_weights then has N + 1 entries).
+        NotImplementedError together with donor.  None: the call without it."""
         from types import SimpleNamespace
         vacated = _losses.check_vacated(vacated, depth.shape[-1], "prepare_guidance")
+        if row_kind is not None:
+            if donor is not None:
+                raise NotImplementedError("prepare_guidance: row_kind (a camera move) together with donor is not supported")
+            row_kind = _losses.check_row_kind(row_kind, int(torch.as_tensor(correspondences).reshape(-1, 4).shape[0]),
+                                              "prepare_guidance")
+            if object_weights is not None and pair_instances is None:
+                raise ValueError("prepare_guidance: row_kind with object_weights needs pair_instances (the background is "
+                                 "instance N)")
         if donor is not None:
             donor = self._check_donor(donor, activations_orig, correspondences, pair_instances, object_labels)
         if object_labels is not None and pair_instances is not None:
@@ -527,6 +540,10 @@ class GuidedStableDiffuser(GuidedDiffuser):
             st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
                                              device=self.device, vacated=vacated, pair_instances=pair_instances,
                                              row_donor=donor[1])
+        elif row_kind is not None:
+            st.pc = _process_correspondences(correspondences, depth.shape[-1], self.conf.bg_erosion, grid=self.unet.sample_size,
+                                             device=self.device, vacated=vacated, row_kind=row_kind,
+                                             pair_instances=pair_instances if object_weights is not None else None)
         elif object_weights is None and vacated is None:
             st.pc = self.process_correspondences(correspondences, img_res=depth.shape[-1], bg_erosion=self.conf.bg_erosion)
         elif object_weights is None:
@@ -808,7 +825,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def _batch_edit_steps(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                           fg_weight=None, bg_weight=None, cond=None, orig=None, status_out=None, object_labels=None,
-                          object_weights=None, pair_instances=None, donor=None, vacated=None, lock=None):
+                          object_weights=None, pair_instances=None, row_kind=None, donor=None, vacated=None, lock=None):
         """The batched edit as a generator: yields after the preparation and after every denoising step (everything is only
         ENQUEUED on the current stream by then), returns the final latents [K,4,H,W] through StopIteration.  One body for the
         one-stream call below and for the lanes of guided_inference_batch_lanes.  fg_weight / bg_weight: one value, or one per
@@ -817,8 +834,11 @@ class GuidedStableDiffuser(GuidedDiffuser):
         of K (prepare_guidance; None entries are unlocked edits).  pair_instances: None or a list of K, the instances of every
         edit's correspondence rows (prepare_guidance).  vacated: None, one image for all K edits or a list of K (None entries: edits that
         delete nothing).  donor: None or (activations_donor, list of K row_donor) -- one donor image for all K edits, whose
-        channels-last copy they share (prepare_guidance)."""
+        channels-last copy they share (prepare_guidance).  row_kind: None or a list of K (None entries: edits without a camera),
+        the kinds of every edit's correspondence rows (prepare_guidance)."""
         K = len(depths)
+        if row_kind is not None and len(row_kind) != K:
+            raise ValueError(f"guided_inference_batch: row_kind has {len(row_kind)} entries for {K} edits")
         if donor is not None and (not isinstance(donor, (tuple, list)) or len(donor) != 2 or not isinstance(donor[1], (list, tuple))
                                   or len(donor[1]) != K):
             raise ValueError(f"guided_inference_batch: donor must be (activations_donor, a list of {K} row_donor arrays)")
@@ -839,6 +859,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
                                              orig=sts[0].orig if sts else orig, cond=sts[0].cond if sts else cond,
                                              object_labels=object_labels, object_weights=object_weights, lock=locks[i],
                                              pair_instances=None if pair_instances is None else pair_instances[i],
+                                             row_kind=None if row_kind is None else row_kind[i],
                                              donor=None if donor is None else (sts[0].donor if sts else donor[0], donor[1][i]),
                                              vacated=per(vacated, i)))
         x = _nhwc(latents.to(self.device, torch.float32)).expand(K, -1, -1, -1).contiguous()
@@ -852,7 +873,7 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference_batch(self, latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                fg_weight=None, bg_weight=None, object_labels=None, object_weights=None,
-                               pair_instances=None, donor=None, vacated=None, lock=None):
+                               pair_instances=None, row_kind=None, donor=None, vacated=None, lock=None):
         """K edits of one image at once.  depths: list of K edited disparities [1,1,H,W]; correspondences_list:
         K [N_k,4] tensors; fg_weight / bg_weight: one value or K.  Needs an engine built with max_batch >= 2K.  Returns images
         [K,3,H,W]; 'auto' grad_scale: FloatingPointError when an edit met a non-finite value.  object_labels / object_weights: one
@@ -861,13 +882,14 @@ class GuidedStableDiffuser(GuidedDiffuser):
         correspondence rows, in place of the label image (prepare_guidance).  vacated: None, one vacated image for all K edits
         or a list of K with None for the edits that delete nothing (prepare_guidance; DESIGN.md "Object removal").  donor: None or
         (activations_donor, list of K row_donor), one donor image for all K edits (prepare_guidance; DESIGN.md "Object
-        insertion")."""
+        insertion").  row_kind: None or a list of K, the kinds of every edit's correspondence rows (prepare_guidance; DESIGN.md
+        "Camera moves")."""
         status = []
         with torch.no_grad(), self.on_stream():
             gen = self._batch_edit_steps(latents, depths, uncond_embeddings, prompt, activations_orig, correspondences_list,
                                          fg_weight, bg_weight, status_out=status, object_labels=object_labels,
                                          object_weights=object_weights, lock=lock, pair_instances=pair_instances,
-                                         donor=donor, vacated=vacated)
+                                         row_kind=row_kind, donor=donor, vacated=vacated)
             try:
                 while True:
                     next(gen)
@@ -885,7 +907,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
         arguments of guided_inference per item, plus optional object_labels (or pair_instances: an edit with copies) /
         object_weights (prepare_guidance: a multi-object edit with a weight per object) and an optional lock ((keep,
         trajectory), prepare_guidance: locked and unlocked items may share a batch) and an optional vacated (the image of the pixels the
-        item's removed objects leave behind, prepare_guidance: items with and without it share a batch); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
+        item's removed objects leave behind, prepare_guidance: items with and without it share a batch) and an optional row_kind (the kinds of
+        the item's correspondence rows, prepare_guidance: an edit that moves the camera); fg_weight / bg_weight: one value or K.  Items with the same activations_orig
         tensors share one channels-last copy of them, items with the same prompt one encoding.  One resolution (the
         engine's); needs max_batch >= 2K and max_diff_batch >= K, raises otherwise (never splits).  Returns images [K,3,H,W]
         in item order and sets last_latents; 'auto' grad_scale: FloatingPointError naming the items that met a non-finite
@@ -917,7 +940,8 @@ class GuidedStableDiffuser(GuidedDiffuser):
                 st = self.prepare_guidance(it["depth"], it["prompt"], it["activations_orig"], it["correspondences"],
                                            per(fg_weight, i), per(bg_weight, i), orig=origs.get(okey), cond=conds.get(it["prompt"]),
                                            object_labels=it.get("object_labels"), object_weights=it.get("object_weights"),
-                                           lock=locks[i], pair_instances=it.get("pair_instances"), vacated=it.get("vacated"))
+                                           lock=locks[i], pair_instances=it.get("pair_instances"), vacated=it.get("vacated"),
+                                           row_kind=it.get("row_kind"))
                 origs[okey], conds[it["prompt"]] = st.orig, st.cond
                 sts.append(st)
             x = torch.cat([_nhwc(it["latents"].to(self.device, torch.float32)) for it in items]).contiguous()
@@ -1141,20 +1165,21 @@ class GuidedStableDiffuser(GuidedDiffuser):
 
     def guided_inference(self, latents, depth, uncond_embeddings, prompt, activations_orig, correspondences,
                          fg_weight=None, bg_weight=None, save_denoising_steps=False, record=None, object_labels=None,
-                         object_weights=None, pair_instances=None, donor=None, vacated=None, lock=None):
+                         object_weights=None, pair_instances=None, row_kind=None, donor=None, vacated=None, lock=None):
         """object_labels (or pair_instances, the instance of every correspondence row of an edit with copies) / object_weights:
         a weight per object for the foreground term (prepare_guidance).  lock: (keep,
         trajectory), the background lock -- after every DDIM step the latents are blended with the reconstruction's outside
         the edit's region (prepare_guidance; DESIGN.md "Background lock").  vacated: the image of the pixels the edit's removed
         objects leave behind (prepare_guidance; DESIGN.md "Object removal").  donor: (activations_donor, row_donor) of an edit
-        that brings in objects of another image (prepare_guidance; DESIGN.md "Object insertion")."""
+        that brings in objects of another image (prepare_guidance; DESIGN.md "Object insertion").  row_kind: the kinds of the
+        correspondence rows of an edit that moves the camera (prepare_guidance; DESIGN.md "Camera moves")."""
         with torch.no_grad(), self.on_stream():
             torch.manual_seed(self.conf.seed)
             self.scheduler.set_timesteps(self.conf.num_timesteps, device=self.device)
             timesteps, _ = self.get_timesteps(self.conf.num_timesteps, 1.0)
             st = self.prepare_guidance(depth, prompt, activations_orig, correspondences, fg_weight, bg_weight,
                                        object_labels=object_labels, object_weights=object_weights, lock=lock,
-                                       pair_instances=pair_instances, donor=donor, vacated=vacated)
+                                       pair_instances=pair_instances, row_kind=row_kind, donor=donor, vacated=vacated)
             denoising_steps = {"opt": [], "post-opt": []} if save_denoising_steps else None
             x = _nhwc(latents.to(self.device, torch.float32))
             for t_idx, t in enumerate(timesteps):

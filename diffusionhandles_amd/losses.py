@@ -99,8 +99,20 @@ def check_row_donor(row_donor, n_rows, what="process_correspondences"):
     return r
 
 
-def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, row_donor=None, vacated=None,
-                            object_labels=None, pair_instances=None):
+def check_row_kind(row_kind, n_rows, what="process_correspondences"):
+    """The kinds of an edit's correspondence rows (camera moves, DESIGN.md "Camera moves") -> None or a flat uint8 tensor of
+    n_rows entries: 0 = a host row, 1 = a donor row, 2 = a background row.  ValueError naming `what` for another length.
+    Host only: it reads the shape."""
+    if row_kind is None:
+        return None
+    r = torch.as_tensor(row_kind).reshape(-1)
+    if r.numel() != int(n_rows):
+        raise ValueError(f"{what}: row_kind has {r.numel()} entries for {n_rows} correspondences")
+    return r
+
+
+def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, device=None, row_donor=None, row_kind=None,
+                            vacated=None, object_labels=None, pair_instances=None):
     """[N,4] int64 (ox,oy,tx,ty) -> dict with original_x/y, transformed_x/y, background_x/y[_orig|_trans].
     object_labels ([H, W] uint8, object_label_image): adds "object", the 0-based object of every kept pair (int64, host), and
     `pair_obj` (uint8, device) to device_lists.
@@ -114,9 +126,15 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
     same lists); the correspondences may then be empty (the pure removal).  The keys of the dict do not change.
     row_donor ([N] uint8, non-zero = the row's source pixel lies in a DONOR image; DESIGN.md "Object insertion"): such a row
     forms its pair and clears its target cell like any row, and leaves the original-background list alone -- nothing of the
-    host started there.  None is the call without it, with the launches it had (all zeros give the same lists)."""
+    host started there.  None is the call without it, with the launches it had (all zeros give the same lists).
+    row_kind ([N] uint8: 0 = a host row, 1 = a donor row, 2 = a BACKGROUND row of a camera move; DESIGN.md "Camera moves"): a
+    background row forms its pair and clears neither background list -- the background stays background at both of its ends.
+    row_donor remains as the 0 / 1 form; ValueError when both are given.  Kinds 0 and 1 give the lists of row_donor."""
     vacated = check_vacated(vacated, img_res)
     row_donor = check_row_donor(row_donor, int(torch.as_tensor(correspondences).reshape(-1, 4).shape[0]))
+    row_kind = check_row_kind(row_kind, int(torch.as_tensor(correspondences).reshape(-1, 4).shape[0]))
+    if row_donor is not None and row_kind is not None:
+        raise ValueError("process_correspondences: row_donor and row_kind are mutually exclusive (row_kind 1 is a donor row)")
     if object_labels is not None and pair_instances is not None:
         raise ValueError("process_correspondences: object_labels and pair_instances are mutually exclusive")
     if pair_instances is not None:
@@ -140,7 +158,12 @@ def process_correspondences(correspondences, img_res, bg_erosion=0, grid=GRID, d
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     args = (_lib.ptr(corr) if n else _lib.c_p(0), n, int(img_res), grid, int(bg_erosion), _lib.ptr(pairs), _lib.ptr(bg_lists),
             _lib.ptr(bg_masks), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, _lib.stream_ptr())
-    if row_donor is not None:
+    if row_kind is not None:
+        vac = None if vacated is None else (vacated.to(dev) != 0).to(torch.uint8).contiguous()
+        kinds = row_kind.to(dev, torch.uint8).contiguous()
+        _lib.check(L.dh_cells_from_correspondences_rows(*args, _lib.ptr(vac), _lib.ptr(kinds) if n else _lib.c_p(0)),
+                   "dh_cells_from_correspondences_rows")
+    elif row_donor is not None:
         vac = None if vacated is None else (vacated.to(dev) != 0).to(torch.uint8).contiguous()
         flags = (row_donor.to(dev) != 0).to(torch.uint8).contiguous()
         _lib.check(L.dh_cells_from_correspondences_donor(*args, _lib.ptr(vac), _lib.ptr(flags) if n else _lib.c_p(0)),

@@ -636,9 +636,73 @@ def _check_similarity_entry(where, t):
                 raise ValueError(f"{where}: \"pivot\" must be finite, got {pv!r}")
 
 
+CAMERA_KEYS = ("rot_angle", "rot_axis", "translation", "pivot", "pivot_pixel")
+_TRANSFORM_KEYS = ("rotation_angle", "rotation_axis", "translation", "scale", "pivot", "objects", "remove", "object_weights")
+
+
+def _check_camera_entry(where, t):
+    """The optional "camera" of one transforms.json entry (not in the reference; camera moves): a dict {"rot_angle" (degrees,
+    default 0), "rot_axis" (3 numbers, default the Y axis, not zero), "translation" (3 numbers, default 0), "pivot" (3 numbers:
+    a point in the coordinates of depth_to_world_coords) or "pivot_pixel" ([x, y]: the point of that pixel, resolved with
+    depth_transform.pivot_at_pixel when the edit runs)} -- the motion of the CAMERA.  ValueError naming `where`."""
+    if not isinstance(t, dict) or "camera" not in t:
+        return
+    cam = t["camera"]
+    if not isinstance(cam, dict):
+        raise ValueError(f"{where}: \"camera\" must be an object with {CAMERA_KEYS}, got {cam!r}")
+    extra = [k for k in cam if k not in CAMERA_KEYS]
+    if extra:
+        raise ValueError(f"{where}: \"camera\" has unknown keys {extra} (known: {CAMERA_KEYS})")
+    f32 = lambda v: float(np.float32(v))
+    with np.errstate(over="ignore"):
+        if "rot_angle" in cam and not (_is_number(cam["rot_angle"]) and np.isfinite(f32(cam["rot_angle"]))):
+            raise ValueError(f"{where}: \"camera\": \"rot_angle\" must be a finite number, got {cam['rot_angle']!r}")
+        for key in ("rot_axis", "translation", "pivot"):
+            if key in cam:
+                v = cam[key]
+                if not isinstance(v, (list, tuple)) or len(v) != 3 or not all(_is_number(x) for x in v) or \
+                        not all(np.isfinite(f32(x)) for x in v):
+                    raise ValueError(f"{where}: \"camera\": \"{key}\" must be a list of 3 finite numbers, got {v!r}")
+        if "rot_axis" in cam and not any(f32(x) != 0.0 for x in cam["rot_axis"]):
+            raise ValueError(f"{where}: \"camera\": \"rot_axis\" must not be zero")
+    if "pivot_pixel" in cam:
+        v = cam["pivot_pixel"]
+        if "pivot" in cam:
+            raise ValueError(f"{where}: \"camera\" has both \"pivot\" and \"pivot_pixel\"")
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(isinstance(x, int) and not isinstance(x, bool) and x >= 0 for x in v):
+            raise ValueError(f"{where}: \"camera\": \"pivot_pixel\" must be [x, y], two integers >= 0, got {v!r}")
+
+
+def camera_args(t):
+    """The "camera" of one transforms.json entry -> None (no key), or dict(rot_angle, rot_axis, translation) with `pivot` (three
+    floats) or `pivot_pixel` ((x, y), to resolve with depth_transform.pivot_at_pixel) when the entry gives one."""
+    if not isinstance(t, dict) or "camera" not in t:
+        return None
+    _check_camera_entry("camera_args", t)
+    cam = t["camera"]
+    out = dict(rot_angle=float(cam.get("rot_angle", 0.0)), rot_axis=tuple(float(v) for v in cam.get("rot_axis", [0.0, 1.0, 0.0])),
+               translation=tuple(float(v) for v in cam.get("translation", [0.0, 0.0, 0.0])))
+    if "pivot" in cam:
+        out["pivot"] = tuple(float(v) for v in cam["pivot"])
+    if "pivot_pixel" in cam:
+        out["pivot_pixel"] = (int(cam["pivot_pixel"][0]), int(cam["pivot_pixel"][1]))
+    return out
+
+
+def is_pure_camera(t):
+    """An entry with "camera" and no transform key: a pure camera move of the whole image."""
+    return isinstance(t, dict) and "camera" in t and not any(k in t for k in _TRANSFORM_KEYS)
+
+
 def _check_similarity_entries(scene_dir, transforms):
     """Every entry of transforms.json, and every member of its "objects" list."""
     for name, t in transforms.items():
+        _check_camera_entry(f"{scene_dir}: transform {name!r}", t)
+        if isinstance(t, dict) and isinstance(t.get("objects"), (list, tuple)):
+            for m, o in enumerate(t["objects"]):
+                if isinstance(o, dict) and "camera" in o:
+                    raise ValueError(f"{scene_dir}: transform {name!r}, object {m}: \"camera\" belongs to the entry, not to a "
+                                     "member of \"objects\"")
         if isinstance(t, dict) and "remove" in t and "objects" in t:
             raise ValueError(f"{scene_dir}: transform {name!r}: \"remove\" belongs inside a member of \"objects\"")
         _check_similarity_entry(f"{scene_dir}: transform {name!r}", t)
@@ -670,7 +734,11 @@ def load_scene_geometry(scene_dir, img_res=512):
     of a SECOND image (and, for load_scene, its input.png and prompt.txt).  The dict then also has donor = dict(depth, masks).
     A member of "objects" may carry "donor": d: it is an instance of donor mask d, stands behind the host's members, carries
     no "mask" and no "remove", and an entry with donor members draws every donor mask (entry_donor).  The depth scale between
-    the two images is not estimated: the member's "scale" brings it.  Files without the key load to what they loaded to."""
+    the two images is not estimated: the member's "scale" brings it.  Files without the key load to what they loaded to.
+    An entry may carry "camera": {"rot_angle", "rot_axis", "translation", "pivot" | "pivot_pixel": [x, y]} (not in the reference;
+    camera moves, _check_camera_entry): the edit also moves the viewpoint.  In a multi-object scene it stands beside "objects";
+    in a single-mask scene an entry with only "camera" is a pure camera move of the whole image.  Malformed values raise
+    ValueError here, when the scene is loaded; files without the key load to what they loaded to."""
     import torch
     j = os.path.join
     with open(j(scene_dir, "transforms.json")) as f:
@@ -760,6 +828,8 @@ def transform_args(t):
             raise ValueError(f"transform_args: an entry that removes the object is exactly {{\"remove\": true}}, got {dict(t)!r}")
         return dict(remove=True)
     _check_similarity_entry("transform_args", t)
+    if is_pure_camera(t):       # a pure camera move of the whole image: no object transform
+        return dict(camera=camera_args(t), camera_only=True)
     args = dict(rot_angle=float(t.get("rotation_angle", 0.0)),
                 rot_axis=torch.tensor(t.get("rotation_axis", [0.0, 1.0, 0.0]), dtype=torch.float32),
                 translation=torch.tensor(t.get("translation", [0.0, 0.0, 0.0]), dtype=torch.float32))
@@ -767,6 +837,8 @@ def transform_args(t):
         args["scale"] = float(t["scale"]) if _is_number(t["scale"]) else tuple(float(v) for v in t["scale"])
     if "pivot" in t:
         args["pivot"] = tuple(float(v) for v in t["pivot"])
+    if isinstance(t, dict) and "camera" in t:
+        args["camera"] = camera_args(t)
     return args
 
 
@@ -783,6 +855,9 @@ def object_transform_args(entry):
     M' + d for a member of donor mask d, M' the number of (remaining) host masks."""
     if not isinstance(entry, dict) or "objects" not in entry:
         raise ValueError("object_transform_args: the entry has no \"objects\" list")
+    if "camera" in entry:          # camera moves: the entry's camera beside what the entry gives without it
+        rest = OrderedDict((k, v) for k, v in entry.items() if k != "camera")
+        return dict(object_transform_args(rest), camera=camera_args(entry))
     dn = entry_donor(entry["objects"], None, "object_transform_args")
     if dn is not None:
         host, members, index = dn

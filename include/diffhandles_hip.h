@@ -186,6 +186,40 @@ int dh_reproject_donor_edits(const float* depth, const float* bg_depth, const in
                              int footprints, float max_ratio, int corr_capacity,
                              int n_instances, const int32_t* inst_obj, uint8_t* corr_inst,
                              const float* donor_depth, int n_host_objects);
+/* Camera moves (not in the reference; DESIGN.md, "Camera moves"): dh_reproject_donor_edits in which an edit may also move the
+ * VIEWPOINT.  views [n_edits][DH_SIMILARITY_ROW] f64 and has_view [n_edits] u8 are HOST arrays: row e is the inverse motion of
+ * edit e's camera as a similarity row (unit axis, cos and sin of MINUS the camera's angle, translation, scale 1, pivot, has-pivot
+ * flag 1, 0); rows with has_view[e] = 0 are not read.  In an edit with a view EVERY point of the list -- the f32 background
+ * point, or an instance's transformed (X, Y, Z) rounded to f32 -- goes through the view row with the arithmetic of a transform
+ * row: q = fl32(P - c), f32 cross products and dot, the f64 combination, (r + (double)c) + t.  Such an edit has no clamp: a point
+ * whose rint(u) or rint(v) (half to even, before any clamp) leaves 0 .. res - 1, or whose Z is not > 0, bids for no pixel and
+ * yields no row; its vis is 0 and its target_xy (-1, -1).  A pixel no point reached joins the in-fill set and stays out of the
+ * disparity's min / max.  The z-buffer's tie rule is unchanged (z, list index).
+ *   bg_valid [res][res] u8 (device): 0 where bg_depth is in-painted (under the host's foreground and removed masks)
+ *   bg_corr  [n_edits][res * res][4] i64, bg_counts [n_edits] i32 (device): the BACKGROUND rows of the view edits --
+ *            background point i (source pixel i) yields (ox, oy, tx, ty) when bg_valid[i] != 0, the point owns its target
+ *            pixel and that pixel lies outside the cleaned mask; ascending source pixel.  An edit without a view has none
+ *            (bg_counts[e] = 0).  The layout of corr, corr_inst and counts does not change.
+ * An edit without a view is computed as dh_reproject_donor_edits computes it, byte for byte; with has_view all zero (or views
+ * NULL) the call IS that entry's: the three background arguments are neither read nor written and the workspace may be
+ * dh_reproject_donor_workspace_bytes'.  dh_reproject_donor_edits is this entry's call without a view.
+ * Refused (DH_ERR_ARG before any launch, outputs untouched), beyond what the donor entry refuses: a view with footprints != 0;
+ * a view with a null bg_valid, bg_corr or bg_counts; a malformed view row (a member that is not finite, a scale that is not
+ * positive, a has-pivot flag other than 0 or 1). */
+int dh_reproject_camera_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances, int footprints,
+                                        size_t* bytes);
+int dh_reproject_camera_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                              int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                              const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                              int n_edits, const double* xforms_host, const float* bounds,
+                              float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                              uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream,
+                              int footprints, float max_ratio, int corr_capacity,
+                              int n_instances, const int32_t* inst_obj, uint8_t* corr_inst,
+                              const float* donor_depth, int n_host_objects,
+                              const double* views, const uint8_t* has_view, const uint8_t* bg_valid,
+                              int64_t* bg_corr, int32_t* bg_counts);
 /* Object removal, the pure case (not in the reference; DESIGN.md, "Object removal"): the re-projection of the background
  * alone, for an edit that deletes its objects and moves none.  The point list is the res * res pixels of bg_depth; it runs the
  * kernels of the entries above on that part of the list: z-buffer (winner = min (z, point index)), zmap (+inf where no point
@@ -201,6 +235,17 @@ int dh_reproject_background(const float* bg_depth, int res, const float* grid_x,
                             float inv_fx, float inv_fy, double fx, double fy, const float* bounds,
                             float* zmap, float* disparity, int32_t* counts,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* Camera moves, the pure case: dh_reproject_background with one view row (view [DH_SIMILARITY_ROW] f64, host; NULL = no view,
+ * which is dh_reproject_background launch for launch -- that entry is this one's NULL call).  With a view the background points
+ * go through it as in dh_reproject_camera_edits (no clamp, out-of-frame points bid for nothing), the pixels no point reached
+ * are in-filled and stay out of the min / max, and every background point with bg_valid != 0 that owns its target pixel yields
+ * a row: bg_corr [res * res][4] i64, bg_counts [1] i32.  Same workspace.  DH_ERR_ARG before any launch, outputs untouched: a
+ * view with a null bg_valid, bg_corr or bg_counts, a malformed view row. */
+int dh_reproject_camera_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                                   float inv_fx, float inv_fy, double fx, double fy, const float* bounds,
+                                   float* zmap, float* disparity, int32_t* counts,
+                                   void* workspace, size_t workspace_bytes, void* stream,
+                                   const double* view, const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);
@@ -252,6 +297,15 @@ int dh_cells_from_correspondences_donor(const int64_t* corr, int n, int img_res,
                                         int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
                                         void* workspace, size_t workspace_bytes, void* stream,
                                         const uint8_t* vacated, const uint8_t* row_donor);
+/* Camera moves (not in the reference; DESIGN.md, "Camera moves"): the _donor entry with row_kind [n] u8 on the device (may be
+ * NULL) in place of row_donor: 0 = a host row, 1 = a donor row, 2 = a BACKGROUND row of a camera move, which forms its pair and
+ * clears neither mask -- the background stays background at both of its ends, so the global_avg term keeps its two cell lists.
+ * (Any other value is read as 1.)  NULL and kinds {0, 1} are the _donor entry in every output byte, which is this entry's call
+ * with those kinds; same workspace, same refusals. */
+int dh_cells_from_correspondences_rows(const int64_t* corr, int n, int img_res, int grid, int bg_erosion,
+                                       int32_t* pairs, int32_t* bg_lists, uint8_t* bg_masks, int32_t* counts,
+                                       void* workspace, size_t workspace_bytes, void* stream,
+                                       const uint8_t* vacated, const uint8_t* row_kind);
 
 /* Keep map of the background lock: keep [s][s] f32, 0 inside the region an edit touches, 1 far from it, a ramp between.
  * A latent cell (res / s pixels square) is a REGION cell if one of its pixels is non-zero in mask or release (u8 [res][res],

@@ -14,7 +14,10 @@ removed and sphere 0 moved (reproject_removal_edits), and the pure removal of bo
 once for the K edits).
 DH_DONOR=1 (default unset; the two-sphere scene whatever DH_OBJECTS says): two further lines time the K = 8 instance call on the
 two spheres (reproject_instance_edits, instances [0, 1]: what the parent commit runs too) and the same call with one donor
-sphere of tests/object_insertion_ref.py beside them (reproject_donor_edits: object insertion; profiles/object_insertion/)."""
+sphere of tests/object_insertion_ref.py beside them (reproject_donor_edits: object insertion; profiles/object_insertion/).
+DH_CAMERA=1 (default unset; the two-sphere scene whatever DH_OBJECTS says): two further lines time the K = 8 instance call on the
+two spheres and the same call with eight orbit cameras about the centre pixel (depth_transform.orbit_cameras, -14 .. 14 degrees:
+reproject_camera_edits, camera moves; profiles/camera_moves/); the second line also reports the background rows per edit."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -141,6 +144,27 @@ if os.environ.get("DH_DONOR", "0") not in ("", "0"):
                                     donor_masks=donor_masks, **kw)
         return ([r[:2] for r in out[0]], out[1]) if kw.get("return_debug") else [r[:2] for r in out]
     report(donor_call, " two spheres and one donor sphere")
+    M = M_shown
+if os.environ.get("DH_CAMERA", "0") not in ("", "0"):
+    from diffusionhandles_amd.depth_transform import orbit_cameras, reproject_camera_edits, reproject_instance_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    c_depth, c_bg, c_masks = R.two_spheres(res)
+    c_depth, c_bg, c_masks = c_depth.to(dev), c_bg.to(dev), [m.to(dev) for m in c_masks]
+    M_shown, M = M, 2
+    two = [[tfs[i], tfs[(i + 3) % 8]] for i in range(K)]
+    cams = orbit_cameras(c_depth, intr, res // 2, res // 2, [-14.0 + 4.0 * i for i in range(K)])
+    report(lambda **kw: reproject_instance_edits(c_depth, c_bg, c_masks, intr, two, [0, 1], **kw), " two spheres, instances [0, 1]")
+    n_bg = []
+
+    def camera_call(**kw):          # (a camera call returns the instance array beside every result: report() reads pairs)
+        out = reproject_camera_edits(c_depth, c_bg, c_masks, intr, two, [0, 1], cameras=cams, **kw)
+        if kw.get("return_debug"):
+            n_bg[:] = out[1]["n_background"]
+            return [r[:2] for r in out[0]], out[1]
+        return [r[:2] for r in out]
+    report(camera_call, " two spheres, eight orbit cameras")
+    print(f"  background rows per edit {n_bg}", flush=True)
     M = M_shown
 if scale is not None:
     if M == 1:

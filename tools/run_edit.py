@@ -299,6 +299,25 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
                 if getattr(args, "edit_batch", 1) > 1:
                     raise NotImplementedError(f"{scene}: transform {n!r} inserts a donor object (\"donor\"); --edit-batch "
                                               "(mixed-image batches) has no object insertion")
+        # camera moves: refused before any identity is computed where the re-projection or the loop has none
+        for n, t in sc["transforms"].items():
+            if isinstance(t, dict) and "camera" in t:
+                if args.mode != "pc":
+                    raise NotImplementedError(f"{scene}: transform {n!r} moves the camera (\"camera\"); --mode {args.mode} has no "
+                                              "camera moves, use --mode pc")
+                if getattr(args, "footprint_report", {}).get("footprints"):
+                    raise NotImplementedError(f"{scene}: transform {n!r} moves the camera (\"camera\"); --footprints "
+                                              "(depth_transform_footprints) has no camera moves")
+                if getattr(args, "background_lock", False):
+                    raise NotImplementedError(f"{scene}: transform {n!r} moves the camera (\"camera\"); --background-lock "
+                                              "(background_lock) has no camera moves: the reconstruction's latents belong to "
+                                              "another view")
+                if any(isinstance(o, dict) and "donor" in o for o in t.get("objects") or []):
+                    raise NotImplementedError(f"{scene}: transform {n!r} moves the camera (\"camera\") and inserts a donor object "
+                                              "(\"donor\"): not supported together")
+                if getattr(args, "edit_batch", 1) > 1:
+                    raise NotImplementedError(f"{scene}: transform {n!r} moves the camera (\"camera\"); --edit-batch (mixed-image "
+                                              "batches of scene directories) does not pass cameras, use --edit-batch 1")
         if args.mode != "pc":           # object removal: before the identity is computed
             for n, t in sc["transforms"].items():
                 objs = t.get("objects") if isinstance(t, dict) else None
@@ -463,6 +482,19 @@ def write_scene_pages(args, out, img, mask, depth, bg_depth, prompt, res, report
                 f"({res}x{res}, {args.mode})</h3><table border='1' cellspacing='0' cellpadding='4'><tr>{head}</tr>{''.join(rows)}</table></body></html>")
 
 
+def resolve_camera(dh, depth, camera):
+    """camera_args' dict -> the camera tuple of transform_foreground_objects (None -> None); "pivot_pixel" is resolved against
+    the scene's depth with depth_transform.pivot_at_pixel."""
+    if camera is None:
+        return None
+    pivot = camera.get("pivot")
+    if "pivot_pixel" in camera:
+        from diffusionhandles_amd.depth_transform import pivot_at_pixel
+        x, y = camera["pivot_pixel"]
+        pivot = tuple(float(v) for v in pivot_at_pixel(depth, dh.diffuser.get_depth_intrinsics(device=depth.device), x, y))
+    return (camera["rot_angle"], camera["rot_axis"], camera["translation"], pivot)
+
+
 def split_removed(masks, remove):
     """The masks of a multi-object scene as the keywords of an edit call: fg_masks (what the entry leaves) and, for an entry
     with {"remove": true} members (object_transform_args' `remove`), removed_masks."""
@@ -578,13 +610,19 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
             report["edits"].append(dict(name=tf["name"], skipped=True))
             continue
         t0 = time.time()
+        cam = {} if tf.get("camera") is None else dict(camera=resolve_camera(dh, depth, tf["camera"]))
         if p.get("masks_dev") is not None:
             rel = {} if p.get("release") is None else dict(release_mask=p["release"])
             sp = split_removed(p["masks_dev"], tf.get("remove"))
             res_ = dh.transform_foreground_objects(depth, prompt, sp["fg_masks"], bg_depth, null_text, noise, acts,
                                                    transforms=tf["transforms"], object_weights=tf["object_weights"],
                                                    removed_masks=sp.get("removed_masks"), instances=tf.get("instances"),
-                                                   **(dict(donor=donor) if tf.get("donor") else {}), **rel)
+                                                   **(dict(donor=donor) if tf.get("donor") else {}), **rel, **cam)
+        elif tf.get("camera_only"):     # a single-mask scene's entry with only "camera": the whole image from another viewpoint
+            res_ = dh.transform_foreground_objects(depth, prompt, [], depth, null_text, noise, acts, transforms=[], **cam)
+        elif cam:                       # the object moves and the camera moves: the one-mask form of transform_foreground_objects
+            tf5 = (tf["rot_angle"], tf["rot_axis"], tf["translation"], tf.get("scale"), tf.get("pivot"))
+            res_ = dh.transform_foreground_objects(depth, prompt, [mask], bg_depth, null_text, noise, acts, transforms=[tf5], **cam)
         elif tf.get("remove"):          # a single-mask scene's {"remove": true}: a pure removal
             rel = {} if p.get("release") is None else dict(release_mask=p["release"])
             res_ = dh.transform_foreground_objects(depth, prompt, [], bg_depth, null_text, noise, acts, transforms=[],

@@ -60,8 +60,16 @@ struct Arena {
 typedef _Float16 f16;
 typedef __bf16 bf16;
 
-// m / d for 0 <= m < 2^22 and a quotient below a few hundred, from a float reciprocal of d (1 ulp): the product
-// (m + 0.5) * inv is at least 0.5 / d away from an integer, far more than its rounding error, so truncation is exact.
+// m / d from a float reciprocal of d (v_rcp_f32: 1 ulp).  The product (m + 0.5) * inv is at least 0.5 / d away from an integer and
+// carries a relative error of at most 1.5 * 2^-23 (the reciprocal's ulp, the multiply's rounding), i.e. at most 1.5 * 2^-23 * m / d
+// absolute: truncation is exact for every d while 0 <= m < 2^22 / 1.5 (2.79 M; the size of the quotient does not enter).  The
+// engines stay below 2^21 rows per launch (dh_unet_create, dh_vae_*_create), so rows / (rows per image), (row in image) / width and
+// the small in-block divisions are all inside that.
+// ONE caller family goes past it: the GroupNorm slice edges div_small(HW * s, 1 / S) of k_gn_partial, k_concat_gn and
+// k_splitk_reduce_gn reach 2^23 (a 512^2 image) and 18.9 M (768^2).  They are exact for another reason, and only under it: S
+// (gn_slices) is a power of two there, so its reciprocal is exact, and HW * s is a multiple of 4096 below 2^36, hence a float32;
+// (m + 0.5) is then m + 0.5 or rounds back to m, and the product is the exact quotient or lies 2^-6 above it.  A slice count that is
+// no power of two at such sizes would put the last slice's edge off by one row (tests/test_vae_geometry.py walks both statements).
 // An integer division is ~30 dependent instructions and sits in front of the first load of every conv tile.
 __device__ __forceinline__ int div_small(int m, float inv) { return (int)(((float)m + 0.5f) * inv); }
 __device__ __forceinline__ float rcp_fast(int d) { return __builtin_amdgcn_rcpf((float)d); }

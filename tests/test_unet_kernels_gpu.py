@@ -111,6 +111,34 @@ def test_gemm_dense(dtype, M, N, K):
         close(C, F.silu(z), tol, tol, "gemm silu/rowvec")
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("rows", [77, 154])
+@pytest.mark.parametrize("N,K,residual", [(3072, 1024, False), (1024, 1024, True), (4096, 1024, False), (1024, 4096, True)])
+def test_gemm_text_tower(dtype, rows, N, K, residual):
+    """the four GEMMs of a text-tower layer (csrc/text_engine.cpp: q|k|v, out_proj + x, fc1, fc2 + t) as the engine launches them: 77 tokens
+    per prompt, a bias, the residual where the layer adds one, NO split-K workspace; the launch is the one the pinned table names"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_gemm_plan import ALIGNED, BIAS, PASSES, PINNED, RESIDUAL, named, plan
+    g = torch.Generator(device=dev()).manual_seed(rows + N + K)
+    A = torch.randn(rows, K, generator=g, device=dev()).to(dtype)
+    W = (torch.randn(N, K, generator=g, device=dev()) / K ** 0.5).to(dtype)
+    bias = torch.randn(N, generator=g, device=dev())
+    R = torch.randn(rows, N, generator=g, device=dev()).to(dtype) if residual else None
+    ref = A.float() @ W.float().t() + bias + (R.float() if residual else 0.0)
+    C = run_gemm(dtype, A, K, W, rows, N, K, bias=bias, R=R, split=False)
+    torch.cuda.synchronize()
+    rep = (ctypes.c_int * 9)()
+    L().check(L().lib().dh_dbg_gemm_last_tile(rep), "dh_dbg_gemm_last_tile")
+    flags = ALIGNED | BIAS | (RESIDUAL if residual else 0)
+    p = named(plan(rows, N, K, flags=flags, part=0))
+    pinned = dict(PASSES[f"text_b{rows // 77}"])[(rows, N, K, 0, 0, 1, 0, 0, 0, flags)]
+    assert tuple(p[f] for f in PINNED) == pinned, (p, pinned)
+    assert list(rep) == [p["bm"], p["bn"], p["kg"], p["stages"], p["mw"], 1, 0, 0, 0], (list(rep), p)
+    tol = 4e-3 if dtype == torch.float16 else 2.5e-2
+    close(C, ref, tol, tol, f"text tower gemm {rows}x{N}x{K}")
+    close(C[-13:], ref[-13:], tol, tol, f"text tower gemm {rows}x{N}x{K} ragged last rows")
+
+
 # case -> the arm of launch_planned's switch it reaches: (k_gemm_pp, BM, BN, stages, K groups, wave multiplier).  The first five are the
 # shapes the query was specified with; under the policy's short-K rule four of them run the 64x64 tile, so the smallest shapes that
 # reach the 128x128 tile, the unsplit 128x64 tile, a convolution off the 64x64 tile and k_gemm_pp follow (tests/test_gemm_plan.py has
@@ -268,7 +296,9 @@ def test_groupnorm(dtype, B, HW, C, silu):
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("rows,C", [(4096, 320), (1024, 640), (77, 1280), (300, 64)])
+@pytest.mark.parametrize("rows,C", [(4096, 320), (1024, 640), (77, 1280), (300, 64),
+                                    (77, 1024), (154, 1024), (20, 1024),      # the text tower: exactly two full chunks per lane
+                                    (64, 2048)])                               # C > 1536: the LN_MAXCH instantiation
 def test_layernorm(dtype, rows, C):
     g = torch.Generator(device=dev()).manual_seed(C + rows)
     x = (torch.randn(rows, C, generator=g, device=dev()) * 1.5 - 0.3).to(dtype)

@@ -4,10 +4,13 @@ Mirrors /root/reference/diffhandles/depth_transform.py:73-89 (`transform_depth`)
 :198-363 (`transform_depth_pc`), :15-28 (`normalize_depth`), :589-641
 (`depth_to_world_coords`).  All arithmetic runs in the HIP library
 (csrc/geometry.hip) through the C ABI; PyTorch only owns the device buffers.
-`reproject_edits` is the batched form (K rigid transforms of one image in one launch
-sequence) that the reference does not have.
+`reproject` is the batched form (K edits of one image in one launch sequence) that the
+reference does not have: `reproject_plan` decides everything on the host, `_run_plan` allocates
+and launches (DESIGN.md "One host path for the re-projection"); `reproject_edits` ..
+`reproject_camera_edits` are that call under the names and parameter lists they grew up with.
 """
 import ctypes
+import types
 
 import numpy as np
 import torch
@@ -273,25 +276,6 @@ def mesh_has_no_footprints(footprints, footprint_max_ratio, what):
         raise NotImplementedError(f"{what}: depth_transform_mode 'mesh' has no footprints (got footprints=True); use 'pc'")
 
 
-def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_depth_normalization=False,
-                    return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None):
-    """K edits of one image.  transforms: list of (rot_angle_deg, rot_axis[3], translation[3]) or of
-    (rot_angle_deg, rot_axis[3], translation[3], scale, pivot) (check_transform; `reproject_object_edits` says what scale
-    and pivot do).
-
-    Returns a list of (disparity [1,1,H,W] f32 on depth.device, correspondences [N,4] int64 CPU),
-    plus a dict of the intermediate device tensors when return_debug is set.  The reference hands the correspondences
-    over as a CPU tensor (depth_transform.py:339-343) and so does `transform_depth`; device_correspondences=True leaves
-    them where the kernels wrote them, for callers that feed them straight back to the device (the batched edit path:
-    `process_correspondences` accepts either) -- K device-to-host copies and K uploads less per call.
-
-    The one-object call of `reproject_object_edits` (footprints / footprint_max_ratio: see there).
-    """
-    return reproject_object_edits(depth, bg_depth, [fg_mask], intrinsics, [[tf] for tf in transforms],
-                                  use_input_depth_normalization, return_debug, device_correspondences, footprints,
-                                  footprint_max_ratio)
-
-
 def check_instances(instances, n_masks, what="instances"):
     """The instance table of an edit with copies -> list of N mask indices (None -> None: one instance per mask).
     ValueError naming `what` and the instance for more than 8 instances, an entry that is not an integer in 0 .. n_masks - 1,
@@ -316,69 +300,12 @@ def check_instances(instances, n_masks, what="instances"):
     return out
 
 
-def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_input_depth_normalization=False,
-                           return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None):
-    """K edits of one image with M bodies each (not in the reference).  fg_masks: M pairwise disjoint [1,1,H,W] masks
-    (1 <= M <= 8); bg_depth: the depth with ALL objects removed; edits: K lists of M (rot_angle_deg, rot_axis[3],
-    translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.
-
-    Object m turns about the centroid of its own masked points, then moves.  With a 5-tuple it is first scaled -- scale:
-    None (= 1), one positive float or three (sx, sy, sz) along the camera axes of `depth_to_world_coords`, applied to the
-    offsets from the pivot BEFORE the rotation, so a non-uniform scale of a turned object stretches along the un-turned
-    camera axes -- and pivot (None = the centroid; else a point in the coordinates `depth_to_world_coords` returns, see
-    `pivot_at_pixel`) replaces the centroid for the scale and the turn.  Scale 1 with pivot None is the 3-tuple's result
-    bit for bit.  A magnified object leaves gaps between its points; the mask CLOSE bridges them only up to its element,
-    res // 50 (as when an object moves towards the camera).  ValueError naming the edit and the object for a malformed
-    transform (check_transform), before any device work.  The point list is the background pixels, then
-    the points of object 0 in row-major order, then object 1, ...: one z-buffer over all of it, so the objects occlude the
-    background and each other, and equal depths go to the earlier object.  Mask clean-up, correspondence filter, in-fill
-    and normalisation see the union.  Empty masks are dropped (with their transforms); all empty = the empty-mask result of
-    `reproject_edits`.  ValueError for overlapping masks, M > 8, or an edit that does not have M transforms.
-
-    Returns what `reproject_edits` returns: the correspondences [N,4] int64 (ox, oy, tx, ty) in point-list order (object
-    order, row-major within an object).  The debug dict also has obj_start, the M' + 1 offsets of the kept objects'
-    slices in fg_pix / vis / target_xy.
-
-    footprints=True (footprint splatting): the triangles between neighbouring points of ONE object bid in the
-    z-buffer too, so an enlarged or approaching object has no gaps between its points.  The correspondences are then one row
-    per foreground-owned target pixel inside the cleaned mask -- (ox, oy) of the owning point, (tx, ty) of the pixel -- in
-    ROW-MAJOR TARGET order, and there may be more of them than foreground points (at most H * W).  footprint_max_ratio: None
-    or a finite float > 1; a triangle whose source depths differ by more than this factor is left out (no sheets across a
-    depth step inside one mask).  ValueError for a bad ratio or a ratio without footprints, before any device work.
-    Copies of an object (several instances of one mask): `reproject_instance_edits`, of which this is the call without a table.
-    """
-    return reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, None, use_input_depth_normalization,
-                                    return_debug, device_correspondences, footprints, footprint_max_ratio)
-
-
-def reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, use_input_depth_normalization=False,
-                             return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None,
-                             return_instances=False):
-    """`reproject_object_edits` with an instance table (not in the reference): everything said there holds, and --
-
-    instances (copies of an object, DESIGN.md "Object copies"): None, or a list of N mask indices, M <= N <= 8, naming every
-    mask at least once.  Instance n draws the points of mask instances[n] with transform n of every edit (the edits are then K
-    lists of N transforms), about the centroid of that mask (computed once per mask) or its pivot.  The point list is the
-    background, then instance 0's points, instance 1's, ...: one z-buffer, equal depths to the earlier instance.  The
-    correspondences are in point-list order -- a source pixel once per visible, kept instance -- and with footprints the
-    triangles join neighbouring points of one instance.  One table serves all K edits.  ValueError naming the instance (or
-    the edit) for a bad table or an edit that does not have N transforms, before any device work.  The debug dict gains
-    corr_inst [K, capacity] uint8 (the caller's instance index of every correspondence row) and inst_start (the offsets of the
-    kept instances' slices in vis / target_xy); instances=None is `reproject_object_edits`, byte for byte.
-    return_instances=True: every result is (disparity, correspondences [R,4], instances [R] uint8 beside them); without
-    an instance table the instance of a row is the index of its mask.
-    Removing an object: `reproject_removal_edits`, of which this is the call without removed masks.
-    """
-    return reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, None, use_input_depth_normalization,
-                                   return_debug, device_correspondences, footprints, footprint_max_ratio, return_instances)
-
-
 def check_removed_masks(removed_masks, fg_masks, what="removed_masks"):
     """The removed masks of an edit (object removal, DESIGN.md "Object removal") -> list of R >= 0 masks (None -> []).
     ValueError naming `what` and the mask for something that is not a list of masks, or a mask that is not square or not of
     the size of the foreground masks (of the first removed mask when there is no foreground mask).  Host only: it reads shapes.
     Whether a removed mask overlaps a foreground mask or another removed mask is a question about pixels:
-    `reproject_removal_edits` answers it in the device-to-host copy that reads the pixel counts, `removed_overlap` on its own."""
+    `reproject_plan` answers it in the device-to-host copy that reads the pixel counts, `removed_overlap` on its own."""
     if removed_masks is None:
         return []
     if isinstance(removed_masks, (torch.Tensor, np.ndarray)) or not isinstance(removed_masks, (list, tuple)):
@@ -402,7 +329,7 @@ def check_removed_masks(removed_masks, fg_masks, what="removed_masks"):
 def removed_overlap(removed_masks, fg_masks, what="removed_masks"):
     """ValueError naming `what` and the masks when a removed mask shares a pixel with a foreground mask or with an earlier
     removed mask.  Host arithmetic on the masks where they are (one copy per mask pair tested: the error path and host callers;
-    `reproject_removal_edits` carries one flag per removed mask in its own copy and calls this only to name the pair)."""
+    `reproject_plan` carries one flag per removed mask in its own copy and calls this only to name the pair)."""
     removed = check_removed_masks(removed_masks, fg_masks, what)
     flat = lambda m: (m.detach() != 0).reshape(-1)
     for r, mask in enumerate(removed):
@@ -471,75 +398,99 @@ def check_donor(donor_depth, donor_masks, res, n_host, what="donor"):
     return donor_depth, list(donor_masks)
 
 
-def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None,
-                            use_input_depth_normalization=False, return_debug=False, device_correspondences=False,
-                            footprints=False, footprint_max_ratio=None, return_instances=False):
-    """`reproject_instance_edits` for an edit that also DELETES objects (not in the reference; DESIGN.md "Object removal"); the
-    text is `reproject_donor_edits`', of which this is the call without a donor."""
-    return reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, removed_masks, None, None,
-                                 use_input_depth_normalization, return_debug, device_correspondences, footprints,
-                                 footprint_max_ratio, return_instances)
+def donor_rows(rows, instances, n_host):
+    """One byte per correspondence row: 1 where the row's instance draws a donor mask (instances[rows[r]] >= n_host).  `rows`
+    holds instance indices as uint8 (256 table entries: the rows past the counts are not written), the result lies beside it."""
+    lut = torch.zeros(256, dtype=torch.uint8)
+    lut[:len(instances)] = torch.tensor([1 if o >= n_host else 0 for o in instances], dtype=torch.uint8)
+    return lut.to(rows.device)[rows.long()]
 
 
-def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
-                          donor_masks=None, use_input_depth_normalization=False, return_debug=False,
-                          device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False):
-    """`reproject_camera_edits` without cameras: the text is there."""
-    return reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, removed_masks, donor_depth, donor_masks,
-                                  use_input_depth_normalization, return_debug, device_correspondences, footprints,
-                                  footprint_max_ratio, return_instances, None)
+def _plan(kind, entry=None, workspace_query=None, **fields):
+    """The record `reproject_plan` returns: what it decided about one call, host values only, nothing of the compute device.
+
+    kind              "objects", "pure_removal", "pure_camera" or "empty"
+    entry             the C entry that runs (None: "empty" launches nothing)
+    workspace_query   the *_workspace_bytes entry that sizes its workspace
+    res               the side of the images
+    M, D, N           host masks, donor masks and instances as the caller gave them
+    kept              indices of the non-empty masks (host masks, then donor masks)
+    obj_start         int32, len(kept) + 1 offsets of the kept masks' slices of the pixel list
+    n_host_kept       how many kept masks are host masks
+    caller            the caller's instance indices that survive (an empty mask is dropped with its instances)
+    inst_obj          int32 index into kept, per surviving instance
+    inst_start        int32 point-list offsets, per surviving instance
+    n_fg, n_pts       foreground points, and points summed over the instances (equal without copies)
+    cap               correspondence rows per edit
+    with_table        the instance entries run, and the debug dict has corr_inst / inst_start
+    return_instances  every result carries the instance array
+    footprints, ratio the checked footprint settings (check_footprints)
+    edits             K lists of transforms after check_transform (as given where nothing moves)
+    cams              K cameras after check_camera / None, or None for a call without a camera
+    removed           the removed masks (check_removed_masks); removed_given: removed_masks was not None, so the debug dict has vacated
+    donor             (donor depth, donor masks) after check_donor, or None
+    inst              the instance table over the M + D masks (one instance per mask where the caller gave none)
+    masks_u8          [M + D, res * res] uint8, where the masks are
+    vacated           [res * res] bool union of the removed masks, or None
+    covered           camera calls: [res * res] bool, host masks and removed masks (bg_valid is its complement), or None"""
+    p = types.SimpleNamespace(kind=kind, entry=entry, workspace_query=workspace_query, N=0, kept=[], n_host_kept=0, caller=[],
+                              obj_start=np.zeros(1, dtype=np.int32), inst_obj=np.zeros(0, dtype=np.int32),
+                              inst_start=np.zeros(1, dtype=np.int32), n_fg=0, n_pts=0, cap=0, with_table=False, inst=None, masks_u8=None,
+                              vacated=None, covered=None)
+    vars(p).update(fields)
+    return p
 
 
-def reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
-                           donor_masks=None, use_input_depth_normalization=False, return_debug=False,
-                           device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
-                           cameras=None):
-    """`reproject_instance_edits` for an edit that also DELETES objects (not in the reference; DESIGN.md "Object removal"):
-    everything said there holds, and --
+def _removed_stats(removed, seen):
+    """Per removed mask its pixel count and whether it meets the union before it (`seen`, which it joins) -> (the 2 R values as
+    0-d int64 tensors for the caller's one device-to-host copy, `seen` with the removed masks in it)."""
+    extra = []
+    for mask in removed:
+        mr = (mask.detach() != 0).reshape(-1).to(seen.device)
+        extra += [mr.sum(), (mr & seen).any().to(torch.int64)]
+        seen = seen | mr
+    return extra, seen
 
-    removed_masks: None, or a list of R >= 0 [1,1,H,W] masks of the objects the edit deletes, pairwise disjoint from each other
-    and from fg_masks; bg_depth has them removed as well (that is its definition).  transforms, instances and everything else
-    speak about fg_masks as before.  A removed object contributes no point: the point list is the background pixels from
-    bg_depth, then the instances of fg_masks, so with M >= 1 every output is byte for byte the output of the call without
-    removed masks.  Empty removed masks are dropped; None, [] and all-empty masks are `reproject_instance_edits`.
-    Pure removal -- fg_masks empty (M = 0) and at least one non-empty removed mask: the edits are K empty transform lists, and
-    every one of the K results is the re-projection of the background ALONE (z-buffer over the H * W background points, in-fill
-    of the pixels no point owns, normalisation with the optional input bounds; computed once), with no correspondences and zero
-    masks.  That is not the empty-mask result (the normalised INPUT disparity, object included), which stays what it is.
-    ValueError before any device work of the library, naming the mask: a removed mask of another size, one that overlaps a
-    foreground mask or another removed mask, M = 0 without a non-empty removed mask, transforms or instances given for M = 0.
-    The debug dict gains vacated ([H, W] uint8 on the device: the union of the removed masks).
 
-    Object insertion (DESIGN.md "Object insertion") -- donor_depth, donor_masks: the [1,1,H,W] depth of a SECOND image of the
-    host's resolution and intrinsics, and D >= 1 pairwise disjoint masks of objects in it.  The edit's objects are then the
-    host's M masks (0 .. M - 1) followed by the donor's D masks (M .. M + D - 1), M + D <= 8: transforms and instances speak
-    about that list as they speak about fg_masks.  A donor object's points are the unprojection of donor_depth at its mask's
-    pixels, its centroid the sequential-f32 centroid of those points; a pivot is a point of the shared camera coordinates.  From
-    there on everything is shared (one z-buffer, masks, visibility, in-fill, normalisation).  Donor masks may overlap host
-    masks, removed masks and each other's image position freely -- they are pixels of another image.  M = 0 with a donor is the
-    pure insertion (bg_depth: the host depth, or the depth with the removed masks removed).  A row of a donor instance carries
-    its source pixel IN THE DONOR IMAGE; a donor call always returns the instance array (return_instances is implied), and "row
-    r is a donor row" means instances[corr_inst[r]] >= M.  The debug dict gains row_donor [K, capacity] uint8 (device).
-    No relative depth scale is estimated: the caller brings `scale`.  ValueError (check_donor) before any launch;
-    NotImplementedError for footprints with a donor (the pixel -> list-position inverse of the triangles is ambiguous when two
-    images share pixel indices).  No donor -- None, or donor masks that are all empty -- is the call without the keywords,
-    byte for byte, with the same launches.
+def _check_single_image(shape):
+    if len(shape) != 4 or shape[0] != 1:
+        raise ValueError("Only batch size 1 is supported")
 
-    Camera moves (DESIGN.md "Camera moves") -- cameras: None, or a list of K entries, one camera (`check_camera`) or None per
-    edit.  In an edit with a camera every point of the list, background included, is seen from the moved viewpoint: the points
-    that leave the frame are dropped (no clamp onto the border), the pixels no point reaches are in-filled (zero beyond the image
-    border: a known limit of the strip a move uncovers there), and the background yields correspondence rows of its own -- a
-    background pixel outside the host's foreground and removed masks whose point owns a target pixel outside the cleaned mask.
-    A camera call returns the instance array (return_instances is implied): the instance rows first, in the order they always
-    had, then the background rows in ascending source pixel order with instance index N (the number of instances).  An edit
-    without a camera in the same call is what it is in a call of its own, byte for byte, and has no background rows.  The pure
-    camera move is fg_masks = [] with K empty transform lists (bg_depth: the depth, or the depth with the removed masks
-    removed): every row is a background row.  The debug dict gains row_background (K uint8 tensors beside the returned rows: 1 =
-    a background row) and n_background (K ints), bg_corr and bg_counts.  ValueError (`check_camera`) naming the call and the
-    edit, NotImplementedError for footprints with a camera, both before any launch.  cameras=None, or all None, is the call
-    without the keyword, byte for byte, with the same launches.
-    """
-    what = "reproject_removal_edits"
+
+def _removed_fit_depth(removed, shape, what):
+    """A call without a foreground point takes its size from the first removed mask: the depth has to have it."""
+    res = removed[0].shape[-1]
+    if shape[-1] != res or shape[-2] != res:
+        raise ValueError(f"{what}: removed_masks: removed mask 0 is {res} x {res}, the depth {shape[-1]} x {shape[-2]}")
+    return res
+
+
+def _plan_pure_camera(shape, removed):
+    """The checks of a camera call without a foreground point -> (res, the union of the removed masks or None)."""
+    what = "reproject_camera_edits"
+    _check_single_image(shape)
+    res = int(shape[-1])
+    if shape[-2] != res:
+        raise RuntimeError("square depth maps only")
+    for r, mask in enumerate(removed):
+        if mask.shape[-1] != res:
+            raise ValueError(f"{what}: removed_masks: removed mask {r} is {mask.shape[-1]} x {mask.shape[-2]}, the depth {res} x {res}")
+    if not removed:
+        return res, None
+    removed_overlap(removed, [], f"{what}: removed_masks")
+    return res, _removed_stats(removed, torch.zeros(res * res, dtype=torch.bool, device=removed[0].device))[1]
+
+
+def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None, donor_depth=None, donor_masks=None, cameras=None,
+                   footprints=False, footprint_max_ratio=None, return_instances=False, what=None):
+    """Everything `reproject` decides before it touches the compute device -> the record of `_plan`.  depth: the depth or its shape; the
+    other arguments are `reproject`'s.  Every host check of the call (ValueError / NotImplementedError / RuntimeError with the
+    texts the named functions always had; `what` is the caller's name in the two refusals of a call without a foreground mask)
+    and the ONE device-to-host copy of the masks' statistics (pixel counts, overlap flags; none for host masks; `check_donor`
+    reads the donor's masks in a copy of its own).  No call of the library, no compute device, no allocation there: CPU masks
+    on a machine without a GPU give the same plan."""
+    shape = tuple(getattr(depth, "shape", depth))
+    removal = "reproject_removal_edits"
     footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
     fg_masks = list(fg_masks)
     edits = [list(tfs) for tfs in edits]
@@ -555,32 +506,45 @@ def reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instanc
         if footprints:
             raise NotImplementedError("reproject_camera_edits: footprints with a camera are not supported (depth_transform_footprints)")
         return_instances = True
-    removed = check_removed_masks(removed_masks, fg_masks, f"{what}: removed_masks")
+    removed = check_removed_masks(removed_masks, fg_masks, f"{removal}: removed_masks")
     M = len(fg_masks)
     donor = None
     if donor_depth is not None or donor_masks is not None:
-        donor = check_donor(donor_depth, donor_masks, depth.shape[-1], M, "reproject_donor_edits")
+        donor = check_donor(donor_depth, donor_masks, shape[-1], M, "reproject_donor_edits")
     if donor is not None:
         if footprints:
             raise NotImplementedError("reproject_donor_edits: footprints with a donor are not supported (depth_transform_footprints; "
                                       "two images share pixel indices)")
-        if fg_masks and fg_masks[0].shape[-1] != depth.shape[-1]:
+        if fg_masks and fg_masks[0].shape[-1] != shape[-1]:
             raise ValueError("reproject_donor_edits: donor: the foreground masks and the depth differ in size")
         return_instances = True
     donor_list = [] if donor is None else donor[1]
     D = len(donor_list)
+    common = dict(M=M, D=D, return_instances=bool(return_instances), footprints=footprints, ratio=ratio, cams=cams, removed=removed,
+                  removed_given=removed_masks is not None, donor=donor)
+    background = ("dh_reproject_background", "dh_reproject_background_workspace_bytes")
+    camera_background = ("dh_reproject_camera_background", "dh_reproject_background_workspace_bytes")
     if M == 0 and (removed or cams is not None) and donor is None:
         for e, tfs in enumerate(edits):
             if len(tfs) != 0:
-                raise ValueError(f"{what}: edit {e} has {len(tfs)} transforms, but there is no foreground mask (a pure removal "
-                                 f"moves nothing)")
+                raise ValueError(f"{what or removal}: edit {e} has {len(tfs)} transforms, but there is no foreground mask (a pure "
+                                 f"removal moves nothing)")
         if instances is not None and len(list(instances)) != 0:
-            raise ValueError(f"{what}: instances={instances!r} given without a foreground mask (a pure removal has no instance)")
+            raise ValueError(f"{what or removal}: instances={instances!r} given without a foreground mask (a pure removal has no "
+                             f"instance)")
         if cams is not None:
-            return _reproject_pure_camera(depth, bg_depth, removed, intrinsics, cams, use_input_depth_normalization, return_debug,
-                                          device_correspondences)
-        return _reproject_pure_removal(depth, bg_depth, removed, intrinsics, len(edits), use_input_depth_normalization,
-                                       return_debug, device_correspondences, return_instances, instances is not None)
+            res, covered = _plan_pure_camera(shape, removed)
+            return _plan("pure_camera", *camera_background, res=res, edits=edits, covered=covered, **common)
+        _check_single_image(shape)
+        res = _removed_fit_depth(removed, shape, removal)
+        extra, vacated = _removed_stats(removed, torch.zeros(res * res, dtype=torch.bool, device=removed[0].device))
+        tail = torch.stack(extra).tolist()          # the one device-to-host copy of this call
+        if any(tail[1::2]):
+            removed_overlap(removed, [], f"{removal}: removed_masks")
+        if sum(tail[0::2]) == 0:
+            raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got 0")
+        return _plan("pure_removal", *background, res=res, edits=edits, with_table=instances is not None, vacated=vacated,
+                             **common)
     if not 1 <= M <= MAX_OBJECTS and donor is None:
         raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got {M}")
     # (with a donor the table names every mask of the concatenated list: the host's M, then the donor's D)
@@ -602,9 +566,8 @@ def reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instanc
             raise RuntimeError(f"Expected fg_mask to be square, got shape {fg_mask.shape[-2]} x {fg_mask.shape[-1]}.")
         if fg_mask.shape[-1] != fg_masks[0].shape[-1]:
             raise ValueError("Expected all foreground masks to have one size")
-    if depth.dim() != 4 or depth.shape[0] != 1:
-        raise ValueError("Only batch size 1 is supported")
-    res = fg_masks[0].shape[-1] if M else int(depth.shape[-1])
+    _check_single_image(shape)
+    res = fg_masks[0].shape[-1] if M else int(shape[-1])
     # the M pixel counts and the overlap flag: ONE device-to-host copy (none for host masks), before any launch of the library
     flat = [(fg_mask.detach() != 0).reshape(-1) for fg_mask in fg_masks]
     if donor is not None:          # the donor's masks behind the host's (they were checked, and are on the first mask's device)
@@ -614,324 +577,397 @@ def reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instanc
     if M > 1:
         stats = torch.cat([stats, (masks_u8[:M].sum(dim=0) > 1).any()[None].to(stats.dtype)])
     vacated = None
+    covered = masks_u8[:M].sum(dim=0) > 0 if removed or cams is not None else None
     if removed:
-        # the removed masks ride in the same copy: per mask its pixel count and whether it meets the union before it
-        seen = masks_u8[:M].sum(dim=0) > 0
-        vacated = torch.zeros_like(seen)
-        extra = []
-        for mask in removed:
-            mr = (mask.detach() != 0).reshape(-1).to(seen.device)
-            extra += [mr.sum().to(stats.dtype), (mr & seen).any().to(stats.dtype)]
-            seen = seen | mr
-            vacated = vacated | mr
+        # the removed masks ride in the same copy (they are disjoint from the foreground masks, or the call is refused below)
+        extra, everything = _removed_stats(removed, covered)
+        vacated, covered = everything & ~covered, everything
         stats = torch.cat([stats, torch.stack(extra)])
     stats = stats.tolist()
     if M > 1 and stats[M + D]:
         raise ValueError("The foreground masks overlap")
+    n_vacated = 0
     if removed:
         tail = stats[len(stats) - 2 * len(removed):]
         if any(tail[1::2]):
-            removed_overlap(removed, fg_masks, f"{what}: removed_masks")
-            raise ValueError(f"{what}: removed_masks: removed mask {tail[1::2].index(1)} overlaps another mask")
+            removed_overlap(removed, fg_masks, f"{removal}: removed_masks")
+            raise ValueError(f"{removal}: removed_masks: removed mask {tail[1::2].index(1)} overlaps another mask")
         n_vacated = sum(tail[0::2])
     kept = [m for m in range(M + D) if stats[m] > 0]
-    n_host_kept = sum(1 for m in kept if m < M)
     obj_start = np.zeros(len(kept) + 1, dtype=np.int32)
     obj_start[1:] = np.cumsum([stats[m] for m in kept])
     n_fg = int(obj_start[-1])
-    out_dev = depth.device
-    dev = _compute_device(depth)
-    L = _lib.lib()
-    st = _lib.stream_ptr()
-    d = depth.detach().to(dev, torch.float32).contiguous()
-    bg = bg_depth.detach().to(dev, torch.float32).contiguous()
-    masks_u8 = masks_u8.to(dev).contiguous()
-    K = len(edits)
-    bounds = None
-    if use_input_depth_normalization:
-        disp_in = 1.0 / d
-        bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
+    common.update(N=N, edits=edits, inst=inst, with_table=with_table, vacated=vacated)
     if n_fg == 0 and cams is not None:
         # every mask is empty (dropped with its transforms): the pure camera move
-        return _reproject_pure_camera(depth, bg_depth, removed, intrinsics, cams, use_input_depth_normalization, return_debug,
-                                      device_correspondences, N)
-    if n_fg == 0 and removed and n_vacated > 0:
+        res, covered = _plan_pure_camera(shape, removed)
+        return _plan("pure_camera", *camera_background, res=res, covered=covered, **common)
+    if n_fg == 0 and n_vacated > 0:
         # every foreground mask is empty (dropped with its transforms) and an object is deleted: the pure removal
-        return _reproject_pure_removal(depth, bg_depth, removed, intrinsics, len(edits), use_input_depth_normalization,
-                                       return_debug, device_correspondences, return_instances, with_table)
+        _removed_fit_depth(removed, shape, removal)
+        return _plan("pure_removal", *background, res=res, **common)
     if n_fg == 0:
-        # empty foreground: the input disparity and no correspondences (depth_transform.py:203-216)
-        lo_hi = None if bounds is None else (bounds[0], bounds[1])
-        disp = normalize_depth(1.0 / d, bounds=lo_hi).to(out_dev)
-        empty = torch.zeros((0, 4), dtype=torch.int64)
-        res_list = [(disp, empty) + ((torch.zeros(0, dtype=torch.uint8),) if return_instances else ()) for _ in range(K)]
-        if return_debug:
-            return res_list, ({} if removed_masks is None else dict(vacated=_vacated_u8(vacated, res, dev)))
-        return res_list
-
-    gx, gy = _grids(res, res, dev)
-    ifx, ify = _inv_focal(intrinsics)
-    kcpu = intrinsics.detach().to("cpu", torch.float32)
-    fx, fy = float(kcpu[0, 0]), float(kcpu[1, 1])
-    R2 = res * res
-    Mk = len(kept)
-    fg_pix = torch.empty(max(R2, n_fg), dtype=torch.int32, device=dev)      # (beyond R2 only with a donor: its pixels are another image's)
-    n_dev = torch.zeros(Mk, dtype=torch.int32, device=dev)
-    ws_small = torch.empty(4096, dtype=torch.uint8, device=dev)
-    for j, m in enumerate(kept):              # disjoint masks: the slices fill fg_pix[0 .. n_fg), n_fg <= R2
-        _lib.check(L.dh_fg_pixel_list(_lib.ptr(masks_u8[m]), res, _lib.ptr(fg_pix[int(obj_start[j]):]), _lib.ptr(n_dev[j:]),
-                                      _lib.ptr(ws_small), ws_small.numel(), st), "dh_fg_pixel_list")
+        return _plan("empty", res=res, **common)
     # the instances of the kept masks (empty masks are dropped with all of their instances); caller[n'] = the caller's index
     caller = [n for n in range(N) if inst[n] in kept]
     inst_obj = np.asarray([kept.index(inst[n]) for n in caller], dtype=np.int32)
-    Nk = len(caller)
-    sizes = [int(obj_start[o + 1] - obj_start[o]) for o in inst_obj]
-    inst_start = np.zeros(Nk + 1, dtype=np.int32)
-    inst_start[1:] = np.cumsum(sizes)
+    inst_start = np.zeros(len(caller) + 1, dtype=np.int32)
+    inst_start[1:] = np.cumsum([int(obj_start[o + 1] - obj_start[o]) for o in inst_obj])
     n_pts = int(inst_start[-1])                # = n_fg without copies
-    nbytes = ctypes.c_size_t()
     if cams is not None:
-        _lib.check(L.dh_reproject_camera_workspace_bytes(res, n_pts, K, Mk, Nk, 0, ctypes.byref(nbytes)),
-                   "dh_reproject_camera_workspace_bytes")
-    elif with_table:
-        _lib.check(L.dh_reproject_instances_workspace_bytes(res, n_pts, K, Mk, Nk, int(footprints), ctypes.byref(nbytes)),
-                   "dh_reproject_instances_workspace_bytes")
+        entry, query = "dh_reproject_camera_edits", "dh_reproject_camera_workspace_bytes"
+    elif with_table:          # (a donor call sizes its workspace as the instance call it extends)
+        entry = "dh_reproject_instance_edits" if donor is None else "dh_reproject_donor_edits"
+        query = "dh_reproject_instances_workspace_bytes"
     else:
-        _lib.check(L.dh_reproject_footprints_workspace_bytes(res, n_fg, K, Mk, int(footprints), ctypes.byref(nbytes)),
-                   "dh_reproject_footprints_workspace_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        entry, query = "dh_reproject_footprint_edits", "dh_reproject_footprints_workspace_bytes"
+    return _plan("objects", entry, query, res=res, kept=kept, obj_start=obj_start, n_host_kept=sum(1 for m in kept if m < M),
+                         caller=caller, inst_obj=inst_obj, inst_start=inst_start, n_fg=n_fg, n_pts=n_pts,
+                         cap=res * res if footprints else n_pts,          # one row per target pixel with footprints, per point without
+                         masks_u8=masks_u8, covered=covered if cams is not None else None, **common)
+
+
+def _run_plan(p, depth, bg_depth, intrinsics, use_input_depth_normalization, return_debug, device_correspondences):
+    """The one place a re-projection allocates and launches: the geometry set-up every kind shares, then what the plan names."""
+    g = types.SimpleNamespace(out_dev=depth.device, dev=_compute_device(depth), L=_lib.lib(), st=_lib.stream_ptr(), res=p.res,
+                              K=len(p.edits), return_debug=return_debug, on_device=device_correspondences)
+    d = depth.detach().to(g.dev, torch.float32).contiguous()
+    g.d, g.bg = d, bg_depth.detach().to(g.dev, torch.float32).contiguous()
+    g.bounds = None
+    if use_input_depth_normalization:
+        disp_in = 1.0 / d
+        g.bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
+    if p.kind == "empty":
+        # empty foreground: the input disparity and no correspondences (depth_transform.py:203-216)
+        lo_hi = None if g.bounds is None else (g.bounds[0], g.bounds[1])
+        disp = normalize_depth(1.0 / d, bounds=lo_hi).to(g.out_dev)
+        empty = torch.zeros((0, 4), dtype=torch.int64)
+        res_list = [(disp, empty) + ((torch.zeros(0, dtype=torch.uint8),) if p.return_instances else ()) for _ in range(g.K)]
+        return (res_list, dict(vacated=_vacated_u8(p, g)) if p.removed_given else {}) if return_debug else res_list
+    g.gx, g.gy = _grids(g.res, g.res, g.dev)
+    g.ifx, g.ify = _inv_focal(intrinsics)
+    kcpu = intrinsics.detach().to("cpu", torch.float32)
+    g.fx, g.fy = float(kcpu[0, 0]), float(kcpu[1, 1])
+    return _run_objects(p, g) if p.kind == "objects" else _run_background(p, g)
+
+
+def _workspace(p, g):
+    """The workspace of the plan's entry, sized by the query the plan names."""
+    if p.kind != "objects":
+        sizes = (g.res,)
+    elif p.with_table:
+        sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), int(p.footprints))
+    else:
+        sizes = (g.res, p.n_fg, g.K, len(p.kept), int(p.footprints))
+    nbytes = ctypes.c_size_t()
+    _lib.check(getattr(g.L, p.workspace_query)(*sizes, ctypes.byref(nbytes)), p.workspace_query)
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=g.dev), nbytes.value
+
+
+def _vacated_u8(p, g):
+    if p.vacated is None:
+        return torch.zeros((g.res, g.res), dtype=torch.uint8, device=g.dev)
+    return p.vacated.to(g.dev).reshape(g.res, g.res).to(torch.uint8)
+
+
+def _empty_debug(g, table):
+    """The debug tensors of a call without a foreground point (`table`: the instance members too)."""
+    K, res, dev = g.K, g.res, g.dev
+    zeros = torch.zeros((K, res, res), dtype=torch.uint8, device=dev)
+    dbg = dict(raw_mask=zeros, clean_mask=zeros.clone(), vis=torch.zeros((K, 0), dtype=torch.uint8, device=dev),
+               target_xy=torch.zeros((K, 0, 2), dtype=torch.int32, device=dev), fg_pix=torch.zeros(0, dtype=torch.int32, device=dev),
+               corr_dev=torch.zeros((K, 0, 4), dtype=torch.int64, device=dev), obj_start=np.zeros(1, dtype=np.int32))
+    if table:
+        dbg.update(corr_inst=torch.zeros((K, 0), dtype=torch.uint8, device=dev), inst_start=np.zeros(1, dtype=np.int32))
+    return dbg
+
+
+def _view_ptr(view):
+    return None if view is None else view.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _run_background(p, g):
+    """The kinds without a foreground point.  "pure_removal": dh_reproject_background once, its result K times.  "pure_camera":
+    dh_reproject_camera_background once per edit, with the edit's view (an edit without a camera: without a view, the pure
+    removal's result); every row is a background row, instance index N."""
+    camera = p.kind == "pure_camera"
+    dev, res, K = g.dev, g.res, g.K
+    views = [None if c is None else view_row(c) for c in p.cams] if camera else [None]
+    n = len(views)
+    ws, ws_bytes = _workspace(p, g)
+    zmap = torch.empty((n, res, res), dtype=torch.float32, device=dev)
+    disp = torch.empty((n, res, res), dtype=torch.float32, device=dev)
+    counts = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    if camera:
+        covered = torch.zeros(res * res, dtype=torch.bool, device=dev) if p.covered is None else p.covered.to(dev)
+        bg_valid = (~covered).to(torch.uint8).contiguous()
+        bg_corr = torch.empty((K, res * res, 4), dtype=torch.int64, device=dev)
+        bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
+    for e, view in enumerate(views):
+        args = (_lib.ptr(g.bg), res, _lib.ptr(g.gx), _lib.ptr(g.gy), g.ifx, g.ify, g.fx, g.fy, _lib.ptr(g.bounds), _lib.ptr(zmap[e]),
+                _lib.ptr(disp[e]), _lib.ptr(counts[e]), _lib.ptr(ws), ws_bytes, g.st)
+        if camera:
+            args += (_view_ptr(view), _lib.ptr(bg_valid), _lib.ptr(bg_corr[e]), _lib.ptr(bg_counts[e:]))
+        _lib.check(getattr(g.L, p.entry)(*args), p.entry)
+    counts_h = counts.cpu()
+    _check_infill(counts_h[:, 3])
+    placed = (lambda t: t) if g.on_device else (lambda t: t.cpu())
+    if camera:
+        bg_h = bg_counts.cpu().tolist()
+        out = [(disp[e][None, None].to(g.out_dev), placed(bg_corr[e, :nb]), placed(torch.full((nb,), p.N, dtype=torch.uint8, device=dev)))
+               for e, nb in enumerate(bg_h)]
+    else:
+        empty = torch.zeros((0, 4), dtype=torch.int64, device=dev if g.on_device else "cpu")
+        no_inst = torch.zeros(0, dtype=torch.uint8, device=empty.device)
+        out = [(disp[None].to(g.out_dev), empty) + ((no_inst,) if p.return_instances else ())] * K
+    if not g.return_debug:
+        return out
+    dbg = _empty_debug(g, camera or p.with_table or p.return_instances)
+    if camera:
+        dbg.update(zmap=zmap, counts=counts_h, vacated=covered.reshape(res, res).to(torch.uint8),
+                   row_background=[torch.ones(nb, dtype=torch.uint8, device=dev) for nb in bg_h], n_background=[int(v) for v in bg_h],
+                   bg_corr=bg_corr, bg_counts=bg_counts, bg_valid=bg_valid)
+    else:
+        dbg.update(zmap=zmap.expand(K, -1, -1), counts=counts_h.expand(K, -1).contiguous(), vacated=_vacated_u8(p, g))
+    return out, dbg
+
+
+def _run_objects(p, g):
+    """The kind with foreground points: the pixel lists of the kept masks, the buffers, the entry the plan names (each of
+    dh_reproject_footprint_edits, _instance_edits, _donor_edits and _camera_edits takes the arguments of the one before it and a
+    few more), then the results and the debug dict."""
+    dev, res, K, L = g.dev, g.res, g.K, g.L
+    R2, Mk, Nk, n_fg, n_pts, cap = res * res, len(p.kept), len(p.caller), p.n_fg, p.n_pts, p.cap
+    camera, donor = p.cams is not None, p.donor is not None
+    masks_u8 = p.masks_u8.to(dev).contiguous()
+    obj_start, inst_start = p.obj_start, p.inst_start
+    fg_pix = torch.empty(max(R2, n_fg), dtype=torch.int32, device=dev)      # (beyond R2 only with a donor: its pixels are another image's)
+    n_dev = torch.zeros(Mk, dtype=torch.int32, device=dev)
+    ws_small = torch.empty(4096, dtype=torch.uint8, device=dev)
+    for j, m in enumerate(p.kept):              # disjoint masks: the slices fill fg_pix[0 .. n_fg), n_fg <= R2
+        _lib.check(L.dh_fg_pixel_list(_lib.ptr(masks_u8[m]), res, _lib.ptr(fg_pix[int(obj_start[j]):]), _lib.ptr(n_dev[j:]),
+                                      _lib.ptr(ws_small), ws_small.numel(), g.st), "dh_fg_pixel_list")
+    ws, ws_bytes = _workspace(p, g)
     zmap = torch.empty((K, res, res), dtype=torch.float32, device=dev)
     raw = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
     clean = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
     disp = torch.empty((K, res, res), dtype=torch.float32, device=dev)
     vis = torch.empty((K, n_pts), dtype=torch.uint8, device=dev)
     txy = torch.empty((K, n_pts, 2), dtype=torch.int32, device=dev)
-    cap = R2 if footprints else n_pts         # rows per edit: one per target pixel with footprints, one per point without
     corr = torch.empty((K, cap, 4), dtype=torch.int64, device=dev)
     counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
-    rows = _similarity_rows([tfs[n] for tfs in edits for n in caller])    # edit-major, K x Nk rows (C-contiguous)
-    args = (_lib.ptr(d), _lib.ptr(bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
-            _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, K,
-            rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bounds),
+    rows = _similarity_rows([tfs[n] for tfs in p.edits for n in p.caller])    # edit-major, K x Nk rows (C-contiguous)
+    args = (_lib.ptr(g.d), _lib.ptr(g.bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
+            _lib.ptr(g.gx), _lib.ptr(g.gy), g.ifx, g.ify, g.fx, g.fy, K,
+            rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(g.bounds),
             _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
-            _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st, int(footprints), 0.0 if ratio is None else ratio, cap)
+            _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), ws_bytes, g.st, int(p.footprints), 0.0 if p.ratio is None else p.ratio, cap)
     corr_inst = None
-    row_donor = None
-    if with_table:
+    if p.with_table:
         corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
-        if cams is not None:
-            # the view rows (host), the pixels that show the background (the union of the host's masks and the removed masks is
-            # in-painted in bg_depth), and the background rows' buffers
-            views = np.zeros((K, SIMILARITY_ROW), dtype=np.float64)
-            has_view = np.zeros(K, dtype=np.uint8)
-            for e, c in enumerate(cams):
-                if c is not None:
-                    views[e], has_view[e] = view_row(c), 1
-            covered = masks_u8[:M].sum(dim=0) > 0
-            if vacated is not None:
-                covered = covered | vacated.to(dev)
-            bg_valid = (~covered).to(torch.uint8).contiguous()
-            bg_corr = torch.empty((K, R2, 4), dtype=torch.int64, device=dev)
-            bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
-            dd = None if donor is None else donor[0].detach().to(dev, torch.float32).contiguous()
-            _lib.check(L.dh_reproject_camera_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                   _lib.ptr(corr_inst), _lib.ptr(dd), n_host_kept,
-                                                   views.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                   has_view.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _lib.ptr(bg_valid),
-                                                   _lib.ptr(bg_corr), _lib.ptr(bg_counts)), "dh_reproject_camera_edits")
-            if donor is not None:
-                flags = torch.zeros(256, dtype=torch.uint8)
-                flags[:Nk] = torch.tensor([1 if inst[n] >= M else 0 for n in caller], dtype=torch.uint8)
-                row_donor = flags.to(dev)[corr_inst.long()]
-        elif donor is not None:
-            dd = donor[0].detach().to(dev, torch.float32).contiguous()
-            _lib.check(L.dh_reproject_donor_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                  _lib.ptr(corr_inst), _lib.ptr(dd), n_host_kept), "dh_reproject_donor_edits")
-            # one byte per row: whether the row's instance draws a donor mask (256 entries: rows past the counts are not written)
-            flags = torch.zeros(256, dtype=torch.uint8)
-            flags[:Nk] = torch.tensor([1 if inst[n] >= M else 0 for n in caller], dtype=torch.uint8)
-            row_donor = flags.to(dev)[corr_inst.long()]
-        else:
-            _lib.check(L.dh_reproject_instance_edits(*args, Nk, inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                                     _lib.ptr(corr_inst)), "dh_reproject_instance_edits")
-        if caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
-            lut = torch.zeros(256, dtype=torch.uint8)          # (256 entries: the rows past the counts are not written)
-            lut[:Nk] = torch.tensor(caller, dtype=torch.uint8)
-            corr_inst = lut.to(dev)[corr_inst.long()]
-    else:
-        _lib.check(L.dh_reproject_footprint_edits(*args), "dh_reproject_footprint_edits")
+        args += (Nk, p.inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _lib.ptr(corr_inst))
+    if camera or donor:
+        dd = p.donor[0].detach().to(dev, torch.float32).contiguous() if donor else None
+        args += (_lib.ptr(dd), p.n_host_kept)
+    if camera:
+        # the view rows (host), the pixels that show the background (the union of the host's masks and the removed masks is
+        # in-painted in bg_depth), and the background rows' buffers
+        views = np.zeros((K, SIMILARITY_ROW), dtype=np.float64)
+        has_view = np.zeros(K, dtype=np.uint8)
+        for e, c in enumerate(p.cams):
+            if c is not None:
+                views[e], has_view[e] = view_row(c), 1
+        bg_valid = (~p.covered.to(dev)).to(torch.uint8).contiguous()
+        bg_corr = torch.empty((K, R2, 4), dtype=torch.int64, device=dev)
+        bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
+        args += (_view_ptr(views), has_view.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _lib.ptr(bg_valid), _lib.ptr(bg_corr),
+                 _lib.ptr(bg_counts))
+    _lib.check(getattr(L, p.entry)(*args), p.entry)
+    row_donor = donor_rows(corr_inst, [p.inst[n] for n in p.caller], p.M) if donor else None
+    if p.with_table and p.caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
+        lut = torch.zeros(256, dtype=torch.uint8)          # (256 entries: the rows past the counts are not written)
+        lut[:Nk] = torch.tensor(p.caller, dtype=torch.uint8)
+        corr_inst = lut.to(dev)[corr_inst.long()]
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
     out = []
-    bg_h = bg_counts.cpu().tolist() if cams is not None else None
+    bg_h = bg_counts.cpu().tolist() if camera else None
     row_background = []
+    placed = (lambda t: t) if g.on_device else (lambda t: t.cpu())
     for e in range(K):
         n = int(counts_h[e, 0])
-        rows_e, inst_e = corr[e, :n], (corr_inst[e, :n] if return_instances else None)
-        if cams is not None:
+        rows_e, inst_e = corr[e, :n], (corr_inst[e, :n] if p.return_instances else None)
+        if camera:
             # the background rows behind the instance rows, instance index N
             nb = int(bg_h[e])
             rows_e = torch.cat([rows_e, bg_corr[e, :nb]])
-            inst_e = torch.cat([inst_e, torch.full((nb,), N, dtype=torch.uint8, device=dev)])
+            inst_e = torch.cat([inst_e, torch.full((nb,), p.N, dtype=torch.uint8, device=dev)])
             row_background.append(torch.cat([torch.zeros(n, dtype=torch.uint8, device=dev), torch.ones(nb, dtype=torch.uint8, device=dev)]))
-        item = (disp[e][None, None].to(out_dev), rows_e if device_correspondences else rows_e.cpu())
-        if return_instances:
-            item += (inst_e if device_correspondences else inst_e.cpu(),)
-        out.append(item)
-    if return_debug:
-        dbg = dict(zmap=zmap, raw_mask=raw, clean_mask=clean, vis=vis, target_xy=txy, counts=counts_h,
-                   fg_pix=fg_pix[:n_fg], corr_dev=corr, obj_start=obj_start)
-        if with_table:
-            dbg.update(corr_inst=corr_inst, inst_start=inst_start)
-        if removed_masks is not None:
-            dbg.update(vacated=_vacated_u8(vacated, res, dev))
-        if row_donor is not None:
-            dbg.update(row_donor=row_donor)
-        if cams is not None:
-            dbg.update(row_background=row_background, n_background=[int(v) for v in bg_h], bg_corr=bg_corr, bg_counts=bg_counts,
-                       bg_valid=bg_valid)
-        return out, dbg
-    return out
-
-
-def _reproject_pure_camera(depth, bg_depth, removed, intrinsics, cams, use_input_depth_normalization, return_debug,
-                           device_correspondences, N=0):
-    """The pure camera move of `reproject_camera_edits`: dh_reproject_camera_background once per edit, with the edit's view (an
-    edit without a camera: without a view, the pure removal's result).  Every row is a background row, instance index N."""
-    what = "reproject_camera_edits"
-    if depth.dim() != 4 or depth.shape[0] != 1:
-        raise ValueError("Only batch size 1 is supported")
-    res = int(depth.shape[-1])
-    if depth.shape[-2] != res:
-        raise RuntimeError("square depth maps only")
-    for r, mask in enumerate(removed):
-        if mask.shape[-1] != res:
-            raise ValueError(f"{what}: removed_masks: removed mask {r} is {mask.shape[-1]} x {mask.shape[-2]}, the depth {res} x {res}")
-    if removed:
-        removed_overlap(removed, [], f"{what}: removed_masks")
-    out_dev = depth.device
-    dev = _compute_device(depth)
-    L = _lib.lib()
-    st = _lib.stream_ptr()
-    bg = bg_depth.detach().to(dev, torch.float32).contiguous()
-    bounds = None
-    if use_input_depth_normalization:
-        disp_in = 1.0 / depth.detach().to(dev, torch.float32)
-        bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
-    gx, gy = _grids(res, res, dev)
-    ifx, ify = _inv_focal(intrinsics)
-    kcpu = intrinsics.detach().to("cpu", torch.float32)
-    fx, fy = float(kcpu[0, 0]), float(kcpu[1, 1])
-    covered = torch.zeros(res * res, dtype=torch.bool, device=dev)
-    for mask in removed:
-        covered |= (mask.detach() != 0).reshape(-1).to(dev)
-    bg_valid = (~covered).to(torch.uint8).contiguous()
-    K, R2 = len(cams), res * res
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.dh_reproject_background_workspace_bytes(res, ctypes.byref(nbytes)), "dh_reproject_background_workspace_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-    zmap = torch.empty((K, res, res), dtype=torch.float32, device=dev)
-    disp = torch.empty((K, res, res), dtype=torch.float32, device=dev)
-    counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
-    bg_corr = torch.empty((K, R2, 4), dtype=torch.int64, device=dev)
-    bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
-    for e, c in enumerate(cams):
-        view = None if c is None else view_row(c)
-        _lib.check(L.dh_reproject_camera_background(
-            _lib.ptr(bg), res, _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, _lib.ptr(bounds), _lib.ptr(zmap[e]), _lib.ptr(disp[e]),
-            _lib.ptr(counts[e]), _lib.ptr(ws), nbytes.value, st,
-            None if view is None else view.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(bg_valid), _lib.ptr(bg_corr[e]),
-            _lib.ptr(bg_counts[e:])), "dh_reproject_camera_background")
-    counts_h = counts.cpu()
-    _check_infill(counts_h[:, 3])
-    bg_h = bg_counts.cpu().tolist()
-    out, row_background = [], []
-    for e in range(K):
-        nb = int(bg_h[e])
-        rows_e = bg_corr[e, :nb]
-        inst_e = torch.full((nb,), N, dtype=torch.uint8, device=dev)
-        out.append((disp[e][None, None].to(out_dev), rows_e if device_correspondences else rows_e.cpu(),
-                    inst_e if device_correspondences else inst_e.cpu()))
-        row_background.append(torch.ones(nb, dtype=torch.uint8, device=dev))
-    if not return_debug:
+        out.append((disp[e][None, None].to(g.out_dev), placed(rows_e)) + ((placed(inst_e),) if p.return_instances else ()))
+    if not g.return_debug:
         return out
-    zeros = torch.zeros((K, res, res), dtype=torch.uint8, device=dev)
-    dbg = dict(zmap=zmap, raw_mask=zeros, clean_mask=zeros.clone(), vis=torch.zeros((K, 0), dtype=torch.uint8, device=dev),
-               target_xy=torch.zeros((K, 0, 2), dtype=torch.int32, device=dev), counts=counts_h,
-               fg_pix=torch.zeros(0, dtype=torch.int32, device=dev), corr_dev=torch.zeros((K, 0, 4), dtype=torch.int64, device=dev),
-               obj_start=np.zeros(1, dtype=np.int32), vacated=covered.reshape(res, res).to(torch.uint8),
-               corr_inst=torch.zeros((K, 0), dtype=torch.uint8, device=dev), inst_start=np.zeros(1, dtype=np.int32),
-               row_background=row_background, n_background=[int(v) for v in bg_h], bg_corr=bg_corr, bg_counts=bg_counts,
-               bg_valid=bg_valid)
+    dbg = dict(zmap=zmap, raw_mask=raw, clean_mask=clean, vis=vis, target_xy=txy, counts=counts_h,
+               fg_pix=fg_pix[:n_fg], corr_dev=corr, obj_start=obj_start)
+    if p.with_table:
+        dbg.update(corr_inst=corr_inst, inst_start=inst_start)
+    if p.removed_given:
+        dbg.update(vacated=_vacated_u8(p, g))
+    if row_donor is not None:
+        dbg.update(row_donor=row_donor)
+    if camera:
+        dbg.update(row_background=row_background, n_background=[int(v) for v in bg_h], bg_corr=bg_corr, bg_counts=bg_counts,
+                   bg_valid=bg_valid)
     return out, dbg
 
 
-def _vacated_u8(vacated, res, dev):
-    if vacated is None:
-        return torch.zeros((res, res), dtype=torch.uint8, device=dev)
-    return vacated.to(dev).reshape(res, res).to(torch.uint8)
+def reproject(depth, bg_depth, fg_masks, intrinsics, edits, *, instances=None, removed_masks=None, donor_depth=None,
+              donor_masks=None, cameras=None, use_input_depth_normalization=False, return_debug=False,
+              device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False, what=None):
+    """K edits of one image (not in the reference, which has the one-object, one-edit call): `reproject_plan` decides on the
+    host, `_run_plan` allocates and launches.  The named functions below are this call with fewer keywords.
+
+    Objects.  fg_masks: M pairwise disjoint [1,1,H,W] masks (1 <= M <= 8); bg_depth: the depth with ALL objects removed; edits: K
+    lists of M (rot_angle_deg, rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one
+    per mask.  Object m turns about the centroid of its own masked points, then moves.  With a 5-tuple it is first scaled --
+    scale: None (= 1), one positive float or three (sx, sy, sz) along the camera axes of `depth_to_world_coords`, applied to the
+    offsets from the pivot BEFORE the rotation, so a non-uniform scale of a turned object stretches along the un-turned camera
+    axes -- and pivot (None = the centroid; else a point in the coordinates `depth_to_world_coords` returns, see
+    `pivot_at_pixel`) replaces the centroid for the scale and the turn.  Scale 1 with pivot None is the 3-tuple's result bit for
+    bit.  A magnified object leaves gaps between its points; the mask CLOSE bridges them only up to its element, res // 50 (as
+    when an object moves towards the camera).  The point list is the background pixels, then the points of object 0 in row-major
+    order, then object 1, ...: one z-buffer over all of it, so the objects occlude the background and each other, and equal
+    depths go to the earlier object.  Mask clean-up, correspondence filter, in-fill and normalisation see the union.  Empty masks
+    are dropped (with their transforms); all empty = the empty-mask result, the normalised input disparity without
+    correspondences.  ValueError for overlapping masks, M > 8, an edit that does not have M transforms, and, naming the edit and
+    the object, for a malformed transform (check_transform).
+
+    Returns a list of K (disparity [1,1,H,W] f32 on depth.device, correspondences [R,4] int64 (ox, oy, tx, ty) on the CPU, in
+    point-list order), plus a dict of the intermediate device tensors when return_debug is set (obj_start: the M' + 1 offsets of
+    the kept objects' slices in fg_pix / vis / target_xy).  The reference hands the correspondences over as a CPU tensor
+    (depth_transform.py:339-343) and so does `transform_depth`; device_correspondences=True leaves them where the kernels wrote
+    them, for callers that feed them straight back to the device (the batched edit path: `process_correspondences` accepts
+    either) -- K device-to-host copies and K uploads less per call.
+
+    Footprints (footprint splatting) -- footprints=True: the triangles between neighbouring points of ONE object (of
+    one instance) bid in the z-buffer too, so an enlarged or approaching object has no gaps between its points.  The
+    correspondences are then one row per foreground-owned target pixel inside the cleaned mask -- (ox, oy) of the owning point,
+    (tx, ty) of the pixel -- in ROW-MAJOR TARGET order, and there may be more of them than foreground points (at most H * W).
+    footprint_max_ratio: None or a finite float > 1; a triangle whose source depths differ by more than this factor is left out
+    (no sheets across a depth step inside one mask).  ValueError for a bad ratio or a ratio without footprints.
+
+    Copies (DESIGN.md "Object copies") -- instances: None, or a list of N mask indices, M <= N <= 8, naming every mask at least
+    once.  Instance n draws the points of mask instances[n] with transform n of every edit (the edits are then K lists of N
+    transforms), about the centroid of that mask (computed once per mask) or its pivot.  The point list is the background, then
+    instance 0's points, instance 1's, ...: one z-buffer, equal depths to the earlier instance; a source pixel has one row per
+    visible, kept instance.  One table serves all K edits.  ValueError naming the instance (or the edit) for a bad table or an
+    edit that does not have N transforms.  The debug dict gains corr_inst [K, capacity] uint8 (the caller's instance index of
+    every correspondence row) and inst_start (the offsets of the kept instances' slices in vis / target_xy); instances=None is
+    the call without the table, byte for byte.  return_instances=True: every result is (disparity, correspondences [R,4],
+    instances [R] uint8 beside them); without an instance table the instance of a row is the index of its mask.
+
+    Removal (DESIGN.md "Object removal") -- removed_masks: None, or a list of R >= 0 [1,1,H,W] masks of the objects the edit
+    deletes, pairwise disjoint from each other and from fg_masks; bg_depth has them removed as well (that is its definition).
+    A removed object contributes no point, so with M >= 1 every output is byte for byte the output of the call without removed
+    masks.  Empty removed masks are dropped; None, [] and all-empty masks are the call without the keyword.  Pure removal --
+    fg_masks empty (M = 0) and at least one non-empty removed mask: the edits are K empty transform lists, and every one of the K
+    results is the re-projection of the background ALONE (z-buffer over the H * W background points, in-fill of the pixels no
+    point owns, normalisation with the optional input bounds; computed once), with no correspondences and zero masks.  That is
+    not the empty-mask result (the normalised INPUT disparity, object included), which stays what it is.  ValueError naming the
+    mask: a removed mask of another size, one that overlaps a foreground mask or another removed mask, M = 0 without a
+    non-empty removed mask, transforms or instances given for M = 0 (`what`: the caller's name in these two).  The debug dict
+    gains vacated ([H, W] uint8 on the device: the union of the removed masks).
+
+    Insertion (DESIGN.md "Object insertion") -- donor_depth, donor_masks: the [1,1,H,W] depth of a SECOND image of the host's
+    resolution and intrinsics, and D >= 1 pairwise disjoint masks of objects in it.  The edit's objects are then the host's M
+    masks (0 .. M - 1) followed by the donor's D masks (M .. M + D - 1), M + D <= 8: transforms and instances speak about that
+    list.  A donor object's points are the unprojection of donor_depth at its mask's pixels, its centroid the sequential-f32
+    centroid of those points; a pivot is a point of the shared camera coordinates.  From there on everything is shared (one
+    z-buffer, masks, visibility, in-fill, normalisation).  Donor masks may overlap host masks, removed masks and each other's
+    image position freely -- they are pixels of another image.  M = 0 with a donor is the pure insertion (bg_depth: the host
+    depth, or the depth with the removed masks removed).  A row of a donor instance carries its source pixel IN THE DONOR IMAGE;
+    a donor call always returns the instance array (return_instances is implied), and "row r is a donor row" means
+    instances[corr_inst[r]] >= M (`donor_rows`).  The debug dict gains row_donor [K, capacity] uint8 (device).  No relative depth
+    scale is estimated: the caller brings `scale`.  ValueError (check_donor); NotImplementedError for footprints with a donor
+    (the pixel -> list-position inverse of the triangles is ambiguous when two images share pixel indices).  No donor -- None,
+    or donor masks that are all empty -- is the call without the keywords, byte for byte, with the same launches.
+
+    Camera moves (DESIGN.md "Camera moves") -- cameras: None, or a list of K entries, one camera (`check_camera`) or None per
+    edit.  In an edit with a camera every point of the list, background included, is seen from the moved viewpoint: the points
+    that leave the frame are dropped (no clamp onto the border), the pixels no point reaches are in-filled (zero beyond the image
+    border: a known limit of the strip a move uncovers there), and the background yields correspondence rows of its own -- a
+    background pixel outside the host's foreground and removed masks whose point owns a target pixel outside the cleaned mask.
+    A camera call returns the instance array (return_instances is implied): the instance rows first, in the order they always
+    had, then the background rows in ascending source pixel order with instance index N (the number of instances).  An edit
+    without a camera in the same call is what it is in a call of its own, byte for byte, and has no background rows.  The pure
+    camera move is fg_masks = [] with K empty transform lists (bg_depth: the depth, or the depth with the removed masks
+    removed): every row is a background row.  The debug dict gains row_background (K uint8 tensors beside the returned rows: 1 =
+    a background row) and n_background (K ints), bg_corr and bg_counts.  ValueError (`check_camera`) naming the call and the
+    edit, NotImplementedError for footprints with a camera.  cameras=None, or all None, is the call without the keyword, byte
+    for byte, with the same launches.
+
+    Every refusal precedes the first launch of the library (they are `reproject_plan`'s)."""
+    p = reproject_plan(depth, fg_masks, edits, instances=instances, removed_masks=removed_masks, donor_depth=donor_depth,
+                       donor_masks=donor_masks, cameras=cameras, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
+                       return_instances=return_instances, what=what)
+    return _run_plan(p, depth, bg_depth, intrinsics, use_input_depth_normalization, return_debug, device_correspondences)
 
 
-def _reproject_pure_removal(depth, bg_depth, removed, intrinsics, K, use_input_depth_normalization, return_debug,
-                            device_correspondences, return_instances, with_table):
-    """The pure removal of `reproject_removal_edits`: dh_reproject_background once, its result K times."""
-    what = "reproject_removal_edits"
-    if depth.dim() != 4 or depth.shape[0] != 1:
-        raise ValueError("Only batch size 1 is supported")
-    res = removed[0].shape[-1]
-    if depth.shape[-1] != res or depth.shape[-2] != res:
-        raise ValueError(f"{what}: removed_masks: removed mask 0 is {res} x {res}, the depth {depth.shape[-1]} x {depth.shape[-2]}")
-    # the pixel counts and the overlap flags: ONE device-to-host copy (none for host masks), before any launch of the library
-    seen = torch.zeros(res * res, dtype=torch.bool, device=removed[0].device)
-    extra = []
-    for mask in removed:
-        mr = (mask.detach() != 0).reshape(-1).to(seen.device)
-        extra += [mr.sum(), (mr & seen).any().to(torch.int64)]
-        seen = seen | mr
-    tail = torch.stack(extra).tolist()
-    if any(tail[1::2]):
-        removed_overlap(removed, [], f"{what}: removed_masks")
-    if sum(tail[0::2]) == 0:
-        raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got 0")
-    out_dev = depth.device
-    dev = _compute_device(depth)
-    L = _lib.lib()
-    st = _lib.stream_ptr()
-    bg = bg_depth.detach().to(dev, torch.float32).contiguous()
-    bounds = None
-    if use_input_depth_normalization:
-        disp_in = 1.0 / depth.detach().to(dev, torch.float32)
-        bounds = torch.stack([disp_in.min(), disp_in.max()]).to(torch.float32).contiguous()
-    gx, gy = _grids(res, res, dev)
-    ifx, ify = _inv_focal(intrinsics)
-    kcpu = intrinsics.detach().to("cpu", torch.float32)
-    fx, fy = float(kcpu[0, 0]), float(kcpu[1, 1])
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.dh_reproject_background_workspace_bytes(res, ctypes.byref(nbytes)), "dh_reproject_background_workspace_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-    zmap = torch.empty((res, res), dtype=torch.float32, device=dev)
-    disp = torch.empty((res, res), dtype=torch.float32, device=dev)
-    counts = torch.zeros(4, dtype=torch.int32, device=dev)
-    _lib.check(L.dh_reproject_background(_lib.ptr(bg), res, _lib.ptr(gx), _lib.ptr(gy), ifx, ify, fx, fy, _lib.ptr(bounds),
-                                         _lib.ptr(zmap), _lib.ptr(disp), _lib.ptr(counts), _lib.ptr(ws), nbytes.value, st),
-               "dh_reproject_background")
-    counts_h = counts.cpu()
-    _check_infill(counts_h[3:4])
-    disp_out = disp[None, None].to(out_dev)
-    empty = torch.zeros((0, 4), dtype=torch.int64, device=dev if device_correspondences else "cpu")
-    no_inst = torch.zeros(0, dtype=torch.uint8, device=empty.device)
-    out = [(disp_out, empty) + ((no_inst,) if return_instances else ()) for _ in range(K)]
-    if not return_debug:
-        return out
-    zeros = torch.zeros((K, res, res), dtype=torch.uint8, device=dev)
-    dbg = dict(zmap=zmap[None].expand(K, -1, -1), raw_mask=zeros, clean_mask=zeros.clone(),
-               vis=torch.zeros((K, 0), dtype=torch.uint8, device=dev), target_xy=torch.zeros((K, 0, 2), dtype=torch.int32, device=dev),
-               counts=counts_h[None].expand(K, -1).contiguous(), fg_pix=torch.zeros(0, dtype=torch.int32, device=dev),
-               corr_dev=torch.zeros((K, 0, 4), dtype=torch.int64, device=dev), obj_start=np.zeros(1, dtype=np.int32),
-               vacated=seen.to(dev).reshape(res, res).to(torch.uint8))
-    if with_table or return_instances:
-        dbg.update(corr_inst=torch.zeros((K, 0), dtype=torch.uint8, device=dev), inst_start=np.zeros(1, dtype=np.int32))
-    return out, dbg
+def reproject_edits(depth, bg_depth, fg_mask, intrinsics, transforms, use_input_depth_normalization=False,
+                    return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None):
+    """`reproject` for one object: one mask, and one transform (not a list of them) per edit."""
+    return reproject(depth, bg_depth, [fg_mask], intrinsics, [[tf] for tf in transforms],
+                     use_input_depth_normalization=use_input_depth_normalization, return_debug=return_debug,
+                     device_correspondences=device_correspondences, footprints=footprints, footprint_max_ratio=footprint_max_ratio)
+
+
+def reproject_object_edits(depth, bg_depth, fg_masks, intrinsics, edits, use_input_depth_normalization=False,
+                           return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None):
+    """`reproject` for M objects, with or without footprints."""
+    return reproject(depth, bg_depth, fg_masks, intrinsics, edits, use_input_depth_normalization=use_input_depth_normalization,
+                     return_debug=return_debug, device_correspondences=device_correspondences, footprints=footprints,
+                     footprint_max_ratio=footprint_max_ratio)
+
+
+def reproject_instance_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, use_input_depth_normalization=False,
+                             return_debug=False, device_correspondences=False, footprints=False, footprint_max_ratio=None,
+                             return_instances=False):
+    """`reproject` with an instance table (copies of an object)."""
+    return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=instances,
+                     use_input_depth_normalization=use_input_depth_normalization, return_debug=return_debug,
+                     device_correspondences=device_correspondences, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
+                     return_instances=return_instances)
+
+
+def reproject_removal_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None,
+                            use_input_depth_normalization=False, return_debug=False, device_correspondences=False,
+                            footprints=False, footprint_max_ratio=None, return_instances=False):
+    """`reproject` for an edit that also deletes the objects of removed_masks."""
+    return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=instances, removed_masks=removed_masks,
+                     use_input_depth_normalization=use_input_depth_normalization, return_debug=return_debug,
+                     device_correspondences=device_correspondences, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
+                     return_instances=return_instances)
+
+
+def reproject_donor_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
+                          donor_masks=None, use_input_depth_normalization=False, return_debug=False,
+                          device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False):
+    """`reproject` for an edit that also places objects of a donor image."""
+    return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=instances, removed_masks=removed_masks,
+                     donor_depth=donor_depth, donor_masks=donor_masks, use_input_depth_normalization=use_input_depth_normalization,
+                     return_debug=return_debug, device_correspondences=device_correspondences, footprints=footprints,
+                     footprint_max_ratio=footprint_max_ratio, return_instances=return_instances)
+
+
+def reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
+                           donor_masks=None, use_input_depth_normalization=False, return_debug=False,
+                           device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
+                           cameras=None):
+    """`reproject` for edits that may also move the viewpoint."""
+    return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=instances, removed_masks=removed_masks,
+                     donor_depth=donor_depth, donor_masks=donor_masks, cameras=cameras,
+                     use_input_depth_normalization=use_input_depth_normalization, return_debug=return_debug,
+                     device_correspondences=device_correspondences, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
+                     return_instances=return_instances)
 
 
 INFILL_BARRIER_TIMEOUT, INFILL_NOT_CONVERGED, INFILL_BREAKDOWN = -1, -2, -3      # counts[..., 3] < 0 (geometry.hip)
@@ -973,7 +1009,7 @@ def pivot_at_pixel(depth, intrinsics, x, y):
 def transform_depth_footprints(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
                                use_input_depth_normalization=False, scale=None, pivot=None, footprints=False,
                                footprint_max_ratio=None):
-    """`transform_depth_pc` with the footprint settings of `reproject_object_edits` (point mode only).  `transform_depth` and
+    """`transform_depth_pc` with the footprint settings of `reproject` (point mode only).  `transform_depth` and
     `transform_depth_pc` keep the parameter lists they have; `transform_depth_pc` is the footprints-off call of this one."""
     if rot_angle is None:
         rot_angle = 0.0
@@ -988,7 +1024,7 @@ def transform_depth_footprints(depth, bg_depth, fg_mask, intrinsics, rot_angle=N
 
 def transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
                        use_input_depth_normalization=False, scale=None, pivot=None):
-    """The reference's transform_depth_pc (its parameters are a prefix); scale / pivot: see `reproject_object_edits`."""
+    """The reference's transform_depth_pc (its parameters are a prefix); scale / pivot: see `reproject`."""
     return transform_depth_footprints(depth, bg_depth, fg_mask, intrinsics, rot_angle, rot_axis, translation,
                                       use_input_depth_normalization, scale, pivot)
 
@@ -1091,7 +1127,7 @@ def transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, r
 def transform_depth(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_axis=None, translation=None,
                     use_input_depth_normalization=False, depth_transform_mode="pc", scale=None, pivot=None):
     """The reference's transform_depth (depth_transform.py:73-89): its signature is a prefix and its return value unchanged.
-    scale / pivot (not in the reference): see `reproject_object_edits`; mesh mode takes a pivot and refuses a scale.
+    scale / pivot (not in the reference): see `reproject`; mesh mode takes a pivot and refuses a scale.
     (Footprint splatting: `transform_depth_footprints`, point mode only.)"""
     if depth_transform_mode == "pc":
         return transform_depth_pc(depth, bg_depth, fg_mask, intrinsics, rot_angle, rot_axis, translation,

@@ -1,6 +1,4 @@
 """DiffusionHandles facade (reference diffusion_handles.py:15-166) on the native MI355X path."""
-import functools
-
 import torch
 
 from . import conf as _conf
@@ -129,7 +127,6 @@ class DiffusionHandles:
         lanes.  Images are bit-identical to the one-stream result at the same batch.  release_mask (conf background_lock
         only): extra area every edit's lock sets free (transform_foreground_objects)."""
         from .depth_transform import reproject_edits
-        K = len(transforms)
         fp = self._footprints("transform_foreground_batch")
         lk = self._lock_setup("transform_foreground_batch", activations, depth, release_mask)
         with torch.no_grad():
@@ -137,19 +134,34 @@ class DiffusionHandles:
                                     transforms, use_input_depth_normalization, device_correspondences=True, **fp)
             self.last_keep_maps = []
             lock = {} if lk is None else dict(lock=[self._edit_lock(lk, fg_mask, c, depth) for _, c in edits])
-            per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
-            if streams <= 1 and per >= K:
-                imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in edits], null_text_emb, prompt,
-                                                            activations, [c for _, c in edits], fg_weight, bg_weight, **lock)
-            elif per <= 1:
-                imgs = torch.cat(self.diffuser.guided_inference_lanes(init_noise, edits, null_text_emb, prompt, activations,
-                                                                      max(1, int(streams)), fg_weight, bg_weight, **lock))
-            else:
-                chunks = [([d for d, _ in edits[i:i + per]], [c for _, c in edits[i:i + per]]) for i in range(0, K, per)]
-                imgs = torch.cat(self.diffuser.guided_inference_batch_lanes(init_noise, chunks, null_text_emb, prompt,
-                                                                            activations, max(1, int(streams)), fg_weight,
-                                                                            bg_weight, **lock))
+            imgs = self._guided_batch(edits, streams, batch, (init_noise, null_text_emb, prompt, activations, fg_weight, bg_weight),
+                                      {}, lock)
         return imgs, [d for d, _ in edits]
+
+    def _guided_batch(self, edits, streams, batch, args, shared, per_edit, donor_acts=None):
+        """The route of K re-projected edits (disparity, correspondences) of one image, chosen in one place: the whole batch in
+        one loop (one stream, and a batch that holds all K), single edits on lanes (batch = 1), or chunks of `batch` edits (default
+        ceil(K / streams)) on lanes.  args: (init_noise, null_text_emb, prompt, activations, fg_weight, bg_weight); shared: the
+        guidance keywords all edits share; per_edit: those that are one entry per edit (_guidance_keywords) -- the chunked
+        route takes "pair_instances" and "donor" as one list per chunk (the lock stays one entry per edit), and this is the one
+        place where per-edit lists are cut; a "donor" entry travels as (donor_acts, its list).  -> images [K,3,H,W]."""
+        init_noise, null_text_emb, prompt, activations, fg_weight, bg_weight = args
+        K, lanes = len(edits), max(1, int(streams))
+        per = K if batch is None and streams <= 1 else int(batch or -(-K // lanes))
+        whole = streams <= 1 and per >= K
+        cut = (lambda v: v) if whole or per <= 1 else (lambda v: [v[i:i + per] for i in range(0, K, per)])
+        kw = dict(shared, **{k: cut(v) if k in ("pair_instances", "donor") else v for k, v in per_edit.items()})
+        if "donor" in kw:
+            kw["donor"] = (donor_acts, kw["donor"])
+        if whole:
+            return self.diffuser.guided_inference_batch(init_noise, [d for d, _ in edits], null_text_emb, prompt, activations,
+                                                        [c for _, c in edits], fg_weight, bg_weight, **kw)
+        if per <= 1:
+            return torch.cat(self.diffuser.guided_inference_lanes(init_noise, edits, null_text_emb, prompt, activations, lanes,
+                                                                  fg_weight, bg_weight, **kw))
+        chunks = [([d for d, _ in chunk], [c for _, c in chunk]) for chunk in cut(edits)]
+        return torch.cat(self.diffuser.guided_inference_batch_lanes(init_noise, chunks, null_text_emb, prompt, activations, lanes,
+                                                                    fg_weight, bg_weight, **kw))
 
     def _camera_setup(self, what, cameras, donor):
         """The host checks of an edit call's cameras (camera moves; DESIGN.md "Camera moves"), before any identity or launch ->
@@ -194,15 +206,9 @@ class DiffusionHandles:
         """instances given: every result is (disparity, correspondences, instance of every row).  removed_masks: the masks of the
         objects the edits delete (object removal); fg_masks may then be empty and the edits K empty lists.  donor: None or the
         checked donor (_donor_setup): its masks follow fg_masks in the object list, and an instance table is always given."""
-        from .depth_transform import (check_instances, check_removed_masks, reproject_camera_edits, reproject_donor_edits,
-                                      reproject_removal_edits)
-        if cameras is not None:          # (checked by _camera_setup: no donor, no footprints, 'pc' mode)
-            reproject_removal_edits = functools.partial(self._reproject_camera, reproject_camera_edits, cameras)
-            if len(fg_masks) == 0 and removed_masks is None:
-                removed_masks = []
-        if donor is not None:
-            reproject_removal_edits = functools.partial(self._reproject_donor, reproject_donor_edits, donor)
-        n_donor = 0 if donor is None else len(donor[1])
+        from .depth_transform import check_instances, check_transform, reproject
+        if cameras is not None and len(fg_masks) == 0 and removed_masks is None:
+            removed_masks = []          # (checked by _camera_setup: no donor, no footprints, 'pc' mode)
         fp = self._footprints(what)
         if self.conf.depth_transform_mode != "pc":
             if removed_masks is not None:
@@ -213,50 +219,29 @@ class DiffusionHandles:
                                           "object (instances; only 'pc')")
             raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no multi-object "
                                       "re-projection (only 'pc')")
-        if removed_masks is not None:
-            removed = check_removed_masks(removed_masks, list(fg_masks), f"{what}: removed_masks")
-            if len(fg_masks) == 0 and donor is None:
-                if not removed and cameras is None:
-                    raise ValueError(f"Expected 1 to 8 foreground masks, got 0 ({what}: no removed mask either)")
-                if instances is not None and len(list(instances)) != 0:
-                    raise ValueError(f"{what}: instances={instances!r} given without a foreground mask (a pure removal has no "
-                                     "instance)")
-                for e, tfs in enumerate(edits):
-                    if len(tfs) != 0:
-                        raise ValueError(f"{what}: edit {e} has {len(tfs)} transforms, but there is no foreground mask (a pure "
-                                         "removal moves nothing)")
-                return reproject_removal_edits(depth, bg_depth, [], self.diffuser.get_depth_intrinsics(device=depth.device),
-                                               [[] for _ in edits], None, removed, use_input_depth_normalization,
-                                               device_correspondences=device_correspondences, **fp)
+        kw = dict(removed_masks=removed_masks, cameras=cameras, use_input_depth_normalization=use_input_depth_normalization,
+                  device_correspondences=device_correspondences, what=what, **fp)
+        n_donor = 0
+        if donor is not None:
+            kw.update(donor_depth=donor[0], donor_masks=donor[1])
+            n_donor = len(donor[1])
+        intrinsics = self.diffuser.get_depth_intrinsics(device=depth.device)
+        if removed_masks is not None and len(fg_masks) == 0 and donor is None:
+            # nothing moves: the re-projection refuses transforms and an instance table under this call's name
+            return reproject(depth, bg_depth, [], intrinsics, edits, instances=instances, **kw)
         inst = check_instances(instances, len(fg_masks) + n_donor, f"{what}: instances")
         n_bodies, body = (len(fg_masks), "object") if inst is None else (len(inst), "instance")
-        Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
-        dflt = lambda v, d: d if v is None else v
-        if any(len(tfs) != n_bodies for tfs in edits):          # (reproject_object_edits names the edit)
-            defaulted = edits
-        else:
-            from .depth_transform import check_transform
-            defaulted = []
-            for e, tfs in enumerate(edits):
-                full = [check_transform(tf, f"{what}: edit {e}, {body} {m}") for m, tf in enumerate(tfs)]
-                defaulted.append([(dflt(a, 0.0), dflt(ax, Y), dflt(tr, torch.zeros(3)), sc, pv) for a, ax, tr, sc, pv in full])
-        edits = defaulted
-        return reproject_removal_edits(depth, bg_depth, fg_masks, self.diffuser.get_depth_intrinsics(device=depth.device), edits,
-                                       inst, removed_masks, use_input_depth_normalization,
-                                       device_correspondences=device_correspondences, **fp, return_instances=inst is not None)
+        if all(len(tfs) == n_bodies for tfs in edits):          # (else the re-projection names the edit)
+            edits = [[self._fill_transform(check_transform(tf, f"{what}: edit {e}, {body} {m}")) for m, tf in enumerate(tfs)]
+                     for e, tfs in enumerate(edits)]
+        return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=inst, return_instances=inst is not None, **kw)
 
     @staticmethod
-    def _reproject_camera(reproject, cameras, depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks,
-                          use_input_depth_normalization, device_correspondences=False, footprints=False, footprint_max_ratio=None,
-                          return_instances=False):
-        """reproject_camera_edits behind reproject_removal_edits' list: the cameras go last."""
-        return reproject(depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks, None, None,
-                         use_input_depth_normalization, False, device_correspondences, False, None, True, cameras)
-
-    @staticmethod
-    def _reproject_donor(reproject, donor, depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks, *args, **kw):
-        """reproject_donor_edits' positional list without the donor pair, which goes behind removed_masks."""
-        return reproject(depth, bg_depth, fg_masks, intrinsics, edits, inst, removed_masks, donor[0], donor[1], *args, **kw)
+    def _fill_transform(tf):
+        """The None members of a transform's rotation angle, axis and translation filled in: no turn, about Y, no move."""
+        angle, axis, translation, *rest = tf
+        return (0.0 if angle is None else angle, torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32) if axis is None else axis,
+                torch.zeros(3) if translation is None else translation, *rest)
 
     def _donor_setup(self, what, donor, fg_masks, depth, activations):
         """The host checks of an edit call's donor, before any library launch -> None (no donor: None, or every donor mask empty)
@@ -293,13 +278,6 @@ class DiffusionHandles:
                 raise ValueError(f"{what}: donor: activations of layer {k} hold {a.shape[0]} timesteps, the host's {o.shape[0]}")
         checked = check_donor(donor["depth"], donor["masks"], depth.shape[-1], len(fg_masks), what)
         return None if checked is None else checked + (acts,)
-
-    @staticmethod
-    def _donor_rows(rows, instances, n_host):
-        """One byte per correspondence row: 1 where the row's instance draws a donor mask (instances[row] >= n_host)."""
-        lut = torch.zeros(256, dtype=torch.uint8)
-        lut[:len(instances)] = torch.tensor([1 if o >= n_host else 0 for o in instances], dtype=torch.uint8)
-        return lut.to(rows.device)[rows.long()]
 
     @staticmethod
     def _lock_rows(correspondences, row_donor):
@@ -366,7 +344,7 @@ class DiffusionHandles:
         bg_depth: the depth with all of them removed (set_foreground takes the list); transforms: M (rot_angle_deg,
         rot_axis[3], translation[3]) or (rot_angle_deg, rot_axis[3], translation[3], scale, pivot), one per mask.  Each object
         turns about its own centroid, or is scaled and turned about its pivot (transform_foreground); they occlude the background
-        and each other (depth_transform.reproject_object_edits).  The guidance sees the union of the correspondences: its
+        and each other (depth_transform.reproject).  The guidance sees the union of the correspondences: its
         foreground term is the mean over all pairs, so the objects weigh by covered area -- unless object_weights says
         otherwise: "equal" holds every object equally, a sequence of M floats (finite, >= 0, not all zero) sets each weight;
         objects without a visible correspondence drop out and the rest are renormalised (DESIGN.md "A weight per object";
@@ -407,76 +385,83 @@ class DiffusionHandles:
         what = "transform_foreground_objects"
         fg_masks = list(fg_masks)
         cams = self._camera_setup(what, None if camera is None else [camera], donor)
-        if cams is not None:
-            return self._camera_edit(what, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations, transforms,
-                                     fg_weight, bg_weight, use_input_depth_normalization, object_weights, cams, removed_masks,
-                                     instances)
-        dn = self._donor_setup(what, donor, fg_masks, depth, activations)
-        if dn is not None:
-            if removed_masks is not None:
-                self._check_removal(what, fg_masks or list(dn[1]), removed_masks)
-            instances = list(range(len(fg_masks) + len(dn[1]))) if instances is None else instances
-            labels, object_weights = self._object_labels(fg_masks + list(dn[1]), object_weights, instances, f"{what}: instances")
-        else:
-            self._check_removal(what, fg_masks, removed_masks)
-            labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
-        lk = self._lock_setup(what, activations, depth, release_mask)
+        st = self._objects_setup(what, depth, fg_masks, activations, cams, donor, removed_masks, instances, object_weights,
+                                 release_mask)
         with torch.no_grad():
-            (edited_disparity, correspondences, *rows), = self._reproject_objects(
-                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances, removed_masks, dn)
-            self.last_keep_maps = []
-            freed = fg_masks + list(removed_masks or [])
-            lock_corr = correspondences
-            if dn is not None:
-                row_donor = self._donor_rows(rows[0], instances, len(fg_masks))
-                lock_corr = self._lock_rows(correspondences, row_donor)
-            lock = {} if lk is None else dict(lock=self._edit_lock(lk, freed, lock_corr, depth))
-            lock.update(self._vacated(removed_masks, what))
-            if rows:
-                lock["pair_instances"] = rows[0]
-            if dn is not None:
-                lock["donor"] = (dn[2], row_donor)
-            results = self.diffuser.guided_inference(
-                latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
-                activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
-                bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps,
-                object_labels=labels, object_weights=object_weights, **lock)
-        if self.conf.guided_diffuser.save_denoising_steps:
-            edited_img, denoising_steps = results
-            return edited_img, edited_disparity, denoising_steps
-        return results, edited_disparity
-
-    def _camera_rows(self, what, fg_masks, instances, object_weights):
-        """(N, the checked weights or None) of a camera edit: N instances, the background's rows carry instance index N."""
-        from .depth_transform import check_instances
-        inst = check_instances(instances, len(fg_masks), f"{what}: instances") if fg_masks else None
-        N = len(fg_masks) if inst is None else len(inst)
-        if not fg_masks and object_weights is not None:
-            raise ValueError(f"{what}: object_weights={object_weights!r} given without a foreground mask")
-        return N, self._camera_weights(what, object_weights, N)
-
-    def _camera_edit(self, what, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations, transforms, fg_weight,
-                     bg_weight, use_input_depth_normalization, object_weights, cams, removed_masks, instances):
-        """transform_foreground_objects with a camera: the re-projection's rows (instance rows, then background rows with
-        instance index N) go to guided_inference with their kinds; with weights the instance column is the energy's object."""
-        self._check_removal(what, fg_masks, removed_masks)
-        N, weights = self._camera_rows(what, fg_masks, instances, object_weights)
-        with torch.no_grad():
-            (edited_disparity, correspondences, rows), = self._reproject_objects(
-                what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False, instances, removed_masks, None,
-                cams)
-            self.last_keep_maps = []
-            kw = dict(row_kind=(rows == N).to(torch.uint8) * 2, **self._vacated(removed_masks, what))
-            if weights is not None:
-                kw.update(pair_instances=rows, object_weights=weights)
+            res = self._reproject_objects(what, depth, bg_depth, fg_masks, [transforms], use_input_depth_normalization, False,
+                                          st.instances, removed_masks, st.donor, cams)
+            shared, per_edit = self._guidance_keywords(what, st, res, depth, fg_masks, removed_masks)
+            kw = dict(shared, **{k: v[0] for k, v in per_edit.items()})
+            if st.donor is not None:
+                kw["donor"] = (st.donor[2], kw["donor"])
+            edited_disparity, correspondences = res[0][:2]
             results = self.diffuser.guided_inference(
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
                 bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps, **kw)
+        return self._edit_result(results, edited_disparity)
+
+    def _edit_result(self, results, edited_disparity):
+        """What a single edit returns: (image, disparity), with conf save_denoising_steps (image, disparity, denoising steps)."""
         if self.conf.guided_diffuser.save_denoising_steps:
             edited_img, denoising_steps = results
             return edited_img, edited_disparity, denoising_steps
         return results, edited_disparity
+
+    def _objects_setup(self, what, depth, fg_masks, activations, cams, donor, removed_masks, instances, object_weights, release_mask):
+        """The host checks an edit of several objects makes before its re-projection, for one edit and for K alike -> a record
+        of: cams (the checked cameras, _camera_setup), donor (the checked donor or None, _donor_setup), instances (the table; with a
+        donor the implied one over the host's and the donor's masks), labels and weights (_object_labels; with cameras the
+        weights of _camera_weights: the background is instance N), N (with cameras: the instance index of the background's rows)
+        and lock (_lock_setup; None with cameras, which the lock refuses)."""
+        from types import SimpleNamespace
+        if cams is not None:
+            from .depth_transform import check_instances
+            self._check_removal(what, fg_masks, removed_masks)
+            inst = check_instances(instances, len(fg_masks), f"{what}: instances") if fg_masks else None
+            N = len(fg_masks) if inst is None else len(inst)
+            if not fg_masks and object_weights is not None:
+                raise ValueError(f"{what}: object_weights={object_weights!r} given without a foreground mask")
+            return SimpleNamespace(cams=cams, donor=None, instances=instances, labels=None, N=N, lock=None,
+                                   weights=self._camera_weights(what, object_weights, N))
+        dn = self._donor_setup(what, donor, fg_masks, depth, activations)
+        bodies = fg_masks
+        if dn is not None:
+            if removed_masks is not None:
+                self._check_removal(what, fg_masks or list(dn[1]), removed_masks)
+            bodies = fg_masks + list(dn[1])
+            instances = list(range(len(bodies))) if instances is None else instances
+        else:
+            self._check_removal(what, fg_masks, removed_masks)
+        labels, weights = self._object_labels(bodies, object_weights, instances, f"{what}: instances")
+        return SimpleNamespace(cams=None, donor=dn, instances=instances, labels=labels, weights=weights, N=None,
+                               lock=self._lock_setup(what, activations, depth, release_mask))
+
+    def _guidance_keywords(self, what, st, res, depth, fg_masks, removed_masks):
+        """The guidance's keywords for the K re-projected edits `res` of one _objects_setup -> (those all edits share, those
+        that are one entry per edit: K long lists).  A "donor" entry is the donor-row flags per edit; the loops take it as
+        (the donor's activations, flags)."""
+        self.last_keep_maps = []
+        shared, per_edit = self._vacated(removed_masks, what), {}
+        if st.cams is not None:
+            # the rows are the instance rows, then the background's with instance index N; with weights the instance column is
+            # the energy's object.  (An edit without a camera has no background row: its kinds are all zero, the call without.)
+            per_edit["row_kind"] = [(r[2] == st.N).to(torch.uint8) * 2 for r in res]
+            if st.weights is not None:
+                per_edit["pair_instances"] = [r[2] for r in res]
+                shared["object_weights"] = st.weights
+            return shared, per_edit
+        shared.update(object_labels=st.labels, object_weights=st.weights)
+        lock_corrs = [r[1] for r in res]
+        if st.donor is not None:
+            from .depth_transform import donor_rows
+            per_edit["donor"] = [donor_rows(r[2], st.instances, len(fg_masks)) for r in res]
+            lock_corrs = [self._lock_rows(c, f) for c, f in zip(lock_corrs, per_edit["donor"])]
+        if st.lock is not None:
+            per_edit["lock"] = [self._edit_lock(st.lock, fg_masks + list(removed_masks or []), c, depth) for c in lock_corrs]
+        if st.instances is not None:
+            per_edit["pair_instances"] = [r[2] for r in res]
+        return shared, per_edit
 
     def transform_foreground_objects_batch(self, depth, prompt, fg_masks, bg_depth, null_text_emb, init_noise, activations,
                                            edits, fg_weight=None, bg_weight=None, use_input_depth_normalization=False,
@@ -501,64 +486,19 @@ class DiffusionHandles:
             raise ValueError(f"{what}: cameras has {len(cameras)} entries for {len(edits)} edits")
         cams = self._camera_setup(what, cameras, donor)
         if cams is not None:
-            K = len(edits)
-            if streams > 1 or (batch is not None and int(batch) < K):
+            if streams > 1 or (batch is not None and int(batch) < len(edits)):
                 raise NotImplementedError(f"{what}: cameras run as one batch on one stream (streams={streams}, batch={batch})")
             if release_mask is not None:
                 raise ValueError(f"{what}: release_mask needs conf background_lock: true")
-            self._check_removal(what, fg_masks, removed_masks)
-            N, weights = self._camera_rows(what, fg_masks, instances, object_weights)
-            with torch.no_grad():
-                res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, instances,
-                                              removed_masks, None, cams)
-                self.last_keep_maps = []
-                # (an edit without a camera has no background row: its kinds are all zero, which is the call without them)
-                kw = dict(row_kind=[(r[2] == N).to(torch.uint8) * 2 for r in res], **self._vacated(removed_masks, what))
-                if weights is not None:
-                    kw.update(pair_instances=[r[2] for r in res], object_weights=weights)
-                imgs = self.diffuser.guided_inference_batch(init_noise, [r[0] for r in res], null_text_emb, prompt, activations,
-                                                            [r[1] for r in res], fg_weight, bg_weight, **kw)
-            return imgs, [r[0] for r in res]
-        dn = self._donor_setup(what, donor, fg_masks, depth, activations)
-        if dn is not None:
-            if removed_masks is not None:
-                self._check_removal(what, fg_masks or list(dn[1]), removed_masks)
-            instances = list(range(len(fg_masks) + len(dn[1]))) if instances is None else instances
-            labels, object_weights = self._object_labels(fg_masks + list(dn[1]), object_weights, instances, f"{what}: instances")
-        else:
-            self._check_removal(what, fg_masks, removed_masks)
-            labels, object_weights = self._object_labels(fg_masks, object_weights, instances, f"{what}: instances")
-        lk = self._lock_setup(what, activations, depth, release_mask)
-        K = len(edits)
+        st = self._objects_setup(what, depth, fg_masks, activations, cams, donor, removed_masks, instances, object_weights,
+                                 release_mask)
         with torch.no_grad():
-            res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, instances,
-                                          removed_masks, dn)
-            rows = [r[2] for r in res] if instances is not None else None
+            res = self._reproject_objects(what, depth, bg_depth, fg_masks, edits, use_input_depth_normalization, True, st.instances,
+                                          removed_masks, st.donor, cams)
+            shared, per_edit = self._guidance_keywords(what, st, res, depth, fg_masks, removed_masks)
             res = [r[:2] for r in res]
-            per = K if batch is None and streams <= 1 else int(batch or -(-K // max(1, int(streams))))
-            obj = dict(object_labels=labels, object_weights=object_weights, **self._vacated(removed_masks, what))
-            self.last_keep_maps = []
-            whole = streams <= 1 and per >= K or per <= 1          # per edit; the chunked call takes one list per chunk
-            lock_corrs = [c for _, c in res]
-            if dn is not None:
-                flags = [self._donor_rows(r, instances, len(fg_masks)) for r in rows]
-                lock_corrs = [self._lock_rows(c, f) for c, f in zip(lock_corrs, flags)]
-                obj["donor"] = (dn[2], flags if whole else [flags[i:i + per] for i in range(0, K, per)])
-            if lk is not None:
-                obj["lock"] = [self._edit_lock(lk, fg_masks + list(removed_masks or []), c, depth) for c in lock_corrs]
-            if rows is not None:
-                obj["pair_instances"] = rows if whole else [rows[i:i + per] for i in range(0, K, per)]
-            if streams <= 1 and per >= K:
-                imgs = self.diffuser.guided_inference_batch(init_noise, [d for d, _ in res], null_text_emb, prompt, activations,
-                                                            [c for _, c in res], fg_weight, bg_weight, **obj)
-            elif per <= 1:
-                imgs = torch.cat(self.diffuser.guided_inference_lanes(init_noise, res, null_text_emb, prompt, activations,
-                                                                      max(1, int(streams)), fg_weight, bg_weight, **obj))
-            else:
-                chunks = [([d for d, _ in res[i:i + per]], [c for _, c in res[i:i + per]]) for i in range(0, K, per)]
-                imgs = torch.cat(self.diffuser.guided_inference_batch_lanes(init_noise, chunks, null_text_emb, prompt,
-                                                                            activations, max(1, int(streams)), fg_weight,
-                                                                            bg_weight, **obj))
+            imgs = self._guided_batch(res, streams, batch, (init_noise, null_text_emb, prompt, activations, fg_weight, bg_weight),
+                                      shared, per_edit, None if st.donor is None else st.donor[2])
         return imgs, [d for d, _ in res]
 
     EDIT_FIELDS = ("depth", "prompt", "fg_mask", "bg_depth", "null_text_emb", "init_noise", "activations")
@@ -650,8 +590,6 @@ class DiffusionHandles:
         if unet is not None and (unet.max_batch < 2 * K or unet.max_diff_batch < K):
             raise RuntimeError(f"engine max_batch {unet.max_batch} / max_diff_batch {unet.max_diff_batch} too small for {K} edits: "
                                f"build the diffuser with max_batch >= {2 * K}")
-        Y = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float32)
-        dflt = lambda v, d: d if v is None else v
         groups = {}                  # image (and its mask tensors) -> indices of its edits, in input order
         for i, e in enumerate(edits):
             masks = tuple(id(m) for m in e["fg_masks"]) if e.get("fg_masks") is not None else (id(e["fg_mask"]),)
@@ -691,8 +629,7 @@ class DiffusionHandles:
                         for i in idx:
                             labels[i] = label if weights[i] is not None else None
                 else:
-                    tfs = [(dflt(edits[i].get("rot_angle"), 0.0), dflt(edits[i].get("rot_axis"), Y),
-                            dflt(edits[i].get("translation"), torch.zeros(3)), edits[i].get("scale"), edits[i].get("pivot"))
+                    tfs = [self._fill_transform([edits[i].get(k) for k in ("rot_angle", "rot_axis", "translation", "scale", "pivot")])
                            for i in idx]
                     res = reproject_edits(e0["depth"], e0["bg_depth"], e0["fg_mask"],
                                           self.diffuser.get_depth_intrinsics(device=e0["depth"].device), tfs,
@@ -720,7 +657,7 @@ class DiffusionHandles:
         masked points) or a point in those coordinates (depth_transform.pivot_at_pixel) -- is what the object is scaled and
         turned about.  In 'pc' mode a magnified object leaves gaps between its points, bridged only up to the mask CLOSE's
         element (res // 50) -- unless the conf has depth_transform_footprints: true (footprint splatting, point mode only;
-        depth_transform_footprint_max_ratio is its optional depth-ratio guard; depth_transform.reproject_object_edits);
+        depth_transform_footprint_max_ratio is its optional depth-ratio guard; depth_transform.reproject);
         'mesh' mode takes a pivot and refuses a scale and footprints (NotImplementedError).  With conf background_lock: true
         the edit's latents are held to the reconstruction outside its region (DESIGN.md "Background lock"; both modes)."""
         fp = self._footprints("transform_foreground")
@@ -740,7 +677,4 @@ class DiffusionHandles:
                 latents=init_noise, depth=edited_disparity, uncond_embeddings=null_text_emb, prompt=prompt,
                 activations_orig=activations, correspondences=correspondences, fg_weight=fg_weight,
                 bg_weight=bg_weight, save_denoising_steps=self.conf.guided_diffuser.save_denoising_steps, **lock)
-        if self.conf.guided_diffuser.save_denoising_steps:
-            edited_img, denoising_steps = results
-            return edited_img, edited_disparity, denoising_steps
-        return results, edited_disparity
+        return self._edit_result(results, edited_disparity)

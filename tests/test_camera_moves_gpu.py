@@ -749,3 +749,36 @@ def test_run_edit_passes_the_camera_of_a_scene_directory(tiny, tmp_path):
         with pytest.raises(NotImplementedError, match="moves the camera.*" + name):
             run_edit.run_scene(bad, dh.conf, lambda res: called.append(res), str(scene), str(tmp_path / "refused"), None)
     assert not called
+
+
+def test_the_host_plan_is_what_the_run_does_and_every_name_is_the_one_call():
+    """depth_transform.reproject_plan against the run it plans (DESIGN.md "One host path for the re-projection"), at 64 pixels:
+    an instance call with a dropped empty mask, a donor call and a camera call.  The plan's point and row counts and offsets are
+    the debug dictionary's, the instance column names survivors only, and the named function returns the bits of `reproject`
+    called with the same keywords."""
+    from diffusionhandles_amd import depth_transform as DT
+    from oracle import depth_ref as D
+    res = 64
+    depth, bg, masks = R.two_spheres(res)
+    d, b, m = depth.to(dev()), bg.to(dev()), [x.to(dev()) for x in masks]
+    tfs = [_t(tf) for tf in S.edits_for(res, depth)[0]]
+    donor_depth, donor_masks = I.donor_scene(res, "disjoint")
+    donor = dict(donor_depth=donor_depth.to(dev()), donor_masks=[x.to(dev()) for x in donor_masks])
+    cam = CM.cameras_for(depth)["pan"]
+    calls = [(DT.reproject_instance_edits, [m[0], torch.zeros_like(m[0]), m[1]], [[tfs[0], tfs[1], tfs[1], tfs[0]]],
+              dict(instances=[2, 1, 0, 0], return_instances=True), [0, 2, 3]),
+             (DT.reproject_donor_edits, m, [tfs + [tfs[0][:3] + (0.8, None)]], donor, [0, 1, 2]),
+             (DT.reproject_camera_edits, m, [tfs, tfs], dict(cameras=[cam, None]), [0, 1])]
+    for named, fg, edits, kw, caller in calls:
+        p = DT.reproject_plan(d, fg, edits, **kw)
+        assert p.kind == "objects" and p.entry == "dh_" + named.__name__ and p.caller == caller
+        out, dbg = named(d, b, fg, D.intrinsics_f32(), edits, return_debug=True, **kw)
+        assert dbg["vis"].shape[1] == p.n_pts and dbg["corr_dev"].shape[1] == p.cap
+        assert np.array_equal(dbg["obj_start"], p.obj_start) and np.array_equal(dbg["inst_start"], p.inst_start)
+        for e in range(len(edits)):
+            n = int(dbg["counts"][e, 0])
+            assert n > 0 and set(dbg["corr_inst"][e, :n].tolist()) <= set(p.caller), (named.__name__, e)
+        direct = DT.reproject(d, b, fg, D.intrinsics_f32(), edits, **kw)
+        assert len(direct) == len(out) == len(edits)
+        for e, (x, y) in enumerate(zip(out, direct)):
+            assert len(x) == len(y) == 3 and all(torch.equal(s, t) for s, t in zip(x, y)), (named.__name__, e)

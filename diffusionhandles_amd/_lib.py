@@ -260,6 +260,10 @@ DEBUG_SIGNATURES = {
     "dh_dbg_cg_limits": (c_i, [ctypes.POINTER(c_i)]),
     "dh_dbg_cg_max_iter": (c_i, [c_i]),
     "dh_dbg_footprint_tier": (c_i, [c_i]),
+    # arena hooks (host only): the gap every workspace take leaves behind it, and the log of takes (base, offset, bytes)
+    "dh_dbg_arena_gap": (c_i, [c_i]),
+    "dh_dbg_arena_log": (c_i, [c_i]),
+    "dh_dbg_arena_log_read": (c_i, [ctypes.POINTER(ctypes.c_int64), c_i, ctypes.POINTER(c_i)]),
     # hooks of the kernels only the engines launch (tests/test_engine_kernels_gpu.py)
     # dh_dbg_gemm's arguments with `pad` behind `up`
     "dh_dbg_gemm_pad": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i,

@@ -148,11 +148,27 @@ extern "C" int dh_keep_map(const int64_t* corr, int n, const uint8_t* mask, cons
   return DH_OK;
 }
 
+namespace dh {
+struct CellsWs {
+  uint8_t *valid, *two;
+  int *idx, *bc;
+};
+static bool carve_cells(Arena& a, int n, int grid, CellsWs& w) {
+  const size_t nn = n > 0 ? n : 1, G2 = (size_t)grid * grid;
+  w.valid = a.take<uint8_t>(nn);
+  w.idx = a.take<int>(nn);
+  w.two = a.take<uint8_t>(2 * G2);
+  w.bc = a.take<int>(3 * (size_t)(cdiv((int)nn, CP_TILE) + cdiv((int)G2, CP_TILE) + 2));
+  return a.ok();
+}
+}  // namespace dh
+
 extern "C" int dh_cells_workspace_bytes(int n, int grid, size_t* bytes) {
   DH_REQUIRE(n >= 0 && grid >= 1 && bytes, "bad arguments");
-  size_t nn = n > 0 ? n : 1;
-  *bytes = align_up(nn, 256) + align_up(nn * sizeof(int), 256) + align_up(2 * (size_t)grid * grid, 256) +
-           (size_t)(3 * (cdiv((int)nn, CP_TILE) + cdiv(grid * grid, CP_TILE) + 2)) * sizeof(int) + 4096;
+  Arena a(nullptr, (size_t)-1);
+  CellsWs w;
+  carve_cells(a, n, grid, w);
+  *bytes = a.off + 256;
   return DH_OK;
 }
 
@@ -174,16 +190,13 @@ static int cells_rows(const int64_t* corr, int n, int img_res, int grid, int bg_
   DH_REQUIRE(n == 0 || corr, "null corr");
   DH_REQUIRE(!vacated || img_res <= 32768, "img_res too large for a vacated image");
   DH_REQUIRE(2 * grid * grid <= 60000, "grid too large for the erosion kernel");
-  size_t need;
-  dh_cells_workspace_bytes(n, grid, &need);
-  DH_REQUIRE(workspace_bytes >= need, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int G2 = grid * grid;
   Arena a(workspace, workspace_bytes);
-  uint8_t* valid = a.take<uint8_t>(n > 0 ? n : 1);
-  int* idx = a.take<int>(n > 0 ? n : 1);
-  uint8_t* two = a.take<uint8_t>(2 * (size_t)G2);
-  int* bc = a.take<int>(3 * (cdiv(n > 0 ? n : 1, CP_TILE) + cdiv(G2, CP_TILE) + 2));
+  CellsWs w;
+  DH_REQUIRE(carve_cells(a, n, grid, w), "workspace too small");
+  uint8_t *valid = w.valid, *two = w.two;
+  int *idx = w.idx, *bc = w.bc;
   DH_CHECK_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int), st));
   hipLaunchKernelGGL(k_init_masks, dim3(cdiv(2 * G2, 256)), dim3(256), 0, st, two, 2 * G2);
   if (n > 0) {

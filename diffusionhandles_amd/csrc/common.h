@@ -41,7 +41,14 @@ void set_error(const std::string& s);
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// Bump allocator over a caller-provided workspace.
+// test hooks (host only, debug_api.cpp: dh_dbg_arena_gap, dh_dbg_arena_log): bytes every Arena skips behind a take (0 = the
+// product's layout, byte for byte), and whether takes are recorded
+extern size_t g_arena_gap;
+extern bool g_arena_log;
+void arena_log_take(const void* base, size_t off, size_t bytes);
+
+// Bump allocator over a caller-provided workspace.  A size query carves a null-based arena with the carve function of its entry
+// and answers off + 256; the entry carves the caller's buffer and refuses on !ok().
 struct Arena {
   char* base;
   size_t cap, off;
@@ -50,7 +57,8 @@ struct Arena {
   T* take(size_t n) {
     off = align_up(off, 256);
     T* r = (T*)(base + off);
-    off += n * sizeof(T);
+    if (g_arena_log) arena_log_take(base, off, n * sizeof(T));
+    off += n * sizeof(T) + g_arena_gap;
     return r;
   }
   bool ok() const { return off <= cap; }

@@ -3,8 +3,45 @@
 // product path.
 #include <stdlib.h>
 
+#include <vector>
+
 #include "unet_kernels.h"
 using namespace dh;
+
+// ---- arena hooks (host only; tests/test_arena_hooks.py, tests/test_workspace_guards_gpu.py) ------------------------------------
+// Plain globals like the CG cap and the footprint tier: set by a test, read by every Arena (common.h), reset by the test.
+namespace dh {
+size_t g_arena_gap = 0;
+bool g_arena_log = false;
+static std::vector<int64_t> g_arena_takes;        // (base address, offset, bytes) per take
+void arena_log_take(const void* base, size_t off, size_t bytes) {
+  g_arena_takes.push_back((int64_t)(intptr_t)base);
+  g_arena_takes.push_back((int64_t)off);
+  g_arena_takes.push_back((int64_t)bytes);
+}
+}  // namespace dh
+// every take of every arena, in the size queries and in the entries alike, skips `bytes` behind its sub-buffer: a band no
+// kernel may touch.  0 (the default) is the product's layout byte for byte.
+extern "C" int dh_dbg_arena_gap(int bytes) {
+  DH_REQUIRE(bytes >= 0 && bytes <= 65536 && bytes % 256 == 0, "the gap is 0 or a multiple of 256 up to 65536");
+  dh::g_arena_gap = (size_t)bytes;
+  return DH_OK;
+}
+// enable != 0: clear the log and record every take from now on (a query's null-based arena logs base 0); 0: stop recording
+extern "C" int dh_dbg_arena_log(int enable) {
+  if (enable) dh::g_arena_takes.clear();
+  dh::g_arena_log = enable != 0;
+  return DH_OK;
+}
+// out [cap][3] = (base address, offset, bytes) of the first min(cap, *n) takes, *n = the takes recorded
+extern "C" int dh_dbg_arena_log_read(int64_t* out, int cap, int* n) {
+  DH_REQUIRE(n && cap >= 0 && (cap == 0 || out), "bad arguments");
+  const size_t have = dh::g_arena_takes.size() / 3;
+  for (size_t i = 0; i < have && i < (size_t)cap; ++i)
+    for (int j = 0; j < 3; ++j) out[3 * i + j] = dh::g_arena_takes[3 * i + j];
+  *n = (int)have;
+  return DH_OK;
+}
 
 static void* g_dbg_tiled = nullptr;      // the tiled copy of the last weight matrix dh_dbg_gemm was given
 

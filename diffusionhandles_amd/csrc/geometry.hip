@@ -1811,11 +1811,37 @@ extern "C" int dh_reproject_background(const float* bg_depth, int res, const flo
                                         workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr);
 }
 
+namespace dh {
+struct BlendWs {
+  double *vx, *vr, *vp, *vq;
+  uint8_t *m0, *m1;
+  float* lap;
+  int *unk, *pixmap;
+  int2 *nb_ud, *nb_lr;
+  int* bc;
+  CgSync* cgs;
+};
+static bool carve_blend(Arena& a, int res, BlendWs& w) {
+  const size_t R2 = (size_t)res * res;
+  w.vx = a.take<double>(R2); w.vr = a.take<double>(R2); w.vp = a.take<double>(R2); w.vq = a.take<double>(R2);
+  w.m0 = a.take<uint8_t>(R2); w.m1 = a.take<uint8_t>(R2);
+  w.lap = a.take<float>(R2);
+  w.unk = a.take<int>(R2);
+  w.pixmap = a.take<int>(R2);
+  w.nb_ud = a.take<int2>(R2);
+  w.nb_lr = a.take<int2>(R2);
+  w.bc = a.take<int>(cdiv((int)R2, CP_TILE) + 2);
+  w.cgs = a.take<CgSync>(1);
+  return a.ok();
+}
+}  // namespace dh
+
 extern "C" int dh_laplacian_blend_workspace_bytes(int res, size_t* bytes) {
   DH_REQUIRE(res >= 2 && bytes, "bad arguments");
-  const size_t R2 = (size_t)res * res;
-  *bytes = 4 * align_up(R2 * 8, 256) + 3 * align_up(R2, 256) + 3 * align_up(R2 * 4, 256) + 2 * align_up(R2 * 8, 256) +
-           (size_t)(cdiv((int)R2, CP_TILE) + 2) * 4 + 4096 + align_up(sizeof(CgSync), 256);
+  Arena a(nullptr, (size_t)-1);
+  BlendWs w;
+  carve_blend(a, res, w);
+  *bytes = a.off + 256;
   return DH_OK;
 }
 
@@ -1826,21 +1852,18 @@ extern "C" int dh_laplacian_blend(const float* depth, const float* bg_depth, con
                                   int dilate_iters, float* out, int32_t* counts, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   DH_REQUIRE(depth && bg_depth && fg_mask && out && counts && workspace && res >= 2 && dilate_iters >= 0, "bad arguments");
-  size_t need;
-  dh_laplacian_blend_workspace_bytes(res, &need);
-  DH_REQUIRE(workspace_bytes >= need, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int R2 = res * res;
   Arena a(workspace, workspace_bytes);
-  double* vx = a.take<double>(R2); double* vr = a.take<double>(R2); double* vp = a.take<double>(R2); double* vq = a.take<double>(R2);
-  uint8_t* m0 = a.take<uint8_t>(R2); uint8_t* m1 = a.take<uint8_t>(R2);
-  float* lap = a.take<float>(R2);
-  int* unk = a.take<int>(R2);
-  int* pixmap = a.take<int>(R2);
-  int2* nb_ud = a.take<int2>(R2);
-  int2* nb_lr = a.take<int2>(R2);
-  int* bc = a.take<int>(cdiv(R2, CP_TILE) + 2);
-  CgSync* cgs = a.take<CgSync>(1);
+  BlendWs w;
+  DH_REQUIRE(carve_blend(a, res, w), "workspace too small");
+  double *vx = w.vx, *vr = w.vr, *vp = w.vp, *vq = w.vq;
+  uint8_t *m0 = w.m0, *m1 = w.m1;
+  float* lap = w.lap;
+  int *unk = w.unk, *pixmap = w.pixmap;
+  int2 *nb_ud = w.nb_ud, *nb_lr = w.nb_lr;
+  int* bc = w.bc;
+  CgSync* cgs = w.cgs;
   DH_CHECK_HIP(hipMemcpyAsync(m0, fg_mask, R2, hipMemcpyDeviceToDevice, st));
   uint8_t *src = m0, *dst = m1;
   for (int i = 0; i < dilate_iters; ++i) {

@@ -227,11 +227,32 @@ __global__ void k_mesh_finish(int res, const float* zmap, const unsigned int* mi
 
 using namespace dh;
 
+namespace dh {
+struct MeshWs {
+  float *vb, *vf;
+  unsigned long long* zbuf;
+  int *src_xy, *fg_list, *bc;
+  unsigned int* minmax;
+};
+static bool carve_mesh(Arena& a, int res, MeshWs& w) {
+  const size_t R2 = (size_t)res * res;
+  w.vb = a.take<float>(3 * R2);
+  w.vf = a.take<float>(3 * R2);
+  w.zbuf = a.take<unsigned long long>(R2);
+  w.src_xy = a.take<int>(2 * R2);
+  w.fg_list = a.take<int>(R2);
+  w.bc = a.take<int>(cdiv((int)R2, CP_TILE) + 2);
+  w.minmax = a.take<unsigned int>(2);
+  return a.ok();
+}
+}  // namespace dh
+
 extern "C" int dh_mesh_workspace_bytes(int res, size_t* bytes) {
   DH_REQUIRE(res >= 2 && bytes, "bad arguments");
-  const size_t R2 = (size_t)res * res;
-  *bytes = 2 * align_up(R2 * 12, 256) + align_up(R2 * 8, 256) + align_up(R2 * 8, 256) + align_up(R2, 256) +
-           align_up(R2 * 4, 256) + (size_t)(cdiv((int)R2, CP_TILE) + 2) * 4 + 4096;
+  Arena a(nullptr, (size_t)-1);
+  MeshWs w;
+  carve_mesh(a, res, w);
+  *bytes = a.off + 256;
   return DH_OK;
 }
 
@@ -245,19 +266,15 @@ extern "C" int dh_mesh_reproject(const float* depth, const float* bg_depth, cons
   DH_REQUIRE(depth && bg_depth && fg_mask && grid && lin01 && xform, "null input");
   DH_REQUIRE(zmap && disparity && fg_flag && corr && counts && workspace, "null output");
   DH_REQUIRE(res >= 2 && blur_radius >= 0.f, "bad arguments");
-  size_t need;
-  dh_mesh_workspace_bytes(res, &need);
-  DH_REQUIRE(workspace_bytes >= need, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int R2 = res * res;
   Arena a(workspace, workspace_bytes);
-  float* vb = a.take<float>((size_t)3 * R2);
-  float* vf = a.take<float>((size_t)3 * R2);
-  unsigned long long* zbuf = a.take<unsigned long long>(R2);
-  int* src_xy = a.take<int>((size_t)2 * R2);
-  int* fg_list = a.take<int>(R2);
-  int* bc = a.take<int>(cdiv(R2, CP_TILE) + 2);
-  unsigned int* minmax = a.take<unsigned int>(2);
+  MeshWs w;
+  DH_REQUIRE(carve_mesh(a, res, w), "workspace too small");
+  float *vb = w.vb, *vf = w.vf;
+  unsigned long long* zbuf = w.zbuf;
+  int *src_xy = w.src_xy, *fg_list = w.fg_list, *bc = w.bc;
+  unsigned int* minmax = w.minmax;
   MeshXf xf;
   xf.ax = xform[0]; xf.ay = xform[1]; xf.az = xform[2]; xf.c = xform[3]; xf.s = xform[4];
   xf.tx = xform[5]; xf.ty = xform[6]; xf.tz = xform[7]; xf.cx = xform[8]; xf.cy = xform[9]; xf.cz = xform[10];

@@ -49,16 +49,26 @@ __device__ __forceinline__ uint4 tr_frag(const unsigned short* tptr, int cbase, 
   return make_uint4(l2.x, l2.y, u2.x, u2.y);
 }
 
-// registers 8s..8s+7 of an accumulator -> B operand (16-bit)
+// registers 8s..8s+7 of an accumulator -> B operand (16-bit), rounded to NEAREST in both types.  fp16 used v_cvt_pkrtz_f16_f32
+// (toward zero) until tests/test_attention_range_gpu.py: the forward's o = sum(P16 v) / sum(P) then came out low by up to 2^-11 of
+// itself -- the row maximum's own P, exp2 of an fma residue a hair under zero, became 1 - 2^-11 -- and delta = rowsum(dO o) carried
+// that bias times |delta| into dS, where a common component of k (dq) or a sum over many alike rows (dk) adds it up coherently: dq,
+// dk 1.1 to 2.2 tolerances off where the once-rounded o gives 0.4.  gfx950's v_cvt_pk_f16_f32 rounds to nearest, one instruction too.
+typedef float pk2f __attribute__((ext_vector_type(2)));
+typedef _Float16 pk2h __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pack2_f16(float a, float b) {
+  const pk2f x = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(x, pk2h));
+}
 template <class T>
 __device__ __forceinline__ uint4 pack8(const v16f& p, int s);
 template <>
 __device__ __forceinline__ uint4 pack8<f16>(const v16f& p, int s) {
   uint4 o;
-  o.x = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 0], p[8 * s + 1]));
-  o.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 2], p[8 * s + 3]));
-  o.z = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 4], p[8 * s + 5]));
-  o.w = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(p[8 * s + 6], p[8 * s + 7]));
+  o.x = pack2_f16(p[8 * s + 0], p[8 * s + 1]);
+  o.y = pack2_f16(p[8 * s + 2], p[8 * s + 3]);
+  o.z = pack2_f16(p[8 * s + 4], p[8 * s + 5]);
+  o.w = pack2_f16(p[8 * s + 6], p[8 * s + 7]);
   return o;
 }
 template <>

@@ -208,8 +208,9 @@ def test_to_out_input_gradient_with_dq_epilogue(dtype, B, Nq, H, Nk, K, expect):
     The saved q is the two-launch forward's; the saved o and lse are the fp32 attention of that stored q, o rounded to the storage
     type, so that the gradient under test and the autograd reference differentiate the same function at the same point.  (With
     the o of k_attn_fwd instead, the single-key case misses the autograd gate at fp16 -- worst element 1.85 x tolerance, 0.34 % of
-    the elements over it, fused and unfused alike: that kernel rounds P toward zero, so its o is V (1 - 2^-11) wherever exp2
-    returns a hair under one, delta = rowsum(dO o) no longer cancels dP, and the exact gradient there is zero.)"""
+    the elements over it, fused and unfused alike: that kernel then rounded P toward zero, so its o was V (1 - 2^-11) wherever
+    exp2 returns a hair under one, delta = rowsum(dO o) no longer cancelled dP, and the exact gradient there is zero.  pack8 has
+    rounded to nearest since DESIGN.md 8c; the saved o stays the reference's, which keeps this a test of the gradient alone.)"""
     c = make_case(dtype, B, Nq, H, Nk, K, False, seed=B * 1000 + Nq + H + Nk + K + 1)
     M, C = c["M"], c["C"]
     q, _, _, _ = run_xattn(c, 1, 1 | 16)

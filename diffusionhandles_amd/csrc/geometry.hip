@@ -713,7 +713,18 @@ constexpr int CG_BARRIER_TIMEOUT = -1, CG_NOT_CONVERGED = -2, CG_BREAKDOWN = -3;
 static int g_cg_max_iter = 0;
 static inline int cg_cap(int own) { return g_cg_max_iter > 0 ? g_cg_max_iter : own; }
 
-// Harmonic in-fill: A x = b with A = 4 I - adjacency(masked), solved by CG in float64 by ONE
+// The image border of the in-fill (infill_border of the border entries): 0 = zero (a neighbour beyond the frame is a known 0: the
+// diagonal stays 4), 1 = reflect (the mirror ghost cell x_ghost = x_self: the diagonal of an unknown is the number of its
+// neighbours inside the image).  The neighbour tables carry it: a slot holds an unknown's index, CG_NB_NONE (a known or absent
+// neighbour) or, under reflect only, CG_NB_FRAME (beyond the frame), and the diagonal is recounted from the slots wherever a
+// product reads them -- compares beside loads, no register per unknown.  Under zero no slot holds CG_NB_FRAME, the count is
+// exactly 4.0 and every product has the bits it had with the literal.  Every `>= 0` test reads both sentinels as "no unknown".
+constexpr int CG_NB_NONE = -1, CG_NB_FRAME = -2;
+__device__ __forceinline__ double cg_diag(int u, int d, int l, int r) {
+  return (double)(4 - (u == CG_NB_FRAME) - (d == CG_NB_FRAME) - (l == CG_NB_FRAME) - (r == CG_NB_FRAME));
+}
+
+// Harmonic in-fill: A x = b with A = D - adjacency(masked), D = 4 I or the in-image degree (above), solved by CG in float64 by ONE
 // workgroup per edit (deterministic fixed-tree reductions).  The vectors are indexed by UNKNOWN (compact, coalesced);
 // the four neighbour unknowns of every unknown are resolved once through a pixel -> unknown map, so an iteration is
 // three streaming passes plus four gathers per unknown.  (Used for holes of more than CG_SLOTS * 1024 pixels; smaller
@@ -724,9 +735,10 @@ __global__ void __launch_bounds__(1024) k_cg_fill(int res, float* disp, const ui
                                                   double* __restrict__ vq, int max_iter,
                                                   double tol2, int* counts_out, const float* rhs_extra, int min_n,
                                                   int* pixmap, int2* nb_ud, size_t nb_ud_stride, int2* nb_lr,
-                                                  size_t nb_lr_stride) {
+                                                  size_t nb_lr_stride, int border) {
   __shared__ double sm[16];
   const int e = blockIdx.x, R2 = res * res;
+  const int off = border ? CG_NB_FRAME : CG_NB_NONE;     // what a slot beyond the frame holds
   const int n = counts[e * count_stride + slot_n];
   if (n <= min_n) return;                                // solved on chip by cg_fill_lds (inside k_cg_fill_multi)
   float* d = disp + (size_t)e * R2;
@@ -748,10 +760,10 @@ __global__ void __launch_bounds__(1024) k_cg_fill(int res, float* disp, const ui
     int pix = U[i], y = pix / res, xx = pix - y * res;
     double b = 0.0;
     int2 ud = make_int2(-1, -1), lr = make_int2(-1, -1);
-    if (y > 0) { if (!mk[pix - res]) b += (double)d[pix - res]; else ud.x = map[pix - res]; }
-    if (y < res - 1) { if (!mk[pix + res]) b += (double)d[pix + res]; else ud.y = map[pix + res]; }
-    if (xx > 0) { if (!mk[pix - 1]) b += (double)d[pix - 1]; else lr.x = map[pix - 1]; }
-    if (xx < res - 1) { if (!mk[pix + 1]) b += (double)d[pix + 1]; else lr.y = map[pix + 1]; }
+    if (y > 0) { if (!mk[pix - res]) b += (double)d[pix - res]; else ud.x = map[pix - res]; } else ud.x = off;
+    if (y < res - 1) { if (!mk[pix + res]) b += (double)d[pix + res]; else ud.y = map[pix + res]; } else ud.y = off;
+    if (xx > 0) { if (!mk[pix - 1]) b += (double)d[pix - 1]; else lr.x = map[pix - 1]; } else lr.x = off;
+    if (xx < res - 1) { if (!mk[pix + 1]) b += (double)d[pix + 1]; else lr.y = map[pix + 1]; } else lr.y = off;
     if (rhs_extra) b -= (double)rhs_extra[(size_t)e * R2 + pix];
     nud[i] = ud; nlr[i] = lr;
     x[i] = 0.0;
@@ -770,7 +782,7 @@ __global__ void __launch_bounds__(1024) k_cg_fill(int res, float* disp, const ui
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
       const int2 ud = nud[i], lr = nlr[i];
       const double pi = p[i];
-      double a = 4.0 * pi;
+      double a = cg_diag(ud.x, ud.y, lr.x, lr.y) * pi;
       if (ud.x >= 0) a -= p[ud.x];
       if (ud.y >= 0) a -= p[ud.y];
       if (lr.x >= 0) a -= p[lr.x];
@@ -808,10 +820,11 @@ __global__ void __launch_bounds__(1024) k_cg_fill(int res, float* disp, const ui
 constexpr int CG_SLOTS = 8;      // unknowns per thread: n <= 8192 takes this path
 __device__ __forceinline__ void cg_fill_lds(int e, int res, float* disp, const uint8_t* inpaint, const int* unk, const int* counts,
                                             int count_stride, int slot_n, int slot_it, int* pixmap, int max_iter, double tol2,
-                                            int* counts_out, const float* rhs_extra) {
+                                            int* counts_out, const float* rhs_extra, int border) {
   __shared__ double sm[16];
   __shared__ double sp[CG_SLOTS * 1024];
   const int R2 = res * res;
+  const int off = border ? CG_NB_FRAME : CG_NB_NONE;
   const int n = counts[e * count_stride + slot_n];
   if (n > CG_SLOTS * 1024) return;
   float* d = disp + (size_t)e * R2;
@@ -835,10 +848,10 @@ __device__ __forceinline__ void cg_fill_lds(int e, int res, float* disp, const u
     if (i < n) {
       const int pix = U[i], y = pix / res, xx = pix - y * res;
       double b = 0.0;
-      if (y > 0) { if (!mk[pix - res]) b += (double)d[pix - res]; else nb[sl][0] = map[pix - res]; }
-      if (y < res - 1) { if (!mk[pix + res]) b += (double)d[pix + res]; else nb[sl][1] = map[pix + res]; }
-      if (xx > 0) { if (!mk[pix - 1]) b += (double)d[pix - 1]; else nb[sl][2] = map[pix - 1]; }
-      if (xx < res - 1) { if (!mk[pix + 1]) b += (double)d[pix + 1]; else nb[sl][3] = map[pix + 1]; }
+      if (y > 0) { if (!mk[pix - res]) b += (double)d[pix - res]; else nb[sl][0] = map[pix - res]; } else nb[sl][0] = off;
+      if (y < res - 1) { if (!mk[pix + res]) b += (double)d[pix + res]; else nb[sl][1] = map[pix + res]; } else nb[sl][1] = off;
+      if (xx > 0) { if (!mk[pix - 1]) b += (double)d[pix - 1]; else nb[sl][2] = map[pix - 1]; } else nb[sl][2] = off;
+      if (xx < res - 1) { if (!mk[pix + 1]) b += (double)d[pix + 1]; else nb[sl][3] = map[pix + 1]; } else nb[sl][3] = off;
       if (rhs_extra) b -= (double)rhs_extra[(size_t)e * R2 + pix];
       r[sl] = b;
       sp[i] = b;
@@ -857,7 +870,7 @@ __device__ __forceinline__ void cg_fill_lds(int e, int res, float* disp, const u
       const int i = threadIdx.x + sl * 1024;
       if (i < n) {
         const double pi = sp[i];
-        double a = 4.0 * pi;
+        double a = cg_diag(nb[sl][0], nb[sl][1], nb[sl][2], nb[sl][3]) * pi;
         if (nb[sl][0] >= 0) a -= sp[nb[sl][0]];
         if (nb[sl][1] >= 0) a -= sp[nb[sl][1]];
         if (nb[sl][2] >= 0) a -= sp[nb[sl][2]];
@@ -953,13 +966,14 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
                                                         double* vr, double* vp0, double* vp1, int max_iter, double tol2,
                                                         int* counts_out, const float* rhs_extra, int min_n, int* pixmap,
                                                         int2* nb_ud, size_t nb_ud_stride, int2* nb_lr, size_t nb_lr_stride,
-                                                        CgSync* sync) {
+                                                        CgSync* sync, int border) {
   __shared__ double sm[16];
   const int e = blockIdx.y, wg = blockIdx.x, R2 = res * res;
   const int n = counts[e * count_stride + slot_n];
   if (n <= min_n) {                                                 // small enough for one CU's LDS: workgroup 0 solves it on chip
     if (wg == 0 && min_n > 0)
-      cg_fill_lds(e, res, disp, inpaint, unk, counts, count_stride, slot_n, slot_it, pixmap, max_iter, tol2, counts_out, rhs_extra);
+      cg_fill_lds(e, res, disp, inpaint, unk, counts, count_stride, slot_n, slot_it, pixmap, max_iter, tol2, counts_out, rhs_extra,
+                  border);
     return;
   }
   if (n > CGM_WGS * CGM_EPT * 1024) return;                        // (uniform over the system's workgroups)
@@ -1002,12 +1016,13 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
     rl[k] = 0.0; wl[k] = 0.0; zl[k] = 0.0; sl[k] = 0.0;
     if (i < (unsigned)i1) {
       const int pix = U[i], y = pix / res, xx = pix - y * res;
+      const int off = border ? CG_NB_FRAME : CG_NB_NONE;
       double b = 0.0;
       int2 ud = make_int2(-1, -1), lr = make_int2(-1, -1);
-      if (y > 0) { if (!mk[pix - res]) b += (double)d[pix - res]; else ud.x = map[pix - res]; }
-      if (y < res - 1) { if (!mk[pix + res]) b += (double)d[pix + res]; else ud.y = map[pix + res]; }
-      if (xx > 0) { if (!mk[pix - 1]) b += (double)d[pix - 1]; else lr.x = map[pix - 1]; }
-      if (xx < res - 1) { if (!mk[pix + 1]) b += (double)d[pix + 1]; else lr.y = map[pix + 1]; }
+      if (y > 0) { if (!mk[pix - res]) b += (double)d[pix - res]; else ud.x = map[pix - res]; } else ud.x = off;
+      if (y < res - 1) { if (!mk[pix + res]) b += (double)d[pix + res]; else ud.y = map[pix + res]; } else ud.y = off;
+      if (xx > 0) { if (!mk[pix - 1]) b += (double)d[pix - 1]; else lr.x = map[pix - 1]; } else lr.x = off;
+      if (xx < res - 1) { if (!mk[pix + 1]) b += (double)d[pix + 1]; else lr.y = map[pix + 1]; } else lr.y = off;
       if (rhs_extra) b -= (double)rhs_extra[(size_t)e * R2 + pix];
       nud[i] = ud; nlr[i] = lr;                  // (read back by this thread only)
       x[i] = 0.0;
@@ -1033,7 +1048,7 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
     const unsigned i = (unsigned)i0 + threadIdx.x + k * 1024u;
     if (i < (unsigned)i1) {
       const int2 ud = nud[i], lr = nlr[i];
-      double a = 4.0 * rl[k];
+      double a = cg_diag(ud.x, ud.y, lr.x, lr.y) * rl[k];
       if (ud.x >= 0) a -= cg_get(r + ud.x);
       if (ud.y >= 0) a -= cg_get(r + ud.y);
       if (lr.x >= 0) a -= cg_get(r + lr.x);
@@ -1055,7 +1070,7 @@ __global__ void __launch_bounds__(1024) k_cg_fill_multi(int res, float* disp, co
   };
   // A v at unknown i: the own value from a register, the neighbours' read past the caches from the array v was published in
   auto lap_at = [&](const double* v, double own, int2 ud, int2 lr) {
-    double a = 4.0 * own;
+    double a = cg_diag(ud.x, ud.y, lr.x, lr.y) * own;
     if (ud.x >= 0) a -= cg_get(v + ud.x);
     if (ud.y >= 0) a -= cg_get(v + ud.y);
     if (lr.x >= 0) a -= cg_get(v + lr.x);
@@ -1170,12 +1185,14 @@ __global__ void k_dilate_cross(const uint8_t* src, uint8_t* dst, int res) {
   if (x < res - 1) v |= src[p + 1];
   dst[p] = v ? 1 : 0;
 }
-// 5-point Laplacian with zero padding (scipy.ndimage.convolve(mode='constant')), f64 sum rounded to f32
-__global__ void k_laplacian(const float* img, float* out, int res) {
+// 5-point Laplacian, f64 sum rounded to f32.  border 0: zero padding (scipy.ndimage.convolve(mode='constant')); 1: replicate
+// padding (mode='nearest'): a neighbour beyond the frame is the pixel itself, so the centre weight is the in-image degree
+__global__ void k_laplacian(const float* img, float* out, int res, int border) {
   int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= res * res) return;
   int y = p / res, x = p - y * res;
-  double a = -4.0 * (double)img[p];
+  const int deg = border ? (y > 0) + (y < res - 1) + (x > 0) + (x < res - 1) : 4;
+  double a = -(double)deg * (double)img[p];
   if (y > 0) a += (double)img[p - res];
   if (y < res - 1) a += (double)img[p + res];
   if (x > 0) a += (double)img[p - 1];
@@ -1405,7 +1422,9 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
                                uint8_t* corr_inst, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
                                int footprints, float max_ratio, int corr_capacity, const float* donor_depth = nullptr,
                                int n_host_objects = -1, const double* views = nullptr, const uint8_t* has_view = nullptr,
-                               const uint8_t* bg_valid = nullptr, int64_t* bg_corr = nullptr, int32_t* bg_counts = nullptr) {
+                               const uint8_t* bg_valid = nullptr, int64_t* bg_corr = nullptr, int32_t* bg_counts = nullptr,
+                               int infill_border = 0) {
+  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
   DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start && inst_obj, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
@@ -1566,10 +1585,11 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   DH_CHECK_HIP(hipMemsetAsync(w.cgsync, 0, (size_t)K * sizeof(CgSync), st));
   hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, K), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
                      w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, cg_lds ? CG_SLOTS * 1024 : 0, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P, w.cgsync);
+                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P, w.cgsync,
+                     infill_border);
   hipLaunchKernelGGL(k_cg_fill, dim3(K), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
                      w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CGM_WGS * CGM_EPT * 1024, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P);
+                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P, infill_border);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -1610,6 +1630,29 @@ extern "C" int dh_reproject_camera_workspace_bytes(int res, int n_pts, int n_edi
   return DH_OK;
 }
 
+// The in-fill border: the camera entry with the border rule of the harmonic in-fill (0 = zero, 1 = reflect; see CG_NB_FRAME).
+// Per call, not per edit; the workspace is the camera entry's.
+extern "C" int dh_reproject_border_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                          int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                          const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                          const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                          uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                          int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                          void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
+                                          const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
+                                          int n_host_objects, const double* views, const uint8_t* has_view,
+                                          const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border) {
+  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
+  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
+  DH_REQUIRE(n_edits >= 1, "bad sizes");
+  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
+                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
+                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
+                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
+                             infill_border);
+}
+
+// the call with the zero border
 extern "C" int dh_reproject_camera_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
                                           int n_objects, const int32_t* obj_start, int res, const float* grid_x,
                                           const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
@@ -1620,12 +1663,10 @@ extern "C" int dh_reproject_camera_edits(const float* depth, const float* bg_dep
                                           const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
                                           int n_host_objects, const double* views, const uint8_t* has_view,
                                           const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts) {
-  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
-  DH_REQUIRE(n_edits >= 1, "bad sizes");
-  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
-                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
-                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
-                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts);
+  return dh_reproject_border_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy,
+                                   n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
+                                   workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances, inst_obj,
+                                   corr_inst, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts, 0);
 }
 
 // the call without a view
@@ -1744,11 +1785,15 @@ extern "C" int dh_reproject_background_workspace_bytes(int res, size_t* bytes) {
 // launch).  The view lives in the one transform row the carving holds and the background never reads; with it the points go
 // through k_points' view path (no clamp: points out of frame bid for nothing), the pixels no point reached stay out of the
 // min / max, and every owned background point with bg_valid != 0 yields a row (bg_corr [res * res][4], bg_counts [1]).
-extern "C" int dh_reproject_camera_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+//
+// dh_reproject_border_background: the same with the border rule of the harmonic in-fill (0 = zero, 1 = reflect); the workspace
+// is dh_reproject_background_workspace_bytes' either way.
+extern "C" int dh_reproject_border_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
                                                float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
                                                float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
                                                void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
-                                               int32_t* bg_counts) {
+                                               int32_t* bg_counts, int infill_border) {
+  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
   DH_REQUIRE(bg_depth && grid_x && grid_y, "null input");
   DH_REQUIRE(zmap && disparity && counts && workspace, "null output");
   DH_REQUIRE(res >= 2 && res <= 32768, "bad sizes");
@@ -1795,12 +1840,23 @@ extern "C" int dh_reproject_camera_background(const float* bg_depth, int res, co
   DH_CHECK_HIP(hipMemsetAsync(w.cgsync, 0, sizeof(CgSync), st));
   hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, 1), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
                      w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CG_SLOTS * 1024, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2, w.cgsync);
+                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2, w.cgsync,
+                     infill_border);
   hipLaunchKernelGGL(k_cg_fill, dim3(1), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
                      w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CGM_WGS * CGM_EPT * 1024, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2);
+                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2, infill_border);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+// the call with the zero border
+extern "C" int dh_reproject_camera_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                                               float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
+                                               float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                               void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
+                                               int32_t* bg_counts) {
+  return dh_reproject_border_background(bg_depth, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, bounds, zmap, disparity, counts,
+                                        workspace, workspace_bytes, stream, view, bg_valid, bg_corr, bg_counts, 0);
 }
 
 // the call without a view
@@ -1848,9 +1904,12 @@ extern "C" int dh_laplacian_blend_workspace_bytes(int res, size_t* bytes) {
 // DiffusionHandles.set_foreground (diffusion_handles.py:90-111) = utils.solve_laplacian_depth (utils.py:49-102)
 // over binary_dilation(fg_mask, iterations): out = depth outside the dilated mask, inside the solution of
 // 4 x - sum(masked nbrs) = sum(known depth nbrs) - laplacian(bg_depth).
-extern "C" int dh_laplacian_blend(const float* depth, const float* bg_depth, const uint8_t* fg_mask, int res,
-                                  int dilate_iters, float* out, int32_t* counts, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+// infill_border = 1 (reflect): the diagonal is the in-image degree and the Laplacian of bg_depth uses replicate padding, so
+// depth == bg_depth on the ring still gives out == bg_depth inside.  The workspace is dh_laplacian_blend_workspace_bytes'.
+extern "C" int dh_laplacian_blend_border(const float* depth, const float* bg_depth, const uint8_t* fg_mask, int res,
+                                         int dilate_iters, float* out, int32_t* counts, void* workspace,
+                                         size_t workspace_bytes, void* stream, int infill_border) {
+  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
   DH_REQUIRE(depth && bg_depth && fg_mask && out && counts && workspace && res >= 2 && dilate_iters >= 0, "bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const int R2 = res * res;
@@ -1870,15 +1929,24 @@ extern "C" int dh_laplacian_blend(const float* depth, const float* bg_depth, con
     hipLaunchKernelGGL(k_dilate_cross, dim3(cdiv(R2, 256)), dim3(256), 0, st, src, dst, res);
     uint8_t* t = src; src = dst; dst = t;
   }
-  hipLaunchKernelGGL(k_laplacian, dim3(cdiv(R2, 256)), dim3(256), 0, st, bg_depth, lap, res);
+  hipLaunchKernelGGL(k_laplacian, dim3(cdiv(R2, 256)), dim3(256), 0, st, bg_depth, lap, res, infill_border);
   DH_CHECK_HIP(hipMemcpyAsync(out, depth, (size_t)R2 * 4, hipMemcpyDeviceToDevice, st));
   DH_CHECK_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int), st));
   compact(src, R2, 1, 0, unk, 0, counts + 2, 1, bc, st);
   DH_CHECK_HIP(hipMemsetAsync(cgs, 0, sizeof(CgSync), st));
   hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, 1), dim3(1024), 0, st, res, out, src, unk, counts, 4, 2, 3, vx, vr, vp, vq,
-                     cg_cap(50000), 1e-24, counts, (const float*)lap, CG_SLOTS * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2, cgs);
+                     cg_cap(50000), 1e-24, counts, (const float*)lap, CG_SLOTS * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2, cgs,
+                     infill_border);
   hipLaunchKernelGGL(k_cg_fill, dim3(1), dim3(1024), 0, st, res, out, src, unk, counts, 4, 2, 3, vx, vr, vp, vq, cg_cap(50000),
-                     1e-24, counts, (const float*)lap, CGM_WGS * CGM_EPT * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2);
+                     1e-24, counts, (const float*)lap, CGM_WGS * CGM_EPT * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2,
+                     infill_border);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+// the call with the zero border
+extern "C" int dh_laplacian_blend(const float* depth, const float* bg_depth, const uint8_t* fg_mask, int res,
+                                  int dilate_iters, float* out, int32_t* counts, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  return dh_laplacian_blend_border(depth, bg_depth, fg_mask, res, dilate_iters, out, counts, workspace, workspace_bytes, stream, 0);
 }

@@ -7,7 +7,7 @@ Mirrors /root/reference/diffhandles/depth_transform.py:73-89 (`transform_depth`)
 `reproject` is the batched form (K edits of one image in one launch sequence) that the
 reference does not have: `reproject_plan` decides everything on the host, `_run_plan` allocates
 and launches (DESIGN.md "One host path for the re-projection"); `reproject_edits` ..
-`reproject_camera_edits` are that call under the names and parameter lists they grew up with.
+`reproject_border_edits` are that call under the names and parameter lists they grew up with.
 """
 import ctypes
 import types
@@ -276,6 +276,28 @@ def mesh_has_no_footprints(footprints, footprint_max_ratio, what):
         raise NotImplementedError(f"{what}: depth_transform_mode 'mesh' has no footprints (got footprints=True); use 'pc'")
 
 
+INFILL_BORDERS = ("zero", "reflect")          # the C value is the index (include/diffhandles_hip.h, "The image border of the in-fill")
+
+
+def check_infill_border(value, what="infill_border"):
+    """The image border of the in-fill -> 0 (None or "zero": a neighbour beyond the frame is a known 0) or 1 ("reflect": the
+    mirror ghost cell, zero normal derivative at the frame).  ValueError naming the call for anything else.  Host only."""
+    if value is None:
+        return 0
+    if isinstance(value, str) and value in INFILL_BORDERS:
+        return INFILL_BORDERS.index(value)
+    raise ValueError(f"{what}: infill_border must be 'zero' or 'reflect' (or None = 'zero'), got {value!r}")
+
+
+def mesh_has_no_infill_border(value, what):
+    """Mesh mode in-fills against zero only: the setting is checked as the point mode checks it, then "reflect" is refused.
+    `transform_depth_mesh` and `transform_depth` keep the parameter lists they have and take no border, so the callers that
+    read the setting (DiffusionHandles' conf key, tools/run_edit.py --infill-border) refuse it for them here.  Host only."""
+    if check_infill_border(value, what):
+        raise NotImplementedError(f"{what}: depth_transform_mode 'mesh' has no reflecting in-fill border (got "
+                                  f"infill_border={value!r}); use 'pc'")
+
+
 def check_instances(instances, n_masks, what="instances"):
     """The instance table of an edit with copies -> list of N mask indices (None -> None: one instance per mask).
     ValueError naming `what` and the instance for more than 8 instances, an entry that is not an integer in 0 .. n_masks - 1,
@@ -432,11 +454,12 @@ def _plan(kind, entry=None, workspace_query=None, **fields):
     inst              the instance table over the M + D masks (one instance per mask where the caller gave none)
     masks_u8          [M + D, res * res] uint8, where the masks are
     vacated           [res * res] bool union of the removed masks, or None
-    covered           camera calls: [res * res] bool, host masks and removed masks (bg_valid is its complement), or None"""
+    covered           camera calls: [res * res] bool, host masks and removed masks (bg_valid is its complement), or None
+    infill_border     0 (zero) or 1 (reflect: the border entries run, with the arguments the named entry lacks left empty)"""
     p = types.SimpleNamespace(kind=kind, entry=entry, workspace_query=workspace_query, N=0, kept=[], n_host_kept=0, caller=[],
                               obj_start=np.zeros(1, dtype=np.int32), inst_obj=np.zeros(0, dtype=np.int32),
                               inst_start=np.zeros(1, dtype=np.int32), n_fg=0, n_pts=0, cap=0, with_table=False, inst=None, masks_u8=None,
-                              vacated=None, covered=None)
+                              vacated=None, covered=None, infill_border=0)
     vars(p).update(fields)
     return p
 
@@ -482,7 +505,7 @@ def _plan_pure_camera(shape, removed):
 
 
 def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None, donor_depth=None, donor_masks=None, cameras=None,
-                   footprints=False, footprint_max_ratio=None, return_instances=False, what=None):
+                   footprints=False, footprint_max_ratio=None, return_instances=False, what=None, infill_border="zero"):
     """Everything `reproject` decides before it touches the compute device -> the record of `_plan`.  depth: the depth or its shape; the
     other arguments are `reproject`'s.  Every host check of the call (ValueError / NotImplementedError / RuntimeError with the
     texts the named functions always had; `what` is the caller's name in the two refusals of a call without a foreground mask)
@@ -492,6 +515,7 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     shape = tuple(getattr(depth, "shape", depth))
     removal = "reproject_removal_edits"
     footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
+    border = check_infill_border(infill_border, "reproject_border_edits")
     fg_masks = list(fg_masks)
     edits = [list(tfs) for tfs in edits]
     cams = None
@@ -521,9 +545,11 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     donor_list = [] if donor is None else donor[1]
     D = len(donor_list)
     common = dict(M=M, D=D, return_instances=bool(return_instances), footprints=footprints, ratio=ratio, cams=cams, removed=removed,
-                  removed_given=removed_masks is not None, donor=donor)
+                  removed_given=removed_masks is not None, donor=donor, infill_border=border)
     background = ("dh_reproject_background", "dh_reproject_background_workspace_bytes")
     camera_background = ("dh_reproject_camera_background", "dh_reproject_background_workspace_bytes")
+    if border:          # one entry for both kinds without a foreground point; the workspace does not grow
+        background = camera_background = ("dh_reproject_border_background", "dh_reproject_background_workspace_bytes")
     if M == 0 and (removed or cams is not None) and donor is None:
         for e, tfs in enumerate(edits):
             if len(tfs) != 0:
@@ -621,6 +647,9 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
         query = "dh_reproject_instances_workspace_bytes"
     else:
         entry, query = "dh_reproject_footprint_edits", "dh_reproject_footprints_workspace_bytes"
+    if border:          # the camera entry's list and a trailing border; sized by the query of the call it extends
+        entry = "dh_reproject_border_edits"
+        query = "dh_reproject_camera_workspace_bytes" if cams is not None else "dh_reproject_instances_workspace_bytes"
     return _plan("objects", entry, query, res=res, kept=kept, obj_start=obj_start, n_host_kept=sum(1 for m in kept if m < M),
                          caller=caller, inst_obj=inst_obj, inst_start=inst_start, n_fg=n_fg, n_pts=n_pts,
                          cap=res * res if footprints else n_pts,          # one row per target pixel with footprints, per point without
@@ -655,7 +684,7 @@ def _workspace(p, g):
     """The workspace of the plan's entry, sized by the query the plan names."""
     if p.kind != "objects":
         sizes = (g.res,)
-    elif p.with_table:
+    elif p.with_table or p.infill_border:
         sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), int(p.footprints))
     else:
         sizes = (g.res, p.n_fg, g.K, len(p.kept), int(p.footprints))
@@ -689,7 +718,8 @@ def _view_ptr(view):
 def _run_background(p, g):
     """The kinds without a foreground point.  "pure_removal": dh_reproject_background once, its result K times.  "pure_camera":
     dh_reproject_camera_background once per edit, with the edit's view (an edit without a camera: without a view, the pure
-    removal's result); every row is a background row, instance index N."""
+    removal's result); every row is a background row, instance index N.  With a reflecting in-fill border both kinds run
+    dh_reproject_border_background (a pure removal: without a view)."""
     camera = p.kind == "pure_camera"
     dev, res, K = g.dev, g.res, g.K
     views = [None if c is None else view_row(c) for c in p.cams] if camera else [None]
@@ -708,6 +738,10 @@ def _run_background(p, g):
                 _lib.ptr(disp[e]), _lib.ptr(counts[e]), _lib.ptr(ws), ws_bytes, g.st)
         if camera:
             args += (_view_ptr(view), _lib.ptr(bg_valid), _lib.ptr(bg_corr[e]), _lib.ptr(bg_counts[e:]))
+        elif p.infill_border:
+            args += (None, None, None, None)
+        if p.infill_border:
+            args += (p.infill_border,)
         _lib.check(getattr(g.L, p.entry)(*args), p.entry)
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
@@ -735,7 +769,8 @@ def _run_background(p, g):
 def _run_objects(p, g):
     """The kind with foreground points: the pixel lists of the kept masks, the buffers, the entry the plan names (each of
     dh_reproject_footprint_edits, _instance_edits, _donor_edits and _camera_edits takes the arguments of the one before it and a
-    few more), then the results and the debug dict."""
+    few more; dh_reproject_border_edits takes the camera entry's and the border, with the identity table, no donor and no view
+    where the plan has none), then the results and the debug dict."""
     dev, res, K, L = g.dev, g.res, g.K, g.L
     R2, Mk, Nk, n_fg, n_pts, cap = res * res, len(p.kept), len(p.caller), p.n_fg, p.n_pts, p.cap
     camera, donor = p.cams is not None, p.donor is not None
@@ -765,8 +800,9 @@ def _run_objects(p, g):
     corr_inst = None
     if p.with_table:
         corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
+    if p.with_table or p.infill_border:
         args += (Nk, p.inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _lib.ptr(corr_inst))
-    if camera or donor:
+    if camera or donor or p.infill_border:
         dd = p.donor[0].detach().to(dev, torch.float32).contiguous() if donor else None
         args += (_lib.ptr(dd), p.n_host_kept)
     if camera:
@@ -782,6 +818,10 @@ def _run_objects(p, g):
         bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
         args += (_view_ptr(views), has_view.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _lib.ptr(bg_valid), _lib.ptr(bg_corr),
                  _lib.ptr(bg_counts))
+    elif p.infill_border:
+        args += (None, None, None, None, None)
+    if p.infill_border:
+        args += (p.infill_border,)
     _lib.check(getattr(L, p.entry)(*args), p.entry)
     row_donor = donor_rows(corr_inst, [p.inst[n] for n in p.caller], p.M) if donor else None
     if p.with_table and p.caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
@@ -822,7 +862,8 @@ def _run_objects(p, g):
 
 def reproject(depth, bg_depth, fg_masks, intrinsics, edits, *, instances=None, removed_masks=None, donor_depth=None,
               donor_masks=None, cameras=None, use_input_depth_normalization=False, return_debug=False,
-              device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False, what=None):
+              device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False, what=None,
+              infill_border="zero"):
     """K edits of one image (not in the reference, which has the one-object, one-edit call): `reproject_plan` decides on the
     host, `_run_plan` allocates and launches.  The named functions below are this call with fewer keywords.
 
@@ -893,8 +934,8 @@ def reproject(depth, bg_depth, fg_masks, intrinsics, edits, *, instances=None, r
 
     Camera moves (DESIGN.md "Camera moves") -- cameras: None, or a list of K entries, one camera (`check_camera`) or None per
     edit.  In an edit with a camera every point of the list, background included, is seen from the moved viewpoint: the points
-    that leave the frame are dropped (no clamp onto the border), the pixels no point reaches are in-filled (zero beyond the image
-    border: a known limit of the strip a move uncovers there), and the background yields correspondence rows of its own -- a
+    that leave the frame are dropped (no clamp onto the border), the pixels no point reaches are in-filled (against zero beyond
+    the image border unless infill_border="reflect", below), and the background yields correspondence rows of its own -- a
     background pixel outside the host's foreground and removed masks whose point owns a target pixel outside the cleaned mask.
     A camera call returns the instance array (return_instances is implied): the instance rows first, in the order they always
     had, then the background rows in ascending source pixel order with instance index N (the number of instances).  An edit
@@ -905,10 +946,17 @@ def reproject(depth, bg_depth, fg_masks, intrinsics, edits, *, instances=None, r
     edit, NotImplementedError for footprints with a camera.  cameras=None, or all None, is the call without the keyword, byte
     for byte, with the same launches.
 
+    In-fill border (DESIGN.md "In-fill border") -- infill_border: "zero" (or None; the default: a neighbour beyond the frame is a
+    known 0, which pulls an in-fill region that touches the frame towards disparity 0 there) or "reflect" (the mirror ghost
+    cell: zero normal derivative at the frame, the diagonal of an unknown is the number of its neighbours inside the image).
+    One setting per call.  It changes the disparity inside in-fill components that touch the frame and nothing else: every
+    integer output stays, and "zero" is the call without the keyword, byte for byte, through the same entries.  Composes with
+    everything above.  ValueError (`check_infill_border`) for any other value.
+
     Every refusal precedes the first launch of the library (they are `reproject_plan`'s)."""
     p = reproject_plan(depth, fg_masks, edits, instances=instances, removed_masks=removed_masks, donor_depth=donor_depth,
                        donor_masks=donor_masks, cameras=cameras, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
-                       return_instances=return_instances, what=what)
+                       return_instances=return_instances, what=what, infill_border=infill_border)
     return _run_plan(p, depth, bg_depth, intrinsics, use_input_depth_normalization, return_debug, device_correspondences)
 
 
@@ -963,11 +1011,21 @@ def reproject_camera_edits(depth, bg_depth, fg_masks, intrinsics, edits, instanc
                            device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
                            cameras=None):
     """`reproject` for edits that may also move the viewpoint."""
+    return reproject_border_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, removed_masks, donor_depth, donor_masks,
+                                  use_input_depth_normalization, return_debug, device_correspondences, footprints,
+                                  footprint_max_ratio, return_instances, cameras)
+
+
+def reproject_border_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
+                           donor_masks=None, use_input_depth_normalization=False, return_debug=False,
+                           device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
+                           cameras=None, infill_border="zero"):
+    """`reproject` with the image border of the in-fill ("zero" or "reflect"); `reproject_camera_edits` is its call without it."""
     return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=instances, removed_masks=removed_masks,
                      donor_depth=donor_depth, donor_masks=donor_masks, cameras=cameras,
                      use_input_depth_normalization=use_input_depth_normalization, return_debug=return_debug,
                      device_correspondences=device_correspondences, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
-                     return_instances=return_instances)
+                     return_instances=return_instances, infill_border=infill_border)
 
 
 INFILL_BARRIER_TIMEOUT, INFILL_NOT_CONVERGED, INFILL_BREAKDOWN = -1, -2, -3      # counts[..., 3] < 0 (geometry.hip)
@@ -1070,7 +1128,8 @@ def transform_depth_mesh(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, r
                          footprint_max_ratio=None):
     """depth_transform.py:91-195 with our own HIP triangle rasteriser in place of pytorch3d (parity unpinned).
     pivot: None or three floats, the point the object turns about in place of its centroid; a scale other than 1 raises
-    NotImplementedError before any device work (the mesh path has no scale), and so does footprints=True (point mode only)."""
+    NotImplementedError before any device work (the mesh path has no scale), and so does footprints=True (point mode only).
+    The mesh path in-fills against zero beyond the image border and has no setting for it (`mesh_has_no_infill_border`)."""
     mesh_has_no_footprints(footprints, footprint_max_ratio, "transform_depth_mesh")
     pivot = _mesh_similarity(scale, pivot, "transform_depth_mesh")
     if depth.dim() != 4 or depth.shape[0] != 1:
@@ -1138,11 +1197,14 @@ def transform_depth(depth, bg_depth, fg_mask, intrinsics, rot_angle=None, rot_ax
     raise ValueError(f"Unknown depth transform mode '{depth_transform_mode}'.")
 
 
-def laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15, return_iterations=False):
+def laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15, return_iterations=False, infill_border="zero"):
     """set_foreground's background-depth update (diffusion_handles.py:90-111): `depth` everywhere except
     inside the dilated foreground mask, where the background depth's Laplacian is integrated from the
     surrounding depth values.  [1,1,H,W] tensors in, [1,1,H,W] float32 out (on depth.device); with return_iterations also
-    the CG iteration count of the solve."""
+    the CG iteration count of the solve.  infill_border: "zero" (or None; the reference's blend) or "reflect" -- the diagonal of
+    an unknown is the number of its neighbours inside the image and the Laplacian of bg_depth uses replicate padding, so a
+    mismatch depth - bg_depth around a mask that touches the frame is no longer forced to 0 there (`reproject`)."""
+    border = check_infill_border(infill_border, "laplacian_depth_blend")
     res = depth.shape[-1]
     if depth.shape[-2] != res:
         raise RuntimeError("square depth maps only")
@@ -1157,8 +1219,12 @@ def laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15, return
     nbytes = ctypes.c_size_t()
     _lib.check(L.dh_laplacian_blend_workspace_bytes(res, ctypes.byref(nbytes)))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-    _lib.check(L.dh_laplacian_blend(_lib.ptr(d), _lib.ptr(bg), _lib.ptr(m), res, int(dilate_iterations), _lib.ptr(out),
-                                    _lib.ptr(counts), _lib.ptr(ws), nbytes.value, _lib.stream_ptr()), "dh_laplacian_blend")
+    args = (_lib.ptr(d), _lib.ptr(bg), _lib.ptr(m), res, int(dilate_iterations), _lib.ptr(out), _lib.ptr(counts), _lib.ptr(ws),
+            nbytes.value, _lib.stream_ptr())
+    if border:
+        _lib.check(L.dh_laplacian_blend_border(*args, border), "dh_laplacian_blend_border")
+    else:
+        _lib.check(L.dh_laplacian_blend(*args), "dh_laplacian_blend")
     its = counts[3:4].cpu()
     _check_infill(its)
     if return_iterations:

@@ -66,27 +66,49 @@ class DiffusionHandles:
         """Background depth = input depth with the hole of the (15x cross-dilated) foreground mask in-filled
         from the background depth's Laplacian (reference diffusion_handles.py:90-111).  fg_mask may be a list of masks
         (several objects, transform_foreground_objects): the blend runs over their union.  The masks of objects an edit DELETES
-        (removed_masks of transform_foreground_objects) belong in that list too: bg_depth is the depth with all of them removed."""
+        (removed_masks of transform_foreground_objects) belong in that list too: bg_depth is the depth with all of them removed.
+        With conf depth_transform_infill_border: reflect the blend treats the image frame as a mirror (_infill_border); the
+        parameter list stays the reference's."""
         if isinstance(fg_mask, (list, tuple)):
             union = fg_mask[0] != 0
             for m in fg_mask[1:]:
                 union = union | (m != 0)
             fg_mask = union.to(fg_mask[0].dtype)
-        return laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15)
+        return laplacian_depth_blend(depth, bg_depth, fg_mask, dilate_iterations=15,
+                                     infill_border=self._infill_border("set_foreground"))
+
+    def _conf_get(self, key, default=None):
+        conf = self.conf
+        return conf.get(key, default) if hasattr(conf, "get") else getattr(conf, key, default)
+
+    def _infill_border(self, what):
+        """The optional top-level conf key depth_transform_infill_border (absent = zero) -> "zero" or "reflect", the keyword of
+        the depth_transform calls (DESIGN.md "In-fill border").  ValueError for any other value; "reflect" under a mode other
+        than 'pc' raises NotImplementedError naming the setting: the mesh mode in-fills against zero only.  No device work."""
+        from .depth_transform import INFILL_BORDERS, check_infill_border, mesh_has_no_infill_border
+        value = self._conf_get("depth_transform_infill_border", None)
+        if self.conf.depth_transform_mode != "pc":
+            mesh_has_no_infill_border(value, f"{what}: conf depth_transform_infill_border")
+        return INFILL_BORDERS[check_infill_border(value, f"{what}: conf depth_transform_infill_border")]
 
     def _footprints(self, what):
         """The optional top-level conf keys depth_transform_footprints (absent = false) and
         depth_transform_footprint_max_ratio (absent = none) as the keywords of the depth_transform calls.  Checked on the host
         (ValueError); a true depth_transform_footprints under a mode other than 'pc' raises NotImplementedError: the mesh mode
-        has no footprints.  No device work."""
+        has no footprints.  The third key of the re-projection, depth_transform_infill_border, is read and checked here too
+        (_infill_border: every edit call passes through this helper before any device work) and travels in
+        _reproject_keywords.  No device work."""
         from .depth_transform import check_footprints, mesh_has_no_footprints
-        conf = self.conf
-        get = conf.get if hasattr(conf, "get") else lambda k, d=None: getattr(conf, k, d)
-        fp, ratio = get("depth_transform_footprints", False), get("depth_transform_footprint_max_ratio", None)
-        if conf.depth_transform_mode != "pc":
+        fp, ratio = self._conf_get("depth_transform_footprints", False), self._conf_get("depth_transform_footprint_max_ratio", None)
+        if self.conf.depth_transform_mode != "pc":
             mesh_has_no_footprints(fp, ratio, f"{what}: conf depth_transform_footprints")
         fp, _ = check_footprints(fp, ratio, f"{what}: conf depth_transform_footprints")
+        self._infill_border(what)
         return dict(footprints=fp, footprint_max_ratio=ratio)
+
+    def _reproject_keywords(self, what):
+        """_footprints and the in-fill border: the keywords of depth_transform.reproject that come from the conf."""
+        return dict(self._footprints(what), infill_border=self._infill_border(what))
 
     def _lock_setup(self, what, activations, depth, release_mask=None):
         """The optional top-level conf keys background_lock (absent = false), background_lock_dilate and
@@ -126,12 +148,14 @@ class DiffusionHandles:
         concurrent lanes that share the U-Net weights (GuidedStableDiffuser.fork); batch = 1 runs single (B = 1) edits on the
         lanes.  Images are bit-identical to the one-stream result at the same batch.  release_mask (conf background_lock
         only): extra area every edit's lock sets free (transform_foreground_objects)."""
-        from .depth_transform import reproject_edits
-        fp = self._footprints("transform_foreground_batch")
+        from .depth_transform import reproject
+        fp = self._reproject_keywords("transform_foreground_batch")
         lk = self._lock_setup("transform_foreground_batch", activations, depth, release_mask)
         with torch.no_grad():
-            edits = reproject_edits(depth, bg_depth, fg_mask, self.diffuser.get_depth_intrinsics(device=depth.device),
-                                    transforms, use_input_depth_normalization, device_correspondences=True, **fp)
+            # (`reproject_edits` keeps its parameter list, which has no border: its body, with the border)
+            edits = reproject(depth, bg_depth, [fg_mask], self.diffuser.get_depth_intrinsics(device=depth.device),
+                              [[tf] for tf in transforms], use_input_depth_normalization=use_input_depth_normalization,
+                              device_correspondences=True, **fp)
             self.last_keep_maps = []
             lock = {} if lk is None else dict(lock=[self._edit_lock(lk, fg_mask, c, depth) for _, c in edits])
             imgs = self._guided_batch(edits, streams, batch, (init_noise, null_text_emb, prompt, activations, fg_weight, bg_weight),
@@ -209,7 +233,7 @@ class DiffusionHandles:
         from .depth_transform import check_instances, check_transform, reproject
         if cameras is not None and len(fg_masks) == 0 and removed_masks is None:
             removed_masks = []          # (checked by _camera_setup: no donor, no footprints, 'pc' mode)
-        fp = self._footprints(what)
+        fp = self._reproject_keywords(what)
         if self.conf.depth_transform_mode != "pc":
             if removed_masks is not None:
                 raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no object removal "
@@ -521,8 +545,8 @@ class DiffusionHandles:
         re-projected in separate calls, and edits with and without it share the batch.  A multi-object edit may carry `camera`
         (camera moves, transform_foreground_objects; fg_masks may then be [] with no transforms: a pure camera move): edits with
         and without a camera share the batch, and edits of one image share its re-projection call."""
-        from .depth_transform import check_instances, check_removed_masks, check_transform, reproject_edits
-        fp = self._footprints("transform_foregrounds")
+        from .depth_transform import check_instances, check_removed_masks, check_transform, reproject
+        fp = self._reproject_keywords("transform_foregrounds")
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
                                       "batched re-projection (only 'pc')")
@@ -631,9 +655,9 @@ class DiffusionHandles:
                 else:
                     tfs = [self._fill_transform([edits[i].get(k) for k in ("rot_angle", "rot_axis", "translation", "scale", "pivot")])
                            for i in idx]
-                    res = reproject_edits(e0["depth"], e0["bg_depth"], e0["fg_mask"],
-                                          self.diffuser.get_depth_intrinsics(device=e0["depth"].device), tfs,
-                                          use_input_depth_normalization, device_correspondences=True, **fp)
+                    res = reproject(e0["depth"], e0["bg_depth"], [e0["fg_mask"]],
+                                    self.diffuser.get_depth_intrinsics(device=e0["depth"].device), [[tf] for tf in tfs],
+                                    use_input_depth_normalization=use_input_depth_normalization, device_correspondences=True, **fp)
                 for i, r in zip(idx, res):
                     reproj[i] = r
             self.last_keep_maps = []
@@ -658,16 +682,25 @@ class DiffusionHandles:
         turned about.  In 'pc' mode a magnified object leaves gaps between its points, bridged only up to the mask CLOSE's
         element (res // 50) -- unless the conf has depth_transform_footprints: true (footprint splatting, point mode only;
         depth_transform_footprint_max_ratio is its optional depth-ratio guard; depth_transform.reproject);
-        'mesh' mode takes a pivot and refuses a scale and footprints (NotImplementedError).  With conf background_lock: true
+        'mesh' mode takes a pivot and refuses a scale, footprints and a reflecting in-fill border (NotImplementedError; conf
+        depth_transform_infill_border: reflect, depth_transform.reproject: both then apply to every edit call and to
+        set_foreground).  With conf background_lock: true
         the edit's latents are held to the reconstruction outside its region (DESIGN.md "Background lock"; both modes)."""
-        fp = self._footprints("transform_foreground")
+        fp = self._reproject_keywords("transform_foreground")
         lk = self._lock_setup("transform_foreground", activations, depth)
         with torch.no_grad():
             geo = dict(depth=depth, bg_depth=bg_depth, fg_mask=fg_mask,
                        intrinsics=self.diffuser.get_depth_intrinsics(device=depth.device),
                        rot_angle=rot_angle, rot_axis=rot_axis, translation=translation,
                        use_input_depth_normalization=use_input_depth_normalization, scale=scale, pivot=pivot)
-            if fp["footprints"]:          # ('pc' mode: _footprints refused the others; transform_depth keeps the reference's list)
+            border = fp.pop("infill_border")
+            if border != "zero":          # ('pc' mode: _footprints refused the others; the named calls keep their lists)
+                from .depth_transform import reproject
+                tf = self._fill_transform((rot_angle, rot_axis, translation, scale, pivot))
+                (edited_disparity, correspondences), = reproject(
+                    depth, bg_depth, [fg_mask], geo["intrinsics"], [[tf]],
+                    use_input_depth_normalization=use_input_depth_normalization, infill_border=border, **fp)
+            elif fp["footprints"]:
                 edited_disparity, correspondences = transform_depth_footprints(**geo, **fp)
             else:
                 edited_disparity, correspondences = transform_depth(**geo, depth_transform_mode=self.conf.depth_transform_mode)

@@ -246,6 +246,35 @@ int dh_reproject_camera_background(const float* bg_depth, int res, const float* 
                                    float* zmap, float* disparity, int32_t* counts,
                                    void* workspace, size_t workspace_bytes, void* stream,
                                    const double* view, const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts);
+/* The image border of the in-fill (not in the reference; DESIGN.md, "In-fill border").  infill_border: 0 = zero -- a neighbour
+ * beyond the frame counts as a known 0, the diagonal of every unknown is 4: what every entry above computes -- or 1 = reflect
+ * -- the mirror ghost cell x_ghost = x_self (zero normal derivative at the frame): the diagonal of an unknown is the number of
+ * its 4-neighbours inside the image (4, 3 on an edge, 2 in a corner); off-diagonals and right-hand side do not change.  A hole
+ * that does not touch the frame is the same system under both.  The border holds for the call, not per edit.
+ *   dh_reproject_border_edits       dh_reproject_camera_edits plus infill_border; that entry is this one's infill_border = 0 call
+ *   dh_reproject_border_background  dh_reproject_camera_background plus infill_border; likewise
+ * The workspaces do NOT grow: size them with dh_reproject_camera_workspace_bytes (or, without a view, the donor / instance
+ * query) and dh_reproject_background_workspace_bytes.  Every integer output is what it is under infill_border = 0; only the
+ * disparity inside in-fill components that touch the frame, and counts[.][3], differ.
+ * DH_ERR_ARG before any launch, outputs untouched, beyond what those entries refuse: infill_border other than 0 or 1. */
+int dh_reproject_border_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                              int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                              const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                              int n_edits, const double* xforms_host, const float* bounds,
+                              float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                              uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream,
+                              int footprints, float max_ratio, int corr_capacity,
+                              int n_instances, const int32_t* inst_obj, uint8_t* corr_inst,
+                              const float* donor_depth, int n_host_objects,
+                              const double* views, const uint8_t* has_view, const uint8_t* bg_valid,
+                              int64_t* bg_corr, int32_t* bg_counts, int infill_border);
+int dh_reproject_border_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                                   float inv_fx, float inv_fy, double fx, double fy, const float* bounds,
+                                   float* zmap, float* disparity, int32_t* counts,
+                                   void* workspace, size_t workspace_bytes, void* stream,
+                                   const double* view, const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts,
+                                   int infill_border);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);
@@ -262,6 +291,14 @@ int dh_laplacian_blend_workspace_bytes(int res, size_t* bytes);
 int dh_laplacian_blend(const float* depth, const float* bg_depth, const uint8_t* fg_mask, int res,
                        int dilate_iters, float* out, int32_t* counts, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* The blend with the in-fill border (above): infill_border = 1 (reflect) solves deg x - sum(masked nbrs) = sum(known depth
+ * nbrs) - laplacian(bg_depth) with deg the number of in-image neighbours and the Laplacian of bg_depth under replicate padding
+ * (scipy.ndimage.convolve(mode="nearest")), so depth == bg_depth around the mask still gives out == bg_depth inside.
+ * dh_laplacian_blend is the infill_border = 0 call.  Same workspace (dh_laplacian_blend_workspace_bytes: it does not grow).
+ * DH_ERR_ARG before any launch, outputs untouched: infill_border other than 0 or 1. */
+int dh_laplacian_blend_border(const float* depth, const float* bg_depth, const uint8_t* fg_mask, int res,
+                              int dilate_iters, float* out, int32_t* counts, void* workspace,
+                              size_t workspace_bytes, void* stream, int infill_border);
 
 /* --------------------------------------------------------------------------------------
  * Correspondences -> grid x grid cell index lists.  Replaces

@@ -17,7 +17,10 @@ two spheres (reproject_instance_edits, instances [0, 1]: what the parent commit 
 sphere of tests/object_insertion_ref.py beside them (reproject_donor_edits: object insertion; profiles/object_insertion/).
 DH_CAMERA=1 (default unset; the two-sphere scene whatever DH_OBJECTS says): two further lines time the K = 8 instance call on the
 two spheres and the same call with eight orbit cameras about the centre pixel (depth_transform.orbit_cameras, -14 .. 14 degrees:
-reproject_camera_edits, camera moves; profiles/camera_moves/); the second line also reports the background rows per edit."""
+reproject_camera_edits, camera moves; profiles/camera_moves/); the second line also reports the background rows per edit.
+DH_BORDER=reflect (default unset = zero): every call of the run in-fills with the reflecting image border (the named calls
+timed here keep their parameter lists, so the setting is given to depth_transform.reproject, which they all are;
+profiles/infill_border/); every line then says so."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -47,6 +50,12 @@ elif M == 2:
     call = lambda **kw: reproject_object_edits(depth, bg_depth, masks, intr, edits, **kw)
 else:
     sys.exit("DH_OBJECTS: 1 or 2")
+border = os.environ.get("DH_BORDER") or "zero"
+if border != "zero":
+    import diffusionhandles_amd.depth_transform as _DT
+    _DT.check_infill_border(border, "DH_BORDER")
+    _reproject = _DT.reproject
+    _DT.reproject = lambda *a, **kw: _reproject(*a, **dict(kw, infill_border=border))
 scale = float(os.environ["DH_SCALE"]) if os.environ.get("DH_SCALE") else None
 footprints = os.environ.get("DH_FOOTPRINTS", "0") not in ("", "0")
 CG_LDS, CG_MULTI = 8192, 65536          # dh_dbg_cg_limits: largest hole solved on chip / by the multi-workgroup CG
@@ -57,6 +66,8 @@ def solver(n):
 
 
 def report(call, label, **fp):
+    if border != "zero":
+        label += f" border={border}"
     if fp:
         label, inner = label + " footprints", call
         call = lambda **kw: inner(**kw, **fp)

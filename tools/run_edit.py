@@ -51,7 +51,8 @@ def load_config(path):
                 if kk not in conf.guided_diffuser and kk not in C.OPTIONAL_GUIDED_KEYS:
                     raise ValueError(f"{path}: unknown key guided_diffuser.{kk}")
                 conf.guided_diffuser[kk] = vv
-        elif k in conf or k in ("background_lock", "background_lock_dilate", "background_lock_feather"):
+        elif k in conf or k in ("background_lock", "background_lock_dilate", "background_lock_feather",
+                                "depth_transform_infill_border"):
             conf[k] = v
         else:
             raise ValueError(f"{path}: unknown key {k}")
@@ -74,6 +75,22 @@ def apply_footprint_args(args, conf):
     fp, ratio = check_footprints(fp, ratio, "--footprints")
     args.footprint_report = dict(footprints=fp, footprint_max_ratio=ratio)
     return args.footprint_report
+
+
+def apply_border_args(args, conf):
+    """--infill-border -> the optional conf key depth_transform_infill_border (DiffusionHandles reads it for --scene,
+    --test-set and --edit-batch alike), checked as the library checks it (ValueError; NotImplementedError for reflect in mesh
+    mode) before any engine is built and before any identity.  Returns what the report carries (nothing for the zero border:
+    the reports of such runs stay what they were)."""
+    from diffusionhandles_amd.depth_transform import INFILL_BORDERS, check_infill_border, mesh_has_no_infill_border
+    if args.infill_border is not None:
+        conf["depth_transform_infill_border"] = args.infill_border
+    value = conf.get("depth_transform_infill_border")
+    if conf.depth_transform_mode != "pc":
+        mesh_has_no_infill_border(value, "--infill-border")
+    border = check_infill_border(value, "--infill-border")
+    args.border_report = dict(infill_border=INFILL_BORDERS[border]) if border else {}
+    return args.border_report
 
 
 def apply_lock_args(args, conf):
@@ -136,6 +153,10 @@ def parse(argv=None):
     ap.add_argument("--footprint-max-ratio", type=float, default=None, metavar="R",
                     help="with --footprints: leave out triangles whose source depths differ by more than the factor R > 1 "
                          "(conf key depth_transform_footprint_max_ratio)")
+    ap.add_argument("--infill-border", default=None, choices=["zero", "reflect"],
+                    help="the image border of the depth in-fill in 'pc' mode (conf key depth_transform_infill_border): reflect = "
+                         "zero normal derivative at the frame, so a region a camera move or a removal uncovers at the frame is "
+                         "not pulled towards disparity 0 there; applies to the re-projection and to set_foreground")
     ap.add_argument("--background-lock", action="store_true",
                     help="hold every edit's latents to the reconstruction outside the region the edit touches (conf key "
                          "background_lock); the identity cache then also keeps the reconstruction trajectory, a release.png in "
@@ -159,6 +180,7 @@ def main():
         conf.depth_transform_mode = args.mode
     args.mode = conf.depth_transform_mode
     apply_footprint_args(args, conf)
+    apply_border_args(args, conf)
     apply_lock_args(args, conf)
     state = {"dh": None}           # the engine is built on first use: a run that skips every scene never touches the GPU
 
@@ -224,7 +246,7 @@ def main():
                 f"{len(reports)} scenes</h3><table border='1' cellspacing='0' cellpadding='4'><tr><th>scene</th><th>edits</th>"
                 f"<th>identity s</th></tr>{rows}</table></body></html>")
     total = dict(test_set=set_name, scenes=reports, config=args.config, depth_transform_mode=conf.depth_transform_mode,
-                 **args.footprint_report, **args.lock_report,
+                 **args.footprint_report, **args.border_report, **args.lock_report,
                  edits_run=sum(1 for r in reports for e in r["edits"] if not e.get("skipped")),
                  edits_skipped=sum(1 for r in reports for e in r["edits"] if e.get("skipped")))
     if batch_seconds is not None:
@@ -415,7 +437,8 @@ def scene_identity(args, dh, p, out, identity=None):
     recon = dh.diffuser.decode_latent_image(latent)
     write_png(os.path.join(out, "recon.png"), recon[0].permute(1, 2, 0).float().cpu().numpy())
     report = dict(resolution=res, mode=args.mode, identity_s=round(t_identity, 2), identity_from_cache=bool(identity_from_cache),
-                  edits=[], **getattr(args, "footprint_report", {}), **getattr(args, "lock_report", {}))
+                  edits=[], **getattr(args, "footprint_report", {}), **getattr(args, "border_report", {}),
+                  **getattr(args, "lock_report", {}))
     if args.identity_batch > 1:
         report["identity_batch"] = args.identity_batch
     return depth, bg_depth, mask, img, null_text, noise, acts, report

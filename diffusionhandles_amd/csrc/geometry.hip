@@ -212,7 +212,9 @@ __device__ __forceinline__ bool has_view(const Xf* views, int e) { return views 
 // arithmetic, its input the f32 background point or the instance's (X, Y, Z) rounded to f32; such an edit has no clamp: a
 // point whose rint(u) or rint(v) (half to even, before any clamp) leaves 0 .. res - 1, or whose Z is not > 0, bids for no
 // pixel and leaves pix = -1.  An edit without a view skips all of it behind the uniform flag.
-template <bool FP>
+// VS (view surfaces, further down; never with FP): an edit with a view also leaves (u, v, Z) of EVERY point of the list -- after
+// the view, before the discard, the clamp and the rounding -- in uvz, 3 doubles per point and edit ([K][P][3]).
+template <bool FP, bool VS = false>
 __global__ void k_points(const float* depth, const float* donor_depth, int n_host, const float* bg_depth, const int* fg_pix,
                          int n_pts, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
@@ -255,6 +257,10 @@ __global__ void k_points(const float* depth, const float* donor_depth, int n_hos
   v = (v * 0.5 + 0.5) * m;
   if (FP && i >= R2) {
     double* o = uvz + ((size_t)e * n_pts + (i - R2)) * 3;
+    o[0] = u; o[1] = v; o[2] = Z;
+  }
+  if (VS && view) {
+    double* o = uvz + ((size_t)e * P + i) * 3;
     o[0] = u; o[1] = v; o[2] = Z;
   }
   const unsigned long long key = sortable_f64(Z);
@@ -308,13 +314,19 @@ __global__ void k_fp_inverse(const int* fg_pix, int n_fg, int* inv) {
 }
 
 // the part of a triangle that no instance changes: F = the fg_pix positions of its three source pixels.  false = a vertex outside
-// the masks, or the depth-ratio guard
+// the masks, or the depth-ratio guard.  BG (view surfaces): a triangle of the background sheet -- F = the source pixels themselves
+// (every quad of the image has its two triangles), depth = bg_depth, inv unread.
+template <bool BG = false>
 __device__ __forceinline__ bool fp_source(int t, int res, const int* inv, const float* depth, float max_ratio, int3& F) {
   const int q = t >> 1, h = t & 1, qy = q / (res - 1), qx = q - qy * (res - 1);
   const int p00 = qy * res + qx, p01 = p00 + 1, p10 = p00 + res, p11 = p10 + 1;
   const int s0 = p10, s1 = h ? p01 : p11, s2 = h ? p00 : p01;
-  F = make_int3(inv[s0], inv[s1], inv[s2]);
-  if ((F.x | F.y | F.z) < 0) return false;
+  if (BG) {
+    F = make_int3(s0, s1, s2);
+  } else {
+    F = make_int3(inv[s0], inv[s1], inv[s2]);
+    if ((F.x | F.y | F.z) < 0) return false;
+  }
   if (max_ratio > 0.f) {          // on the SOURCE depths, f32: a quad across a depth step inside one mask makes no sheet
     const float d0 = depth[s0], d1 = depth[s1], d2 = depth[s2];
     const float zmin = fminf(fminf(d0, d1), d2), zmax = fmaxf(fmaxf(d0, d1), d2);
@@ -326,15 +338,26 @@ __device__ __forceinline__ bool fp_source(int t, int res, const int* inv, const 
 // false = the triangle F does not exist for instance n or is dropped (a vertex outside the mask of the instance, Z <= 0,
 // non-finite u / v, area <= 0, an empty candidate box).  n is uniform where this is called (a loop counter, a wave's list
 // entry): the table is read with scalars.  J holds POINT-LIST positions.
+// VS (view surfaces): uvz holds every point of the list, R2 + n_pts per edit, and the pointer handed in is that of the first
+// FOREGROUND point of edit 0.  The background is one more "instance", n = MAX_OBJECTS, whose slice is the whole image: the
+// point-list positions -R2 .. -1, position j = source pixel - R2, so that the vertex address and the bidder index R2 + j of
+// fp_bid are those of the background point itself.
+template <bool VS = false>
 __device__ __forceinline__ bool fp_setup(const int3 F, int n, int e, int res, int n_pts, const InstTable& tab, const double* uvz,
                                          FpTri& T, int3& J) {
   // fg_pix position -> point-list position of instance n; inside the instance's slice = the pixel is of its mask
-  const int off = tab.off[n], lo = tab.start[n], hi = tab.start[n + 1];
+  int off, lo, hi;
+  if (VS && n == MAX_OBJECTS) {
+    off = res * res; lo = -off; hi = 0;
+  } else {
+    off = tab.off[n]; lo = tab.start[n]; hi = tab.start[n + 1];
+  }
   const int j0 = F.x - off, j1 = F.y - off, j2 = F.z - off;
   if (j0 < lo || j0 >= hi || j1 < lo || j1 >= hi || j2 < lo || j2 >= hi) return false;
-  const double* a = uvz + ((size_t)e * n_pts + j0) * 3;
-  const double* b = uvz + ((size_t)e * n_pts + j1) * 3;
-  const double* c = uvz + ((size_t)e * n_pts + j2) * 3;
+  const double* base = uvz + (size_t)e * (VS ? res * res + n_pts : n_pts) * 3;
+  const double* a = base + (ptrdiff_t)j0 * 3;
+  const double* b = base + (ptrdiff_t)j1 * 3;
+  const double* c = base + (ptrdiff_t)j2 * 3;
   T.u0 = a[0]; T.v0 = a[1]; T.z0 = a[2];
   T.u1 = b[0]; T.v1 = b[1]; T.z1 = b[2];
   T.u2 = c[0]; T.v2 = c[1]; T.z2 = c[2];
@@ -388,37 +411,53 @@ static inline int fp_tier() { return g_fp_tier > 0 ? g_fp_tier : FP_TIER_DEFAULT
 // (appended in pass 1; pass 2 replays the list); the result does not depend on `tier`: atomicMin commutes.
 // The list holds triangle * MAX_OBJECTS + instance (unsigned: 16 res^2 < 2^32 for every res the CLOSE element admits); an
 // instance has at most 2 |mask| triangles, so 2 n_pts entries per edit hold every list (and 2 (res - 1)^2 without copies).
+// VS (view surfaces): only the edits with a view draw; after the instances the triangle of the background sheet, instance code
+// MAX_OBJECTS.  The list then holds triangle * (MAX_OBJECTS + 1) + code, still 32 bits: 18 res^2 < 2^32 up to res = 15 446,
+// and the CLOSE element (res / 50 squared <= MAX_OFFS offsets) stops at res = 3 249.  2 (res - 1)^2 more entries per edit.
+template <bool VS>
+__device__ __forceinline__ void fp_draw(const int3 F, int n, unsigned t, int e, int pass, int res, int n_pts, const InstTable& tab,
+                                        const double* uvz, int tier, unsigned long long* zb, int* ow, unsigned* big_list,
+                                        size_t big_stride, int* big_count) {
+  FpTri T;
+  int3 J;
+  if (!fp_setup<VS>(F, n, e, res, n_pts, tab, uvz, T, J)) return;
+  const long long cand = (long long)(T.c1 - T.c0 + 1) * (T.r1 - T.r0 + 1);
+  if (cand > tier) {
+    if (pass == 1) big_list[(size_t)e * big_stride + atomicAdd(&big_count[e], 1)] = t * (MAX_OBJECTS + (VS ? 1 : 0)) + n;
+    return;
+  }
+  for (int r = T.r0; r <= T.r1; ++r)
+    for (int c = T.c0; c <= T.c1; ++c) fp_bid(T, J, c, r, pass, res, res * res, zb, ow);
+}
+
+template <bool VS>
 __global__ void k_fp_tri(int pass, int res, int n_pts, int n_inst, const int* inv, const InstTable tab, const double* uvz,
                          const float* depth, float max_ratio, int tier, unsigned long long* zbuf, int* owner, unsigned* big_list,
-                         size_t big_stride, int* big_count) {
+                         size_t big_stride, int* big_count, const float* bg_depth, const Xf* views) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
   const int nt = 2 * (res - 1) * (res - 1), R2 = res * res;
   if (t >= nt) return;
-  int3 F;
-  if (!fp_source(t, res, inv, depth, max_ratio, F)) return;
+  if (VS && !has_view(views, e)) return;
   unsigned long long* zb = zbuf + (size_t)e * R2;
   int* ow = owner + (size_t)e * R2;
-  for (int n = 0; n < n_inst; ++n) {
-    FpTri T;
-    int3 J;
-    if (!fp_setup(F, n, e, res, n_pts, tab, uvz, T, J)) continue;
-    const long long cand = (long long)(T.c1 - T.c0 + 1) * (T.r1 - T.r0 + 1);
-    if (cand > tier) {
-      if (pass == 1) big_list[(size_t)e * big_stride + atomicAdd(&big_count[e], 1)] = (unsigned)t * MAX_OBJECTS + n;
-      continue;
-    }
-    for (int r = T.r0; r <= T.r1; ++r)
-      for (int c = T.c0; c <= T.c1; ++c) fp_bid(T, J, c, r, pass, res, R2, zb, ow);
-  }
+  int3 F;
+  if ((!VS || n_inst > 0) && fp_source(t, res, inv, depth, max_ratio, F))
+    for (int n = 0; n < n_inst; ++n) fp_draw<VS>(F, n, (unsigned)t, e, pass, res, n_pts, tab, uvz, tier, zb, ow, big_list, big_stride, big_count);
+  if (VS && fp_source<true>(t, res, nullptr, bg_depth, max_ratio, F))
+    fp_draw<VS>(F, MAX_OBJECTS, (unsigned)t, e, pass, res, n_pts, tab, uvz, tier, zb, ow, big_list, big_stride, big_count);
 }
 
 // wave tier: one 64-lane wave per listed (triangle, instance), the lanes striding over its box
 constexpr int FP_WAVE_BLOCKS = 256;
+template <bool VS>
 __global__ void __launch_bounds__(256) k_fp_wave(int pass, int res, int n_pts, const int* inv, const InstTable tab, const double* uvz,
                                                  const float* depth, float max_ratio, unsigned long long* zbuf, int* owner,
-                                                 const unsigned* big_list, size_t big_stride, const int* big_count) {
+                                                 const unsigned* big_list, size_t big_stride, const int* big_count,
+                                                 const float* bg_depth, const Xf* views) {
   const int e = blockIdx.y, lane = threadIdx.x & 63;
   const int R2 = res * res;
+  if (VS && !has_view(views, e)) return;
+  constexpr unsigned CODES = MAX_OBJECTS + (VS ? 1 : 0);
   const int n = big_count[e];
   unsigned long long* zb = zbuf + (size_t)e * R2;
   int* ow = owner + (size_t)e * R2;
@@ -426,8 +465,13 @@ __global__ void __launch_bounds__(256) k_fp_wave(int pass, int res, int n_pts, c
     FpTri T;
     int3 F, J;
     const unsigned ent = __builtin_amdgcn_readfirstlane(big_list[(size_t)e * big_stride + k]);
-    if (!fp_source((int)(ent / MAX_OBJECTS), res, inv, depth, max_ratio, F)) continue;
-    if (!fp_setup(F, (int)(ent % MAX_OBJECTS), e, res, n_pts, tab, uvz, T, J)) continue;
+    const int code = (int)(ent % CODES);
+    if (VS && code == MAX_OBJECTS) {
+      if (!fp_source<true>((int)(ent / CODES), res, nullptr, bg_depth, max_ratio, F)) continue;
+    } else if (!fp_source((int)(ent / CODES), res, inv, depth, max_ratio, F)) {
+      continue;
+    }
+    if (!fp_setup<VS>(F, code, e, res, n_pts, tab, uvz, T, J)) continue;
     const int W = T.c1 - T.c0 + 1, cand = W * (T.r1 - T.r0 + 1);          // (<= res * res: the box lies inside the image)
     for (int i = lane; i < cand; i += 64) {
       const int dr = i / W;
@@ -463,6 +507,49 @@ __global__ void k_write_corr_target(int R2, int res, const int* fg_pix, const In
   c[2] = t % res;
   c[3] = t / res;
   if (corr_inst) corr_inst[(size_t)e * corr_stride + r] = (uint8_t)n;
+}
+
+// View surfaces, the rows of a call with the setting: an edit with a view takes them per TARGET pixel, row-major.  vis = the
+// owner of the pixel is a foreground point (vis of these edits zeroed before); keep_inst = foreground-owned and inside the cleaned
+// mask (k_write_corr_target writes the rows); keep_bg = owned by background point o with bg_valid[o] != 0 and outside the cleaned
+// mask.  An edit without a view gets no flag: its rows are the point path's.  clean_stride: R2, or 0 for one zero image.
+__global__ void k_vs_flags(int R2, int n_pts, const int* owner, const uint8_t* clean, size_t clean_stride, const uint8_t* bg_valid,
+                           const Xf* views, uint8_t* vis, uint8_t* keep_inst, uint8_t* keep_bg) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  if (p >= R2) return;
+  const size_t o = (size_t)e * R2 + p;
+  uint8_t fi = 0, fb = 0;
+  if (has_view(views, e)) {
+    const int w = owner[o];                        // (unowned: the initial 0x7f7f7f7f, beyond every point of the list)
+    const bool cl = clean[(size_t)e * clean_stride + p] != 0;
+    if (w < R2) {
+      fb = bg_valid[w] && !cl ? 1 : 0;
+    } else if (w < R2 + n_pts) {
+      vis[(size_t)e * n_pts + (w - R2)] = 1;
+      fi = cl ? 1 : 0;
+    }
+  }
+  if (keep_inst) keep_inst[o] = fi;
+  keep_bg[o] = fb;
+}
+
+// background row r of edit e: the r-th flagged target pixel t and its owner o, (o % res, o / res, t % res, t / res)
+__global__ void k_vs_write_bg(int R2, int res, const int* owner, const int* row_idx, const int* bg_counts, long long* bg_corr) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x, e = blockIdx.y;
+  if (r >= bg_counts[e]) return;
+  const int t = row_idx[(size_t)e * R2 + r];
+  const int o = owner[(size_t)e * R2 + t];
+  long long* c = bg_corr + ((size_t)e * R2 + r) * 4;
+  c[0] = o % res;
+  c[1] = o / res;
+  c[2] = t % res;
+  c[3] = t / res;
+}
+
+// the instance rows of a call with view surfaces: counts[e][0] = the point rows (edits without a view) + the target rows
+__global__ void k_vs_add_counts(int K, const int* target_counts, int* counts) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < K) counts[4 * e] += target_counts[e];
 }
 
 __device__ __forceinline__ unsigned int sortable_f32(float x) {
@@ -607,13 +694,16 @@ __global__ void k_morph_bits(const unsigned* src, unsigned* dst, int res, const 
   dst[(size_t)blockIdx.y * wpr * res + idx] = inv_out ? ~acc : acc;
 }
 
+// (target_views: NULL, or the views of a call with view surfaces -- an edit with a view then keeps no POINT, its rows are taken
+// per target pixel)
 __global__ void k_keep_flags(int n_pts, int R2, int P, const int* pix_arr, const uint8_t* vis, const uint8_t* clean,
-                             uint8_t* keep) {
+                             uint8_t* keep, const Xf* target_views) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
   if (j >= n_pts) return;
   int pix = pix_arr[(size_t)e * P + R2 + j];
-  keep[(size_t)e * n_pts + j] = (pix >= 0 && vis[(size_t)e * n_pts + j] && clean[(size_t)e * R2 + pix]) ? 1 : 0;
+  keep[(size_t)e * n_pts + j] =
+      (pix >= 0 && vis[(size_t)e * n_pts + j] && clean[(size_t)e * R2 + pix] && !has_view(target_views, e)) ? 1 : 0;
 }
 
 // row r of edit e: the r-th kept point-list position, its source pixel through the table, its instance beside it
@@ -1280,13 +1370,15 @@ struct ReprojectWs {
   size_t big_stride;
   // camera moves only (a call in which no edit has a view takes nothing: its workspace is what it was)
   Xf* views;
+  // view surfaces only (a view edit with the setting; they share the footprints' members, never taken together): uvz then
+  // holds every point of the list, inv only with foreground points, and the list has the background's slots too
 };
 
 // n_fg: the foreground points of the point list (with copies n_pts, the sum over the instances); M: masks; N: transform rows
 // per edit (instances; 0 = M, the call without copies, whose carving -- and so every workspace query that existed before the
 // copies -- is what it was: the wave tier's list then has a slot per triangle of the grid, else 2 n_pts per edit)
 static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false, int N = 0,
-                  bool camera = false) {
+                  bool camera = false, bool surfaces = false) {
   const size_t R2 = (size_t)res * res, P = R2 + n_fg;
   w.xf = a.take<Xf>((size_t)K * (N > 0 ? N : M));
   w.cen = a.take<float>(4 * M);
@@ -1318,6 +1410,13 @@ static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, boo
     w.big_count = a.take<int>(K);
   }
   w.views = camera ? a.take<Xf>(K) : nullptr;
+  if (surfaces) {
+    w.uvz = a.take<double>((size_t)K * P * 3);
+    w.inv = n_fg > 0 ? a.take<int>(R2) : nullptr;
+    w.big_stride = (size_t)2 * n_fg + (size_t)2 * (res - 1) * (res - 1);
+    w.big_list = a.take<unsigned>((size_t)K * w.big_stride);
+    w.big_count = a.take<int>(K);
+  }
   return a.ok();
 }
 
@@ -1423,8 +1522,13 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
                                int footprints, float max_ratio, int corr_capacity, const float* donor_depth = nullptr,
                                int n_host_objects = -1, const double* views = nullptr, const uint8_t* has_view = nullptr,
                                const uint8_t* bg_valid = nullptr, int64_t* bg_corr = nullptr, int32_t* bg_counts = nullptr,
-                               int infill_border = 0) {
+                               int infill_border = 0, int view_surfaces = 0, float surface_max_ratio = 0.f) {
   DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
+  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
+  DH_REQUIRE(surface_max_ratio == 0.f || (surface_max_ratio > 1.f && surface_max_ratio <= 3.4028234663852886e38f),
+             "surface_max_ratio must be 0 (none) or finite and > 1");
+  DH_REQUIRE(surface_max_ratio == 0.f || view_surfaces, "surface_max_ratio without view_surfaces");
+  DH_REQUIRE(!(view_surfaces && footprints), "view_surfaces with footprints are not supported (footprints stay refused with a view)");
   DH_REQUIRE(depth && bg_depth && fg_pix && grid_x && grid_y && xforms_host && obj_start && inst_obj, "null input");
   DH_REQUIRE(zmap && raw_mask && clean_mask && disparity && vis && target_xy && corr && counts, "null output");
   DH_REQUIRE(res >= 2 && n_fg > 0 && n_edits >= 1, "bad sizes");
@@ -1438,6 +1542,7 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
     DH_REQUIRE(donor_depth, "donor objects without a donor depth");
     DH_REQUIRE(!footprints, "footprints with a donor are not supported (two images share pixel indices)");
     DH_REQUIRE(corr_inst, "a donor needs the instance column (corr_inst)");
+    DH_REQUIRE(!view_surfaces, "view_surfaces with a donor are not supported (two images share pixel indices)");
   }
   if (!donor_depth) donor_depth = depth;
   DH_REQUIRE(max_ratio == 0.f || (max_ratio > 1.f && max_ratio <= 3.4028234663852886e38f),
@@ -1474,6 +1579,10 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
     DH_REQUIRE(!footprints, "footprints with a view are not supported");
     DH_REQUIRE(bg_valid && bg_corr && bg_counts, "a view needs bg_valid, bg_corr and bg_counts");
   }
+  // view surfaces act only where an edit has a view: without one the call is the call without the setting
+  const bool surfaces = view_host != nullptr && view_surfaces != 0;
+  DH_REQUIRE(!surfaces || (long long)corr_capacity >= (long long)res * res,
+             "correspondence capacity too small (res * res rows per edit with view surfaces)");
   hipStream_t st = (hipStream_t)stream;
   const int K = n_edits, M = n_objects, N = n_inst;
   const ObjTable tab = obj_table(M, obj_start, n_fg);
@@ -1482,7 +1591,8 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   const int R2 = res * res, P = R2 + n_pts;
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
-  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N, view_host != nullptr), "workspace too small");
+  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N, view_host != nullptr, surfaces),
+             "workspace too small");
   const size_t corr_stride = (size_t)corr_capacity;
   if (view_host) DH_CHECK_HIP(hipMemcpyAsync(w.views, view_host, (size_t)K * sizeof(Xf), hipMemcpyHostToDevice, st));
 
@@ -1506,12 +1616,31 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   // footprints: the triangle kernels run once per z-buffer pass, thread tier then wave tier (the list is built in pass 1)
   const int n_tri = 2 * (res - 1) * (res - 1);
   auto footprint_pass = [&](int pass) {
-    hipLaunchKernelGGL(k_fp_tri, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_pts, N, w.inv, itab, w.uvz, depth,
-                       max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count);
-    hipLaunchKernelGGL(k_fp_wave, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_pts, w.inv, itab, w.uvz, depth, max_ratio,
-                       w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count);
+    hipLaunchKernelGGL(k_fp_tri<false>, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_pts, N, w.inv, itab, w.uvz, depth,
+                       max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, (const float*)nullptr,
+                       (const Xf*)nullptr);
+    hipLaunchKernelGGL(k_fp_wave<false>, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_pts, w.inv, itab, w.uvz, depth,
+                       max_ratio, w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, (const float*)nullptr, (const Xf*)nullptr);
   };
-  if (footprints) {
+  // view surfaces: the same two tiers over the instances' triangles and the background sheet, in the edits with a view (the
+  // vertex pointer is that of the first foreground point: see fp_setup)
+  auto surface_pass = [&](int pass) {
+    const double* fg_uvz = w.uvz + (size_t)R2 * 3;
+    hipLaunchKernelGGL(k_fp_tri<true>, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_pts, N, w.inv, itab, fg_uvz, depth,
+                       surface_max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, bg_depth,
+                       (const Xf*)w.views);
+    hipLaunchKernelGGL(k_fp_wave<true>, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_pts, w.inv, itab, fg_uvz, depth,
+                       surface_max_ratio, w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, bg_depth, (const Xf*)w.views);
+  };
+  if (surfaces) {
+    DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
+    DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
+    hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
+    hipLaunchKernelGGL((k_points<false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth,
+                       fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz,
+                       (const Xf*)w.views);
+    surface_pass(1);
+  } else if (footprints) {
     DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
     hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
@@ -1526,6 +1655,7 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
   if (footprints) footprint_pass(2);
+  if (surfaces) surface_pass(2);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), K), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, raw_mask,
                      disparity, w.minmax, (const Xf*)w.views);
   hipLaunchKernelGGL(k_fg_vis, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, R2, P, res, w.pix, w.owner, vis,
@@ -1557,13 +1687,29 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
                        4, corr_stride, (long long*)corr, corr_inst);
   } else {
     hipLaunchKernelGGL(k_keep_flags, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, R2, P, w.pix, vis, clean_mask,
-                       w.keep);
+                       w.keep, surfaces ? (const Xf*)w.views : (const Xf*)nullptr);
     compact(w.keep, n_pts, K, n_pts, w.keep_idx, n_pts, counts + 0, 4, w.block_counts, st);
     hipLaunchKernelGGL(k_write_corr, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, res, fg_pix, itab, target_xy,
                        w.keep_idx, counts, 4, corr_stride, (long long*)corr, corr_inst);
   }
+  if (surfaces) {
+    // the edits with a view: vis again (a point is visible when it owns a pixel), then the rows per TARGET pixel, the
+    // instances' and the background's.  Flags and lists live in the morphology's and the in-fill's buffers (tmp_a: dead;
+    // inpaint / unk: written again further down); the row counts of the target pass in the wave tier's counter (dead).
+    for (int e = 0; e < K; ++e)
+      if (has_view[e]) DH_CHECK_HIP(hipMemsetAsync(vis + (size_t)e * n_pts, 0, (size_t)n_pts, st));
+    hipLaunchKernelGGL(k_vs_flags, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, n_pts, w.owner, clean_mask, (size_t)R2, bg_valid,
+                       (const Xf*)w.views, vis, w.inpaint, w.tmp_a);
+    compact(w.inpaint, R2, K, R2, w.unk, R2, w.big_count, 1, w.block_counts, st);
+    hipLaunchKernelGGL(k_write_corr_target, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, res, fg_pix, itab, w.owner, w.unk,
+                       w.big_count, 1, corr_stride, (long long*)corr, corr_inst);
+    hipLaunchKernelGGL(k_vs_add_counts, dim3(cdiv(K, 64)), dim3(64), 0, st, K, w.big_count, counts);
+    compact(w.tmp_a, R2, K, R2, w.unk, R2, bg_counts, 1, w.block_counts, st);
+    hipLaunchKernelGGL(k_vs_write_bg, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, res, w.owner, w.unk, bg_counts,
+                       (long long*)bg_corr);
+  }
   hipLaunchKernelGGL(k_count_flags, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, vis, n_pts, counts, 4, 1);
-  if (w.views) {
+  if (w.views && !surfaces) {
     // the background rows: flags and the compacted list live in the in-fill's buffers (inpaint / unk: written just below)
     hipLaunchKernelGGL(k_bg_row_flags, dim3(cdiv(R2, 256), K), dim3(256), 0, st, R2, P, w.pix, w.owner, clean_mask, (size_t)R2,
                        bg_valid, (const Xf*)w.views, w.inpaint);
@@ -1630,8 +1776,45 @@ extern "C" int dh_reproject_camera_workspace_bytes(int res, int n_pts, int n_edi
   return DH_OK;
 }
 
+// View surfaces ("View surfaces"): the border entry with the setting (0 / 1, per call) and the depth-ratio guard of
+// its triangles (0 = none).  In an edit with a view the instances' triangles AND the two triangles of every source quad of the
+// background bid in the z-buffer of the points; the rows of such an edit are taken per target pixel (corr_capacity >= res * res).
+// An edit without a view is the point path; a call in which no edit has a view is the border entry's call, launch for launch.
+extern "C" int dh_reproject_surface_ws_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
+                                                    int view_surfaces, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
+  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
+  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
+  Arena a(nullptr, (size_t)-1);
+  ReprojectWs w;
+  carve(a, res, n_pts, n_edits, n_objects, w, false, n_instances, true, view_surfaces != 0);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_reproject_surface_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                           int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                           const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                           const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                           uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                           int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                           void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
+                                           const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
+                                           int n_host_objects, const double* views, const uint8_t* has_view,
+                                           const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border,
+                                           int view_surfaces, float surface_max_ratio) {
+  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
+  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
+  DH_REQUIRE(n_edits >= 1, "bad sizes");
+  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
+                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
+                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
+                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
+                             infill_border, view_surfaces, surface_max_ratio);
+}
+
 // The in-fill border: the camera entry with the border rule of the harmonic in-fill (0 = zero, 1 = reflect; see CG_NB_FRAME).
-// Per call, not per edit; the workspace is the camera entry's.
+// Per call, not per edit; the workspace is the camera entry's.  The call without view surfaces.
 extern "C" int dh_reproject_border_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
                                           int n_objects, const int32_t* obj_start, int res, const float* grid_x,
                                           const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
@@ -1642,14 +1825,11 @@ extern "C" int dh_reproject_border_edits(const float* depth, const float* bg_dep
                                           const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
                                           int n_host_objects, const double* views, const uint8_t* has_view,
                                           const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border) {
-  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
-  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
-  DH_REQUIRE(n_edits >= 1, "bad sizes");
-  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
-                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
-                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
-                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
-                             infill_border);
+  return dh_reproject_surface_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy,
+                                    n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
+                                    workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances, inst_obj,
+                                    corr_inst, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
+                                    infill_border, 0, 0.f);
 }
 
 // the call with the zero border
@@ -1788,12 +1968,30 @@ extern "C" int dh_reproject_background_workspace_bytes(int res, size_t* bytes) {
 //
 // dh_reproject_border_background: the same with the border rule of the harmonic in-fill (0 = zero, 1 = reflect); the workspace
 // is dh_reproject_background_workspace_bytes' either way.
-extern "C" int dh_reproject_border_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
-                                               float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
-                                               float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                               void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
-                                               int32_t* bg_counts, int infill_border) {
+//
+// dh_reproject_surface_background: the same with view surfaces (0 / 1) and the depth-ratio guard of the triangles (0 = none): with
+// a view the two triangles of every source quad bid beside the points, and the rows are one per target pixel whose owner has
+// bg_valid, row-major.  Without a view, or with 0, it is the border entry's call and workspace.
+extern "C" int dh_reproject_surface_background_ws_bytes(int res, int view_surfaces, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && res <= 32768 && bytes, "bad arguments");
+  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
+  Arena a(nullptr, (size_t)-1);
+  ReprojectWs w;
+  carve(a, res, 0, 1, 1, w, false, 0, false, view_surfaces != 0);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_reproject_surface_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                                                float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
+                                                float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                                void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
+                                                int32_t* bg_counts, int infill_border, int view_surfaces, float surface_max_ratio) {
   DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
+  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
+  DH_REQUIRE(surface_max_ratio == 0.f || (surface_max_ratio > 1.f && surface_max_ratio <= 3.4028234663852886e38f),
+             "surface_max_ratio must be 0 (none) or finite and > 1");
+  DH_REQUIRE(surface_max_ratio == 0.f || view_surfaces, "surface_max_ratio without view_surfaces");
   DH_REQUIRE(bg_depth && grid_x && grid_y, "null input");
   DH_REQUIRE(zmap && disparity && counts && workspace, "null output");
   DH_REQUIRE(res >= 2 && res <= 32768, "bad sizes");
@@ -1806,7 +2004,8 @@ extern "C" int dh_reproject_border_background(const float* bg_depth, int res, co
   const int R2 = res * res;
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
-  DH_REQUIRE(carve(a, res, 0, 1, 1, w), "workspace too small");
+  const bool surfaces = view_host != nullptr && view_surfaces != 0;
+  DH_REQUIRE(carve(a, res, 0, 1, 1, w, false, 0, false, surfaces), "workspace too small");
   const Xf* dview = nullptr;
   if (view_host) {
     DH_CHECK_HIP(hipMemcpyAsync(w.xf, view_host, sizeof(Xf), hipMemcpyHostToDevice, st));
@@ -1821,12 +2020,36 @@ extern "C" int dh_reproject_border_background(const float* bg_depth, int res, co
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0, 2 * sizeof(unsigned int), st));
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0xff, sizeof(unsigned int), st));
   DH_CHECK_HIP(hipMemsetAsync(w.tmp_b, 0, (size_t)R2, st));
-  hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth, (const int*)nullptr, 0, res,
-                     grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr, dview);
+  const int n_tri = 2 * (res - 1) * (res - 1);
+  auto surface_pass = [&](int pass) {          // the background sheet alone: no instance, the vertex pointer past the R2 points
+    hipLaunchKernelGGL(k_fp_tri<true>, dim3(cdiv(n_tri, 256), 1), dim3(256), 0, st, pass, res, 0, 0, (const int*)nullptr, itab,
+                       (const double*)(w.uvz + (size_t)R2 * 3), bg_depth, surface_max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list,
+                       w.big_stride, w.big_count, bg_depth, dview);
+    hipLaunchKernelGGL(k_fp_wave<true>, dim3(FP_WAVE_BLOCKS, 1), dim3(256), 0, st, pass, res, 0, (const int*)nullptr, itab,
+                       (const double*)(w.uvz + (size_t)R2 * 3), bg_depth, surface_max_ratio, w.zbuf, w.owner, w.big_list, w.big_stride,
+                       w.big_count, bg_depth, dview);
+  };
+  if (surfaces) {
+    DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, sizeof(int), st));
+    hipLaunchKernelGGL((k_points<false, true>), dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth,
+                       (const int*)nullptr, 0, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key,
+                       w.uvz, dview);
+    surface_pass(1);
+  } else {
+    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth, (const int*)nullptr, 0, res,
+                       grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr, dview);
+  }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.zbuf, w.pix, w.key, w.owner);
+  if (surfaces) surface_pass(2);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), 1), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, w.tmp_a,
                      disparity, w.minmax, dview);
-  if (dview) {
+  if (surfaces) {
+    hipLaunchKernelGGL(k_vs_flags, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, 0, w.owner, w.tmp_b, (size_t)0, bg_valid, dview,
+                       (uint8_t*)nullptr, (uint8_t*)nullptr, w.inpaint);
+    compact(w.inpaint, R2, 1, R2, w.unk, R2, bg_counts, 1, w.block_counts, st);
+    hipLaunchKernelGGL(k_vs_write_bg, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, res, w.owner, w.unk, bg_counts,
+                       (long long*)bg_corr);
+  } else if (dview) {
     hipLaunchKernelGGL(k_bg_row_flags, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.pix, w.owner, w.tmp_b, (size_t)0, bg_valid,
                        dview, w.inpaint);
     compact(w.inpaint, R2, 1, R2, w.unk, R2, bg_counts, 1, w.block_counts, st);
@@ -1857,6 +2080,16 @@ extern "C" int dh_reproject_camera_background(const float* bg_depth, int res, co
                                                int32_t* bg_counts) {
   return dh_reproject_border_background(bg_depth, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, bounds, zmap, disparity, counts,
                                         workspace, workspace_bytes, stream, view, bg_valid, bg_corr, bg_counts, 0);
+}
+
+// the call without view surfaces
+extern "C" int dh_reproject_border_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                                               float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
+                                               float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                               void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
+                                               int32_t* bg_counts, int infill_border) {
+  return dh_reproject_surface_background(bg_depth, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, bounds, zmap, disparity, counts,
+                                         workspace, workspace_bytes, stream, view, bg_valid, bg_corr, bg_counts, infill_border, 0, 0.f);
 }
 
 // the call without a view

@@ -298,6 +298,36 @@ def mesh_has_no_infill_border(value, what):
                                   f"infill_border={value!r}); use 'pc'")
 
 
+def check_view_surfaces(view_surfaces, view_surface_max_ratio, what="view_surfaces"):
+    """The view-surface settings of a point-mode call (DESIGN.md "View surfaces") -> (bool, None or the ratio as a float32
+    value).  ValueError for a ratio that is not a finite float > 1 (as float32) and for a ratio without the setting.  The one
+    validator; host only: no device work."""
+    view_surfaces = bool(view_surfaces)
+    if view_surface_max_ratio is None:
+        return view_surfaces, None
+    try:
+        if np.ndim(view_surface_max_ratio) != 0:
+            raise TypeError("not a scalar")
+        with np.errstate(over="ignore"):
+            ratio = float(np.float32(view_surface_max_ratio))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: view_surface_max_ratio must be a number > 1 or None, got {view_surface_max_ratio!r}") from None
+    if isinstance(view_surface_max_ratio, bool) or not (np.isfinite(ratio) and ratio > 1.0):
+        raise ValueError(f"{what}: view_surface_max_ratio must be finite and > 1 (as float32), got {view_surface_max_ratio!r}")
+    if not view_surfaces:
+        raise ValueError(f"{what}: view_surface_max_ratio={view_surface_max_ratio!r} without view_surfaces=True")
+    return view_surfaces, ratio
+
+
+def mesh_has_no_view_surfaces(view_surfaces, view_surface_max_ratio, what):
+    """Mesh mode draws triangles already and has no camera: the settings are checked as the point mode checks them, then
+    view_surfaces=True is refused.  Host only."""
+    view_surfaces, _ = check_view_surfaces(view_surfaces, view_surface_max_ratio, what)
+    if view_surfaces:
+        raise NotImplementedError(f"{what}: depth_transform_mode 'mesh' has no view surfaces (got depth_transform_view_surfaces=True); "
+                                  f"use 'pc'")
+
+
 def check_instances(instances, n_masks, what="instances"):
     """The instance table of an edit with copies -> list of N mask indices (None -> None: one instance per mask).
     ValueError naming `what` and the instance for more than 8 instances, an entry that is not an integer in 0 .. n_masks - 1,
@@ -455,11 +485,14 @@ def _plan(kind, entry=None, workspace_query=None, **fields):
     masks_u8          [M + D, res * res] uint8, where the masks are
     vacated           [res * res] bool union of the removed masks, or None
     covered           camera calls: [res * res] bool, host masks and removed masks (bg_valid is its complement), or None
-    infill_border     0 (zero) or 1 (reflect: the border entries run, with the arguments the named entry lacks left empty)"""
+    infill_border     0 (zero) or 1 (reflect: the border entries run, with the arguments the named entry lacks left empty)
+    view_surfaces     the setting is on AND an edit has a camera: the surface entries run, one row per target pixel in the edits
+                      with a camera (False otherwise: the setting acts only where there is a view); surface_ratio: None or the
+                      checked ratio"""
     p = types.SimpleNamespace(kind=kind, entry=entry, workspace_query=workspace_query, N=0, kept=[], n_host_kept=0, caller=[],
                               obj_start=np.zeros(1, dtype=np.int32), inst_obj=np.zeros(0, dtype=np.int32),
                               inst_start=np.zeros(1, dtype=np.int32), n_fg=0, n_pts=0, cap=0, with_table=False, inst=None, masks_u8=None,
-                              vacated=None, covered=None, infill_border=0)
+                              vacated=None, covered=None, infill_border=0, view_surfaces=False, surface_ratio=None)
     vars(p).update(fields)
     return p
 
@@ -505,7 +538,8 @@ def _plan_pure_camera(shape, removed):
 
 
 def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None, donor_depth=None, donor_masks=None, cameras=None,
-                   footprints=False, footprint_max_ratio=None, return_instances=False, what=None, infill_border="zero"):
+                   footprints=False, footprint_max_ratio=None, return_instances=False, what=None, infill_border="zero",
+                   view_surfaces=False, view_surface_max_ratio=None):
     """Everything `reproject` decides before it touches the compute device -> the record of `_plan`.  depth: the depth or its shape; the
     other arguments are `reproject`'s.  Every host check of the call (ValueError / NotImplementedError / RuntimeError with the
     texts the named functions always had; `what` is the caller's name in the two refusals of a call without a foreground mask)
@@ -516,6 +550,7 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     removal = "reproject_removal_edits"
     footprints, ratio = check_footprints(footprints, footprint_max_ratio, "reproject_object_edits")
     border = check_infill_border(infill_border, "reproject_border_edits")
+    surfaces, surface_ratio = check_view_surfaces(view_surfaces, view_surface_max_ratio, "reproject_surface_edits")
     fg_masks = list(fg_masks)
     edits = [list(tfs) for tfs in edits]
     cams = None
@@ -536,6 +571,9 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     if donor_depth is not None or donor_masks is not None:
         donor = check_donor(donor_depth, donor_masks, shape[-1], M, "reproject_donor_edits")
     if donor is not None:
+        if surfaces:
+            raise NotImplementedError("reproject_surface_edits: view surfaces with a donor are not supported "
+                                      "(depth_transform_view_surfaces; two images share pixel indices)")
         if footprints:
             raise NotImplementedError("reproject_donor_edits: footprints with a donor are not supported (depth_transform_footprints; "
                                       "two images share pixel indices)")
@@ -545,11 +583,15 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     donor_list = [] if donor is None else donor[1]
     D = len(donor_list)
     common = dict(M=M, D=D, return_instances=bool(return_instances), footprints=footprints, ratio=ratio, cams=cams, removed=removed,
-                  removed_given=removed_masks is not None, donor=donor, infill_border=border)
+                  removed_given=removed_masks is not None, donor=donor, infill_border=border,
+                  view_surfaces=surfaces and cams is not None, surface_ratio=surface_ratio if cams is not None else None)
+    surfaces = common["view_surfaces"]          # (without a camera the call is the call without the setting)
     background = ("dh_reproject_background", "dh_reproject_background_workspace_bytes")
     camera_background = ("dh_reproject_camera_background", "dh_reproject_background_workspace_bytes")
     if border:          # one entry for both kinds without a foreground point; the workspace does not grow
         background = camera_background = ("dh_reproject_border_background", "dh_reproject_background_workspace_bytes")
+    if surfaces:        # (a camera is present: the border entry's list, the setting and the ratio; a workspace query of its own)
+        camera_background = ("dh_reproject_surface_background", "dh_reproject_surface_background_ws_bytes")
     if M == 0 and (removed or cams is not None) and donor is None:
         for e, tfs in enumerate(edits):
             if len(tfs) != 0:
@@ -650,9 +692,11 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     if border:          # the camera entry's list and a trailing border; sized by the query of the call it extends
         entry = "dh_reproject_border_edits"
         query = "dh_reproject_camera_workspace_bytes" if cams is not None else "dh_reproject_instances_workspace_bytes"
+    if surfaces:        # the border entry's list, the setting and the ratio; the rows of a view edit are per target pixel
+        entry, query = "dh_reproject_surface_edits", "dh_reproject_surface_ws_bytes"
     return _plan("objects", entry, query, res=res, kept=kept, obj_start=obj_start, n_host_kept=sum(1 for m in kept if m < M),
                          caller=caller, inst_obj=inst_obj, inst_start=inst_start, n_fg=n_fg, n_pts=n_pts,
-                         cap=res * res if footprints else n_pts,          # one row per target pixel with footprints, per point without
+                         cap=res * res if footprints or surfaces else n_pts,          # one row per target pixel with footprints / view surfaces, per point without
                          masks_u8=masks_u8, covered=covered if cams is not None else None, **common)
 
 
@@ -683,7 +727,9 @@ def _run_plan(p, depth, bg_depth, intrinsics, use_input_depth_normalization, ret
 def _workspace(p, g):
     """The workspace of the plan's entry, sized by the query the plan names."""
     if p.kind != "objects":
-        sizes = (g.res,)
+        sizes = (g.res, 1) if p.view_surfaces else (g.res,)
+    elif p.view_surfaces:
+        sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), 1)
     elif p.with_table or p.infill_border:
         sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), int(p.footprints))
     else:
@@ -740,8 +786,10 @@ def _run_background(p, g):
             args += (_view_ptr(view), _lib.ptr(bg_valid), _lib.ptr(bg_corr[e]), _lib.ptr(bg_counts[e:]))
         elif p.infill_border:
             args += (None, None, None, None)
-        if p.infill_border:
+        if p.infill_border or p.view_surfaces:
             args += (p.infill_border,)
+        if p.view_surfaces:
+            args += (1, 0.0 if p.surface_ratio is None else p.surface_ratio)
         _lib.check(getattr(g.L, p.entry)(*args), p.entry)
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
@@ -800,7 +848,7 @@ def _run_objects(p, g):
     corr_inst = None
     if p.with_table:
         corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
-    if p.with_table or p.infill_border:
+    if p.with_table or p.infill_border or p.view_surfaces:
         args += (Nk, p.inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _lib.ptr(corr_inst))
     if camera or donor or p.infill_border:
         dd = p.donor[0].detach().to(dev, torch.float32).contiguous() if donor else None
@@ -820,8 +868,10 @@ def _run_objects(p, g):
                  _lib.ptr(bg_counts))
     elif p.infill_border:
         args += (None, None, None, None, None)
-    if p.infill_border:
+    if p.infill_border or p.view_surfaces:
         args += (p.infill_border,)
+    if p.view_surfaces:
+        args += (1, 0.0 if p.surface_ratio is None else p.surface_ratio)
     _lib.check(getattr(L, p.entry)(*args), p.entry)
     row_donor = donor_rows(corr_inst, [p.inst[n] for n in p.caller], p.M) if donor else None
     if p.with_table and p.caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
@@ -863,7 +913,7 @@ def _run_objects(p, g):
 def reproject(depth, bg_depth, fg_masks, intrinsics, edits, *, instances=None, removed_masks=None, donor_depth=None,
               donor_masks=None, cameras=None, use_input_depth_normalization=False, return_debug=False,
               device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False, what=None,
-              infill_border="zero"):
+              infill_border="zero", view_surfaces=False, view_surface_max_ratio=None):
     """K edits of one image (not in the reference, which has the one-object, one-edit call): `reproject_plan` decides on the
     host, `_run_plan` allocates and launches.  The named functions below are this call with fewer keywords.
 
@@ -953,10 +1003,22 @@ def reproject(depth, bg_depth, fg_masks, intrinsics, edits, *, instances=None, r
     integer output stays, and "zero" is the call without the keyword, byte for byte, through the same entries.  Composes with
     everything above.  ValueError (`check_infill_border`) for any other value.
 
+    View surfaces (DESIGN.md "View surfaces") -- view_surfaces=True: in an edit WITH a camera the whole scene is splatted as
+    triangles -- between neighbouring points of one instance (the footprint rules, vertices after the view) and over every
+    source quad of the background -- beside the points, in the one z-buffer; so a camera that moves closer or orbits leaves
+    unowned only what it really uncovers, and a magnified near surface does not let the far one show through.  Such an edit
+    takes its rows per target pixel, row-major: the instance rows (the owning point's source pixel, the pixel), then the
+    background rows (the owning background pixel, the pixel; the owner outside the host's and the removed masks, the pixel
+    outside the cleaned mask).  vis = the point owns a pixel.  view_surface_max_ratio: None or a finite float > 1, the
+    depth-ratio guard of the triangles (instances: on depth; background: on bg_depth).  The setting acts only where there is a
+    view: an edit without a camera, and a call without any, is what it is without the setting, byte for byte.  ValueError
+    (`check_view_surfaces`); NotImplementedError with a donor.  `footprints=True` with a camera stays refused.
+
     Every refusal precedes the first launch of the library (they are `reproject_plan`'s)."""
     p = reproject_plan(depth, fg_masks, edits, instances=instances, removed_masks=removed_masks, donor_depth=donor_depth,
                        donor_masks=donor_masks, cameras=cameras, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
-                       return_instances=return_instances, what=what, infill_border=infill_border)
+                       return_instances=return_instances, what=what, infill_border=infill_border, view_surfaces=view_surfaces,
+                       view_surface_max_ratio=view_surface_max_ratio)
     return _run_plan(p, depth, bg_depth, intrinsics, use_input_depth_normalization, return_debug, device_correspondences)
 
 
@@ -1021,11 +1083,23 @@ def reproject_border_edits(depth, bg_depth, fg_masks, intrinsics, edits, instanc
                            device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
                            cameras=None, infill_border="zero"):
     """`reproject` with the image border of the in-fill ("zero" or "reflect"); `reproject_camera_edits` is its call without it."""
+    return reproject_surface_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances, removed_masks, donor_depth, donor_masks,
+                                   use_input_depth_normalization, return_debug, device_correspondences, footprints,
+                                   footprint_max_ratio, return_instances, cameras, infill_border)
+
+
+def reproject_surface_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
+                            donor_masks=None, use_input_depth_normalization=False, return_debug=False,
+                            device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
+                            cameras=None, infill_border="zero", view_surfaces=False, view_surface_max_ratio=None):
+    """`reproject` with view surfaces (the scene as triangles in the edits with a camera); `reproject_border_edits` is its call
+    without them."""
     return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=instances, removed_masks=removed_masks,
                      donor_depth=donor_depth, donor_masks=donor_masks, cameras=cameras,
                      use_input_depth_normalization=use_input_depth_normalization, return_debug=return_debug,
                      device_correspondences=device_correspondences, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
-                     return_instances=return_instances, infill_border=infill_border)
+                     return_instances=return_instances, infill_border=infill_border, view_surfaces=view_surfaces,
+                     view_surface_max_ratio=view_surface_max_ratio)
 
 
 INFILL_BARRIER_TIMEOUT, INFILL_NOT_CONVERGED, INFILL_BREAKDOWN = -1, -2, -3      # counts[..., 3] < 0 (geometry.hip)

@@ -104,11 +104,29 @@ class DiffusionHandles:
             mesh_has_no_footprints(fp, ratio, f"{what}: conf depth_transform_footprints")
         fp, _ = check_footprints(fp, ratio, f"{what}: conf depth_transform_footprints")
         self._infill_border(what)
+        self._view_surfaces(what)
         return dict(footprints=fp, footprint_max_ratio=ratio)
 
-    def _reproject_keywords(self, what):
-        """_footprints and the in-fill border: the keywords of depth_transform.reproject that come from the conf."""
-        return dict(self._footprints(what), infill_border=self._infill_border(what))
+    def _view_surfaces(self, what):
+        """The optional top-level conf keys depth_transform_view_surfaces (absent = false) and
+        depth_transform_view_surface_max_ratio (absent = none) as the keywords of depth_transform.reproject (DESIGN.md "View
+        surfaces"): under a camera the scene is splatted as triangles.  Checked on the host (ValueError,
+        depth_transform.check_view_surfaces); a true key under a mode other than 'pc' raises NotImplementedError naming the
+        setting.  Read wherever an edit call reads its camera -- and, like the border, by every edit call through _footprints,
+        before any device work.  Without a camera the setting changes nothing."""
+        from .depth_transform import check_view_surfaces, mesh_has_no_view_surfaces
+        vs = self._conf_get("depth_transform_view_surfaces", False)
+        ratio = self._conf_get("depth_transform_view_surface_max_ratio", None)
+        if self.conf.depth_transform_mode != "pc":
+            mesh_has_no_view_surfaces(vs, ratio, f"{what}: conf depth_transform_view_surfaces")
+        vs, _ = check_view_surfaces(vs, ratio, f"{what}: conf depth_transform_view_surfaces")
+        return dict(view_surfaces=vs, view_surface_max_ratio=ratio)
+
+    def _reproject_keywords(self, what, cameras=False):
+        """_footprints and the in-fill border: the keywords of depth_transform.reproject that come from the conf; cameras: the
+        call passes cameras on, so the view-surface keywords travel too."""
+        kw = dict(self._footprints(what), infill_border=self._infill_border(what))
+        return dict(kw, **self._view_surfaces(what)) if cameras else kw
 
     def _lock_setup(self, what, activations, depth, release_mask=None):
         """The optional top-level conf keys background_lock (absent = false), background_lock_dilate and
@@ -198,6 +216,7 @@ class DiffusionHandles:
         cams = [check_camera(c, f"{what}: edit {e}") for e, c in enumerate(cameras)]
         if all(c is None for c in cams):
             return None
+        self._view_surfaces(what)          # (the keys that act on a camera edit: mesh mode names the setting when it is on)
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no camera moves "
                                       "(camera; only 'pc')")
@@ -233,7 +252,7 @@ class DiffusionHandles:
         from .depth_transform import check_instances, check_transform, reproject
         if cameras is not None and len(fg_masks) == 0 and removed_masks is None:
             removed_masks = []          # (checked by _camera_setup: no donor, no footprints, 'pc' mode)
-        fp = self._reproject_keywords(what)
+        fp = self._reproject_keywords(what, cameras=True)
         if self.conf.depth_transform_mode != "pc":
             if removed_masks is not None:
                 raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no object removal "
@@ -288,6 +307,9 @@ class DiffusionHandles:
                                       "(donor; only 'pc')")
         if self._footprints(what)["footprints"]:
             raise NotImplementedError(f"{what}: depth_transform_footprints: true has no object insertion (donor; two images "
+                                      "share pixel indices)")
+        if self._view_surfaces(what)["view_surfaces"]:
+            raise NotImplementedError(f"{what}: depth_transform_view_surfaces: true has no object insertion (donor; two images "
                                       "share pixel indices)")
         from .depth_transform import check_donor
         acts = donor["activations"]

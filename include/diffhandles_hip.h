@@ -275,6 +275,46 @@ int dh_reproject_border_background(const float* bg_depth, int res, const float* 
                                    void* workspace, size_t workspace_bytes, void* stream,
                                    const double* view, const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts,
                                    int infill_border);
+/* View surfaces (not in the reference; DESIGN.md, "View surfaces").  view_surfaces: 0 = every point of the list is one pixel,
+ * what every entry above computes -- or 1 = in an edit WITH a view the scene is splatted as triangles: between neighbouring
+ * points of one instance (the footprint rules, vertices after the view) and over every source quad of the background (vertices
+ * the background points, the depth-ratio guard on the f32 bg_depth, bidder index = the source pixel of the vertex with the
+ * largest weight).  All bids meet in the one z-buffer: winner = min (z, index).  Such an edit takes its rows per TARGET pixel,
+ * row-major: instance rows (corr, corr_inst) for the instance-owned pixels inside the cleaned mask, background rows (bg_corr,
+ * bg_counts) (o % res, o / res, tx, ty) for the pixels whose owner o < res * res has bg_valid[o] and that lie outside it; vis[j]
+ * = point j owns at least one pixel; target_xy[j] stays the point's own pixel.  An edit without a view is the point path, byte
+ * for byte; a call in which no edit has a view is the border entry's call, launch for launch.
+ * surface_max_ratio: 0 = none, else the depth-ratio guard of the triangles (finite, > 1).  The setting holds for the call.
+ *   dh_reproject_surface_edits       dh_reproject_border_edits plus the two; that entry is this one's (0, 0.f) call
+ *   dh_reproject_surface_background  dh_reproject_border_background plus the two; likewise
+ * Workspaces: the two queries below; with view_surfaces = 0 they equal dh_reproject_camera_workspace_bytes (footprints = 0) and
+ * dh_reproject_background_workspace_bytes.  With 1 they add 24 bytes per point and edit (the stored vertices), the inverse pixel
+ * map and 2 n_pts + 2 (res - 1)^2 list slots per edit.
+ * DH_ERR_ARG before any launch, outputs untouched, beyond what those entries refuse: view_surfaces other than 0 or 1; a ratio
+ * that is not 0 or finite and > 1; a ratio without the setting; view_surfaces = 1 with footprints = 1; view_surfaces = 1 with a
+ * donor mask (n_host_objects < n_objects); corr_capacity < res * res when an edit has a view and the setting is on. */
+int dh_reproject_surface_ws_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
+                                         int view_surfaces, size_t* bytes);
+int dh_reproject_surface_background_ws_bytes(int res, int view_surfaces, size_t* bytes);
+int dh_reproject_surface_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                               int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                               const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                               int n_edits, const double* xforms_host, const float* bounds,
+                               float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                               uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                               void* workspace, size_t workspace_bytes, void* stream,
+                               int footprints, float max_ratio, int corr_capacity,
+                               int n_instances, const int32_t* inst_obj, uint8_t* corr_inst,
+                               const float* donor_depth, int n_host_objects,
+                               const double* views, const uint8_t* has_view, const uint8_t* bg_valid,
+                               int64_t* bg_corr, int32_t* bg_counts, int infill_border,
+                               int view_surfaces, float surface_max_ratio);
+int dh_reproject_surface_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
+                                    float inv_fx, float inv_fy, double fx, double fy, const float* bounds,
+                                    float* zmap, float* disparity, int32_t* counts,
+                                    void* workspace, size_t workspace_bytes, void* stream,
+                                    const double* view, const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts,
+                                    int infill_border, int view_surfaces, float surface_max_ratio);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);

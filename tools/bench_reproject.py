@@ -20,7 +20,9 @@ two spheres and the same call with eight orbit cameras about the centre pixel (d
 reproject_camera_edits, camera moves; profiles/camera_moves/); the second line also reports the background rows per edit.
 DH_BORDER=reflect (default unset = zero): every call of the run in-fills with the reflecting image border (the named calls
 timed here keep their parameter lists, so the setting is given to depth_transform.reproject, which they all are;
-profiles/infill_border/); every line then says so."""
+profiles/infill_border/); every line then says so.
+DH_VIEW_SURFACES=1 [DH_VIEW_SURFACE_RATIO=R] (default unset), next to DH_CAMERA=1: the camera line runs with view surfaces
+(reproject_surface_edits: the scene as triangles under the eight cameras; profiles/view_surfaces/) and says so."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -167,14 +169,24 @@ if os.environ.get("DH_CAMERA", "0") not in ("", "0"):
     cams = orbit_cameras(c_depth, intr, res // 2, res // 2, [-14.0 + 4.0 * i for i in range(K)])
     report(lambda **kw: reproject_instance_edits(c_depth, c_bg, c_masks, intr, two, [0, 1], **kw), " two spheres, instances [0, 1]")
     n_bg = []
+    surfaces = os.environ.get("DH_VIEW_SURFACES", "0") not in ("", "0")
+    vs = {}
+    if surfaces:
+        from diffusionhandles_amd.depth_transform import reproject_surface_edits
+        ratio = os.environ.get("DH_VIEW_SURFACE_RATIO")
+        vs = dict(view_surfaces=True, view_surface_max_ratio=float(ratio) if ratio else None)
 
     def camera_call(**kw):          # (a camera call returns the instance array beside every result: report() reads pairs)
-        out = reproject_camera_edits(c_depth, c_bg, c_masks, intr, two, [0, 1], cameras=cams, **kw)
+        if surfaces:
+            out = reproject_surface_edits(c_depth, c_bg, c_masks, intr, two, [0, 1], cameras=cams, **vs, **kw)
+        else:
+            out = reproject_camera_edits(c_depth, c_bg, c_masks, intr, two, [0, 1], cameras=cams, **kw)
         if kw.get("return_debug"):
             n_bg[:] = out[1]["n_background"]
             return [r[:2] for r in out[0]], out[1]
         return [r[:2] for r in out]
-    report(camera_call, " two spheres, eight orbit cameras")
+    report(camera_call, " two spheres, eight orbit cameras" +
+           (f" view surfaces (ratio {vs['view_surface_max_ratio']})" if surfaces else ""))
     print(f"  background rows per edit {n_bg}", flush=True)
     M = M_shown
 if scale is not None:

@@ -52,7 +52,8 @@ def load_config(path):
                     raise ValueError(f"{path}: unknown key guided_diffuser.{kk}")
                 conf.guided_diffuser[kk] = vv
         elif k in conf or k in ("background_lock", "background_lock_dilate", "background_lock_feather",
-                                "depth_transform_infill_border"):
+                                "depth_transform_infill_border", "depth_transform_view_surfaces",
+                                "depth_transform_view_surface_max_ratio"):
             conf[k] = v
         else:
             raise ValueError(f"{path}: unknown key {k}")
@@ -91,6 +92,24 @@ def apply_border_args(args, conf):
     border = check_infill_border(value, "--infill-border")
     args.border_report = dict(infill_border=INFILL_BORDERS[border]) if border else {}
     return args.border_report
+
+
+def apply_view_surface_args(args, conf):
+    """--view-surfaces / --view-surface-max-ratio -> the optional conf keys depth_transform_view_surfaces /
+    depth_transform_view_surface_max_ratio (DiffusionHandles reads them wherever an edit carries a camera), checked as the
+    library checks them (ValueError; NotImplementedError in mesh mode) before any engine is built and before any identity.
+    Returns what the report carries (nothing with the setting off: the reports of such runs stay what they were)."""
+    from diffusionhandles_amd.depth_transform import check_view_surfaces, mesh_has_no_view_surfaces
+    if args.view_surfaces:
+        conf["depth_transform_view_surfaces"] = True
+    if args.view_surface_max_ratio is not None:
+        conf["depth_transform_view_surface_max_ratio"] = args.view_surface_max_ratio
+    vs, ratio = conf.get("depth_transform_view_surfaces", False), conf.get("depth_transform_view_surface_max_ratio")
+    if conf.depth_transform_mode != "pc":
+        mesh_has_no_view_surfaces(vs, ratio, "--view-surfaces")
+    vs, ratio = check_view_surfaces(vs, ratio, "--view-surfaces")
+    args.view_surface_report = dict(view_surfaces=True, view_surface_max_ratio=ratio) if vs else {}
+    return args.view_surface_report
 
 
 def apply_lock_args(args, conf):
@@ -157,6 +176,13 @@ def parse(argv=None):
                     help="the image border of the depth in-fill in 'pc' mode (conf key depth_transform_infill_border): reflect = "
                          "zero normal derivative at the frame, so a region a camera move or a removal uncovers at the frame is "
                          "not pulled towards disparity 0 there; applies to the re-projection and to set_foreground")
+    ap.add_argument("--view-surfaces", action="store_true",
+                    help="--scene: under a camera move splat the whole scene as triangles in 'pc' mode (conf key "
+                         "depth_transform_view_surfaces): the background and every object are surfaces, so a camera that moves "
+                         "closer or orbits leaves unowned only what it uncovers and far surfaces do not show through near ones")
+    ap.add_argument("--view-surface-max-ratio", type=float, default=None, metavar="R",
+                    help="with --view-surfaces: leave out triangles whose source depths differ by more than the factor R > 1 "
+                         "(conf key depth_transform_view_surface_max_ratio)")
     ap.add_argument("--background-lock", action="store_true",
                     help="hold every edit's latents to the reconstruction outside the region the edit touches (conf key "
                          "background_lock); the identity cache then also keeps the reconstruction trajectory, a release.png in "
@@ -181,6 +207,7 @@ def main():
     args.mode = conf.depth_transform_mode
     apply_footprint_args(args, conf)
     apply_border_args(args, conf)
+    apply_view_surface_args(args, conf)
     apply_lock_args(args, conf)
     state = {"dh": None}           # the engine is built on first use: a run that skips every scene never touches the GPU
 
@@ -246,7 +273,7 @@ def main():
                 f"{len(reports)} scenes</h3><table border='1' cellspacing='0' cellpadding='4'><tr><th>scene</th><th>edits</th>"
                 f"<th>identity s</th></tr>{rows}</table></body></html>")
     total = dict(test_set=set_name, scenes=reports, config=args.config, depth_transform_mode=conf.depth_transform_mode,
-                 **args.footprint_report, **args.border_report, **args.lock_report,
+                 **args.footprint_report, **args.border_report, **args.view_surface_report, **args.lock_report,
                  edits_run=sum(1 for r in reports for e in r["edits"] if not e.get("skipped")),
                  edits_skipped=sum(1 for r in reports for e in r["edits"] if e.get("skipped")))
     if batch_seconds is not None:
@@ -318,6 +345,9 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
                 if getattr(args, "footprint_report", {}).get("footprints"):
                     raise NotImplementedError(f"{scene}: transform {n!r} inserts a donor object (\"donor\"); --footprints "
                                               "(depth_transform_footprints) has no object insertion")
+                if getattr(args, "view_surface_report", {}).get("view_surfaces"):
+                    raise NotImplementedError(f"{scene}: transform {n!r} inserts a donor object (\"donor\"); --view-surfaces "
+                                              "(depth_transform_view_surfaces) has no object insertion")
                 if getattr(args, "edit_batch", 1) > 1:
                     raise NotImplementedError(f"{scene}: transform {n!r} inserts a donor object (\"donor\"); --edit-batch "
                                               "(mixed-image batches) has no object insertion")
@@ -438,6 +468,7 @@ def scene_identity(args, dh, p, out, identity=None):
     write_png(os.path.join(out, "recon.png"), recon[0].permute(1, 2, 0).float().cpu().numpy())
     report = dict(resolution=res, mode=args.mode, identity_s=round(t_identity, 2), identity_from_cache=bool(identity_from_cache),
                   edits=[], **getattr(args, "footprint_report", {}), **getattr(args, "border_report", {}),
+                  **getattr(args, "view_surface_report", {}),
                   **getattr(args, "lock_report", {}))
     if args.identity_batch > 1:
         report["identity_batch"] = args.identity_batch

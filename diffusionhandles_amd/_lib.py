@@ -122,6 +122,11 @@ SIGNATURES = {
                                          ctypes.POINTER(c_d), ctypes.POINTER(ctypes.c_uint8), c_p, c_p, c_p, c_i, c_i, c_f]),
     "dh_reproject_surface_background": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_sz, c_p,
                                               ctypes.POINTER(c_d), c_p, c_p, c_p, c_i, c_i, c_f]),
+    "dh_reproject_bend_ws_bytes": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
+    "dh_reproject_bend_edits": (c_i, [c_p, c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_i, c_p, c_p, c_f, c_f, c_d,
+                                      c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                      c_p, c_i, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p, c_p, c_i,
+                                      ctypes.POINTER(c_d), ctypes.POINTER(ctypes.c_uint8), c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p]),
     "dh_reproject_background_workspace_bytes": (c_i, [c_i, ctypes.POINTER(c_sz)]),
     "dh_reproject_background": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "dh_unproject": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_p, c_p]),

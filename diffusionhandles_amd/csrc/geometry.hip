@@ -214,12 +214,18 @@ __device__ __forceinline__ bool has_view(const Xf* views, int e) { return views 
 // pixel and leaves pix = -1.  An edit without a view skips all of it behind the uniform flag.
 // VS (view surfaces, further down; never with FP): an edit with a view also leaves (u, v, Z) of EVERY point of the list -- after
 // the view, before the discard, the clamp and the rounding -- in uvz, 3 doubles per point and edit ([K][P][3]).
-template <bool FP, bool VS = false>
+// SK (bend edits, dh_reproject_bend_edits; DESIGN.md, "Bend edits"): an instance has n_bones rows per edit (xf is
+// [K][n_inst][n_bones]) and point-list position j the weights bone_w[(e * n_pts + j) * n_bones ..], one contiguous load.  The
+// point goes to the f64 sum of w_b * xf_apply(row_b) over the bones with w_b != 0, b ascending, the first product opening the
+// sum (w = 1 on one bone leaves that bone's bits); all weights 0 = bone 0 with weight 1.  One row is live at a time: the loop
+// over the bones is not unrolled and the weight of bone b is a select over scalars, never an indexed private array.
+template <bool FP, bool VS = false, bool SK = false>
 __global__ void k_points(const float* depth, const float* donor_depth, int n_host, const float* bg_depth, const int* fg_pix,
                          int n_pts, int res,
                          const float* gx, const float* gy, float ifx, float ify, double fx, double fy,
                          const Xf* xf, const float* cen, const InstTable tab, int n_inst, unsigned long long* zbuf,
-                         int* pix_out, unsigned long long* key_out, double* uvz, const Xf* views) {
+                         int* pix_out, unsigned long long* key_out, double* uvz, const Xf* views, const float* bone_w,
+                         int n_bones) {
   const int R2 = res * res, P = R2 + n_pts;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   int e = blockIdx.y;
@@ -235,12 +241,50 @@ __global__ void k_points(const float* depth, const float* donor_depth, int n_hos
     const int n = inst_of(i - R2, tab, off, o);
     float x, y, z;
     unproject_px(o >= n_host ? donor_depth : depth, fg_pix[i - R2 + off], res, gx, gy, ifx, ify, x, y, z);
-    const Xf t = xf[e * n_inst + n];
-    // (the centroid is read whether or not the row has a pivot: three selects, no divergent branch around dependent loads)
-    const bool piv = t.has_pivot != 0.0;
-    const float g0 = cen[4 * o], g1 = cen[4 * o + 1], g2 = cen[4 * o + 2];
-    const float c0 = piv ? (float)t.px : g0, c1 = piv ? (float)t.py : g1, c2 = piv ? (float)t.pz : g2;
-    xf_apply(t, x, y, z, c0, c1, c2, X, Y, Z);
+    if (!SK) {
+      const Xf t = xf[e * n_inst + n];
+      // (the centroid is read whether or not the row has a pivot: three selects, no divergent branch around dependent loads)
+      const bool piv = t.has_pivot != 0.0;
+      const float g0 = cen[4 * o], g1 = cen[4 * o + 1], g2 = cen[4 * o + 2];
+      const float c0 = piv ? (float)t.px : g0, c1 = piv ? (float)t.py : g1, c2 = piv ? (float)t.pz : g2;
+      xf_apply(t, x, y, z, c0, c1, c2, X, Y, Z);
+    } else {
+      // the weights of this point: one n_bones-wide load (the entry checks the 16-byte alignment the float4 needs)
+      const float* wp = bone_w + ((size_t)e * n_pts + (i - R2)) * n_bones;
+      float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
+      if (n_bones == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(wp);
+        w0 = q.x; w1 = q.y; w2 = q.z; w3 = q.w;
+      } else if (n_bones == 2) {
+        const float2 q = *reinterpret_cast<const float2*>(wp);
+        w0 = q.x; w1 = q.y;
+      } else if (n_bones == 3) {
+        w0 = wp[0]; w1 = wp[1]; w2 = wp[2];
+      } else {
+        w0 = wp[0];
+      }
+      if (w0 == 0.f && w1 == 0.f && w2 == 0.f && w3 == 0.f) w0 = 1.f;
+      const float g0 = cen[4 * o], g1 = cen[4 * o + 1], g2 = cen[4 * o + 2];
+      const Xf* rows = xf + (size_t)(e * n_inst + n) * n_bones;
+      bool open = false;
+      X = 0.0; Y = 0.0; Z = 0.0;
+#pragma unroll 1
+      for (int b = 0; b < n_bones; ++b) {
+        const float wb = b == 0 ? w0 : b == 1 ? w1 : b == 2 ? w2 : w3;
+        if (wb == 0.f) continue;
+        const Xf t = rows[b];
+        const bool piv = t.has_pivot != 0.0;
+        const float c0 = piv ? (float)t.px : g0, c1 = piv ? (float)t.py : g1, c2 = piv ? (float)t.pz : g2;
+        double bx, by, bz;
+        xf_apply(t, x, y, z, c0, c1, c2, bx, by, bz);
+        const double wd = (double)wb;
+        bx = wd * bx; by = wd * by; bz = wd * bz;
+        X = open ? X + bx : bx;
+        Y = open ? Y + by : by;
+        Z = open ? Z + bz : bz;
+        open = true;
+      }
+    }
   }
   bool view = false;
   if (!FP) {
@@ -1377,10 +1421,11 @@ struct ReprojectWs {
 // n_fg: the foreground points of the point list (with copies n_pts, the sum over the instances); M: masks; N: transform rows
 // per edit (instances; 0 = M, the call without copies, whose carving -- and so every workspace query that existed before the
 // copies -- is what it was: the wave tier's list then has a slot per triangle of the grid, else 2 n_pts per edit)
+// (B: rows per instance, the bones of a bend edit; 1 = every carving that existed before them)
 static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false, int N = 0,
-                  bool camera = false, bool surfaces = false) {
+                  bool camera = false, bool surfaces = false, int B = 1) {
   const size_t R2 = (size_t)res * res, P = R2 + n_fg;
-  w.xf = a.take<Xf>((size_t)K * (N > 0 ? N : M));
+  w.xf = a.take<Xf>((size_t)K * (N > 0 ? N : M) * B);
   w.cen = a.take<float>(4 * M);
   w.zbuf = a.take<unsigned long long>(K * R2);
   w.owner = a.take<int>(K * R2);
@@ -1522,7 +1567,12 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
                                int footprints, float max_ratio, int corr_capacity, const float* donor_depth = nullptr,
                                int n_host_objects = -1, const double* views = nullptr, const uint8_t* has_view = nullptr,
                                const uint8_t* bg_valid = nullptr, int64_t* bg_corr = nullptr, int32_t* bg_counts = nullptr,
-                               int infill_border = 0, int view_surfaces = 0, float surface_max_ratio = 0.f) {
+                               int infill_border = 0, int view_surfaces = 0, float surface_max_ratio = 0.f, int n_bones = 1,
+                               const float* bone_w = nullptr) {
+  // bend edits: n_bones rows per instance and edit; the weights stay on the device and are never read here
+  DH_REQUIRE(n_bones >= 1 && n_bones <= DH_MAX_BONES, "n_bones must lie in 1 .. 4");
+  DH_REQUIRE(n_bones == 1 || bone_w, "n_bones > 1 without bone_w");
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(bone_w) & 15u) == 0, "bone_w must be 16-byte aligned");
   DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
   DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
   DH_REQUIRE(surface_max_ratio == 0.f || (surface_max_ratio > 1.f && surface_max_ratio <= 3.4028234663852886e38f),
@@ -1563,7 +1613,7 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
              "correspondence capacity too small (n_fg rows per edit without footprints, res * res with)");
   // every row before any launch: a scale that is not positive and finite would collapse or mirror the object or spread NaN over
   // the z-buffer; a pivot is checked whether or not the row's flag selects it
-  for (size_t r = 0; r < (size_t)n_edits * n_inst; ++r) {
+  for (size_t r = 0; r < (size_t)n_edits * n_inst * n_bones; ++r) {
     const double* row = xforms_host + r * DH_SIMILARITY_ROW;
     for (int k = 8; k < 11; ++k)
       DH_REQUIRE((float)row[k] > 0.0f && row[k] <= 3.4028234663852886e38, "transform row: the scale must be positive and finite");
@@ -1591,7 +1641,8 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   const int R2 = res * res, P = R2 + n_pts;
   Arena a(workspace, workspace_bytes);
   ReprojectWs w;
-  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N, view_host != nullptr, surfaces),
+  DH_REQUIRE(!(identity_carve && n_bones > 1), "bones need the instance carving");
+  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N, view_host != nullptr, surfaces, n_bones),
              "workspace too small");
   const size_t corr_stride = (size_t)corr_capacity;
   if (view_host) DH_CHECK_HIP(hipMemcpyAsync(w.views, view_host, (size_t)K * sizeof(Xf), hipMemcpyHostToDevice, st));
@@ -1603,7 +1654,7 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   const int no = ellipse_offsets(ko < 1 ? 1 : ko, ho);
   DH_CHECK_HIP(hipMemcpyAsync(w.offs_close, hc, nc * sizeof(int2), hipMemcpyHostToDevice, st));
   DH_CHECK_HIP(hipMemcpyAsync(w.offs_open, ho, no * sizeof(int2), hipMemcpyHostToDevice, st));
-  DH_CHECK_HIP(hipMemcpyAsync(w.xf, xforms_host, (size_t)K * N * sizeof(Xf), hipMemcpyHostToDevice, st));
+  DH_CHECK_HIP(hipMemcpyAsync(w.xf, xforms_host, (size_t)K * N * n_bones * sizeof(Xf), hipMemcpyHostToDevice, st));
   DH_CHECK_HIP(hipMemsetAsync(w.zbuf, 0xff, (size_t)K * R2 * sizeof(unsigned long long), st));
   DH_CHECK_HIP(hipMemsetAsync(w.owner, 0x7f, (size_t)K * R2 * sizeof(int), st));
   DH_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)K * 4 * sizeof(int), st));
@@ -1636,22 +1687,36 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
     DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
     hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
-    hipLaunchKernelGGL((k_points<false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth,
-                       fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz,
-                       (const Xf*)w.views);
+    if (bone_w)
+      hipLaunchKernelGGL((k_points<false, true, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
+                         bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
+                         w.key, w.uvz, (const Xf*)w.views, bone_w, n_bones);
+    else
+      hipLaunchKernelGGL((k_points<false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
+                         bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
+                         w.key, w.uvz, (const Xf*)w.views, (const float*)nullptr, 1);
     surface_pass(1);
   } else if (footprints) {
     DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
     hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
-    hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth, fg_pix,
-                       n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz,
-                       (const Xf*)nullptr);
+    if (bone_w)
+      hipLaunchKernelGGL((k_points<true, false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
+                         bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
+                         w.key, w.uvz, (const Xf*)nullptr, bone_w, n_bones);
+    else
+      hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth,
+                         fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key,
+                         w.uvz, (const Xf*)nullptr, (const float*)nullptr, 1);
     footprint_pass(1);
+  } else if (bone_w) {
+    hipLaunchKernelGGL((k_points<false, false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
+                       bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
+                       w.key, (double*)nullptr, (const Xf*)w.views, bone_w, n_bones);
   } else {
     hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth, fg_pix,
                        n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key,
-                       (double*)nullptr, (const Xf*)w.views);
+                       (double*)nullptr, (const Xf*)w.views, (const float*)nullptr, 1);
   }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
   if (footprints) footprint_pass(2);
@@ -1792,6 +1857,49 @@ extern "C" int dh_reproject_surface_ws_bytes(int res, int n_pts, int n_edits, in
   return DH_OK;
 }
 
+// Bend edits ("Bend edits"): the surface entry with n_bones transform rows per instance and edit (xforms_host is
+// [n_edits][n_instances][n_bones][DH_SIMILARITY_ROW]) and the weight of every point and bone on the device (bone_w
+// [n_edits][n_pts][n_bones], by point-list position).  A point goes to the weighted sum of where its bones put it
+// (k_points<.., SK>); everything after the point transform sees points as before.  n_bones = 1 with bone_w = NULL is the
+// surface entry's call, launch for launch; the workspace grows only by the device copy of the extra rows.
+extern "C" int dh_reproject_bend_ws_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances, int view_surfaces,
+                                          int footprints, int n_bones, size_t* bytes) {
+  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
+  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
+  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
+  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
+  DH_REQUIRE(!(footprints && view_surfaces), "view_surfaces with footprints are not supported");
+  DH_REQUIRE(n_bones >= 1 && n_bones <= DH_MAX_BONES, "n_bones must lie in 1 .. 4");
+  Arena a(nullptr, (size_t)-1);
+  ReprojectWs w;
+  carve(a, res, n_pts, n_edits, n_objects, w, footprints != 0, n_instances, true, view_surfaces != 0, n_bones);
+  *bytes = a.off + 256;
+  return DH_OK;
+}
+
+extern "C" int dh_reproject_bend_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                                       int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                                       const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
+                                       const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
+                                       uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
+                                       int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                       void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
+                                       const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
+                                       int n_host_objects, const double* views, const uint8_t* has_view,
+                                       const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border,
+                                       int view_surfaces, float surface_max_ratio, int n_bones,
+                                       const float* bone_w) {
+  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
+  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
+  DH_REQUIRE(n_edits >= 1, "bad sizes");
+  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
+                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
+                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
+                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
+                             infill_border, view_surfaces, surface_max_ratio, n_bones, bone_w);
+}
+
+// the call without bones
 extern "C" int dh_reproject_surface_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
                                            int n_objects, const int32_t* obj_start, int res, const float* grid_x,
                                            const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
@@ -1803,14 +1911,11 @@ extern "C" int dh_reproject_surface_edits(const float* depth, const float* bg_de
                                            int n_host_objects, const double* views, const uint8_t* has_view,
                                            const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border,
                                            int view_surfaces, float surface_max_ratio) {
-  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
-  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
-  DH_REQUIRE(n_edits >= 1, "bad sizes");
-  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
-                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
-                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
-                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
-                             infill_border, view_surfaces, surface_max_ratio);
+  return dh_reproject_bend_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy,
+                                 n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
+                                 workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances, inst_obj,
+                                 corr_inst, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
+                                 infill_border, view_surfaces, surface_max_ratio, 1, nullptr);
 }
 
 // The in-fill border: the camera entry with the border rule of the harmonic in-fill (0 = zero, 1 = reflect; see CG_NB_FRAME).
@@ -2033,11 +2138,12 @@ extern "C" int dh_reproject_surface_background(const float* bg_depth, int res, c
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, sizeof(int), st));
     hipLaunchKernelGGL((k_points<false, true>), dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth,
                        (const int*)nullptr, 0, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key,
-                       w.uvz, dview);
+                       w.uvz, dview, (const float*)nullptr, 1);
     surface_pass(1);
   } else {
     hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth, (const int*)nullptr, 0, res,
-                       grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr, dview);
+                       grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr, dview,
+                       (const float*)nullptr, 1);
   }
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.zbuf, w.pix, w.key, w.owner);
   if (surfaces) surface_pass(2);

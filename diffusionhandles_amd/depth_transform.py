@@ -133,6 +133,116 @@ def check_transform(tf, what="transform"):
     return angle, axis, trans, sc, pv
 
 
+MAX_BONES = 4                # DH_MAX_BONES (include/diffhandles_hip.h)
+
+
+class Bend:
+    """A bend edit of one instance (DESIGN.md "Bend edits"): it may stand wherever a transform tuple of an instance stands.
+    bones: 1 .. 4 ordinary transforms, 3- or 5-tuples, each with its own scale and pivot; weights: an array or tensor
+    [B, H, W], the weight of bone b at every pixel of the image.  A point of the instance goes to the weighted sum of where
+    each bone puts it (linear-blend skinning).  Immutable; nothing is checked here (`check_bend`)."""
+    __slots__ = ("bones", "weights")
+
+    def __init__(self, bones, weights):
+        object.__setattr__(self, "bones", tuple(tuple(b) if isinstance(b, (list, tuple)) else b for b in bones))
+        object.__setattr__(self, "weights", weights)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Bend is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("Bend is immutable")
+
+    def __repr__(self):
+        shape = tuple(getattr(self.weights, "shape", ()))
+        return f"Bend({len(self.bones)} bones, weights {shape})"
+
+
+def check_bend(bend, mask, what="bend"):
+    """A `Bend` of the instance that draws `mask` ([1,1,H,W] or [H,W]) -> the `Bend` with every bone through `check_transform`
+    and the weights as a float32 tensor [B, H, W] where they were.  ValueError naming `what` (the call, the edit and the
+    instance) and the member: a bone that is no transform, B outside 1 .. 4, weights that are not [B, H, W] of the mask's
+    size, that are not finite or negative, or that do not sum to 1 within 1e-5 on the mask's pixels.  Before any launch of the
+    library (weights on a device are read there)."""
+    checked, flags = _bend_checks(bend, mask, what)
+    _raise_bend_flags(what, flags.tolist())
+    return checked
+
+
+def _bend_checks(bend, mask, what):
+    """`check_bend` up to the values of the weights -> (the checked `Bend`, a float64 tensor where the weights are: [any weight
+    not finite, any weight < 0, the largest |sum - 1| on the mask's pixels]).  Nothing here waits for the device, so a call with
+    several Bends reads all their flags in one copy (`reproject_plan`)."""
+    if not isinstance(bend, Bend):
+        raise ValueError(f"{what}: expected a Bend, got {type(bend).__name__}")
+    B = len(bend.bones)
+    if not 1 <= B <= MAX_BONES:
+        raise ValueError(f"{what}: a Bend has 1 to {MAX_BONES} bones, got {B}")
+    bones = tuple(check_transform(b, f"{what}: bone {i}") for i, b in enumerate(bend.bones))
+    w = bend.weights
+    try:
+        w = (w.detach() if isinstance(w, torch.Tensor) else torch.as_tensor(np.asarray(w))).to(torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: weights must be an array or tensor [B, H, W], got {type(bend.weights).__name__}") from None
+    hw = tuple(mask.shape[-2:])
+    if w.dim() != 3 or w.shape[0] != B or tuple(w.shape[1:]) != hw:
+        raise ValueError(f"{what}: weights must be [{B}, {hw[0]}, {hw[1]}] ({B} bones, the mask's size), got {list(w.shape)}")
+    on = (mask.detach() if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))).reshape(hw) != 0
+    on = on.to(w.device)
+    off = (w.to(torch.float64).sum(dim=0) - 1.0).abs()
+    off = torch.where(on & ~torch.isnan(off), off, torch.zeros_like(off)).max()          # (a NaN is the first flag's)
+    flags = torch.stack([(~torch.isfinite(w)).any().to(torch.float64), (w < 0).any().to(torch.float64), off])
+    return Bend(bones, w.contiguous()), flags
+
+
+def _raise_bend_flags(what, flags):
+    if flags[0]:
+        raise ValueError(f"{what}: weights must be finite")
+    if flags[1]:
+        raise ValueError(f"{what}: weights must be >= 0")
+    if flags[2] > 1e-5:
+        raise ValueError(f"{what}: weights must sum to 1 on the mask's pixels (within 1e-5), off by up to {flags[2]:.3g}")
+
+
+def check_body(tf, mask, what):
+    """What stands for an instance in an edit: a transform tuple (`check_transform`) or a `Bend` (`check_bend` against the
+    instance's mask)."""
+    return check_bend(tf, mask, what) if isinstance(tf, Bend) else check_transform(tf, what)
+
+
+def bend_chain(depth, intrinsics, mask, p0, p1, width, rot_angle, rot_axis, translation=(0.0, 0.0, 0.0), pivot=None, bones=2):
+    """The `Bend` that bends the object of `mask` across the line p0 -> p1 (pixels, (x, y)): with d the signed pixel distance of
+    a pixel from the line, d = ((x - x0)(y1 - y0) - (y - y0)(x1 - x0)) / |p1 - p0|, and s = clamp(d / width + 0.5, 0, 1) (B - 1),
+    bone b has the hat weight max(0, 1 - |s - b|), turns by rot_angle b / (B - 1) about rot_axis through `pivot` and moves by
+    translation b / (B - 1).  The side with d < -width / 2 stays put (bone 0), the side beyond +width / 2 takes the full
+    motion, and the band between blends neighbouring bones.  pivot: a point in the coordinates of `depth_to_world_coords`;
+    None = `pivot_at_pixel` of the midpoint of p0 p1.  More bones spread a large angle over smaller steps: linear-blend
+    skinning pulls the band between two bones towards the chord.  ValueError: width <= 0, p0 == p1, bones outside 2 .. 4."""
+    what = "bend_chain"
+    try:
+        (x0, y0), (x1, y1) = (float(p0[0]), float(p0[1])), (float(p1[0]), float(p1[1]))
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"{what}: p0 and p1 must be pixels (x, y), got {p0!r}, {p1!r}") from None
+    if not all(np.isfinite(v) for v in (x0, y0, x1, y1)):
+        raise ValueError(f"{what}: p0 and p1 must be finite, got {p0!r}, {p1!r}")
+    if (x0, y0) == (x1, y1):
+        raise ValueError(f"{what}: p0 == p1 ({p0!r}) is no line")
+    if not (isinstance(width, (int, float)) and np.isfinite(width) and width > 0):
+        raise ValueError(f"{what}: width must be a positive number of pixels, got {width!r}")
+    if not (isinstance(bones, int) and not isinstance(bones, bool) and 2 <= bones <= MAX_BONES):
+        raise ValueError(f"{what}: bones must be 2 .. {MAX_BONES}, got {bones!r}")
+    h, w = (int(v) for v in mask.shape[-2:])
+    if pivot is None:
+        pivot = pivot_at_pixel(depth, intrinsics, int(round((x0 + x1) / 2.0)), int(round((y0 + y1) / 2.0)))
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
+    d = ((xx - x0) * (y1 - y0) - (yy - y0) * (x1 - x0)) / float(np.hypot(x1 - x0, y1 - y0))
+    s = (d / float(width) + 0.5).clamp(0.0, 1.0) * (bones - 1)
+    weights = torch.stack([(1.0 - (s - b).abs()).clamp(min=0.0) for b in range(bones)]).to(torch.float32)
+    tr = _f32_list(translation)
+    tfs = [(float(rot_angle) * b / (bones - 1), rot_axis, tuple(t * b / (bones - 1) for t in tr), None, pivot) for b in range(bones)]
+    return Bend(tfs, weights)
+
+
 SIMILARITY_ROW = 16          # DH_SIMILARITY_ROW (include/diffhandles_hip.h)
 
 
@@ -488,11 +598,14 @@ def _plan(kind, entry=None, workspace_query=None, **fields):
     infill_border     0 (zero) or 1 (reflect: the border entries run, with the arguments the named entry lacks left empty)
     view_surfaces     the setting is on AND an edit has a camera: the surface entries run, one row per target pixel in the edits
                       with a camera (False otherwise: the setting acts only where there is a view); surface_ratio: None or the
-                      checked ratio"""
+                      checked ratio
+    bent, n_bones     an instance of an edit is a `Bend`: dh_reproject_bend_edits runs, with n_bones rows per instance and edit (the
+                      largest bone count of the call; shorter instances pad with copies of their bone 0 at weight 0) and the
+                      weights gathered at the instances' pixels.  False, 1: the call it was"""
     p = types.SimpleNamespace(kind=kind, entry=entry, workspace_query=workspace_query, N=0, kept=[], n_host_kept=0, caller=[],
                               obj_start=np.zeros(1, dtype=np.int32), inst_obj=np.zeros(0, dtype=np.int32),
                               inst_start=np.zeros(1, dtype=np.int32), n_fg=0, n_pts=0, cap=0, with_table=False, inst=None, masks_u8=None,
-                              vacated=None, covered=None, infill_border=0, view_surfaces=False, surface_ratio=None)
+                              vacated=None, covered=None, infill_border=0, view_surfaces=False, surface_ratio=None, n_bones=1, bent=False)
     vars(p).update(fields)
     return p
 
@@ -627,8 +740,9 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
             if instances is None:
                 raise ValueError(f"Edit {e} has {len(tfs)} transforms for {M + D} foreground masks")
             raise ValueError(f"Edit {e} has {len(tfs)} transforms for {N} instances")
-    edits = [[check_transform(tf, f"edit {e}, {'object' if instances is None else 'instance'} {m}") for m, tf in enumerate(tfs)]
-             for e, tfs in enumerate(edits)]
+    # (a Bend is checked against the mask its instance draws, below, once the masks' sizes are known to agree)
+    edits = [[tf if isinstance(tf, Bend) else check_transform(tf, f"edit {e}, {'object' if instances is None else 'instance'} {m}")
+              for m, tf in enumerate(tfs)] for e, tfs in enumerate(edits)]
     for fg_mask in fg_masks:
         if fg_mask.shape[-2] != fg_mask.shape[-1]:
             raise RuntimeError(f"Expected fg_mask to be square, got shape {fg_mask.shape[-2]} x {fg_mask.shape[-1]}.")
@@ -636,6 +750,23 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
             raise ValueError("Expected all foreground masks to have one size")
     _check_single_image(shape)
     res = fg_masks[0].shape[-1] if M else int(shape[-1])
+    n_bones, flags = 1, []
+    for e, tfs in enumerate(edits):
+        for m, tf in enumerate(tfs):
+            if isinstance(tf, Bend):
+                name = f"reproject_bend_edits: edit {e}, {'object' if instances is None else 'instance'} {m}"
+                tfs[m], f = _bend_checks(tf, (fg_masks + list(donor_list))[inst[m]], name)
+                flags.append((name, f))
+                n_bones = max(n_bones, len(tfs[m].bones))
+    bent = bool(flags)
+    if bent:          # the weights' flags of every Bend of the call: ONE copy per device they lie on
+        where = {}
+        for name, f in flags:
+            where.setdefault(f.device, []).append((name, f))
+        for group in where.values():
+            for (name, _), row in zip(group, torch.stack([f for _, f in group]).tolist()):
+                _raise_bend_flags(name, row)
+    common.update(n_bones=n_bones, bent=bent)
     # the M pixel counts and the overlap flag: ONE device-to-host copy (none for host masks), before any launch of the library
     flat = [(fg_mask.detach() != 0).reshape(-1) for fg_mask in fg_masks]
     if donor is not None:          # the donor's masks behind the host's (they were checked, and are on the first mask's device)
@@ -694,6 +825,8 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
         query = "dh_reproject_camera_workspace_bytes" if cams is not None else "dh_reproject_instances_workspace_bytes"
     if surfaces:        # the border entry's list, the setting and the ratio; the rows of a view edit are per target pixel
         entry, query = "dh_reproject_surface_edits", "dh_reproject_surface_ws_bytes"
+    if bent:            # the surface entry's list, the bones and the weights; a call without a Bend is the call it was
+        entry, query = "dh_reproject_bend_edits", "dh_reproject_bend_ws_bytes"
     return _plan("objects", entry, query, res=res, kept=kept, obj_start=obj_start, n_host_kept=sum(1 for m in kept if m < M),
                          caller=caller, inst_obj=inst_obj, inst_start=inst_start, n_fg=n_fg, n_pts=n_pts,
                          cap=res * res if footprints or surfaces else n_pts,          # one row per target pixel with footprints / view surfaces, per point without
@@ -728,6 +861,8 @@ def _workspace(p, g):
     """The workspace of the plan's entry, sized by the query the plan names."""
     if p.kind != "objects":
         sizes = (g.res, 1) if p.view_surfaces else (g.res,)
+    elif p.bent:
+        sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), int(p.view_surfaces), int(p.footprints), p.n_bones)
     elif p.view_surfaces:
         sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), 1)
     elif p.with_table or p.infill_border:
@@ -814,6 +949,30 @@ def _run_background(p, g):
     return out, dbg
 
 
+def _bone_rows(p, fg_pix, dev):
+    """The rows and weights of a call with a `Bend`: rows [K][Nk][B][16] f64 (host) -- B = p.n_bones; an instance with fewer
+    bones, or an ordinary transform, pads with copies of its bone 0 -- and bone_w [K][n_pts][B] f32 on the device: the weights of
+    a `Bend` gathered at its instance's pixels (fg_pix holds the pixel list of every kept mask), 1 on bone 0 for an ordinary
+    transform, 0 on the padding."""
+    K, Nk, B = len(p.edits), len(p.caller), p.n_bones
+    flat = []
+    bone_w = torch.zeros((K, p.n_pts, B), dtype=torch.float32, device=dev)
+    bone_w[:, :, 0] = 1.0          # (an ordinary transform: bone 0; a Bend overwrites its slice)
+    pix_of = {}                    # the pixel indices of a kept mask, once per call
+    for e, tfs in enumerate(p.edits):
+        for j, n in enumerate(p.caller):
+            tf = tfs[n]
+            bones = list(tf.bones) if isinstance(tf, Bend) else [tf]
+            flat += bones + [bones[0]] * (B - len(bones))
+            if isinstance(tf, Bend):
+                a, b, o = int(p.inst_start[j]), int(p.inst_start[j + 1]), int(p.inst_obj[j])
+                if o not in pix_of:
+                    pix_of[o] = fg_pix[int(p.obj_start[o]):int(p.obj_start[o + 1])].long()
+                w = tf.weights.to(dev).reshape(len(bones), -1)
+                bone_w[e, a:b, :len(bones)] = w[:, pix_of[o]].t()
+    return _similarity_rows(flat), bone_w
+
+
 def _run_objects(p, g):
     """The kind with foreground points: the pixel lists of the kept masks, the buffers, the entry the plan names (each of
     dh_reproject_footprint_edits, _instance_edits, _donor_edits and _camera_edits takes the arguments of the one before it and a
@@ -839,7 +998,11 @@ def _run_objects(p, g):
     txy = torch.empty((K, n_pts, 2), dtype=torch.int32, device=dev)
     corr = torch.empty((K, cap, 4), dtype=torch.int64, device=dev)
     counts = torch.zeros((K, 4), dtype=torch.int32, device=dev)
-    rows = _similarity_rows([tfs[n] for tfs in p.edits for n in p.caller])    # edit-major, K x Nk rows (C-contiguous)
+    bone_w = None
+    if p.bent:
+        rows, bone_w = _bone_rows(p, fg_pix, dev)
+    else:
+        rows = _similarity_rows([tfs[n] for tfs in p.edits for n in p.caller])    # edit-major, K x Nk rows (C-contiguous)
     args = (_lib.ptr(g.d), _lib.ptr(g.bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
             _lib.ptr(g.gx), _lib.ptr(g.gy), g.ifx, g.ify, g.fx, g.fy, K,
             rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(g.bounds),
@@ -848,9 +1011,9 @@ def _run_objects(p, g):
     corr_inst = None
     if p.with_table:
         corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
-    if p.with_table or p.infill_border or p.view_surfaces:
+    if p.with_table or p.infill_border or p.view_surfaces or p.bent:
         args += (Nk, p.inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _lib.ptr(corr_inst))
-    if camera or donor or p.infill_border:
+    if camera or donor or p.infill_border or p.bent:
         dd = p.donor[0].detach().to(dev, torch.float32).contiguous() if donor else None
         args += (_lib.ptr(dd), p.n_host_kept)
     if camera:
@@ -866,12 +1029,14 @@ def _run_objects(p, g):
         bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
         args += (_view_ptr(views), has_view.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _lib.ptr(bg_valid), _lib.ptr(bg_corr),
                  _lib.ptr(bg_counts))
-    elif p.infill_border:
+    elif p.infill_border or p.bent:
         args += (None, None, None, None, None)
-    if p.infill_border or p.view_surfaces:
+    if p.infill_border or p.view_surfaces or p.bent:
         args += (p.infill_border,)
-    if p.view_surfaces:
-        args += (1, 0.0 if p.surface_ratio is None else p.surface_ratio)
+    if p.view_surfaces or p.bent:
+        args += (int(p.view_surfaces), 0.0 if p.surface_ratio is None else p.surface_ratio)
+    if p.bent:
+        args += (p.n_bones, _lib.ptr(bone_w))
     _lib.check(getattr(L, p.entry)(*args), p.entry)
     row_donor = donor_rows(corr_inst, [p.inst[n] for n in p.caller], p.M) if donor else None
     if p.with_table and p.caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
@@ -1014,6 +1179,15 @@ def reproject(depth, bg_depth, fg_masks, intrinsics, edits, *, instances=None, r
     view: an edit without a camera, and a call without any, is what it is without the setting, byte for byte.  ValueError
     (`check_view_surfaces`); NotImplementedError with a donor.  `footprints=True` with a camera stays refused.
 
+    Bend edits (DESIGN.md "Bend edits") -- a `Bend` in place of an instance's transform tuple, in any edit, for a host or a donor
+    instance: the instance carries up to 4 transforms (bones) and a weight per pixel and bone, and each of its points goes to
+    the weighted sum of where the bones put it (linear-blend skinning; `bend_chain` builds one from a line across the object).
+    Everything after the point transform sees points as before, so copies, removal, a donor, cameras, view surfaces, the
+    in-fill border and footprints compose; with footprints the triangles between neighbouring points stretch over the outside
+    of the bend.  Plain skinning is not volume preserving: two bones about one pivot pull the band between them towards the
+    chord (more bones, smaller steps).  ValueError (`check_bend`) naming the edit and the instance.  A call without a `Bend`
+    is the call it was: the same entry, the same bytes.
+
     Every refusal precedes the first launch of the library (they are `reproject_plan`'s)."""
     p = reproject_plan(depth, fg_masks, edits, instances=instances, removed_masks=removed_masks, donor_depth=donor_depth,
                        donor_masks=donor_masks, cameras=cameras, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
@@ -1103,6 +1277,19 @@ def reproject_surface_edits(depth, bg_depth, fg_masks, intrinsics, edits, instan
 
 
 INFILL_BARRIER_TIMEOUT, INFILL_NOT_CONVERGED, INFILL_BREAKDOWN = -1, -2, -3      # counts[..., 3] < 0 (geometry.hip)
+
+
+def reproject_bend_edits(depth, bg_depth, fg_masks, intrinsics, edits, instances=None, removed_masks=None, donor_depth=None,
+                         donor_masks=None, use_input_depth_normalization=False, return_debug=False,
+                         device_correspondences=False, footprints=False, footprint_max_ratio=None, return_instances=False,
+                         cameras=None, infill_border="zero", view_surfaces=False, view_surface_max_ratio=None):
+    """`reproject` for edits in which an instance may be a `Bend`; `reproject_surface_edits` is its call without one."""
+    return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=instances, removed_masks=removed_masks,
+                     donor_depth=donor_depth, donor_masks=donor_masks, cameras=cameras,
+                     use_input_depth_normalization=use_input_depth_normalization, return_debug=return_debug,
+                     device_correspondences=device_correspondences, footprints=footprints, footprint_max_ratio=footprint_max_ratio,
+                     return_instances=return_instances, infill_border=infill_border, view_surfaces=view_surfaces,
+                     view_surface_max_ratio=view_surface_max_ratio)
 
 
 class InfillNotConverged(RuntimeError):

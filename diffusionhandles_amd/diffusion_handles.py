@@ -249,11 +249,14 @@ class DiffusionHandles:
         """instances given: every result is (disparity, correspondences, instance of every row).  removed_masks: the masks of the
         objects the edits delete (object removal); fg_masks may then be empty and the edits K empty lists.  donor: None or the
         checked donor (_donor_setup): its masks follow fg_masks in the object list, and an instance table is always given."""
-        from .depth_transform import check_instances, check_transform, reproject
+        from .depth_transform import Bend, check_body, check_instances, reproject
         if cameras is not None and len(fg_masks) == 0 and removed_masks is None:
             removed_masks = []          # (checked by _camera_setup: no donor, no footprints, 'pc' mode)
         fp = self._reproject_keywords(what, cameras=True)
         if self.conf.depth_transform_mode != "pc":
+            if any(isinstance(tf, Bend) for tfs in edits for tf in tfs):
+                raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no bend edits "
+                                          "(Bend; only 'pc')")
             if removed_masks is not None:
                 raise NotImplementedError(f"{what}: depth_transform_mode {self.conf.depth_transform_mode!r} has no object removal "
                                           "(removed_masks; only 'pc')")
@@ -275,9 +278,19 @@ class DiffusionHandles:
         inst = check_instances(instances, len(fg_masks) + n_donor, f"{what}: instances")
         n_bodies, body = (len(fg_masks), "object") if inst is None else (len(inst), "instance")
         if all(len(tfs) == n_bodies for tfs in edits):          # (else the re-projection names the edit)
-            edits = [[self._fill_transform(check_transform(tf, f"{what}: edit {e}, {body} {m}")) for m, tf in enumerate(tfs)]
+            every = list(fg_masks) + ([] if donor is None else list(donor[1]))
+            mask_of = lambda m: every[m if inst is None else inst[m]]
+            edits = [[self._fill_body(check_body(tf, mask_of(m), f"{what}: edit {e}, {body} {m}")) for m, tf in enumerate(tfs)]
                      for e, tfs in enumerate(edits)]
         return reproject(depth, bg_depth, fg_masks, intrinsics, edits, instances=inst, return_instances=inst is not None, **kw)
+
+    @classmethod
+    def _fill_body(cls, tf):
+        """_fill_transform for what stands for an instance: a transform, or a Bend (every bone filled in)."""
+        from .depth_transform import Bend
+        if isinstance(tf, Bend):
+            return Bend([cls._fill_transform(b) for b in tf.bones], tf.weights)
+        return cls._fill_transform(tf)
 
     @staticmethod
     def _fill_transform(tf):
@@ -427,7 +440,13 @@ class DiffusionHandles:
         background; under the default area weighting the background's rows outnumber the objects' by roughly ten to one.
         fg_masks = [] with transforms = [] is the pure camera move.  ValueError (depth_transform.check_camera) before any
         launch; NotImplementedError naming the setting for mesh mode, footprints, background_lock: true and a donor.
-        camera=None is the call without the keyword, byte for byte."""
+        camera=None is the call without the keyword, byte for byte.
+        Bend edits (DESIGN.md "Bend edits"): a member of transforms may be a depth_transform.Bend -- up to 4 transforms (bones)
+        and a weight per pixel and bone; depth_transform.bend_chain builds one from a line across the object -- and the
+        object then changes its shape: each of its points goes to the weighted sum of where the bones put it.  Everything
+        else of the call (instances, removed_masks, donor, camera, object_weights, footprints, view surfaces, the in-fill
+        border, the background lock) sees points, rows and masks as before.  ValueError (depth_transform.check_bend) naming the
+        call, the edit and the instance before any launch; NotImplementedError naming Bend in mesh mode."""
         what = "transform_foreground_objects"
         fg_masks = list(fg_masks)
         cams = self._camera_setup(what, None if camera is None else [camera], donor)
@@ -567,7 +586,7 @@ class DiffusionHandles:
         re-projected in separate calls, and edits with and without it share the batch.  A multi-object edit may carry `camera`
         (camera moves, transform_foreground_objects; fg_masks may then be [] with no transforms: a pure camera move): edits with
         and without a camera share the batch, and edits of one image share its re-projection call."""
-        from .depth_transform import check_instances, check_removed_masks, check_transform, reproject
+        from .depth_transform import check_body, check_instances, check_removed_masks, check_transform, reproject
         fp = self._reproject_keywords("transform_foregrounds")
         if self.conf.depth_transform_mode != "pc":
             raise NotImplementedError(f"transform_foregrounds: depth_transform_mode {self.conf.depth_transform_mode!r} has no "
@@ -615,7 +634,8 @@ class DiffusionHandles:
                     raise ValueError(f"transform_foregrounds: edit {i} has {0 if tfs is None else len(tfs)} transforms for "
                                      f"{n_bodies} {body}")
                 for m, tf in enumerate(tfs):
-                    check_transform(tf, f"transform_foregrounds: edit {i}, {'object' if inst is None else 'instance'} {m}")
+                    check_body(tf, masks[m if inst is None else inst[m]],
+                               f"transform_foregrounds: edit {i}, {'object' if inst is None else 'instance'} {m}")
                 if e.get("object_weights") is not None and cams[i] is not None:
                     weights[i] = self._camera_weights(f"transform_foregrounds: edit {i}", e["object_weights"], n_bodies)
                 elif e.get("object_weights") is not None:

@@ -637,7 +637,62 @@ def _check_similarity_entry(where, t):
 
 
 CAMERA_KEYS = ("rot_angle", "rot_axis", "translation", "pivot", "pivot_pixel")
-_TRANSFORM_KEYS = ("rotation_angle", "rotation_axis", "translation", "scale", "pivot", "objects", "remove", "object_weights")
+BEND_KEYS = ("p0", "p1", "width", "bones", "pivot_pixel")
+_TRANSFORM_KEYS = ("rotation_angle", "rotation_axis", "translation", "scale", "pivot", "objects", "remove", "object_weights", "bend")
+
+
+def _check_bend_entry(where, t):
+    """The optional "bend" of a member of "objects", or of the entry of a single-mask scene (not in the reference; bend edits): a
+    dict {"p0": [x, y], "p1": [x, y] (pixels: the line the object bends across), "width" (pixels, > 0: the band that blends),
+    "bones" (2 .. 4, default 2), "pivot_pixel" ([x, y], optional: the turn goes through the point of that pixel; default: the
+    member's "pivot", else the midpoint of p0 p1)}.  The member's own rotation_angle / rotation_axis / translation are then
+    the FULL motion of the far side, handed to depth_transform.bend_chain when the edit runs.  ValueError naming `where`."""
+    if not isinstance(t, dict) or "bend" not in t:
+        return
+    b = t["bend"]
+    if not isinstance(b, dict):
+        raise ValueError(f"{where}: \"bend\" must be an object with {BEND_KEYS}, got {b!r}")
+    extra = [k for k in b if k not in BEND_KEYS]
+    if extra:
+        raise ValueError(f"{where}: \"bend\" has unknown keys {extra} (known: {BEND_KEYS})")
+    for key in ("p0", "p1", "width"):
+        if key not in b:
+            raise ValueError(f"{where}: \"bend\" needs \"{key}\"")
+    for key in ("p0", "p1"):
+        v = b[key]
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_is_number(x) and np.isfinite(x) for x in v):
+            raise ValueError(f"{where}: \"bend\": \"{key}\" must be a pixel [x, y], two finite numbers, got {v!r}")
+    if [float(x) for x in b["p0"]] == [float(x) for x in b["p1"]]:
+        raise ValueError(f"{where}: \"bend\": \"p0\" and \"p1\" are one pixel ({b['p0']!r}): no line")
+    if not (_is_number(b["width"]) and np.isfinite(b["width"]) and b["width"] > 0):
+        raise ValueError(f"{where}: \"bend\": \"width\" must be a positive number of pixels, got {b['width']!r}")
+    n = b.get("bones", 2)
+    if not (isinstance(n, int) and not isinstance(n, bool) and 2 <= n <= 4):
+        raise ValueError(f"{where}: \"bend\": \"bones\" must be 2, 3 or 4, got {n!r}")
+    if "pivot_pixel" in b:
+        v = b["pivot_pixel"]
+        if "pivot" in t:
+            raise ValueError(f"{where}: \"bend\" has \"pivot_pixel\" and the entry a \"pivot\"")
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(isinstance(x, int) and not isinstance(x, bool) and x >= 0 for x in v):
+            raise ValueError(f"{where}: \"bend\": \"pivot_pixel\" must be [x, y], two integers >= 0, got {v!r}")
+    if "scale" in t:
+        raise ValueError(f"{where}: an entry with \"bend\" takes no \"scale\" (the bones of a bend chain are rigid)")
+    if "remove" in t or "objects" in t:
+        raise ValueError(f"{where}: \"bend\" belongs to one object: a member of \"objects\", or the entry of a single-mask scene")
+
+
+def bend_args(t):
+    """The "bend" of one entry -> None (no key), or dict(p0, p1, width, bones) with `pivot_pixel` ((x, y)) when it gives one: the
+    keyword arguments of depth_transform.bend_chain that do not come from the entry's own transform keys."""
+    if not isinstance(t, dict) or "bend" not in t:
+        return None
+    _check_bend_entry("bend_args", t)
+    b = t["bend"]
+    out = dict(p0=(float(b["p0"][0]), float(b["p0"][1])), p1=(float(b["p1"][0]), float(b["p1"][1])), width=float(b["width"]),
+               bones=int(b.get("bones", 2)))
+    if "pivot_pixel" in b:
+        out["pivot_pixel"] = (int(b["pivot_pixel"][0]), int(b["pivot_pixel"][1]))
+    return out
 
 
 def _check_camera_entry(where, t):
@@ -706,9 +761,11 @@ def _check_similarity_entries(scene_dir, transforms):
         if isinstance(t, dict) and "remove" in t and "objects" in t:
             raise ValueError(f"{scene_dir}: transform {name!r}: \"remove\" belongs inside a member of \"objects\"")
         _check_similarity_entry(f"{scene_dir}: transform {name!r}", t)
+        _check_bend_entry(f"{scene_dir}: transform {name!r}", t)
         if isinstance(t, dict) and isinstance(t.get("objects"), (list, tuple)):
             for m, o in enumerate(t["objects"]):
                 _check_similarity_entry(f"{scene_dir}: transform {name!r}, object {m}", o)
+                _check_bend_entry(f"{scene_dir}: transform {name!r}, object {m}", o)
 
 
 def load_scene_geometry(scene_dir, img_res=512):
@@ -738,7 +795,11 @@ def load_scene_geometry(scene_dir, img_res=512):
     An entry may carry "camera": {"rot_angle", "rot_axis", "translation", "pivot" | "pivot_pixel": [x, y]} (not in the reference;
     camera moves, _check_camera_entry): the edit also moves the viewpoint.  In a multi-object scene it stands beside "objects";
     in a single-mask scene an entry with only "camera" is a pure camera move of the whole image.  Malformed values raise
-    ValueError here, when the scene is loaded; files without the key load to what they loaded to."""
+    ValueError here, when the scene is loaded; files without the key load to what they loaded to.
+    A member of "objects" -- in a single-mask scene the entry itself -- may carry "bend": {"p0", "p1", "width", "bones",
+    "pivot_pixel"} (not in the reference; bend edits, _check_bend_entry): the object bends across the line p0 p1, its own
+    rotation_angle / rotation_axis / translation being the full motion of the far side (depth_transform.bend_chain).
+    Malformed values raise ValueError here; files without the key load to what they loaded to."""
     import torch
     j = os.path.join
     with open(j(scene_dir, "transforms.json")) as f:
@@ -828,6 +889,7 @@ def transform_args(t):
             raise ValueError(f"transform_args: an entry that removes the object is exactly {{\"remove\": true}}, got {dict(t)!r}")
         return dict(remove=True)
     _check_similarity_entry("transform_args", t)
+    _check_bend_entry("transform_args", t)
     if is_pure_camera(t):       # a pure camera move of the whole image: no object transform
         return dict(camera=camera_args(t), camera_only=True)
     args = dict(rot_angle=float(t.get("rotation_angle", 0.0)),
@@ -839,6 +901,8 @@ def transform_args(t):
         args["pivot"] = tuple(float(v) for v in t["pivot"])
     if isinstance(t, dict) and "camera" in t:
         args["camera"] = camera_args(t)
+    if isinstance(t, dict) and "bend" in t:          # (not in the reference) the entry's motion is a bend chain's full motion
+        args["bend"] = bend_args(t)
     return args
 
 
@@ -852,7 +916,9 @@ def object_transform_args(entry):
     `instances` then speak about the remaining members and the remaining masks.  When a member carries "donor" (entry_donor)
     the dict also has `donor`, the donor mask index of every donor member: `transforms` and the weights list the host's
     (remaining) members and then the donor's, and `instances` is always there -- the host's table (or 0, 1, ...), then
-    M' + d for a member of donor mask d, M' the number of (remaining) host masks."""
+    M' + d for a member of donor mask d, M' the number of (remaining) host masks.  When a member carries "bend" (bend_args) the
+    dict also has `bends`, one entry per transform: None, or the member's bend_args -- the caller replaces that transform by
+    depth_transform.bend_chain of its angle, axis, translation and pivot (tools/run_edit.py)."""
     if not isinstance(entry, dict) or "objects" not in entry:
         raise ValueError("object_transform_args: the entry has no \"objects\" list")
     if "camera" in entry:          # camera moves: the entry's camera beside what the entry gives without it
@@ -864,6 +930,8 @@ def object_transform_args(entry):
         out = object_transform_args({"objects": host}) if host else dict(transforms=[], object_weights=None)
         n_host = max(out["instances"]) + 1 if "instances" in out else len(out["transforms"])
         more = object_transform_args({"objects": members})
+        if "bends" in out or "bends" in more:
+            out["bends"] = out.get("bends", [None] * len(out["transforms"])) + more.get("bends", [None] * len(more["transforms"]))
         out["transforms"] = out["transforms"] + more["transforms"]
         out["instances"] = out.get("instances", list(range(n_host))) + [n_host + d for d in index]
         w = entry.get("object_weights")
@@ -872,15 +940,17 @@ def object_transform_args(entry):
         return out
     rem = entry_removal(entry["objects"], None, "object_transform_args")
     members = entry["objects"] if rem is None else rem[1]
-    triples = []
+    triples, bends = [], []
     for t in members:
         a = transform_args(t)
         triple = (a["rot_angle"], a["rot_axis"], a["translation"])
         triples.append(triple + (a.get("scale"), a.get("pivot")) if "scale" in a or "pivot" in a else triple)
+        bends.append(a.get("bend"))
+    bent = {} if all(b is None for b in bends) else dict(bends=bends)
     w = entry.get("object_weights")
     if w is not None and not isinstance(w, str):
         w = [float(v) for v in w]
     if rem is not None:          # `remove`: the scene's mask indices the edit deletes; `instances` counts among the remaining masks
-        return dict(transforms=triples, object_weights=w, remove=rem[0], **({} if rem[2] is None else dict(instances=rem[2])))
+        return dict(transforms=triples, object_weights=w, remove=rem[0], **({} if rem[2] is None else dict(instances=rem[2])), **bent)
     inst = entry_instances(entry["objects"], None, "object_transform_args")
-    return dict(transforms=triples, object_weights=w, **({} if inst is None else dict(instances=inst)))
+    return dict(transforms=triples, object_weights=w, **({} if inst is None else dict(instances=inst)), **bent)

@@ -315,6 +315,44 @@ int dh_reproject_surface_background(const float* bg_depth, int res, const float*
                                     void* workspace, size_t workspace_bytes, void* stream,
                                     const double* view, const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts,
                                     int infill_border, int view_surfaces, float surface_max_ratio);
+/* Bend edits (not in the reference, which moves an object as one rigid body and has no such mode; DESIGN.md, "Bend edits"):
+ * linear-blend skinning of the point transform.  An instance carries n_bones transform rows per edit and every point of it a
+ * weight per bone.  dh_reproject_bend_edits is dh_reproject_surface_edits plus
+ *   n_bones     1 .. DH_MAX_BONES, for the call;
+ *   xforms_host then [n_edits][n_instances][n_bones][DH_SIMILARITY_ROW] f64 (host): every row with the meaning it has above, its
+ *               own scale and its own pivot, or else the mask's centroid;
+ *   bone_w      [n_edits][n_pts][n_bones] f32 on the DEVICE, 16-byte aligned, by point-list position (instance after instance).
+ * With X_b = the point under row b (the arithmetic of the entries above, unchanged), the point goes to the f64 sum, not
+ * contracted, over b ascending and only over the bones with w_b != 0: acc = w_b0 * X_b0 for the first such bone, then
+ * acc = acc + w_b * X_b, per component.  A point whose weights are all 0 takes bone 0 with weight 1.  The view row, the
+ * projection, the clamp or discard, the stored vertices of footprints and view surfaces and the z key act on acc as they act
+ * on (X, Y, Z) above.  So weights (1, 0, ..) everywhere give the bits of the call without bones.  A donor instance may have
+ * bones like any other.  Plain linear-blend skinning: not volume preserving.
+ * The entry never reads bone_w on the host.  The weights are the CALLER's to validate: any finite weights give the weighted
+ * sum as written, with no normalisation (weights that do not sum to 1 scale the point about the camera centre).
+ * n_bones = 1 with bone_w = NULL is dh_reproject_surface_edits launch for launch and byte for byte: that entry is this call.
+ * Workspace: dh_reproject_bend_ws_bytes = dh_reproject_surface_ws_bytes at footprints = 0, n_bones = 1; more bones grow it only
+ * by the device copy of the extra rows, n_edits * n_instances * (n_bones - 1) * DH_SIMILARITY_ROW doubles (rounded up to the
+ * arena's alignment).  footprints = 1 (never with view_surfaces = 1) adds what footprints add to the instance query, so the one
+ * query sizes every call of this entry.
+ * DH_ERR_ARG before any launch, outputs untouched, beyond what that entry refuses: n_bones outside 1 .. DH_MAX_BONES; n_bones
+ * > 1 with a null bone_w; a bone_w that is not 16-byte aligned; any of the n_edits * n_instances * n_bones rows malformed. */
+#define DH_MAX_BONES 4
+int dh_reproject_bend_ws_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
+                               int view_surfaces, int footprints, int n_bones, size_t* bytes);
+int dh_reproject_bend_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
+                            int n_objects, const int32_t* obj_start, int res, const float* grid_x,
+                            const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
+                            int n_edits, const double* xforms_host, const float* bounds,
+                            float* zmap, uint8_t* raw_mask, uint8_t* clean_mask, float* disparity,
+                            uint8_t* vis, int32_t* target_xy, int64_t* corr, int32_t* counts,
+                            void* workspace, size_t workspace_bytes, void* stream,
+                            int footprints, float max_ratio, int corr_capacity,
+                            int n_instances, const int32_t* inst_obj, uint8_t* corr_inst,
+                            const float* donor_depth, int n_host_objects,
+                            const double* views, const uint8_t* has_view, const uint8_t* bg_valid,
+                            int64_t* bg_corr, int32_t* bg_counts, int infill_border,
+                            int view_surfaces, float surface_max_ratio, int n_bones, const float* bone_w);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);

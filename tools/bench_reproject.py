@@ -22,7 +22,12 @@ DH_BORDER=reflect (default unset = zero): every call of the run in-fills with th
 timed here keep their parameter lists, so the setting is given to depth_transform.reproject, which they all are;
 profiles/infill_border/); every line then says so.
 DH_VIEW_SURFACES=1 [DH_VIEW_SURFACE_RATIO=R] (default unset), next to DH_CAMERA=1: the camera line runs with view surfaces
-(reproject_surface_edits: the scene as triangles under the eight cameras; profiles/view_surfaces/) and says so."""
+(reproject_surface_edits: the scene as triangles under the eight cameras; profiles/view_surfaces/) and says so.
+DH_BEND=B (default unset; 2 .. 4; the two-sphere scene whatever DH_OBJECTS says): two further lines time the K = 8 call on the two
+spheres unbent (reproject_object_edits) and the same call with sphere 0 a depth_transform.bend_chain of B bones across its
+middle, the edit's own transform the full motion of its lower half (reproject_bend_edits; profiles/bend/).  The weights lie on
+the device; the bent call's time includes the host's check of them and the gather at the objects' pixels.  With
+DH_FOOTPRINTS=1 both lines are followed by their footprint runs."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -188,6 +193,32 @@ if os.environ.get("DH_CAMERA", "0") not in ("", "0"):
     report(camera_call, " two spheres, eight orbit cameras" +
            (f" view surfaces (ratio {vs['view_surface_max_ratio']})" if surfaces else ""))
     print(f"  background rows per edit {n_bg}", flush=True)
+    M = M_shown
+bend = int(os.environ.get("DH_BEND", "0") or 0)
+if bend:
+    from diffusionhandles_amd.depth_transform import Bend, bend_chain, reproject_bend_edits, reproject_object_edits
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import multi_object_ref as R
+    if not 2 <= bend <= 4:
+        sys.exit("DH_BEND: 2 to 4 bones")
+    b_depth, b_bg, b_masks = R.two_spheres(res)
+    b_depth, b_bg, b_masks = b_depth.to(dev), b_bg.to(dev), [m.to(dev) for m in b_masks]
+    M_shown, M = M, 2
+    two = [[tfs[i], tfs[(i + 3) % 8]] for i in range(K)]
+    cx, cy, rad, _ = R.SPHERES[0]
+    k = res / 512.0
+    p0, p1 = (int((cx - rad) * k), int(cy * k)), (int((cx + rad) * k), int(cy * k))
+
+    def chain(tf):
+        c = bend_chain(b_depth, intr, b_masks[0], p0, p1, res / 8.0, tf[0], tf[1], tf[2], bones=bend)
+        return Bend(c.bones, c.weights.to(dev))
+    bent = [[chain(e[0]), e[1]] for e in two]
+    report(lambda **kw: reproject_object_edits(b_depth, b_bg, b_masks, intr, two, **kw), " two spheres, unbent")
+    report(lambda **kw: reproject_bend_edits(b_depth, b_bg, b_masks, intr, bent, **kw), f" two spheres, sphere 0 a bend chain of {bend} bones")
+    if footprints:
+        report(lambda **kw: reproject_object_edits(b_depth, b_bg, b_masks, intr, two, **kw), " two spheres, unbent", footprints=True)
+        report(lambda **kw: reproject_bend_edits(b_depth, b_bg, b_masks, intr, bent, **kw),
+               f" two spheres, sphere 0 a bend chain of {bend} bones", footprints=True)
     M = M_shown
 if scale is not None:
     if M == 1:

@@ -370,6 +370,12 @@ def prepare_scene(args, scene, out, transform_names, warn=True):
                 if getattr(args, "edit_batch", 1) > 1:
                     raise NotImplementedError(f"{scene}: transform {n!r} moves the camera (\"camera\"); --edit-batch (mixed-image "
                                               "batches of scene directories) does not pass cameras, use --edit-batch 1")
+        if args.mode != "pc":           # bend edits: before the identity is computed
+            for n, t in sc["transforms"].items():
+                objs = t.get("objects") if isinstance(t, dict) else None
+                if (isinstance(t, dict) and "bend" in t) or any(isinstance(o, dict) and "bend" in o for o in objs or []):
+                    raise NotImplementedError(f"{scene}: transform {n!r} bends an object (\"bend\"); --mode {args.mode} has no bend "
+                                              "edits, use --mode pc")
         if args.mode != "pc":           # object removal: before the identity is computed
             for n, t in sc["transforms"].items():
                 objs = t.get("objects") if isinstance(t, dict) else None
@@ -549,6 +555,36 @@ def resolve_camera(dh, depth, camera):
     return (camera["rot_angle"], camera["rot_axis"], camera["translation"], pivot)
 
 
+def resolve_bends(dh, tf, depth, masks, donor=None):
+    """The transforms of one entry with depth_transform.bend_chain in place of every member that carries "bend"
+    (object_transform_args' `bends`; a single-mask scene's transform_args: `bend`).  masks: the masks the entry leaves, in
+    order; donor: the scene's donor (depth, masks) when the entry has donor members.  A member's own angle, axis and
+    translation are the chain's full motion; its "pivot", or the bend's "pivot_pixel" (resolved against the depth the member's
+    mask belongs to), the chain's pivot."""
+    from diffusionhandles_amd.depth_transform import bend_chain, pivot_at_pixel
+    if "transforms" in tf:
+        tfs, bends = list(tf["transforms"]), tf.get("bends")
+    else:
+        tfs, bends = [(tf["rot_angle"], tf["rot_axis"], tf["translation"], tf.get("scale"), tf.get("pivot"))], [tf.get("bend")]
+    if not bends or all(b is None for b in bends):
+        return tfs
+    intr = dh.diffuser.get_depth_intrinsics(device=depth.device)
+    every = [(depth, m) for m in masks]
+    if donor is not None:
+        every += [(donor["depth"].to(depth.device), m.to(depth.device)) for m in donor["masks"]]
+    inst = tf.get("instances") or list(range(len(tfs)))
+    for n, b in enumerate(bends):
+        if b is None:
+            continue
+        d, m = every[inst[n]]
+        t = tfs[n]
+        pivot = t[4] if len(t) == 5 else None
+        if "pivot_pixel" in b:
+            pivot = pivot_at_pixel(d, intr, *b["pivot_pixel"])
+        tfs[n] = bend_chain(d, intr, m, b["p0"], b["p1"], b["width"], t[0], t[1], t[2], pivot, b["bones"])
+    return tfs
+
+
 def split_removed(masks, remove):
     """The masks of a multi-object scene as the keywords of an edit call: fg_masks (what the entry leaves) and, for an entry
     with {"remove": true} members (object_transform_args' `remove`), removed_masks."""
@@ -608,8 +644,12 @@ def run_test_set_batched(args, conf, handles, names, input_dir):
             if prep[s].get("release") is not None:          # (--background-lock: the scene's release.png)
                 common["release_mask"] = prep[s]["release"]
             if r["fg_masks"] is not None:
-                edits.append(dict(common, **split_removed(r["fg_masks"], tf.get("remove")), transforms=tf["transforms"],
+                sp = split_removed(r["fg_masks"], tf.get("remove"))
+                edits.append(dict(common, **sp, transforms=resolve_bends(handles(prep[s]["res"]), tf, r["depth"], sp["fg_masks"]),
                                   object_weights=tf["object_weights"], instances=tf.get("instances")))
+            elif tf.get("bend"):            # a single-mask scene's entry with "bend": the one-mask form of the multi-object edit
+                edits.append(dict(common, fg_masks=[r["fg_mask"]],
+                                  transforms=resolve_bends(handles(prep[s]["res"]), tf, r["depth"], [r["fg_mask"]])))
             elif tf.get("remove"):          # a single-mask scene's {"remove": true}: a pure removal
                 edits.append(dict(common, fg_masks=[], transforms=[], removed_masks=[r["fg_mask"]]))
             else:
@@ -669,9 +709,14 @@ def run_scene(args, conf, handles, scene, out, transform_names, identity=None):
             rel = {} if p.get("release") is None else dict(release_mask=p["release"])
             sp = split_removed(p["masks_dev"], tf.get("remove"))
             res_ = dh.transform_foreground_objects(depth, prompt, sp["fg_masks"], bg_depth, null_text, noise, acts,
-                                                   transforms=tf["transforms"], object_weights=tf["object_weights"],
+                                                   transforms=resolve_bends(dh, tf, depth, sp["fg_masks"], p.get("donor")),
+                                                   object_weights=tf["object_weights"],
                                                    removed_masks=sp.get("removed_masks"), instances=tf.get("instances"),
                                                    **(dict(donor=donor) if tf.get("donor") else {}), **rel, **cam)
+        elif tf.get("bend"):            # a single-mask scene's entry with "bend": the one-mask form of transform_foreground_objects
+            rel = {} if p.get("release") is None else dict(release_mask=p["release"])
+            res_ = dh.transform_foreground_objects(depth, prompt, [mask], bg_depth, null_text, noise, acts,
+                                                   transforms=resolve_bends(dh, tf, depth, [mask]), **rel, **cam)
         elif tf.get("camera_only"):     # a single-mask scene's entry with only "camera": the whole image from another viewpoint
             res_ = dh.transform_foreground_objects(depth, prompt, [], depth, null_text, noise, acts, transforms=[], **cam)
         elif cam:                       # the object moves and the camera moves: the one-mask form of transform_foreground_objects

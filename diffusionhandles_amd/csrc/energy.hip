@@ -48,7 +48,15 @@ __global__ void k_load_map(const T* src, float* dst, int C, int hin, int win, in
   }
 }
 
-// transpose of k_load_map: one block per INPUT cell, gathers from the grid cells that read it
+// transpose of k_load_map: one block per INPUT cell, gathers from the grid cells that read it.
+// The gather window, per axis.  Grid row y reads input rows i0 = floor(s) and i0 + 1 at s = sy (y + 0.5) - 0.5, so it
+// reads row yi with a non-zero weight only if yi - 1 < s < yi + 1, that is
+//     (yi - 0.5) / sy - 0.5  <  y  <  (yi + 1.5) / sy - 0.5        (sy = h_in / grid, any ratio)
+// The two clamps of bilinear_src stay inside it: s < 0 becomes s = 0 and reads row 0 alone -- those y lie below the upper
+// bound of yi = 0 and the window's lower end is clamped to 0; i0 = n_in - 1 reads the last row alone (i1 = i0) -- those y
+// have s >= n_in - 1 > yi - 1 for yi = n_in - 1 and the upper end is clamped to grid - 1.  One more cell on either side
+// absorbs the f32 rounding of the bounds; a cell of the window that does not read (yi, xi) has weight 0 and is skipped,
+// so the cells that count are added in ascending (y, x) order whatever the window's width.
 template <class T>
 __global__ void k_store_grad(const float* g, T* out, int C, int hin, int win, int grid, float scale) {
   const int cell = blockIdx.x;
@@ -59,8 +67,8 @@ __global__ void k_store_grad(const float* g, T* out, int C, int hin, int win, in
   }
   const int yi = cell / win, xi = cell - yi * win;
   const float sy = (float)hin / (float)grid, sx = (float)win / (float)grid;
-  int ylo = (int)floorf(((float)yi - 1.f) / sy) - 1, yhi = (int)ceilf(((float)yi + 1.f) / sy) + 1;
-  int xlo = (int)floorf(((float)xi - 1.f) / sx) - 1, xhi = (int)ceilf(((float)xi + 1.f) / sx) + 1;
+  int ylo = (int)floorf(((float)yi - 0.5f) / sy - 0.5f) - 1, yhi = (int)ceilf(((float)yi + 1.5f) / sy - 0.5f) + 1;
+  int xlo = (int)floorf(((float)xi - 0.5f) / sx - 0.5f) - 1, xhi = (int)ceilf(((float)xi + 1.5f) / sx - 0.5f) + 1;
   ylo = ylo < 0 ? 0 : ylo; xlo = xlo < 0 ? 0 : xlo;
   yhi = yhi > grid - 1 ? grid - 1 : yhi; xhi = xhi > grid - 1 ? grid - 1 : xhi;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {

@@ -172,7 +172,8 @@ def test_cells_bit_exact(golden):
 
 
 def test_energy_vs_golden(golden):
-    """fp32 inputs: loss rel 1e-5, gradient abs 1e-6 (f32 summation order differs)."""
+    """fp32 inputs: loss rel 1e-5, gradient abs 1e-6 (f32 summation order differs).
+    The 16-bit and the resized forms of this path are held per element in tests/test_energy_general_gpu.py."""
     from diffusionhandles_amd import losses as LS
     g3, g5 = golden("g3_zbuffer.npz"), golden("g5_energy.npz")
     corr = torch.from_numpy(g3["t2_corr"].astype(np.int64))

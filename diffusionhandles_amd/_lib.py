@@ -49,6 +49,30 @@ class EnergyDonorItem(ctypes.Structure):
     _fields_ = [("item", EnergyItem), ("donor", c_p), ("donor_objects", ctypes.c_uint32)]
 
 
+class ReprojectArgs(ctypes.Structure):
+    """dh_reproject_args: the one argument record of dh_reproject / dh_reproject_workspace (zero means off); field for field
+    the header's struct.  A new record has struct_bytes set."""
+    _i32, _u8p, _i32p = ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+    _fields_ = [("struct_bytes", ctypes.c_uint32),
+                ("res", _i32), ("n_fg", _i32), ("n_objects", _i32), ("n_edits", _i32), ("n_instances", _i32), ("n_bones", _i32),
+                ("corr_capacity", _i32),
+                ("footprints", _i32), ("n_donor_objects", _i32), ("infill_border", _i32), ("view_surfaces", _i32),
+                ("max_ratio", c_f), ("surface_max_ratio", c_f), ("inv_fx", c_f), ("inv_fy", c_f), ("fx", c_d), ("fy", c_d),
+                # device inputs
+                ("depth", c_p), ("bg_depth", c_p), ("fg_pix", c_p), ("grid_x", c_p), ("grid_y", c_p), ("bounds", c_p),
+                ("donor_depth", c_p), ("bg_valid", c_p), ("bone_w", c_p),
+                # host inputs
+                ("obj_start", _i32p), ("inst_obj", _i32p), ("xforms_host", ctypes.POINTER(c_d)), ("views", ctypes.POINTER(c_d)),
+                ("has_view", _u8p),
+                # device outputs
+                ("zmap", c_p), ("raw_mask", c_p), ("clean_mask", c_p), ("disparity", c_p), ("vis", c_p), ("target_xy", c_p),
+                ("corr", c_p), ("corr_inst", c_p), ("counts", c_p), ("bg_corr", c_p), ("bg_counts", c_p),
+                ("workspace", c_p), ("workspace_bytes", c_sz), ("stream", c_p)]
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=ctypes.sizeof(ReprojectArgs), **fields)
+
+
 class LockItem(ctypes.Structure):
     """dh_lock_item: one edit of dh_ddim_cfg_step_locked"""
     _fields_ = [("keep", c_p), ("ref", c_p)]
@@ -127,6 +151,9 @@ SIGNATURES = {
                                       c_d, c_i, ctypes.POINTER(c_d), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
                                       c_p, c_i, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p, c_p, c_i,
                                       ctypes.POINTER(c_d), ctypes.POINTER(ctypes.c_uint8), c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p]),
+    # the call and its query; every dh_reproject_* row above is this record filled by the library (csrc/reproject_compat.cpp)
+    "dh_reproject": (c_i, [ctypes.POINTER(ReprojectArgs)]),
+    "dh_reproject_workspace": (c_i, [ctypes.POINTER(ReprojectArgs), ctypes.POINTER(c_sz)]),
     "dh_reproject_background_workspace_bytes": (c_i, [c_i, ctypes.POINTER(c_sz)]),
     "dh_reproject_background": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "dh_unproject": (c_i, [c_p, c_i, c_p, c_p, c_f, c_f, c_p, c_p]),
@@ -284,6 +311,8 @@ DEBUG_SIGNATURES = {
     "dh_dbg_arena_gap": (c_i, [c_i]),
     "dh_dbg_arena_log": (c_i, [c_i]),
     "dh_dbg_arena_log_read": (c_i, [ctypes.POINTER(ctypes.c_int64), c_i, ctypes.POINTER(c_i)]),
+    # (record, out, cap, n): the members of a dh_reproject_args as the library reads them (tests/test_reproject_record.py)
+    "dh_dbg_reproject_args": (c_i, [ctypes.POINTER(ReprojectArgs), ctypes.POINTER(ctypes.c_int64), c_i, ctypes.POINTER(c_i)]),
     # hooks of the kernels only the engines launch (tests/test_engine_kernels_gpu.py)
     # dh_dbg_gemm's arguments with `pad` behind `up`
     "dh_dbg_gemm_pad": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i,

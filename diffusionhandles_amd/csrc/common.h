@@ -21,13 +21,15 @@ void set_error(const std::string& s);
     }                                                                                   \
   } while (0)
 
-#define DH_REQUIRE(cond, msg)                                                           \
+// (name: the function a refusal is reported under -- DH_REQUIRE: the one it stands in)
+#define DH_REQUIRE_AS(name, cond, msg)                                                  \
   do {                                                                                  \
     if (!(cond)) {                                                                      \
-      dh::set_error(std::string(__func__) + ": " + (msg));                              \
+      dh::set_error(std::string(name) + ": " + (msg));                                  \
       return DH_ERR_ARG;                                                                \
     }                                                                                   \
   } while (0)
+#define DH_REQUIRE(cond, msg) DH_REQUIRE_AS(__func__, cond, msg)
 
 #define DH_LAUNCH_CHECK()                                                               \
   do {                                                                                  \

@@ -3,6 +3,7 @@
 // product path.
 #include <stdlib.h>
 
+#include <cstring>
 #include <vector>
 
 #include "unet_kernels.h"
@@ -43,7 +44,34 @@ extern "C" int dh_dbg_arena_log_read(int64_t* out, int cap, int* n) {
   return DH_OK;
 }
 
-static void* g_dbg_tiled = nullptr;      // the tiled copy of the last weight matrix dh_dbg_gemm was given
+// the members of a dh_reproject_args as this library reads them, in declaration order: integers by value, floats, doubles and
+// pointers by bit pattern (the ctypes twin in _lib.py is compared against it).  *n = the members there are
+extern "C" int dh_dbg_reproject_args(const dh_reproject_args* a, int64_t* out, int cap, int* n) {
+  DH_REQUIRE(a && n && cap >= 0 && (cap == 0 || out), "bad arguments");
+  std::vector<int64_t> v;
+  auto bits = [&](auto x) {
+    int64_t b = 0;
+    static_assert(sizeof x <= sizeof b, "a member wider than 64 bits");
+    memcpy(&b, &x, sizeof x);
+    v.push_back(b);
+  };
+  for (int64_t x : {(int64_t)a->struct_bytes, (int64_t)a->res, (int64_t)a->n_fg, (int64_t)a->n_objects, (int64_t)a->n_edits,
+                    (int64_t)a->n_instances, (int64_t)a->n_bones, (int64_t)a->corr_capacity, (int64_t)a->footprints,
+                    (int64_t)a->n_donor_objects, (int64_t)a->infill_border, (int64_t)a->view_surfaces})
+    v.push_back(x);
+  bits(a->max_ratio), bits(a->surface_max_ratio), bits(a->inv_fx), bits(a->inv_fy), bits(a->fx), bits(a->fy);
+  bits(a->depth), bits(a->bg_depth), bits(a->fg_pix), bits(a->grid_x), bits(a->grid_y), bits(a->bounds), bits(a->donor_depth);
+  bits(a->bg_valid), bits(a->bone_w);
+  bits(a->obj_start), bits(a->inst_obj), bits(a->xforms_host), bits(a->views), bits(a->has_view);
+  bits(a->zmap), bits(a->raw_mask), bits(a->clean_mask), bits(a->disparity), bits(a->vis), bits(a->target_xy), bits(a->corr);
+  bits(a->corr_inst), bits(a->counts), bits(a->bg_corr), bits(a->bg_counts);
+  bits(a->workspace), bits(a->workspace_bytes), bits(a->stream);
+  for (size_t i = 0; i < v.size() && i < (size_t)cap; ++i) out[i] = v[i];
+  *n = (int)v.size();
+  return DH_OK;
+}
+
+static void* g_dbg_tiled = nullptr;     // the tiled copy of the last weight matrix dh_dbg_gemm was given
 
 // timing runs (tools/bench_gemm_warmth.py): one streaming read over the tiled weights, i.e. what a prefetch would leave in the caches
 __global__ void k_dbg_touch(const uint4* p, size_t n16, unsigned* sink) {

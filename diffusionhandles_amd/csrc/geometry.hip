@@ -1422,8 +1422,24 @@ struct ReprojectWs {
 // per edit (instances; 0 = M, the call without copies, whose carving -- and so every workspace query that existed before the
 // copies -- is what it was: the wave tier's list then has a slot per triangle of the grid, else 2 n_pts per edit)
 // (B: rows per instance, the bones of a bend edit; 1 = every carving that existed before them)
-static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, bool footprints = false, int N = 0,
-                  bool camera = false, bool surfaces = false, int B = 1) {
+struct CarveSpec {
+  int res, n_fg, K, M, N, B;
+  bool footprints, camera, surfaces;
+};
+
+// What a record carves, for the call and for the query alike.  n_pts and any_view are the two facts they learn differently (the
+// call from its checked tables and view rows, the query from what the record says).  Without a foreground point the view lives
+// in the one transform row the carving holds, so nothing is taken for it.  View surfaces act only where there is a view.
+static CarveSpec carve_spec(const dh_reproject_args& a, int n_pts, bool any_view) {
+  const bool surfaces = any_view && a.view_surfaces != 0;
+  if (a.n_fg == 0) return {a.res, 0, a.n_edits, a.n_objects > 0 ? a.n_objects : 1, 0, 1, false, false, surfaces};
+  return {a.res, n_pts, a.n_edits, a.n_objects, a.inst_obj || a.n_instances ? a.n_instances : 0, a.n_bones > 1 ? a.n_bones : 1,
+          a.footprints != 0, any_view, surfaces};
+}
+
+static bool carve(Arena& a, const CarveSpec& s, ReprojectWs& w) {
+  const int res = s.res, n_fg = s.n_fg, K = s.K, M = s.M, N = s.N, B = s.B;
+  const bool footprints = s.footprints, camera = s.camera, surfaces = s.surfaces;
   const size_t R2 = (size_t)res * res, P = R2 + n_fg;
   w.xf = a.take<Xf>((size_t)K * (N > 0 ? N : M) * B);
   w.cen = a.take<float>(4 * M);
@@ -1469,29 +1485,6 @@ static bool carve(Arena& a, int res, int n_fg, int K, int M, ReprojectWs& w, boo
 
 using namespace dh;
 
-extern "C" int dh_reproject_objects_workspace_bytes(int res, int n_fg, int n_edits, int n_objects, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && n_fg >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, n_fg, n_edits, n_objects, w);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-extern "C" int dh_reproject_footprints_workspace_bytes(int res, int n_fg, int n_edits, int n_objects, int footprints, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && n_fg >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
-  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, n_fg, n_edits, n_objects, w, footprints != 0);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-extern "C" int dh_reproject_workspace_bytes(int res, int n_fg, int n_edits, size_t* bytes) {
-  return dh_reproject_objects_workspace_bytes(res, n_fg, n_edits, 1, bytes);
-}
-
 extern "C" int dh_fg_pixel_list(const uint8_t* fg_mask, int res, int32_t* fg_pix, int32_t* n_fg_dev, void* workspace,
                                 size_t workspace_bytes, void* stream) {
   DH_REQUIRE(fg_mask && fg_pix && n_fg_dev && workspace, "null pointer");
@@ -1525,6 +1518,20 @@ extern "C" int dh_masked_centroid(const float* depth, const int32_t* fg_pix, int
 // (a row without a view is all zero).  NULL when no edit has a view: that call is the call of the entries without the
 // arguments, launch for launch.  ok = false: a view row is malformed (checked as the transform rows are).  The buffer
 // outlives the call (the copy to the device is asynchronous), one per calling thread.
+// One similarity row, members 8 .. 14: a scale that is not positive and finite would collapse or mirror the object or spread NaN
+// over the z-buffer; a pivot is checked whether or not the row's flag selects it.  why: the refusal of a transform row.
+static bool row_ok(const double* row, const char** why) {
+  const double big = 3.4028234663852886e38;
+  *why = "transform row: the scale must be positive and finite";
+  for (int k = 8; k < 11; ++k)
+    if (!((float)row[k] > 0.0f && row[k] <= big)) return false;
+  *why = "transform row: the pivot must be finite";
+  for (int k = 11; k < 14; ++k)
+    if (!(row[k] >= -big && row[k] <= big)) return false;
+  *why = "transform row: the has-pivot flag must be 0 or 1";
+  return row[14] == 0.0 || row[14] == 1.0;
+}
+
 static const double* view_rows(const double* views, const uint8_t* has_view, int K, bool* ok) {
   thread_local std::vector<double> rows;
   *ok = true;
@@ -1538,38 +1545,93 @@ static const double* view_rows(const double* views, const uint8_t* has_view, int
     const double* row = views + (size_t)e * DH_SIMILARITY_ROW;
     double* w = rows.data() + (size_t)e * DH_SIMILARITY_ROW;
     const double big = 3.4028234663852886e38;
+    const char* why;
     for (int k = 0; k < 8; ++k) *ok = *ok && row[k] >= -big && row[k] <= big;          // axis, cos, sin, translation: finite
-    for (int k = 8; k < 11; ++k) *ok = *ok && (float)row[k] > 0.0f && row[k] <= big;
-    for (int k = 11; k < 14; ++k) *ok = *ok && row[k] >= -big && row[k] <= big;
-    *ok = *ok && (row[14] == 0.0 || row[14] == 1.0);
+    *ok = *ok && row_ok(row, &why);
     for (int k = 0; k < DH_SIMILARITY_ROW - 1; ++k) w[k] = row[k];
     w[DH_SIMILARITY_ROW - 1] = 1.0;
   }
   return rows.data();
 }
 
+// The one launch of k_points<FP, VS, SK>: footprints, view surfaces (never with footprints: refused before any launch, so six
+// instances exist) and bones; `args` is the kernel's argument list after the stream.
+template <class... A>
+static void launch_points(bool fp, bool vs, bool sk, dim3 grid, hipStream_t st, A... args) {
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, args...); };
+  if (vs) sk ? go(k_points<false, true, true>) : go(k_points<false, true, false>);
+  else if (fp) sk ? go(k_points<true, false, true>) : go(k_points<true, false, false>);
+  else sk ? go(k_points<false, false, true>) : go(k_points<false, false, false>);
+}
+
+// The triangle kernels of one z-buffer pass over K edits: thread tier, then wave tier (the list is built in pass 1).  VS: view
+// surfaces (bg_depth and the views given: the background sheet bids too), else footprints.
+template <bool VS>
+static void launch_triangles(int pass, int res, int K, int n_pts, int N, const InstTable& itab, const double* uvz, const float* depth,
+                             float ratio, const ReprojectWs& w, const float* bg_depth, const Xf* views, hipStream_t st) {
+  hipLaunchKernelGGL(k_fp_tri<VS>, dim3(cdiv(2 * (res - 1) * (res - 1), 256), K), dim3(256), 0, st, pass, res, n_pts, N, (const int*)w.inv,
+                     itab, uvz, depth, ratio, fp_tier(), w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, bg_depth, views);
+  hipLaunchKernelGGL(k_fp_wave<VS>, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_pts, (const int*)w.inv, itab, uvz, depth, ratio,
+                     w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, bg_depth, views);
+}
+
+// The harmonic in-fill of K images: the multi-workgroup solver, then the single-workgroup one; each takes the systems of its
+// size class (multi_min: the smallest the first takes; holes beyond one CU's LDS go to CGM_WGS workgroups per image, beyond that
+// kernel's register budget of 65 536 unknowns to the single-workgroup kernel).  Every polled word is zeroed per call.
+struct CgScratch {
+  double *vx, *vr, *vp, *vq;
+  int* pixmap;
+  int2 *nb_ud, *nb_lr;
+  size_t ud_stride, lr_stride;
+  CgSync* sync;
+};
+static int launch_infill(const CgScratch& s, int K, int res, float* x, const uint8_t* unknown, const int* unk, int* counts,
+                         int max_iter, const float* rhs, int multi_min, int border, hipStream_t st) {
+  DH_CHECK_HIP(hipMemsetAsync(s.sync, 0, (size_t)K * sizeof(CgSync), st));
+  hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, K), dim3(1024), 0, st, res, x, unknown, unk, counts, 4, 2, 3, s.vx, s.vr, s.vp,
+                     s.vq, max_iter, 1e-24, counts, rhs, multi_min, s.pixmap, s.nb_ud, s.ud_stride, s.nb_lr, s.lr_stride, s.sync,
+                     border);
+  hipLaunchKernelGGL(k_cg_fill, dim3(K), dim3(1024), 0, st, res, x, unknown, unk, counts, 4, 2, 3, s.vx, s.vr, s.vp, s.vq, max_iter,
+                     1e-24, counts, rhs, CGM_WGS * CGM_EPT * 1024, s.pixmap, s.nb_ud, s.ud_stride, s.nb_lr, s.lr_stride, border);
+  return DH_OK;
+}
+// the scratch of the solve in a re-projection: the z-buffer, owner map and key list are dead by then (last read by k_pixels /
+// k_write_corr)
+static CgScratch reproject_cg_scratch(const ReprojectWs& w, size_t R2, size_t P) {
+  return {w.vx, w.vr, w.vp, w.vq, w.owner, reinterpret_cast<int2*>(w.zbuf), reinterpret_cast<int2*>(w.key), R2, P, w.cgsync};
+}
+
 // n_objects masks: mask m owns fg_pix[obj_start[m] .. obj_start[m + 1]).  n_inst instances per edit: instance n draws the points
 // of mask inst_obj[n] with row e * n_inst + n of xforms_host (DH_SIMILARITY_ROW doubles: rotation, translation, scale, pivot);
 // the point list holds them one after the other (InstTable), n_pts foreground points in all.  Only k_centroid (masks) and
 // k_points, the triangles and the row writers (instances) know about either; from the z-buffer on the point list is one list.
-// The one code path of the re-projection: identity_carve = the call without copies (inst_obj[n] = n) with the workspace
-// layout it always had -- dh_reproject_footprint_edits, and through it the similarity, object and single-object entries.
+// The one code path of the re-projection with foreground points.  inst_obj = NULL with n_instances = 0: the call without copies
+// (inst_obj[n] = n) with the workspace layout it always had -- dh_reproject_footprint_edits' and the entries' before it.
 //
 // footprints = 1 (point mode's footprint splatting): the triangles between neighbouring points of one INSTANCE bid in the same
 // z-buffer, in both passes; vis, the kept set and the correspondences are then taken per TARGET pixel (corr_capacity rows per
 // edit: res * res; without footprints n_pts).  max_ratio: 0 = none, else the depth-ratio guard of the triangles (finite, > 1).
-static int reproject_instances(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg, int n_objects,
-                               const int32_t* obj_start, int n_inst, const int32_t* inst_obj, bool identity_carve, int res,
-                               const float* grid_x, const float* grid_y, float inv_fx, float inv_fy, double fx, double fy,
-                               int n_edits, const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                               uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy, int64_t* corr,
-                               uint8_t* corr_inst, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream,
-                               int footprints, float max_ratio, int corr_capacity, const float* donor_depth = nullptr,
-                               int n_host_objects = -1, const double* views = nullptr, const uint8_t* has_view = nullptr,
-                               const uint8_t* bg_valid = nullptr, int64_t* bg_corr = nullptr, int32_t* bg_counts = nullptr,
-                               int infill_border = 0, int view_surfaces = 0, float surface_max_ratio = 0.f, int n_bones = 1,
-                               const float* bone_w = nullptr) {
-  // bend edits: n_bones rows per instance and edit; the weights stay on the device and are never read here
+static int reproject_instances(const dh_reproject_args& a) {
+  const float *depth = a.depth, *bg_depth = a.bg_depth, *grid_x = a.grid_x, *grid_y = a.grid_y, *bounds = a.bounds;
+  const float *donor_depth = a.donor_depth, *bone_w = a.bone_w;
+  const int32_t *fg_pix = a.fg_pix, *obj_start = a.obj_start;
+  const double* xforms_host = a.xforms_host;
+  const uint8_t *has_view = a.has_view, *bg_valid = a.bg_valid;
+  float *zmap = a.zmap, *disparity = a.disparity;
+  uint8_t *raw_mask = a.raw_mask, *clean_mask = a.clean_mask, *vis = a.vis, *corr_inst = a.corr_inst;
+  int32_t *target_xy = a.target_xy, *counts = a.counts, *bg_counts = a.bg_counts;
+  int64_t *corr = a.corr, *bg_corr = a.bg_corr;
+  const int res = a.res, n_fg = a.n_fg, n_objects = a.n_objects, n_edits = a.n_edits, corr_capacity = a.corr_capacity;
+  const int footprints = a.footprints, infill_border = a.infill_border, view_surfaces = a.view_surfaces;
+  const float inv_fx = a.inv_fx, inv_fy = a.inv_fy, max_ratio = a.max_ratio, surface_max_ratio = a.surface_max_ratio;
+  const double fx = a.fx, fy = a.fy;
+  // the identity table: N = M, instance n draws mask n, on the carving the footprint entry always had
+  static const int32_t identity[MAX_OBJECTS] = {0, 1, 2, 3, 4, 5, 6, 7};
+  const bool identity_carve = !a.inst_obj && a.n_instances == 0;
+  const int32_t* inst_obj = identity_carve ? identity : a.inst_obj;
+  const int n_inst = identity_carve ? n_objects : a.n_instances;
+  // bend edits: n_bones rows per instance and edit (0 = 1: none); the weights stay on the device and are never read here
+  const int n_bones = a.n_bones == 0 ? 1 : a.n_bones;
   DH_REQUIRE(n_bones >= 1 && n_bones <= DH_MAX_BONES, "n_bones must lie in 1 .. 4");
   DH_REQUIRE(n_bones == 1 || bone_w, "n_bones > 1 without bone_w");
   DH_REQUIRE((reinterpret_cast<uintptr_t>(bone_w) & 15u) == 0, "bone_w must be 16-byte aligned");
@@ -1585,8 +1647,8 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
   DH_REQUIRE(n_inst >= 1 && n_inst <= MAX_OBJECTS, "1 to 8 instances");
   DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
-  // the donor: masks n_host_objects .. n_objects - 1 draw from donor_depth (-1 = the call of an entry without the argument)
-  if (n_host_objects == -1) n_host_objects = n_objects;
+  // the donor: masks n_host_objects .. n_objects - 1, the last n_donor_objects, draw from donor_depth
+  const int n_host_objects = n_objects - a.n_donor_objects;
   DH_REQUIRE(n_host_objects >= 0 && n_host_objects <= n_objects, "n_host_objects must lie in 0 .. n_objects");
   if (n_host_objects < n_objects) {
     DH_REQUIRE(donor_depth, "donor objects without a donor depth");
@@ -1611,19 +1673,14 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   DH_REQUIRE((long long)res * res + n_pts_ll <= 2147483647LL, "res * res + n_pts does not fit the int owner map");
   DH_REQUIRE((long long)corr_capacity >= (footprints ? (long long)res * res : n_pts_ll),
              "correspondence capacity too small (n_fg rows per edit without footprints, res * res with)");
-  // every row before any launch: a scale that is not positive and finite would collapse or mirror the object or spread NaN over
-  // the z-buffer; a pivot is checked whether or not the row's flag selects it
+  // every row before any launch
   for (size_t r = 0; r < (size_t)n_edits * n_inst * n_bones; ++r) {
-    const double* row = xforms_host + r * DH_SIMILARITY_ROW;
-    for (int k = 8; k < 11; ++k)
-      DH_REQUIRE((float)row[k] > 0.0f && row[k] <= 3.4028234663852886e38, "transform row: the scale must be positive and finite");
-    for (int k = 11; k < 14; ++k)
-      DH_REQUIRE(row[k] >= -3.4028234663852886e38 && row[k] <= 3.4028234663852886e38, "transform row: the pivot must be finite");
-    DH_REQUIRE(row[14] == 0.0 || row[14] == 1.0, "transform row: the has-pivot flag must be 0 or 1");
+    const char* why;
+    DH_REQUIRE(row_ok(xforms_host + r * DH_SIMILARITY_ROW, &why), why);
   }
   // camera moves: every view row before any launch; without a view in any edit the call is the call without the arguments
   bool views_ok = true;
-  const double* view_host = view_rows(views, has_view, n_edits, &views_ok);
+  const double* view_host = view_rows(a.views, has_view, n_edits, &views_ok);
   DH_REQUIRE(views_ok, "view row: malformed (finite members, scale positive, has-pivot flag 0 or 1)");
   if (view_host) {
     DH_REQUIRE(!footprints, "footprints with a view are not supported");
@@ -1633,17 +1690,16 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
   const bool surfaces = view_host != nullptr && view_surfaces != 0;
   DH_REQUIRE(!surfaces || (long long)corr_capacity >= (long long)res * res,
              "correspondence capacity too small (res * res rows per edit with view surfaces)");
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)a.stream;
   const int K = n_edits, M = n_objects, N = n_inst;
   const ObjTable tab = obj_table(M, obj_start, n_fg);
   int n_pts = 0;
   const InstTable itab = inst_table(N, inst_obj, obj_start, &n_pts);
   const int R2 = res * res, P = R2 + n_pts;
-  Arena a(workspace, workspace_bytes);
+  Arena arena(a.workspace, a.workspace_bytes);
   ReprojectWs w;
   DH_REQUIRE(!(identity_carve && n_bones > 1), "bones need the instance carving");
-  DH_REQUIRE(carve(a, res, n_pts, K, M, w, footprints != 0, identity_carve ? 0 : N, view_host != nullptr, surfaces, n_bones),
-             "workspace too small");
+  DH_REQUIRE(carve(arena, carve_spec(a, n_pts, view_host != nullptr), w), "workspace too small");
   const size_t corr_stride = (size_t)corr_capacity;
   if (view_host) DH_CHECK_HIP(hipMemcpyAsync(w.views, view_host, (size_t)K * sizeof(Xf), hipMemcpyHostToDevice, st));
 
@@ -1664,63 +1720,24 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
 
   hipLaunchKernelGGL(k_centroid, dim3(M), dim3(CEN_CHUNK), 0, st, depth, donor_depth, n_host_objects, fg_pix, tab, res, grid_x,
                      grid_y, inv_fx, inv_fy, w.cen);
-  // footprints: the triangle kernels run once per z-buffer pass, thread tier then wave tier (the list is built in pass 1)
-  const int n_tri = 2 * (res - 1) * (res - 1);
-  auto footprint_pass = [&](int pass) {
-    hipLaunchKernelGGL(k_fp_tri<false>, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_pts, N, w.inv, itab, w.uvz, depth,
-                       max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, (const float*)nullptr,
-                       (const Xf*)nullptr);
-    hipLaunchKernelGGL(k_fp_wave<false>, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_pts, w.inv, itab, w.uvz, depth,
-                       max_ratio, w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, (const float*)nullptr, (const Xf*)nullptr);
+  // footprints: the triangles between an instance's points; view surfaces: those and the background sheet, in the edits with a
+  // view (the vertex pointer is that of the first foreground point: see fp_setup).  Never both.
+  auto triangle_pass = [&](int pass) {
+    if (footprints) launch_triangles<false>(pass, res, K, n_pts, N, itab, w.uvz, depth, max_ratio, w, nullptr, nullptr, st);
+    if (surfaces) launch_triangles<true>(pass, res, K, n_pts, N, itab, w.uvz + (size_t)R2 * 3, depth, surface_max_ratio, w, bg_depth, w.views, st);
   };
-  // view surfaces: the same two tiers over the instances' triangles and the background sheet, in the edits with a view (the
-  // vertex pointer is that of the first foreground point: see fp_setup)
-  auto surface_pass = [&](int pass) {
-    const double* fg_uvz = w.uvz + (size_t)R2 * 3;
-    hipLaunchKernelGGL(k_fp_tri<true>, dim3(cdiv(n_tri, 256), K), dim3(256), 0, st, pass, res, n_pts, N, w.inv, itab, fg_uvz, depth,
-                       surface_max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, bg_depth,
-                       (const Xf*)w.views);
-    hipLaunchKernelGGL(k_fp_wave<true>, dim3(FP_WAVE_BLOCKS, K), dim3(256), 0, st, pass, res, n_pts, w.inv, itab, fg_uvz, depth,
-                       surface_max_ratio, w.zbuf, w.owner, w.big_list, w.big_stride, w.big_count, bg_depth, (const Xf*)w.views);
-  };
-  if (surfaces) {
+  if (surfaces || footprints) {
     DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
     DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
     hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
-    if (bone_w)
-      hipLaunchKernelGGL((k_points<false, true, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
-                         bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
-                         w.key, w.uvz, (const Xf*)w.views, bone_w, n_bones);
-    else
-      hipLaunchKernelGGL((k_points<false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
-                         bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
-                         w.key, w.uvz, (const Xf*)w.views, (const float*)nullptr, 1);
-    surface_pass(1);
-  } else if (footprints) {
-    DH_CHECK_HIP(hipMemsetAsync(w.inv, 0xff, (size_t)R2 * sizeof(int), st));
-    DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, (size_t)K * sizeof(int), st));
-    hipLaunchKernelGGL(k_fp_inverse, dim3(cdiv(n_fg, 256)), dim3(256), 0, st, fg_pix, n_fg, w.inv);
-    if (bone_w)
-      hipLaunchKernelGGL((k_points<true, false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
-                         bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
-                         w.key, w.uvz, (const Xf*)nullptr, bone_w, n_bones);
-    else
-      hipLaunchKernelGGL(k_points<true>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth,
-                         fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key,
-                         w.uvz, (const Xf*)nullptr, (const float*)nullptr, 1);
-    footprint_pass(1);
-  } else if (bone_w) {
-    hipLaunchKernelGGL((k_points<false, false, true>), dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects,
-                       bg_depth, fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix,
-                       w.key, (double*)nullptr, (const Xf*)w.views, bone_w, n_bones);
-  } else {
-    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(P, 256), K), dim3(256), 0, st, depth, donor_depth, n_host_objects, bg_depth, fg_pix,
-                       n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key,
-                       (double*)nullptr, (const Xf*)w.views, (const float*)nullptr, 1);
   }
+  // (the carving leaves uvz null without triangles and views null without a view, footprints included: they never meet a view)
+  launch_points(footprints != 0, surfaces, bone_w != nullptr, dim3(cdiv(P, 256), K), st, depth, donor_depth, n_host_objects, bg_depth,
+                fg_pix, n_pts, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, N, w.zbuf, w.pix, w.key, w.uvz,
+                w.views, bone_w, bone_w ? n_bones : 1);
+  triangle_pass(1);
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(P, 256), K), dim3(256), 0, st, P, R2, w.zbuf, w.pix, w.key, w.owner);
-  if (footprints) footprint_pass(2);
-  if (surfaces) surface_pass(2);
+  triangle_pass(2);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), K), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, raw_mask,
                      disparity, w.minmax, (const Xf*)w.views);
   hipLaunchKernelGGL(k_fg_vis, dim3(cdiv(n_pts, 256), K), dim3(256), 0, st, n_pts, R2, P, res, w.pix, w.owner, vis,
@@ -1790,327 +1807,52 @@ static int reproject_instances(const float* depth, const float* bg_depth, const 
 #else
   constexpr bool cg_lds = true;
 #endif
-  // scratch of the solve: the z-buffer, owner map and key list are dead by now (last read by k_pixels / k_write_corr)
-  // holes beyond one CU's LDS: CGM_WGS workgroups per edit (every polled word zeroed per call); beyond that kernel's
-  // register budget (65 536 unknowns) the single-workgroup kernel
-  DH_CHECK_HIP(hipMemsetAsync(w.cgsync, 0, (size_t)K * sizeof(CgSync), st));
-  hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, K), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
-                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, cg_lds ? CG_SLOTS * 1024 : 0, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P, w.cgsync,
-                     infill_border);
-  hipLaunchKernelGGL(k_cg_fill, dim3(K), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
-                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CGM_WGS * CGM_EPT * 1024, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)P, infill_border);
+  const int rc = launch_infill(reproject_cg_scratch(w, R2, P), K, res, disparity, w.inpaint, w.unk, counts, cg_cap(20000), nullptr,
+                               cg_lds ? CG_SLOTS * 1024 : 0, infill_border, st);
+  if (rc != DH_OK) return rc;
   DH_LAUNCH_CHECK();
   return DH_OK;
-}
-
-extern "C" int dh_reproject_instances_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
-                                                      int footprints, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
-  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
-  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, n_pts, n_edits, n_objects, w, footprints != 0, n_instances);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-// Donor objects: masks n_host_objects .. n_objects - 1 of fg_pix / obj_start are masks of ANOTHER image of the same resolution
-// and intrinsics, and their points are the unprojection of donor_depth.  Only k_centroid and k_points read a depth, so only they
-// know; a correspondence row of a donor instance carries its source pixel in the donor image, and corr_inst tells which rows
-// those are.  The workspace is the instance entry's.
-extern "C" int dh_reproject_donor_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
-                                                  int footprints, size_t* bytes) {
-  return dh_reproject_instances_workspace_bytes(res, n_pts, n_edits, n_objects, n_instances, footprints, bytes);
-}
-
-// Camera moves: the donor entry with one view row per edit (views, has_view: host), the image of the pixels that show the
-// background (bg_valid) and the background rows (bg_corr [K][res * res][4], bg_counts [K]).  The one code path: without a
-// view in any edit nothing of the three is read or written and the workspace is the donor entry's.
-extern "C" int dh_reproject_camera_workspace_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
-                                                   int footprints, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
-  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
-  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, n_pts, n_edits, n_objects, w, footprints != 0, n_instances, true);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-// View surfaces ("View surfaces"): the border entry with the setting (0 / 1, per call) and the depth-ratio guard of
-// its triangles (0 = none).  In an edit with a view the instances' triangles AND the two triangles of every source quad of the
-// background bid in the z-buffer of the points; the rows of such an edit are taken per target pixel (corr_capacity >= res * res).
-// An edit without a view is the point path; a call in which no edit has a view is the border entry's call, launch for launch.
-extern "C" int dh_reproject_surface_ws_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances,
-                                                    int view_surfaces, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
-  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
-  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, n_pts, n_edits, n_objects, w, false, n_instances, true, view_surfaces != 0);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-// Bend edits ("Bend edits"): the surface entry with n_bones transform rows per instance and edit (xforms_host is
-// [n_edits][n_instances][n_bones][DH_SIMILARITY_ROW]) and the weight of every point and bone on the device (bone_w
-// [n_edits][n_pts][n_bones], by point-list position).  A point goes to the weighted sum of where its bones put it
-// (k_points<.., SK>); everything after the point transform sees points as before.  n_bones = 1 with bone_w = NULL is the
-// surface entry's call, launch for launch; the workspace grows only by the device copy of the extra rows.
-extern "C" int dh_reproject_bend_ws_bytes(int res, int n_pts, int n_edits, int n_objects, int n_instances, int view_surfaces,
-                                          int footprints, int n_bones, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && n_pts >= 0 && n_edits >= 1 && n_objects >= 1 && n_objects <= MAX_OBJECTS && bytes, "bad arguments");
-  DH_REQUIRE(n_instances >= 1 && n_instances <= MAX_OBJECTS, "1 to 8 instances");
-  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
-  DH_REQUIRE(footprints == 0 || footprints == 1, "footprints must be 0 or 1");
-  DH_REQUIRE(!(footprints && view_surfaces), "view_surfaces with footprints are not supported");
-  DH_REQUIRE(n_bones >= 1 && n_bones <= DH_MAX_BONES, "n_bones must lie in 1 .. 4");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, n_pts, n_edits, n_objects, w, footprints != 0, n_instances, true, view_surfaces != 0, n_bones);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-extern "C" int dh_reproject_bend_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                       int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                       const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                       const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                       uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                       int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                       void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
-                                       const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
-                                       int n_host_objects, const double* views, const uint8_t* has_view,
-                                       const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border,
-                                       int view_surfaces, float surface_max_ratio, int n_bones,
-                                       const float* bone_w) {
-  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
-  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
-  DH_REQUIRE(n_edits >= 1, "bad sizes");
-  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
-                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
-                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
-                             corr_capacity, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
-                             infill_border, view_surfaces, surface_max_ratio, n_bones, bone_w);
-}
-
-// the call without bones
-extern "C" int dh_reproject_surface_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                           int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                           const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                           const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                           uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                           int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                           void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
-                                           const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
-                                           int n_host_objects, const double* views, const uint8_t* has_view,
-                                           const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border,
-                                           int view_surfaces, float surface_max_ratio) {
-  return dh_reproject_bend_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy,
-                                 n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
-                                 workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances, inst_obj,
-                                 corr_inst, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
-                                 infill_border, view_surfaces, surface_max_ratio, 1, nullptr);
-}
-
-// The in-fill border: the camera entry with the border rule of the harmonic in-fill (0 = zero, 1 = reflect; see CG_NB_FRAME).
-// Per call, not per edit; the workspace is the camera entry's.  The call without view surfaces.
-extern "C" int dh_reproject_border_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                          int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                          const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                          const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                          uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                          int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                          void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
-                                          const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
-                                          int n_host_objects, const double* views, const uint8_t* has_view,
-                                          const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts, int infill_border) {
-  return dh_reproject_surface_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy,
-                                    n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
-                                    workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances, inst_obj,
-                                    corr_inst, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts,
-                                    infill_border, 0, 0.f);
-}
-
-// the call with the zero border
-extern "C" int dh_reproject_camera_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                          int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                          const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                          const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                          uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                          int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                          void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
-                                          const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
-                                          int n_host_objects, const double* views, const uint8_t* has_view,
-                                          const uint8_t* bg_valid, int64_t* bg_corr, int32_t* bg_counts) {
-  return dh_reproject_border_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy,
-                                   n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
-                                   workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances, inst_obj,
-                                   corr_inst, donor_depth, n_host_objects, views, has_view, bg_valid, bg_corr, bg_counts, 0);
-}
-
-// the call without a view
-extern "C" int dh_reproject_donor_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                         int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                         const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                         const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                         uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                         int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                         void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
-                                         const int32_t* inst_obj, uint8_t* corr_inst, const float* donor_depth,
-                                         int n_host_objects) {
-  DH_REQUIRE(n_host_objects >= 0, "n_host_objects must lie in 0 .. n_objects");
-  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_instances, inst_obj, false, res, grid_x, grid_y,
-                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
-                             target_xy, corr, corr_inst, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
-                             corr_capacity, donor_depth, n_host_objects);
-}
-
-// the call without a donor: donor_depth = NULL, every mask is the host's
-extern "C" int dh_reproject_instance_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                            int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                            const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                            const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                            uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                            int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                            void* stream, int footprints, float max_ratio, int corr_capacity, int n_instances,
-                                            const int32_t* inst_obj, uint8_t* corr_inst) {
-  return dh_reproject_donor_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx,
-                                  fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr,
-                                  counts, workspace, workspace_bytes, stream, footprints, max_ratio, corr_capacity, n_instances,
-                                  inst_obj, corr_inst, nullptr, n_objects);
-}
-
-// the identity table: N = M, instance n draws mask n, no instance column
-extern "C" int dh_reproject_footprint_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                             const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                             uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                             int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                             void* stream, int footprints, float max_ratio, int corr_capacity) {
-  static const int32_t identity[MAX_OBJECTS] = {0, 1, 2, 3, 4, 5, 6, 7};
-  return reproject_instances(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, n_objects, identity, true, res, grid_x, grid_y,
-                             inv_fx, inv_fy, fx, fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis,
-                             target_xy, corr, nullptr, counts, workspace, workspace_bytes, stream, footprints, max_ratio,
-                             corr_capacity);
-}
-
-extern "C" int dh_reproject_similarity_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                             int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                             const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                             const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                             uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                             int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                             void* stream) {
-  return dh_reproject_footprint_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx,
-                                      fy, n_edits, xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr,
-                                      counts, workspace, workspace_bytes, stream, 0, 0.f, n_fg);
-}
-
-// the rows of the rigid entries (8 doubles) widened to similarity rows: scale 1, no pivot.  The buffer outlives the call (the
-// copy to the device is asynchronous), one per calling thread.
-static const double* rigid_rows(const double* rows8, size_t n) {
-  thread_local std::vector<double> wide;
-  wide.assign(n * DH_SIMILARITY_ROW, 0.0);
-  for (size_t r = 0; r < n; ++r) {
-    double* w = wide.data() + r * DH_SIMILARITY_ROW;
-    for (int k = 0; k < 8; ++k) w[k] = rows8[r * 8 + k];
-    w[8] = w[9] = w[10] = 1.0;
-  }
-  return wide.data();
-}
-
-extern "C" int dh_reproject_object_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg,
-                                         int n_objects, const int32_t* obj_start, int res, const float* grid_x,
-                                         const float* grid_y, float inv_fx, float inv_fy, double fx, double fy, int n_edits,
-                                         const double* xforms_host, const float* bounds, float* zmap, uint8_t* raw_mask,
-                                         uint8_t* clean_mask, float* disparity, uint8_t* vis, int32_t* target_xy,
-                                         int64_t* corr, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                         void* stream) {
-  DH_REQUIRE(xforms_host, "null input");
-  DH_REQUIRE(n_edits >= 1, "bad sizes");
-  DH_REQUIRE(n_objects >= 1 && n_objects <= MAX_OBJECTS, "1 to 8 objects");
-  return dh_reproject_similarity_edits(depth, bg_depth, fg_pix, n_fg, n_objects, obj_start, res, grid_x, grid_y, inv_fx, inv_fy, fx,
-                                       fy, n_edits, rigid_rows(xforms_host, (size_t)n_edits * n_objects), bounds, zmap, raw_mask,
-                                       clean_mask, disparity, vis, target_xy, corr, counts, workspace, workspace_bytes, stream);
-}
-
-extern "C" int dh_reproject_edits(const float* depth, const float* bg_depth, const int32_t* fg_pix, int n_fg, int res,
-                                  const float* grid_x, const float* grid_y, float inv_fx, float inv_fy, double fx,
-                                  double fy, int n_edits, const double* xforms_host, const float* bounds, float* zmap,
-                                  uint8_t* raw_mask, uint8_t* clean_mask, float* disparity, uint8_t* vis,
-                                  int32_t* target_xy, int64_t* corr, int32_t* counts, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-  const int32_t one[2] = {0, n_fg};
-  return dh_reproject_object_edits(depth, bg_depth, fg_pix, n_fg, 1, one, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, n_edits,
-                                   xforms_host, bounds, zmap, raw_mask, clean_mask, disparity, vis, target_xy, corr, counts,
-                                   workspace, workspace_bytes, stream);
 }
 
 // Object removal, the pure case (no foreground point left): the background part of the point list through the kernels of
 // reproject_instances -- k_points (n_pts = 0: every thread takes the background branch), k_resolve, k_pixels, k_normalize, the
 // in-fill solvers -- on the carving of a one-edit call without foreground.  Nothing is foreground, so raw and cleaned masks are
 // zero and stay in the workspace; the in-fill set is the pixels no point owns (k_unowned in the raw mask's place).
-extern "C" int dh_reproject_background_workspace_bytes(int res, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && res <= 32768 && bytes, "bad arguments");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, 0, 1, 1, w);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-// Camera moves, the pure case: the background entry with one view row (view NULL = no view: dh_reproject_background, launch for
-// launch).  The view lives in the one transform row the carving holds and the background never reads; with it the points go
-// through k_points' view path (no clamp: points out of frame bid for nothing), the pixels no point reached stay out of the
-// min / max, and every owned background point with bg_valid != 0 yields a row (bg_corr [res * res][4], bg_counts [1]).
 //
-// dh_reproject_border_background: the same with the border rule of the harmonic in-fill (0 = zero, 1 = reflect); the workspace
-// is dh_reproject_background_workspace_bytes' either way.
+// Camera moves, the pure case: with a view row (has_view[0]; none = the pure removal, launch for launch) the view lives in the
+// one transform row the carving holds and the background never reads; the points go through k_points' view path (no clamp:
+// points out of frame bid for nothing), the pixels no point reached stay out of the min / max, and every owned background point
+// with bg_valid != 0 yields a row (bg_corr [res * res][4], bg_counts [1]).  infill_border: the border rule of the harmonic
+// in-fill.  view_surfaces with a view: the two triangles of every source quad bid beside the points (surface_max_ratio: their
+// depth-ratio guard), and the rows are one per target pixel whose owner has bg_valid, row-major.
 //
-// dh_reproject_surface_background: the same with view surfaces (0 / 1) and the depth-ratio guard of the triangles (0 = none): with
-// a view the two triangles of every source quad bid beside the points, and the rows are one per target pixel whose owner has
-// bg_valid, row-major.  Without a view, or with 0, it is the border entry's call and workspace.
-extern "C" int dh_reproject_surface_background_ws_bytes(int res, int view_surfaces, size_t* bytes) {
-  DH_REQUIRE(res >= 2 && res <= 32768 && bytes, "bad arguments");
-  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
-  Arena a(nullptr, (size_t)-1);
-  ReprojectWs w;
-  carve(a, res, 0, 1, 1, w, false, 0, false, view_surfaces != 0);
-  *bytes = a.off + 256;
-  return DH_OK;
-}
-
-extern "C" int dh_reproject_surface_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
-                                                float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
-                                                float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                                void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
-                                                int32_t* bg_counts, int infill_border, int view_surfaces, float surface_max_ratio) {
-  DH_REQUIRE(infill_border == 0 || infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
-  DH_REQUIRE(view_surfaces == 0 || view_surfaces == 1, "view_surfaces must be 0 or 1");
-  DH_REQUIRE(surface_max_ratio == 0.f || (surface_max_ratio > 1.f && surface_max_ratio <= 3.4028234663852886e38f),
+// A launch sequence of its own: no morphology, k_unowned.  Its refusals carry the name of the entry it was written as.
+#define BG_REQUIRE(cond, msg) DH_REQUIRE_AS("dh_reproject_surface_background", cond, msg)
+static int reproject_background(const dh_reproject_args& a) {
+  const float *bg_depth = a.bg_depth, *grid_x = a.grid_x, *grid_y = a.grid_y;
+  float *zmap = a.zmap, *disparity = a.disparity;
+  int32_t *counts = a.counts, *bg_counts = a.bg_counts;
+  const int res = a.res;
+  BG_REQUIRE(a.infill_border == 0 || a.infill_border == 1, "infill_border must be 0 (zero) or 1 (reflect)");
+  BG_REQUIRE(a.view_surfaces == 0 || a.view_surfaces == 1, "view_surfaces must be 0 or 1");
+  BG_REQUIRE(a.surface_max_ratio == 0.f || (a.surface_max_ratio > 1.f && a.surface_max_ratio <= 3.4028234663852886e38f),
              "surface_max_ratio must be 0 (none) or finite and > 1");
-  DH_REQUIRE(surface_max_ratio == 0.f || view_surfaces, "surface_max_ratio without view_surfaces");
-  DH_REQUIRE(bg_depth && grid_x && grid_y, "null input");
-  DH_REQUIRE(zmap && disparity && counts && workspace, "null output");
-  DH_REQUIRE(res >= 2 && res <= 32768, "bad sizes");
-  const uint8_t one = 1;
+  BG_REQUIRE(a.surface_max_ratio == 0.f || a.view_surfaces, "surface_max_ratio without view_surfaces");
+  BG_REQUIRE(bg_depth && grid_x && grid_y, "null input");
+  BG_REQUIRE(zmap && disparity && counts && a.workspace, "null output");
+  BG_REQUIRE(res >= 2 && res <= 32768, "bad sizes");
+  BG_REQUIRE(a.n_edits == 1, "the call without a foreground point takes one edit");
   bool view_ok = true;
-  const double* view_host = view_rows(view, &one, 1, &view_ok);
-  DH_REQUIRE(view_ok, "view row: malformed (finite members, scale positive, has-pivot flag 0 or 1)");
-  if (view_host) DH_REQUIRE(bg_valid && bg_corr && bg_counts, "a view needs bg_valid, bg_corr and bg_counts");
-  hipStream_t st = (hipStream_t)stream;
+  const double* view_host = view_rows(a.views, a.has_view, 1, &view_ok);
+  BG_REQUIRE(view_ok, "view row: malformed (finite members, scale positive, has-pivot flag 0 or 1)");
+  if (view_host) BG_REQUIRE(a.bg_valid && a.bg_corr && bg_counts, "a view needs bg_valid, bg_corr and bg_counts");
+  hipStream_t st = (hipStream_t)a.stream;
   const int R2 = res * res;
-  Arena a(workspace, workspace_bytes);
+  Arena arena(a.workspace, a.workspace_bytes);
   ReprojectWs w;
-  const bool surfaces = view_host != nullptr && view_surfaces != 0;
-  DH_REQUIRE(carve(a, res, 0, 1, 1, w, false, 0, false, surfaces), "workspace too small");
+  const CarveSpec spec = carve_spec(a, 0, view_host != nullptr);
+  const bool surfaces = spec.surfaces;
+  BG_REQUIRE(carve(arena, spec, w), "workspace too small");
   const Xf* dview = nullptr;
   if (view_host) {
     DH_CHECK_HIP(hipMemcpyAsync(w.xf, view_host, sizeof(Xf), hipMemcpyHostToDevice, st));
@@ -2125,85 +1867,85 @@ extern "C" int dh_reproject_surface_background(const float* bg_depth, int res, c
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0, 2 * sizeof(unsigned int), st));
   DH_CHECK_HIP(hipMemsetAsync(w.minmax, 0xff, sizeof(unsigned int), st));
   DH_CHECK_HIP(hipMemsetAsync(w.tmp_b, 0, (size_t)R2, st));
-  const int n_tri = 2 * (res - 1) * (res - 1);
   auto surface_pass = [&](int pass) {          // the background sheet alone: no instance, the vertex pointer past the R2 points
-    hipLaunchKernelGGL(k_fp_tri<true>, dim3(cdiv(n_tri, 256), 1), dim3(256), 0, st, pass, res, 0, 0, (const int*)nullptr, itab,
-                       (const double*)(w.uvz + (size_t)R2 * 3), bg_depth, surface_max_ratio, fp_tier(), w.zbuf, w.owner, w.big_list,
-                       w.big_stride, w.big_count, bg_depth, dview);
-    hipLaunchKernelGGL(k_fp_wave<true>, dim3(FP_WAVE_BLOCKS, 1), dim3(256), 0, st, pass, res, 0, (const int*)nullptr, itab,
-                       (const double*)(w.uvz + (size_t)R2 * 3), bg_depth, surface_max_ratio, w.zbuf, w.owner, w.big_list, w.big_stride,
-                       w.big_count, bg_depth, dview);
+    launch_triangles<true>(pass, res, 1, 0, 0, itab, w.uvz + (size_t)R2 * 3, bg_depth, a.surface_max_ratio, w, bg_depth, dview, st);
   };
-  if (surfaces) {
-    DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, sizeof(int), st));
-    hipLaunchKernelGGL((k_points<false, true>), dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth,
-                       (const int*)nullptr, 0, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key,
-                       w.uvz, dview, (const float*)nullptr, 1);
-    surface_pass(1);
-  } else {
-    hipLaunchKernelGGL(k_points<false>, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, bg_depth, bg_depth, 0, bg_depth, (const int*)nullptr, 0, res,
-                       grid_x, grid_y, inv_fx, inv_fy, fx, fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, (double*)nullptr, dview,
-                       (const float*)nullptr, 1);
-  }
+  if (surfaces) DH_CHECK_HIP(hipMemsetAsync(w.big_count, 0, sizeof(int), st));
+  launch_points(false, surfaces, false, dim3(cdiv(R2, 256), 1), st, bg_depth, bg_depth, 0, bg_depth, nullptr, 0, res, grid_x, grid_y,
+                a.inv_fx, a.inv_fy, a.fx, a.fy, w.xf, w.cen, itab, 0, w.zbuf, w.pix, w.key, w.uvz, dview, nullptr, 1);
+  if (surfaces) surface_pass(1);
   hipLaunchKernelGGL(k_resolve, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.zbuf, w.pix, w.key, w.owner);
   if (surfaces) surface_pass(2);
   hipLaunchKernelGGL(k_pixels, dim3(cdiv(R2, 256 * PIX_PER_THREAD), 1), dim3(256), 0, st, R2, w.zbuf, w.owner, zmap, w.tmp_a,
                      disparity, w.minmax, dview);
   if (surfaces) {
-    hipLaunchKernelGGL(k_vs_flags, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, 0, w.owner, w.tmp_b, (size_t)0, bg_valid, dview,
+    hipLaunchKernelGGL(k_vs_flags, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, 0, w.owner, w.tmp_b, (size_t)0, a.bg_valid, dview,
                        (uint8_t*)nullptr, (uint8_t*)nullptr, w.inpaint);
     compact(w.inpaint, R2, 1, R2, w.unk, R2, bg_counts, 1, w.block_counts, st);
     hipLaunchKernelGGL(k_vs_write_bg, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, res, w.owner, w.unk, bg_counts,
-                       (long long*)bg_corr);
+                       (long long*)a.bg_corr);
   } else if (dview) {
-    hipLaunchKernelGGL(k_bg_row_flags, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.pix, w.owner, w.tmp_b, (size_t)0, bg_valid,
+    hipLaunchKernelGGL(k_bg_row_flags, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, w.pix, w.owner, w.tmp_b, (size_t)0, a.bg_valid,
                        dview, w.inpaint);
     compact(w.inpaint, R2, 1, R2, w.unk, R2, bg_counts, 1, w.block_counts, st);
     hipLaunchKernelGGL(k_write_bg_corr, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, R2, res, w.pix, w.unk, bg_counts,
-                       (long long*)bg_corr);
+                       (long long*)a.bg_corr);
   }
   hipLaunchKernelGGL(k_unowned, dim3(cdiv(R2, 256)), dim3(256), 0, st, R2, w.zbuf, w.tmp_a);
-  hipLaunchKernelGGL(k_normalize, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, disparity, w.minmax, bounds, w.tmp_a, w.tmp_b,
+  hipLaunchKernelGGL(k_normalize, dim3(cdiv(R2, 256), 1), dim3(256), 0, st, R2, disparity, w.minmax, a.bounds, w.tmp_a, w.tmp_b,
                      w.inpaint, w.zbuf, dview);
   compact(w.inpaint, R2, 1, R2, w.unk, R2, counts + 2, 4, w.block_counts, st);
-  DH_CHECK_HIP(hipMemsetAsync(w.cgsync, 0, sizeof(CgSync), st));
-  hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, 1), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
-                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CG_SLOTS * 1024, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2, w.cgsync,
-                     infill_border);
-  hipLaunchKernelGGL(k_cg_fill, dim3(1), dim3(1024), 0, st, res, disparity, w.inpaint, w.unk, counts, 4, 2, 3, w.vx,
-                     w.vr, w.vp, w.vq, cg_cap(20000), 1e-24, counts, (const float*)nullptr, CGM_WGS * CGM_EPT * 1024, w.owner,
-                     reinterpret_cast<int2*>(w.zbuf), (size_t)R2, reinterpret_cast<int2*>(w.key), (size_t)R2, infill_border);
+  const int rc = launch_infill(reproject_cg_scratch(w, R2, R2), 1, res, disparity, w.inpaint, w.unk, counts, cg_cap(20000), nullptr,
+                               CG_SLOTS * 1024, a.infill_border, st);
+  if (rc != DH_OK) return rc;
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
 
-// the call with the zero border
-extern "C" int dh_reproject_camera_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
-                                               float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
-                                               float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                               void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
-                                               int32_t* bg_counts) {
-  return dh_reproject_border_background(bg_depth, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, bounds, zmap, disparity, counts,
-                                        workspace, workspace_bytes, stream, view, bg_valid, bg_corr, bg_counts, 0);
+#undef BG_REQUIRE
+
+// what every workspace query answers: the end of a carving in a null-based arena, and the slack behind it
+template <class F>
+static size_t carved_bytes(F carve_into) {
+  Arena a(nullptr, (size_t)-1);
+  carve_into(a);
+  return a.off + 256;
 }
 
-// the call without view surfaces
-extern "C" int dh_reproject_border_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y,
-                                               float inv_fx, float inv_fy, double fx, double fy, const float* bounds, float* zmap,
-                                               float* disparity, int32_t* counts, void* workspace, size_t workspace_bytes,
-                                               void* stream, const double* view, const uint8_t* bg_valid, int64_t* bg_corr,
-                                               int32_t* bg_counts, int infill_border) {
-  return dh_reproject_surface_background(bg_depth, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, bounds, zmap, disparity, counts,
-                                         workspace, workspace_bytes, stream, view, bg_valid, bg_corr, bg_counts, infill_border, 0, 0.f);
+// The two entries of the re-projection (include/diffhandles_hip.h, dh_reproject_args).  Every positional dh_reproject_* entry
+// and query is a record filled in csrc/reproject_compat.cpp.
+extern "C" int dh_reproject(const dh_reproject_args* a) {
+  DH_REQUIRE(a && a->struct_bytes == sizeof(dh_reproject_args), "struct_bytes is not sizeof(dh_reproject_args)");
+  return a->n_fg == 0 ? reproject_background(*a) : reproject_instances(*a);
 }
 
-// the call without a view
-extern "C" int dh_reproject_background(const float* bg_depth, int res, const float* grid_x, const float* grid_y, float inv_fx,
-                                       float inv_fy, double fx, double fy, const float* bounds, float* zmap, float* disparity,
-                                       int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-  return dh_reproject_camera_background(bg_depth, res, grid_x, grid_y, inv_fx, inv_fy, fx, fy, bounds, zmap, disparity, counts,
-                                        workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr);
+extern "C" int dh_reproject_workspace(const dh_reproject_args* a, size_t* bytes) {
+  DH_REQUIRE(a && a->struct_bytes == sizeof(dh_reproject_args), "struct_bytes is not sizeof(dh_reproject_args)");
+  DH_REQUIRE(a->res >= 2 && a->n_fg >= 0 && a->n_edits >= 1 && a->n_objects >= (a->n_fg > 0 ? 1 : 0) && a->n_objects <= MAX_OBJECTS && bytes,
+             "bad arguments");
+  const bool table = a->inst_obj || a->n_instances;
+  DH_REQUIRE(!table || (a->n_instances >= 1 && a->n_instances <= MAX_OBJECTS), "1 to 8 instances");
+  DH_REQUIRE(a->view_surfaces == 0 || a->view_surfaces == 1, "view_surfaces must be 0 or 1");
+  DH_REQUIRE(a->footprints == 0 || a->footprints == 1, "footprints must be 0 or 1");
+  DH_REQUIRE(!(a->footprints && a->view_surfaces), "view_surfaces with footprints are not supported");
+  DH_REQUIRE(a->n_bones >= 0 && a->n_bones <= DH_MAX_BONES, "n_bones must lie in 1 .. 4");
+  long long n_pts = a->n_fg;
+  if (a->inst_obj && a->obj_start) {          // the points of the instances, as the call counts them
+    n_pts = 0;
+    for (int n = 0; n < a->n_instances; ++n) {
+      DH_REQUIRE(a->inst_obj[n] >= 0 && a->inst_obj[n] < a->n_objects, "inst_obj: an instance names a mask outside 0 .. n_objects - 1");
+      n_pts += a->obj_start[a->inst_obj[n] + 1] - a->obj_start[a->inst_obj[n]];
+    }
+    DH_REQUIRE(n_pts >= 0 && n_pts <= 2147483647LL, "bad arguments");
+  }
+  bool any_view = false;
+  for (int e = 0; a->has_view && e < a->n_edits; ++e) any_view = any_view || a->has_view[e] != 0;
+  const CarveSpec spec = carve_spec(*a, (int)n_pts, any_view);
+  *bytes = carved_bytes([&](Arena& arena) {
+    ReprojectWs w;
+    carve(arena, spec, w);
+  });
+  return DH_OK;
 }
 
 namespace dh {
@@ -2233,10 +1975,10 @@ static bool carve_blend(Arena& a, int res, BlendWs& w) {
 
 extern "C" int dh_laplacian_blend_workspace_bytes(int res, size_t* bytes) {
   DH_REQUIRE(res >= 2 && bytes, "bad arguments");
-  Arena a(nullptr, (size_t)-1);
-  BlendWs w;
-  carve_blend(a, res, w);
-  *bytes = a.off + 256;
+  *bytes = carved_bytes([&](Arena& a) {
+    BlendWs w;
+    carve_blend(a, res, w);
+  });
   return DH_OK;
 }
 
@@ -2255,30 +1997,19 @@ extern "C" int dh_laplacian_blend_border(const float* depth, const float* bg_dep
   Arena a(workspace, workspace_bytes);
   BlendWs w;
   DH_REQUIRE(carve_blend(a, res, w), "workspace too small");
-  double *vx = w.vx, *vr = w.vr, *vp = w.vp, *vq = w.vq;
-  uint8_t *m0 = w.m0, *m1 = w.m1;
-  float* lap = w.lap;
-  int *unk = w.unk, *pixmap = w.pixmap;
-  int2 *nb_ud = w.nb_ud, *nb_lr = w.nb_lr;
-  int* bc = w.bc;
-  CgSync* cgs = w.cgs;
-  DH_CHECK_HIP(hipMemcpyAsync(m0, fg_mask, R2, hipMemcpyDeviceToDevice, st));
-  uint8_t *src = m0, *dst = m1;
+  DH_CHECK_HIP(hipMemcpyAsync(w.m0, fg_mask, R2, hipMemcpyDeviceToDevice, st));
+  uint8_t *src = w.m0, *dst = w.m1;
   for (int i = 0; i < dilate_iters; ++i) {
     hipLaunchKernelGGL(k_dilate_cross, dim3(cdiv(R2, 256)), dim3(256), 0, st, src, dst, res);
     uint8_t* t = src; src = dst; dst = t;
   }
-  hipLaunchKernelGGL(k_laplacian, dim3(cdiv(R2, 256)), dim3(256), 0, st, bg_depth, lap, res, infill_border);
+  hipLaunchKernelGGL(k_laplacian, dim3(cdiv(R2, 256)), dim3(256), 0, st, bg_depth, w.lap, res, infill_border);
   DH_CHECK_HIP(hipMemcpyAsync(out, depth, (size_t)R2 * 4, hipMemcpyDeviceToDevice, st));
   DH_CHECK_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int), st));
-  compact(src, R2, 1, 0, unk, 0, counts + 2, 1, bc, st);
-  DH_CHECK_HIP(hipMemsetAsync(cgs, 0, sizeof(CgSync), st));
-  hipLaunchKernelGGL(k_cg_fill_multi, dim3(CGM_WGS, 1), dim3(1024), 0, st, res, out, src, unk, counts, 4, 2, 3, vx, vr, vp, vq,
-                     cg_cap(50000), 1e-24, counts, (const float*)lap, CG_SLOTS * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2, cgs,
-                     infill_border);
-  hipLaunchKernelGGL(k_cg_fill, dim3(1), dim3(1024), 0, st, res, out, src, unk, counts, 4, 2, 3, vx, vr, vp, vq, cg_cap(50000),
-                     1e-24, counts, (const float*)lap, CGM_WGS * CGM_EPT * 1024, pixmap, nb_ud, (size_t)R2, nb_lr, (size_t)R2,
-                     infill_border);
+  compact(src, R2, 1, 0, w.unk, 0, counts + 2, 1, w.bc, st);
+  const CgScratch scratch = {w.vx, w.vr, w.vp, w.vq, w.pixmap, w.nb_ud, w.nb_lr, (size_t)R2, (size_t)R2, w.cgs};
+  const int rc = launch_infill(scratch, 1, res, out, src, w.unk, counts, cg_cap(50000), w.lap, CG_SLOTS * 1024, infill_border, st);
+  if (rc != DH_OK) return rc;
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

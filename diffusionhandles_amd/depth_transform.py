@@ -5,9 +5,11 @@ Mirrors /root/reference/diffhandles/depth_transform.py:73-89 (`transform_depth`)
 (`depth_to_world_coords`).  All arithmetic runs in the HIP library
 (csrc/geometry.hip) through the C ABI; PyTorch only owns the device buffers.
 `reproject` is the batched form (K edits of one image in one launch sequence) that the
-reference does not have: `reproject_plan` decides everything on the host, `_run_plan` allocates
-and launches (DESIGN.md "One host path for the re-projection"); `reproject_edits` ..
-`reproject_border_edits` are that call under the names and parameter lists they grew up with.
+reference does not have: `reproject_plan` decides everything on the host, `reproject_record` turns
+the plan into the one argument record of the C call (dh_reproject_args), `_run_plan` allocates and
+launches (DESIGN.md "One host path for the re-projection", "One record for the re-projection");
+`reproject_edits` .. `reproject_border_edits` are that call under the names and parameter lists they
+grew up with.
 """
 import ctypes
 import types
@@ -568,12 +570,11 @@ def donor_rows(rows, instances, n_host):
     return lut.to(rows.device)[rows.long()]
 
 
-def _plan(kind, entry=None, workspace_query=None, **fields):
+def _plan(kind, **fields):
     """The record `reproject_plan` returns: what it decided about one call, host values only, nothing of the compute device.
 
-    kind              "objects", "pure_removal", "pure_camera" or "empty"
-    entry             the C entry that runs (None: "empty" launches nothing)
-    workspace_query   the *_workspace_bytes entry that sizes its workspace
+    kind              "objects", "pure_removal", "pure_camera" or "empty" ("empty" launches nothing; the others are one
+                      dh_reproject call, or one per edit, on the record `reproject_record` makes of the plan)
     res               the side of the images
     M, D, N           host masks, donor masks and instances as the caller gave them
     kept              indices of the non-empty masks (host masks, then donor masks)
@@ -584,7 +585,7 @@ def _plan(kind, entry=None, workspace_query=None, **fields):
     inst_start        int32 point-list offsets, per surviving instance
     n_fg, n_pts       foreground points, and points summed over the instances (equal without copies)
     cap               correspondence rows per edit
-    with_table        the instance entries run, and the debug dict has corr_inst / inst_start
+    with_table        the call carries the instance table, and the debug dict has corr_inst / inst_start
     return_instances  every result carries the instance array
     footprints, ratio the checked footprint settings (check_footprints)
     edits             K lists of transforms after check_transform (as given where nothing moves)
@@ -595,14 +596,13 @@ def _plan(kind, entry=None, workspace_query=None, **fields):
     masks_u8          [M + D, res * res] uint8, where the masks are
     vacated           [res * res] bool union of the removed masks, or None
     covered           camera calls: [res * res] bool, host masks and removed masks (bg_valid is its complement), or None
-    infill_border     0 (zero) or 1 (reflect: the border entries run, with the arguments the named entry lacks left empty)
-    view_surfaces     the setting is on AND an edit has a camera: the surface entries run, one row per target pixel in the edits
-                      with a camera (False otherwise: the setting acts only where there is a view); surface_ratio: None or the
-                      checked ratio
-    bent, n_bones     an instance of an edit is a `Bend`: dh_reproject_bend_edits runs, with n_bones rows per instance and edit (the
+    infill_border     0 (zero) or 1 (reflect)
+    view_surfaces     the setting is on AND an edit has a camera: one row per target pixel in the edits with a camera (False
+                      otherwise: the setting acts only where there is a view); surface_ratio: None or the checked ratio
+    bent, n_bones     an instance of an edit is a `Bend`: n_bones rows per instance and edit (the
                       largest bone count of the call; shorter instances pad with copies of their bone 0 at weight 0) and the
                       weights gathered at the instances' pixels.  False, 1: the call it was"""
-    p = types.SimpleNamespace(kind=kind, entry=entry, workspace_query=workspace_query, N=0, kept=[], n_host_kept=0, caller=[],
+    p = types.SimpleNamespace(kind=kind, N=0, kept=[], n_host_kept=0, caller=[],
                               obj_start=np.zeros(1, dtype=np.int32), inst_obj=np.zeros(0, dtype=np.int32),
                               inst_start=np.zeros(1, dtype=np.int32), n_fg=0, n_pts=0, cap=0, with_table=False, inst=None, masks_u8=None,
                               vacated=None, covered=None, infill_border=0, view_surfaces=False, surface_ratio=None, n_bones=1, bent=False)
@@ -699,12 +699,6 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
                   removed_given=removed_masks is not None, donor=donor, infill_border=border,
                   view_surfaces=surfaces and cams is not None, surface_ratio=surface_ratio if cams is not None else None)
     surfaces = common["view_surfaces"]          # (without a camera the call is the call without the setting)
-    background = ("dh_reproject_background", "dh_reproject_background_workspace_bytes")
-    camera_background = ("dh_reproject_camera_background", "dh_reproject_background_workspace_bytes")
-    if border:          # one entry for both kinds without a foreground point; the workspace does not grow
-        background = camera_background = ("dh_reproject_border_background", "dh_reproject_background_workspace_bytes")
-    if surfaces:        # (a camera is present: the border entry's list, the setting and the ratio; a workspace query of its own)
-        camera_background = ("dh_reproject_surface_background", "dh_reproject_surface_background_ws_bytes")
     if M == 0 and (removed or cams is not None) and donor is None:
         for e, tfs in enumerate(edits):
             if len(tfs) != 0:
@@ -715,7 +709,7 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
                              f"instance)")
         if cams is not None:
             res, covered = _plan_pure_camera(shape, removed)
-            return _plan("pure_camera", *camera_background, res=res, edits=edits, covered=covered, **common)
+            return _plan("pure_camera", res=res, edits=edits, covered=covered, **common)
         _check_single_image(shape)
         res = _removed_fit_depth(removed, shape, removal)
         extra, vacated = _removed_stats(removed, torch.zeros(res * res, dtype=torch.bool, device=removed[0].device))
@@ -724,7 +718,7 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
             removed_overlap(removed, [], f"{removal}: removed_masks")
         if sum(tail[0::2]) == 0:
             raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got 0")
-        return _plan("pure_removal", *background, res=res, edits=edits, with_table=instances is not None, vacated=vacated,
+        return _plan("pure_removal", res=res, edits=edits, with_table=instances is not None, vacated=vacated,
                              **common)
     if not 1 <= M <= MAX_OBJECTS and donor is None:
         raise ValueError(f"Expected 1 to {MAX_OBJECTS} foreground masks, got {M}")
@@ -800,11 +794,11 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     if n_fg == 0 and cams is not None:
         # every mask is empty (dropped with its transforms): the pure camera move
         res, covered = _plan_pure_camera(shape, removed)
-        return _plan("pure_camera", *camera_background, res=res, covered=covered, **common)
+        return _plan("pure_camera", res=res, covered=covered, **common)
     if n_fg == 0 and n_vacated > 0:
         # every foreground mask is empty (dropped with its transforms) and an object is deleted: the pure removal
         _removed_fit_depth(removed, shape, removal)
-        return _plan("pure_removal", *background, res=res, **common)
+        return _plan("pure_removal", res=res, **common)
     if n_fg == 0:
         return _plan("empty", res=res, **common)
     # the instances of the kept masks (empty masks are dropped with all of their instances); caller[n'] = the caller's index
@@ -813,21 +807,7 @@ def reproject_plan(depth, fg_masks, edits, *, instances=None, removed_masks=None
     inst_start = np.zeros(len(caller) + 1, dtype=np.int32)
     inst_start[1:] = np.cumsum([int(obj_start[o + 1] - obj_start[o]) for o in inst_obj])
     n_pts = int(inst_start[-1])                # = n_fg without copies
-    if cams is not None:
-        entry, query = "dh_reproject_camera_edits", "dh_reproject_camera_workspace_bytes"
-    elif with_table:          # (a donor call sizes its workspace as the instance call it extends)
-        entry = "dh_reproject_instance_edits" if donor is None else "dh_reproject_donor_edits"
-        query = "dh_reproject_instances_workspace_bytes"
-    else:
-        entry, query = "dh_reproject_footprint_edits", "dh_reproject_footprints_workspace_bytes"
-    if border:          # the camera entry's list and a trailing border; sized by the query of the call it extends
-        entry = "dh_reproject_border_edits"
-        query = "dh_reproject_camera_workspace_bytes" if cams is not None else "dh_reproject_instances_workspace_bytes"
-    if surfaces:        # the border entry's list, the setting and the ratio; the rows of a view edit are per target pixel
-        entry, query = "dh_reproject_surface_edits", "dh_reproject_surface_ws_bytes"
-    if bent:            # the surface entry's list, the bones and the weights; a call without a Bend is the call it was
-        entry, query = "dh_reproject_bend_edits", "dh_reproject_bend_ws_bytes"
-    return _plan("objects", entry, query, res=res, kept=kept, obj_start=obj_start, n_host_kept=sum(1 for m in kept if m < M),
+    return _plan("objects", res=res, kept=kept, obj_start=obj_start, n_host_kept=sum(1 for m in kept if m < M),
                          caller=caller, inst_obj=inst_obj, inst_start=inst_start, n_fg=n_fg, n_pts=n_pts,
                          cap=res * res if footprints or surfaces else n_pts,          # one row per target pixel with footprints / view surfaces, per point without
                          masks_u8=masks_u8, covered=covered if cams is not None else None, **common)
@@ -857,21 +837,55 @@ def _run_plan(p, depth, bg_depth, intrinsics, use_input_depth_normalization, ret
     return _run_objects(p, g) if p.kind == "objects" else _run_background(p, g)
 
 
-def _workspace(p, g):
-    """The workspace of the plan's entry, sized by the query the plan names."""
+def _host_ptr(arr, ctype):
+    return arr.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+def reproject_record(p, K):
+    """The size-and-settings part of the dh_reproject_args (include/diffhandles_hip.h) of the plan's call with K edits: sizes, the
+    mask and instance tables, the donor count, has_view, border, surfaces and ratio, footprints and ratio, bones, capacity --
+    everything dh_reproject_workspace reads.  Pure host; `_run_objects` / `_run_background` add the pointers and call
+    dh_reproject.  Zero means off, so a member is set only where the plan has the feature:
+      the table      with an instance table, a camera, a reflecting border or a `Bend` (without: the identity table on the
+                     workspace layout of the call without copies)
+      has_view       with a camera: one flag per edit
+    A kind without a foreground point ("pure_removal", "pure_camera") is one call per edit: n_fg = 0, n_edits = 1, and
+    has_view[0] says whether ANY edit has a camera (the one workspace serves them all; `_run_background` sets each edit's).
+    ValueError for the kind "empty", which launches nothing."""
+    if p.kind == "empty":
+        raise ValueError("reproject_record: an empty plan launches nothing and has no record")
+    a = _lib.ReprojectArgs(res=p.res, n_fg=p.n_fg, n_edits=K, infill_border=p.infill_border, view_surfaces=int(p.view_surfaces),
+                           surface_max_ratio=0.0 if p.surface_ratio is None else p.surface_ratio)
+    has_view = None if p.cams is None else np.asarray([c is not None for c in p.cams], dtype=np.uint8)
     if p.kind != "objects":
-        sizes = (g.res, 1) if p.view_surfaces else (g.res,)
-    elif p.bent:
-        sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), int(p.view_surfaces), int(p.footprints), p.n_bones)
-    elif p.view_surfaces:
-        sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), 1)
-    elif p.with_table or p.infill_border:
-        sizes = (g.res, p.n_pts, g.K, len(p.kept), len(p.caller), int(p.footprints))
+        a.n_edits = 1
+        has_view = None if has_view is None else np.asarray([has_view.any()], dtype=np.uint8)
     else:
-        sizes = (g.res, p.n_fg, g.K, len(p.kept), int(p.footprints))
+        a.n_objects, a.n_donor_objects, a.corr_capacity = len(p.kept), len(p.kept) - p.n_host_kept, p.cap
+        a.footprints, a.max_ratio = int(p.footprints), 0.0 if p.ratio is None else p.ratio
+        a.obj_start = _host_ptr(p.obj_start, ctypes.c_int32)
+        if p.with_table or p.cams is not None or p.infill_border or p.bent:
+            a.n_instances, a.inst_obj = len(p.caller), _host_ptr(p.inst_obj, ctypes.c_int32)
+        if p.bent:
+            a.n_bones = p.n_bones
+    if has_view is not None:
+        a.has_view = _host_ptr(has_view, ctypes.c_uint8)
+    a.host_arrays = (p.obj_start, p.inst_obj, has_view)          # (the record points into them)
+    return a
+
+
+def _workspace(a, g):
+    """The workspace of the record's call, sized by dh_reproject_workspace."""
     nbytes = ctypes.c_size_t()
-    _lib.check(getattr(g.L, p.workspace_query)(*sizes, ctypes.byref(nbytes)), p.workspace_query)
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=g.dev), nbytes.value
+    _lib.check(g.L.dh_reproject_workspace(ctypes.byref(a), ctypes.byref(nbytes)), "dh_reproject_workspace")
+    a.workspace_tensor = torch.empty(nbytes.value, dtype=torch.uint8, device=g.dev)
+    a.workspace, a.workspace_bytes, a.stream = _lib.ptr(a.workspace_tensor), nbytes.value, g.st
+
+
+def _geometry(a, g):
+    """The members every call shares: the background depth, the pixel grids, the intrinsics, the bounds."""
+    a.bg_depth, a.grid_x, a.grid_y, a.bounds = _lib.ptr(g.bg), _lib.ptr(g.gx), _lib.ptr(g.gy), _lib.ptr(g.bounds)
+    a.inv_fx, a.inv_fy, a.fx, a.fy = g.ifx, g.ify, g.fx, g.fy
 
 
 def _vacated_u8(p, g):
@@ -892,20 +906,17 @@ def _empty_debug(g, table):
     return dbg
 
 
-def _view_ptr(view):
-    return None if view is None else view.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
 def _run_background(p, g):
-    """The kinds without a foreground point.  "pure_removal": dh_reproject_background once, its result K times.  "pure_camera":
-    dh_reproject_camera_background once per edit, with the edit's view (an edit without a camera: without a view, the pure
-    removal's result); every row is a background row, instance index N.  With a reflecting in-fill border both kinds run
-    dh_reproject_border_background (a pure removal: without a view)."""
+    """The kinds without a foreground point (dh_reproject with n_fg = 0).  "pure_removal": one call, its result K times.
+    "pure_camera": one call per edit, with the edit's view (an edit without a camera: without a view, the pure removal's
+    result); every row is a background row, instance index N."""
     camera = p.kind == "pure_camera"
     dev, res, K = g.dev, g.res, g.K
     views = [None if c is None else view_row(c) for c in p.cams] if camera else [None]
     n = len(views)
-    ws, ws_bytes = _workspace(p, g)
+    a = reproject_record(p, K)
+    _workspace(a, g)
+    _geometry(a, g)
     zmap = torch.empty((n, res, res), dtype=torch.float32, device=dev)
     disp = torch.empty((n, res, res), dtype=torch.float32, device=dev)
     counts = torch.zeros((n, 4), dtype=torch.int32, device=dev)
@@ -915,17 +926,12 @@ def _run_background(p, g):
         bg_corr = torch.empty((K, res * res, 4), dtype=torch.int64, device=dev)
         bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
     for e, view in enumerate(views):
-        args = (_lib.ptr(g.bg), res, _lib.ptr(g.gx), _lib.ptr(g.gy), g.ifx, g.ify, g.fx, g.fy, _lib.ptr(g.bounds), _lib.ptr(zmap[e]),
-                _lib.ptr(disp[e]), _lib.ptr(counts[e]), _lib.ptr(ws), ws_bytes, g.st)
+        a.zmap, a.disparity, a.counts = _lib.ptr(zmap[e]), _lib.ptr(disp[e]), _lib.ptr(counts[e])
         if camera:
-            args += (_view_ptr(view), _lib.ptr(bg_valid), _lib.ptr(bg_corr[e]), _lib.ptr(bg_counts[e:]))
-        elif p.infill_border:
-            args += (None, None, None, None)
-        if p.infill_border or p.view_surfaces:
-            args += (p.infill_border,)
-        if p.view_surfaces:
-            args += (1, 0.0 if p.surface_ratio is None else p.surface_ratio)
-        _lib.check(getattr(g.L, p.entry)(*args), p.entry)
+            a.host_arrays[2][0] = view is not None
+            a.views = None if view is None else _host_ptr(view, ctypes.c_double)
+            a.bg_valid, a.bg_corr, a.bg_counts = _lib.ptr(bg_valid), _lib.ptr(bg_corr[e]), _lib.ptr(bg_counts[e:])
+        _lib.check(g.L.dh_reproject(ctypes.byref(a)), "dh_reproject")
     counts_h = counts.cpu()
     _check_infill(counts_h[:, 3])
     placed = (lambda t: t) if g.on_device else (lambda t: t.cpu())
@@ -974,10 +980,8 @@ def _bone_rows(p, fg_pix, dev):
 
 
 def _run_objects(p, g):
-    """The kind with foreground points: the pixel lists of the kept masks, the buffers, the entry the plan names (each of
-    dh_reproject_footprint_edits, _instance_edits, _donor_edits and _camera_edits takes the arguments of the one before it and a
-    few more; dh_reproject_border_edits takes the camera entry's and the border, with the identity table, no donor and no view
-    where the plan has none), then the results and the debug dict."""
+    """The kind with foreground points: the pixel lists of the kept masks, the buffers, dh_reproject on the plan's record, then
+    the results and the debug dict."""
     dev, res, K, L = g.dev, g.res, g.K, g.L
     R2, Mk, Nk, n_fg, n_pts, cap = res * res, len(p.kept), len(p.caller), p.n_fg, p.n_pts, p.cap
     camera, donor = p.cams is not None, p.donor is not None
@@ -989,7 +993,9 @@ def _run_objects(p, g):
     for j, m in enumerate(p.kept):              # disjoint masks: the slices fill fg_pix[0 .. n_fg), n_fg <= R2
         _lib.check(L.dh_fg_pixel_list(_lib.ptr(masks_u8[m]), res, _lib.ptr(fg_pix[int(obj_start[j]):]), _lib.ptr(n_dev[j:]),
                                       _lib.ptr(ws_small), ws_small.numel(), g.st), "dh_fg_pixel_list")
-    ws, ws_bytes = _workspace(p, g)
+    a = reproject_record(p, K)
+    _workspace(a, g)
+    _geometry(a, g)
     zmap = torch.empty((K, res, res), dtype=torch.float32, device=dev)
     raw = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
     clean = torch.empty((K, res, res), dtype=torch.uint8, device=dev)
@@ -1003,41 +1009,28 @@ def _run_objects(p, g):
         rows, bone_w = _bone_rows(p, fg_pix, dev)
     else:
         rows = _similarity_rows([tfs[n] for tfs in p.edits for n in p.caller])    # edit-major, K x Nk rows (C-contiguous)
-    args = (_lib.ptr(g.d), _lib.ptr(g.bg), _lib.ptr(fg_pix), n_fg, Mk, obj_start.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), res,
-            _lib.ptr(g.gx), _lib.ptr(g.gy), g.ifx, g.ify, g.fx, g.fy, K,
-            rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _lib.ptr(g.bounds),
-            _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp), _lib.ptr(vis), _lib.ptr(txy),
-            _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(ws), ws_bytes, g.st, int(p.footprints), 0.0 if p.ratio is None else p.ratio, cap)
+    a.depth, a.fg_pix, a.xforms_host = _lib.ptr(g.d), _lib.ptr(fg_pix), _host_ptr(rows, ctypes.c_double)
+    a.zmap, a.raw_mask, a.clean_mask, a.disparity = _lib.ptr(zmap), _lib.ptr(raw), _lib.ptr(clean), _lib.ptr(disp)
+    a.vis, a.target_xy, a.corr, a.counts, a.bone_w = _lib.ptr(vis), _lib.ptr(txy), _lib.ptr(corr), _lib.ptr(counts), _lib.ptr(bone_w)
     corr_inst = None
     if p.with_table:
         corr_inst = torch.empty((K, cap), dtype=torch.uint8, device=dev)
-    if p.with_table or p.infill_border or p.view_surfaces or p.bent:
-        args += (Nk, p.inst_obj.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _lib.ptr(corr_inst))
-    if camera or donor or p.infill_border or p.bent:
-        dd = p.donor[0].detach().to(dev, torch.float32).contiguous() if donor else None
-        args += (_lib.ptr(dd), p.n_host_kept)
+        a.corr_inst = _lib.ptr(corr_inst)
+    if donor:
+        dd = p.donor[0].detach().to(dev, torch.float32).contiguous()
+        a.donor_depth = _lib.ptr(dd)
     if camera:
         # the view rows (host), the pixels that show the background (the union of the host's masks and the removed masks is
         # in-painted in bg_depth), and the background rows' buffers
         views = np.zeros((K, SIMILARITY_ROW), dtype=np.float64)
-        has_view = np.zeros(K, dtype=np.uint8)
         for e, c in enumerate(p.cams):
             if c is not None:
-                views[e], has_view[e] = view_row(c), 1
+                views[e] = view_row(c)
         bg_valid = (~p.covered.to(dev)).to(torch.uint8).contiguous()
         bg_corr = torch.empty((K, R2, 4), dtype=torch.int64, device=dev)
         bg_counts = torch.zeros(K, dtype=torch.int32, device=dev)
-        args += (_view_ptr(views), has_view.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _lib.ptr(bg_valid), _lib.ptr(bg_corr),
-                 _lib.ptr(bg_counts))
-    elif p.infill_border or p.bent:
-        args += (None, None, None, None, None)
-    if p.infill_border or p.view_surfaces or p.bent:
-        args += (p.infill_border,)
-    if p.view_surfaces or p.bent:
-        args += (int(p.view_surfaces), 0.0 if p.surface_ratio is None else p.surface_ratio)
-    if p.bent:
-        args += (p.n_bones, _lib.ptr(bone_w))
-    _lib.check(getattr(L, p.entry)(*args), p.entry)
+        a.views, a.bg_valid, a.bg_corr, a.bg_counts = _host_ptr(views, ctypes.c_double), _lib.ptr(bg_valid), _lib.ptr(bg_corr), _lib.ptr(bg_counts)
+    _lib.check(L.dh_reproject(ctypes.byref(a)), "dh_reproject")
     row_donor = donor_rows(corr_inst, [p.inst[n] for n in p.caller], p.M) if donor else None
     if p.with_table and p.caller != list(range(Nk)):         # instances of empty masks were dropped: the indices reported stay the caller's
         lut = torch.zeros(256, dtype=torch.uint8)          # (256 entries: the rows past the counts are not written)

@@ -353,6 +353,56 @@ int dh_reproject_bend_edits(const float* depth, const float* bg_depth, const int
                             const double* views, const uint8_t* has_view, const uint8_t* bg_valid,
                             int64_t* bg_corr, int32_t* bg_counts, int infill_border,
                             int view_surfaces, float surface_max_ratio, int n_bones, const float* bone_w);
+/* THE CALL of the re-projection: one argument record.  Every dh_reproject_* entry and every *_workspace_bytes / *_ws_bytes query
+ * above is this record with some members filled and the rest zero (csrc/reproject_compat.cpp); a member has the meaning, the
+ * type, the place (host / device) and the refusals stated at the entry that introduced it.  ZERO MEANS OFF: a record that is
+ * zero beyond the members of dh_reproject_object_edits' call (with similarity rows) is that call.
+ *   struct_bytes      sizeof(dh_reproject_args); anything else is DH_ERR_ARG before any other member is read
+ *   n_fg              > 0: foreground points of fg_pix.  0: the call WITHOUT a foreground point (dh_reproject_surface_background):
+ *                     n_edits = 1, the view row is read when has_view[0] != 0; of the tables, the transform rows and the
+ *                     foreground outputs nothing is read or written
+ *   n_instances, inst_obj   inst_obj = NULL with n_instances = 0: the identity table (instance n draws mask n) on the workspace
+ *                     layout of dh_reproject_footprint_edits; else the table of dh_reproject_instance_edits
+ *   n_bones           0 or 1: no bones (bone_w is not read); else as dh_reproject_bend_edits
+ *   n_donor_objects   the trailing masks that draw from donor_depth (0 = no donor): n_objects - n_host_objects of the donor entry
+ *   xforms_host       [n_edits][n_instances or n_objects][max(n_bones, 1)][DH_SIMILARITY_ROW] f64, host
+ * dh_reproject_workspace answers the workspace of the call the record describes.  It reads the sizes, the settings and the host
+ * arrays obj_start, inst_obj (both given: n_pts is summed over the instances; else n_pts = n_fg) and has_view (NULL = no view),
+ * no other pointer, and carves as dh_reproject does; *bytes is written only on DH_OK. */
+typedef struct dh_reproject_args {
+  uint32_t struct_bytes;
+  int32_t res, n_fg, n_objects, n_edits, n_instances, n_bones, corr_capacity;
+  int32_t footprints, n_donor_objects, infill_border, view_surfaces;
+  float max_ratio, surface_max_ratio;
+  float inv_fx, inv_fy;
+  double fx, fy;
+  /* device inputs */
+  const float *depth, *bg_depth;
+  const int32_t* fg_pix;
+  const float *grid_x, *grid_y, *bounds, *donor_depth;
+  const uint8_t* bg_valid;
+  const float* bone_w;
+  /* host inputs */
+  const int32_t *obj_start, *inst_obj;
+  const double *xforms_host, *views;
+  const uint8_t* has_view;
+  /* device outputs */
+  float* zmap;
+  uint8_t *raw_mask, *clean_mask;
+  float* disparity;
+  uint8_t* vis;
+  int32_t* target_xy;
+  int64_t* corr;
+  uint8_t* corr_inst;
+  int32_t* counts;
+  int64_t* bg_corr;
+  int32_t* bg_counts;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+} dh_reproject_args;
+int dh_reproject(const dh_reproject_args* a);
+int dh_reproject_workspace(const dh_reproject_args* a, size_t* bytes);
 /* unprojected points only (depth_to_world_coords), [res*res][3] f32 */
 int dh_unproject(const float* depth, int res, const float* grid_x, const float* grid_y,
                  float inv_fx, float inv_fy, float* points, void* stream);

@@ -19,6 +19,7 @@ import camera_moves_ref as CM  # noqa: E402
 import infill_border_ref as IB  # noqa: E402
 import multi_object_ref as R  # noqa: E402
 import object_insertion_ref as OI  # noqa: E402
+import reproject_calls as RC  # noqa: E402
 import similarity_ref as S  # noqa: E402
 import test_camera_moves_gpu as CG  # noqa: E402  (helpers only: _setup, _view_rows, _check, _untouched, tiny, _common)
 import test_object_copies_gpu as OC  # noqa: E402  (helpers only: _rows, _t)
@@ -379,7 +380,7 @@ def test_host_call_against_the_reference_and_an_unbent_call_is_the_call_it_was()
     b = DT.reproject_bend_edits(*args, plain)
     for x, y in zip(a, b):
         assert all(torch.equal(u, v) for u, v in zip(x, y))
-    assert DT.reproject_plan(c.depth, c.masks, plain).entry == "dh_reproject_footprint_edits"
+    assert RC.fields(DT.reproject_plan(c.depth, c.masks, plain)) == RC.FOOTPRINT
 
 
 tiny = CG.tiny

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import reproject_calls as RC  # noqa: E402
 import bend_ref as BR  # noqa: E402
 import footprints_ref as F  # noqa: E402
 import multi_object_ref as R  # noqa: E402
@@ -273,7 +274,7 @@ def test_the_plan_with_and_without_a_bend():
     mk = lambda bones: DT.bend_chain(depth, D.intrinsics_f32(), masks[0], (cx, cy - rad), (cx, cy + rad), 8.0, 40.0, Z, pivot=piv, bones=bones)
     tf = (10.0, Y, Z0)
     p = DT.reproject_plan(depth, masks, [[mk(2), tf], [tf, tf], [mk(3), tf]])
-    assert (p.kind, p.entry, p.workspace_query) == ("objects", "dh_reproject_bend_edits", "dh_reproject_bend_ws_bytes")
+    assert (p.kind, RC.fields(p)) == ("objects", dict(RC.INSTANCE, bones=3))          # the bones, on the instance carving
     assert p.bent is True and p.n_bones == 3 and p.cap == p.n_pts and not p.with_table
     n0, n1 = int(masks[0].sum()), int(masks[1].sum())
     fg_pix = torch.cat([torch.nonzero(m.reshape(-1) != 0)[:, 0] for m in masks]).to(torch.int32)
@@ -289,19 +290,18 @@ def test_the_plan_with_and_without_a_bend():
     for kw, cap in ((dict(footprints=True), 64 * 64), (dict(cameras=[(4.0, Y, Z0, None)], view_surfaces=True), 64 * 64),
                     (dict(infill_border="reflect"), None), (dict(cameras=[(4.0, Y, Z0, None)]), None)):
         q = DT.reproject_plan(depth, masks, [[mk(4), tf]], **kw)
-        assert (q.entry, q.workspace_query, q.n_bones, q.bent) == ("dh_reproject_bend_edits", "dh_reproject_bend_ws_bytes", 4, True)
+        f = RC.fields(q)
+        assert (f["bones"], f["table"], q.n_bones, q.bent) == (4, True, 4, True)
+        assert (f["views"], f["surfaces"], f["border"]) == ("cameras" in kw, int("view_surfaces" in kw), int("infill_border" in kw))
         assert q.cap == (q.n_pts if cap is None else cap)
     q = DT.reproject_plan(depth, masks, [[mk(2), mk(4), tf]], instances=[0, 0, 1])
     assert q.n_bones == 4 and q.with_table and q.n_pts == 2 * n0 + n1
     # without a Bend every plan is the plan it was: the entries named before this feature, one row per instance
-    for kw, entry, query in ((dict(), "dh_reproject_footprint_edits", "dh_reproject_footprints_workspace_bytes"),
-                             (dict(instances=[0, 1, 0]), "dh_reproject_instance_edits", "dh_reproject_instances_workspace_bytes"),
-                             (dict(infill_border="reflect"), "dh_reproject_border_edits", "dh_reproject_instances_workspace_bytes"),
-                             (dict(cameras=[(4.0, Y, Z0, None)]), "dh_reproject_camera_edits", "dh_reproject_camera_workspace_bytes"),
-                             (dict(cameras=[(4.0, Y, Z0, None)], view_surfaces=True), "dh_reproject_surface_edits", "dh_reproject_surface_ws_bytes")):
+    for kw, call in ((dict(), RC.FOOTPRINT), (dict(instances=[0, 1, 0]), RC.INSTANCE), (dict(infill_border="reflect"), RC.border(RC.INSTANCE)),
+                     (dict(cameras=[(4.0, Y, Z0, None)]), RC.CAMERA), (dict(cameras=[(4.0, Y, Z0, None)], view_surfaces=True), RC.SURFACE)):
         n = 3 if "instances" in kw else 2
         q = DT.reproject_plan(depth, masks, [[tf] * n], **kw)
-        assert (q.entry, q.workspace_query, q.n_bones, q.bent) == (entry, query, 1, False), kw
+        assert (RC.fields(q), q.n_bones, q.bent) == (call, 1, False), kw
         assert q.edits == [[DT.check_transform(tf)] * n]
 
 

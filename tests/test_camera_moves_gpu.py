@@ -20,6 +20,7 @@ import multi_object_ref as R  # noqa: E402
 import object_copies_ref as C  # noqa: E402
 import object_insertion_ref as I  # noqa: E402
 import object_removal_ref as RM  # noqa: E402
+import reproject_calls as RC  # noqa: E402
 import similarity_ref as S  # noqa: E402
 import test_object_copies_gpu as OC  # noqa: E402  (helpers only: _setup, _rows, _t)
 
@@ -765,13 +766,13 @@ def test_the_host_plan_is_what_the_run_does_and_every_name_is_the_one_call():
     donor_depth, donor_masks = I.donor_scene(res, "disjoint")
     donor = dict(donor_depth=donor_depth.to(dev()), donor_masks=[x.to(dev()) for x in donor_masks])
     cam = CM.cameras_for(depth)["pan"]
-    calls = [(DT.reproject_instance_edits, [m[0], torch.zeros_like(m[0]), m[1]], [[tfs[0], tfs[1], tfs[1], tfs[0]]],
+    calls = [(DT.reproject_instance_edits, RC.INSTANCE, [m[0], torch.zeros_like(m[0]), m[1]], [[tfs[0], tfs[1], tfs[1], tfs[0]]],
               dict(instances=[2, 1, 0, 0], return_instances=True), [0, 2, 3]),
-             (DT.reproject_donor_edits, m, [tfs + [tfs[0][:3] + (0.8, None)]], donor, [0, 1, 2]),
-             (DT.reproject_camera_edits, m, [tfs, tfs], dict(cameras=[cam, None]), [0, 1])]
-    for named, fg, edits, kw, caller in calls:
+             (DT.reproject_donor_edits, RC.DONOR, m, [tfs + [tfs[0][:3] + (0.8, None)]], donor, [0, 1, 2]),
+             (DT.reproject_camera_edits, RC.CAMERA, m, [tfs, tfs], dict(cameras=[cam, None]), [0, 1])]
+    for named, call, fg, edits, kw, caller in calls:
         p = DT.reproject_plan(d, fg, edits, **kw)
-        assert p.kind == "objects" and p.entry == "dh_" + named.__name__ and p.caller == caller
+        assert p.kind == "objects" and RC.fields(p) == call and p.caller == caller
         out, dbg = named(d, b, fg, D.intrinsics_f32(), edits, return_debug=True, **kw)
         assert dbg["vis"].shape[1] == p.n_pts and dbg["corr_dev"].shape[1] == p.cap
         assert np.array_equal(dbg["obj_start"], p.obj_start) and np.array_equal(dbg["inst_start"], p.inst_start)

@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import camera_moves_ref as CM  # noqa: E402
 import footprints_ref as F  # noqa: E402
 import infill_border_ref as IB  # noqa: E402
+import reproject_calls as RC  # noqa: E402
 import multi_object_ref as R  # noqa: E402
 import object_removal_ref as RM  # noqa: E402
 import test_camera_moves_gpu as TC  # noqa: E402  (helpers only: _setup, _view_rows, _call, _check, _untouched, _background_call, tiny)
@@ -248,7 +249,7 @@ def test_pure_removal_of_an_object_at_the_frame():
     ref, g = RM.background_alone(bg2)
     ref = IB.harmonic_fill(g["disparity"], g["unowned"], "reflect").astype(np.float32)
     p = DT.reproject_plan(depth, [], [[], []], removed_masks=[mask], infill_border="reflect")
-    assert (p.kind, p.entry) == ("pure_removal", "dh_reproject_border_background")
+    assert (p.kind, RC.fields(p)) == ("pure_removal", RC.border(RC.BACKGROUND))
     out, dbg = DT.reproject(depth.to(dev()), got, [], D.intrinsics_f32(), [[], []], removed_masks=[mask.to(dev())], infill_border="reflect",
                             return_debug=True)
     assert len(out) == 2 and all(len(r[1]) == 0 for r in out)
@@ -269,7 +270,7 @@ def test_object_edit_whose_infill_touches_the_frame():
     assert touch.any() and rest.any()
     args = (depth.to(dev()), bg.to(dev()), [m.to(dev()) for m in masks], D.intrinsics_f32(), [[OC._t(tf) for tf in tfs]])
     p = DT.reproject_plan(depth, masks, [[OC._t(tf) for tf in tfs]], infill_border="reflect")
-    assert p.entry == "dh_reproject_border_edits" and not p.with_table
+    assert RC.fields(p) == RC.border(RC.INSTANCE) and not p.with_table
     ((disp, corr),), dbg = DT.reproject(*args, infill_border="reflect", return_debug=True)
     ((disp0, corr0),), dbg0 = DT.reproject(*args, return_debug=True)
     assert torch.equal(corr, geo[1]) and torch.equal(corr, corr0)

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import camera_moves_ref as CM  # noqa: E402
 import infill_border_ref as IB  # noqa: E402
 import multi_object_ref as R  # noqa: E402
+import reproject_calls as RC  # noqa: E402
 
 from oracle import depth_ref as D  # noqa: E402
 
@@ -223,24 +224,26 @@ def test_the_plan_carries_the_border_and_names_the_border_entries():
     tf = (10.0, Y, Z3)
     cam = (4.0, Y, Z3, None)
     zero = DT.reproject_plan(depth, masks, [[tf, tf]])
-    assert zero.infill_border == 0 and zero.entry == "dh_reproject_footprint_edits"
+    assert zero.infill_border == 0 and RC.fields(zero) == RC.FOOTPRINT
     for value in (None, "zero"):
         p = DT.reproject_plan(depth, masks, [[tf, tf]], infill_border=value)
-        assert (p.infill_border, p.entry, p.workspace_query) == (0, zero.entry, zero.workspace_query)
-    for kw, query in ((dict(), "dh_reproject_instances_workspace_bytes"), (dict(footprints=True), "dh_reproject_instances_workspace_bytes"),
-                      (dict(instances=[0, 1, 0]), "dh_reproject_instances_workspace_bytes"),
-                      (dict(cameras=[cam]), "dh_reproject_camera_workspace_bytes")):
+        assert (p.infill_border, RC.fields(p)) == (0, RC.fields(zero))
+    # (the border call is the call it extends with the border, sized as that call is: without a camera the instance call)
+    for kw, call in ((dict(), RC.INSTANCE), (dict(footprints=True), RC.INSTANCE), (dict(instances=[0, 1, 0]), RC.INSTANCE),
+                     (dict(cameras=[cam]), RC.CAMERA)):
         n = 3 if "instances" in kw else 2
         p = DT.reproject_plan(depth, masks, [[tf] * n], infill_border="reflect", **kw)
-        assert (p.kind, p.infill_border, p.entry, p.workspace_query) == ("objects", 1, "dh_reproject_border_edits", query), kw
+        assert (p.kind, p.infill_border, RC.fields(p)) == ("objects", 1, RC.border(call)), kw
         q = DT.reproject_plan(depth, masks, [[tf] * n], **kw)
-        assert q.infill_border == 0 and q.entry != p.entry and (q.n_pts, q.cap, q.with_table) == (p.n_pts, p.cap, p.with_table)
+        assert q.infill_border == 0 and RC.fields(q) != RC.fields(p) and (q.n_pts, q.cap, q.with_table) == (p.n_pts, p.cap, p.with_table)
     p = DT.reproject_plan(depth, [], [[]], removed_masks=masks, infill_border="reflect")
-    assert (p.kind, p.entry, p.infill_border) == ("pure_removal", "dh_reproject_border_background", 1)
+    assert (p.kind, RC.fields(p), p.infill_border) == ("pure_removal", RC.border(RC.BACKGROUND), 1)
     p = DT.reproject_plan(depth, [], [[]], cameras=[cam], infill_border="reflect")
-    assert (p.kind, p.entry, p.workspace_query) == ("pure_camera", "dh_reproject_border_background", "dh_reproject_background_workspace_bytes")
+    assert (p.kind, RC.fields(p)) == ("pure_camera", RC.border(RC.CAMERA_BACKGROUND))
     p = DT.reproject_plan(depth, [torch.zeros_like(masks[0])], [[tf]], infill_border="reflect")
-    assert p.kind == "empty" and p.entry is None
+    assert p.kind == "empty"
+    with pytest.raises(ValueError, match="launches nothing"):
+        DT.reproject_record(p, 1)
 
 
 def test_mesh_mode_refuses_reflect_before_any_device_work():

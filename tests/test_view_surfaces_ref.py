@@ -11,6 +11,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import reproject_calls as RC  # noqa: E402
 import camera_moves_ref as CM  # noqa: E402
 import test_arena_hooks as AH  # noqa: E402  (helpers only: the arena fixture, the pinned sizes, the size / gap / take checks)
 import multi_object_ref as R  # noqa: E402
@@ -269,15 +270,14 @@ def test_the_plan_names_the_surface_entries_only_with_a_camera():
     for border, value in (("zero", 0), ("reflect", 1)):
         p = DT.reproject_plan(depth, masks, [[tf, tf], [tf, tf]], cameras=[cam, None], view_surfaces=True, view_surface_max_ratio=1.25,
                               infill_border=border)
-        assert (p.kind, p.entry, p.workspace_query) == ("objects", "dh_reproject_surface_edits", "dh_reproject_surface_ws_bytes")
+        assert (p.kind, RC.fields(p)) == ("objects", dict(RC.SURFACE, border=value))          # views, the setting, no bones, the table
         assert p.cap == 64 * 64 and p.view_surfaces is True and p.surface_ratio == 1.25 and p.infill_border == value and p.with_table
         q = DT.reproject_plan(depth, masks, [[tf, tf], [tf, tf]], cameras=[cam, None], infill_border=border)
         assert q.view_surfaces is False and q.surface_ratio is None and q.cap == q.n_pts == p.n_pts
-        assert q.entry == ("dh_reproject_border_edits" if value else "dh_reproject_camera_edits")
-        assert q.workspace_query == "dh_reproject_camera_workspace_bytes"
+        assert RC.fields(q) == (RC.border(RC.CAMERA) if value else RC.CAMERA)
+        assert DT.reproject_record(q, 2).view_surfaces == 0 and list(DT.reproject_record(q, 2).has_view[0:2]) == [1, 0]
         p = DT.reproject_plan(depth, [], [[]], cameras=[cam], view_surfaces=True, infill_border=border)
-        assert (p.kind, p.entry, p.workspace_query, p.view_surfaces) == \
-            ("pure_camera", "dh_reproject_surface_background", "dh_reproject_surface_background_ws_bytes", True)
+        assert (p.kind, RC.fields(p), p.view_surfaces) == ("pure_camera", dict(RC.SURFACE_BACKGROUND, border=value), True)
     # off, and on without a camera: every plan is the one it was, field for field
     for kw in (dict(), dict(instances=[0, 1, 0]), dict(footprints=True), dict(infill_border="reflect"), dict(cameras=[None]),
                dict(removed_masks=[])):
@@ -293,8 +293,7 @@ def test_the_plan_names_the_surface_entries_only_with_a_camera():
                 assert same, (kw, extra, k)
     a = DT.reproject_plan(depth, [], [[]], removed_masks=masks)
     b = DT.reproject_plan(depth, [], [[]], removed_masks=masks, view_surfaces=True)
-    assert (a.kind, a.entry, a.workspace_query) == (b.kind, b.entry, b.workspace_query) == \
-        ("pure_removal", "dh_reproject_background", "dh_reproject_background_workspace_bytes")
+    assert (a.kind, RC.fields(a)) == (b.kind, RC.fields(b)) == ("pure_removal", RC.BACKGROUND)
 
 
 # ---- 8. the edit calls and the tool ----------------------------------------------------------------------------------------------
@@ -323,13 +322,13 @@ def test_the_conf_keys_reach_the_plan_of_every_camera_call(monkeypatch):
     seen = []
 
     def run_plan(p, *a, **kw):
-        seen.append((p.entry, p.view_surfaces, p.surface_ratio, p.cap == p.res * p.res))
+        seen.append((RC.fields(p), p.view_surfaces, p.surface_ratio, p.cap == p.res * p.res))
         raise Reached
 
     monkeypatch.setattr(DT, "_run_plan", run_plan)
-    on = ("dh_reproject_surface_edits", True)
-    for keys, want in ((dict(), ("dh_reproject_camera_edits", False, None, False)),
-                       (dict(depth_transform_view_surfaces=False), ("dh_reproject_camera_edits", False, None, False)),
+    on = (RC.SURFACE, True)
+    for keys, want in ((dict(), (RC.CAMERA, False, None, False)),
+                       (dict(depth_transform_view_surfaces=False), (RC.CAMERA, False, None, False)),
                        (dict(depth_transform_view_surfaces=True), on + (None, True)),
                        (dict(depth_transform_view_surfaces=True, depth_transform_view_surface_max_ratio=1.5), on + (1.5, True))):
         dh = FP._handles("pc", **keys)
@@ -343,7 +342,7 @@ def test_the_conf_keys_reach_the_plan_of_every_camera_call(monkeypatch):
             seen.clear()
             with pytest.raises(Reached):
                 call()
-            assert len(seen) == 1 and seen[0][1:3] == (False, None) and "surface" not in seen[0][0], (name, keys, seen)
+            assert len(seen) == 1 and seen[0][1:3] == (False, None) and seen[0][0]["surfaces"] == 0, (name, keys, seen)
     assert "depth_transform_view_surfaces" not in C.load_default() and "depth_transform_view_surface_max_ratio" not in C.load_default()
 
 

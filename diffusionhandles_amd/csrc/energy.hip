@@ -812,6 +812,7 @@ static int build_plan(const char* who, const int32_t* pairs, const uint8_t* pair
 extern "C" int dh_energy_plan_build(const int32_t* pairs, int n_pairs, const int32_t* bg_trans, int n_bg_trans, int grid,
                                     void* plan, size_t plan_bytes, void* stream) {
   DH_REQUIRE(plan && grid >= 1 && n_pairs >= 0 && n_bg_trans >= 0, "bad arguments");
+  DH_REQUIRE((size_t)(grid * grid + 256) * sizeof(int) <= 64 * 1024, "grid too large for the dedupe histogram");
   DH_REQUIRE((n_pairs == 0 || pairs) && (n_bg_trans == 0 || bg_trans), "null list");
   return build_plan(__func__, pairs, nullptr, n_pairs, bg_trans, n_bg_trans, grid, nullptr, 0, plan, plan_bytes, (hipStream_t)stream);
 }

@@ -260,6 +260,15 @@ def test_library_rejects_bad_weights_before_any_launch():
         assert build(M, w, counts) != 0, (M, w, counts)
         assert L.dh_last_error()
     assert build(2, [1.0, 1.0], [4155, 795], nb.value - 4096) != 0
+    # grid 128: the dedupe histogram (grid^2 + 256 ints of LDS) passes 64 KB -- both builds refuse it, before their first memset
+    too_large = b"grid too large for the dedupe histogram"
+    assert L.dh_energy_plan_build_objects(_lib.ptr(dl["pairs"]), _lib.ptr(dl["pair_obj"]), n, _lib.ptr(dl["bg_trans"]),
+                                          dl["bg_trans"].numel(), 128, 2, (ctypes.c_float * 2)(1.0, 1.0),
+                                          (ctypes.c_int32 * 2)(4155, 795), _lib.ptr(buf), nb.value, _lib.stream_ptr()) != 0
+    assert too_large in L.dh_last_error()
+    assert L.dh_energy_plan_build(_lib.ptr(dl["pairs"]), n, _lib.ptr(dl["bg_trans"]), dl["bg_trans"].numel(), 128, _lib.ptr(buf),
+                                  nb.value, _lib.stream_ptr()) != 0
+    assert too_large in L.dh_last_error() and b"dh_energy_plan_build" in L.dh_last_error()
     torch.cuda.synchronize()
     assert torch.equal(buf, good)                                            # nothing was launched by the refused calls
     with pytest.raises(ValueError, match="positive"):

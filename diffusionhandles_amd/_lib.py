@@ -18,6 +18,7 @@ c_i = ctypes.c_int
 c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_sz = ctypes.c_size_t
+c_l = ctypes.c_long
 
 
 class UNetConfig(ctypes.Structure):
@@ -101,6 +102,8 @@ SIGNATURES = {
     # host-only query of the attention dispatch, and what the last launch of a kind passed (tests/test_attn_plan.py)
     "dh_dbg_attn_plan": (c_i, [ctypes.POINTER(AttnPlanQuery), ctypes.POINTER(ctypes.c_int32), c_i]),
     "dh_dbg_attn_last_launch": (c_i, [c_i, ctypes.POINTER(ctypes.c_int32), c_i]),
+    # (dtype, x, ldx, gamma, beta, y, stats, dy, add, dx, rows, C, eps, stream): dh_dbg_layernorm with a row pitch for x
+    "dh_dbg_layernorm_ld": (c_i, [c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_p]),
     "dh_version": (c_i, []),
     "dh_device_count": (c_i, []),
     "dh_reproject_workspace_bytes": (c_i, [c_i, c_i, c_i, ctypes.POINTER(c_sz)]),
@@ -244,7 +247,6 @@ SIGNATURES = {
 }
 
 # test hooks (csrc/debug_api.cpp): single-kernel entry points used only by tests/
-c_l = ctypes.c_long
 DEBUG_SIGNATURES = {
     "dh_dbg_gemm": (c_i, [c_i, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i,
                           c_p, c_l, c_p, c_l, c_i, c_p, c_sz, c_p]),

@@ -373,6 +373,7 @@ extern "C" int dh_dbg_gemm_layernorm_bwd(int dtype, const void* A, long lda, con
                                          const float* gamma, const float* stats, const void* add, void* dy, void* dx, float* partial,
                                          size_t partial_elems, int* done_out, void* stream) {
   DH_REQUIRE(A && W && x && gamma && stats && dy && dx && K % 64 == 0 && N % 64 == 0 && ldx >= N, "bad arguments (N, K must be multiples of 64)");
+  DH_REQUIRE(N <= LN_MAX_C, "N must be <= " + std::to_string(LN_MAX_C) + " (LayerNorm row width)");
   static void* tiled = nullptr;
   static size_t tiled_cap = 0;
   const size_t need = (size_t)N * K * 2;
@@ -431,14 +432,31 @@ extern "C" int dh_dbg_groupnorm(int dtype, const void* x, const float* gamma, co
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
+// the row widths k_ln_fwd / k_ln_bwd hold (unet_kernels.h LN_MAX_C)
+static bool ln_width_ok(int C) { return C >= 8 && C % 8 == 0 && C <= LN_MAX_C; }
+static std::string ln_width_text() { return "C must be a multiple of 8 and <= " + std::to_string(LN_MAX_C) + " (LayerNorm row width)"; }
 extern "C" int dh_dbg_layernorm(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats,
                                 const void* dy, const void* add, void* dx, int rows, int C, float eps, void* stream) {
+  DH_REQUIRE(ln_width_ok(C), ln_width_text());
   launch_layernorm_fwd(dtype, x, gamma, beta, y, stats, rows, C, eps, (hipStream_t)stream);
   if (dy && dx) launch_layernorm_bwd(dtype, x, dy, gamma, stats, add, dx, rows, C, (hipStream_t)stream);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
+// dh_dbg_layernorm with x at row pitch ldx (elements, >= C; y, dy, add and dx stay dense), the way the engine passes a tensor's
+// pitch to both launchers.  stats may be NULL for a forward alone; add may be NULL or alias dx.
+extern "C" int dh_dbg_layernorm_ld(int dtype, const void* x, long ldx, const float* gamma, const float* beta, void* y, float* stats,
+                                   const void* dy, const void* add, void* dx, int rows, int C, float eps, void* stream) {
+  DH_REQUIRE(ln_width_ok(C), ln_width_text());
+  DH_REQUIRE(x && gamma && beta && y && rows >= 1 && ldx >= C && ldx % 8 == 0, "bad arguments (ldx >= C, ldx % 8 == 0)");
+  DH_REQUIRE(!(dy && dx) || stats, "the backward reads the saved statistics: stats must not be NULL");
+  launch_layernorm_fwd(dtype, x, gamma, beta, y, stats, rows, C, eps, (hipStream_t)stream, ldx);
+  if (dy && dx) launch_layernorm_bwd(dtype, x, dy, gamma, stats, add, dx, rows, C, (hipStream_t)stream, ldx);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
 extern "C" int dh_dbg_geglu(int dtype, const void* x, void* y, const void* dy, void* dx, int rows, int F, void* stream) {
+  DH_REQUIRE(F >= 16 && F % 16 == 0, "F must be a positive multiple of 16 (paired column layout)");
   launch_geglu_fwd(dtype, x, y, rows, F, (hipStream_t)stream);
   if (dy && dx) launch_geglu_bwd(dtype, x, dy, dx, rows, F, (hipStream_t)stream);
   DH_LAUNCH_CHECK();

@@ -38,6 +38,7 @@ extern "C" int dh_text_encoder_create(const dh_text_config* cfg, dh_text_encoder
   DH_REQUIRE(cfg && out, "null pointer");
   DH_REQUIRE(cfg->dtype == DH_DTYPE_F16 || cfg->dtype == DH_DTYPE_BF16, "dtype must be f16 or bf16");
   DH_REQUIRE(cfg->hidden % 64 == 0 && cfg->intermediate % 64 == 0 && cfg->heads * 64 == cfg->hidden, "hidden = 64 * heads, widths multiples of 64");
+  DH_REQUIRE(cfg->hidden <= LN_MAX_C, "hidden must be <= " + std::to_string(LN_MAX_C) + " (LayerNorm row width)");
   DH_REQUIRE(cfg->layers >= 1 && cfg->max_tokens >= 1 && cfg->max_tokens <= 1024 && cfg->max_batch >= 1 && cfg->max_batch <= 64, "bad configuration");
   dh_text_encoder* e = new dh_text_encoder();
   e->cfg = *cfg;

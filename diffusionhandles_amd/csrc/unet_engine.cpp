@@ -814,6 +814,8 @@ extern "C" int dh_unet_create(const dh_unet_config* cfg, dh_unet** out) {
     DH_REQUIRE(cfg->block_out_channels[i] % 64 == 0, "block_out_channels must be multiples of 64");
     DH_REQUIRE(cfg->block_out_channels[i] == cfg->heads[i] * 64, "head dim must be 64");
     DH_REQUIRE(cfg->block_out_channels[i] % cfg->norm_groups == 0, "channels must divide into norm groups");
+    // a transformer block's LayerNorm rows are block_out_channels[i] wide
+    DH_REQUIRE(cfg->block_out_channels[i] <= LN_MAX_C, "block_out_channels must be <= " + std::to_string(LN_MAX_C) + " (LayerNorm row width)");
   }
   return create_engine(cfg, nullptr, out);
 }

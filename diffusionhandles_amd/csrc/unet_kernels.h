@@ -145,6 +145,11 @@ void launch_groupnorm_bwd(int dtype, const void* x, const void* dy, const float*
 void launch_gelu(int dtype, const void* x, void* y, size_t n, hipStream_t st);
 // LayerNorm over C per row; stats [rows][2]
 // (ldx: row stride of x, 0 = C; the other operands are dense)
+// One wave holds a row as up to LN_MAXCH sixteen-byte chunks per lane: C % 8 == 0 and C <= LN_MAX_C, or the kernels read only the
+// first LN_MAX_C channels of a row and still divide by C.  The launchers do not check; the engines refuse such widths when they are
+// created (dh_unet_create, dh_text_encoder_create) and the debug entries refuse them per call.
+constexpr int LN_MAXCH = 8;
+constexpr int LN_MAX_C = 64 * 8 * LN_MAXCH;
 void launch_layernorm_fwd(int dtype, const void* x, const float* gamma, const float* beta, void* y, float* stats,
                           int rows, int C, float eps, hipStream_t st, long ldx = 0);
 // dx = ln_bwd(dy) (+ add)   (add may alias nothing; dx written)

@@ -606,8 +606,7 @@ void launch_concat_gn(int dtype, const void* a, int Ca, const void* b, int Cb, v
 }
 
 // ----------------------------------------------------------------------------- LayerNorm
-// one wave per row; C/8 sixteen-byte chunks spread over the lanes (C <= 4096)
-constexpr int LN_MAXCH = 8;
+// one wave per row; C/8 sixteen-byte chunks spread over the lanes (C <= LN_MAX_C, unet_kernels.h)
 
 template <class T, int NCH>      // NCH: 8-element chunks per lane (C <= 512 * NCH)
 __global__ void __launch_bounds__(256, NCH <= 3 ? 4 : 1) k_ln_fwd(const T* x, const float* gamma, const float* beta, T* y, float* stats, int rows, int C,

@@ -899,6 +899,16 @@ typedef struct dh_attn_plan_query {
 int dh_dbg_attn_plan(const dh_attn_plan_query* q, int32_t* out, int n_out);
 int dh_dbg_attn_last_launch(int kind, int32_t* out, int n_out);
 
+/* --------------------------------------------------------------------------------------
+ * LayerNorm forward (y [rows][C], stats [rows][2] = (mean, rstd) per row; stats may be NULL) and, when dy and dx are given, its
+ * backward dx = rstd (dy gamma - mean(dy gamma) - xhat mean(dy gamma xhat)) (+ add), the way the engines launch the pair: x has the
+ * row pitch ldx (elements, >= C, a multiple of 8), every other operand is dense; add may be NULL or alias dx.  dtype: DH_DTYPE_F16 /
+ * DH_DTYPE_BF16 for x, y, dy, add, dx; gamma, beta f32.  Refused: C % 8 != 0, C > 4096 (one wave holds a row as at most eight
+ * sixteen-byte chunks per lane), a backward without stats.  tests/test_layernorm_gpu.py.
+ * ------------------------------------------------------------------------------------ */
+int dh_dbg_layernorm_ld(int dtype, const void* x, long ldx, const float* gamma, const float* beta, void* y, float* stats,
+                        const void* dy, const void* add, void* dx, int rows, int C, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

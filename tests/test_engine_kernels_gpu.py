@@ -11,42 +11,16 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from per_element import EMIN, MANT, ulp16, within  # noqa: F401  (other test files import them from here)
 from test_unet_kernels_gpu import DT, L, P, close, dev, poisoned
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float16, torch.bfloat16]
-MANT = {torch.float16: 10, torch.bfloat16: 7}               # stored mantissa bits
-EMIN = {torch.float16: -14, torch.bfloat16: -126}           # exponent of the smallest normal number
 
 
 def gen(seed):
     return torch.Generator(device=dev()).manual_seed(seed)
-
-
-def ulp16(ref, dtype):
-    """spacing of `dtype` at the magnitude of every element of ref (fp64); the subnormal spacing below the smallest normal"""
-    a = ref.double().abs()
-    _, e = torch.frexp(a)                                   # |ref| = m 2^e, m in [0.5, 1)
-    e = torch.where(a > 0, e - 1, torch.full_like(e, EMIN[dtype])).clamp(min=EMIN[dtype])
-    return torch.ldexp(torch.ones_like(a), e - MANT[dtype])
-
-
-def within(got, ref, tol, what):
-    """every element of got finite and within tol (a tensor) of ref (fp64); the message names the worst element"""
-    assert tuple(got.shape) == tuple(ref.shape), f"{what}: shape {tuple(got.shape)} != reference {tuple(ref.shape)}"
-    g, r = got.double(), ref.double()
-    tol = torch.as_tensor(tol, dtype=torch.float64, device=r.device).expand_as(r)
-    nonfin = ~torch.isfinite(g)
-    ratio = torch.where(nonfin, torch.full_like(r, float("inf")), (g - r).abs() / tol)
-    worst = int(ratio.argmax())
-    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(worst), ratio.shape))
-    wr = ratio.reshape(-1)[worst].item()
-    print(f"{what}: worst {wr:.3g} x tolerance")
-    assert int(nonfin.sum()) == 0 and wr <= 1.0, (
-        f"{what}: worst element {idx} got {g.reshape(-1)[worst].item():.9g} ref {r.reshape(-1)[worst].item():.9g} "
-        f"({wr:.3g} x tolerance {tol.reshape(-1)[worst].item():.3g}), non-finite {int(nonfin.sum())}, "
-        f"over tolerance {int((ratio > 1.0).sum())} of {ratio.numel()}")
 
 
 def bits(t):
@@ -438,7 +412,7 @@ def test_gelu_every_finite_value(dtype):
 def test_gelu_grad_every_finite_value(dtype):
     """gelu_grad through the GEGLU backward: every finite 16-bit value as the gate, value 1 and dy 1, so that d_gate = gelu'(g) (and
     d_value = y = gelu(g))"""
-    from test_unet_kernels_gpu import glu_paired_index
+    from layernorm_ref import glu_paired_index
     g = finite_patterns(dtype, 16)
     Fd = g.numel()
     idx = glu_paired_index(Fd).to(dev())

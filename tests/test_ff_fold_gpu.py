@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from layernorm_ref import glu_paired_index
+
 pytestmark = pytest.mark.gpu
 
 DT = {torch.float16: 0, torch.bfloat16: 1}
@@ -42,11 +44,6 @@ def close(got, ref, rtol, atol, what, frac=1e-4, ceiling=8.0):
     msg = f"{what}: worst element {worst} got {g.reshape(-1)[worst].item():.6g} ref {r.reshape(-1)[worst].item():.6g}"
     assert ratio.reshape(-1)[worst].item() <= ceiling, msg
     assert (ratio > 1.0).float().mean().item() <= frac, msg
-
-
-def glu_paired_index(Fd):
-    n = torch.arange(2 * Fd)
-    return ((n >> 4) & 1) * Fd + 16 * (n >> 5) + (n & 15)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])

@@ -24,7 +24,8 @@ import test_xattn_epilogue_gpu as XA
 from test_gemm_classes import CLASS_CASES, launch_class
 from test_gemm_plan import (ALIGNED, BIAS, GLU_BWD, GLU_FWD, GN_BWD, GN_STATS, LN_BWD, LNF, RESIDUAL, ROWVEC, SILU, XATTN_DQ, XATTN_FWD,
                             named, plan, shipped_hooks)  # noqa: F401  (shipped_hooks: autouse, the shipped policy)
-from test_unet_kernels_gpu import DT, L, P, close, dev, glu_paired_index, nhwc, poisoned
+from layernorm_ref import glu_paired_index
+from test_unet_kernels_gpu import DT, L, P, close, dev, nhwc, poisoned
 
 pytestmark = pytest.mark.gpu
 

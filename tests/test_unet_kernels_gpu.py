@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from layernorm_ref import glu_paired_index
+
 pytestmark = pytest.mark.gpu
 
 DT = {torch.float16: 0, torch.bfloat16: 1}
@@ -312,13 +314,6 @@ def test_layernorm(dtype, rows, C):
     tol = 4e-3 if dtype == torch.float16 else 2.5e-2
     close(y, ref, tol, tol, "ln fwd")
     close(dx, gref + add.float(), tol, tol * 2, "ln bwd")
-
-
-def glu_paired_index(Fd):
-    """Stored column n' of a GEGLU pre-activation tensor [rows][2F] -> column of the torch layout (value | gate): every 32-column
-    block holds the 16 value columns of outputs 16b .. 16b+15, then their 16 gate columns (csrc/unet_kernels.h glu_src_row)."""
-    n = torch.arange(2 * Fd)
-    return ((n >> 4) & 1) * Fd + 16 * (n >> 5) + (n & 15)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
